@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- RTF of the F5-TTS hot path (CFM.sample -> DiT x NFE -> Vocos) on N MI355X GPUs of one node.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python bench.py --gpus N ...        (N > 1 outside torchrun: starts its own N ranks as a child torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -16,7 +16,12 @@ timed region.  value = generated audio seconds of ALL ranks / wall seconds (the 
 audio_sec / wall_sec, higher is better); rtf_wall_over_audio (the reference's own convention, benchmark.py:457) is
 its inverse.  `value` scales weakly: every rank synthesises its own utterance per step.
 
-Beside it, every line carries
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints the line: `ms_per_step` is the
+wall time of one timed step.  --dump-outputs DIR writes what the last timed step returned (mel, waveform(s), trajectory) as
+DIR/<name>.npy in float32 from the same seeded inputs every run, so that two builds can be compared output for output.
+
+With --full, the line also carries `clocks` (shader clock / power during the timed region), `phases` (host / sample / vocoder
+split of a step), `roofline` and `kernel_classes` (per-launch timing of an extra pass), `cpu_baseline`, and
   precisions  the same C2 step timed at every operand precision (f32 = exact-f32 MFMA; f16x3; f16p; f16; bf16) with
               the generated-mel L-inf of that precision against the f32 engine on the same inputs (the f32 engine itself
               is pinned against the CPU oracle at this size by tests/test_configs_gpu.py): each speed number sits with
@@ -32,6 +37,7 @@ Beside it, every line carries
 from __future__ import annotations
 
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -83,7 +89,16 @@ def parse():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a ONE-GPU box: every rank uses cuda:0 and the collectives run on gloo "
                          "through host copies (RCCL refuses two ranks on one device); never used for reported numbers")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (clocks, phases, roofline, precisions, c3, c4, "
+                         "cpu_baseline; the --no-* options above pick among them); without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (mel, waveform(s), trajectory) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.setup_runs < 0:
+        ap.error("--steps must be >= 1, --warmup and --setup-runs >= 0")
+    return args
 
 
 def dit_flops_per_seq_forward(N, D=1024, depth=22, F=2048, Dt=512, mel=100):
@@ -235,6 +250,25 @@ class ClockWatch:
                 "source": "amdgpu hwmon freq1_input / power1_input, sampled every %d ms during the timed region" % int(self.period * 1e3)}
 
 
+DUMP_BYTES = 63 * 10**6   # --dump-outputs: array data in all (the .npy headers stay within 64 MB beside it)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes each of `arrays` (name -> tensor, in priority order) as <out_dir>/<name>.npy in float32.  An
+    array that no longer fits into what is left of DUMP_BYTES keeps that many of its flattened elements, at indices drawn
+    with a fixed seed: the same arguments write the same selection."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES // 4
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > left:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, left, replace=False))]
+        left -= a.size
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port() -> int:
     import socket
     with socket.socket() as so:
@@ -329,11 +363,13 @@ def main():
         gather_buf = torch.empty(world * B, N, 100, device=dev)
 
     def step(m=None):
-        out, _traj = (m or model).sample(cond, text, dur_t, lens=lens_t, **kw)
+        """One timed step: returns what a caller receives -- the mel, the waveform (one per utterance where their lengths
+        differ) and the ODE trajectory."""
+        out, traj = (m or model).sample(cond, text, dur_t, lens=lens_t, **kw)
         if uniform:
             wav = voc.decode(out[:, ref:, :].permute(0, 2, 1))
         else:  # per item, as the reference's harness does (eval_infer_batch.py:202-206): own prompt / total length
-            wav = [voc.decode(out[i:i + 1, refs[i]:durs[i], :].permute(0, 2, 1)) for i in range(B)][-1]
+            wav = [voc.decode(out[i:i + 1, refs[i]:durs[i], :].permute(0, 2, 1)) for i in range(B)]
         if world > 1:
             if args.rehearse_one_gpu:   # gloo has no device collectives: same call shape on host copies
                 host = torch.empty(gather_buf.shape, dtype=gather_buf.dtype)
@@ -341,7 +377,7 @@ def main():
                 gather_buf.copy_(host)
             else:
                 dist.all_gather_into_tensor(gather_buf, out)
-        return out, wav
+        return out, wav, traj
 
     def barrier():
         if world > 1:
@@ -361,15 +397,23 @@ def main():
         step()
     barrier()
     for _ in range(args.warmup):
-        out, wav = step()
+        step()
     barrier()
-    with ClockWatch(dev.index) as cw:
+    with (ClockWatch(dev.index) if args.full else contextlib.nullcontext()) as cw:
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            out, wav = step()
+            out, wav, traj = step()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
-    assert torch.isfinite(out).all() and torch.isfinite(wav).all()
+    wavs = wav if isinstance(wav, list) else [wav]
+    assert torch.isfinite(out).all() and all(torch.isfinite(w).all() for w in wavs)
+    if args.dump_outputs and rank == 0:
+        arrays = {"mel": out}
+        arrays.update({"wav": wav} if not isinstance(wav, list) else {"wav_%02d" % i: w for i, w in enumerate(wav)})
+        if world > 1:
+            arrays["mel_all_ranks"] = gather_buf
+        arrays["traj"] = traj
+        dump_outputs(args.dump_outputs, arrays)
 
     audio_per_step = gen_frames_total * 256 / 24000
     value = audio_per_step * args.steps * world / elapsed
@@ -394,7 +438,8 @@ def main():
         result["parity_precision"] = "f16x3"   # UNetT has no AdaLN gates: its block products dominate the error
         result["parity_note"] = ("E2-TTS UNetT meets north_star's 1e-3 only with split-f16 products in every block (--precision f16x3: "
                                  "~610-640 ms per step on one MI355X, profiles/r03_o_bench_c5_f16x3.json; f16p 5.0e-3, bf16 3e-2 at Base size)")
-    result["clocks"] = cw.summary()   # rank 0's GPU during the timed region (None where sysfs does not offer it)
+    if args.full:
+        result["clocks"] = cw.summary()   # rank 0's GPU during the timed region (None where sysfs does not offer it)
     if world > 1:
         result["rccl_ranks"] = dist.get_world_size()
         result["collective_backend"] = dist.get_backend()
@@ -403,60 +448,61 @@ def main():
         except Exception as ex:
             result["rccl_version"] = repr(ex)
 
-    # ---- diagnostic split of one step (after the timed region, not part of the metric).  The host side of a step is
-    # measured UNTHROTTLED: the engine's pinned staging ring holds 8 calls, so a host that is more than 8 utterances ahead
-    # of the GPU waits there (back-pressure, an idle wait -- in a long timed region enqueue time per step therefore tends
-    # to the GPU time per step and says nothing about host cost).  Here: 4 steps enqueued from an idle stream.
-    phases = {}
-    torch.cuda.synchronize()
-    rec = {}
-    orig_sample, orig_decode = eng.sample, voc.decode
+    if args.full:
+        # ---- diagnostic split of one step (after the timed region, not part of the metric).  The host side of a step is
+        # measured UNTHROTTLED: the engine's pinned staging ring holds 8 calls, so a host that is more than 8 utterances ahead
+        # of the GPU waits there (back-pressure, an idle wait -- in a long timed region enqueue time per step therefore tends
+        # to the GPU time per step and says nothing about host cost).  Here: 4 steps enqueued from an idle stream.
+        phases = {}
+        torch.cuda.synchronize()
+        rec = {}
+        orig_sample, orig_decode = eng.sample, voc.decode
 
-    def t_sample(*a, **k):
+        def t_sample(*a, **k):
+            a0 = time.perf_counter()
+            r = orig_sample(*a, **k)
+            rec["engine_sample_call"] = rec.get("engine_sample_call", 0.0) + time.perf_counter() - a0
+            return r
+
+        def t_decode(*a, **k):
+            a0 = time.perf_counter()
+            r = orig_decode(*a, **k)
+            rec["vocos_decode_call"] = rec.get("vocos_decode_call", 0.0) + time.perf_counter() - a0
+            return r
+
+        eng.sample, voc.decode = t_sample, t_decode
+        # (C5: the BigVGAN decode of one step is ~2,700 launches; several steps overrun the stream's command queue and the
+        #  host blocks on it -- again back-pressure, not host cost -- so one step is enqueued there)
+        nrep = 1 if args.workload == "c5" else 4
         a0 = time.perf_counter()
-        r = orig_sample(*a, **k)
-        rec["engine_sample_call"] = rec.get("engine_sample_call", 0.0) + time.perf_counter() - a0
-        return r
-
-    def t_decode(*a, **k):
-        a0 = time.perf_counter()
-        r = orig_decode(*a, **k)
-        rec["vocos_decode_call"] = rec.get("vocos_decode_call", 0.0) + time.perf_counter() - a0
-        return r
-
-    eng.sample, voc.decode = t_sample, t_decode
-    # (C5: the BigVGAN decode of one step is ~2,700 launches; several steps overrun the stream's command queue and the
-    #  host blocks on it -- again back-pressure, not host cost -- so one step is enqueued there)
-    nrep = 1 if args.workload == "c5" else 4
-    a0 = time.perf_counter()
-    for _ in range(nrep):
-        step()
-    a1 = time.perf_counter()
-    torch.cuda.synchronize()
-    eng.sample, voc.decode = orig_sample, orig_decode
-    phases["host_enqueue_ms_per_step"] = (a1 - a0) / nrep * 1e3
-    phases["host_ms_per_step_in"] = {k: v / nrep * 1e3 for k, v in rec.items()}   # rest = sample() argument handling + noise draw
-    ps, pv = [], []
-    for _ in range(3):
+        for _ in range(nrep):
+            step()
+        a1 = time.perf_counter()
         torch.cuda.synchronize()
-        a = time.perf_counter()
-        o_, _ = model.sample(cond, text, dur_t, lens=lens_t, **kw)
-        torch.cuda.synchronize()
-        b = time.perf_counter()
-        if uniform:
-            voc.decode(o_[:, ref:, :].permute(0, 2, 1))
-        torch.cuda.synchronize()
-        c = time.perf_counter()
-        ps.append((b - a) * 1e3)
-        pv.append((c - b) * 1e3)
-    phases["sample_ms_min_max"] = [min(ps), max(ps)]
-    phases["vocos_ms_min_max"] = [min(pv), max(pv)]
-    result["phases"] = phases
+        eng.sample, voc.decode = orig_sample, orig_decode
+        phases["host_enqueue_ms_per_step"] = (a1 - a0) / nrep * 1e3
+        phases["host_ms_per_step_in"] = {k: v / nrep * 1e3 for k, v in rec.items()}   # rest = sample() argument handling + noise draw
+        ps, pv = [], []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            a = time.perf_counter()
+            o_, _ = model.sample(cond, text, dur_t, lens=lens_t, **kw)
+            torch.cuda.synchronize()
+            b = time.perf_counter()
+            if uniform:
+                voc.decode(o_[:, ref:, :].permute(0, 2, 1))
+            torch.cuda.synchronize()
+            c = time.perf_counter()
+            ps.append((b - a) * 1e3)
+            pv.append((c - b) * 1e3)
+        phases["sample_ms_min_max"] = [min(ps), max(ps)]
+        phases["vocos_ms_min_max"] = [min(pv), max(pv)]
+        result["phases"] = phases
 
     if rank == 0:
         # ---- roofline of the dominant kernel class (MFMA GEMMs), per-launch HIP events on the launch stream, in a
         # dedicated pass over the same workload right after the timed region
-        if not args.no_profile:
+        if args.full and not args.no_profile:
             eng.profile(True)
             model.sample(cond, text, dur_t, lens=lens_t, **kw)
             torch.cuda.synchronize()
@@ -493,7 +539,7 @@ def main():
                 result["whole_path_tflops"] = total_fl / (ms_per_step * 1e-3) / 1e12
 
     # ---- the same step at every operand precision, each with its own accuracy (rank 0 of a 1-GPU run, C2 only)
-    if world == 1 and args.workload == "c2" and not args.no_precisions:
+    if args.full and world == 1 and args.workload == "c2" and not args.no_precisions:
         ksteps = max(1, min(args.steps, 5))
         _, ref_model = (tr, model) if args.precision == "f32" else build_model("f32")
         ref_out, ref_traj = ref_model.sample(cond, text, dur_t, lens=lens_t, **kw)
@@ -506,7 +552,7 @@ def main():
             torch.cuda.synchronize()
             a = time.perf_counter()
             for _ in range(ksteps):
-                o_, _w = step(m)
+                step(m)
             torch.cuda.synchronize()
             ms = (time.perf_counter() - a) / ksteps * 1e3
             o2, t2 = m.sample(cond, text, dur_t, lens=lens_t, **kw)
@@ -533,7 +579,7 @@ def main():
     # ---- C3 (BASELINE.json configs[2]; the reference's batch workload, benchmark.py:413-424: steps=32, cfg 2, sway -1): B=32
     # variable-length utterances padded to 1024 frames, NFE=32, with the default attn_mask_enabled=False (pad rows computed, the
     # reference's behaviour) and with attn_mask_enabled=True (the engine runs the valid rows only, RowPack)
-    if world == 1 and args.workload == "c2" and not args.no_c3:
+    if args.full and world == 1 and args.workload == "c2" and not args.no_c3:
         cond3_cpu, text3, durs3, refs3 = make_inputs(P, args, rank, workload="c3", B=32)
         cond3 = cond3_cpu.to(dev)
         kw3 = dict(steps=32, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=0)
@@ -568,7 +614,7 @@ def main():
         del cond3
 
     # ---- C4: the 256-utterance job sharded data-parallel over the ranks (strong scaling), one all_gather of the mel
-    if args.workload == "c2" and not args.no_c4:
+    if args.full and args.workload == "c2" and not args.no_c4:
         from f5_tts_amd import dist as D
         conds4, texts4, durs4 = make_c4_job(P, args.c4_utts)
         conds4 = [c.to(dev) for c in conds4]          # prompts resident in HBM; text ids stay on the host (see above)
@@ -631,7 +677,7 @@ def main():
                                             "single all_gather (~19 MB per rank) and host contention between rank processes"})
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.workload == "c2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "c2":
             try:
                 result["cpu_baseline"] = cpu_baseline(P, args, tr.state_dict(), voc.state_dict(), cond_cpu, text_cpu)
             except Exception as ex:  # the baseline is a report, never a reason to lose the bench line

@@ -168,6 +168,87 @@ def bucketing_case(name="bucketing"):
     print("wrote", name, [len(c["batches"]) for c in cases])
 
 
+def reference_pins_cases():
+    """The reference's own outputs for tests/test_oracle_vs_reference.py: one packed CFG forward of F5-TTS Base at N=192
+    (vocab_size + 1 embeddings, as load_model passes them, utils_infer.py:313-317) and a tiny attn_mask_enabled sample()
+    of two ragged utterances.  Inputs are drawn exactly as the test draws them and stored beside the outputs."""
+    name = "ref_base_cfg_forward"
+    if not ONLY or name in ONLY:
+        arch = dict(P.config.F5TTS_BASE)
+        nv = P.config.VOCAB_SIZE + 1
+        sd = P.weights.synthetic_state_dict(P.weights.dit_param_shapes(arch, nv))
+        ref = rh.build_reference_cfm(dict(arch), nv)
+        ref.transformer.load_state_dict(sd, strict=True)
+        g = torch.Generator().manual_seed(5)
+        x = torch.randn(1, 192, 100, generator=g)
+        cond = torch.randn(1, 192, 100, generator=g)
+        cond[:, 60:] = 0
+        text = torch.randint(0, nv - 1, (1, 40), generator=g)
+        t = torch.tensor(0.25)
+        with torch.no_grad():
+            r = ref.transformer(x=x, cond=cond, text=text, time=t, cfg_infer=True, cache=False)
+        save(name, dict(arch=arch, backbone="DiT", nvocab=nv, wseed=0, weights_checksum=weights_checksum(sd)),
+             x=x, cond=cond, text=text, time=t, out=r)
+    name = "ref_tiny_sample_attnmask"
+    if not ONLY or name in ONLY:
+        arch = dict(P.config.F5TTS_TINY, attn_mask_enabled=True)
+        nv = 33
+        sd = P.weights.synthetic_state_dict(P.weights.dit_param_shapes(arch, nv), seed=4)
+        ref = rh.build_reference_cfm(dict(arch), nv)
+        ref.transformer.load_state_dict(sd, strict=True)
+        g = torch.Generator().manual_seed(9)
+        cond = torch.randn(2, 28, 100, generator=g)
+        text = torch.randint(0, nv, (2, 15), generator=g)
+        text[1, 9:] = -1
+        kw = dict(lens=torch.tensor([28, 19]), steps=10, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=11)
+        r_out, r_traj = ref.sample(cond, text, torch.tensor([60, 47]), **kw)
+        save(name, dict(arch=arch, backbone="DiT", nvocab=nv, wseed=4, weights_checksum=weights_checksum(sd),
+                        duration=[60, 47], lens=[28, 19], steps=10, cfg_strength=2.0, sway=-1.0, seed=11),
+             cond=cond, text=text, out=r_out, traj=r_traj)
+
+
+def infer_harness_case(name="ref_infer_harness"):
+    """The reference's inference harness (infer/utils_infer.py) run on the inputs of tests/test_infer_harness.py, with that
+    test's deterministic fake model and vocoder: chunk_text, _convert_peft_state_dict_to_plain and infer_batch_process
+    (batch and streaming).  What the fake model received is recorded per call, the waveforms and spectrograms in full."""
+    if ONLY and name not in ONLY:
+        return
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("_infer_harness_test", os.path.join(ROOT, "tests", "test_infer_harness.py"))
+    T = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(T)
+    ui = rh.load_infer()
+    meta = dict(note="infer/utils_infer.py run on the inputs and fakes of tests/test_infer_harness.py")
+    arrays = {}
+    meta["chunk_text"] = [dict(text=t, max_chars=mc, chunks=ui.chunk_text(t, mc)) for t in T.CHUNK_TEXTS for mc in T.CHUNK_SIZES]
+    merged = ui._convert_peft_state_dict_to_plain(T.peft_state_dict())
+    meta["peft_keys"] = sorted(merged)
+    for i, k in enumerate(meta["peft_keys"]):
+        arrays[f"peft_{i}"] = merged[k]
+    audio = T.prompt_audio()
+    meta["batch"] = []
+    for j, kw in enumerate(T.batch_kwargs()):
+        m = T.FakeModel()
+        m._tokenizer_type = "custom"
+        wave, sr, spec_ = next(ui.infer_batch_process((audio, 24000), T.REF_TEXT, T.TEXTS, m, T.FakeVocoder(), progress=None,
+                                                      device="cpu", **kw))
+        rec = dict(sr=sr, calls=[dict(nw=c["nw"], rms=c["rms"], duration=c["duration"], steps=c["steps"], cfg=c["cfg"],
+                                      sway=c["sway"], text="".join(c["text"][0])) for c in m.calls], stream={})
+        arrays[f"wave_{j}"], arrays[f"spec_{j}"] = wave, spec_
+        for cs in T.STREAM_CHUNKS:
+            m = T.FakeModel()
+            m._tokenizer_type = "custom"
+            ch = list(ui.infer_batch_process((audio, 24000), T.REF_TEXT, T.TEXTS, m, T.FakeVocoder(), progress=None,
+                                             device="cpu", streaming=True, chunk_size=cs, **kw))
+            rec["stream"][str(cs)] = dict(sr=[s for _, s in ch], lengths=[len(w) for w, _ in ch])
+            arrays[f"stream_{j}_{cs}"] = np.concatenate([w for w, _ in ch])
+        meta["batch"].append(rec)
+    meta["empty"] = list(next(ui.infer_batch_process((audio, 24000), T.REF_TEXT, [], T.FakeModel(), T.FakeVocoder(),
+                                                     progress=None, device="cpu")))
+    save(name, meta, **arrays)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = rh.load()
@@ -210,6 +291,8 @@ def main():
     e2_tiny = dict(dim=256, depth=4, heads=4, dim_head=64, ff_mult=2, text_mask_padding=False, pe_attn_head=1,
                    text_dim=None, conv_layers=0, attn_mask_enabled=False, qk_norm=None)
     bucketing_case()
+    reference_pins_cases()
+    infer_harness_case()
     sample_case("sample_unett_b2", e2_tiny, B=2, cond_len=20, nt=12, duration=[44, 31], lens=[20, 12], steps=5,
                 text_pad=[12, 8], backbone="UNetT")
 

@@ -180,13 +180,38 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=4" in (r.stderr + r.stdout)
 
 
-def test_clock_watch_is_inert_without_gpu_sysfs():
-    """bench.py's ClockWatch must never fail a run: with no GPU (here) or no hwmon files it samples nothing and reports None."""
+def test_clock_watch_is_inert_without_gpu_sysfs(monkeypatch):
+    """bench.py's ClockWatch must never fail a run: with no GPU or no hwmon files it samples nothing and reports None.  The
+    hwmon files are hidden here, so that a host with a GPU takes the same path."""
     import importlib
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench.glob, "glob", lambda pattern: [])
     cw = bench.ClockWatch(0)
     with cw:
         pass
     assert cw.summary() is None
+
+
+def test_bench_dump_outputs_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per array, in full while they fit the byte budget; the array that does not fit
+    keeps a seeded sample of its elements -- the same one on every run -- and the files never hold more than the budget."""
+    import importlib
+    import sys
+
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 1000)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"mel": torch.randn(2, 10, 30, generator=g), "wav": torch.randn(100, generator=g, dtype=torch.float64),
+              "traj": torch.randn(5, 2, 10, 30, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["mel.npy", "traj.npy", "wav.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["mel"], arrays["mel"].numpy()) and np.array_equal(got["wav"], arrays["wav"].float().numpy())
+    assert got["traj"].shape == (1000 - 600 - 100,) and np.isin(got["traj"], arrays["traj"].numpy()).all()
+    assert np.array_equal(got["traj"], np.load(tmp_path / "b" / "traj.npy"))
