@@ -217,6 +217,55 @@ int f5k_convpos(int32_t prec, const float* x, const float* w, const float* bias,
 /* LayerNorm(no affine, eps) * (1 + scale[b]) + shift[b]; x f32[R, D], scale/shift f32[R / rows_per_batch, D] */
 int f5k_layernorm_mod(const float* x, const float* scale, const float* shift, float* out, int32_t R, int32_t D,
                       int32_t rows_per_batch, float eps, f5_stream stream);
+/* LayerNorm modulate as f5k_layernorm_mod, through the instantiation the engine uses for an operand precision: out is f32
+ * (F5_PREC_F32 / F5_PREC_F16X3; planar 1: stored pre-split, 2: plain rows split afterwards by split_planar_kernel; D % 32 == 0)
+ * or bf16 / f16 [R, D], caller-owned; out_f32
+ * (or NULL) receives an f32 copy of a 16-bit out.  m_limit >= 0: device-side row count (rows >= m_limit are not written). */
+int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* scale, const float* shift, void* out, float* out_f32,
+                         int32_t R, int32_t D, int32_t rows_per_batch, float eps, int32_t m_limit, int32_t planar,
+                         f5_stream stream);
+
+/* One backbone GEMM C = A W^T (A f32 [M, K], W f32 [N, K], bias f32 [N], all cast to the operand type of `prec`) through a
+ * production epilogue of csrc/gemm.h, built as the engine builds it.  Outputs go to caller-owned device buffers. */
+#define F5K_EPI_STORE 0    /* EpiStore: out0 = act(C + bias) [M, N], f32 or (out16) the 16-bit operand type             */
+#define F5K_EPI_GATE_RES 1 /* EpiGateRes: out0 = x f32 [M, N] = res + gate[b] * (C + bias); rows past lens[b] keep res     */
+#define F5K_EPI_QKV 2      /* EpiQKV: out0 = q, out1 = k [Bp, H, Nseq, 64], out2 = v^T [Bp, H, 64, Npad]                   */
+#define F5K_EPI_QKNORM 3   /* EpiQKV without rotary / scale, then qknorm_rope_kernel in place (qk_norm = "rms_norm")     */
+typedef struct f5k_epi {
+    int32_t kind;        /* F5K_EPI_* */
+    int32_t cfg;         /* -1: launch_gemm's own dispatch (remainder split included); else a forced GemmCfg 2, 8, 9, 10, 13, 20 */
+    int32_t a_presplit;  /* F5_PREC_F16X3: A is handed over pre-split (what the store4_planar producers write) */
+    int32_t m_limit;     /* >= 0: device-side row count <= M; -1: none (QKV with row_start sets it itself) */
+    int32_t out16;       /* STORE: output in the 16-bit operand type; QKV on f32 / f16x3 operands: q / k / v^T as f16 */
+    int32_t act;         /* STORE: F5_ACT_* (engine: none, GELU-tanh) */
+    int32_t planar;      /* STORE, f32 output under F5_PREC_F16X3: 1 stored pre-split by the epilogue, 2 plain store split afterwards
+                            by split_planar_kernel (N % 32 == 0) */
+    int32_t gate_stride; /* GATE_RES: floats between the gate vectors of consecutive batch rows (0: one vector) */
+    int32_t rows_per_batch;
+    int32_t nlens;       /* GATE_RES: entries of lens_host (>= the batch rows M spans) */
+    const float* res;    /* GATE_RES: residual [M, N] (may be out0) */
+    const float* gate;   /* GATE_RES: gate vectors or NULL (1) */
+    const int32_t* lens_host;
+    int32_t H, Nseq, Npad, pe_heads;   /* QKV / QKNORM: N == 3 * H * 64; Npad % 8 == 0, Npad >= Nseq */
+    float q_scale;
+    int32_t maxpos;      /* rows of rope_cos / rope_sin [maxpos, 32] (>= Nseq) */
+    const float* rope_cos;
+    const float* rope_sin;
+    const int32_t* row_start_host; /* QKV: packed rows (RowPack) [Bp + 1], multiples of 4, or NULL (M == Bp * Nseq) */
+    int32_t Bp;
+    int32_t pad0;
+    const float* gq;     /* QKNORM: RMSNorm gains [64] of q and k */
+    const float* gk;
+    void* out0;
+    void* out1;
+    void* out2;
+    float* out0_f32;     /* f32 copies of 16-bit outputs (NULL: none) over n0 / n1 / n2 elements */
+    float* out1_f32;
+    float* out2_f32;
+    int64_t n0, n1, n2;
+} f5k_epi;
+int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const float* bias, int32_t M, int32_t N, int32_t K,
+                 const f5k_epi* p, f5_stream stream);
 /* repeated-launch timing of one GEMM shape (for bench/roofline): returns average microseconds per launch */
 int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tile_m, int32_t tile_n, int32_t iters,
                   float* avg_us, f5_stream stream);

@@ -45,6 +45,19 @@ _p = C.c_void_p
 _i = C.c_int32
 _f = C.c_float
 
+F5K_EPI_STORE, F5K_EPI_GATE_RES, F5K_EPI_QKV, F5K_EPI_QKNORM = 0, 1, 2, 3
+
+
+class f5k_epi(C.Structure):
+    """Epilogue parameters of f5k_gemm_epi (include/f5_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "cfg", "a_presplit", "m_limit", "out16", "act", "planar", "gate_stride",
+                                         "rows_per_batch", "nlens")] + \
+        [("res", _p), ("gate", _p), ("lens_host", C.POINTER(C.c_int32))] + \
+        [(n, C.c_int32) for n in ("H", "Nseq", "Npad", "pe_heads")] + [("q_scale", C.c_float), ("maxpos", C.c_int32)] + \
+        [("rope_cos", _p), ("rope_sin", _p), ("row_start_host", C.POINTER(C.c_int32)), ("Bp", C.c_int32), ("pad0", C.c_int32),
+         ("gq", _p), ("gk", _p), ("out0", _p), ("out1", _p), ("out2", _p), ("out0_f32", _p), ("out1_f32", _p), ("out2_f32", _p),
+         ("n0", C.c_int64), ("n1", C.c_int64), ("n2", C.c_int64)]
+
 # name -> (restype, argtypes); mirrors include/f5_hip.h exactly (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "f5_last_error": (C.c_char_p, []),
@@ -77,6 +90,8 @@ SIGNATURES = {
     "f5k_attention": (_i, [_i, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),
     "f5k_convpos": (_i, [_i, _p, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),
     "f5k_layernorm_mod": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
+    "f5k_layernorm_mod_ex": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _p]),
+    "f5k_gemm_epi": (_i, [_i, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_epi), _p]),
     "f5k_gemm_time": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
     "f5_profile_enable": (_i, [_p, _i]),
     "f5_profile_read": (_i, [_p, C.POINTER(_f), C.POINTER(_i), C.POINTER(C.c_double), _i]),

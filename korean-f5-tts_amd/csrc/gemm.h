@@ -391,8 +391,8 @@ template <typename TO> struct EpiQKV {
     __device__ __forceinline__ TRowCtx trow(int m, int M) const {
         int b = m / Nseq, pos = m - b * Nseq;
         if (rowmap) {   // rows m .. m+3 belong to one utterance (its rows start at a multiple of 4): V^T columns pos .. pos+3 < Npad
-            const int2 bp = rowmap[m];
-            return {(size_t)bp.x * H * 64 * Npad + bp.y, bp.y, bp.x, m + 3 < M, m, M};
+            const int2 bp = rowmap[m];   // (alignment rows at positions >= Nseq are dropped, as row() drops them for q / k)
+            return {(size_t)bp.x * H * 64 * Npad + bp.y, bp.y, bp.x, m + 3 < M && bp.y + 3 < Nseq, m, M};
         }
         return {(size_t)b * H * 64 * Npad + pos, pos, b, (pos & 3) == 0 && pos + 3 < Nseq, m, M};
     }
@@ -410,7 +410,7 @@ template <typename TO> struct EpiQKV {
                 if (mm < r.M) {
                     int bb = mm / Nseq, pp = mm - bb * Nseq;
                     if (rowmap) { const int2 bp = rowmap[mm]; bb = bp.x; pp = bp.y; }
-                    vt[(size_t)bb * H * 64 * Npad + c.hoff + pp] = from_f32<TO>(v[rr] + c.b);
+                    if (pp < Nseq) vt[(size_t)bb * H * 64 * Npad + c.hoff + pp] = from_f32<TO>(v[rr] + c.b);
                 }
             }
         }

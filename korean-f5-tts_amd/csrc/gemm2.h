@@ -227,8 +227,10 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
     constexpr int PRE_WORDS = sizeof(typename Epi::Pre) >= 4 ? (int)sizeof(typename Epi::Pre) / 4 : 0;
     // (measured, normalised by the attention kernel of the same run: early setup helps the residual GEMMs ~2 %, is
     // neutral for FF1 and costs the 128x192 QKV tile ~3 % -- 230 VGPRs live across the loop -- so big transposing tiles
-    // set up late)
-    constexpr bool EARLY = MI * NJ * (1 + PRE_WORDS) <= 64 && !(Epi::kTransposes && MI * NJ >= 12);
+    // set up late).  The transposing epilogue (EpiQKV) always sets up late: with its rotary table requested before the loop, the
+    // 64x64 tile returned wrong q / k values on the rotary heads in a few lanes of occasional launches (tests/test_epilogues_gpu.py
+    // test_remainder_split_matches_one_64x64_launch: 7 of 16 launches at 16,400 rows; none of 32 with the late setup).
+    constexpr bool EARLY = MI * NJ * (1 + PRE_WORDS) <= 64 && !Epi::kTransposes;
     const int mw = m0 + wr * TM, nw = n0 + wc * TN;
     bool any_row = false, any_tr = false;
 #pragma unroll

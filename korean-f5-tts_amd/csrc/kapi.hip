@@ -206,3 +206,216 @@ extern "C" int f5k_layernorm_mod(const float* x, const float* scale, const float
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
 }
+
+template <typename TO>
+static int layernorm_ex_impl(const float* x, const float* scale, const float* shift, void* out, float* out_f32, int R, int D,
+                             int rows_per_batch, float eps, int m_limit, int planar, hipStream_t s) {
+    Scratch<int> ml;
+    if (m_limit >= 0) {
+        HIPCHK(ml.alloc(1));
+        HIPCHK(hipMemcpy(ml.p, &m_limit, 4, hipMemcpyHostToDevice));
+    }
+    TO* o = static_cast<TO*>(out);
+    hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((R + 3) / 4), dim3(256), 0, s, x, D, o, D, R, D, eps, scale, shift, D, rows_per_batch,
+                       1, Prefetch{}, m_limit >= 0 ? ml.p : nullptr, planar == 1);
+    KCHK();
+    if constexpr (std::is_same_v<TO, float>) {   // planar 2: the plain rows, then split_planar_kernel (what planar 1 must equal)
+        if (planar == 2) {
+            hipLaunchKernelGGL(split_planar_kernel, dim3(ew_blocks((long)R * D / 32)), dim3(256), 0, s, o, (long)R * D / 32);
+            KCHK();
+        }
+    }
+    if (!std::is_same_v<TO, float> && out_f32) {
+        hipLaunchKernelGGL((to_f32_kernel<TO>), dim3(ew_blocks((long)R * D)), dim3(256), 0, s, o, out_f32, (long)R * D);
+        KCHK();
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return F5_OK;
+}
+
+extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* scale, const float* shift, void* out, float* out_f32,
+                                    int32_t R, int32_t D, int32_t rows_per_batch, float eps, int32_t m_limit, int32_t planar,
+                                    f5_stream stream) {
+    if (!x || !out || R <= 0 || D <= 0 || D % 4 || D > 2048 || rows_per_batch <= 0 || m_limit < -1)
+        return fail(F5_EINVAL, "f5k_layernorm_mod_ex: bad arguments");
+    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
+        return fail(F5_EINVAL, "f5k_layernorm_mod_ex: precision must be f32, f16x3, bf16 or f16");
+    if (planar < 0 || planar > 2 || (planar && (prec == F5_PREC_BF16 || prec == F5_PREC_F16 || D % 32)) || (planar == 2 && m_limit >= 0))
+        return fail(F5_EINVAL, "f5k_layernorm_mod_ex: planar needs an f32 output and D %% 32 == 0 (planar 2: every row)");
+    return F5K_BY_PREC(prec, layernorm_ex_impl, x, scale, shift, out, out_f32, R, D, rows_per_batch, eps, m_limit, planar,
+                       (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------- f5k_gemm_epi
+// One GEMM through a production epilogue: EpiStore / EpiGateRes / EpiQKV constructed field for field as engine_impl.h does, the
+// rotary table through rope_frag_kernel, packed rows through fill_rowmap_kernel, qk_norm through qknorm_rope_kernel.
+template <typename T, typename Epi>
+static int epi_gemm(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const Epi& epi, int cfg, const int* ml,
+                    int split) {
+    const bool v3_ok = ((sizeof(T) == 2 && !split) || split == 2) && gemm3_epilogue_ok(epi);
+    if (cfg == G3_256x256_PP && !v3_ok)
+        return fail(F5_EINVAL, "f5k_gemm_epi: the ping-pong kernel (cfg 20) takes 16-bit or pre-split operands and a QKV split at 256 columns");
+    HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, cfg, ml, 0, GemmConv{}, split));
+    return F5_OK;
+}
+
+template <typename TO> static int copy_f32(hipStream_t s, const void* src, float* dst, int64_t n) {
+    if constexpr (!std::is_same_v<TO, float>) {
+        if (dst && n > 0) {
+            hipLaunchKernelGGL((to_f32_kernel<TO>), dim3(ew_blocks((long)n)), dim3(256), 0, s, static_cast<const TO*>(src), dst, (long)n);
+            KCHK();
+        }
+    }
+    return F5_OK;
+}
+
+template <typename T, typename TO>
+static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const float* bias, const f5k_epi& p, const int* ml,
+                   int split) {
+    Scratch<float> frag;
+    HIPCHK(frag.alloc((size_t)p.maxpos * 64));
+    hipLaunchKernelGGL(rope_frag_kernel, dim3(ew_blocks((long)p.maxpos * 16)), dim3(256), 0, s, p.rope_cos, p.rope_sin, frag.p, (long)p.maxpos);
+    KCHK();
+    Scratch<int> rs;
+    Scratch<int2> rowmap;
+    if (p.row_start_host) {
+        HIPCHK(rs.alloc((size_t)p.Bp + 1));
+        HIPCHK(hipMemcpy(rs.p, p.row_start_host, ((size_t)p.Bp + 1) * 4, hipMemcpyHostToDevice));
+        HIPCHK(rowmap.alloc((size_t)M));
+        HIPCHK(hipMemsetAsync(rowmap.p, 0, (size_t)M * sizeof(int2), s));
+        hipLaunchKernelGGL(fill_rowmap_kernel, dim3(p.Bp), dim3(256), 0, s, rs.p, rowmap.p);
+        KCHK();
+        ml = rs.p + p.Bp;   // m_limit = row_start[Bp] (sample_body: RowPack::rows_dev)
+    }
+    const bool norm = p.kind == F5K_EPI_QKNORM;
+    TO* q = static_cast<TO*>(p.out0);
+    TO* k = static_cast<TO*>(p.out1);
+    CHK(epi_gemm<T>(s, a, w, ld, M, N, K,
+                    EpiQKV<TO>{q, k, static_cast<TO*>(p.out2), bias, frag.p, p.Nseq, p.Npad, p.H, norm ? 0 : p.pe_heads,
+                               norm ? 1.0f : p.q_scale, rowmap.p},
+                    p.cfg, ml, split));
+    if (norm) {
+        const long qrows = (long)p.Bp * p.H * p.Nseq;
+        hipLaunchKernelGGL((qknorm_rope_kernel<TO>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, q, k, p.gq, p.gk,
+                           p.rope_cos, p.rope_sin, qrows, p.Nseq, p.H, p.pe_heads, p.q_scale, 1e-6f);
+        KCHK();
+    }
+    CHK(copy_f32<TO>(s, p.out0, p.out0_f32, p.n0));
+    CHK(copy_f32<TO>(s, p.out1, p.out1_f32, p.n1));
+    CHK(copy_f32<TO>(s, p.out2, p.out2_f32, p.n2));
+    HIPCHK(hipStreamSynchronize(s));   // (the rotary table and the row map are freed on return)
+    return F5_OK;
+}
+
+template <typename T>
+static int gemm_epi_impl(const float* A, const float* W, const float* bias, int M, int N, int K, const f5k_epi& p, hipStream_t s) {
+    const int Kp = round_up(K, GEMM_ROW_BYTES / (int)sizeof(T));
+    Scratch<T> a, w;
+    HIPCHK(a.alloc((size_t)M * Kp));
+    HIPCHK(w.alloc((size_t)N * Kp));
+    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)M * Kp)), dim3(256), 0, s, A, K, M, K, a.p, Kp, M);
+    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)N * Kp)), dim3(256), 0, s, W, K, N, K, w.p, Kp, N);
+    KCHK();
+    int split = 0;
+    if constexpr (std::is_same_v<T, float>) {
+        if (g_split16) {
+            HIPCHK(maybe_split<T>(s, w.p, (size_t)N * Kp));
+            if (p.a_presplit) HIPCHK(maybe_split<T>(s, a.p, (size_t)M * Kp));
+            split = p.a_presplit ? 2 : 1;
+        }
+    }
+    Scratch<int> ml;
+    if (p.m_limit >= 0) {
+        HIPCHK(ml.alloc(1));
+        HIPCHK(hipMemcpy(ml.p, &p.m_limit, 4, hipMemcpyHostToDevice));
+    }
+    Scratch<int> lens;
+    switch (p.kind) {
+        case F5K_EPI_STORE:
+            if (p.out16) {
+                if constexpr (sizeof(T) == 2) {
+                    CHK(epi_gemm<T>(s, a.p, w.p, Kp, M, N, Kp, EpiStore<T>{static_cast<T*>(p.out0), N, bias, p.act}, p.cfg, ml.p, split));
+                    CHK(copy_f32<T>(s, p.out0, p.out0_f32, p.n0));
+                }
+            } else {   // planar 2: the plain store, then split_planar_kernel over the whole output (what planar 1 must equal)
+                CHK(epi_gemm<T>(s, a.p, w.p, Kp, M, N, Kp, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, p.planar == 1}, p.cfg,
+                                ml.p, split));
+                if (p.planar == 2) {
+                    hipLaunchKernelGGL(split_planar_kernel, dim3(ew_blocks((long)M * N / 32)), dim3(256), 0, s, static_cast<float*>(p.out0),
+                                       (long)M * N / 32);
+                    KCHK();
+                }
+            }
+            break;
+        case F5K_EPI_GATE_RES:
+            if (p.lens_host) {
+                HIPCHK(lens.alloc((size_t)p.nlens));
+                HIPCHK(hipMemcpy(lens.p, p.lens_host, (size_t)p.nlens * 4, hipMemcpyHostToDevice));
+            }
+            CHK(epi_gemm<T>(s, a.p, w.p, Kp, M, N, Kp,
+                            EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p}, p.cfg,
+                            ml.p, split));
+            break;
+        default:   // QKV / QKNORM: the output type is the operand type, or f16 on f32 operands (the f16x3 attn16 path)
+            if (p.out16) {
+                if constexpr (std::is_same_v<T, float>) CHK((epi_qkv<T, f16_t>(s, a.p, w.p, Kp, M, N, Kp, bias, p, ml.p, split)));
+            } else {
+                CHK((epi_qkv<T, T>(s, a.p, w.p, Kp, M, N, Kp, bias, p, ml.p, split)));
+            }
+            break;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return F5_OK;
+}
+
+extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const float* bias, int32_t M, int32_t N, int32_t K,
+                            const f5k_epi* p, f5_stream stream) {
+    if (!A || !W || !p || !p->out0 || M <= 0 || N <= 0 || K <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm_epi: bad arguments (N %% 4 == 0)");
+    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
+        return fail(F5_EINVAL, "f5k_gemm_epi: precision must be f32, f16x3, bf16 or f16");
+    const int c = p->cfg;
+    if (c != -1 && c != G2_128x128_8W && c != G2_64x64_4W && c != G2_128x64_8W && c != G2_128x192_8W && c != G2_256x128_8W && c != G3_256x256_PP)
+        return fail(F5_EINVAL, "f5k_gemm_epi: cfg must be -1, 2, 8, 9, 10, 13 or 20");
+    if (p->m_limit < -1 || p->m_limit > M) return fail(F5_EINVAL, "f5k_gemm_epi: m_limit must be -1 or 0..M");
+    if (p->a_presplit && prec != F5_PREC_F16X3) return fail(F5_EINVAL, "f5k_gemm_epi: a_presplit needs F5_PREC_F16X3");
+    const bool op16 = prec == F5_PREC_BF16 || prec == F5_PREC_F16;
+    switch (p->kind) {
+        case F5K_EPI_STORE:
+            if (p->out16 && !op16) return fail(F5_EINVAL, "f5k_gemm_epi: a 16-bit STORE needs a 16-bit operand precision");
+            if (p->planar < 0 || p->planar > 2 || (p->planar && (p->out16 || prec != F5_PREC_F16X3 || N % 32)) || (p->planar == 2 && p->m_limit >= 0))
+                return fail(F5_EINVAL, "f5k_gemm_epi: planar needs an f32 output under f16x3 and N %% 32 == 0 (planar 2: every row)");
+            if (p->act != F5_ACT_NONE && p->act != F5_ACT_GELU_TANH) return fail(F5_EINVAL, "f5k_gemm_epi: act must be none or GELU-tanh");
+            break;
+        case F5K_EPI_GATE_RES:
+            if (p->out16 || p->rows_per_batch <= 0 || !p->res) return fail(F5_EINVAL, "f5k_gemm_epi: GATE_RES needs res and rows_per_batch > 0");
+            if (p->lens_host && p->nlens < (M - 1) / p->rows_per_batch + 1) return fail(F5_EINVAL, "f5k_gemm_epi: lens shorter than the batch rows");
+            break;
+        case F5K_EPI_QKV:
+        case F5K_EPI_QKNORM: {
+            const bool norm = p->kind == F5K_EPI_QKNORM;
+            if (!p->out1 || !p->out2 || !bias || !p->rope_cos || !p->rope_sin || p->H <= 0 || N != 3 * p->H * 64 || p->Nseq <= 0 ||
+                p->Npad < p->Nseq || p->Npad % 8 || p->pe_heads < 0 || p->pe_heads > p->H || p->maxpos < p->Nseq || p->Bp <= 0)
+                return fail(F5_EINVAL, "f5k_gemm_epi: bad QKV arguments");
+            if (p->out16 && op16) return fail(F5_EINVAL, "f5k_gemm_epi: out16 QKV is the f16 output of f32 / f16x3 operands");
+            if (norm && (p->out16 || !p->gq || !p->gk || p->row_start_host)) return fail(F5_EINVAL, "f5k_gemm_epi: bad QKNORM arguments");
+            if (p->row_start_host) {
+                if (p->m_limit != -1 || p->row_start_host[0] != 0 || p->row_start_host[p->Bp] > M)
+                    return fail(F5_EINVAL, "f5k_gemm_epi: row_start must start at 0, end <= M and replaces m_limit");
+                for (int b = 0; b < p->Bp; ++b) {
+                    const int cnt = p->row_start_host[b + 1] - p->row_start_host[b];
+                    if (p->row_start_host[b] % 4 || cnt < 0 || cnt > round_up(p->Nseq, 4))
+                        return fail(F5_EINVAL, "f5k_gemm_epi: row_start entries must be multiples of 4, at most round_up(Nseq, 4) apart");
+                }
+            } else if (M != p->Bp * p->Nseq) {
+                return fail(F5_EINVAL, "f5k_gemm_epi: M must be Bp * Nseq without row_start");
+            }
+            break;
+        }
+        default: return fail(F5_EINVAL, "f5k_gemm_epi: unknown epilogue kind");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    g_split16 = prec == F5_PREC_F16X3;
+    const int rc = F5K_BY_PREC(prec, gemm_epi_impl, A, W, bias, M, N, K, *p, s);
+    g_split16 = false;
+    return rc;
+}

@@ -53,3 +53,88 @@ def k_layernorm_mod(x, scale, shift, rows_per_batch, eps=1e-6):
     out = torch.empty_like(x)
     _lib.check(lib.f5k_layernorm_mod(_p(x), _p(scale), _p(shift), _p(out), R, D, rows_per_batch, eps, _s()), "f5k_layernorm_mod")
     return out
+
+
+# ---- guarded output buffers and the production-epilogue entry points (tests/test_epilogues_gpu.py)
+SENT32 = 0x7FA5A5A5   # a NaN in f32
+SENT16 = 0x7FA5       # a NaN in both f16 and bf16
+GUARD = 64            # elements of sentinel before and after every buffer (keeps 128-byte alignment)
+
+
+class Guarded:
+    """A device buffer of `shape` x `dtype` between two guard bands, all filled with a NaN sentinel before the launch."""
+
+    def __init__(self, shape, dtype):
+        self.shape, self.dtype = tuple(shape), dtype
+        self.n = 1
+        for s in self.shape:
+            self.n *= s
+        wide = dtype == torch.float32
+        self.sent = SENT32 if wide else SENT16
+        self.raw = torch.full((2 * GUARD + self.n,), self.sent, dtype=torch.int32 if wide else torch.int16, device=DEV)
+
+    @classmethod
+    def like(cls, t):
+        """A guarded copy of f32 tensor t (e.g. a residual that the epilogue updates in place)."""
+        g = cls(t.shape, torch.float32)
+        g.value.copy_(t)
+        return g
+
+    @property
+    def bits(self):
+        return self.raw[GUARD:GUARD + self.n].view(self.shape)
+
+    @property
+    def value(self):
+        return self.raw[GUARD:GUARD + self.n].view(self.dtype).view(self.shape)
+
+    def ptr(self):
+        return self.raw.data_ptr() + GUARD * self.raw.element_size()
+
+    def guards_intact(self):
+        return bool((self.raw[:GUARD] == self.sent).all() and (self.raw[GUARD + self.n:] == self.sent).all())
+
+
+def k_layernorm_mod_ex(prec, x, scale, shift, out, rows_per_batch, m_limit=-1, planar=0, eps=1e-6):
+    """out: a Guarded of [R, D] (f32 for f32 / f16x3, else the 16-bit type); returns its values as f32."""
+    lib = _lib.load()
+    R, D = x.shape
+    cpy = None if out.dtype == torch.float32 else torch.empty(R, D, device=DEV)
+    _lib.check(lib.f5k_layernorm_mod_ex(prec_id(prec), _p(x), _p(scale), _p(shift), C.c_void_p(out.ptr()), _p(cpy), R, D,
+                                        rows_per_batch, eps, m_limit, planar, _s()), "f5k_layernorm_mod_ex")
+    return out.value if cpy is None else cpy
+
+
+def k_gemm_epi(prec, A, W, bias, kind, outs, *, cfg=-1, a_presplit=False, m_limit=-1, out16=False, act=0, planar=0, res=None,
+               gate=None, gate_stride=0, rows_per_batch=1, lens=None, H=0, Nseq=0, Npad=0, pe_heads=0, q_scale=1.0, rope_cos=None,
+               rope_sin=None, row_start=None, Bp=0, gq=None, gk=None):
+    """One GEMM through a production epilogue (f5k_gemm_epi).  outs: Guarded buffers (STORE / GATE_RES: [out]; QKV: [q, k, vt]).
+    Returns their values as f32 (16-bit outputs through the library's to_f32_kernel)."""
+    lib = _lib.load()
+    M, K = A.shape
+    N = W.shape[0]
+    p = _lib.f5k_epi()
+    p.kind, p.cfg, p.a_presplit, p.m_limit, p.out16, p.act, p.planar = kind, cfg, int(a_presplit), m_limit, int(out16), act, planar
+    p.gate_stride, p.rows_per_batch = gate_stride, rows_per_batch
+    p.res = 0 if res is None else (res.ptr() if isinstance(res, Guarded) else res.data_ptr())
+    p.gate = 0 if gate is None else gate.data_ptr()
+    la = _lib.int_array(lens)
+    if la is not None:
+        p.lens_host, p.nlens = la, len(lens)
+    p.H, p.Nseq, p.Npad, p.pe_heads, p.q_scale = H, Nseq, Npad, pe_heads, q_scale
+    if rope_cos is not None:
+        p.rope_cos, p.rope_sin, p.maxpos = rope_cos.data_ptr(), rope_sin.data_ptr(), rope_cos.shape[0]
+    rs = _lib.int_array(row_start)
+    if rs is not None:
+        p.row_start_host = rs
+    p.Bp = Bp
+    p.gq = 0 if gq is None else gq.data_ptr()
+    p.gk = 0 if gk is None else gk.data_ptr()
+    cps = [None if o.dtype == torch.float32 else torch.empty(o.shape, device=DEV) for o in outs]
+    for i, o in enumerate(outs):
+        setattr(p, f"out{i}", o.ptr())
+        if cps[i] is not None:
+            setattr(p, f"out{i}_f32", cps[i].data_ptr())
+            setattr(p, f"n{i}", o.n)
+    _lib.check(lib.f5k_gemm_epi(prec_id(prec), _p(A), _p(W), _p(bias), M, N, K, C.byref(p), _s()), "f5k_gemm_epi")
+    return [o.value if c is None else c for o, c in zip(outs, cps)]
