@@ -8,6 +8,7 @@
  *
  * Each function names the reference interface it replaces (paths relative to the reference's src/f5_tts/):
  *   f5_sample        <- CFM.sample's ODE solve                       model/cfm.py:151-223 (odeint call :218)
+ *   f5_sample_ode    <- the same with odeint_kwargs=dict(method="euler" | "midpoint")  model/cfm.py:42,218
  *   f5_dit_forward   <- DiT.forward / UNetT.forward                  model/backbones/dit.py:278-329, unett.py:217-280
  *   f5_text_embed    <- TextEmbedding.forward (+ per-sample loop)    model/backbones/dit.py:86-115,244-258
  *   f5_vocos_decode  <- vocoder.decode(mel)                          infer/utils_infer.py:702-703 (third-party vocos)
@@ -125,7 +126,19 @@ int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_
               const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
               const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream);
 
-/* Pre-sizes the activation arena (otherwise it grows on first use, which calls hipMalloc inside f5_sample). */
+/* Fixed-grid ODE solvers of f5_sample_ode (torchdiffeq's odeint(method=...), cfm.py:42,218). */
+#define F5_ODE_EULER 0     /* y += dt * f(t[i], y): 1 backbone evaluation per step */
+#define F5_ODE_MIDPOINT 1  /* y_mid = y + f(t[i], y) * dt/2; y += dt * f(t[i] + dt/2, y_mid): 2 evaluations per step (NFE = 2 * steps);
+                            * the trajectory holds the grid points only */
+
+/* f5_sample with the solver chosen by `method` (F5_ODE_*); f5_sample is f5_sample_ode(..., F5_ODE_EULER).  An unknown
+ * method fails with F5_EINVAL. */
+int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                  const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
+                  const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream, int32_t method);
+
+/* Pre-sizes the activation arena (otherwise it grows on first use, which calls hipMalloc inside f5_sample).  The plan for
+ * max_steps covers both solvers: a midpoint call with steps <= max_steps needs no regrowth. */
 int f5_reserve(f5_engine* e, int32_t max_batch, int32_t max_frames, int32_t max_steps);
 
 /* ------------------------------------------------------------------------------------------------ Vocos */

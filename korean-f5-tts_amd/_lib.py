@@ -13,6 +13,8 @@ F5_PREC_F32, F5_PREC_BF16, F5_PREC_F16, F5_PREC_F16X3, F5_PREC_F16P = 0, 1, 2, 3
 PRECISIONS = {"f32": F5_PREC_F32, "fp32": F5_PREC_F32, "bf16": F5_PREC_BF16, "f16": F5_PREC_F16, "fp16": F5_PREC_F16,
               "f16x3": F5_PREC_F16X3, "f16p": F5_PREC_F16P, "parity": F5_PREC_F16P}
 F5_BACKBONE_DIT, F5_BACKBONE_UNETT = 0, 1
+F5_ODE_EULER, F5_ODE_MIDPOINT = 0, 1
+ODE_METHODS = {"euler": F5_ODE_EULER, "midpoint": F5_ODE_MIDPOINT}
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_MISH = 0, 1, 2, 3, 4
 PROFILE_CLASSES = ("gemm", "attention", "layernorm", "convpos", "misc", "text_encoder", "time_adaln")
 
@@ -69,6 +71,7 @@ SIGNATURES = {
     "f5_text_embed": (_i, [_p, _p, _i, _i, C.POINTER(_i), _i, _i, _p, _p]),
     "f5_dit_forward": (_i, [_p, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), _i, _i, _i, _i, _i, _p, _p]),
     "f5_sample": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p]),
+    "f5_sample_ode": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_reserve": (_i, [_p, _i, _i, _i]),
     "f5_vocos_create": (_i, [C.POINTER(f5_vocos_config), C.POINTER(_p)]),
     "f5_vocos_destroy": (_i, [_p]),

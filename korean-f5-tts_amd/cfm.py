@@ -1,7 +1,8 @@
 """Drop-in for the reference's `CFM` inference surface (model/cfm.py:34-229): same constructor keywords, same
 `sample()` signature and return value, same attributes read by callers (`.transformer`, `.mel_spec`,
 `.vocab_char_map`, `.device`, `.dim`, `.num_channels`).  Argument handling (cfm.py:103-158, 196-216, 219-229) is
-host-side Python; the ODE solve itself (cfm.py:160-191, 218) is ONE call into the HIP engine (f5_sample).
+host-side Python; the ODE solve itself (cfm.py:160-191, 218) is ONE call into the HIP engine (f5_sample_ode), with
+odeint_kwargs["method"] "euler" or "midpoint" (torchdiffeq's fixed-grid solvers; midpoint makes 2 evaluations per step).
 Training (`forward`, cfm.py:231-302) is out of scope.
 """
 from __future__ import annotations
@@ -19,8 +20,9 @@ class CFM(nn.Module):
                  audio_drop_prob=0.3, cond_drop_prob=0.2, num_channels=None, mel_spec_module: nn.Module | None = None,
                  mel_spec_kwargs: dict = dict(), frac_lengths_mask=(0.7, 1.0), vocab_char_map=None):
         super().__init__()
-        if odeint_kwargs.get("method", "euler") != "euler":
-            raise NotImplementedError("only the fixed-grid Euler solver (every shipped config) is built")
+        if odeint_kwargs.get("method", "euler") not in ("euler", "midpoint"):
+            raise NotImplementedError(f"ODE method {odeint_kwargs.get('method')!r}: only the fixed-grid solvers "
+                                      "'euler' (every shipped config) and 'midpoint' are built")
         self.frac_lengths_mask = frac_lengths_mask
         if mel_spec_module is None:
             from .mel import MelSpec
@@ -112,7 +114,8 @@ class CFM(nn.Module):
 
         eng = self.transformer.engine()
         out, trajectory = eng.sample(None if no_ref_audio else cond, cond_mask, y0, text_cpu, t.tolist(), cfg_strength,
-                                     lens=duration.tolist() if batch > 1 else None, want_traj=True)
+                                     lens=duration.tolist() if batch > 1 else None, want_traj=True,
+                                     method=self.odeint_kwargs.get("method", "euler"))
         self.transformer.clear_cache()
         if exists(vocoder):
             out = vocoder(out.permute(0, 2, 1))

@@ -231,6 +231,54 @@ static __global__ void euler_cfg_packed_kernel(float* __restrict__ y, const floa
         if (traj_slot) reinterpret_cast<float4*>(traj_slot)[i] = yy;
     }
 }
+// ------------------------------------------------------------------------------------- CFG + midpoint half step
+// y_mid = y + (p + (p - u) * cfg) * (dt / 2)   (torchdiffeq Midpoint._step_func: f0 at (t[i], y), y_mid = y + f0 * half_dt).
+// The full step is euler_cfg(_packed)_kernel on the prediction made at y_mid: y += dt * f(t[i] + dt / 2, y_mid).
+static __global__ void midpoint_half_cfg_kernel(const float* __restrict__ y, const float* __restrict__ pred, long half_elems,
+                                                const float* __restrict__ tgrid, int step, float cfg, int use_cfg,
+                                                float* __restrict__ y_mid) {
+    const float hdt = 0.5f * (tgrid[step + 1] - tgrid[step]);   // f32, in torchdiffeq's order
+    const long n4 = half_elems / 4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        float4 yy = reinterpret_cast<const float4*>(y)[i];
+        const float4 p = reinterpret_cast<const float4*>(pred)[i];
+        float4 v = p;
+        if (use_cfg) {
+            const float4 u = reinterpret_cast<const float4*>(pred + half_elems)[i];
+            v.x = p.x + (p.x - u.x) * cfg; v.y = p.y + (p.y - u.y) * cfg;
+            v.z = p.z + (p.z - u.z) * cfg; v.w = p.w + (p.w - u.w) * cfg;
+        }
+        yy.x += v.x * hdt; yy.y += v.y * hdt; yy.z += v.z * hdt; yy.w += v.w * hdt;
+        reinterpret_cast<float4*>(y_mid)[i] = yy;
+    }
+}
+// RowPack twin (pred on packed rows, as euler_cfg_packed_kernel reads it); frames past a sample's length get y_mid = y
+static __global__ void midpoint_half_cfg_packed_kernel(const float* __restrict__ y, const float* __restrict__ pred, int B, int N,
+                                                       int mel, const int* __restrict__ row_start, const int* __restrict__ lens,
+                                                       const float* __restrict__ tgrid, int step, float cfg, int use_cfg,
+                                                       float* __restrict__ y_mid) {
+    const float hdt = 0.5f * (tgrid[step + 1] - tgrid[step]);
+    const int c4n = mel / 4;
+    const long total = (long)B * N * c4n;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4n);
+        const long fr = i / c4n;
+        const int n = (int)(fr % N), b = (int)(fr / N);
+        float4 yy = reinterpret_cast<const float4*>(y)[i];
+        if (n < lens[b]) {
+            const float4 p = reinterpret_cast<const float4*>(pred + ((size_t)row_start[b] + n) * mel)[c];
+            float4 v = p;
+            if (use_cfg) {
+                const float4 u = reinterpret_cast<const float4*>(pred + ((size_t)row_start[B + b] + n) * mel)[c];
+                v.x = p.x + (p.x - u.x) * cfg; v.y = p.y + (p.y - u.y) * cfg;
+                v.z = p.z + (p.z - u.z) * cfg; v.w = p.w + (p.w - u.w) * cfg;
+            }
+            yy.x += v.x * hdt; yy.y += v.y * hdt; yy.z += v.z * hdt; yy.w += v.w * hdt;
+        }
+        reinterpret_cast<float4*>(y_mid)[i] = yy;
+    }
+}
+
 // rowmap[row_start[b'] + n] = (b', n) for n < row_start[b' + 1] - row_start[b']   (one block per batch row)
 static __global__ void fill_rowmap_kernel(const int* __restrict__ row_start, int2* __restrict__ rowmap) {
     const int bp = blockIdx.x, r0 = row_start[bp], cnt = row_start[bp + 1] - r0;

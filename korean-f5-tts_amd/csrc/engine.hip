@@ -5,7 +5,8 @@
 //   residual stream x, embed h, c1   f32 [2B*N, D]
 //   xn (LN-modulated), attn out, ffh T   [2B*N, D | inner | F]          T = bf16 / f16 (speed) or f32 (parity)
 //   q, k                             T   [2B, H, N, 64]      v^T  T [2B, H, 64, Npad]
-//   mod                              f32 [steps, (6*depth + 2) * D]     all AdaLN vectors of all layers for ALL steps
+//   mod                              f32 [evals, (6*depth + 2) * D]     all AdaLN vectors of all layers for ALL backbone
+//                                                                       evaluations (steps, or 2 * steps for midpoint)
 // Weights are engine-owned copies: GEMM operands in T ([out, in], K padded to whole 128-byte K-tiles), everything that feeds
 // fp32-only stages (time MLP, AdaLN stack, text encoder, norms, biases) in f32.
 //
@@ -218,9 +219,12 @@ bool graphs_enabled(f5_engine* e) {
     }
     return e->graphs_on == 1;
 }
-extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
-                         const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
-                         const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream) {
+extern "C" int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                             const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
+                             const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream,
+                             int32_t method) {
+    if (method != F5_ODE_EULER && method != F5_ODE_MIDPOINT)
+        return fail(F5_EINVAL, "f5_sample_ode: unknown ODE method %d (F5_ODE_EULER = 0, F5_ODE_MIDPOINT = 1)", method);
     CHK(check_ready(e, B, N));
     if ((!cond && cond_frames > 0) || !cond_mask || !y0 || !text || !t_host || !out || nt <= 0 || steps <= 0 || cond_frames < 0 ||
         cond_frames > N)
@@ -231,7 +235,14 @@ extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, c
             if (lens_host[i] <= 0 || lens_host[i] > N) return fail(F5_EINVAL, "lens[%d]=%d out of (0, N]", i, lens_host[i]);
     hipStream_t s = (hipStream_t)stream;
     e->prof.clear();
-    return F5_OPS(e, sample(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj, s));
+    return F5_OPS(e, sample(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj, s,
+                            method));
+}
+extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                         const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
+                         const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream) {
+    return f5_sample_ode(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj,
+                         stream, F5_ODE_EULER);
 }
 
 extern "C" int f5_profile_enable(f5_engine* e, int32_t on) {

@@ -261,9 +261,11 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     const size_t Bp = 2 * (size_t)B, D = c.dim, Dt = c.text_dim, F = c.ff_dim, mel = c.mel_dim;
     const size_t Nt = c.backbone == F5_BACKBONE_UNETT ? N + 1 : N;  // UNetT prepends the time token
     const size_t rows = Bp * Nt;
-    const size_t SS = (size_t)std::max(S + 1, (int)Bp + 1);
+    // time rows: one per backbone evaluation -- S (Euler) or 2 S (midpoint) in sample(), Bp in forward() -- and behind the
+    // evaluation times in tdev the grid t[0..S] (sample_body: the dt of every step)
+    const size_t SS = (size_t)std::max(2 * S + 1, (int)Bp + 1);
     w.Npad = round_up((int)Nt, 64);
-    w.tdev = a.take<float>(SS);
+    w.tdev = a.take<float>(SS + (size_t)S + 1);
     w.feat = a.take<float>(SS * 256);
     w.th = a.take<float>(SS * D);
     w.temb = a.take<float>(SS * D);
@@ -294,6 +296,7 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     w.ffh = a.take<T>(rows * F);
     w.in_cond = a.take<float>((size_t)B * N * mel);
     w.y = a.take<float>((size_t)B * N * mel);
+    w.y_mid = a.take<float>((size_t)B * N * mel);
     w.out_buf = a.take<float>((size_t)B * N * mel);
     w.traj_buf = a.take<float>((size_t)(S + 1) * B * N * mel);
     w.in_mask = a.take<unsigned char>((size_t)B * N + 16);
@@ -881,13 +884,19 @@ static bool uc_cacheable(const f5_engine* e, int B, bool has_lens) {
     return B == 1 && !has_lens && !(e->cfg.text_mask_padding && e->cfg.conv_layers > 0) && !(e->cfg.options & F5_OPT_TEXT_AVG_UPSAMPLE);
 }
 
-// the stream-ordered body of sample(): everything between "inputs are in the arena" and "outputs are in the arena"
+// the stream-ordered body of sample(): everything between "inputs are in the arena" and "outputs are in the arena".
+// w.tdev holds the evaluation times (feature rows) and then the grid: Euler evaluates at t[0..steps-1], which IS the
+// grid's head, so tdev = t[0..steps] as uploaded; midpoint evaluates at t[i] (row 2i) and t[i] + dt/2 (row 2i+1), and
+// the grid follows at tdev + 2 steps (sample_impl).
 template <typename T>
 static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_strength, bool has_lens, int B, int N,
-                       bool want_traj, hipStream_t s) {
+                       bool want_traj, hipStream_t s, int method = F5_ODE_EULER) {
     const f5_config& c = e->cfg;
     const int mel = c.mel_dim;
     const bool use_cfg = !(cfg_strength < 1e-5f);
+    const bool mid = method == F5_ODE_MIDPOINT;
+    const int evals = mid ? 2 : 1;                           // backbone evaluations per step
+    const float* tgrid = mid ? w.tdev + 2 * steps : w.tdev;
     const int Bp = use_cfg ? 2 * B : B;
     const int* lens_dev = has_lens ? w.lens : nullptr;
     const long half = (long)B * N * mel;
@@ -898,7 +907,7 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
                        w.in_mask, w.step_cond, (long)B * N, mel);
     KCHK();
     e->prof.end(s);
-    CHK(run_time_path<T>(e, w, steps, s));  // features of t[0..steps-1]
+    CHK(run_time_path<T>(e, w, evals * steps, s));  // features of every evaluation time
     const int* tlens = (c.backbone == F5_BACKBONE_DIT && has_lens) ? w.lens_plain : nullptr;
     CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 0, w.text_c, s));
     if (use_cfg) {
@@ -947,15 +956,27 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
     for (int i = 0; i < steps; ++i) {
         if (split) {
             hipStream_t s1 = e->side_stream;
-            HIPCHK(hipEventRecord(e->ev_fork, s));            // y of this step (and, first time, the text embeddings) ready
-            HIPCHK(hipStreamWaitEvent(s1, e->ev_fork, 0));
-            // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
-            CHK(run_backbone<T>(e, w, w.y, w.step_cond, B, B, N, i, 0, lens_dev, 0, w.text_c, w.text_c, s));
-            CHK(run_backbone<T>(e, w2, w.y, w.step_cond, B, B, N, i, 0, lens_dev, 1, w.text_u, w.text_u, s1));
-            HIPCHK(hipEventRecord(e->ev_join, s1));
-            HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));
+            // one CFG evaluation at state x: conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
+            auto split_eval = [&](const float* x, int row) -> int {
+                HIPCHK(hipEventRecord(e->ev_fork, s));            // x (and, first time, the text embeddings) ready
+                HIPCHK(hipStreamWaitEvent(s1, e->ev_fork, 0));
+                CHK(run_backbone<T>(e, w, x, w.step_cond, B, B, N, row, 0, lens_dev, 0, w.text_c, w.text_c, s));
+                CHK(run_backbone<T>(e, w2, x, w.step_cond, B, B, N, row, 0, lens_dev, 1, w.text_u, w.text_u, s1));
+                HIPCHK(hipEventRecord(e->ev_join, s1));
+                HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));
+                return F5_OK;
+            };
+            CHK(split_eval(w.y, evals * i));
+            if (mid) {
+                e->prof.begin(PC_MISC, s);
+                hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
+                                   cfg_strength, use_cfg ? 1 : 0, w.y_mid);
+                KCHK();
+                e->prof.end(s);
+                CHK(split_eval(w.y_mid, 2 * i + 1));
+            }
             e->prof.begin(PC_MISC, s);
-            hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, w.tdev, i,
+            hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
                                cfg_strength, use_cfg ? 1 : 0, want_traj ? w.traj_buf + (size_t)(i + 1) * half : nullptr);
             KCHK();
             e->prof.end(s);
@@ -967,16 +988,32 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
             const size_t yo = (size_t)u0 * N * mel, to = (size_t)u0 * N * c.text_dim;
             const long half_c = (long)bc * N * mel;
             const RowPack pk = chunk_pack(u0, cidx, bc);
-            CHK(run_backbone<T>(e, w, w.y + yo, w.step_cond + yo, bc, use_cfg ? 2 * bc : bc, N, i, 0,
-                                lens_dev ? lens_dev + 2 * u0 : nullptr, 0, w.text_c + to,
-                                use_cfg ? w.text_u + to : w.text_c + to, s, pk));
+            auto eval = [&](const float* x, int row) {
+                return run_backbone<T>(e, w, x, w.step_cond + yo, bc, use_cfg ? 2 * bc : bc, N, row, 0,
+                                       lens_dev ? lens_dev + 2 * u0 : nullptr, 0, w.text_c + to,
+                                       use_cfg ? w.text_u + to : w.text_c + to, s, pk);
+            };
+            CHK(eval(w.y + yo, evals * i));
+            if (mid) {   // y_mid = y + f(t[i], y) * dt/2, then the full step below on f(t[i] + dt/2, y_mid)
+                e->prof.begin(PC_MISC, s);
+                if (pk)
+                    hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred,
+                                       bc, N, mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0,
+                                       w.y_mid + yo);
+                else
+                    hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c,
+                                       tgrid, i, cfg_strength, use_cfg ? 1 : 0, w.y_mid + yo);
+                KCHK();
+                e->prof.end(s);
+                CHK(eval(w.y_mid + yo, 2 * i + 1));
+            }
             e->prof.begin(PC_MISC, s);
             float* slot = want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
             if (pk)
                 hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, bc, N,
-                                   mel, pk.row_start, lens_dev + 2 * u0, w.tdev, i, cfg_strength, use_cfg ? 1 : 0, slot);
+                                   mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0, slot);
             else
-                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c, w.tdev,
+                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c, tgrid,
                                    i, cfg_strength, use_cfg ? 1 : 0, slot);
             KCHK();
             e->prof.end(s);
@@ -993,7 +1030,7 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
 template <typename T>
 static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
                        int nt, const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N,
-                       float* out, float* traj, hipStream_t s) {
+                       float* out, float* traj, hipStream_t s, int method) {
     const int mel = e->cfg.mel_dim;
     const long half = (long)B * N * mel;
     if (nt > e->res_nt) {   // the text staging buffer is part of the arena plan
@@ -1005,7 +1042,19 @@ static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const u
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     // ---- inputs -> arena (eager, on the caller's stream)
     e->cur_chunk = chunk_utts(e, B, N, !(cfg_strength < 1e-5f), lens_host);
-    CHK(upload_small<T>(e, w, t_host, steps + 1, lens_host, B, s, e->cur_chunk, cfg_strength < 1e-5f ? 1 : 2));
+    if (method == F5_ODE_MIDPOINT) {
+        // evaluation times t[i], t[i] + dt/2 (f32, in torchdiffeq's order: half_dt = 0.5 * (t[i+1] - t[i])), then the grid
+        std::vector<float> tt((size_t)3 * steps + 1);
+        for (int i = 0; i < steps; ++i) {
+            const float hdt = 0.5f * (t_host[i + 1] - t_host[i]);
+            tt[2 * i] = t_host[i];
+            tt[2 * i + 1] = t_host[i] + hdt;
+        }
+        std::copy(t_host, t_host + steps + 1, tt.begin() + 2 * steps);
+        CHK(upload_small<T>(e, w, tt.data(), 3 * steps + 1, lens_host, B, s, e->cur_chunk, cfg_strength < 1e-5f ? 1 : 2));
+    } else {
+        CHK(upload_small<T>(e, w, t_host, steps + 1, lens_host, B, s, e->cur_chunk, cfg_strength < 1e-5f ? 1 : 2));
+    }
     if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
     if (cond_frames > 0)
         HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
@@ -1021,8 +1070,8 @@ static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const u
     unsigned cfg_bits;
     memcpy(&cfg_bits, &cfg_strength, 4);
     char kb[160];
-    snprintf(kb, sizeof(kb), "%d|%d|%d|%d|%08x|%d|%d|%d", B, N, nt, steps, cfg_bits, lens_host ? 1 : 0, traj ? 1 : 0,
-             e->cur_chunk);
+    snprintf(kb, sizeof(kb), "%d|%d|%d|%d|%08x|%d|%d|%d|m%d", B, N, nt, steps, cfg_bits, lens_host ? 1 : 0, traj ? 1 : 0,
+             e->cur_chunk, method);
     const std::string base_key(kb);
     const std::string key = base_key + (uc_hit ? "|uc" : "|nouc");
     bool done = false;
@@ -1047,7 +1096,8 @@ static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const u
             hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
             if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                const int rc = sample_body<T>(e, w, nt, steps, cfg_strength, lens_host != nullptr, B, N, traj != nullptr, e->cap_stream);
+                const int rc = sample_body<T>(e, w, nt, steps, cfg_strength, lens_host != nullptr, B, N, traj != nullptr, e->cap_stream,
+                                              method);
                 const hipError_t ce = hipStreamEndCapture(e->cap_stream, &graph);
                 if (rc == F5_OK && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                     if (e->graphs.size() >= 16) {
@@ -1074,7 +1124,7 @@ static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const u
         }
     }
     if (!done) {
-        CHK(sample_body<T>(e, w, nt, steps, cfg_strength, lens_host != nullptr, B, N, traj != nullptr, s));
+        CHK(sample_body<T>(e, w, nt, steps, cfg_strength, lens_host != nullptr, B, N, traj != nullptr, s, method));
         trace_done("eager launches");
         if (std::find(e->warm.begin(), e->warm.end(), base_key) == e->warm.end()) e->warm.push_back(base_key);
     }
@@ -1105,6 +1155,7 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
 template <typename T>
 int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
                          const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
-                         float* traj, hipStream_t s) {
-    return sample_impl<T>(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj, s);
+                         float* traj, hipStream_t s, int method) {
+    return sample_impl<T>(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj, s,
+                          method);
 }

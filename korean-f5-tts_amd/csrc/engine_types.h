@@ -252,7 +252,7 @@ template <typename U> static int dev_alloc(f5_engine* e, U** out, size_t n) {
 // ---------------------------------------------------------------------------------------------- workspace
 template <typename T> struct Work {
     // per call
-    float *tdev, *feat, *th, *temb, *st, *mod;
+    float *tdev, *feat, *th, *temb, *st, *mod;   // tdev: the evaluation times (feature rows), then the grid (sample_body)
     int* lens;        // per-sample lengths, chunk-major: for each chunk of Bc utterances [Bc values][the same Bc values]
     int* lens_plain;  // the same lengths once, in utterance order (text encoder)
     int* row_start;   // RowPack: per chunk [2 Bc + 1] first packed row of every batch row (cond half, uncond half), last = rows
@@ -269,6 +269,7 @@ template <typename T> struct Work {
     float* pred_all; // UNetT proj_out over N+1 tokens
     // sample(): engine-owned copies of the call's inputs / outputs so that the captured graph has stable pointers
     float *in_cond, *y, *out_buf, *traj_buf;
+    float* y_mid;     // F5_ODE_MIDPOINT: the state at the half step [B, N, mel]
     unsigned char* in_mask;
     long long* in_text;
     int Npad;
@@ -311,7 +312,7 @@ template <typename T> struct EngineOps {
                        hipStream_t s);
     static int sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
                       const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
-                      float* traj, hipStream_t s);
+                      float* traj, hipStream_t s, int method);
 };
 extern template struct EngineOps<float>;
 extern template struct EngineOps<bf16_t>;

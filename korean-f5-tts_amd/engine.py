@@ -146,9 +146,12 @@ class Engine:
                                                _stream_ptr(self.device)), "f5_dit_forward")
         return out
 
-    def sample(self, cond, cond_mask, y0, text, t_grid, cfg_strength, lens=None, want_traj=True):
+    def sample(self, cond, cond_mask, y0, text, t_grid, cfg_strength, lens=None, want_traj=True, method="euler"):
         """cond f32[B,Nc,mel] (Nc <= N: the engine zero-pads, cfm.py:145; None = no_ref_audio), cond_mask bool[B,N],
-        y0 f32[B,N,mel], text i64[B,nt], t_grid list[float]."""
+        y0 f32[B,N,mel], text i64[B,nt], t_grid list[float]; method "euler" (1 backbone evaluation per step) or
+        "midpoint" (2 per step), torchdiffeq's fixed-grid solvers on the same grid."""
+        if method not in _lib.ODE_METHODS:
+            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
         B, N, mel = y0.shape
         cond_frames = 0 if cond is None else cond.shape[1]
         steps = len(t_grid) - 1
@@ -160,9 +163,10 @@ class Engine:
         out = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
         traj = torch.empty(steps + 1, B, N, mel, device=self.device, dtype=torch.float32) if want_traj else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.f5_sample(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y0), _ptr(text), text.shape[1],
-                                          _lib.float_array(t_grid), steps, float(cfg_strength), _lib.int_array(lens),
-                                          B, N, _ptr(out), _ptr(traj), _stream_ptr(self.device)), "f5_sample")
+            _lib.check(self.lib.f5_sample_ode(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y0), _ptr(text), text.shape[1],
+                                              _lib.float_array(t_grid), steps, float(cfg_strength), _lib.int_array(lens),
+                                              B, N, _ptr(out), _ptr(traj), _stream_ptr(self.device), _lib.ODE_METHODS[method]),
+                       "f5_sample_ode")
         return out, traj
 
     # ------------------------------------------------------------------ profiling
