@@ -100,10 +100,12 @@ def amp_block1(V, pfx, x, k, dilations, fu, fd):
 
 
 @torch.no_grad()
-def bigvgan_forward(V: dict, cfg: dict, mel: torch.Tensor) -> torch.Tensor:
-    """mel f32[B, num_mels, T] -> wav f32[B, 1, T * prod(upsample_rates)]   (BigVGAN.forward)."""
-    fu, fd = aa_filters()
-    x = F.conv1d(mel.to(torch.float32), V["conv_pre.weight"], V["conv_pre.bias"], padding=3)
+def bigvgan_forward(V: dict, cfg: dict, mel: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """mel f32[B, num_mels, T] -> wav f32[B, 1, T * prod(upsample_rates)]   (BigVGAN.forward).
+    dtype=torch.float64 evaluates the same operation in float64 on the same weights and the same (f32) anti-aliasing filters."""
+    fu, fd = (f.to(dtype) for f in aa_filters())
+    V = {k: v.to(dtype) for k, v in V.items()}
+    x = F.conv1d(mel.to(dtype), V["conv_pre.weight"], V["conv_pre.bias"], padding=3)
     nk = len(cfg["resblock_kernel_sizes"])
     for i, (u, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
         x = F.conv_transpose1d(x, V[f"ups.{i}.0.weight"], V[f"ups.{i}.0.bias"], stride=u, padding=(k - u) // 2)
@@ -152,13 +154,15 @@ def librosa_slaney_mel_fb(sr: int, n_fft: int, n_mels: int, fmin: float = 0.0, f
 
 
 @torch.no_grad()
-def mel_spectrogram_bigvgan(wav, n_fft=1024, hop=256, n_mels=100, sample_rate=24000, win=1024, fmin=0.0, fmax=None):
+def mel_spectrogram_bigvgan(wav, n_fft=1024, hop=256, n_mels=100, sample_rate=24000, win=1024, fmin=0.0, fmax=None,
+                            dtype=torch.float32, fb=None):
     """modules.py:33-75 `get_bigvgan_mel_spectrogram`: reflect pad (n_fft - hop) / 2 on both sides, stft(center=False, hann),
-    sqrt(re^2 + im^2 + 1e-9), slaney mel basis, log(clamp(., 1e-5)).  wav [B, nw] -> [B, n_mels, T]."""
-    fb = librosa_slaney_mel_fb(sample_rate, n_fft, n_mels, fmin, fmax)
+    sqrt(re^2 + im^2 + 1e-9), slaney mel basis, log(clamp(., 1e-5)).  wav [B, nw] -> [B, n_mels, T].
+    dtype=torch.float64 evaluates it in float64; fb [n_mels, n_freqs] replaces the restated filterbank."""
+    fb = (librosa_slaney_mel_fb(sample_rate, n_fft, n_mels, fmin, fmax) if fb is None else fb).to(dtype)
     pad = (n_fft - hop) // 2
-    w = F.pad(wav.unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
-    spec = torch.stft(w, n_fft, hop_length=hop, win_length=win, window=torch.hann_window(win), center=False, pad_mode="reflect",
+    w = F.pad(wav.to(dtype).unsqueeze(1), (pad, pad), mode="reflect").squeeze(1)
+    spec = torch.stft(w, n_fft, hop_length=hop, win_length=win, window=torch.hann_window(win, dtype=dtype), center=False, pad_mode="reflect",
                       normalized=False, onesided=True, return_complex=True)
     mag = torch.sqrt(torch.view_as_real(spec).pow(2).sum(-1) + 1e-9)
     return torch.log(torch.clamp(torch.matmul(fb, mag), min=1e-5))

@@ -486,8 +486,15 @@ def draw_noise(duration: torch.Tensor, mel_dim: int, seed) -> torch.Tensor:
 # -------------------------------------------------------------------------------------------------- Vocos
 
 
-def vocos_backbone(V, mel):
-    """mel f32[b, 100, T] -> f32[b, T, 512].  Restated from the published Vocos architecture (parity unpinned)."""
+def weights_as(V, dtype):
+    """The weights in `dtype` (the same tensors when they already are: the f32 path stays bit-identical)."""
+    return {k: v.to(dtype) for k, v in V.items()}
+
+
+def vocos_backbone(V, mel, dtype=torch.float32):
+    """mel f32[b, 100, T] -> f32[b, T, 512].  Restated from the published Vocos architecture (parity unpinned).
+    dtype=torch.float64 evaluates the same operation on the same weights in float64 (the kernels' tests)."""
+    V, mel = weights_as(V, dtype), mel.to(dtype)
     dim = V["backbone.embed.weight"].shape[0]
     h = F.conv1d(mel, V["backbone.embed.weight"], V["backbone.embed.bias"], padding=3)
     h = F.layer_norm(h.transpose(1, 2), (dim,), V["backbone.norm.weight"], V["backbone.norm.bias"], eps=1e-6)
@@ -505,19 +512,21 @@ def vocos_backbone(V, mel):
                         eps=1e-6)
 
 
-def istft_head_spec(V, h):
+def istft_head_spec(V, h, dtype=torch.float32):
     """export_vocoder_to_onnx.py:51-59: Linear -> (mag, phase) -> exp, clip 1e2, cos/sin.  Returns (re, im) [b,513,T]."""
+    V, h = weights_as(V, dtype), h.to(dtype)
     x = linear(h, V, "head.out").transpose(1, 2)
     mag, p = x.chunk(2, dim=1)
     mag = torch.clip(torch.exp(mag), max=1e2)
     return mag * torch.cos(p), mag * torch.sin(p)
 
 
-def vocos_decode(V, mel, n_fft=1024, hop=256):
-    """mel f32[b, 100, T] -> wav f32[b, (T-1)*hop]  (Vocos ISTFTHead, padding="center" -> torch.istft center=True)."""
-    re, im = istft_head_spec(V, vocos_backbone(V, mel))
+def vocos_decode(V, mel, n_fft=1024, hop=256, dtype=torch.float32):
+    """mel f32[b, 100, T] -> wav f32[b, (T-1)*hop]  (Vocos ISTFTHead, padding="center" -> torch.istft center=True).
+    dtype=torch.float64: the whole decode in float64 (complex128 spectrum, float64 window)."""
+    re, im = istft_head_spec(V, vocos_backbone(V, mel, dtype), dtype)
     spec = torch.complex(re, im)
-    return torch.istft(spec, n_fft, hop, n_fft, window=torch.hann_window(n_fft), center=True)
+    return torch.istft(spec, n_fft, hop, n_fft, window=torch.hann_window(n_fft, dtype=dtype), center=True)
 
 
 # ----------------------------------------------------------------------------------------- mel front-end
@@ -539,10 +548,13 @@ def htk_mel_filterbank(n_freqs, n_mels, sample_rate, f_min=0.0, f_max=None):
     return torch.clamp(torch.min(down, up), min=0.0)  # [n_freqs, n_mels]
 
 
-def mel_spectrogram_vocos(wav, n_fft=1024, hop=256, n_mels=100, sample_rate=24000):
-    """modules.py:78-104: MelSpectrogram(power=1, center=True, norm=None) -> clamp(min=1e-5).log(); wav [b, nw] -> [b, n_mels, T]."""
-    spec = torch.stft(wav, n_fft, hop_length=hop, win_length=n_fft, window=torch.hann_window(n_fft), center=True,
+def mel_spectrogram_vocos(wav, n_fft=1024, hop=256, n_mels=100, sample_rate=24000, dtype=torch.float32, fb=None):
+    """modules.py:78-104: MelSpectrogram(power=1, center=True, norm=None) -> clamp(min=1e-5).log(); wav [b, nw] -> [b, n_mels, T].
+    dtype=torch.float64 evaluates it in float64; fb [n_freqs, n_mels] replaces the restated filterbank (e.g. the product's own
+    table, so that a kernel test checks arithmetic only)."""
+    wav = wav.to(dtype)
+    spec = torch.stft(wav, n_fft, hop_length=hop, win_length=n_fft, window=torch.hann_window(n_fft, dtype=dtype), center=True,
                       pad_mode="reflect", normalized=False, onesided=True, return_complex=True).abs()
-    fb = htk_mel_filterbank(n_fft // 2 + 1, n_mels, sample_rate)
+    fb = (htk_mel_filterbank(n_fft // 2 + 1, n_mels, sample_rate) if fb is None else fb).to(dtype)
     mel = torch.matmul(spec.transpose(1, 2), fb).transpose(1, 2)
     return mel.clamp(min=1e-5).log()

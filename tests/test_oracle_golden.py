@@ -87,3 +87,30 @@ def test_vocos_istft_matches_torch_and_head_formula():
         env[t * 256:t * 256 + 1024] += torch.hann_window(1024) ** 2
     y = (y / env)[:, 512:-512]
     assert (y - wav).abs().max() < 1e-4 * max(1.0, wav.abs().max().item())
+
+
+def test_float64_restatements_agree_with_f32():
+    """dtype=torch.float64 (the GPU kernel tests' references) evaluates the same operations as the f32 default: on small cases
+    the two agree to f32 rounding, so the float64 path cannot drift into a different operation."""
+    import f5_tts_amd as P
+    from oracle import bigvgan_oracle as BO
+
+    f64 = torch.float64
+    g = torch.Generator().manual_seed(2)
+    V = P.weights.synthetic_state_dict(P.weights.vocos_param_shapes(P.config.VOCOS_TINY), seed=1)
+    mel = torch.randn(2, 100, 6, generator=g)
+    h32, h64 = O.vocos_backbone(V, mel), O.vocos_backbone(V, mel, dtype=f64)
+    assert h64.dtype == f64 and (h64 - h32).abs().max() < 1e-5
+    for a, b in zip(O.istft_head_spec(V, h32), O.istft_head_spec(V, h32, dtype=f64)):
+        assert b.dtype == f64 and (b - a).abs().max() < 1e-5 * a.abs().max()
+    w32, w64 = O.vocos_decode(V, mel), O.vocos_decode(V, mel, dtype=f64)
+    assert w64.dtype == f64 and w64.shape == w32.shape and (w64 - w32).abs().max() < 1e-5 * w32.abs().max()
+    wav = torch.randn(2, 3000, generator=g) * 0.1
+    for fn in (O.mel_spectrogram_vocos, BO.mel_spectrogram_bigvgan):
+        m32, m64 = fn(wav), fn(wav, dtype=f64)
+        assert m64.dtype == f64 and m64.shape == m32.shape and (m64 - m32).abs().max() < 1e-4
+    cfg = P.config.BIGVGAN_TINY
+    VB = P.weights.synthetic_state_dict(P.weights.bigvgan_param_shapes(cfg), seed=1)
+    mel = torch.randn(1, 100, 5, generator=g)
+    b32, b64 = BO.bigvgan_forward(VB, cfg, mel), BO.bigvgan_forward(VB, cfg, mel, dtype=f64)
+    assert b64.dtype == f64 and b64.shape == b32.shape and (b64 - b32).abs().max() < 1e-5

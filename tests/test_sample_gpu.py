@@ -291,7 +291,7 @@ def test_vocos_decode_vs_oracle():
         assert wav.shape == ref.shape
         e = (wav - ref).abs().max().item()
         print(f"[vocos f32] T={T}: wav Linf {e:.3e} (peak {ref.abs().max().item():.3f})")
-        assert e < 1e-3 * max(1.0, ref.abs().max().item())
+        assert e < 2e-6 * max(1.0, ref.abs().max().item())      # measured 8.0e-7 (T = 130)
 
 
 def test_mel_frontend_vs_oracle_and_wav_prompt():
