@@ -51,6 +51,9 @@ extern "C" {
 #define F5_OPT_QK_RMSNORM 1        /* qk_norm="rms_norm" (modules.py:397-404,481-484): weights ...attn.q_norm.weight / k_norm.weight [64] */
 #define F5_OPT_LONG_SKIP 2         /* long_skip_connection=True (dit.py:205,313-324): long_skip_connection.weight [D, 2D] */
 #define F5_OPT_TEXT_AVG_UPSAMPLE 4 /* text_embedding_average_upsampling=True (dit.py:54-84; needs text_mask_padding) */
+#define F5_OPT_ADAPTERS 8          /* resident LoRA adapters (f5_adapter_*, f5_set_adapter below): f5_finalize keeps the fp32 masters
+                                      of the adaptable tensors.  Not a constructor option of the reference: its counterpart is
+                                      train/train_lora.py's recipe + the merge of infer/utils_infer.py:198-239 */
 
 #define F5_BACKBONE_DIT 0
 #define F5_BACKBONE_UNETT 1
@@ -140,6 +143,48 @@ int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const ui
 /* Pre-sizes the activation arena (otherwise it grows on first use, which calls hipMalloc inside f5_sample).  The plan for
  * max_steps covers both solvers: a midpoint call with steps <= max_steps needs no regrowth. */
 int f5_reserve(f5_engine* e, int32_t max_batch, int32_t max_frames, int32_t max_steps);
+
+/* ------------------------------------------------------------------------------------- resident adapters
+ * One resident base model, many LoRA fine-tunes of it (train/train_lora.py: low-rank pairs on the attention linears of every
+ * DiT block and on input_embed.proj, the text encoder trained in full).  Switching MERGES, as the reference does before it runs
+ * (infer/utils_infer.py:198-239): f5_set_adapter rewrites, in place, the packed GEMM operands of the tensors an adapter
+ * touches, so a forward costs what it cost before and the captured HIP graphs of f5_sample stay valid (no address moves).
+ *
+ * Needs F5_OPT_ADAPTERS in f5_config.options (DiT only): f5_finalize then keeps the fp32 masters of every adaptable tensor in
+ * engine-owned memory (4 * depth * dim * heads * 64 + dim * (2 * mel_dim + text_dim) + the text encoder, in floats: 0.39 GB at
+ * Base size) and builds the device-side descriptor table a switch reads.  Without the bit nothing is kept and
+ * f5_adapter_create / f5_set_adapter fail with F5_ESTATE.
+ *
+ * Adaptable by a low-rank pair (any other name is F5_EINVAL):
+ *   transformer_blocks.<i>.attn.{to_q,to_k,to_v,to_out.0}.weight      input_embed.proj.weight
+ * Replaceable in full: every tensor whose name starts with "text_embed." (table, ConvNeXt-V2 blocks), at the engine's shapes.
+ *
+ * The merge arithmetic is fixed, per element and in fp32, without fused multiply-add:
+ *   acc = 0;  for r = 0 .. rank-1: acc = acc + B[o][r] * A[r][i]   (product rounded, then added; ascending r)
+ *   W'[o][i] = W[o][i] + acc * scale
+ * followed by exactly the conversion f5_finalize applies to a plain weight of the engine's precision (rounding to bf16 / f16,
+ * zero K padding, the hi / lo split of F5_PREC_F16X3 and of F5_PREC_F16P's input layer).  An engine switched to an adapter
+ * therefore holds, bit for bit, the packed weights of a fresh engine loaded with the state dict merged by this rule. */
+typedef struct f5_adapter f5_adapter;
+/* An empty adapter bound to `e` (finalized, F5_OPT_ADAPTERS).  It stays usable until f5_destroy(e) or the next
+ * f5_load_weight / f5_finalize on e (after which every call on it except f5_adapter_destroy fails with F5_ESTATE). */
+int f5_adapter_create(f5_engine* e, f5_adapter** out);
+/* Fails with F5_ESTATE while the adapter is the engine's active one (set another, or NULL, first). */
+int f5_adapter_destroy(f5_adapter* a);
+/* One low-rank pair for the weight `name` [out, in]: A f32[rank, in], B f32[out, rank] (device, contiguous), 1 <= rank <= 128,
+ * any per-pair rank.  The adapter keeps copies (made on `stream`; allocates and synchronises).  A second put of a name
+ * replaces the first.  F5_EINVAL, with a message that names the tensor, for an unknown target, a rank out of range or
+ * mismatching shapes; F5_ESTATE while the adapter is active. */
+int f5_adapter_put_lora(f5_adapter* a, const char* name, const void* A_dev_f32, const int64_t* a_shape, int32_t a_ndim,
+                        const void* B_dev_f32, const int64_t* b_shape, int32_t b_ndim, float scale, f5_stream stream);
+/* One full replacement of the tensor `name` (fp32, device, contiguous; the shape must equal the engine's).  Same rules. */
+int f5_adapter_put_tensor(f5_adapter* a, const char* name, const void* dev_f32, const int64_t* shape, int32_t ndim,
+                          f5_stream stream);
+/* Makes `a` (NULL: the base model) the model the engine computes with: rewrites the packed form of every tensor `a` touches and
+ * restores from the masters every tensor the previously active adapter touched and `a` does not.  Enqueues one kernel launch per
+ * 512 tensors to rewrite on `stream` and nothing else: no allocation, no copy from the host, no synchronisation, no graph
+ * invalidation.  The cached unconditional text embedding is dropped.  Calls that follow on the same stream see the new model. */
+int f5_set_adapter(f5_engine* e, f5_adapter* a, f5_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ Vocos */
 typedef struct f5_vocos_config {

@@ -8,7 +8,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libf5hip.so")
 
-F5_OPT_QK_RMSNORM, F5_OPT_LONG_SKIP, F5_OPT_TEXT_AVG_UPSAMPLE = 1, 2, 4
+F5_OPT_QK_RMSNORM, F5_OPT_LONG_SKIP, F5_OPT_TEXT_AVG_UPSAMPLE, F5_OPT_ADAPTERS = 1, 2, 4, 8
 F5_PREC_F32, F5_PREC_BF16, F5_PREC_F16, F5_PREC_F16X3, F5_PREC_F16P = 0, 1, 2, 3, 4
 PRECISIONS = {"f32": F5_PREC_F32, "fp32": F5_PREC_F32, "bf16": F5_PREC_BF16, "f16": F5_PREC_F16, "fp16": F5_PREC_F16,
               "f16x3": F5_PREC_F16X3, "f16p": F5_PREC_F16P, "parity": F5_PREC_F16P}
@@ -73,6 +73,11 @@ SIGNATURES = {
     "f5_sample": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p]),
     "f5_sample_ode": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_reserve": (_i, [_p, _i, _i, _i]),
+    "f5_adapter_create": (_i, [_p, C.POINTER(_p)]),
+    "f5_adapter_destroy": (_i, [_p]),
+    "f5_adapter_put_lora": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p, C.POINTER(C.c_int64), _i, _f, _p]),
+    "f5_adapter_put_tensor": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),
+    "f5_set_adapter": (_i, [_p, _p, _p]),
     "f5_vocos_create": (_i, [C.POINTER(f5_vocos_config), C.POINTER(_p)]),
     "f5_vocos_destroy": (_i, [_p]),
     "f5_vocos_load_weight": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),

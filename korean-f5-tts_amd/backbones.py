@@ -7,6 +7,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from . import adapters as A
 from . import weights as W
 from .config import normalize_arch
 from .engine import Engine
@@ -35,6 +36,9 @@ class _HipBackbone(nn.Module):
         self._device = torch.device(device) if device is not None else None
         self._sd: dict[str, torch.Tensor] = {}
         self._engine: Engine | None = None
+        self._adapters: dict[str, tuple[dict, dict]] = {}   # name -> ({module: (A, B, scale)}, {name: replacement tensor}), host fp32
+        self._adapter_handles: dict[str, object] = {}       # name -> f5_adapter handle of the current engine
+        self.active_adapter: str | None = None
         self._anchor = nn.Parameter(torch.zeros(1), requires_grad=False)  # lets `.to(device)` / `.device` work
 
     # ---- shapes / state dict -------------------------------------------------------------------------
@@ -61,7 +65,7 @@ class _HipBackbone(nn.Module):
             if k in sd and tuple(sd[k].shape) != tuple(shp):
                 raise RuntimeError(f"{k}: shape {tuple(sd[k].shape)} != {tuple(shp)}")
         self._sd = {k: sd[k].detach().to("cpu", torch.float32) for k in shapes if k in sd}
-        self._engine = None  # re-upload lazily on the current device
+        self._drop_engine()  # re-upload lazily on the current device
         return nn.modules.module._IncompatibleKeys(missing, unexpected)
 
     # ---- engine ----------------------------------------------------------------------------------------
@@ -76,11 +80,77 @@ class _HipBackbone(nn.Module):
         if self._engine is None or self._engine.device != dev:
             if not self._sd:
                 raise RuntimeError("no weights loaded: call load_state_dict() or init_synthetic()")
+            self._drop_engine()
             e = Engine(self.arch, self.text_num_embeds, self.mel_dim, backbone=self.backbone_name,
-                       precision=self.precision, device=dev, max_pos=self.max_pos)
+                       precision=self.precision, device=dev, max_pos=self.max_pos, adapters=bool(self._adapters))
             e.load_state_dict(self._sd)
             self._engine = e
+            for name, (pairs, full) in self._adapters.items():
+                self._adapter_handles[name] = e.new_adapter(pairs, full)
+            if self.active_adapter is not None:
+                e.set_adapter(self._adapter_handles[self.active_adapter])
         return self._engine
+
+    def _drop_engine(self):
+        """Forgets the engine (and the adapter handles that belong to it); the next engine() builds a new one."""
+        self._adapter_handles = {}   # (the Engine frees them with itself)
+        self._engine = None
+
+    # ---- resident LoRA adapters (the interface PEFT users know: add / set / delete) ---------------------------
+    @property
+    def adapters(self) -> list[str]:
+        return list(self._adapters)
+
+    def add_adapter(self, name: str, tensors: dict, *, lora_alpha=32, lora_r=16, alpha_pattern=None, rank_pattern=None):
+        """Registers a LoRA fine-tune of the loaded weights under `name` without activating it.  `tensors`:
+        `<module>.lora_A.weight` [r, in] / `<module>.lora_B.weight` [out, r] for to_q / to_k / to_v / to_out.0 of any DiT
+        block and input_embed.proj (any rank 1 .. 128 per pair), and full replacements of `text_embed.*` tensors under
+        their own names.  A pair's scale is alpha / r with PEFT's alpha_pattern / rank_pattern overrides (the reference's
+        recipe, train/train_lora.py: 32 / 16, and {"input_embed.proj": 128} / {"input_embed.proj": 64}).
+        The first adapter added after the engine was built rebuilds the engine once (it has to keep fp32 masters);
+        later adds upload to the resident engine, and set_adapter() never rebuilds."""
+        if self.backbone_name != "DiT":
+            raise NotImplementedError("resident adapters are built for the DiT backbone only")
+        if name in self._adapters:
+            raise ValueError(f"adapter {name!r} exists: delete_adapter() it first")
+        pairs, full = A.split_adapter_tensors(W.strip_prefixes(tensors))
+        shapes = self.param_shapes()
+        host_pairs = {}
+        for mod, (a, b) in pairs.items():
+            shp = shapes.get(mod + ".weight")
+            if shp is None or tuple(shp) != (b.shape[0], a.shape[1]):
+                raise ValueError(f"{mod}: lora_A {tuple(a.shape)} / lora_B {tuple(b.shape)} do not fit the weight {shp}")
+            host_pairs[mod] = (a.detach().to("cpu", torch.float32), b.detach().to("cpu", torch.float32),
+                               A.pair_scale(mod, lora_alpha, lora_r, alpha_pattern, rank_pattern))
+        for k, v in full.items():
+            if k not in shapes or tuple(shapes[k]) != tuple(v.shape):
+                raise ValueError(f"{k}: shape {tuple(v.shape)} != {shapes.get(k)}")
+        host_full = {k: v.detach().to("cpu", torch.float32) for k, v in full.items()}
+        self._adapters[name] = (host_pairs, host_full)
+        if self._engine is not None:
+            if not self._engine.adapters:
+                self._drop_engine()          # built without F5_OPT_ADAPTERS: rebuilt, once, by the next engine()
+            else:
+                self._adapter_handles[name] = self._engine.new_adapter(host_pairs, host_full)
+
+    def set_adapter(self, name: str | None):
+        """Switches the resident model to adapter `name` (None: the base weights): one kernel launch that rewrites the
+        packed weights in place; captured graphs, the arena and every other weight stay."""
+        if name is not None and name not in self._adapters:
+            raise KeyError(f"no adapter {name!r} (have {self.adapters})")
+        self.active_adapter = name
+        if self._engine is not None and self._engine.adapters:
+            self._engine.set_adapter(None if name is None else self._adapter_handles[name])
+
+    def delete_adapter(self, name: str):
+        if name not in self._adapters:
+            raise KeyError(f"no adapter {name!r} (have {self.adapters})")
+        if name == self.active_adapter:
+            raise RuntimeError(f"adapter {name!r} is active: set_adapter() another one (or None) first")
+        del self._adapters[name]
+        h = self._adapter_handles.pop(name, None)
+        if h is not None and self._engine is not None:
+            self._engine.free_adapter(h)
 
     def clear_cache(self):
         """The reference clears its per-sample() text cache here (dit.py:275-276); the engine keeps no state

@@ -54,7 +54,7 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     if (c->backbone != F5_BACKBONE_DIT && c->backbone != F5_BACKBONE_UNETT) return fail(F5_EINVAL, "bad backbone");
     if (c->backbone == F5_BACKBONE_UNETT && (c->depth % 2)) return fail(F5_EINVAL, "UNetT depth must be even");
     if (c->text_dim > 2048 || c->dim > 2048) return fail(F5_EINVAL, "dims > 2048 unsupported");
-    if (c->options & ~(F5_OPT_QK_RMSNORM | F5_OPT_LONG_SKIP | F5_OPT_TEXT_AVG_UPSAMPLE)) return fail(F5_EINVAL, "unknown option bits %d", c->options);
+    if (c->options & ~(F5_OPT_QK_RMSNORM | F5_OPT_LONG_SKIP | F5_OPT_TEXT_AVG_UPSAMPLE | F5_OPT_ADAPTERS)) return fail(F5_EINVAL, "unknown option bits %d", c->options);
     if (c->options && c->backbone != F5_BACKBONE_DIT) return fail(F5_EINVAL, "F5_OPT_* are options of the DiT backbone (dit.py:160-166)");
     if ((c->options & F5_OPT_TEXT_AVG_UPSAMPLE) && !c->text_mask_padding)
         return fail(F5_EINVAL, "text_embedding_average_upsampling requires text_mask_padding to be True (dit.py:41-42)");
@@ -68,6 +68,11 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     e->io_split = c->precision == F5_PREC_F16P;
     if (e->split16 && getenv("F5_X3_ABLATE")) e->x3_ablate = atoi(getenv("F5_X3_ABLATE"));
     if (getenv("F5_X3_ATTN_SPLIT") && getenv("F5_X3_ATTN_SPLIT")[0] == '1') e->x3_attn_hi = (e->x3_ablate >> 1) & 3;
+    e->adapters_on = (c->options & F5_OPT_ADAPTERS) != 0;
+    if (e->adapters_on && e->x3_ablate) {   // (the ablation zeroes lo halves once, at finalize: a switch would write them back)
+        delete e;
+        return fail(F5_EINVAL, "F5_OPT_ADAPTERS cannot be combined with the F5_X3_ABLATE diagnostic");
+    }
     *out = e;
     return F5_OK;
 }
@@ -84,6 +89,8 @@ extern "C" int f5_load_weight(f5_engine* e, const char* name, const void* dev, c
     e->finalized = false;
     e->uc_N = -1;
     e->clear_graphs();
+    e->active = nullptr;   // the packed weights are about to be rebuilt: adapters made for them are stale
+    e->adapt_gen++;
     return e->ws.put(name, dev, shape, ndim, (hipStream_t)stream);
 }
 extern "C" int f5_finalize(f5_engine* e, f5_stream stream) {
@@ -96,8 +103,24 @@ extern "C" int f5_finalize(f5_engine* e, f5_stream stream) {
     e->pb = Packed<bf16_t>();
     e->ph = Packed<f16_t>();
     e->uc_N = -1;
+    e->targets.clear();
+    e->target_slot.clear();
+    e->base_table = nullptr;
+    e->active = nullptr;
+    e->adapt_gen++;
     int r = F5_OPS(e, finalize(e, s));
     if (r != F5_OK) return r;
+    if (e->adapters_on) {   // F5_OPT_ADAPTERS: the masters of the adaptable tensors stay (engine-owned), and so does the table a switch reads
+        std::vector<MergeDesc> tab;
+        for (auto& t : e->targets) {
+            tab.push_back(t.base);
+            auto it = e->ws.t.find(t.name);
+            e->owned.push_back(it->second.p);
+            e->ws.t.erase(it);
+        }
+        CHK(dev_alloc(e, &e->base_table, tab.size()));
+        HIPCHK(hipMemcpy(e->base_table, tab.data(), tab.size() * sizeof(MergeDesc), hipMemcpyHostToDevice));
+    }
     HIPCHK(hipStreamSynchronize(s));
     // the raw fp32 copies are no longer needed
     for (auto& kv : e->ws.t) {

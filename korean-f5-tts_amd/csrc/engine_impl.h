@@ -100,6 +100,40 @@ static int copy_vec(f5_engine* e, hipStream_t s, const std::string& name, std::i
     return F5_OK;
 }
 
+// F5_OPT_ADAPTERS: records one adaptable tensor as it is packed -- where its fp32 master lives and where (and in which layout) its
+// packed form went -- for f5_adapter_put_* / f5_set_adapter (adapter.hip).  dst1: a second packed copy of the same tensor.
+template <typename T> static int merge_kind(const f5_engine* e) {
+    if constexpr (std::is_same_v<T, float>) return e->split16 ? MK_PLANAR : MK_F32;
+    return std::is_same_v<T, bf16_t> ? MK_BF16 : MK_F16;
+}
+static int reg_target(f5_engine* e, const std::string& name, bool lowrank, int out, int in, int ldw, void* dst0, int kind0,
+                      void* dst1 = nullptr, int kind1 = MK_NONE) {
+    if (!e->adapters_on) return F5_OK;
+    const Tensor* t = e->ws.get(name);
+    if (!t) return fail(F5_ESTATE, "missing weight '%s'", name.c_str());
+    if (kind0 != MK_TAPS && (in % 4 || ldw % 4 || ((kind0 == MK_PLANAR || kind1 == MK_PLANAR) && ldw % 32)))
+        return fail(F5_EINVAL, "F5_OPT_ADAPTERS: '%s' [%d, %d] (row pitch %d) is not made of whole groups of four columns", name.c_str(), out, in, ldw);
+    if (e->targets.size() >= MERGE_TABLE_BIT) return fail(F5_EINVAL, "F5_OPT_ADAPTERS: more than %d adaptable tensors", MERGE_TABLE_BIT);
+    AdaptTarget a;
+    a.name = name;
+    a.shape = t->shape;
+    a.lowrank = lowrank;
+    a.base.W = t->p;
+    a.base.A = a.base.B = nullptr;
+    a.base.dst0 = dst0;
+    a.base.dst1 = dst1;
+    a.base.out = out; a.base.in = in; a.base.ldw = ldw; a.base.rank = 0;
+    a.base.scale = 0.f;
+    a.base.kind0 = kind0; a.base.kind1 = kind1; a.base.pad = 0;
+    e->target_slot[name] = (int)e->targets.size();
+    e->targets.push_back(a);
+    return F5_OK;
+}
+static int reg_linear_f32(f5_engine* e, const std::string& p, const LinW<float>& L, int N, int K) {   // a text-encoder Linear: weight + bias
+    CHK(reg_target(e, p + ".weight", false, N, K, L.ldw, L.w, MK_F32));
+    return reg_target(e, p + ".bias", false, 1, N, N, L.b, MK_F32);
+}
+
 template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStream_t s) {
     const f5_config& c = e->cfg;
     const int D = c.dim, Dt = c.text_dim, F = c.ff_dim, inner = e->inner, mel = c.mel_dim;
@@ -121,6 +155,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     CHK(pack_linear<float>(e, s, "time_embed.time_mlp.2.weight", "time_embed.time_mlp.2.bias", D, D, &P.time2));
     // text encoder
     CHK(copy_vec(e, s, "text_embed.text_embed.weight", {c.text_num_embeds + 1, Dt}, &P.E));
+    CHK(reg_target(e, "text_embed.text_embed.weight", false, c.text_num_embeds + 1, Dt, Dt, P.E, MK_F32));
     if (c.conv_layers > 0) {
         if (!(t = e->ws.get("aux.text_pos")) || t->shape.size() != 2 || t->shape[1] != Dt)
             return fail(F5_ESTATE, "missing/invalid aux.text_pos [P, text_dim]");
@@ -142,6 +177,14 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         CHK(copy_vec(e, s, p + ".grn.beta", {1, 1, 2 * Dt}, &tb.beta));
         CHK(pack_linear<float>(e, s, p + ".pwconv1.weight", p + ".pwconv1.bias", 2 * Dt, Dt, &tb.pw1));
         CHK(pack_linear<float>(e, s, p + ".pwconv2.weight", p + ".pwconv2.bias", Dt, 2 * Dt, &tb.pw2));
+        CHK(reg_target(e, p + ".dwconv.weight", false, Dt, 7, 7, tb.dwk, MK_TAPS));
+        CHK(reg_target(e, p + ".dwconv.bias", false, 1, Dt, Dt, tb.dwb, MK_F32));
+        CHK(reg_target(e, p + ".norm.weight", false, 1, Dt, Dt, tb.lnw, MK_F32));
+        CHK(reg_target(e, p + ".norm.bias", false, 1, Dt, Dt, tb.lnb, MK_F32));
+        CHK(reg_target(e, p + ".grn.gamma", false, 1, 2 * Dt, 2 * Dt, tb.gamma, MK_F32));
+        CHK(reg_target(e, p + ".grn.beta", false, 1, 2 * Dt, 2 * Dt, tb.beta, MK_F32));
+        CHK(reg_linear_f32(e, p + ".pwconv1", tb.pw1, 2 * Dt, Dt));
+        CHK(reg_linear_f32(e, p + ".pwconv2", tb.pw2, Dt, 2 * Dt));
     }
     // input embedding
     CHK(pack_linear_bb<T>(e, s, "input_embed.proj.weight", "input_embed.proj.bias", D, e->kin, &P.in_proj));
@@ -173,6 +216,12 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         const std::string ff = dit ? p + ".ff" : p + ".4";
         CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q", at + ".to_k", at + ".to_v"}, inner, D, &b.qkv));
         CHK(pack_linear_bb<T>(e, s, at + ".to_out.0.weight", at + ".to_out.0.bias", D, inner, &b.out));
+        if (dit) {   // the reference's LoRA targets (train/train_lora.py); q / k / v are row ranges of the fused operand
+            const char* qkv_names[3] = {".to_q.weight", ".to_k.weight", ".to_v.weight"};
+            for (int j = 0; j < 3; ++j)
+                CHK(reg_target(e, at + qkv_names[j], true, inner, D, b.qkv.ldw, b.qkv.w + (size_t)j * inner * b.qkv.ldw, merge_kind<T>(e)));
+            CHK(reg_target(e, at + ".to_out.0.weight", true, D, inner, b.out.ldw, b.out.w, merge_kind<T>(e)));
+        }
         CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &b.ff1));
         CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &b.ff2));
         if constexpr (std::is_same_v<T, float>) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves zeroed) for a class
@@ -251,6 +300,9 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         }
     }
     if (e->x3_ablate & 256) zlo_w(P.proj_out.w, (size_t)P.proj_out.N * P.proj_out.ldw);
+    // (F5_PREC_F16P holds the input projection twice: f16 rows and the split-planar f32 operand the forward reads)
+    CHK(reg_target(e, "input_embed.proj.weight", true, D, e->kin, P.in_proj.ldw, P.in_proj.w, merge_kind<T>(e),
+                   e->io_split ? P.in_proj_f.w : nullptr, e->io_split ? MK_PLANAR : MK_NONE));
     HIPCHK(hipGetLastError());
     return F5_OK;
 }

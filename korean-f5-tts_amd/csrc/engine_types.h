@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "adapter.h"
 #include "attn2.h"
 #include "convpos.h"
 #include "elementwise.h"
@@ -177,6 +178,26 @@ template <typename T> struct Packed {
     int text_pos_rows = 0;
 };
 
+// One adaptable tensor of an engine built with F5_OPT_ADAPTERS (registered by finalize_t as it packs): the state-dict name, the
+// shape a put must match, and the "restore" descriptor -- fp32 master -> packed destination(s) -- an adapter's own descriptor starts from.
+struct AdaptTarget {
+    std::string name;
+    std::vector<int64_t> shape;
+    bool lowrank = false;   // takes a low-rank pair (else: replaceable in full)
+    MergeDesc base{};
+};
+struct f5_adapter {
+    f5_engine* eng = nullptr;     // null once the engine is gone
+    unsigned gen = 0;             // the engine's adapt_gen when the adapter was created (a later f5_finalize makes it stale)
+    MergeDesc* table = nullptr;   // device [targets]: the descriptors of the slots this adapter touches
+    std::map<int, std::vector<void*>> bufs;   // slot -> the device copies (A, B or the replacement tensor) its descriptor points to
+    ~f5_adapter() {
+        for (auto& kv : bufs)
+            for (void* p : kv.second) (void)hipFree(p);
+        if (table) (void)hipFree(table);
+    }
+};
+
 struct f5_engine {
     f5_config cfg{};
     int inner = 0, kin = 0, kin_pad = 0, modN = 0;
@@ -224,6 +245,14 @@ struct f5_engine {
     // (host copies, used for the profiler's FLOP counts only) and the switch (F5_PACK_ROWS, default on)
     std::vector<double> pack_rows_host, pack_sq_host;
     int pack_rows = -1;
+    // resident adapters (F5_OPT_ADAPTERS; adapter.hip)
+    bool adapters_on = false;
+    std::vector<AdaptTarget> targets;
+    std::map<std::string, int> target_slot;
+    MergeDesc* base_table = nullptr;     // device [targets] (in `owned`)
+    f5_adapter* active = nullptr;
+    std::vector<f5_adapter*> adapters;   // every live adapter bound to this engine
+    unsigned adapt_gen = 0;
     void clear_graphs() {
         for (auto& g : graphs) {
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
@@ -233,6 +262,7 @@ struct f5_engine {
         warm.clear();
     }
     ~f5_engine() {
+        for (f5_adapter* a : adapters) a->eng = nullptr;
         clear_graphs();
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
         if (side_stream) (void)hipStreamDestroy(side_stream);

@@ -56,7 +56,7 @@ class Engine:
     """One f5_engine handle bound to one device (one process per GPU; handles are not shared across streams)."""
 
     def __init__(self, arch: dict, text_num_embeds: int, mel_dim: int = 100, *, backbone: str = "DiT",
-                 precision: str = "f16p", device="cuda", max_pos: int = 8192):
+                 precision: str = "f16p", device="cuda", max_pos: int = 8192, adapters: bool = False):
         self.lib = _lib.load()  # raises if the HIP library is not built
         if not torch.cuda.is_available():
             raise _lib.F5Error("no GPU visible: the F5-TTS engine has no CPU path")
@@ -86,16 +86,24 @@ class Engine:
             raise AssertionError("text_embedding_average_upsampling requires text_mask_padding to be True")   # dit.py:41-42
         cfg.options = ((_lib.F5_OPT_QK_RMSNORM if a.get("qk_norm") else 0) | (_lib.F5_OPT_LONG_SKIP if a.get("long_skip_connection") else 0) |
                        (_lib.F5_OPT_TEXT_AVG_UPSAMPLE if a.get("text_embedding_average_upsampling") else 0))
+        # resident LoRA adapters (F5_OPT_ADAPTERS): the engine keeps the fp32 masters of the adaptable tensors
+        if adapters and backbone != "DiT":
+            raise _lib.F5Error("resident adapters are built for the DiT backbone only")
+        self.adapters = bool(adapters)
+        cfg.options |= _lib.F5_OPT_ADAPTERS if adapters else 0
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_create(C.byref(cfg), C.byref(self._h)), "f5_create")
         self.ready = False
+        self._adapter_handles: list = []   # live f5_adapter handles of this engine (freed with it)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
             try:
                 self.lib.f5_destroy(h)
+                for a in getattr(self, "_adapter_handles", []):   # (after the engine: none of them is "active" any more)
+                    self.lib.f5_adapter_destroy(a)
             except Exception:
                 pass
             self._h = None
@@ -119,6 +127,39 @@ class Engine:
     def reserve(self, max_batch: int, max_frames: int, max_steps: int = 32):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_reserve(self._h, max_batch, max_frames, max_steps), "f5_reserve")
+
+    # ------------------------------------------------------------------ resident adapters
+    def new_adapter(self, pairs: dict, full: dict) -> C.c_void_p:
+        """Uploads one adapter: pairs {module: (A [r, in], B [out, r], scale)}, full {name: replacement tensor}.
+        Returns the f5_adapter handle (free_adapter)."""
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            st = _stream_ptr(self.device)
+            _lib.check(self.lib.f5_adapter_create(self._h, C.byref(h)), "f5_adapter_create")
+            try:
+                for mod, (a, b, scale) in pairs.items():
+                    da, db = _dev_f32(a, self.device), _dev_f32(b, self.device)
+                    _lib.check(self.lib.f5_adapter_put_lora(h, (mod + ".weight").encode(), _ptr(da), _lib.shape_array(da.shape), da.dim(),
+                                                            _ptr(db), _lib.shape_array(db.shape), db.dim(), float(scale), st),
+                               f"f5_adapter_put_lora({mod})")
+                for name, t in full.items():
+                    d = _dev_f32(t, self.device)
+                    _lib.check(self.lib.f5_adapter_put_tensor(h, name.encode(), _ptr(d), _lib.shape_array(d.shape), d.dim(), st),
+                               f"f5_adapter_put_tensor({name})")
+            except Exception:
+                self.lib.f5_adapter_destroy(h)
+                raise
+        self._adapter_handles.append(h)
+        return h
+
+    def free_adapter(self, h):
+        _lib.check(self.lib.f5_adapter_destroy(h), "f5_adapter_destroy")
+        self._adapter_handles.remove(h)
+
+    def set_adapter(self, h):
+        """h: a handle of new_adapter, or None for the base model.  One kernel launch on the current stream."""
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.f5_set_adapter(self._h, h, _stream_ptr(self.device)), "f5_set_adapter")
 
     # ------------------------------------------------------------------ compute
     def text_embed(self, text: torch.Tensor, N: int, lens=None, drop_text=False) -> torch.Tensor:

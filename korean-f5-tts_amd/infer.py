@@ -4,6 +4,7 @@
   chunk_text                         utils_infer.py:83-110      text -> chunks of <= max_chars utf-8 bytes
   convert_peft_state_dict_to_plain   utils_infer.py:198-239     PEFT/LoRA keys -> plain weights (W + B A * alpha / r)
   load_checkpoint                    utils_infer.py:242-286     .pt / .safetensors, EMA prefix, legacy mel buffers
+  load_adapter                       (no reference counterpart) a PEFT checkpoint as a RESIDENT adapter of the loaded base
   load_model                         utils_infer.py:292-345     CFM(model_cls(**cfg, text_num_embeds=vocab+1, mel_dim))
   load_vocoder                       utils_infer.py:114-137     local vocos checkpoint only (no network here)
   infer_batch_process / infer_process utils_infer.py:453-778    mono mix, RMS-to-0.1, duration formula, sample(),
@@ -81,6 +82,38 @@ def convert_peft_state_dict_to_plain(state_dict: dict, lora_alpha: float = 32.0,
         else:
             out[k] = v
     return out
+
+
+def _read_checkpoint_state_dict(ckpt_path: str, use_ema: bool) -> dict:
+    """The state dict of a reference checkpoint (utils_infer.py:254-282): .safetensors or .pt, EMA or model weights."""
+    if ckpt_path.split(".")[-1] == "safetensors":
+        from safetensors.torch import load_file
+
+        ckpt = load_file(ckpt_path, device="cpu")
+        ckpt = {"ema_model_state_dict": ckpt} if use_ema else {"model_state_dict": ckpt}
+    else:
+        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
+    if use_ema:
+        sd = {k.replace("ema_model.", ""): v for k, v in ckpt["ema_model_state_dict"].items() if k not in ("initted", "step")}
+        for legacy in ("mel_spec.mel_stft.mel_scale.fb", "mel_spec.mel_stft.spectrogram.window"):
+            sd.pop(legacy, None)
+        return sd
+    return ckpt["model_state_dict"]
+
+
+def load_adapter(model, ckpt_path: str, name: str, use_ema: bool = True, *, lora_alpha=32, lora_r=16, alpha_pattern=None,
+                 rank_pattern=None):
+    """Reads a PEFT / LoRA checkpoint (train/train_lora.py) as adapter `name` of the model's backbone instead of
+    merging it into a second model: the low-rank pairs are kept, the non-LoRA tensors that differ from the loaded base
+    (the text encoder the recipe trains in full) become replacement tensors, equal ones are dropped; a `base_layer` that
+    differs from the base, or a differing tensor that is not replaceable, raises.  Activate with
+    `model.transformer.set_adapter(name)`; `set_adapter(None)` returns to the base."""
+    from .adapters import split_peft_state_dict
+
+    tr = getattr(model, "transformer", model)
+    _, tensors = split_peft_state_dict(_read_checkpoint_state_dict(ckpt_path, use_ema), base=tr.state_dict())
+    tr.add_adapter(name, tensors, lora_alpha=lora_alpha, lora_r=lora_r, alpha_pattern=alpha_pattern, rank_pattern=rank_pattern)
+    return model
 
 
 def load_checkpoint(model, ckpt_path: str, device: str, dtype=None, use_ema: bool = True):
