@@ -28,6 +28,14 @@ template <typename T, bool BB> static int maybe_split_weight(f5_engine* e, hipSt
     }
     return F5_OK;
 }
+// diagnostic F5_X3_ABLATE: a split-planar f32 operand (weights at finalize, a class's A operand in the forward) as plain f16 -- the lo
+// halves of its 32-element blocks zeroed.  Only the float engine has such operands.
+template <typename T> static void zero_lo_planar(hipStream_t s, T* p, size_t elems) {
+    if constexpr (std::is_same_v<T, float>) {
+        const long blocks = (long)(elems / 32);
+        hipLaunchKernelGGL(zero_lo_planar_kernel, dim3(ew_blocks(blocks * 4)), dim3(256), 0, s, p, blocks);
+    }
+}
 // the conv position embedding runs split too where its K blocks stay inside one tap (32 | channels per group: dim 512, 1024)
 static inline bool conv_split(const f5_engine* e) { return e->split16 && convpos_can_split(e->cfg.dim); }
 // every backbone GEMM goes through here (the time / text paths call launch_gemm<float> directly: always plain f32)
@@ -188,11 +196,10 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     }
     // input embedding
     CHK(pack_linear_bb<T>(e, s, "input_embed.proj.weight", "input_embed.proj.bias", D, e->kin, &P.in_proj));
-    auto zlo_w = [&](T* wp, size_t elems) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves of the split layout zeroed)
-        if constexpr (std::is_same_v<T, float>)
-            hipLaunchKernelGGL(zero_lo_planar_kernel, dim3(ew_blocks((long)elems / 8)), dim3(256), 0, s, wp, (long)(elems / 32));
+    auto zlo = [&](int bit, LinW<T>& L) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves zeroed) for a class
+        if (e->x3_ablate & bit) zero_lo_planar(s, L.w, (size_t)L.N * L.ldw);
     };
-    if (e->x3_ablate & 64) zlo_w(P.in_proj.w, (size_t)P.in_proj.N * P.in_proj.ldw);
+    zlo(64, P.in_proj);
     const int cpg = D / 16;
     P.conv_kp = round_up(31 * cpg, GEMM_ROW_BYTES / (int)sizeof(T));   // whole K-tiles, zero padded (convpos.h)
     for (int j = 0; j < 2; ++j) {
@@ -203,7 +210,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         hipLaunchKernelGGL((conv_pack_kernel<T>), dim3(ew_blocks((long)D * P.conv_kp)), dim3(256), 0, s, w->p,
                            P.conv_w[j], (long)D, cpg, 31, P.conv_kp);
         if (conv_split(e)) CHK((maybe_split_weight<T, true>(e, s, P.conv_w[j], (size_t)D * P.conv_kp)));   // F5_PREC_F16X3 (convpos.h SPLIT)
-        if (conv_split(e) && (e->x3_ablate & 128)) zlo_w(P.conv_w[j], (size_t)D * P.conv_kp);
+        if (conv_split(e) && (e->x3_ablate & 128)) zero_lo_planar(s, P.conv_w[j], (size_t)D * P.conv_kp);
         CHK(copy_vec(e, s, p + ".bias", {D}, &P.conv_b[j]));
     }
     // transformer
@@ -224,17 +231,11 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         }
         CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &b.ff1));
         CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &b.ff2));
-        if constexpr (std::is_same_v<T, float>) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves zeroed) for a class
-            auto zlo = [&](LinW<T>& L) {
-                const long blocks = (long)L.N * L.ldw / 32;
-                hipLaunchKernelGGL(zero_lo_planar_kernel, dim3(ew_blocks(blocks * 4)), dim3(256), 0, s, L.w, blocks);
-            };
-            if (e->x3_ablate & 1) zlo(b.qkv);
-            if (e->x3_ablate & 8) zlo(b.out);
-            if (e->x3_ablate & 16) zlo(b.ff1);
-            if (e->x3_ablate & 32) zlo(b.ff2);
-            HIPCHK(hipGetLastError());
-        }
+        zlo(1, b.qkv);
+        zlo(8, b.out);
+        zlo(16, b.ff1);
+        zlo(32, b.ff2);
+        HIPCHK(hipGetLastError());
         if (c.options & F5_OPT_QK_RMSNORM) {
             CHK(copy_vec(e, s, at + ".q_norm.weight", {64}, &b.qn));
             CHK(copy_vec(e, s, at + ".k_norm.weight", {64}, &b.kn));
@@ -246,13 +247,8 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
             CHK(copy_vec(e, s, p + ".3.g", {D}, &b.norm2_g));
             if (i >= c.depth / 2 && e->ws.get(p + ".0.weight")) {
                 CHK(pack_linear_bb<T>(e, s, p + ".0.weight", "", D, 2 * D, &b.skip));
-                if constexpr (std::is_same_v<T, float>) {
-                    if (e->x3_ablate & 512) {   // diagnostic: the skip projection with plain f16 weights
-                        const long blocks = (long)b.skip.N * b.skip.ldw / 32;
-                        hipLaunchKernelGGL(zero_lo_planar_kernel, dim3(ew_blocks(blocks * 4)), dim3(256), 0, s, b.skip.w, blocks);
-                        HIPCHK(hipGetLastError());
-                    }
-                }
+                zlo(512, b.skip);   // diagnostic: the skip projection with plain f16 weights
+                HIPCHK(hipGetLastError());
             }
         }
     }
@@ -299,7 +295,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
             if (convpos_can_split(D)) CHK((maybe_split_weight<float, true>(e, s, P.conv_w_f[j], (size_t)D * P.conv_kp_f)));
         }
     }
-    if (e->x3_ablate & 256) zlo_w(P.proj_out.w, (size_t)P.proj_out.N * P.proj_out.ldw);
+    zlo(256, P.proj_out);
     // (F5_PREC_F16P holds the input projection twice: f16 rows and the split-planar f32 operand the forward reads)
     CHK(reg_target(e, "input_embed.proj.weight", true, D, e->kin, P.in_proj.ldw, P.in_proj.w, merge_kind<T>(e),
                    e->io_split ? P.in_proj_f.w : nullptr, e->io_split ? MK_PLANAR : MK_NONE));
@@ -379,20 +375,20 @@ template <> inline Packed<f16_t>& packed<f16_t>(f5_engine* e) { return e->ph; }
 template <typename T> static int run_time_path(f5_engine* e, Work<T>& w, int S, hipStream_t s) {
     Packed<T>& P = packed<T>(e);
     const int D = e->cfg.dim;
-    e->prof.begin(PC_TIME, s);
-    hipLaunchKernelGGL(time_sinus_kernel, dim3((S * 128 + 255) / 256), dim3(256), 0, s, w.tdev, P.time_freqs, w.feat, S, 128);
-    KCHK();
-    HIPCHK(launch_gemm<float>(s, w.feat, 256, P.time0.w, P.time0.ldw, S, D, 256,
-                              EpiStore<float>{w.th, D, P.time0.b, F5_ACT_SILU}));
-    HIPCHK(launch_gemm<float>(s, w.th, D, P.time2.w, P.time2.ldw, S, D, D, EpiStore<float>{w.temb, D, P.time2.b, F5_ACT_NONE}));
-    if (e->cfg.backbone == F5_BACKBONE_DIT) {
-        hipLaunchKernelGGL(act_kernel, dim3(ew_blocks((long)S * D)), dim3(256), 0, s, w.temb, w.st, (long)S * D, F5_ACT_SILU);
+    return e->prof.timed(PC_TIME, s, [&]() -> int {
+        hipLaunchKernelGGL(time_sinus_kernel, dim3((S * 128 + 255) / 256), dim3(256), 0, s, w.tdev, P.time_freqs, w.feat, S, 128);
         KCHK();
-        HIPCHK(launch_gemm<float>(s, w.st, D, P.mod.w, P.mod.ldw, S, e->modN, D,
-                                  EpiStore<float>{w.mod, e->modN, P.mod.b, F5_ACT_NONE}));
-    }
-    e->prof.end(s);
-    return F5_OK;
+        HIPCHK(launch_gemm<float>(s, w.feat, 256, P.time0.w, P.time0.ldw, S, D, 256,
+                                  EpiStore<float>{w.th, D, P.time0.b, F5_ACT_SILU}));
+        HIPCHK(launch_gemm<float>(s, w.th, D, P.time2.w, P.time2.ldw, S, D, D, EpiStore<float>{w.temb, D, P.time2.b, F5_ACT_NONE}));
+        if (e->cfg.backbone == F5_BACKBONE_DIT) {
+            hipLaunchKernelGGL(act_kernel, dim3(ew_blocks((long)S * D)), dim3(256), 0, s, w.temb, w.st, (long)S * D, F5_ACT_SILU);
+            KCHK();
+            HIPCHK(launch_gemm<float>(s, w.st, D, P.mod.w, P.mod.ldw, S, e->modN, D,
+                                      EpiStore<float>{w.mod, e->modN, P.mod.b, F5_ACT_NONE}));
+        }
+        return F5_OK;
+    });
 }
 
 // text ids -> text embedding [B, N, Dt] (dit.py:86-115 + per-sample lengths dit.py:247-258)
@@ -404,51 +400,202 @@ static int run_text_embed(f5_engine* e, Work<T>& w, const int64_t* text, int B, 
     const int Dt = c.text_dim;
     const bool dit = c.backbone == F5_BACKBONE_DIT;
     const long rows = (long)B * N;
-    e->prof.begin(PC_TEXT, s);
     if (c.conv_layers > 0 && dit && N > P.text_pos_rows) return fail(F5_EINVAL, "N=%d exceeds aux.text_pos rows", N);
-    float* cur = c.conv_layers > 0 ? w.tx_a : out;  // block input/output (updated in place); last block writes `out`
-    const int pos_rows = P.text_pos_rows > 0 ? P.text_pos_rows : 1;
-    hipLaunchKernelGGL(text_embed_kernel, dim3(ew_blocks(rows * Dt / 4)), dim3(256), 0, s, (const long long*)text, nt, P.E,
-                       P.text_pos, cur, B, N, Dt, lens_dev, drop_text, c.text_mask_padding && c.conv_layers > 0,
-                       c.conv_layers > 0, dit ? 1 << 30 : pos_rows);
-    KCHK();
-    for (int i = 0; i < c.conv_layers; ++i) {
-        TextBlockW& tb = P.tblocks[i];
-        float* nxt = (i == c.conv_layers - 1) ? out : cur;
-        hipLaunchKernelGGL(dwconv7_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, cur, w.tx_b, tb.dwk, tb.dwb, tb.lnw,
-                           tb.lnb, B, N, Dt, lens_dev, 1e-6f);
+    return e->prof.timed(PC_TEXT, s, [&]() -> int {
+        float* cur = c.conv_layers > 0 ? w.tx_a : out;  // block input/output (updated in place); last block writes `out`
+        const int pos_rows = P.text_pos_rows > 0 ? P.text_pos_rows : 1;
+        hipLaunchKernelGGL(text_embed_kernel, dim3(ew_blocks(rows * Dt / 4)), dim3(256), 0, s, (const long long*)text, nt, P.E,
+                           P.text_pos, cur, B, N, Dt, lens_dev, drop_text, c.text_mask_padding && c.conv_layers > 0,
+                           c.conv_layers > 0, dit ? 1 << 30 : pos_rows);
         KCHK();
-        HIPCHK(launch_gemm<float>(s, w.tx_b, Dt, tb.pw1.w, tb.pw1.ldw, (int)rows, 2 * Dt, Dt,
-                                  EpiStore<float>{w.tx_h1, 2 * Dt, tb.pw1.b, F5_ACT_GELU_ERF}));
-        hipLaunchKernelGGL(grn_partial_kernel, dim3((2 * Dt + 255) / 256, GRN_P, B), dim3(256), 0, s, w.tx_h1, w.grn_part,
-                           N, 2 * Dt, lens_dev);
-        KCHK();
-        const int rpb = 16;
-        hipLaunchKernelGGL(grn_apply_kernel, dim3((N + rpb - 1) / rpb, B), dim3(256), (2 * Dt + 8) * sizeof(float), s,
-                           w.tx_h1, w.grn_part, tb.gamma, tb.beta, N, 2 * Dt, lens_dev, rpb);
-        KCHK();
-        // residual add: nxt = cur + pwconv2(h1)
-        HIPCHK(launch_gemm<float>(s, w.tx_h1, 2 * Dt, tb.pw2.w, tb.pw2.ldw, (int)rows, Dt, 2 * Dt,
-                                  EpiGateRes{nxt, cur, Dt, tb.pw2.b, nullptr, 0, N, nullptr}));
-        if (c.text_mask_padding) {
-            hipLaunchKernelGGL(zero_filler_rows_kernel, dim3(ew_blocks(rows * Dt / 4)), dim3(256), 0, s,
-                               (const long long*)text, nt, nxt, B, N, Dt);
+        for (int i = 0; i < c.conv_layers; ++i) {
+            TextBlockW& tb = P.tblocks[i];
+            float* nxt = (i == c.conv_layers - 1) ? out : cur;
+            hipLaunchKernelGGL(dwconv7_ln_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, cur, w.tx_b, tb.dwk, tb.dwb, tb.lnw,
+                               tb.lnb, B, N, Dt, lens_dev, 1e-6f);
+            KCHK();
+            HIPCHK(launch_gemm<float>(s, w.tx_b, Dt, tb.pw1.w, tb.pw1.ldw, (int)rows, 2 * Dt, Dt,
+                                      EpiStore<float>{w.tx_h1, 2 * Dt, tb.pw1.b, F5_ACT_GELU_ERF}));
+            hipLaunchKernelGGL(grn_partial_kernel, dim3((2 * Dt + 255) / 256, GRN_P, B), dim3(256), 0, s, w.tx_h1, w.grn_part,
+                               N, 2 * Dt, lens_dev);
+            KCHK();
+            const int rpb = 16;
+            hipLaunchKernelGGL(grn_apply_kernel, dim3((N + rpb - 1) / rpb, B), dim3(256), (2 * Dt + 8) * sizeof(float), s,
+                               w.tx_h1, w.grn_part, tb.gamma, tb.beta, N, 2 * Dt, lens_dev, rpb);
+            KCHK();
+            // residual add: nxt = cur + pwconv2(h1)
+            HIPCHK(launch_gemm<float>(s, w.tx_h1, 2 * Dt, tb.pw2.w, tb.pw2.ldw, (int)rows, Dt, 2 * Dt,
+                                      EpiGateRes{nxt, cur, Dt, tb.pw2.b, nullptr, 0, N, nullptr}));
+            if (c.text_mask_padding) {
+                hipLaunchKernelGGL(zero_filler_rows_kernel, dim3(ew_blocks(rows * Dt / 4)), dim3(256), 0, s,
+                                   (const long long*)text, nt, nxt, B, N, Dt);
+                KCHK();
+            }
+            cur = nxt;
+        }
+        if (lens_dev && c.conv_layers > 0) {
+            hipLaunchKernelGGL(zero_tail_rows_kernel, dim3(ew_blocks(rows * Dt / 4)), dim3(256), 0, s, out, B, N, Dt, lens_dev);
             KCHK();
         }
-        cur = nxt;
+        if (c.options & F5_OPT_TEXT_AVG_UPSAMPLE) {   // dit.py:112-113: after the text blocks; the mask is that of the ORIGINAL ids
+            hipLaunchKernelGGL(text_avg_upsample_kernel, dim3(B), dim3(256), (size_t)N * sizeof(int), s, (const long long*)text, nt, out, w.tx_b, N, Dt,
+                               lens_dev);
+            KCHK();
+            HIPCHK(hipMemcpyAsync(out, w.tx_b, (size_t)rows * Dt * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        return F5_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------------- stages shared by both backbones
+// What the stages of one forward share: the engine, the stream, the geometry and (DiT) the tables of a packed batch.
+struct FwdCtx {
+    f5_engine* e;
+    hipStream_t s;
+    int B, Bp, N, rows;    // N: tokens per batch row (UNetT blocks: the frames + the time token); rows = Bp * N: launch geometry, the padded batch
+    const int* lens_dev;   // per-batch-row lengths, or null
+    RowPack pk;            // packed variable-length batch (rows present = *pk.rows_dev); empty: the padded batch as it is
+    const int* ml() const { return pk.rows_dev; }              // device row count of a packed batch, or null
+    int mh() const { return pk ? (int)pk.rows_host : 0; }      // rows expected (the call's own lengths): tile choice only
+    int pl() const { return e->split16 ? 1 : 0; }              // F5_PREC_F16X3: xn / ao / ffh are written pre-split (the A operands of the block GEMMs)
+    double gflops(double n, double k) const { return 2.0 * (pk ? pk.rows_host : (double)rows) * n * k; }
+    // one backbone GEMM over all rows, as a profiled launch
+    template <typename T, typename Epi> int gemm(const T* A, int lda, const LinW<T>& L, int n, int k, const Epi& epi, bool a_planar = false) const {
+        HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] { return egemm<T>(e, s, A, lda, L.w, L.ldw, rows, n, k, epi, -1, ml(), mh(), a_planar); }));
+        return F5_OK;
     }
-    if (lens_dev && c.conv_layers > 0) {
-        hipLaunchKernelGGL(zero_tail_rows_kernel, dim3(ew_blocks(rows * Dt / 4)), dim3(256), 0, s, out, B, N, Dt, lens_dev);
-        KCHK();
+    // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed)
+    template <typename T> void ablate(int bit, T* a, int k) const {
+        if (e->x3_ablate & bit) zero_lo_planar(s, a, (size_t)rows * k);
     }
-    if (c.options & F5_OPT_TEXT_AVG_UPSAMPLE) {   // dit.py:112-113: after the text blocks; the mask is that of the ORIGINAL ids
-        hipLaunchKernelGGL(text_avg_upsample_kernel, dim3(B), dim3(256), (size_t)N * sizeof(int), s, (const long long*)text, nt, out, w.tx_b, N, Dt,
-                           lens_dev);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(out, w.tx_b, (size_t)rows * Dt * sizeof(float), hipMemcpyDeviceToDevice, s));
+};
+
+// Input embedding: [y, cond, text] packed as rows of U, the input projection, and the conv position embedding (two grouped convs, the second
+// with the projection as its residual) into dst.  U = T, or (F5_PREC_F16P, e->io_split) float: the rows packed as f32, input projection and
+// convs as split-f16 products on f32 operands (what the f16 blocks then see is x, the f32 residual stream, exactly as in F5_PREC_F16X3).
+// ablate: diagnostic F5_X3_ABLATE bits 64 / 128 on the activation side -- the unsplit f32 operands as f16 sees them (the DiT only).
+template <typename T, typename U>
+static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float* cond, int drop_cond_first, const float* text_first,
+                       const float* text_second, float* dst, bool ablate = false) {
+    f5_engine* e = f.e;
+    hipStream_t s = f.s;
+    Packed<T>& P = packed<T>(e);
+    Prof& pr = e->prof;
+    const f5_config& c = e->cfg;
+    const int D = c.dim, rows = f.rows, B = f.B, Bp = f.Bp, N = f.N;
+    const RowPack& pk = f.pk;
+    U* acat = reinterpret_cast<U*>(w.acat);
+    const LinW<U>* ip;
+    U* const* cw;
+    int kp;
+    bool cs;
+    if constexpr (std::is_same_v<U, T>) {
+        ip = &P.in_proj; cw = P.conv_w; kp = P.conv_kp; cs = conv_split(e);
+    } else {
+        ip = &P.in_proj_f; cw = P.conv_w_f; kp = P.conv_kp_f; cs = convpos_can_split(D);
     }
-    e->prof.end(s);
+    HIPCHK(pr.timed(PC_MISC, s, [&] {
+        hipLaunchKernelGGL((pack_input_kernel<U>), dim3(ew_blocks((long)rows * e->kin / 4)), dim3(256), 0, s, y, cond, text_first, text_second,
+                           acat, e->kin_pad, B, Bp, N, c.mel_dim, c.text_dim, drop_cond_first, pk.rowmap, f.ml(), f.lens_dev);
+        return hipGetLastError();
+    }));
+    auto ablate_round = [&](int bit, const float* src, float* to, long n) -> const float* {   // diagnostic F5_X3_ABLATE: an unsplit f32 operand as f16 sees it
+        if (!ablate || !(e->x3_ablate & bit)) return src;
+        hipLaunchKernelGGL(round_f16_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, src, to, n);
+        return to;
+    };
+    if constexpr (std::is_same_v<U, float>) ablate_round(64, acat, acat, (long)rows * e->kin_pad);
+    HIPCHK(pr.timed(PC_GEMM, s, f.gflops(D, e->kin), [&] {
+        const EpiStore<float> epi{w.h, D, ip->b, F5_ACT_NONE};
+        if constexpr (std::is_same_v<U, T>) return egemm<T>(e, s, acat, e->kin_pad, ip->w, ip->ldw, rows, D, e->kin_pad, epi, -1, f.ml(), f.mh());
+        else return launch_gemm<float>(s, acat, e->kin_pad, ip->w, ip->ldw, rows, D, e->kin_pad, epi, -1, f.ml(), f.mh(), GemmConv{}, 1);
+    }));
+    const double conv_fl = f.gflops(D, (D / 16) * 31);
+    HIPCHK(pr.timed(PC_CONV, s, conv_fl, [&] {
+        // (ablation: conv 1 reads a rounded COPY of h -- w.x is free until conv 2 writes it -- because h itself is conv 2's f32 residual)
+        const float* conv1_in = ablate_round(128, w.h, w.x, (long)rows * D);
+        return launch_convpos<U>(s, conv1_in, cw[0], kp, P.conv_b[0], nullptr, w.c1, Bp, N, D, f.lens_dev, B, pk.row_start, cs);
+    }));
+    ablate_round(128, w.c1, w.c1, (long)rows * D);
+    HIPCHK(pr.timed(PC_CONV, s, conv_fl, [&] {
+        return launch_convpos<U>(s, w.c1, cw[1], kp, P.conv_b[1], w.h, dst, Bp, N, D, f.lens_dev, B, pk.row_start, cs);
+    }));
     return F5_OK;
+}
+
+// Attention sub-block on the normed stream w.xn: QKV projection, attention, out-projection with the caller's residual epilogue.
+template <typename T>
+static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, bool qk_norm, const EpiGateRes& out_epi) {
+    f5_engine* e = f.e;
+    hipStream_t s = f.s;
+    Packed<T>& P = packed<T>(e);
+    Prof& pr = e->prof;
+    const f5_config& c = e->cfg;
+    const int D = c.dim, inner = e->inner, H = c.heads, B = f.B, Bp = f.Bp, N = f.N, pl = f.pl();
+    const RowPack& pk = f.pk;
+    const int pe_heads = c.pe_attn_head < 0 ? H : c.pe_attn_head;
+    const int* attn_lens = (c.attn_mask_enabled && f.lens_dev) ? f.lens_dev : nullptr;
+    const double attn_fl = 4.0 * H * 64 * (pk ? pk.sq_host : (double)Bp * N * N);
+    f.ablate(1, w.xn, D);
+    // F5_PREC_F16X3 with plain-f16 attention products (x3_attn_hi == 3): q / k / v^T leave the QKV epilogue as f16 and the fast
+    // 16-bit attention kernel writes its output pre-split for the out-projection (the f32 buffers are reused at half their size)
+    bool attn16 = false;
+    if constexpr (std::is_same_v<T, float>) {
+        attn16 = e->split16 && e->x3_attn_hi == 3 && !qk_norm;
+        if (attn16) {
+            f16_t *q = reinterpret_cast<f16_t*>(w.q), *k = reinterpret_cast<f16_t*>(w.k), *vt = reinterpret_cast<f16_t*>(w.vt);
+            CHK(f.gemm(w.xn, D, bw.qkv, 3 * inner, D,
+                       EpiQKV<f16_t>{q, k, vt, bw.qkv.b, P.rope_frag, N, w.Npad, H, pe_heads, attention_q_scale<f16_t>(), pk.rowmap}, pl));
+            HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
+                return launch_attention_v2<f16_t>(s, q, k, vt, nullptr, Bp, H, N, w.Npad, attn_lens, B, f.lens_dev, pk.row_start, w.ao);
+            }));
+        }
+    }
+    if (!attn16) {
+        CHK(f.gemm(w.xn, D, bw.qkv, 3 * inner, D,
+                   EpiQKV<T>{w.q, w.k, w.vt, bw.qkv.b, P.rope_frag, N, w.Npad, H, qk_norm ? 0 : pe_heads,
+                             qk_norm ? 1.0f : attention_q_scale<T>(), pk.rowmap}, pl));
+        if (qk_norm) {   // RMSNorm on q / k comes BEFORE the rotary embedding (modules.py:481-497): the epilogue left both raw
+            const long qrows = (long)Bp * H * N;
+            HIPCHK(pr.timed(PC_MISC, s, [&] {
+                hipLaunchKernelGGL((qknorm_rope_kernel<T>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, w.q, w.k, bw.qn, bw.kn,
+                                   P.rope_cos, P.rope_sin, qrows, N, H, pe_heads, attention_q_scale<T>(), 1e-6f);
+                return hipGetLastError();
+            }));
+        }
+        HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
+            return launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, N, w.Npad, attn_lens, B, f.lens_dev, pk.row_start, e->split16, pl,
+                                        e->x3_attn_hi);
+        }));
+    }
+    f.ablate(8, w.ao, inner);
+    return f.gemm(w.ao, inner, bw.out, D, inner, out_epi, pl);
+}
+
+// Feed-forward pair on the normed stream w.xn: FF1 with GELU(tanh), FF2 with the caller's residual epilogue.
+template <typename T> static int ff_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, const EpiGateRes& out_epi) {
+    const int D = f.e->cfg.dim, F = f.e->cfg.ff_dim, pl = f.pl();
+    f.ablate(16, w.xn, D);
+    CHK(f.gemm(w.xn, D, bw.ff1, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl}, pl));
+    f.ablate(32, w.ffh, F);
+    return f.gemm(w.ffh, F, bw.ff2, D, F, out_epi, pl);
+}
+
+// Output projection of the normed stream xn into pred.  U = T: w.xn as the final norm left it; U = float (F5_PREC_F16P): pre-split f32
+// rows, as a product of two pre-split operands.
+template <typename T, typename U> static int project_out(const FwdCtx& f, const U* xn, float* pred) {
+    f5_engine* e = f.e;
+    Packed<T>& P = packed<T>(e);
+    const int D = e->cfg.dim, mel = e->cfg.mel_dim;
+    if constexpr (std::is_same_v<U, T>) {
+        return f.gemm(xn, D, P.proj_out, mel, D, EpiStore<float>{pred, mel, P.proj_out.b, F5_ACT_NONE}, f.pl());
+    } else {
+        HIPCHK(e->prof.timed(PC_GEMM, f.s, f.gflops(mel, D), [&] {
+            return launch_gemm<float>(f.s, xn, D, P.proj_out_f.w, P.proj_out_f.ldw, f.rows, mel, D,
+                                      EpiStore<float>{pred, mel, P.proj_out_f.b, F5_ACT_NONE}, -1, f.ml(), f.mh(), GemmConv{}, 2);
+        }));
+        return F5_OK;
+    }
 }
 
 // One DiT forward over Bp packed rows (dit.py:297-327).  mod_row: AdaLN vectors of this step; mod_stride: distance
@@ -459,197 +606,68 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
                            const float* text_first, const float* text_second, hipStream_t s, const RowPack& pk = RowPack{}) {
     Packed<T>& P = packed<T>(e);
     const f5_config& c = e->cfg;
-    const int D = c.dim, F = c.ff_dim, inner = e->inner, mel = c.mel_dim, H = c.heads;
-    const int rows = Bp * N;                        // launch geometry: the padded batch (pk: rows present = *pk.rows_dev)
-    const int* ml = pk.rows_dev;                    // device row count of a packed batch, or null
-    const int mh = pk ? (int)pk.rows_host : 0;      // rows expected (the call's own lengths): tile choice only
+    const int D = c.dim, rows = Bp * N;
+    const FwdCtx f{e, s, B, Bp, N, rows, lens_dev, pk};
+    const int* ml = f.ml();
+    const int mh = f.mh(), pl = f.pl();
     const int* gate_lens = pk ? nullptr : lens_dev; // (a packed batch has no padded rows to leave untouched)
     Prof& pr = e->prof;
-    const double rows_fl = pk ? pk.rows_host : (double)rows;
-    auto gflops = [&](double n, double k) { return 2.0 * rows_fl * n * k; };
-    const double conv_fl = 2.0 * rows_fl * D * (D / 16) * 31;
-    if (e->io_split) {
-        // F5_PREC_F16P: [y, cond, text] packed as f32 rows; input projection and conv position embedding as split-f16 products on f32
-        // operands (what the f16 blocks then see is x, the f32 residual stream, exactly as in F5_PREC_F16X3)
-        float* acat_f = reinterpret_cast<float*>(w.acat);
-        pr.begin(PC_MISC, s);
-        hipLaunchKernelGGL((pack_input_kernel<float>), dim3(ew_blocks((long)rows * e->kin / 4)), dim3(256), 0, s, y, cond,
-                           text_first, text_second, acat_f, e->kin_pad, B, Bp, N, mel, c.text_dim, drop_cond_first, pk.rowmap, ml,
-                           lens_dev);
-        KCHK();
-        pr.end(s);
-        pr.begin(PC_GEMM, s, gflops(D, e->kin));
-        HIPCHK(launch_gemm<float>(s, acat_f, e->kin_pad, P.in_proj_f.w, P.in_proj_f.ldw, rows, D, e->kin_pad,
-                                  EpiStore<float>{w.h, D, P.in_proj_f.b, F5_ACT_NONE}, -1, ml, mh, GemmConv{}, 1));
-        pr.end(s);
-        const bool cs = convpos_can_split(D);
-        pr.begin(PC_CONV, s, conv_fl);
-        HIPCHK(launch_convpos<float>(s, w.h, P.conv_w_f[0], P.conv_kp_f, P.conv_b[0], nullptr, w.c1, Bp, N, D, lens_dev, B, pk.row_start, cs));
-        pr.end(s);
-        pr.begin(PC_CONV, s, conv_fl);
-        HIPCHK(launch_convpos<float>(s, w.c1, P.conv_w_f[1], P.conv_kp_f, P.conv_b[1], w.h, w.x, Bp, N, D, lens_dev, B, pk.row_start, cs));
-        pr.end(s);
-    } else {
-    // input embedding
-    pr.begin(PC_MISC, s);
-    hipLaunchKernelGGL((pack_input_kernel<T>), dim3(ew_blocks((long)rows * e->kin / 4)), dim3(256), 0, s, y, cond,
-                       text_first, text_second, w.acat, e->kin_pad, B, Bp, N, mel, c.text_dim, drop_cond_first, pk.rowmap, ml,
-                       lens_dev);
-    KCHK();
-    pr.end(s);
-    auto ablate_round = [&](int bit, const float* src, float* dst, long n) -> const float* {   // diagnostic F5_X3_ABLATE: an unsplit f32 operand as f16 sees it
-        if (!(e->x3_ablate & bit)) return src;
-        hipLaunchKernelGGL(round_f16_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, src, dst, n);
-        return dst;
-    };
-    if constexpr (std::is_same_v<T, float>) ablate_round(64, w.acat, w.acat, (long)rows * e->kin_pad);
-    pr.begin(PC_GEMM, s, gflops(D, e->kin));
-    HIPCHK(egemm<T>(e, s, w.acat, e->kin_pad, P.in_proj.w, P.in_proj.ldw, rows, D, e->kin_pad,
-                          EpiStore<float>{w.h, D, P.in_proj.b, F5_ACT_NONE}, -1, ml, mh));
-    pr.end(s);
-    pr.begin(PC_CONV, s, conv_fl);
-    // (ablation: conv 1 reads a rounded COPY of h -- w.x is free until conv 2 writes it -- because h itself is conv 2's f32 residual)
-    const float* conv1_in = ablate_round(128, w.h, w.x, (long)rows * D);
-    HIPCHK(launch_convpos<T>(s, conv1_in, P.conv_w[0], P.conv_kp, P.conv_b[0], nullptr, w.c1, Bp, N, D, lens_dev, B, pk.row_start, conv_split(e)));
-    pr.end(s);
-    ablate_round(128, w.c1, w.c1, (long)rows * D);
-    pr.begin(PC_CONV, s, conv_fl);
-    HIPCHK(launch_convpos<T>(s, w.c1, P.conv_w[1], P.conv_kp, P.conv_b[1], w.h, w.x, Bp, N, D, lens_dev, B, pk.row_start, conv_split(e)));
-    pr.end(s);
-    }
+    if (e->io_split) CHK((embed_input<T, float>(f, w, y, cond, drop_cond_first, text_first, text_second, w.x)));
+    else CHK((embed_input<T, T>(f, w, y, cond, drop_cond_first, text_first, text_second, w.x, true)));
     const bool long_skip = (c.options & F5_OPT_LONG_SKIP) != 0;
     if (long_skip)   // residual = x (dit.py:313-314); h is free once the conv embedding has used it as its own residual
         HIPCHK(hipMemcpyAsync(w.h, w.x, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     const bool qk_norm = (c.options & F5_OPT_QK_RMSNORM) != 0;
-    const int pe_heads = c.pe_attn_head < 0 ? H : c.pe_attn_head;
-    const int* attn_lens = (c.attn_mask_enabled && lens_dev) ? lens_dev : nullptr;
-    const int pl = e->split16 ? 1 : 0;   // F5_PREC_F16X3: xn / ao / ffh are written pre-split (the A operands of the block GEMMs)
-    auto ablate_a = [&](int bit, T* a, int k) {   // diagnostic F5_X3_ABLATE: the class's A operand as plain f16 (lo halves zeroed)
-        if constexpr (std::is_same_v<T, float>) {
-            if (e->x3_ablate & bit) {
-                const long blocks = (long)rows * k / 32;
-                hipLaunchKernelGGL(zero_lo_planar_kernel, dim3(ew_blocks(blocks * 4)), dim3(256), 0, s, a, blocks);
-            }
-        }
-    };
     // weight prefetch from the LayerNorm launches (see layernorm_kernel): only where the GEMMs are latency-bound
     const bool wpf = rows <= 4096 && !(getenv("F5_WEIGHT_PREFETCH") && getenv("F5_WEIGHT_PREFETCH")[0] == '0');
+    auto prefetch = [&](const LinW<T>& a, const LinW<T>& b) {   // the weights of the two GEMMs behind a LayerNorm
+        return wpf ? Prefetch{(const char*)a.w, (size_t)a.N * a.ldw * sizeof(T), (const char*)b.w, (size_t)b.N * b.ldw * sizeof(T)} : Prefetch{};
+    };
+    // AdaLN LayerNorm of the stream into out (rows of T, or pre-split f32 rows): out = LN(x) * (1 + scale) + shift
+    auto adaln = [&](auto* out, const float* scale, const float* shift, const Prefetch& pf, int planar) {
+        using TO = std::remove_pointer_t<decltype(out)>;
+        return pr.timed(PC_LN, s, [&] {
+            hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, out, D, rows, D, 1e-6f, scale, shift,
+                               mod_stride, N, 1, pf, ml, planar);
+            return hipGetLastError();
+        });
+    };
     for (int l = 0; l < c.depth; ++l) {
         BlockW<T>& bw = P.blocks[l];
         const float* m = mod_row + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        pr.begin(PC_LN, s);
-        hipLaunchKernelGGL((layernorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, w.xn, D, rows, D, 1e-6f,
-                           m + D, m, mod_stride, N, 1,
-                           wpf ? Prefetch{(const char*)bw.qkv.w, (size_t)3 * inner * bw.qkv.ldw * sizeof(T),
-                                          (const char*)bw.out.w, (size_t)D * bw.out.ldw * sizeof(T)} : Prefetch{}, ml, pl);
-        KCHK();
-        pr.end(s);
-        ablate_a(1, w.xn, D);
-        pr.begin(PC_GEMM, s, gflops(3 * inner, D));
-        // F5_PREC_F16X3 with plain-f16 attention products (x3_attn_hi == 3): q / k / v^T leave the QKV epilogue as f16 and the fast
-        // 16-bit attention kernel writes its output pre-split for the out-projection (the f32 buffers are reused at half their size)
-        bool attn16 = false;
-        if constexpr (std::is_same_v<T, float>) {
-            attn16 = e->split16 && e->x3_attn_hi == 3 && !qk_norm;
-            if (attn16)
-                HIPCHK(egemm<T>(e, s, w.xn, D, bw.qkv.w, bw.qkv.ldw, rows, 3 * inner, D,
-                                EpiQKV<f16_t>{reinterpret_cast<f16_t*>(w.q), reinterpret_cast<f16_t*>(w.k), reinterpret_cast<f16_t*>(w.vt),
-                                              bw.qkv.b, P.rope_frag, N, w.Npad, H, pe_heads, attention_q_scale<f16_t>(), pk.rowmap},
-                                -1, ml, mh, pl));
-        }
-        if (!attn16) {
-        HIPCHK(egemm<T>(e, s, w.xn, D, bw.qkv.w, bw.qkv.ldw, rows, 3 * inner, D,
-                              EpiQKV<T>{w.q, w.k, w.vt, bw.qkv.b, P.rope_frag, N, w.Npad, H, qk_norm ? 0 : pe_heads,
-                                        qk_norm ? 1.0f : attention_q_scale<T>(), pk.rowmap},
-                              -1, ml, mh, pl));
-        }
-        pr.end(s);
-        if (qk_norm) {   // RMSNorm on q / k comes BEFORE the rotary embedding (modules.py:481-497): the epilogue left both raw
-            const long qrows = (long)Bp * H * N;
-            pr.begin(PC_MISC, s);
-            hipLaunchKernelGGL((qknorm_rope_kernel<T>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, w.q, w.k, bw.qn, bw.kn,
-                               P.rope_cos, P.rope_sin, qrows, N, H, pe_heads, attention_q_scale<T>(), 1e-6f);
-            KCHK();
-            pr.end(s);
-        }
-        pr.begin(PC_ATTN, s, 4.0 * H * 64 * (pk ? pk.sq_host : (double)Bp * N * N));
-        if constexpr (std::is_same_v<T, float>) {
-            if (attn16)
-                HIPCHK(launch_attention_v2<f16_t>(s, reinterpret_cast<const f16_t*>(w.q), reinterpret_cast<const f16_t*>(w.k),
-                                                  reinterpret_cast<const f16_t*>(w.vt), nullptr, Bp, H, N, w.Npad, attn_lens, B, lens_dev,
-                                                  pk.row_start, reinterpret_cast<float*>(w.ao)));
-        }
-        if (!attn16) {
-        HIPCHK(launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, N, w.Npad, attn_lens, B, lens_dev, pk.row_start, e->split16, pl,
-                                    e->x3_attn_hi));
-        }
-        pr.end(s);
-        ablate_a(8, w.ao, inner);
-        pr.begin(PC_GEMM, s, gflops(D, inner));
-        HIPCHK(egemm<T>(e, s, w.ao, inner, bw.out.w, bw.out.ldw, rows, D, inner,
-                              EpiGateRes{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens}, -1, ml, mh, pl));
-        pr.end(s);
-        pr.begin(PC_LN, s);
-        hipLaunchKernelGGL((layernorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, w.xn, D, rows, D, 1e-6f,
-                           m + 4 * D, m + 3 * D, mod_stride, N, 1,
-                           wpf ? Prefetch{(const char*)bw.ff1.w, (size_t)F * bw.ff1.ldw * sizeof(T),
-                                          (const char*)bw.ff2.w, (size_t)D * bw.ff2.ldw * sizeof(T)} : Prefetch{}, ml, pl);
-        KCHK();
-        pr.end(s);
-        ablate_a(16, w.xn, D);
-        pr.begin(PC_GEMM, s, gflops(F, D));
-        HIPCHK(egemm<T>(e, s, w.xn, D, bw.ff1.w, bw.ff1.ldw, rows, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl}, -1, ml, mh, pl));
-        pr.end(s);
-        ablate_a(32, w.ffh, F);
-        pr.begin(PC_GEMM, s, gflops(D, F));
-        HIPCHK(egemm<T>(e, s, w.ffh, F, bw.ff2.w, bw.ff2.ldw, rows, D, F,
-                              EpiGateRes{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr}, -1, ml, mh, pl));
-        pr.end(s);
+        HIPCHK(adaln(w.xn, m + D, m, prefetch(bw.qkv, bw.out), pl));
+        CHK(attention_block<T>(f, w, bw, qk_norm, EpiGateRes{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens}));
+        HIPCHK(adaln(w.xn, m + 4 * D, m + 3 * D, prefetch(bw.ff1, bw.ff2), pl));
+        CHK(ff_block<T>(f, w, bw, EpiGateRes{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr}));
     }
     if (long_skip) {   // x = long_skip_connection(cat((x, residual), dim=-1))   (dit.py:323-324)
-        pr.begin(PC_MISC, s);
+        auto cat_skip = [&](auto* cat) {
+            return pr.timed(PC_MISC, s, [&] {
+                hipLaunchKernelGGL((cat2_kernel<std::remove_pointer_t<decltype(cat)>>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s,
+                                   w.x, w.h, cat, (long)rows, D);
+                return hipGetLastError();
+            });
+        };
+        const EpiStore<float> epi{w.x, D, nullptr, F5_ACT_NONE};
         if (e->io_split) {
             float* cat_f = reinterpret_cast<float*>(w.cat2);
-            hipLaunchKernelGGL((cat2_kernel<float>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s, w.x, w.h, cat_f, (long)rows, D);
-            KCHK();
-            pr.end(s);
-            pr.begin(PC_GEMM, s, gflops(D, 2 * D));
-            HIPCHK(launch_gemm<float>(s, cat_f, 2 * D, P.long_skip_f.w, P.long_skip_f.ldw, rows, D, 2 * D,
-                                      EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}, -1, ml, mh, GemmConv{}, 1));
+            HIPCHK(cat_skip(cat_f));
+            HIPCHK(pr.timed(PC_GEMM, s, f.gflops(D, 2 * D), [&] {
+                return launch_gemm<float>(s, cat_f, 2 * D, P.long_skip_f.w, P.long_skip_f.ldw, rows, D, 2 * D, epi, -1, ml, mh, GemmConv{}, 1);
+            }));
         } else {
-            hipLaunchKernelGGL((cat2_kernel<T>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s, w.x, w.h, w.cat2, (long)rows, D);
-            KCHK();
-            pr.end(s);
-            pr.begin(PC_GEMM, s, gflops(D, 2 * D));
-            HIPCHK(egemm<T>(e, s, w.cat2, 2 * D, P.long_skip.w, P.long_skip.ldw, rows, D, 2 * D, EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE},
-                            -1, ml, mh));
+            HIPCHK(cat_skip(w.cat2));
+            CHK(f.gemm(w.cat2, 2 * D, P.long_skip, D, 2 * D, epi));
         }
-        pr.end(s);
     }
     const float* mf = mod_row + (size_t)c.depth * 6 * D;  // (scale, shift)
     if (e->io_split) {   // F5_PREC_F16P: final norm to f32 (pre-split rows in c1, free since the conv embedding) + split output projection
-        pr.begin(PC_LN, s);
-        hipLaunchKernelGGL((layernorm_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, w.c1, D, rows, D, 1e-6f, mf,
-                           mf + D, mod_stride, N, 1, Prefetch{}, ml, 1);
-        KCHK();
-        pr.end(s);
-        pr.begin(PC_GEMM, s, gflops(mel, D));
-        HIPCHK(launch_gemm<float>(s, w.c1, D, P.proj_out_f.w, P.proj_out_f.ldw, rows, mel, D,
-                                  EpiStore<float>{w.pred, mel, P.proj_out_f.b, F5_ACT_NONE}, -1, ml, mh, GemmConv{}, 2));
-        pr.end(s);
-        return F5_OK;
+        HIPCHK(adaln(w.c1, mf, mf + D, Prefetch{}, 1));
+        return project_out<T, float>(f, w.c1, w.pred);
     }
-    pr.begin(PC_LN, s);
-    hipLaunchKernelGGL((layernorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, w.xn, D, rows, D, 1e-6f, mf,
-                       mf + D, mod_stride, N, 1, Prefetch{}, ml, pl);
-    KCHK();
-    pr.end(s);
-    ablate_a(256, w.xn, D);
-    pr.begin(PC_GEMM, s, gflops(mel, D));
-    HIPCHK(egemm<T>(e, s, w.xn, D, P.proj_out.w, P.proj_out.ldw, rows, mel, D,
-                          EpiStore<float>{w.pred, mel, P.proj_out.b, F5_ACT_NONE}, -1, ml, mh, pl));
-    pr.end(s);
-    return F5_OK;
+    HIPCHK(adaln(w.xn, mf, mf + D, Prefetch{}, pl));
+    f.ablate(256, w.xn, D);
+    return project_out<T, T>(f, w.xn, w.pred);
 }
 
 // One UNetT forward over Bp packed rows (unett.py:217-280): time token prepended (N + 1 tokens per row), concat skip
@@ -660,67 +678,32 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
                              const float* text_first, const float* text_second, hipStream_t s) {
     Packed<T>& P = packed<T>(e);
     const f5_config& c = e->cfg;
-    const int D = c.dim, F = c.ff_dim, inner = e->inner, mel = c.mel_dim, H = c.heads;
+    const int D = c.dim, mel = c.mel_dim;
     const int Nt = N + 1;
     const int rows_in = Bp * N, rows = Bp * Nt;
     Prof& pr = e->prof;
-    auto gfl = [&](double r, double n, double k) { return 2.0 * r * n * k; };
-    const double conv_fl = 2.0 * rows_in * D * (D / 16) * 31;
     float* emb = reinterpret_cast<float*>(w.cat2);  // [rows, 2D] of T >= [rows_in, D] f32; free until the first concat; conv input and output must not alias
-    if (e->io_split) {   // F5_PREC_F16P: input projection + conv position embedding as split-f16 products on f32 operands (run_dit_forward)
-        float* acat_f = reinterpret_cast<float*>(w.acat);
-        pr.begin(PC_MISC, s);
-        hipLaunchKernelGGL((pack_input_kernel<float>), dim3(ew_blocks((long)rows_in * e->kin / 4)), dim3(256), 0, s, y, cond,
-                           text_first, text_second, acat_f, e->kin_pad, B, Bp, N, mel, c.text_dim, drop_cond_first);
-        KCHK();
-        pr.end(s);
-        pr.begin(PC_GEMM, s, gfl(rows_in, D, e->kin));
-        HIPCHK(launch_gemm<float>(s, acat_f, e->kin_pad, P.in_proj_f.w, P.in_proj_f.ldw, rows_in, D, e->kin_pad,
-                                  EpiStore<float>{w.h, D, P.in_proj_f.b, F5_ACT_NONE}, -1, nullptr, 0, GemmConv{}, 1));
-        pr.end(s);
-        const bool cs = convpos_can_split(D);
-        pr.begin(PC_CONV, s, conv_fl);
-        HIPCHK(launch_convpos<float>(s, w.h, P.conv_w_f[0], P.conv_kp_f, P.conv_b[0], nullptr, w.c1, Bp, N, D, nullptr, B, nullptr, cs));
-        pr.end(s);
-        pr.begin(PC_CONV, s, conv_fl);
-        HIPCHK(launch_convpos<float>(s, w.c1, P.conv_w_f[1], P.conv_kp_f, P.conv_b[1], w.h, emb, Bp, N, D, nullptr, B, nullptr, cs));
-        pr.end(s);
-    } else {
-    pr.begin(PC_MISC, s);
-    hipLaunchKernelGGL((pack_input_kernel<T>), dim3(ew_blocks((long)rows_in * e->kin / 4)), dim3(256), 0, s, y, cond,
-                       text_first, text_second, w.acat, e->kin_pad, B, Bp, N, mel, c.text_dim, drop_cond_first);
-    KCHK();
-    pr.end(s);
-    pr.begin(PC_GEMM, s, gfl(rows_in, D, e->kin));
-    HIPCHK(egemm<T>(e, s, w.acat, e->kin_pad, P.in_proj.w, P.in_proj.ldw, rows_in, D, e->kin_pad,
-                          EpiStore<float>{w.h, D, P.in_proj.b, F5_ACT_NONE}));
-    pr.end(s);
-    pr.begin(PC_CONV, s, conv_fl);   // unett.py:99-100: conv_pos_embed is called WITHOUT a mask
-    HIPCHK(launch_convpos<T>(s, w.h, P.conv_w[0], P.conv_kp, P.conv_b[0], nullptr, w.c1, Bp, N, D, nullptr, B, nullptr, conv_split(e)));
-    pr.end(s);
-    pr.begin(PC_CONV, s, conv_fl);
-    HIPCHK(launch_convpos<T>(s, w.c1, P.conv_w[1], P.conv_kp, P.conv_b[1], w.h, emb, Bp, N, D, nullptr, B, nullptr, conv_split(e)));
-    pr.end(s);
-    }
-    pr.begin(PC_MISC, s);
+    // the input embedding runs on the N frames of every row, unpacked and (unett.py:99-100: conv_pos_embed is called WITHOUT a mask) unmasked
+    const FwdCtx in{e, s, B, Bp, N, rows_in, nullptr, RowPack{}};
+    if (e->io_split) CHK((embed_input<T, float>(in, w, y, cond, drop_cond_first, text_first, text_second, emb)));
+    else CHK((embed_input<T, T>(in, w, y, cond, drop_cond_first, text_first, text_second, emb)));
     // The skip stack needs no copies: the stream entering block l < depth/2 is WRITTEN into skip slot l (by the assemble kernel / the
     // FF2 epilogue of block l - 1), the block's first residual update reads it there and writes w.x, and nothing writes the slot again.
     const int half = c.depth / 2;
     auto slot = [&](int l) { return w.skips + (size_t)l * rows * D; };
-    hipLaunchKernelGGL(unett_assemble_kernel, dim3(ew_blocks((long)rows * D / 4)), dim3(256), 0, s, emb, temb, temb_stride,
-                       half > 0 ? slot(0) : w.x, Bp, N, D);
-    KCHK();
-    pr.end(s);
-    const int pe_heads = c.pe_attn_head < 0 ? H : c.pe_attn_head;
-    const int* attn_lens = (c.attn_mask_enabled && lens_dev) ? lens_dev : nullptr;   // lens_dev holds len + 1 for UNetT
-    const int pl = e->split16 ? 1 : 0;   // F5_PREC_F16X3: xn / ao / ffh written pre-split (as in run_dit_forward)
-    auto ablate_a = [&](int bit, T* a, int k) {   // diagnostic F5_X3_ABLATE (run_dit_forward): the class's A operand as plain f16
-        if constexpr (std::is_same_v<T, float>) {
-            if (e->x3_ablate & bit) {
-                const long blocks = (long)rows * k / 32;
-                hipLaunchKernelGGL(zero_lo_planar_kernel, dim3(ew_blocks(blocks * 4)), dim3(256), 0, s, a, blocks);
-            }
-        }
+    HIPCHK(pr.timed(PC_MISC, s, [&] {
+        hipLaunchKernelGGL(unett_assemble_kernel, dim3(ew_blocks((long)rows * D / 4)), dim3(256), 0, s, emb, temb, temb_stride,
+                           half > 0 ? slot(0) : w.x, Bp, N, D);
+        return hipGetLastError();
+    }));
+    const FwdCtx f{e, s, B, Bp, Nt, rows, lens_dev, RowPack{}};   // the blocks: N + 1 tokens per row; lens_dev holds len + 1 for UNetT
+    const int pl = f.pl();
+    auto rmsnorm = [&](const float* x, auto* out, const float* g, int planar) {   // out (rows of T, or pre-split f32 rows) = RMSNorm(x) * g
+        return pr.timed(PC_LN, s, [&] {
+            hipLaunchKernelGGL((xrmsnorm_kernel<std::remove_pointer_t<decltype(out)>>), dim3((rows + 3) / 4), dim3(256), 0, s, x, D, out, D, rows, D, g,
+                               planar);
+            return hipGetLastError();
+        });
     };
     for (int l = 0; l < c.depth; ++l) {
         BlockW<T>& bw = P.blocks[l];
@@ -728,91 +711,30 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
         float* x_out = l + 1 < half ? slot(l + 1) : w.x;         // where the block leaves it
         if (l >= half) {
             const float* skip = w.skips + (size_t)(c.depth - 1 - l) * rows * D;   // LIFO (skips.pop())
-            pr.begin(PC_MISC, s);
-            hipLaunchKernelGGL((cat2_kernel<T>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s, w.x, skip, w.cat2,
-                               (long)rows, D, pl);   // (F5_PREC_F16X3: pre-split, so that the projection runs on pre-split operands too)
-            KCHK();
-            pr.end(s);
-            ablate_a(512, w.cat2, 2 * D);   // diagnostic: ... and its A operand as plain f16
-            pr.begin(PC_GEMM, s, gfl(rows, D, 2 * D));
-            HIPCHK(egemm<T>(e, s, w.cat2, 2 * D, bw.skip.w, bw.skip.ldw, rows, D, 2 * D,
-                                  EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}, -1, nullptr, 0, pl));
-            pr.end(s);
+            HIPCHK(pr.timed(PC_MISC, s, [&] {
+                hipLaunchKernelGGL((cat2_kernel<T>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s, w.x, skip, w.cat2,
+                                   (long)rows, D, pl);   // (F5_PREC_F16X3: pre-split, so that the projection runs on pre-split operands too)
+                return hipGetLastError();
+            }));
+            f.ablate(512, w.cat2, 2 * D);   // diagnostic: ... and its A operand as plain f16
+            CHK(f.gemm(w.cat2, 2 * D, bw.skip, D, 2 * D, EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}, pl));
         }
-        pr.begin(PC_LN, s);
-        hipLaunchKernelGGL((xrmsnorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, x_in, D, w.xn, D, rows, D, bw.norm1_g, pl);
-        KCHK();
-        pr.end(s);
-        ablate_a(1, w.xn, D);
-        pr.begin(PC_GEMM, s, gfl(rows, 3 * inner, D));
-        bool attn16 = false;   // (run_dit_forward)
-        if constexpr (std::is_same_v<T, float>) {
-            attn16 = e->split16 && e->x3_attn_hi == 3;
-            if (attn16)
-                HIPCHK(egemm<T>(e, s, w.xn, D, bw.qkv.w, bw.qkv.ldw, rows, 3 * inner, D,
-                                EpiQKV<f16_t>{reinterpret_cast<f16_t*>(w.q), reinterpret_cast<f16_t*>(w.k), reinterpret_cast<f16_t*>(w.vt),
-                                              bw.qkv.b, P.rope_frag, Nt, w.Npad, H, pe_heads, attention_q_scale<f16_t>()},
-                                -1, nullptr, 0, pl));
-        }
-        if (!attn16) {
-        HIPCHK(egemm<T>(e, s, w.xn, D, bw.qkv.w, bw.qkv.ldw, rows, 3 * inner, D,
-                              EpiQKV<T>{w.q, w.k, w.vt, bw.qkv.b, P.rope_frag, Nt, w.Npad, H, pe_heads, attention_q_scale<T>()},
-                              -1, nullptr, 0, pl));
-        }
-        pr.end(s);
-        pr.begin(PC_ATTN, s, 4.0 * Bp * H * (double)Nt * Nt * 64);
-        if constexpr (std::is_same_v<T, float>) {
-            if (attn16)
-                HIPCHK(launch_attention_v2<f16_t>(s, reinterpret_cast<const f16_t*>(w.q), reinterpret_cast<const f16_t*>(w.k),
-                                                  reinterpret_cast<const f16_t*>(w.vt), nullptr, Bp, H, Nt, w.Npad, attn_lens, B, lens_dev,
-                                                  nullptr, reinterpret_cast<float*>(w.ao)));
-        }
-        if (!attn16) {
-        HIPCHK(launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, Nt, w.Npad, attn_lens, B, lens_dev, nullptr, e->split16, pl,
-                                    e->x3_attn_hi));
-        }
-        pr.end(s);
-        ablate_a(8, w.ao, inner);
-        pr.begin(PC_GEMM, s, gfl(rows, D, inner));
-        HIPCHK(egemm<T>(e, s, w.ao, inner, bw.out.w, bw.out.ldw, rows, D, inner,
-                              EpiGateRes{w.x, x_in, D, bw.out.b, nullptr, 0, Nt, lens_dev}, -1, nullptr, 0, pl));
-        pr.end(s);
-        pr.begin(PC_LN, s);
-        hipLaunchKernelGGL((xrmsnorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, w.xn, D, rows, D, bw.norm2_g, pl);
-        KCHK();
-        pr.end(s);
-        ablate_a(16, w.xn, D);
-        pr.begin(PC_GEMM, s, gfl(rows, F, D));
-        HIPCHK(egemm<T>(e, s, w.xn, D, bw.ff1.w, bw.ff1.ldw, rows, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl}, -1, nullptr, 0, pl));
-        pr.end(s);
-        ablate_a(32, w.ffh, F);
-        pr.begin(PC_GEMM, s, gfl(rows, D, F));
-        HIPCHK(egemm<T>(e, s, w.ffh, F, bw.ff2.w, bw.ff2.ldw, rows, D, F, EpiGateRes{x_out, w.x, D, bw.ff2.b, nullptr, 0, Nt, nullptr}, -1, nullptr, 0, pl));
-        pr.end(s);
+        HIPCHK(rmsnorm(x_in, w.xn, bw.norm1_g, pl));
+        CHK(attention_block<T>(f, w, bw, false, EpiGateRes{w.x, x_in, D, bw.out.b, nullptr, 0, Nt, lens_dev}));
+        HIPCHK(rmsnorm(w.x, w.xn, bw.norm2_g, pl));
+        CHK(ff_block<T>(f, w, bw, EpiGateRes{x_out, w.x, D, bw.ff2.b, nullptr, 0, Nt, nullptr}));
     }
     if (e->io_split) {   // F5_PREC_F16P: final norm to pre-split f32 rows (in the skip stack's first slot: every skip has been popped) + split projection
-        float* xn_f = w.skips;
-        pr.begin(PC_LN, s);
-        hipLaunchKernelGGL((xrmsnorm_kernel<float>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, xn_f, D, rows, D, P.norm_out_g, 1);
-        KCHK();
-        pr.end(s);
-        pr.begin(PC_GEMM, s, gfl(rows, mel, D));
-        HIPCHK(launch_gemm<float>(s, xn_f, D, P.proj_out_f.w, P.proj_out_f.ldw, rows, mel, D,
-                                  EpiStore<float>{w.pred_all, mel, P.proj_out_f.b, F5_ACT_NONE}, -1, nullptr, 0, GemmConv{}, 2));
-        pr.end(s);
+        HIPCHK(rmsnorm(w.x, w.skips, P.norm_out_g, 1));
+        CHK((project_out<T, float>(f, w.skips, w.pred_all)));
     } else {
-    pr.begin(PC_LN, s);
-    hipLaunchKernelGGL((xrmsnorm_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, w.xn, D, rows, D, P.norm_out_g, pl);
-    KCHK();
-    pr.end(s);
-    pr.begin(PC_GEMM, s, gfl(rows, mel, D));
-    HIPCHK(egemm<T>(e, s, w.xn, D, P.proj_out.w, P.proj_out.ldw, rows, mel, D, EpiStore<float>{w.pred_all, mel, P.proj_out.b, F5_ACT_NONE}, -1, nullptr, 0, pl));
-    pr.end(s);
+        HIPCHK(rmsnorm(w.x, w.xn, P.norm_out_g, pl));
+        CHK((project_out<T, T>(f, w.xn, w.pred_all)));
     }
-    pr.begin(PC_MISC, s);
-    hipLaunchKernelGGL(strip_first_token_kernel, dim3(ew_blocks((long)rows_in * mel / 4)), dim3(256), 0, s, w.pred_all, w.pred, Bp, N, mel);
-    KCHK();
-    pr.end(s);
+    HIPCHK(pr.timed(PC_MISC, s, [&] {
+        hipLaunchKernelGGL(strip_first_token_kernel, dim3(ew_blocks((long)rows_in * mel / 4)), dim3(256), 0, s, w.pred_all, w.pred, Bp, N, mel);
+        return hipGetLastError();
+    }));
     return F5_OK;
 }
 
@@ -912,6 +834,7 @@ static int forward_impl(f5_engine* e, const float* x, const float* cond, const i
     return F5_OK;
 }
 // the second (unconditional) half of every [2B ...] activation buffer, as a Work of its own
+// (open finding, ADVICE.md first item: the offsets of acat and cat2 do not follow F5_PREC_F16P / F5_OPT_LONG_SKIP)
 template <typename T> static Work<T> second_half(const f5_engine* e, const Work<T>& w, int B, int N) {
     const f5_config& c = e->cfg;
     const size_t rows = (size_t)B * N;
@@ -954,11 +877,11 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
     const long half = (long)B * N * mel;
     const int64_t* text = reinterpret_cast<const int64_t*>(w.in_text);
     // step_cond = where(cond_mask, cond, 0)   (cfm.py:151-153)
-    e->prof.begin(PC_MISC, s);
-    hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)nullptr,
-                       w.in_mask, w.step_cond, (long)B * N, mel);
-    KCHK();
-    e->prof.end(s);
+    HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+        hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)nullptr,
+                           w.in_mask, w.step_cond, (long)B * N, mel);
+        return hipGetLastError();
+    }));
     CHK(run_time_path<T>(e, w, evals * steps, s));  // features of every evaluation time
     const int* tlens = (c.backbone == F5_BACKBONE_DIT && has_lens) ? w.lens_plain : nullptr;
     CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 0, w.text_c, s));
@@ -1020,18 +943,18 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
             };
             CHK(split_eval(w.y, evals * i));
             if (mid) {
-                e->prof.begin(PC_MISC, s);
-                hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
-                                   cfg_strength, use_cfg ? 1 : 0, w.y_mid);
-                KCHK();
-                e->prof.end(s);
+                HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                    hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
+                                       cfg_strength, use_cfg ? 1 : 0, w.y_mid);
+                    return hipGetLastError();
+                }));
                 CHK(split_eval(w.y_mid, 2 * i + 1));
             }
-            e->prof.begin(PC_MISC, s);
-            hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
-                               cfg_strength, use_cfg ? 1 : 0, want_traj ? w.traj_buf + (size_t)(i + 1) * half : nullptr);
-            KCHK();
-            e->prof.end(s);
+            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
+                                   cfg_strength, use_cfg ? 1 : 0, want_traj ? w.traj_buf + (size_t)(i + 1) * half : nullptr);
+                return hipGetLastError();
+            }));
             continue;
         }
         int cidx = 0;
@@ -1047,36 +970,36 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
             };
             CHK(eval(w.y + yo, evals * i));
             if (mid) {   // y_mid = y + f(t[i], y) * dt/2, then the full step below on f(t[i] + dt/2, y_mid)
-                e->prof.begin(PC_MISC, s);
-                if (pk)
-                    hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred,
-                                       bc, N, mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0,
-                                       w.y_mid + yo);
-                else
-                    hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c,
-                                       tgrid, i, cfg_strength, use_cfg ? 1 : 0, w.y_mid + yo);
-                KCHK();
-                e->prof.end(s);
+                HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                    if (pk)
+                        hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred,
+                                           bc, N, mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0,
+                                           w.y_mid + yo);
+                    else
+                        hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c,
+                                           tgrid, i, cfg_strength, use_cfg ? 1 : 0, w.y_mid + yo);
+                    return hipGetLastError();
+                }));
                 CHK(eval(w.y_mid + yo, 2 * i + 1));
             }
-            e->prof.begin(PC_MISC, s);
-            float* slot = want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
-            if (pk)
-                hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, bc, N,
-                                   mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0, slot);
-            else
-                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c, tgrid,
-                                   i, cfg_strength, use_cfg ? 1 : 0, slot);
-            KCHK();
-            e->prof.end(s);
+            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                float* slot = want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
+                if (pk)
+                    hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, bc, N,
+                                       mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0, slot);
+                else
+                    hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c, tgrid,
+                                       i, cfg_strength, use_cfg ? 1 : 0, slot);
+                return hipGetLastError();
+            }));
         }
     }
     // out = where(cond_mask, cond, y)   (cfm.py:221-223)
-    e->prof.begin(PC_MISC, s);
-    hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)w.y, w.in_mask,
-                       w.out_buf, (long)B * N, mel);
-    KCHK();
-    e->prof.end(s);
+    HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+        hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)w.y, w.in_mask,
+                           w.out_buf, (long)B * N, mel);
+        return hipGetLastError();
+    }));
     return F5_OK;
 }
 template <typename T>

@@ -79,7 +79,19 @@ struct Prof {
         cls.clear();
         flops.clear();
     }
-    void begin(int c, hipStream_t s, double fl = 0.0) {
+    // One launch site: start event, launch() -- which issues the launch(es) on s and returns their status (hipError_t or an F5 code) --,
+    // stop event.  With the profiler off it is launch() alone.  The bracket is closed on every path, so a failed launch cannot leave
+    // a record open (end() drops every later record once begins and ends stop pairing up).
+    template <typename F> auto timed(int c, hipStream_t s, double fl, F&& launch) -> decltype(launch()) {
+        begin(c, s, fl);
+        const auto rc = launch();
+        end(s);
+        return rc;
+    }
+    template <typename F> auto timed(int c, hipStream_t s, F&& launch) -> decltype(launch()) { return timed(c, s, 0.0, launch); }
+
+private:
+    void begin(int c, hipStream_t s, double fl) {
         if (!on || used + 2 > MAXEV) return;
         while ((int)ev.size() < used + 2) {
             hipEvent_t e;

@@ -44,43 +44,32 @@ inline int pick_cfg_v2(int M, int N, bool allow_v3 = false, float g3_penalty = 0
 template <typename Epi> inline bool epilogue_streams_residual(const Epi&) { return false; }
 inline bool epilogue_streams_residual(const EpiGateRes&) { return true; }
 
+// One tile switch for every operand form.  MODE (gemm2.h): 0 plain operands; 3 W in the split_planar layout, A f32 split in
+// registers, products on the f16 pipe; 5 both operands pre-split (the ping-pong kernel's DIAG bit 8).
+template <typename T, typename Epi, int MODE>
+inline hipError_t launch_gemm_tile(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi, int cfg,
+                                   const int* ml, const GemmConv& cv) {
+    switch (cfg) {
+        case G3_256x256_PP:
+            if constexpr (MODE != 3) {   // (W-only split operands have no ping-pong kernel: the 256x128 tile)
+                if (cv.tpt == 0 && cv.m_base == 0) return launch_gemm3<T, Epi, MODE == 5 ? 8 : 0>(s, A, lda, W, ldw, M, N, K, epi, ml);
+            }
+            [[fallthrough]];   // (the ping-pong kernel has no implicit-conv / row-offset mode)
+        case G2_256x128_8W: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi, MODE>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
+        case G2_128x192_8W: return launch_gemm2_cfg<T, 128, 192, 2, 4, 3, Epi, MODE>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
+        case G2_128x128_8W: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi, MODE>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
+        case G2_128x64_8W: return launch_gemm2_cfg<T, 128, 64, 4, 2, 4, Epi, MODE>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
+        default: return launch_gemm2_cfg<T, 64, 64, 2, 2, 3, Epi, MODE>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
+    }
+}
 template <typename T, typename Epi>
 inline hipError_t launch_gemm_v2(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
                                  const Epi& epi, int cfg, const int* ml = nullptr, const GemmConv& cv = GemmConv{}, int split = 0) {
     if constexpr (std::is_same_v<T, float>) {
-        if (split == 2) {   // both operands pre-split (gemm2.h MODE 5; the ping-pong kernel's DIAG bit 8)
-            switch (cfg) {
-                case G3_256x256_PP:
-                    if (cv.tpt == 0 && cv.m_base == 0) return launch_gemm3<T, Epi, 8>(s, A, lda, W, ldw, M, N, K, epi, ml);
-                    [[fallthrough]];
-                case G2_256x128_8W: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi, 5>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                case G2_128x192_8W: return launch_gemm2_cfg<T, 128, 192, 2, 4, 3, Epi, 5>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                case G2_128x128_8W: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi, 5>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                case G2_128x64_8W: return launch_gemm2_cfg<T, 128, 64, 4, 2, 4, Epi, 5>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                default: return launch_gemm2_cfg<T, 64, 64, 2, 2, 3, Epi, 5>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-            }
-        }
-        if (split) {   // W in the split_planar layout, A f32 split in registers, products on the f16 pipe (gemm2.h MODE 3)
-            switch (cfg) {
-                case G3_256x256_PP:
-                case G2_256x128_8W: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi, 3>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                case G2_128x192_8W: return launch_gemm2_cfg<T, 128, 192, 2, 4, 3, Epi, 3>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                case G2_128x128_8W: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi, 3>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                case G2_128x64_8W: return launch_gemm2_cfg<T, 128, 64, 4, 2, 4, Epi, 3>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-                default: return launch_gemm2_cfg<T, 64, 64, 2, 2, 3, Epi, 3>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-            }
-        }
+        if (split == 2) return launch_gemm_tile<T, Epi, 5>(s, A, lda, W, ldw, M, N, K, epi, cfg, ml, cv);
+        if (split) return launch_gemm_tile<T, Epi, 3>(s, A, lda, W, ldw, M, N, K, epi, cfg, ml, cv);
     } else if (split) return hipErrorInvalidValue;
-    switch (cfg) {
-        case G3_256x256_PP:
-            if (cv.tpt == 0 && cv.m_base == 0) return launch_gemm3<T, Epi>(s, A, lda, W, ldw, M, N, K, epi, ml);
-            [[fallthrough]];   // (the ping-pong kernel has no implicit-conv / row-offset mode)
-        case G2_256x128_8W: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-        case G2_128x192_8W: return launch_gemm2_cfg<T, 128, 192, 2, 4, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-        case G2_128x128_8W: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-        case G2_128x64_8W: return launch_gemm2_cfg<T, 128, 64, 4, 2, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-        default: return launch_gemm2_cfg<T, 64, 64, 2, 2, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
-    }
+    return launch_gemm_tile<T, Epi, 0>(s, A, lda, W, ldw, M, N, K, epi, cfg, ml, cv);
 }
 
 // m_limit (device int, may be null): rows actually present, <= M (the v2 / v3 kernels only: the engine's operands always qualify)
