@@ -38,6 +38,22 @@ int f5_fail(int code, const char* fmt, ...) {
 extern "C" const char* f5_last_error(void) { return g_err; }
 extern "C" const char* f5_version(void) { return "f5hip 2 gfx950"; }
 // ----------------------------------------------------------------------------------------------- create
+// the switches of one engine (engine_types.h Switches): the environment as f5_create finds it
+static Switches read_switches(const f5_config& c) {
+    auto flag = [](const char* name, bool dflt) {   // "0" switches off, "1" switches on
+        const char* v = getenv(name);
+        return (v && v[0] == (dflt ? '0' : '1')) ? !dflt : dflt;
+    };
+    Switches sw;
+    sw.graphs = flag("F5_HIP_GRAPH", true);
+    sw.split_cfg = flag("F5_SPLIT_CFG", false);
+    sw.pack_rows = flag("F5_PACK_ROWS", true);
+    if (const char* v = getenv("F5_CHUNK_ROWS")) sw.chunk_rows = std::max(1L, atol(v));   // (a budget below one utterance: one utterance)
+    sw.weight_prefetch = flag("F5_WEIGHT_PREFETCH", true);
+    if (const char* v = getenv("F5_X3_ABLATE")) sw.x3_ablate = c.precision == F5_PREC_F16X3 ? atoi(v) : 0;
+    sw.x3_attn_split = flag("F5_X3_ATTN_SPLIT", false);
+    return sw;
+}
 extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     if (!c || !out) return fail(F5_EINVAL, "f5_create: null argument");
     if (c->dim_head != 64) return fail(F5_EINVAL, "dim_head must be 64 (got %d)", c->dim_head);
@@ -66,10 +82,9 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     e->modN = (6 * c->depth + 2) * c->dim;
     e->split16 = c->precision == F5_PREC_F16X3;
     e->io_split = c->precision == F5_PREC_F16P;
-    if (e->split16 && getenv("F5_X3_ABLATE")) e->x3_ablate = atoi(getenv("F5_X3_ABLATE"));
-    if (getenv("F5_X3_ATTN_SPLIT") && getenv("F5_X3_ATTN_SPLIT")[0] == '1') e->x3_attn_hi = (e->x3_ablate >> 1) & 3;
+    e->sw = read_switches(*c);
     e->adapters_on = (c->options & F5_OPT_ADAPTERS) != 0;
-    if (e->adapters_on && e->x3_ablate) {   // (the ablation zeroes lo halves once, at finalize: a switch would write them back)
+    if (e->adapters_on && e->sw.x3_ablate) {   // (the ablation zeroes lo halves once, at finalize: a switch would write them back)
         delete e;
         return fail(F5_EINVAL, "F5_OPT_ADAPTERS cannot be combined with the F5_X3_ABLATE diagnostic");
     }
@@ -160,11 +175,11 @@ extern "C" int f5_reserve(f5_engine* e, int32_t B, int32_t N, int32_t S) {
 // Utterances per backbone call inside sample(): the ODE state of different utterances never interacts, so a large batch
 // is stepped in chunks whose activations (x 4 B, xn, q, k, v, ffh 2 B per element: ~17 KB per row) stay inside the 256 MB
 // Infinity Cache between the kernels of a block, instead of streaming every intermediate through HBM (C3: 65,536 rows).
-// F5_CHUNK_ROWS overrides the row budget (tests force tiny chunks).
+// F5_CHUNK_ROWS overrides the row budget (tests force tiny chunks).  F5_SPLIT_CFG=1 steps the whole batch per half.
 // With row packing (RowPack) an utterance costs its own length, not the padded one: the budget then counts the rows
 // actually present (C3 with attn_mask_enabled: 2 chunks of 16 utterances ~ 22,600 valid rows each).
-int chunk_utts(f5_engine* e, int B, int N, bool use_cfg, const int32_t* lens_host) {
-    if (split_cfg_enabled(e)) return B;   // the opt-in two-stream mode steps the whole batch per half
+static int chunk_utts(const f5_engine* e, int B, int N, bool use_cfg, const int32_t* packed_lens) {
+    if (e->sw.split_cfg) return B;
     // Equal chunks; how many is chosen by counting ROUNDS of GEMM tiles: a backbone call on R rows runs its N = 1024 GEMMs (out-proj, FF2) in
     // ceil(R / 16,384) rounds of 256 tiles of 256 x 256, so k chunks cost k * ceil(R_chunk / 16,384) rounds; among the cheapest counts
     // the one whose chunks are closest to 32,768 rows wins (the activations of such a chunk stay inside the Infinity Cache).  Measured:
@@ -172,14 +187,13 @@ int chunk_utts(f5_engine* e, int B, int N, bool use_cfg, const int32_t* lens_hos
     // (45,200 valid rows): 2 x 22,600 (2 x 2 rounds) 1,103 ms, **1 x 45,200 (3 rounds) 1,018** -- round 2's fixed 32,768-row budget
     // chose the former.  F5_CHUNK_ROWS forces a fixed budget instead (tests use tiny chunks).
     long rows_per_utt = (long)(use_cfg ? 2 : 1) * (N + (e->cfg.backbone == F5_BACKBONE_UNETT ? 1 : 0));
-    if (lens_host && pack_rows_enabled(e)) {
+    if (packed_lens) {
         long total = 0;
-        for (int i = 0; i < B; ++i) total += (lens_host[i] + 3) / 4 * 4;
+        for (int i = 0; i < B; ++i) total += (packed_lens[i] + 3) / 4 * 4;
         rows_per_utt = std::max(1L, (long)(use_cfg ? 2 : 1) * total / B);
     }
-    if (getenv("F5_CHUNK_ROWS")) {
-        const long budget = atol(getenv("F5_CHUNK_ROWS"));
-        long bc = budget / rows_per_utt;
+    if (e->sw.chunk_rows) {
+        long bc = e->sw.chunk_rows / rows_per_utt;
         if (bc < 1) bc = 1;
         if (bc >= B) return B;
         const long nchunks = (B + bc - 1) / bc;
@@ -196,6 +210,50 @@ int chunk_utts(f5_engine* e, int B, int N, bool use_cfg, const int32_t* lens_hos
         if (best_cost < 0 || cost < best_cost || (cost == best_cost && dist < best_dist)) { best_k = kk; best_cost = cost; best_dist = dist; }
     }
     return (int)((B + best_k - 1) / best_k);
+}
+SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk, int nt, int steps, int method,
+                       float cfg_strength, bool want_traj) {
+    SamplePlan p;
+    p.B = B; p.N = N; p.nt = nt; p.steps = steps; p.method = method; p.cfg_strength = cfg_strength;
+    p.use_cfg = !(cfg_strength < 1e-5f);
+    p.has_lens = lens_host != nullptr;
+    p.want_traj = want_traj;
+    p.halves = p.use_cfg ? 2 : 1;
+    p.evals = method == F5_ODE_MIDPOINT ? 2 : 1;
+    const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;
+    p.pack = p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg;
+    p.split = e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
+    p.chunk = chunk ? chunk : chunk_utts(e, B, N, p.use_cfg, p.pack ? lens_host : nullptr);
+    for (int u0 = 0; u0 < B; u0 += p.chunk) {
+        SamplePlan::Chunk k{(int)p.chunks.size(), u0, std::min(p.chunk, B - u0), 0, 0};
+        for (int i = 0; lens_host && i < k.bc; ++i) {
+            k.rows += (double)p.halves * round_up(lens_host[u0 + i], 4);
+            k.sq += (double)p.halves * lens_host[u0 + i] * lens_host[u0 + i];
+        }
+        p.chunks.push_back(k);
+    }
+    return p;
+}
+// the signature a captured sample() body is cached under (F5_TRACE prints it; tools/pmc_one.py reads it)
+std::string graph_key(const SamplePlan& p) {
+    unsigned cfg_bits;
+    memcpy(&cfg_bits, &p.cfg_strength, 4);
+    char kb[160];
+    snprintf(kb, sizeof(kb), "%d|%d|%d|%d|%08x|%d|%d|%d|m%d", p.B, p.N, p.nt, p.steps, cfg_bits, p.has_lens ? 1 : 0, p.want_traj ? 1 : 0,
+             p.chunk, p.method);
+    return kb;
+}
+// What sample() uploads to Work::tdev: the evaluation times (one feature row each), then the grid t[0..steps].  Euler evaluates at
+// t[0..steps-1], which IS the grid's head; midpoint at t[i] (row 2i) and t[i] + dt/2 (row 2i+1), and the grid follows at 2 steps.
+std::vector<float> time_table(const float* t_host, int steps, int method) {
+    std::vector<float> tt;
+    for (int i = 0; method == F5_ODE_MIDPOINT && i < steps; ++i) {
+        const float hdt = 0.5f * (t_host[i + 1] - t_host[i]);   // f32, in torchdiffeq's order
+        tt.push_back(t_host[i]);
+        tt.push_back(t_host[i] + hdt);
+    }
+    tt.insert(tt.end(), t_host, t_host + steps + 1);
+    return tt;
 }
 static int check_ready(f5_engine* e, int B, int N) {
     if (!e) return fail(F5_EINVAL, "null engine");
@@ -218,29 +276,6 @@ extern "C" int f5_dit_forward(f5_engine* e, const float* x, const float* cond, c
     if (!x || !cond || !text || !time_host || !out || nt <= 0) return fail(F5_EINVAL, "f5_dit_forward: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     return F5_OPS(e, forward(e, x, cond, text, nt, time_host, lens_host, B, N, cfg_infer, drop_audio_cond, drop_text, out, s));
-}
-bool split_cfg_enabled(f5_engine* e) {
-    if (e->split_cfg < 0) {
-        const char* v = getenv("F5_SPLIT_CFG");
-        e->split_cfg = (v && v[0] == '1') ? 1 : 0;   // opt-in: 35.4 ms as two eager chains, 35.2 ms as a two-branch
-                                                     // hipGraph, against 34.4 ms packed
-    }
-    return e->split_cfg == 1;
-}
-// Row packing (RowPack) for DiT batches with attn_mask_enabled: on unless F5_PACK_ROWS=0
-bool pack_rows_enabled(f5_engine* e) {
-    if (e->pack_rows < 0) {
-        const char* v = getenv("F5_PACK_ROWS");
-        e->pack_rows = (v && v[0] == '0') ? 0 : 1;
-    }
-    return e->pack_rows == 1 && e->cfg.attn_mask_enabled && e->cfg.backbone == F5_BACKBONE_DIT && !split_cfg_enabled(e);
-}
-bool graphs_enabled(f5_engine* e) {
-    if (e->graphs_on < 0) {
-        const char* v = getenv("F5_HIP_GRAPH");
-        e->graphs_on = (v && v[0] == '0') ? 0 : 1;
-    }
-    return e->graphs_on == 1;
 }
 extern "C" int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
                              const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,

@@ -197,7 +197,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     // input embedding
     CHK(pack_linear_bb<T>(e, s, "input_embed.proj.weight", "input_embed.proj.bias", D, e->kin, &P.in_proj));
     auto zlo = [&](int bit, LinW<T>& L) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves zeroed) for a class
-        if (e->x3_ablate & bit) zero_lo_planar(s, L.w, (size_t)L.N * L.ldw);
+        if (e->sw.x3_ablate & bit) zero_lo_planar(s, L.w, (size_t)L.N * L.ldw);
     };
     zlo(64, P.in_proj);
     const int cpg = D / 16;
@@ -210,7 +210,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         hipLaunchKernelGGL((conv_pack_kernel<T>), dim3(ew_blocks((long)D * P.conv_kp)), dim3(256), 0, s, w->p,
                            P.conv_w[j], (long)D, cpg, 31, P.conv_kp);
         if (conv_split(e)) CHK((maybe_split_weight<T, true>(e, s, P.conv_w[j], (size_t)D * P.conv_kp)));   // F5_PREC_F16X3 (convpos.h SPLIT)
-        if (conv_split(e) && (e->x3_ablate & 128)) zero_lo_planar(s, P.conv_w[j], (size_t)D * P.conv_kp);
+        if (conv_split(e) && (e->sw.x3_ablate & 128)) zero_lo_planar(s, P.conv_w[j], (size_t)D * P.conv_kp);
         CHK(copy_vec(e, s, p + ".bias", {D}, &P.conv_b[j]));
     }
     // transformer
@@ -466,7 +466,7 @@ struct FwdCtx {
     }
     // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed)
     template <typename T> void ablate(int bit, T* a, int k) const {
-        if (e->x3_ablate & bit) zero_lo_planar(s, a, (size_t)rows * k);
+        if (e->sw.x3_ablate & bit) zero_lo_planar(s, a, (size_t)rows * k);
     }
 };
 
@@ -500,7 +500,7 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
         return hipGetLastError();
     }));
     auto ablate_round = [&](int bit, const float* src, float* to, long n) -> const float* {   // diagnostic F5_X3_ABLATE: an unsplit f32 operand as f16 sees it
-        if (!ablate || !(e->x3_ablate & bit)) return src;
+        if (!ablate || !(e->sw.x3_ablate & bit)) return src;
         hipLaunchKernelGGL(round_f16_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, src, to, n);
         return to;
     };
@@ -541,7 +541,7 @@ static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, boo
     // 16-bit attention kernel writes its output pre-split for the out-projection (the f32 buffers are reused at half their size)
     bool attn16 = false;
     if constexpr (std::is_same_v<T, float>) {
-        attn16 = e->split16 && e->x3_attn_hi == 3 && !qk_norm;
+        attn16 = e->split16 && e->sw.x3_attn_hi() == 3 && !qk_norm;
         if (attn16) {
             f16_t *q = reinterpret_cast<f16_t*>(w.q), *k = reinterpret_cast<f16_t*>(w.k), *vt = reinterpret_cast<f16_t*>(w.vt);
             CHK(f.gemm(w.xn, D, bw.qkv, 3 * inner, D,
@@ -565,7 +565,7 @@ static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, boo
         }
         HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
             return launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, N, w.Npad, attn_lens, B, f.lens_dev, pk.row_start, e->split16, pl,
-                                        e->x3_attn_hi);
+                                        e->sw.x3_attn_hi());
         }));
     }
     f.ablate(8, w.ao, inner);
@@ -619,7 +619,7 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
         HIPCHK(hipMemcpyAsync(w.h, w.x, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     const bool qk_norm = (c.options & F5_OPT_QK_RMSNORM) != 0;
     // weight prefetch from the LayerNorm launches (see layernorm_kernel): only where the GEMMs are latency-bound
-    const bool wpf = rows <= 4096 && !(getenv("F5_WEIGHT_PREFETCH") && getenv("F5_WEIGHT_PREFETCH")[0] == '0');
+    const bool wpf = rows <= 4096 && e->sw.weight_prefetch;
     auto prefetch = [&](const LinW<T>& a, const LinW<T>& b) {   // the weights of the two GEMMs behind a LayerNorm
         return wpf ? Prefetch{(const char*)a.w, (size_t)a.N * a.ldw * sizeof(T), (const char*)b.w, (size_t)b.N * b.ldw * sizeof(T)} : Prefetch{};
     };
@@ -749,11 +749,12 @@ static int run_backbone(f5_engine* e, Work<T>& w, const float* y, const float* c
     return run_unett_forward<T>(e, w, y, cond, B, Bp, N, w.temb + (size_t)step_row * e->cfg.dim, per_row_time ? e->cfg.dim : 0,
                                 lens_dev, drop_cond_first, text_first, text_second, s);
 }
-// lens bookkeeping: uploads per-sample lengths (duplicated for the uncond half) through pinned staging
+// uploads the call's small tables through pinned staging: nT times to w.tdev and, where lengths are given, the plan's lens and
+// row_start tables (SamplePlan::Chunk) and lens_plain
 template <typename T>
-static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, const int32_t* lens_host, int B,
-                        hipStream_t s, int chunk = 0, int halves = 2) {
-    if (chunk <= 0 || chunk > B) chunk = B;
+static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, const int32_t* lens_host, const SamplePlan& p,
+                        hipStream_t s) {
+    const int B = p.B;
     const size_t bytes = (size_t)nT * 4 + (size_t)3 * B * 4 + ((size_t)3 * B + 16) * 4 + 64;
     char* hb = nullptr;
     int slot = 0;
@@ -766,58 +767,46 @@ static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, c
     }
     if (lens_host) {
         const int add = e->cfg.backbone == F5_BACKBONE_UNETT ? 1 : 0;  // UNetT masks are left-padded for the time token
-        for (int u0 = 0; u0 < B; u0 += chunk) {   // chunk-major: [cond lens of the chunk][uncond lens of the chunk]
-            const int bc = std::min(chunk, B - u0);
-            for (int i = 0; i < bc; ++i) lh[2 * u0 + i] = lh[2 * u0 + bc + i] = lens_host[u0 + i] + add;
+        int* rs = lh + 3 * B;
+        int nrs = 0;
+        for (const SamplePlan::Chunk& k : p.chunks) {
+            // chunk-major: [cond lens of the chunk][uncond lens of the chunk]
+            int* l = lh + p.lens_at(k);
+            for (int i = 0; i < k.bc; ++i) l[i] = l[k.bc + i] = lens_host[k.u0 + i] + add;
+            // RowPack table: `halves` x bc batch rows (cond half, then uncond half), each rounded up to 4 rows
+            int* t = rs + p.row_start_at(k);
+            t[0] = 0;
+            for (int q = 0; q < p.halves * k.bc; ++q) t[q + 1] = t[q] + round_up(lens_host[k.u0 + q % k.bc], 4);
+            nrs = p.row_start_at(k) + p.halves * k.bc + 1;
         }
         for (int i = 0; i < B; ++i) lh[2 * B + i] = lens_host[i] + add;
         HIPCHK(hipMemcpyAsync(w.lens, lh, (size_t)2 * B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.lens_plain, lh + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, s));
-        // RowPack tables: per chunk, `halves` x Bc batch rows (cond half, then uncond half), each rounded up to 4 rows;
-        // chunk c's table starts at halves * u0 + c (every chunk has one entry more than it has batch rows)
-        int* rs = lh + 3 * B;
-        e->pack_rows_host.clear();
-        e->pack_sq_host.clear();
-        int cidx = 0, nrs = 0;
-        for (int u0 = 0; u0 < B; u0 += chunk, ++cidx) {
-            const int bc = std::min(chunk, B - u0);
-            int* t = rs + halves * u0 + cidx;
-            double sq = 0;
-            t[0] = 0;
-            for (int k = 0; k < halves * bc; ++k) {
-                const int len = lens_host[u0 + k % bc];
-                t[k + 1] = t[k] + round_up(len, 4);
-                sq += (double)len * len;
-            }
-            e->pack_rows_host.push_back((double)t[halves * bc]);
-            e->pack_sq_host.push_back(sq);
-            nrs = halves * u0 + cidx + halves * bc + 1;
-        }
         HIPCHK(hipMemcpyAsync(w.row_start, rs, (size_t)nrs * 4, hipMemcpyHostToDevice, s));
     }
     return e->stage.release(slot, s);
 }
 template <typename T>
-static int text_embed_impl(f5_engine* e, const int64_t* text, int B, int nt, const int32_t* lens_host, int N,
-                           int drop_text, float* out, hipStream_t s) {
+int EngineOps<T>::text_embed(f5_engine* e, const int64_t* text, int B, int nt, const int32_t* lens_host, int N, int drop_text,
+                             float* out, hipStream_t s) {
     CHK(ensure_arena(e, B, N, 1));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
-    CHK(upload_small<T>(e, w, nullptr, 0, lens_host, B, s));
+    CHK(upload_small<T>(e, w, nullptr, 0, lens_host, plan_sample(e, B, N, lens_host, B), s));
     const bool per_sample = lens_host && e->cfg.backbone == F5_BACKBONE_DIT;  // unett.py embeds at the padded length
     return run_text_embed<T>(e, w, text, B, nt, per_sample ? w.lens_plain : nullptr, N, drop_text, out, s);
 }
 template <typename T>
-static int forward_impl(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt,
-                        const float* time_host, const int32_t* lens_host, int B, int N, int cfg_infer,
-                        int drop_audio_cond, int drop_text, float* out, hipStream_t s) {
+int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
+                          const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
+                          hipStream_t s) {
     const int Bp = cfg_infer ? 2 * B : B;
     CHK(ensure_arena(e, B, N, Bp));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     std::vector<float> tt(Bp);
     for (int i = 0; i < Bp; ++i) tt[i] = time_host[i % B];
-    CHK(upload_small<T>(e, w, tt.data(), Bp, lens_host, B, s));
+    CHK(upload_small<T>(e, w, tt.data(), Bp, lens_host, plan_sample(e, B, N, lens_host, B), s));
     const int* lens_dev = lens_host ? w.lens : nullptr;
     CHK(run_time_path<T>(e, w, Bp, s));
     // UNetT embeds text at the padded length for every sample (unett.py:196-215), DiT at each sample's own length
@@ -860,20 +849,13 @@ static bool uc_cacheable(const f5_engine* e, int B, bool has_lens) {
 }
 
 // the stream-ordered body of sample(): everything between "inputs are in the arena" and "outputs are in the arena".
-// w.tdev holds the evaluation times (feature rows) and then the grid: Euler evaluates at t[0..steps-1], which IS the
-// grid's head, so tdev = t[0..steps] as uploaded; midpoint evaluates at t[i] (row 2i) and t[i] + dt/2 (row 2i+1), and
-// the grid follows at tdev + 2 steps (sample_impl).
-template <typename T>
-static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_strength, bool has_lens, int B, int N,
-                       bool want_traj, hipStream_t s, int method = F5_ODE_EULER) {
+// w.tdev holds the evaluation times (feature rows) and then the grid (engine.hip time_table).
+template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const SamplePlan& p, hipStream_t s) {
     const f5_config& c = e->cfg;
-    const int mel = c.mel_dim;
-    const bool use_cfg = !(cfg_strength < 1e-5f);
-    const bool mid = method == F5_ODE_MIDPOINT;
-    const int evals = mid ? 2 : 1;                           // backbone evaluations per step
-    const float* tgrid = mid ? w.tdev + 2 * steps : w.tdev;
-    const int Bp = use_cfg ? 2 * B : B;
-    const int* lens_dev = has_lens ? w.lens : nullptr;
+    const int mel = c.mel_dim, B = p.B, N = p.N;
+    const bool mid = p.method == F5_ODE_MIDPOINT;
+    const float* tgrid = mid ? w.tdev + 2 * p.steps : w.tdev;
+    const int* lens_dev = p.has_lens ? w.lens : nullptr;
     const long half = (long)B * N * mel;
     const int64_t* text = reinterpret_cast<const int64_t*>(w.in_text);
     // step_cond = where(cond_mask, cond, 0)   (cfm.py:151-153)
@@ -882,118 +864,94 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
                            w.in_mask, w.step_cond, (long)B * N, mel);
         return hipGetLastError();
     }));
-    CHK(run_time_path<T>(e, w, evals * steps, s));  // features of every evaluation time
-    const int* tlens = (c.backbone == F5_BACKBONE_DIT && has_lens) ? w.lens_plain : nullptr;
-    CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 0, w.text_c, s));
-    if (use_cfg) {
+    CHK(run_time_path<T>(e, w, p.evals * p.steps, s));  // features of every evaluation time
+    const int* tlens = (c.backbone == F5_BACKBONE_DIT && p.has_lens) ? w.lens_plain : nullptr;
+    CHK(run_text_embed<T>(e, w, text, B, p.nt, tlens, N, 0, w.text_c, s));
+    if (p.use_cfg) {
         const size_t ucn = (size_t)N * c.text_dim;
-        if (uc_cacheable(e, B, has_lens) && e->uc_N == N) {
+        if (uc_cacheable(e, B, p.has_lens) && e->uc_N == N) {
             HIPCHK(hipMemcpyAsync(w.text_u, w.uc, ucn * sizeof(float), hipMemcpyDeviceToDevice, s));
         } else {
-            CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 1, w.text_u, s));
-            if (uc_cacheable(e, B, has_lens)) {   // (never reached under capture: a cache miss always runs eagerly)
+            CHK(run_text_embed<T>(e, w, text, B, p.nt, tlens, N, 1, w.text_u, s));
+            if (uc_cacheable(e, B, p.has_lens)) {   // (never reached under capture: a cache miss always runs eagerly)
                 HIPCHK(hipMemcpyAsync(w.uc, w.text_u, ucn * sizeof(float), hipMemcpyDeviceToDevice, s));
                 e->uc_N = N;
             }
         }
     }
-    if (want_traj) HIPCHK(hipMemcpyAsync(w.traj_buf, w.y, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const bool split = use_cfg && c.backbone == F5_BACKBONE_DIT && !e->prof.on && split_cfg_enabled(e);
+    if (p.want_traj) HIPCHK(hipMemcpyAsync(w.traj_buf, w.y, half * sizeof(float), hipMemcpyDeviceToDevice, s));
     Work<T> w2 = w;
-    if (split) {
+    if (p.split) {
         w2 = second_half<T>(e, w, B, N);
         if (!e->side_stream) HIPCHK(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
         if (!e->ev_fork) HIPCHK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
         if (!e->ev_join) HIPCHK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
     }
-    const int chunk = e->cur_chunk;   // (chunk_utts, decided by sample_impl, which laid w.lens / w.row_start out for this size)
     // packed variable-length batch (RowPack): the row tables of every chunk, built once from the uploaded prefix sums
-    const bool pack = has_lens && pack_rows_enabled(e);
-    const int halves = use_cfg ? 2 : 1;
-    auto chunk_pack = [&](int u0, int cidx, int bc) {
-        RowPack pk;
-        if (!pack) return pk;
-        pk.row_start = w.row_start + halves * u0 + cidx;
-        pk.rowmap = w.rowmap + (size_t)2 * u0 * round_up(N, 4);
-        pk.rows_dev = pk.row_start + halves * bc;
-        if ((size_t)cidx < e->pack_rows_host.size()) { pk.rows_host = e->pack_rows_host[cidx]; pk.sq_host = e->pack_sq_host[cidx]; }
-        return pk;
+    std::vector<RowPack> packs(p.chunks.size());
+    for (const SamplePlan::Chunk& k : p.chunks) {
+        if (!p.pack) break;
+        const int* rs = w.row_start + p.row_start_at(k);
+        packs[k.idx] = RowPack{rs, w.rowmap + p.rowmap_at(k), rs + p.halves * k.bc, k.rows, k.sq};
+        hipLaunchKernelGGL(fill_rowmap_kernel, dim3(p.halves * k.bc), dim3(256), 0, s, rs, w.rowmap + p.rowmap_at(k));
+        KCHK();
+    }
+    // one (CFG) evaluation of a chunk at state x with the vectors of time row `row`, into w.pred
+    auto eval = [&](const SamplePlan::Chunk& k, const RowPack& pk, const float* x, int row) -> int {
+        const size_t yo = p.frame_at(k) * mel, to = p.frame_at(k) * c.text_dim;
+        const float *cond = w.step_cond + yo, *tc = w.text_c + to, *tu = w.text_u + to;
+        const int* lens = lens_dev ? lens_dev + p.lens_at(k) : nullptr;
+        if (!p.split) return run_backbone<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, row, 0, lens, 0, tc, p.use_cfg ? tu : tc, s, pk);
+        // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
+        hipStream_t s1 = e->side_stream;
+        HIPCHK(hipEventRecord(e->ev_fork, s));            // x (and, first time, the text embeddings) ready
+        HIPCHK(hipStreamWaitEvent(s1, e->ev_fork, 0));
+        CHK(run_backbone<T>(e, w, x, cond, k.bc, k.bc, N, row, 0, lens, 0, tc, tc, s));
+        CHK(run_backbone<T>(e, w2, x, cond, k.bc, k.bc, N, row, 0, lens, 1, tu, tu, s1));
+        HIPCHK(hipEventRecord(e->ev_join, s1));
+        HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));
+        return F5_OK;
     };
-    if (pack) {
-        int cidx = 0;
-        for (int u0 = 0; u0 < B; u0 += chunk, ++cidx) {
-            const int bc = std::min(chunk, B - u0);
-            const RowPack pk = chunk_pack(u0, cidx, bc);
-            hipLaunchKernelGGL(fill_rowmap_kernel, dim3(halves * bc), dim3(256), 0, s, pk.row_start, const_cast<int2*>(pk.rowmap));
-            KCHK();
-        }
-    }
-    for (int i = 0; i < steps; ++i) {
-        if (split) {
-            hipStream_t s1 = e->side_stream;
-            // one CFG evaluation at state x: conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
-            auto split_eval = [&](const float* x, int row) -> int {
-                HIPCHK(hipEventRecord(e->ev_fork, s));            // x (and, first time, the text embeddings) ready
-                HIPCHK(hipStreamWaitEvent(s1, e->ev_fork, 0));
-                CHK(run_backbone<T>(e, w, x, w.step_cond, B, B, N, row, 0, lens_dev, 0, w.text_c, w.text_c, s));
-                CHK(run_backbone<T>(e, w2, x, w.step_cond, B, B, N, row, 0, lens_dev, 1, w.text_u, w.text_u, s1));
-                HIPCHK(hipEventRecord(e->ev_join, s1));
-                HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));
-                return F5_OK;
-            };
-            CHK(split_eval(w.y, evals * i));
+    // y_mid = y + f(t[i], y) * dt/2
+    auto half_update = [&](const SamplePlan::Chunk& k, const RowPack& pk, int i) {
+        const size_t yo = p.frame_at(k) * mel;
+        const long n = (long)k.bc * N * mel;
+        return e->prof.timed(PC_MISC, s, [&] {
+            if (pk)
+                hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, k.bc, N, mel,
+                                   pk.row_start, lens_dev + p.lens_at(k), tgrid, i, p.cfg_strength, p.use_cfg ? 1 : 0, w.y_mid + yo);
+            else
+                hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, n, tgrid, i,
+                                   p.cfg_strength, p.use_cfg ? 1 : 0, w.y_mid + yo);
+            return hipGetLastError();
+        });
+    };
+    // y += f * dt (f: Euler at t[i], y; midpoint at t[i] + dt/2, y_mid), copied to the trajectory slot of step i + 1
+    auto full_update = [&](const SamplePlan::Chunk& k, const RowPack& pk, int i) {
+        const size_t yo = p.frame_at(k) * mel;
+        const long n = (long)k.bc * N * mel;
+        float* slot = p.want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
+        return e->prof.timed(PC_MISC, s, [&] {
+            if (pk)
+                hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, k.bc, N, mel,
+                                   pk.row_start, lens_dev + p.lens_at(k), tgrid, i, p.cfg_strength, p.use_cfg ? 1 : 0, slot);
+            else
+                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, n, tgrid, i,
+                                   p.cfg_strength, p.use_cfg ? 1 : 0, slot);
+            return hipGetLastError();
+        });
+    };
+    for (int i = 0; i < p.steps; ++i)
+        for (const SamplePlan::Chunk& k : p.chunks) {
+            const RowPack& pk = packs[k.idx];
+            const size_t yo = p.frame_at(k) * mel;
+            CHK(eval(k, pk, w.y + yo, p.evals * i));
             if (mid) {
-                HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-                    hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
-                                       cfg_strength, use_cfg ? 1 : 0, w.y_mid);
-                    return hipGetLastError();
-                }));
-                CHK(split_eval(w.y_mid, 2 * i + 1));
+                HIPCHK(half_update(k, pk, i));
+                CHK(eval(k, pk, w.y_mid + yo, 2 * i + 1));
             }
-            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.y, w.pred, half, tgrid, i,
-                                   cfg_strength, use_cfg ? 1 : 0, want_traj ? w.traj_buf + (size_t)(i + 1) * half : nullptr);
-                return hipGetLastError();
-            }));
-            continue;
+            HIPCHK(full_update(k, pk, i));
         }
-        int cidx = 0;
-        for (int u0 = 0; u0 < B; u0 += chunk, ++cidx) {
-            const int bc = std::min(chunk, B - u0);
-            const size_t yo = (size_t)u0 * N * mel, to = (size_t)u0 * N * c.text_dim;
-            const long half_c = (long)bc * N * mel;
-            const RowPack pk = chunk_pack(u0, cidx, bc);
-            auto eval = [&](const float* x, int row) {
-                return run_backbone<T>(e, w, x, w.step_cond + yo, bc, use_cfg ? 2 * bc : bc, N, row, 0,
-                                       lens_dev ? lens_dev + 2 * u0 : nullptr, 0, w.text_c + to,
-                                       use_cfg ? w.text_u + to : w.text_c + to, s, pk);
-            };
-            CHK(eval(w.y + yo, evals * i));
-            if (mid) {   // y_mid = y + f(t[i], y) * dt/2, then the full step below on f(t[i] + dt/2, y_mid)
-                HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-                    if (pk)
-                        hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred,
-                                           bc, N, mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0,
-                                           w.y_mid + yo);
-                    else
-                        hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c,
-                                           tgrid, i, cfg_strength, use_cfg ? 1 : 0, w.y_mid + yo);
-                    return hipGetLastError();
-                }));
-                CHK(eval(w.y_mid + yo, 2 * i + 1));
-            }
-            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-                float* slot = want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
-                if (pk)
-                    hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, bc, N,
-                                       mel, pk.row_start, lens_dev + 2 * u0, tgrid, i, cfg_strength, use_cfg ? 1 : 0, slot);
-                else
-                    hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(half_c / 4)), dim3(256), 0, s, w.y + yo, w.pred, half_c, tgrid,
-                                       i, cfg_strength, use_cfg ? 1 : 0, slot);
-                return hipGetLastError();
-            }));
-        }
-    }
     // out = where(cond_mask, cond, y)   (cfm.py:221-223)
     HIPCHK(e->prof.timed(PC_MISC, s, [&] {
         hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)w.y, w.in_mask,
@@ -1002,10 +960,12 @@ static int sample_body(f5_engine* e, Work<T>& w, int nt, int steps, float cfg_st
     }));
     return F5_OK;
 }
+// sample(): plan, stage the inputs into the arena, key, replay / capture / eager, copy the outputs
 template <typename T>
-static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
-                       int nt, const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N,
-                       float* out, float* traj, hipStream_t s, int method) {
+int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
+                         const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
+                         float* traj, hipStream_t s, int method) {
+    const SamplePlan p = plan_sample(e, B, N, lens_host, 0, nt, steps, method, cfg_strength, traj != nullptr);
     const int mel = e->cfg.mel_dim;
     const long half = (long)B * N * mel;
     if (nt > e->res_nt) {   // the text staging buffer is part of the arena plan
@@ -1016,20 +976,8 @@ static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const u
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     // ---- inputs -> arena (eager, on the caller's stream)
-    e->cur_chunk = chunk_utts(e, B, N, !(cfg_strength < 1e-5f), lens_host);
-    if (method == F5_ODE_MIDPOINT) {
-        // evaluation times t[i], t[i] + dt/2 (f32, in torchdiffeq's order: half_dt = 0.5 * (t[i+1] - t[i])), then the grid
-        std::vector<float> tt((size_t)3 * steps + 1);
-        for (int i = 0; i < steps; ++i) {
-            const float hdt = 0.5f * (t_host[i + 1] - t_host[i]);
-            tt[2 * i] = t_host[i];
-            tt[2 * i + 1] = t_host[i] + hdt;
-        }
-        std::copy(t_host, t_host + steps + 1, tt.begin() + 2 * steps);
-        CHK(upload_small<T>(e, w, tt.data(), 3 * steps + 1, lens_host, B, s, e->cur_chunk, cfg_strength < 1e-5f ? 1 : 2));
-    } else {
-        CHK(upload_small<T>(e, w, t_host, steps + 1, lens_host, B, s, e->cur_chunk, cfg_strength < 1e-5f ? 1 : 2));
-    }
+    const std::vector<float> tt = time_table(t_host, steps, method);
+    CHK(upload_small<T>(e, w, tt.data(), (int)tt.size(), lens_host, p, s));
     if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
     if (cond_frames > 0)
         HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
@@ -1037,72 +985,29 @@ static int sample_impl(f5_engine* e, const float* cond, int cond_frames, const u
     HIPCHK(hipMemcpyAsync(w.y, y0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    // ---- body: replay a captured graph when this signature has been seen, else run eagerly (and remember it)
-    const bool use_cfg = !(cfg_strength < 1e-5f);
-    const bool uc_ok = use_cfg && uc_cacheable(e, B, lens_host != nullptr);
+    // ---- key: the signature, and whether the body reads the cached unconditional text embedding (a call that stores it runs eagerly)
+    const bool uc_ok = p.use_cfg && uc_cacheable(e, B, p.has_lens);
     const bool uc_hit = uc_ok && e->uc_N == N;
-    const bool uc_store = uc_ok && !uc_hit;
-    unsigned cfg_bits;
-    memcpy(&cfg_bits, &cfg_strength, 4);
-    char kb[160];
-    snprintf(kb, sizeof(kb), "%d|%d|%d|%d|%08x|%d|%d|%d|m%d", B, N, nt, steps, cfg_bits, lens_host ? 1 : 0, traj ? 1 : 0,
-             e->cur_chunk, method);
-    const std::string base_key(kb);
-    const std::string key = base_key + (uc_hit ? "|uc" : "|nouc");
-    bool done = false;
+    const std::string base_key = graph_key(p), key = base_key + (uc_hit ? "|uc" : "|nouc");
+    // ---- body: replay the captured graph of this key, capture it when the signature has run before, else run eagerly (and remember it)
     static const bool trace = getenv("F5_TRACE") && getenv("F5_TRACE")[0] == '1';   // diagnostic: which path a call takes
     const auto t_body = std::chrono::steady_clock::now();
-    auto trace_done = [&](const char* how) {
-        if (trace)
-            fprintf(stderr, "libf5hip: sample %s [%s]: host %.3f ms\n", key.c_str(), how,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body).count());
-    };
-    if (graphs_enabled(e) && !e->prof.on && !uc_store) {
-        for (auto& g : e->graphs)
-            if (g.key == key) {
-                HIPCHK(hipGraphLaunch(g.exec, s));
-                done = true;
-                trace_done("graph replay");
-                break;
-            }
-        const bool is_warm = std::find(e->warm.begin(), e->warm.end(), base_key) != e->warm.end();
-        if (!done && is_warm) {
-            if (!e->cap_stream) HIPCHK(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                const int rc = sample_body<T>(e, w, nt, steps, cfg_strength, lens_host != nullptr, B, N, traj != nullptr, e->cap_stream,
-                                              method);
-                const hipError_t ce = hipStreamEndCapture(e->cap_stream, &graph);
-                if (rc == F5_OK && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                    if (e->graphs.size() >= 16) {
-                        (void)hipGraphExecDestroy(e->graphs.front().exec);
-                        (void)hipGraphDestroy(e->graphs.front().graph);
-                        e->graphs.erase(e->graphs.begin());
-                    }
-                    e->graphs.push_back({key, graph, exec});
-                    HIPCHK(hipGraphLaunch(exec, s));
-                    done = true;
-                    trace_done("graph capture + instantiate + launch");
-                } else {
-                    // capture is an optimisation: fall back to eager launches, but say so (the wall time doubles on a busy host)
-                    fprintf(stderr, "libf5hip: HIP graph capture of sample() failed (body rc %d, end-capture: %s, last: %s); "
-                                    "continuing with eager launches\n", rc, hipGetErrorString(ce), hipGetErrorString(hipGetLastError()));
-                    if (graph) (void)hipGraphDestroy(graph);
-                    e->graphs_on = 0;
-                }
-            } else {
-                fprintf(stderr, "libf5hip: hipStreamBeginCapture failed (%s); continuing with eager launches\n",
-                        hipGetErrorString(hipGetLastError()));
-                e->graphs_on = 0;
-            }
+    hipGraphExec_t exec = nullptr;
+    const char* how = "eager launches";
+    if (e->sw.graphs && !e->gc.disabled && !e->prof.on && !(uc_ok && !uc_hit)) {
+        if ((exec = e->gc.find(key))) {
+            how = "graph replay";
+        } else if (e->gc.is_warm(base_key)) {
+            CHK(e->gc.capture(key, [&](hipStream_t cs) { return sample_body<T>(e, w, p, cs); }, &exec));
+            if (exec) how = "graph capture + instantiate + launch";
         }
     }
-    if (!done) {
-        CHK(sample_body<T>(e, w, nt, steps, cfg_strength, lens_host != nullptr, B, N, traj != nullptr, s, method));
-        trace_done("eager launches");
-        if (std::find(e->warm.begin(), e->warm.end(), base_key) == e->warm.end()) e->warm.push_back(base_key);
-    }
+    if (exec) HIPCHK(hipGraphLaunch(exec, s));
+    else CHK(sample_body<T>(e, w, p, s));
+    if (trace)
+        fprintf(stderr, "libf5hip: sample %s [%s]: host %.3f ms\n", key.c_str(), how,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body).count());
+    if (!exec) e->gc.mark_warm(base_key);
     // ---- outputs -> caller
     HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1115,22 +1020,4 @@ template <typename T> size_t EngineOps<T>::plan_bytes(const f5_engine* e, int B,
     Arena dry;  // base == nullptr: measures only
     Work<T> w;
     return carve_into<T>(e, dry, w, B, N, S);
-}
-template <typename T>
-int EngineOps<T>::text_embed(f5_engine* e, const int64_t* text, int B, int nt, const int32_t* lens_host, int N, int drop_text,
-                             float* out, hipStream_t s) {
-    return text_embed_impl<T>(e, text, B, nt, lens_host, N, drop_text, out, s);
-}
-template <typename T>
-int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
-                          const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
-                          hipStream_t s) {
-    return forward_impl<T>(e, x, cond, text, nt, time_host, lens_host, B, N, cfg_infer, drop_audio_cond, drop_text, out, s);
-}
-template <typename T>
-int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
-                         const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
-                         float* traj, hipStream_t s, int method) {
-    return sample_impl<T>(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj, s,
-                          method);
 }

@@ -210,11 +210,17 @@ struct f5_adapter {
     }
 };
 
-struct f5_engine {
-    f5_config cfg{};
-    int inner = 0, kin = 0, kin_pad = 0, modN = 0;
-    bool io_split = false;     // F5_PREC_F16P: the f16 engine with its input / output layers as split-f16 products on f32 operands
-    bool split16 = false;      // F5_PREC_F16X3: the f32 engine with the backbone GEMMs on the f16 pipe (gemm2.h MODE 3)
+// Runtime switches: read once from the environment, in f5_create (engine.hip read_switches; the table in INTEGRATION.md).
+struct Switches {
+    bool graphs = true;            // F5_HIP_GRAPH=0: launch the sample() body eagerly
+    // The conditional and unconditional halves of a CFG forward are independent until the Euler update: run them as two
+    // concurrent kernel chains (second stream, fork/join events) so that one chain's launch ramps / drains overlap
+    // the other chain's main loops.  Opt-in with F5_SPLIT_CFG=1: 35.4 ms as two eager chains, 35.2 ms as a two-branch
+    // hipGraph, against 34.4 ms packed.  It steps the whole batch per half, on padded rows.
+    bool split_cfg = false;
+    bool pack_rows = true;         // F5_PACK_ROWS=0: attn_mask_enabled DiT batches on padded rows (no RowPack)
+    long chunk_rows = 0;           // F5_CHUNK_ROWS: fixed row budget of one backbone call inside sample(); 0: unset (chunk_utts)
+    bool weight_prefetch = true;   // F5_WEIGHT_PREFETCH=0: the LayerNorm launches do not prefetch the weights of the GEMMs behind them
     // Diagnostic (F5_X3_ABLATE=<bitmask>, F5_PREC_F16X3 only; tools/x3_ablate.py): contraction classes run with plain f16 products
     // (hi x hi only) instead of the three split products: 1 QKV, 2 attention K Q^T, 4 attention V^T P^T, 8 out-proj, 16 FF1, 32 FF2,
     // 64 input projection, 128 conv position embedding, 256 output projection
@@ -222,7 +228,72 @@ struct f5_engine {
     // F5_PREC_F16X3 attention: both products (K Q^T, V^T P^T) as PLAIN f16 products on the split operands' hi halves -- measured harmless
     // (tools/x3_ablate.py: DiT C2 1.10e-5 -> 1.01e-5, E2-TTS UNetT 1.7e-5 -> 5.2e-5; every GEMM class costs ~1e-3 there) and 7-9 % of
     // the f16x3 step.  F5_X3_ATTN_SPLIT=1 restores the three split products (and lets F5_X3_ABLATE bits 2 / 4 select).
-    int x3_attn_hi = 3;
+    bool x3_attn_split = false;
+    int x3_attn_hi() const { return x3_attn_split ? (x3_ablate >> 1) & 3 : 3; }
+};
+
+// HIP graphs of whole sample() bodies (one per problem signature): ~2600 launches per utterance become one
+// hipGraphLaunch, so the host (shared, sometimes slow) can never be the bottleneck of the ODE loop.  A signature is
+// captured the second time it is seen: its first call runs eagerly and marks it warm.
+struct GraphCache {
+    struct Entry { std::string key; hipGraph_t graph; hipGraphExec_t exec; };
+    std::vector<Entry> graphs;
+    std::vector<std::string> warm;      // signatures (without cache state) that have run eagerly once
+    hipStream_t cap_stream = nullptr;
+    bool disabled = false;              // a capture failed: stop trying (the user's switch is Switches::graphs)
+    GraphCache() = default;
+    GraphCache(const GraphCache&) = delete;   // owns HIP handles (f5_engine's destructor releases them)
+    void clear() {
+        while (!graphs.empty()) evict(0);
+        warm.clear();
+    }
+    hipGraphExec_t find(const std::string& key) const {
+        for (auto& g : graphs)
+            if (g.key == key) return g.exec;
+        return nullptr;
+    }
+    bool is_warm(const std::string& base_key) const { return std::find(warm.begin(), warm.end(), base_key) != warm.end(); }
+    void mark_warm(const std::string& base_key) {
+        if (!is_warm(base_key)) warm.push_back(base_key);
+    }
+    // Captures the launches of body(cap_stream) and instantiates them as *exec; the oldest of 16 entries makes room.  Capture is an
+    // optimisation: when it fails the cache says so, *exec stays null (the caller launches eagerly) and no later call tries again.
+    template <typename F> int capture(const std::string& key, F&& body, hipGraphExec_t* exec) {
+        if (!cap_stream) HIPCHK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
+        hipGraph_t graph = nullptr;
+        if (hipStreamBeginCapture(cap_stream, hipStreamCaptureModeRelaxed) != hipSuccess) {
+            fprintf(stderr, "libf5hip: hipStreamBeginCapture failed (%s); continuing with eager launches\n",
+                    hipGetErrorString(hipGetLastError()));
+        } else {
+            const int rc = body(cap_stream);
+            const hipError_t ce = hipStreamEndCapture(cap_stream, &graph);
+            if (rc == F5_OK && ce == hipSuccess && graph && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+                if (graphs.size() >= 16) evict(0);
+                graphs.push_back({key, graph, *exec});
+                return F5_OK;
+            }
+            // (say so: the wall time doubles on a busy host)
+            fprintf(stderr, "libf5hip: HIP graph capture of sample() failed (body rc %d, end-capture: %s, last: %s); "
+                            "continuing with eager launches\n", rc, hipGetErrorString(ce), hipGetErrorString(hipGetLastError()));
+            if (graph) (void)hipGraphDestroy(graph);
+        }
+        *exec = nullptr;
+        disabled = true;
+        return F5_OK;
+    }
+    void evict(size_t i) {
+        if (graphs[i].exec) (void)hipGraphExecDestroy(graphs[i].exec);
+        if (graphs[i].graph) (void)hipGraphDestroy(graphs[i].graph);
+        graphs.erase(graphs.begin() + i);
+    }
+};
+
+struct f5_engine {
+    f5_config cfg{};
+    int inner = 0, kin = 0, kin_pad = 0, modN = 0;
+    bool io_split = false;     // F5_PREC_F16P: the f16 engine with its input / output layers as split-f16 products on f32 operands
+    bool split16 = false;      // F5_PREC_F16X3: the f32 engine with the backbone GEMMs on the f16 pipe (gemm2.h MODE 3)
+    Switches sw;
     WeightStore ws;
     std::vector<void*> owned;  // packed buffers
     Packed<float> pf;
@@ -238,25 +309,11 @@ struct f5_engine {
     // The buffer lives in the arena (Work::uc), so its lifetime and the invalidation of captured graphs follow every
     // other captured pointer; uc_N = -1 whenever the arena moves or the weights change.
     int uc_N = -1;
-    // HIP graphs of whole sample() bodies (one per problem signature): ~2600 launches per utterance become one
-    // hipGraphLaunch, so the host (shared, sometimes slow) can never be the bottleneck of the ODE loop.
-    struct GraphEntry { std::string key; hipGraph_t graph; hipGraphExec_t exec; };
-    std::vector<GraphEntry> graphs;
-    std::vector<std::string> warm;      // signatures (without cache state) that have run eagerly once
-    hipStream_t cap_stream = nullptr;
-    int graphs_on = -1;                 // -1: read F5_HIP_GRAPH from the environment on first use
-    // The conditional and unconditional halves of a CFG forward are independent until the Euler update: run them as two
-    // concurrent kernel chains (second stream, fork/join events) so that one chain's launch ramps / drains overlap
-    // the other chain's main loops.  Opt-in with F5_SPLIT_CFG=1 (see split_cfg_enabled).
+    GraphCache gc;
+    // F5_SPLIT_CFG (SamplePlan::split): the side stream and the fork / join events, made by the first call that needs them
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int split_cfg = -1;
     int res_nt = 0;
-    int cur_chunk = 0;   // utterances per backbone call of the sample() in progress (chunk_utts, decided once per call)
-    // packed variable-length batches (RowPack): per chunk of the last upload, rows present and sum of squared lengths
-    // (host copies, used for the profiler's FLOP counts only) and the switch (F5_PACK_ROWS, default on)
-    std::vector<double> pack_rows_host, pack_sq_host;
-    int pack_rows = -1;
     // resident adapters (F5_OPT_ADAPTERS; adapter.hip)
     bool adapters_on = false;
     std::vector<AdaptTarget> targets;
@@ -265,18 +322,11 @@ struct f5_engine {
     f5_adapter* active = nullptr;
     std::vector<f5_adapter*> adapters;   // every live adapter bound to this engine
     unsigned adapt_gen = 0;
-    void clear_graphs() {
-        for (auto& g : graphs) {
-            if (g.exec) (void)hipGraphExecDestroy(g.exec);
-            if (g.graph) (void)hipGraphDestroy(g.graph);
-        }
-        graphs.clear();
-        warm.clear();
-    }
+    void clear_graphs() { gc.clear(); }
     ~f5_engine() {
         for (f5_adapter* a : adapters) a->eng = nullptr;
         clear_graphs();
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
+        if (gc.cap_stream) (void)hipStreamDestroy(gc.cap_stream);
         if (side_stream) (void)hipStreamDestroy(side_stream);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
@@ -336,12 +386,35 @@ struct RowPack {
     explicit operator bool() const { return row_start != nullptr; }
 };
 
+// What one sample() call decides before it launches anything (engine.hip plan_sample); upload_small, sample_body and the graph key
+// read it, nothing re-derives it.  The ODE state of different utterances never interacts, so the batch is stepped in chunks of
+// `chunk` utterances (chunk_utts).
+struct SamplePlan {
+    struct Chunk { int idx, u0, bc; double rows, sq; };   // number, first utterance, utterances; packed rows present and sum of squared lengths (host: FLOP counts, tile choice)
+    int B = 0, N = 0, nt = 0, steps = 0, method = F5_ODE_EULER;
+    float cfg_strength = 0.f;
+    bool use_cfg = true, has_lens = false, want_traj = false;
+    int halves = 2;       // batch rows per utterance in a backbone call: cond + uncond, or 1 without CFG
+    int evals = 1;        // backbone evaluations per step (midpoint: 2)
+    bool pack = false;    // RowPack: attn_mask_enabled DiT batches with lengths, unless F5_PACK_ROWS=0 or F5_SPLIT_CFG=1
+    bool split = false;   // F5_SPLIT_CFG=1: the halves as two stream chains (DiT with CFG, profiler off); one chunk, no packing
+    int chunk = 0;
+    std::vector<Chunk> chunks;
+    // Where a chunk lives in the per-call tables.  Work::lens holds [bc][the same bc] per chunk whatever `halves` is; a chunk's
+    // row_start table has halves * bc + 1 entries; rowmap is carved for 2 B rows of round_up(N, 4); state, cond and text are [B, N, *].
+    int lens_at(const Chunk& k) const { return 2 * k.u0; }
+    int row_start_at(const Chunk& k) const { return halves * k.u0 + k.idx; }
+    size_t rowmap_at(const Chunk& k) const { return (size_t)2 * k.u0 * round_up(N, 4); }
+    size_t frame_at(const Chunk& k) const { return (size_t)k.u0 * N; }
+};
+
 // ------------------------------------------------------------------------------------ shared host helpers (engine.hip)
 int ensure_arena(f5_engine* e, int B, int N, int S);
-int chunk_utts(f5_engine* e, int B, int N, bool use_cfg, const int32_t* lens_host = nullptr);
-bool split_cfg_enabled(f5_engine* e);
-bool graphs_enabled(f5_engine* e);
-bool pack_rows_enabled(f5_engine* e);
+// (text_embed / forward pass chunk = B: the whole batch as one chunk, both halves; 0: chunk_utts decides)
+SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk = 0, int nt = 0, int steps = 0,
+                       int method = F5_ODE_EULER, float cfg_strength = 1.f, bool want_traj = false);
+std::string graph_key(const SamplePlan& p);
+std::vector<float> time_table(const float* t_host, int steps, int method);
 
 // Entry points of one operand precision T (float: exact-f32 MFMA; bf16_t / f16_t: 16-bit MFMA operands, f32 accumulate).
 template <typename T> struct EngineOps {
