@@ -144,6 +144,34 @@ int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const ui
  * max_steps covers both solvers: a midpoint call with steps <= max_steps needs no regrowth. */
 int f5_reserve(f5_engine* e, int32_t max_batch, int32_t max_frames, int32_t max_steps);
 
+/* --------------------------------------------------------------------------------------- length buckets
+ * A serving stream gives f5_sample a different N on almost every call, and a captured HIP graph is keyed on the exact shape: such a
+ * stream never replays.  With a length bucket of `granule` frames an eligible call is planned at N_cap = N rounded up to the granule
+ * -- arena layout, launch grids and the graph key use N_cap -- while the true N reaches the kernels through the device-side length
+ * tables of the packed (RowPack) body and through the copies around it, so one captured graph serves every N of a bucket and every
+ * text length.  The frames N .. N_cap-1 are never copied out, and `out` / `traj` are, bit for bit, what the exact path computes.
+ *
+ * Eligible: the DiT backbone; lens_host NULL or every entry equal to N; F5_SPLIT_CFG off; the profiler off; no
+ * F5_OPT_TEXT_AVG_UPSAMPLE; N_cap inside the rotary and text position tables.  Every other call takes the exact path under its
+ * exact key, silently.  The unconditional text embedding is computed inside the body on every bucketed call (no per-N cache).
+ *
+ * granule: 0 = off (the default; F5_LEN_BUCKET=<granule> sets it at f5_create), else a multiple of 8 in [8, 1024]; anything else is
+ * F5_EINVAL.  Clears the graph cache. */
+int f5_set_length_buckets(f5_engine* e, int32_t granule);
+/* Captures and instantiates, without launching anything, one graph per bucket that the lengths n_min .. n_max touch, for f5_sample_ode
+ * calls with this B, steps, cfg_strength, method and traj != NULL (want_traj), and any text of at most nt_max tokens; sizes the arena for
+ * the largest bucket first.  Afterwards the first eligible call at any N of the range replays.  Calls outside these arguments
+ * that grow the arena (a larger B, N, steps or text) drop the prepared graphs, as they drop every graph.  The graph cache holds 16
+ * graphs, or as many as one f5_prepare_sample call asked for, 64 at most: a range of more buckets is F5_EINVAL, and so is one whose
+ * largest bucket exceeds max_pos.  F5_ESTATE with buckets off, before f5_finalize, with F5_HIP_GRAPH=0 or when no call of this
+ * engine can be eligible.  Host work only (allocates); `stream` is not used. */
+int f5_prepare_sample(f5_engine* e, int32_t B, int32_t n_min, int32_t n_max, int32_t nt_max, int32_t steps, float cfg_strength,
+                      int32_t method, int32_t want_traj, f5_stream stream);
+/* out[0..3] = f5_sample bodies captured into a graph (the capturing call launches its graph, and counts here only), replayed from the
+ * cache, launched eagerly, and graphs pushed out of the cache by a newer one -- since f5_create or the last reset.  out == NULL
+ * resets the four counters.  Reads four integers: no device work. */
+int f5_graph_stats(f5_engine* e, int32_t* out);
+
 /* ------------------------------------------------------------------------------------- resident adapters
  * One resident base model, many LoRA fine-tunes of it (train/train_lora.py: low-rank pairs on the attention linears of every
  * DiT block and on input_embed.proj, the text encoder trained in full).  Switching MERGES, as the reference does before it runs

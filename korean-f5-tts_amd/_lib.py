@@ -73,6 +73,9 @@ SIGNATURES = {
     "f5_sample": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p]),
     "f5_sample_ode": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_reserve": (_i, [_p, _i, _i, _i]),
+    "f5_set_length_buckets": (_i, [_p, _i]),
+    "f5_prepare_sample": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
+    "f5_graph_stats": (_i, [_p, C.POINTER(_i)]),
     "f5_adapter_create": (_i, [_p, C.POINTER(_p)]),
     "f5_adapter_destroy": (_i, [_p]),
     "f5_adapter_put_lora": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p, C.POINTER(C.c_int64), _i, _f, _p]),

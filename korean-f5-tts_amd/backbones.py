@@ -13,11 +13,21 @@ from .config import normalize_arch
 from .engine import Engine
 
 
+def valid_length_bucket(granule: int) -> bool:
+    return granule == 0 or (8 <= granule <= 1024 and granule % 8 == 0)
+
+
+def bucket_ceiling(n: int, granule: int) -> int:
+    """The length a sample() call of n frames is planned at under a length bucket of `granule` frames (0: n itself)."""
+    return n if not granule else -(-n // granule) * granule
+
+
 class _HipBackbone(nn.Module):
     backbone_name = "DiT"
 
     def __init__(self, *, mel_dim=100, text_num_embeds=256, precision="parity", device=None, max_pos=8192, **arch):
         super().__init__()
+        self.length_bucket = 0              # granule of the length-bucketed sample() graphs; 0: off (set_length_buckets)
         # "parity" (the default): the fastest operand precision measured inside the 1e-3 mel bar of the fp32 CPU path for THIS backbone
         # (DESIGN.md section 3): DiT "f16p" (f16 blocks, split-f16 input / output layers); the E2-TTS UNetT has no AdaLN gates and
         # every one of its GEMM classes costs ~1e-3 in plain f16, so it gets "f16x3" (split-f16 GEMM products, f16 attention products)
@@ -84,6 +94,8 @@ class _HipBackbone(nn.Module):
             e = Engine(self.arch, self.text_num_embeds, self.mel_dim, backbone=self.backbone_name,
                        precision=self.precision, device=dev, max_pos=self.max_pos, adapters=bool(self._adapters))
             e.load_state_dict(self._sd)
+            if self.length_bucket:
+                e.set_length_buckets(self.length_bucket)
             self._engine = e
             for name, (pairs, full) in self._adapters.items():
                 self._adapter_handles[name] = e.new_adapter(pairs, full)
@@ -95,6 +107,30 @@ class _HipBackbone(nn.Module):
         """Forgets the engine (and the adapter handles that belong to it); the next engine() builds a new one."""
         self._adapter_handles = {}   # (the Engine frees them with itself)
         self._engine = None
+
+    # ---- length-bucketed sample() graphs ------------------------------------------------------------------------
+    def set_length_buckets(self, granule: int):
+        """Plans eligible sample() calls at their length rounded up to `granule` frames (a multiple of 8 in [8, 1024]; 0: off),
+        so that one captured HIP graph serves every length of a bucket; results do not change.  Survives engine rebuilds."""
+        if self.backbone_name != "DiT":
+            raise NotImplementedError("length buckets are built for the DiT backbone only")
+        granule = int(granule)
+        if not valid_length_bucket(granule):
+            raise ValueError(f"length bucket {granule}: expected 0 (off) or a multiple of 8 in [8, 1024]")
+        self.length_bucket = granule
+        if self._engine is not None:
+            self._engine.set_length_buckets(granule)
+
+    def prepare_sample(self, batch: int, n_min: int, n_max: int, nt_max: int, steps: int, cfg_strength: float, *,
+                       method: str = "euler", want_traj: bool = True):
+        """Captures the graphs of every length bucket that durations n_min .. n_max touch before the first request
+        (CFM.sample's arguments: steps after any duplicate_test shortening, texts of at most nt_max tokens)."""
+        if self.backbone_name != "DiT":
+            raise NotImplementedError("length buckets are built for the DiT backbone only")
+        self.engine().prepare_sample(batch, n_min, n_max, nt_max, steps, cfg_strength, method=method, want_traj=want_traj)
+
+    def graph_stats(self, reset: bool = False) -> dict:
+        return self.engine().graph_stats(reset)
 
     # ---- resident LoRA adapters (the interface PEFT users know: add / set / delete) ---------------------------
     @property

@@ -52,6 +52,7 @@ static Switches read_switches(const f5_config& c) {
     sw.weight_prefetch = flag("F5_WEIGHT_PREFETCH", true);
     if (const char* v = getenv("F5_X3_ABLATE")) sw.x3_ablate = c.precision == F5_PREC_F16X3 ? atoi(v) : 0;
     sw.x3_attn_split = flag("F5_X3_ATTN_SPLIT", false);
+    if (const char* v = getenv("F5_LEN_BUCKET")) sw.len_bucket = (int)std::min(std::max(atol(v), -1L), 1L << 20);   // (f5_create refuses a bad granule)
     return sw;
 }
 extern "C" int f5_create(const f5_config* c, f5_engine** out) {
@@ -83,6 +84,11 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     e->split16 = c->precision == F5_PREC_F16X3;
     e->io_split = c->precision == F5_PREC_F16P;
     e->sw = read_switches(*c);
+    if (!valid_len_bucket(e->sw.len_bucket)) {
+        const int g = e->sw.len_bucket;
+        delete e;
+        return fail(F5_EINVAL, "F5_LEN_BUCKET=%d: the granule is 0 (off) or a multiple of 8 in [8, 1024]", g);
+    }
     e->adapters_on = (c->options & F5_OPT_ADAPTERS) != 0;
     if (e->adapters_on && e->sw.x3_ablate) {   // (the ablation zeroes lo halves once, at finalize: a switch would write them back)
         delete e;
@@ -212,8 +218,12 @@ static int chunk_utts(const f5_engine* e, int B, int N, bool use_cfg, const int3
     return (int)((B + best_k - 1) / best_k);
 }
 SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk, int nt, int steps, int method,
-                       float cfg_strength, bool want_traj) {
+                       float cfg_strength, bool want_traj, int n_true) {
     SamplePlan p;
+    // a length-bucket plan: every utterance has n_true frames; the chunking follows the bucket's ceiling alone (it is part of the key)
+    const std::vector<int32_t> own(n_true > 0 ? B : 0, n_true), cap(n_true > 0 ? B : 0, N);
+    if (n_true > 0) lens_host = own.data();
+    p.n_true = n_true;
     p.B = B; p.N = N; p.nt = nt; p.steps = steps; p.method = method; p.cfg_strength = cfg_strength;
     p.use_cfg = !(cfg_strength < 1e-5f);
     p.has_lens = lens_host != nullptr;
@@ -221,9 +231,9 @@ SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_hos
     p.halves = p.use_cfg ? 2 : 1;
     p.evals = method == F5_ODE_MIDPOINT ? 2 : 1;
     const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;
-    p.pack = p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg;
+    p.pack = n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg);
     p.split = e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
-    p.chunk = chunk ? chunk : chunk_utts(e, B, N, p.use_cfg, p.pack ? lens_host : nullptr);
+    p.chunk = chunk ? chunk : chunk_utts(e, B, N, p.use_cfg, n_true > 0 ? cap.data() : p.pack ? lens_host : nullptr);
     for (int u0 = 0; u0 < B; u0 += p.chunk) {
         SamplePlan::Chunk k{(int)p.chunks.size(), u0, std::min(p.chunk, B - u0), 0, 0};
         for (int i = 0; lens_host && i < k.bc; ++i) {
@@ -239,6 +249,9 @@ std::string graph_key(const SamplePlan& p) {
     unsigned cfg_bits;
     memcpy(&cfg_bits, &p.cfg_strength, 4);
     char kb[160];
+    // a length-bucket plan: the bucket's ceiling stands for N, and neither the call's own length nor its text length is part of the key
+    if (p.n_true > 0) snprintf(kb, sizeof(kb), "L%d|%d|%d|%08x|%d|%d|m%d", p.B, p.N, p.steps, cfg_bits, p.want_traj ? 1 : 0, p.chunk, p.method);
+    else
     snprintf(kb, sizeof(kb), "%d|%d|%d|%d|%08x|%d|%d|%d|m%d", p.B, p.N, p.nt, p.steps, cfg_bits, p.has_lens ? 1 : 0, p.want_traj ? 1 : 0,
              p.chunk, p.method);
     return kb;
@@ -301,6 +314,52 @@ extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, c
                          const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream) {
     return f5_sample_ode(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj,
                          stream, F5_ODE_EULER);
+}
+
+// ------------------------------------------------------------------------------------- length buckets
+extern "C" int f5_set_length_buckets(f5_engine* e, int32_t granule) {
+    if (!e) return fail(F5_EINVAL, "null engine");
+    if (!valid_len_bucket(granule))
+        return fail(F5_EINVAL, "f5_set_length_buckets: granule %d is neither 0 (off) nor a multiple of 8 in [8, 1024]", granule);
+    e->sw.len_bucket = granule;
+    e->clear_graphs();
+    e->gc.capacity = GraphCache::DEFAULT_CAPACITY;
+    return F5_OK;
+}
+extern "C" int f5_prepare_sample(f5_engine* e, int32_t B, int32_t n_min, int32_t n_max, int32_t nt_max, int32_t steps, float cfg_strength,
+                                 int32_t method, int32_t want_traj, f5_stream stream) {
+    if (!e) return fail(F5_EINVAL, "null engine");
+    if (!e->finalized) return fail(F5_ESTATE, "f5_finalize has not been called");
+    const int g = e->sw.len_bucket;
+    if (g <= 0) return fail(F5_ESTATE, "f5_prepare_sample needs length buckets: call f5_set_length_buckets (or set F5_LEN_BUCKET) first");
+    if (method != F5_ODE_EULER && method != F5_ODE_MIDPOINT)
+        return fail(F5_EINVAL, "f5_prepare_sample: unknown ODE method %d (F5_ODE_EULER = 0, F5_ODE_MIDPOINT = 1)", method);
+    if (B <= 0 || n_min <= 0 || n_max < n_min || nt_max <= 0 || steps <= 0)
+        return fail(F5_EINVAL, "f5_prepare_sample: bad arguments (B %d, lengths %d .. %d, text %d, steps %d)", B, n_min, n_max, nt_max, steps);
+    if (round_up(n_max, g) + 1 > e->cfg.max_pos)
+        return fail(F5_EINVAL, "f5_prepare_sample: n_max=%d is planned at %d frames, which exceeds the rotary table (%d rows)", n_max,
+                    round_up(n_max, g), e->cfg.max_pos);
+    const int count = (round_up(n_max, g) - round_up(n_min, g)) / g + 1;
+    if (count > GraphCache::MAX_CAPACITY)
+        return fail(F5_EINVAL, "f5_prepare_sample: lengths %d .. %d at granule %d are %d buckets; the graph cache holds at most %d", n_min,
+                    n_max, g, count, (int)GraphCache::MAX_CAPACITY);
+    if (e->cfg.backbone != F5_BACKBONE_DIT) return fail(F5_EINVAL, "f5_prepare_sample: length buckets are built for the DiT backbone");
+    if (e->sw.split_cfg || e->prof.on || (e->cfg.options & F5_OPT_TEXT_AVG_UPSAMPLE))
+        return fail(F5_ESTATE, "f5_prepare_sample: no sample() call of this engine is eligible for a length bucket (F5_SPLIT_CFG, the "
+                               "profiler or text_embedding_average_upsampling is on)");
+    if (!e->sw.graphs || e->gc.disabled) return fail(F5_ESTATE, "f5_prepare_sample: HIP graphs are off (F5_HIP_GRAPH=0, or a capture failed)");
+    (void)stream;   // nothing is enqueued: capture and instantiation are host work
+    return F5_OPS(e, prepare(e, B, n_min, n_max, nt_max, steps, cfg_strength, method, want_traj != 0));
+}
+extern "C" int f5_graph_stats(f5_engine* e, int32_t* out) {
+    if (!e) return fail(F5_EINVAL, "null engine");
+    GraphCache::Stats& st = e->gc.stats;
+    if (!out) {
+        st = GraphCache::Stats();
+        return F5_OK;
+    }
+    out[0] = st.captures; out[1] = st.replays; out[2] = st.eager; out[3] = st.evictions;
+    return F5_OK;
 }
 
 extern "C" int f5_profile_enable(f5_engine* e, int32_t on) {

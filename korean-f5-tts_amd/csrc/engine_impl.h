@@ -534,7 +534,9 @@ static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, boo
     const int D = c.dim, inner = e->inner, H = c.heads, B = f.B, Bp = f.Bp, N = f.N, pl = f.pl();
     const RowPack& pk = f.pk;
     const int pe_heads = c.pe_attn_head < 0 ? H : c.pe_attn_head;
-    const int* attn_lens = (c.attn_mask_enabled && f.lens_dev) ? f.lens_dev : nullptr;
+    // (a packed batch masks its keys whatever attn_mask_enabled says: a length-bucket plan packs utterances that fill their whole length,
+    //  for which masked and unmasked attention coincide)
+    const int* attn_lens = ((c.attn_mask_enabled || pk) && f.lens_dev) ? f.lens_dev : nullptr;
     const double attn_fl = 4.0 * H * 64 * (pk ? pk.sq_host : (double)Bp * N * N);
     f.ablate(1, w.xn, D);
     // F5_PREC_F16X3 with plain-f16 attention products (x3_attn_hi == 3): q / k / v^T leave the QKV epilogue as f16 and the fast
@@ -960,31 +962,69 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
     }));
     return F5_OK;
 }
+// Whether a sample() call takes a length bucket (Switches::len_bucket), and the ceiling it is planned at.  Eligible: the DiT, every
+// utterance as long as the batch (lens NULL or all equal to N: masked and unmasked semantics then coincide, so the packed body serves
+// both), one stream chain, no profiler, and a ceiling inside the rotary / text position tables.  text_embedding_average_upsampling
+// stays on the exact path.  Everything else takes the exact path with the exact key, silently.
+template <typename T> static bool bucket_eligible(f5_engine* e, const int32_t* lens_host, int B, int N, int* n_cap) {
+    const f5_config& c = e->cfg;
+    const int g = e->sw.len_bucket;
+    if (g <= 0 || c.backbone != F5_BACKBONE_DIT || e->sw.split_cfg || e->prof.on || (c.options & F5_OPT_TEXT_AVG_UPSAMPLE)) return false;
+    for (int i = 0; lens_host && i < B; ++i)
+        if (lens_host[i] != N) return false;
+    const int nc = round_up(N, g);
+    if (nc + 1 > c.max_pos || (c.conv_layers > 0 && nc > packed<T>(e).text_pos_rows)) return false;
+    *n_cap = nc;
+    return true;
+}
+// the text staging buffer is part of the arena plan: a longer text moves the carve offsets
+static void reserve_text(f5_engine* e, int nt) {
+    if (nt > e->res_nt) {
+        e->res_nt = nt;
+        e->clear_graphs();
+    }
+}
 // sample(): plan, stage the inputs into the arena, key, replay / capture / eager, copy the outputs
 template <typename T>
 int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
                          const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
                          float* traj, hipStream_t s, int method) {
-    const SamplePlan p = plan_sample(e, B, N, lens_host, 0, nt, steps, method, cfg_strength, traj != nullptr);
+    reserve_text(e, nt);
+    int Nc = N;   // frames per utterance in the arena: N, or the ceiling of N's length bucket
+    const bool bucket = bucket_eligible<T>(e, lens_host, B, N, &Nc);
+    const SamplePlan p = plan_sample(e, B, Nc, lens_host, 0, bucket ? e->res_nt : nt, steps, method, cfg_strength, traj != nullptr, bucket ? N : 0);
     const int mel = e->cfg.mel_dim;
-    const long half = (long)B * N * mel;
-    if (nt > e->res_nt) {   // the text staging buffer is part of the arena plan
-        e->res_nt = nt;
-        e->clear_graphs();
-    }
-    CHK(ensure_arena(e, B, N, steps));
+    const long half = (long)B * Nc * mel;
+    CHK(ensure_arena(e, B, Nc, steps));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     // ---- inputs -> arena (eager, on the caller's stream)
     const std::vector<float> tt = time_table(t_host, steps, method);
-    CHK(upload_small<T>(e, w, tt.data(), (int)tt.size(), lens_host, p, s));
-    if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
+    const std::vector<int32_t> own(bucket ? B : 0, N);
+    CHK(upload_small<T>(e, w, tt.data(), (int)tt.size(), bucket ? own.data() : lens_host, p, s));
+    const size_t row_in = (size_t)N * mel * sizeof(float), row_arena = (size_t)Nc * mel * sizeof(float);   // one utterance, caller's / arena's
+    if (cond_frames < Nc) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
     if (cond_frames > 0)
-        HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
+        HIPCHK(hipMemcpy2DAsync(w.in_cond, row_arena, cond, (size_t)cond_frames * mel * sizeof(float),
                                 (size_t)cond_frames * mel * sizeof(float), B, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.y, y0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    if (!bucket) {
+        HIPCHK(hipMemcpyAsync(w.y, y0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    } else {
+        // The frames N .. Nc-1 of state and mask are written as zero (the two select_rows launches of the body read them; nothing reads
+        // what they produce), and the text sits in rows of res_nt tokens filled with -1: the filler, which is what a shorter text is
+        // padded with anyway (dit.py:87-89), so the body reads the same tokens whatever the call's own text length.
+        if (N < Nc) {
+            HIPCHK(hipMemsetAsync(w.y, 0, half * sizeof(float), s));
+            HIPCHK(hipMemsetAsync(w.in_mask, 0, (size_t)B * Nc, s));
+        }
+        HIPCHK(hipMemcpy2DAsync(w.y, row_arena, y0, row_in, row_in, B, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(w.in_mask, (size_t)Nc, cond_mask, (size_t)N, (size_t)N, B, hipMemcpyDeviceToDevice, s));
+        if (nt < p.nt) HIPCHK(hipMemsetAsync(w.in_text, 0xFF, (size_t)B * p.nt * sizeof(int64_t), s));
+        HIPCHK(hipMemcpy2DAsync(w.in_text, (size_t)p.nt * sizeof(int64_t), text, (size_t)nt * sizeof(int64_t), (size_t)nt * sizeof(int64_t), B,
+                                hipMemcpyDeviceToDevice, s));
+    }
     // ---- key: the signature, and whether the body reads the cached unconditional text embedding (a call that stores it runs eagerly)
     const bool uc_ok = p.use_cfg && uc_cacheable(e, B, p.has_lens);
     const bool uc_hit = uc_ok && e->uc_N == N;
@@ -997,20 +1037,53 @@ int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const
     if (e->sw.graphs && !e->gc.disabled && !e->prof.on && !(uc_ok && !uc_hit)) {
         if ((exec = e->gc.find(key))) {
             how = "graph replay";
+            e->gc.stats.replays++;
         } else if (e->gc.is_warm(base_key)) {
             CHK(e->gc.capture(key, [&](hipStream_t cs) { return sample_body<T>(e, w, p, cs); }, &exec));
             if (exec) how = "graph capture + instantiate + launch";
         }
     }
     if (exec) HIPCHK(hipGraphLaunch(exec, s));
-    else CHK(sample_body<T>(e, w, p, s));
+    else {
+        CHK(sample_body<T>(e, w, p, s));
+        e->gc.stats.eager++;
+    }
     if (trace)
         fprintf(stderr, "libf5hip: sample %s [%s]: host %.3f ms\n", key.c_str(), how,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body).count());
     if (!exec) e->gc.mark_warm(base_key);
-    // ---- outputs -> caller
-    HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // ---- outputs -> caller (a bucket's rows N .. Nc-1 stay behind)
+    if (!bucket) {
+        HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    } else {
+        HIPCHK(hipMemcpy2DAsync(out, row_in, w.out_buf, row_arena, row_in, B, hipMemcpyDeviceToDevice, s));
+        if (traj)
+            HIPCHK(hipMemcpy2DAsync(traj, row_in, w.traj_buf, row_arena, row_in, (size_t)(steps + 1) * B, hipMemcpyDeviceToDevice, s));
+    }
+    return F5_OK;
+}
+// f5_prepare_sample: one graph per length bucket of [n_min, n_max], captured and instantiated without a launch.  The arena is sized for
+// the largest bucket first, so that no call inside the range moves it (and with it every captured pointer).
+template <typename T>
+int EngineOps<T>::prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max, int steps, float cfg_strength, int method, bool want_traj) {
+    const int g = e->sw.len_bucket, c0 = round_up(n_min, g), c1 = round_up(n_max, g);
+    if (e->cfg.conv_layers > 0 && c1 > packed<T>(e).text_pos_rows)
+        return fail(F5_EINVAL, "f5_prepare_sample: n_max=%d is planned at %d frames, which exceeds aux.text_pos (%d rows)", n_max, c1,
+                    packed<T>(e).text_pos_rows);
+    reserve_text(e, nt_max);
+    CHK(ensure_arena(e, B, c1, steps));
+    e->gc.capacity = std::max<size_t>(e->gc.capacity, (size_t)(c1 - c0) / g + 1);
+    Work<T> w;
+    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
+    for (int nc = c0; nc <= c1; nc += g) {
+        const SamplePlan p = plan_sample(e, B, nc, nullptr, 0, e->res_nt, steps, method, cfg_strength, want_traj, nc);
+        const std::string key = graph_key(p) + "|nouc";
+        if (e->gc.find(key)) continue;
+        hipGraphExec_t exec = nullptr;
+        CHK(e->gc.capture(key, [&](hipStream_t cs) { return sample_body<T>(e, w, p, cs); }, &exec));
+        if (!exec) return fail(F5_EHIP, "f5_prepare_sample: the HIP graph of bucket %d could not be captured", nc);
+    }
     return F5_OK;
 }
 

@@ -230,13 +230,25 @@ struct Switches {
     // the f16x3 step.  F5_X3_ATTN_SPLIT=1 restores the three split products (and lets F5_X3_ABLATE bits 2 / 4 select).
     bool x3_attn_split = false;
     int x3_attn_hi() const { return x3_attn_split ? (x3_ablate >> 1) & 3 : 3; }
+    // F5_LEN_BUCKET=<granule> / f5_set_length_buckets: length-bucketed sample() graphs.  0 (the default): off.  Else a multiple of 8 in
+    // [8, 1024]: an eligible sample() call (bucket_eligible, engine_impl.h) is planned at N rounded up to the granule and its true
+    // length reaches the kernels through the device tables of RowPack, so one captured graph serves every N of a bucket.
+    int len_bucket = 0;
 };
+inline bool valid_len_bucket(long g) { return g == 0 || (g >= 8 && g <= 1024 && g % 8 == 0); }
 
 // HIP graphs of whole sample() bodies (one per problem signature): ~2600 launches per utterance become one
 // hipGraphLaunch, so the host (shared, sometimes slow) can never be the bottleneck of the ODE loop.  A signature is
-// captured the second time it is seen: its first call runs eagerly and marks it warm.
+// captured the second time it is seen: its first call runs eagerly and marks it warm (f5_prepare_sample captures ahead of
+// the first call instead).  The cache holds `capacity` entries, oldest out first: 16, or as many as f5_prepare_sample was
+// asked to keep ready, MAX_CAPACITY at most.
 struct GraphCache {
+    enum { DEFAULT_CAPACITY = 16, MAX_CAPACITY = 64 };
     struct Entry { std::string key; hipGraph_t graph; hipGraphExec_t exec; };
+    // f5_graph_stats: sample() bodies captured, replayed and launched eagerly, and entries pushed out by a newer capture
+    struct Stats { int captures = 0, replays = 0, eager = 0, evictions = 0; };
+    Stats stats;
+    size_t capacity = DEFAULT_CAPACITY;
     std::vector<Entry> graphs;
     std::vector<std::string> warm;      // signatures (without cache state) that have run eagerly once
     hipStream_t cap_stream = nullptr;
@@ -256,7 +268,7 @@ struct GraphCache {
     void mark_warm(const std::string& base_key) {
         if (!is_warm(base_key)) warm.push_back(base_key);
     }
-    // Captures the launches of body(cap_stream) and instantiates them as *exec; the oldest of 16 entries makes room.  Capture is an
+    // Captures the launches of body(cap_stream) and instantiates them as *exec; the oldest of `capacity` entries makes room.  Capture is an
     // optimisation: when it fails the cache says so, *exec stays null (the caller launches eagerly) and no later call tries again.
     template <typename F> int capture(const std::string& key, F&& body, hipGraphExec_t* exec) {
         if (!cap_stream) HIPCHK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
@@ -268,8 +280,12 @@ struct GraphCache {
             const int rc = body(cap_stream);
             const hipError_t ce = hipStreamEndCapture(cap_stream, &graph);
             if (rc == F5_OK && ce == hipSuccess && graph && hipGraphInstantiate(exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-                if (graphs.size() >= 16) evict(0);
+                while (graphs.size() >= capacity) {
+                    evict(0);
+                    stats.evictions++;
+                }
                 graphs.push_back({key, graph, *exec});
+                stats.captures++;
                 return F5_OK;
             }
             // (say so: the wall time doubles on a busy host)
@@ -396,7 +412,11 @@ struct SamplePlan {
     bool use_cfg = true, has_lens = false, want_traj = false;
     int halves = 2;       // batch rows per utterance in a backbone call: cond + uncond, or 1 without CFG
     int evals = 1;        // backbone evaluations per step (midpoint: 2)
-    bool pack = false;    // RowPack: attn_mask_enabled DiT batches with lengths, unless F5_PACK_ROWS=0 or F5_SPLIT_CFG=1
+    bool pack = false;    // RowPack: attn_mask_enabled DiT batches with lengths, unless F5_PACK_ROWS=0 or F5_SPLIT_CFG=1; every bucket plan
+    // Length bucket (Switches::len_bucket): N above is the bucket's ceiling -- arena layout, launch grids, the graph key -- and every
+    // utterance has n_true <= N frames, which only the device tables (lens, lens_plain, row_start) and the copies around the body know.
+    // nt is then the capacity of the text staging buffer (f5_engine::res_nt), filled with -1 behind the call's tokens.  0: no bucket.
+    int n_true = 0;
     bool split = false;   // F5_SPLIT_CFG=1: the halves as two stream chains (DiT with CFG, profiler off); one chunk, no packing
     int chunk = 0;
     std::vector<Chunk> chunks;
@@ -411,8 +431,9 @@ struct SamplePlan {
 // ------------------------------------------------------------------------------------ shared host helpers (engine.hip)
 int ensure_arena(f5_engine* e, int B, int N, int S);
 // (text_embed / forward pass chunk = B: the whole batch as one chunk, both halves; 0: chunk_utts decides)
+// (n_true > 0: a length-bucket plan -- N is the bucket's ceiling, every utterance has n_true frames and lens_host is ignored)
 SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk = 0, int nt = 0, int steps = 0,
-                       int method = F5_ODE_EULER, float cfg_strength = 1.f, bool want_traj = false);
+                       int method = F5_ODE_EULER, float cfg_strength = 1.f, bool want_traj = false, int n_true = 0);
 std::string graph_key(const SamplePlan& p);
 std::vector<float> time_table(const float* t_host, int steps, int method);
 
@@ -428,6 +449,7 @@ template <typename T> struct EngineOps {
     static int sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
                       const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
                       float* traj, hipStream_t s, int method);
+    static int prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max, int steps, float cfg_strength, int method, bool want_traj);
 };
 extern template struct EngineOps<float>;
 extern template struct EngineOps<bf16_t>;

@@ -128,6 +128,30 @@ class Engine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_reserve(self._h, max_batch, max_frames, max_steps), "f5_reserve")
 
+    # ------------------------------------------------------------------ length buckets
+    def set_length_buckets(self, granule: int):
+        """0: off.  Else a multiple of 8 in [8, 1024]: eligible sample() calls are planned at N rounded up to it, so that one
+        captured graph serves every length of a bucket (include/f5_hip.h).  Clears the graph cache."""
+        _lib.check(self.lib.f5_set_length_buckets(self._h, int(granule)), "f5_set_length_buckets")
+
+    def prepare_sample(self, batch: int, n_min: int, n_max: int, nt_max: int, steps: int, cfg_strength: float, *,
+                       method: str = "euler", want_traj: bool = True):
+        """Captures the graphs of every length bucket in [n_min, n_max] ahead of the first request (needs length buckets)."""
+        if method not in _lib.ODE_METHODS:
+            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.f5_prepare_sample(self._h, int(batch), int(n_min), int(n_max), int(nt_max), int(steps), float(cfg_strength),
+                                                  _lib.ODE_METHODS[method], int(want_traj), _stream_ptr(self.device)),
+                       "f5_prepare_sample")
+
+    def graph_stats(self, reset: bool = False) -> dict:
+        """sample() bodies captured, replayed and launched eagerly, and graphs evicted, since creation or the last reset."""
+        out = (C.c_int32 * 4)()
+        _lib.check(self.lib.f5_graph_stats(self._h, out), "f5_graph_stats")
+        if reset:
+            _lib.check(self.lib.f5_graph_stats(self._h, None), "f5_graph_stats")
+        return dict(captures=out[0], replays=out[1], eager=out[2], evictions=out[3])
+
     # ------------------------------------------------------------------ resident adapters
     def new_adapter(self, pairs: dict, full: dict) -> C.c_void_p:
         """Uploads one adapter: pairs {module: (A [r, in], B [out, r], scale)}, full {name: replacement tensor}.
