@@ -12,6 +12,7 @@
  *   f5_dit_forward   <- DiT.forward / UNetT.forward                  model/backbones/dit.py:278-329, unett.py:217-280
  *   f5_text_embed    <- TextEmbedding.forward (+ per-sample loop)    model/backbones/dit.py:86-115,244-258
  *   f5_vocos_decode  <- vocoder.decode(mel)                          infer/utils_infer.py:702-703 (third-party vocos)
+ *   f5_vocos_decode_ragged <- the per-item vocoder loop of a batch   eval/eval_infer_batch.py:202-212
  *   f5_bigvgan_forward <- vocoder(mel) (third-party BigVGAN v2)      infer/utils_infer.py:138-152,705
  *   f5_mel_forward   <- MelSpec.forward (vocos / bigvgan type)       model/modules.py:33-146
  *   f5_load_weight   <- load_checkpoint's state-dict assignment      infer/utils_infer.py:242-286
@@ -239,6 +240,19 @@ int f5_vocos_decode(f5_vocos* v, const float* mel, int32_t B, int32_t T, float* 
  * output, which is decoded in place instead of through a transposing copy. */
 int f5_vocos_decode_strided(f5_vocos* v, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_c,
                             int64_t stride_t, float* wav, f5_stream stream);
+/* A ragged batch in one pass: item b is frames [starts_host[b], ends_host[b]) of batch row b (T_b = end - start >= 2), e.g. the
+ * generated part of each row of sample()'s output behind its prompt (the reference's batch driver decodes these one by one,
+ * eval/eval_infer_batch.py:202-212).  The items run as sum(T_b) packed rows; each is convolved, overlap-added and trimmed
+ * inside its own window, and frames outside it are never read, so item b's waveform is bit-identical to
+ * f5_vocos_decode_strided on that slice alone with B = 1.
+ *   wav[b * wav_stride + j], j < (T_b - 1) * hop : the waveform, times gain_host[b] where gains are given (one f32 multiply)
+ *   (T_b - 1) * hop <= j < wav_stride            : 0.0f
+ * wav_stride >= max_b (T_b - 1) * hop.  F5_EINVAL, with nothing launched, for T_b < 2 (the message names the item), a
+ * negative start, too small a wav_stride, B <= 0 or a null mel / ends_host / wav.  The host tables are copied before the
+ * call returns.  No synchronisation except when the workspace grows. */
+int f5_vocos_decode_ragged(f5_vocos* v, const float* mel, int32_t B, int64_t stride_b, int64_t stride_c, int64_t stride_t,
+                           const int32_t* starts_host /* NULL: all 0 */, const int32_t* ends_host,
+                           const float* gain_host /* NULL: 1 */, float* wav, int64_t wav_stride, f5_stream stream);
 
 /* ---------------------------------------------------------------------------------------------- BigVGAN
  * The vocoder of mel_spec_type="bigvgan" (infer/utils_infer.py:138-152: bigvgan.BigVGAN.from_pretrained(

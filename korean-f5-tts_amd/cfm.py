@@ -15,6 +15,16 @@ from torch.nn.utils.rnn import pad_sequence
 from .utils import default, exists, get_epss_timesteps, lens_to_mask, list_str_to_idx, list_str_to_tensor
 
 
+def clamp_durations(text: torch.Tensor, lens: torch.Tensor, duration, max_duration=65536) -> torch.Tensor:
+    """The per-item total lengths sample() runs at (cfm.py:125-141): at least one frame past the longer of the text and the
+    prompt, at most max_duration.  text: CPU long [B, nt] padded with -1; lens: CPU long [B]; duration: int or long [B]."""
+    if isinstance(duration, int):
+        duration = torch.full((lens.shape[0],), duration, dtype=torch.long)
+    duration = duration.to("cpu", torch.long)
+    duration = torch.maximum(torch.maximum((text != -1).sum(dim=-1), lens) + 1, duration)
+    return duration.clamp(max=max_duration)
+
+
 class CFM(nn.Module):
     def __init__(self, transformer: nn.Module, sigma=0.0, odeint_kwargs: dict = dict(method="euler"),
                  audio_drop_prob=0.3, cond_drop_prob=0.2, num_channels=None, mel_spec_module: nn.Module | None = None,
@@ -78,11 +88,7 @@ class CFM(nn.Module):
         cond_mask = lens_to_mask(lens)
         if edit_mask is not None:
             cond_mask = cond_mask & edit_mask.to("cpu")
-        if isinstance(duration, int):
-            duration = torch.full((batch,), duration, dtype=torch.long)
-        duration = duration.to("cpu", torch.long)
-        duration = torch.maximum(torch.maximum((text_cpu != -1).sum(dim=-1), lens) + 1, duration)
-        duration = duration.clamp(max=max_duration)
+        duration = clamp_durations(text_cpu, lens, duration, max_duration)
         N = int(duration.amax())
 
         if duplicate_test:

@@ -360,17 +360,13 @@ static __global__ void zero_filler_rows_kernel(const long long* __restrict__ tex
 }
 
 // Depthwise Conv1d(k=7, pad=3) over the sequence + LayerNorm(C, affine, eps)   (ConvNeXt blocks: modules.py:256-270,
-// Vocos ConvNeXtBlock).  x, out: [B, N, C] fp32; wk: [7][C] (repacked), one wave per token.  Tokens outside
-// [0, lens[b]) read as zero (each sample is convolved at its own length, dit.py:247-258).
-static __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                         const float* __restrict__ wk, const float* __restrict__ wb,
-                                                         const float* __restrict__ lnw, const float* __restrict__ lnb,
-                                                         int B, int N, int C, const int* __restrict__ lens, float eps) {
-    const int lane = threadIdx.x & 63;
-    const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
-    if (row >= (long)B * N) return;
-    const int n = (int)(row % N), b = (int)(row / N);
-    const int len = lens ? lens[b] : N;
+// Vocos ConvNeXtBlock), one wave per token: token n of a segment of `len` tokens whose rows start at xs ([len, C] fp32);
+// wk: [7][C] (repacked).  Taps outside [0, len) read as zero.  Both kernels below run this body, so a token's value does
+// not depend on how its segment was laid out.
+static __device__ __forceinline__ void dwconv7_ln_token(const float* __restrict__ xs, float* __restrict__ orow,
+                                                        const float* __restrict__ wk, const float* __restrict__ wb,
+                                                        const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                                        int n, int len, int C, float eps, int lane) {
     float4 v[8];
     float s = 0.f;
 #pragma unroll
@@ -383,7 +379,7 @@ static __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __r
             for (int k = 0; k < 7; ++k) {
                 const int nn = n + k - 3;
                 if (nn >= 0 && nn < len) {
-                    const float4 xv = *reinterpret_cast<const float4*>(x + ((size_t)b * N + nn) * C + c);
+                    const float4 xv = *reinterpret_cast<const float4*>(xs + (size_t)nn * C + c);
                     const float4 w = *reinterpret_cast<const float4*>(wk + (size_t)k * C + c);
                     a.x += w.x * xv.x; a.y += w.y * xv.y; a.z += w.z * xv.z; a.w += w.w * xv.w;
                 }
@@ -408,11 +404,48 @@ static __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __r
         const int c = lane * 4 + i * 256;
         if (c < C) {
             const float4 w = *reinterpret_cast<const float4*>(lnw + c), bi = *reinterpret_cast<const float4*>(lnb + c);
-            *reinterpret_cast<float4*>(out + (size_t)row * C + c) =
+            *reinterpret_cast<float4*>(orow + c) =
                 make_float4((v[i].x - mean) * rstd * w.x + bi.x, (v[i].y - mean) * rstd * w.y + bi.y,
                             (v[i].z - mean) * rstd * w.z + bi.z, (v[i].w - mean) * rstd * w.w + bi.w);
         }
     }
+}
+
+// x, out: [B, N, C] fp32.  Tokens outside [0, lens[b]) read as zero (each sample is convolved at its own length, dit.py:247-258).
+static __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                         const float* __restrict__ wk, const float* __restrict__ wb,
+                                                         const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                                         int B, int N, int C, const int* __restrict__ lens, float eps) {
+    const int lane = threadIdx.x & 63;
+    const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
+    if (row >= (long)B * N) return;
+    const int n = (int)(row % N), b = (int)(row / N);
+    dwconv7_ln_token(x + (size_t)b * N * C, out + (size_t)row * C, wk, wb, lnw, lnb, n, lens ? lens[b] : N, C, eps, lane);
+}
+
+// Segment table of a packed ragged batch: item b owns rows row_start[b] .. row_start[b + 1] - 1 (B + 1 entries, every
+// segment non-empty).  The item of row r by binary search: r is uniform over a wave (or a block) in the kernels below, so
+// the ~log2(B) probes are scalar loads of a table that stays in cache.
+static __device__ __forceinline__ int segment_of_row(const int* __restrict__ row_start, int B, int r) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (row_start[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// The same over packed rows x, out: [R, C]: each token is convolved inside its own segment, whose ends are the zero padding.
+static __global__ __launch_bounds__(256) void dwconv7_ln_ragged_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                                const float* __restrict__ wk, const float* __restrict__ wb,
+                                                                const float* __restrict__ lnw, const float* __restrict__ lnb,
+                                                                const int* __restrict__ row_start, int B, int R, int C, float eps) {
+    const int lane = threadIdx.x & 63;
+    const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
+    if (row >= R) return;
+    const int b = segment_of_row(row_start, B, (int)row);
+    const int r0 = row_start[b];
+    dwconv7_ln_token(x + (size_t)r0 * C, out + (size_t)row * C, wk, wb, lnw, lnb, (int)row - r0, row_start[b + 1] - r0, C, eps, lane);
 }
 
 // GRN (modules.py:231-240): Gx[b, c] = ||h[b, :len, c]||_2 over the SEQUENCE; Nx = Gx / (mean_c Gx + 1e-6);
@@ -622,29 +655,68 @@ static __global__ void istft_spec_kernel(const float* __restrict__ h, int ldh, f
         S[i] = v;
     }
 }
-// overlap-add of windowed frames + window-envelope normalisation + centre trim = torch.istft(center=True)
-// frames [B*T, nfft] (already multiplied by the synthesis window), wav [B, (T-1)*hop]
+// Ragged im2col7: packed row r = (item b, local frame t) of the segment table; item b is frames [mel_start[b], mel_start[b] +
+// T_b) of batch row b, and taps outside [0, T_b) are the conv's zero padding -- frames before the window (the prompt), past
+// it, and other items' rows are never read.  One block per packed row (the item lookup is uniform over the block).
+static __global__ __launch_bounds__(256) void im2col7_ragged_kernel(const float* __restrict__ mel, long sb, long sc, long st,
+                                                             const int* __restrict__ row_start, const int* __restrict__ mel_start,
+                                                             float* __restrict__ A, int B, int C, int R, int ld) {
+    for (int r = blockIdx.x; r < R; r += gridDim.x) {
+        const int b = segment_of_row(row_start, B, r);
+        const int r0 = row_start[b], t = r - r0, Tb = row_start[b + 1] - r0;
+        const float* src = mel + b * sb + (long)mel_start[b] * st;
+        for (int col = threadIdx.x; col < ld; col += blockDim.x) {
+            float v = 0.f;
+            if (col < 7 * C) {
+                const int k = col / C, ci = col - k * C;
+                const int tt = t + k - 3;
+                if (tt >= 0 && tt < Tb) v = src[ci * sc + tt * st];
+            }
+            A[(size_t)r * ld + col] = v;
+        }
+    }
+}
+// overlap-add of windowed frames + window-envelope normalisation + centre trim = torch.istft(center=True): sample i of one
+// item of T frames [T, nfft] (already multiplied by the synthesis window)
+static __device__ __forceinline__ float istft_ola_sample(const float* __restrict__ frames, const float* __restrict__ win, int T,
+                                                         int nfft, int hop, int i) {
+    const int pos = i + nfft / 2;
+    int t1 = pos / hop;
+    if (t1 > T - 1) t1 = T - 1;
+    int t0 = (pos - nfft + hop) / hop;  // smallest t with t*hop + nfft > pos
+    if (pos - nfft + 1 <= 0) t0 = 0;
+    float acc = 0.f, env = 0.f;
+    for (int t = t0; t <= t1; ++t) {
+        const int j = pos - t * hop;
+        if (j >= 0 && j < nfft) {
+            acc += frames[(size_t)t * nfft + j];
+            env += win[j] * win[j];
+        }
+    }
+    return acc / env;
+}
+// frames [B*T, nfft], wav [B, (T-1)*hop]
 static __global__ void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ win, float* __restrict__ wav,
                                  int B, int T, int nfft, int hop) {
     const int L = (T - 1) * hop;
     const long total = (long)B * L;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int b = (int)(i / L);
-        const int pos = (int)(i % L) + nfft / 2;
-        int t1 = pos / hop;
-        if (t1 > T - 1) t1 = T - 1;
-        int t0 = (pos - nfft + hop) / hop;  // smallest t with t*hop + nfft > pos
-        if (pos - nfft + 1 <= 0) t0 = 0;
-        float acc = 0.f, env = 0.f;
-        for (int t = t0; t <= t1; ++t) {
-            const int j = pos - t * hop;
-            if (j >= 0 && j < nfft) {
-                acc += frames[((size_t)b * T + t) * nfft + j];
-                env += win[j] * win[j];
-            }
-        }
-        wav[i] = acc / env;
+        wav[i] = istft_ola_sample(frames + (size_t)b * T * nfft, win, T, nfft, hop, (int)(i % L));
     }
+}
+// The same per item of a packed batch (blockIdx.y = item): frames [R, nfft]; frame range, envelope and centre trim at the
+// item's own T_b; then x gain[b] as a separate multiply; then zeros up to wav_stride.  wav [B, wav_stride].
+static __global__ void istft_ola_ragged_kernel(const float* __restrict__ frames, const float* __restrict__ win,
+                                        const int* __restrict__ row_start, const float* __restrict__ gain,
+                                        float* __restrict__ wav, long wav_stride, int nfft, int hop) {
+    const int b = blockIdx.y;
+    const int r0 = row_start[b], T = row_start[b + 1] - r0;
+    const long L = (long)(T - 1) * hop;
+    const float g = gain[b];
+    const float* fr = frames + (size_t)r0 * nfft;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < wav_stride; i += (long)gridDim.x * blockDim.x)
+        wav[b * wav_stride + i] = i < L ? istft_ola_sample(fr, win, T, nfft, hop, (int)i) * g : 0.f;
 }
 
 // In place: W f32 [rows, ld] (ld % 32 == 0) -> per 32-element block the 128 bytes the split-operand GEMM reads (gemm2.h MODE 3):

@@ -110,44 +110,6 @@ private:
 };
 enum { PC_GEMM = 0, PC_ATTN = 1, PC_LN = 2, PC_CONV = 3, PC_MISC = 4, PC_TEXT = 5, PC_TIME = 6 };
 
-// Host staging (pinned) for small per-call scalars (time grid, lengths): a ring of slots, each guarded by an event
-// recorded after its last async copy, so that consecutive calls never synchronise the stream.
-struct Staging {
-    enum { NSLOT = 8 };
-    char* host[NSLOT] = {};
-    size_t cap[NSLOT] = {};
-    hipEvent_t ev[NSLOT] = {};
-    bool used[NSLOT] = {};
-    int next = 0;
-    ~Staging() {
-        for (int i = 0; i < NSLOT; ++i) {
-            if (host[i]) (void)hipHostFree(host[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    }
-    int acquire(size_t bytes, char** out, int* slot) {
-        const int i = next;
-        next = (next + 1) % NSLOT;
-        if (!ev[i]) HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-        if (used[i]) HIPCHK(hipEventSynchronize(ev[i]));  // the copies issued from this slot NSLOT calls ago are done
-        if (bytes > cap[i]) {
-            if (host[i]) (void)hipHostFree(host[i]);
-            host[i] = nullptr;
-            cap[i] = 0;
-            HIPCHK(hipHostMalloc((void**)&host[i], std::max<size_t>(bytes, 4096), hipHostMallocDefault));
-            cap[i] = std::max<size_t>(bytes, 4096);
-        }
-        *out = host[i];
-        *slot = i;
-        return F5_OK;
-    }
-    int release(int slot, hipStream_t s) {
-        HIPCHK(hipEventRecord(ev[slot], s));
-        used[slot] = true;
-        return F5_OK;
-    }
-};
-
 // --------------------------------------------------------------------------------------- packed weights
 template <typename T> struct LinW {
     T* w = nullptr;      // [N, ldw]

@@ -5,6 +5,7 @@
 //   inverse real DFT + window  = S[T, 2F(+pad)] x Basis[n_fft, 2F(+pad)]^T   (Basis host-computed in float64 -> f32,
 //                                hann window and 1/n_fft folded in; exact restatement of torch.istft's irfft * window)
 // followed by overlap-add / window-envelope normalisation / centre trim (torch.istft(center=True)).
+// f5_vocos_decode_ragged runs the same stages once over the packed frames of a batch of windows (ragged decode).
 #include <map>
 #include <string>
 #include <vector>
@@ -36,6 +37,7 @@ struct f5_vocos {
     float *head_w = nullptr, *head_b = nullptr, *hann = nullptr, *basis = nullptr;
     std::vector<VBlock> blocks;
     Arena arena;
+    Staging stage;   // pinned slots for the ragged decode's per-call tables
     ~f5_vocos() {
         for (auto& kv : raw)
             if (kv.second.p) (void)hipFree(kv.second.p);
@@ -181,30 +183,31 @@ extern "C" int f5_vocos_decode(f5_vocos* v, const float* mel, int32_t B, int32_t
     return f5_vocos_decode_strided(v, mel, B, T, (int64_t)v->cfg.input_channels * T, T, 1, wav, stream);
 }
 
-extern "C" int f5_vocos_decode_strided(f5_vocos* v, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_c,
-                                       int64_t stride_t, float* wav, f5_stream stream) {
-    if (!v || !mel || !wav) return fail(F5_EINVAL, "f5_vocos_decode: null argument");
-    if (!v->finalized) return fail(F5_ESTATE, "f5_vocos_finalize has not been called");
-    if (B <= 0 || T < 2) return fail(F5_EINVAL, "f5_vocos_decode: need B >= 1 and T >= 2 frames");
-    hipStream_t s = (hipStream_t)stream;
+namespace {
+// Workspace of one decode over R rows (frames): the rectangular call has R = B * T, the ragged one R = sum of T_b packed rows
+struct VWork {
+    float *col, *x, *t1, *h, *hd, *S, *fr;
+    int* tab;   // ragged only: row_start[B + 1] | mel_start[B] | gain[B] (f32 bits)
+};
+}  // namespace
+
+// carves the workspace out of the handle's arena, growing it (the only synchronisation of a decode) when it is too small
+static int vocos_workspace(f5_vocos* v, long R, size_t ntab, VWork* w) {
     const f5_vocos_config& c = v->cfg;
-    const int C = c.input_channels, D = c.dim, I = c.intermediate_dim, nfft = c.n_fft;
-    const long R = (long)B * T;
-    // workspace
-    auto plan = [&](Arena& a, float** col, float** x, float** t1, float** h, float** hd, float** S, float** fr) {
+    auto plan = [&](Arena& a) {
         a.reset();
-        *col = a.take<float>((size_t)R * v->kemb);
-        *x = a.take<float>((size_t)R * D);
-        *t1 = a.take<float>((size_t)R * D);
-        *h = a.take<float>((size_t)R * I);
-        *hd = a.take<float>((size_t)R * v->head_n);
-        *S = a.take<float>((size_t)R * v->K2);
-        *fr = a.take<float>((size_t)R * nfft);
+        w->col = a.take<float>((size_t)R * v->kemb);
+        w->x = a.take<float>((size_t)R * c.dim);
+        w->t1 = a.take<float>((size_t)R * c.dim);
+        w->h = a.take<float>((size_t)R * c.intermediate_dim);
+        w->hd = a.take<float>((size_t)R * v->head_n);
+        w->S = a.take<float>((size_t)R * v->K2);
+        w->fr = a.take<float>((size_t)R * c.n_fft);
+        w->tab = a.take<int>(ntab);
         return align_up(a.off, 256) + 256;
     };
-    float *col, *x, *t1, *h, *hd, *S, *fr;
     Arena dry;
-    const size_t need_b = plan(dry, &col, &x, &t1, &h, &hd, &S, &fr);
+    const size_t need_b = plan(dry);
     if (need_b > v->arena.cap) {
         HIPCHK(hipDeviceSynchronize());
         if (v->arena.base) (void)hipFree(v->arena.base);
@@ -213,18 +216,27 @@ extern "C" int f5_vocos_decode_strided(f5_vocos* v, const float* mel, int32_t B,
         HIPCHK(hipMalloc((void**)&v->arena.base, need_b));
         v->arena.cap = need_b;
     }
-    (void)plan(v->arena, &col, &x, &t1, &h, &hd, &S, &fr);
+    (void)plan(v->arena);
+    return F5_OK;
+}
 
-    hipLaunchKernelGGL(im2col7_kernel, dim3(ew_blocks(R * v->kemb)), dim3(256), 0, s, mel, (long)stride_b, (long)stride_c,
-                       (long)stride_t, col, B, C, T, v->kemb);
-    KCHK();
+// embed GEMM .. iDFT GEMM over the R rows of w.col -> w.fr.  Every stage but the depthwise conv works row by row; the conv
+// sees B rows of T frames, or (row_start given) the segments of a packed batch.
+static int vocos_rows(f5_vocos* v, hipStream_t s, const VWork& w, long R, int B, int T, const int* row_start) {
+    const f5_vocos_config& c = v->cfg;
+    const int D = c.dim, I = c.intermediate_dim, nfft = c.n_fft;
+    float *col = w.col, *x = w.x, *t1 = w.t1, *h = w.h, *hd = w.hd, *S = w.S, *fr = w.fr;
     HIPCHK(launch_gemm<float>(s, col, v->kemb, v->emb_w, v->kemb, (int)R, D, v->kemb, EpiStore<float>{t1, D, v->emb_b, F5_ACT_NONE}));
     hipLaunchKernelGGL((layernorm_kernel<float>), dim3((R + 3) / 4), dim3(256), 0, s, t1, D, x, D, (int)R, D, 1e-6f, v->n0w,
                        v->n0b, 0, 0, 0, Prefetch{});
     KCHK();
     for (auto& b : v->blocks) {
-        hipLaunchKernelGGL(dwconv7_ln_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, t1, b.dwk, b.dwb, b.lnw, b.lnb, B, T, D,
-                           (const int*)nullptr, 1e-6f);
+        if (row_start)
+            hipLaunchKernelGGL(dwconv7_ln_ragged_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, t1, b.dwk, b.dwb, b.lnw, b.lnb,
+                               row_start, B, (int)R, D, 1e-6f);
+        else
+            hipLaunchKernelGGL(dwconv7_ln_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, t1, b.dwk, b.dwb, b.lnw, b.lnb, B, T, D,
+                               (const int*)nullptr, 1e-6f);
         KCHK();
         HIPCHK(launch_gemm<float>(s, t1, D, b.w1, D, (int)R, I, D, EpiStore<float>{h, I, b.b1, F5_ACT_GELU_ERF}));
         // x = x + gamma * (pwconv2(h) + bias)   (layer scale == a gate vector shared by every row)
@@ -237,8 +249,79 @@ extern "C" int f5_vocos_decode_strided(f5_vocos* v, const float* mel, int32_t B,
     hipLaunchKernelGGL(istft_spec_kernel, dim3(ew_blocks(R * v->K2)), dim3(256), 0, s, hd, v->head_n, S, v->K2, R, v->F);
     KCHK();
     HIPCHK(launch_gemm<float>(s, S, v->K2, v->basis, v->K2, (int)R, nfft, v->K2, EpiStore<float>{fr, nfft, nullptr, F5_ACT_NONE}));
-    hipLaunchKernelGGL(istft_ola_kernel, dim3(ew_blocks((long)B * (T - 1) * c.hop_length)), dim3(256), 0, s, fr, v->hann, wav,
-                       B, T, nfft, c.hop_length);
+    return F5_OK;
+}
+
+extern "C" int f5_vocos_decode_strided(f5_vocos* v, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_c,
+                                       int64_t stride_t, float* wav, f5_stream stream) {
+    if (!v || !mel || !wav) return fail(F5_EINVAL, "f5_vocos_decode: null argument");
+    if (!v->finalized) return fail(F5_ESTATE, "f5_vocos_finalize has not been called");
+    if (B <= 0 || T < 2) return fail(F5_EINVAL, "f5_vocos_decode: need B >= 1 and T >= 2 frames");
+    hipStream_t s = (hipStream_t)stream;
+    const f5_vocos_config& c = v->cfg;
+    const long R = (long)B * T;
+    VWork w;
+    CHK(vocos_workspace(v, R, 0, &w));
+    hipLaunchKernelGGL(im2col7_kernel, dim3(ew_blocks(R * v->kemb)), dim3(256), 0, s, mel, (long)stride_b, (long)stride_c,
+                       (long)stride_t, w.col, B, c.input_channels, T, v->kemb);
+    KCHK();
+    CHK(vocos_rows(v, s, w, R, B, T, nullptr));
+    hipLaunchKernelGGL(istft_ola_kernel, dim3(ew_blocks((long)B * (T - 1) * c.hop_length)), dim3(256), 0, s, w.fr, v->hann, wav,
+                       B, T, c.n_fft, c.hop_length);
+    KCHK();
+    return F5_OK;
+}
+
+extern "C" int f5_vocos_decode_ragged(f5_vocos* v, const float* mel, int32_t B, int64_t stride_b, int64_t stride_c,
+                                      int64_t stride_t, const int32_t* starts_host, const int32_t* ends_host,
+                                      const float* gain_host, float* wav, int64_t wav_stride, f5_stream stream) {
+    if (!v || !mel || !ends_host || !wav) return fail(F5_EINVAL, "f5_vocos_decode_ragged: null argument");
+    if (!v->finalized) return fail(F5_ESTATE, "f5_vocos_finalize has not been called");
+    if (B <= 0 || B > 65535) return fail(F5_EINVAL, "f5_vocos_decode_ragged: need 1 <= B <= 65535 items (B = %d)", B);
+    const f5_vocos_config& c = v->cfg;
+    long R = 0, lmax = 0;
+    for (int b = 0; b < B; ++b) {
+        const int st = starts_host ? starts_host[b] : 0, Tb = ends_host[b] - st;
+        if (st < 0) return fail(F5_EINVAL, "f5_vocos_decode_ragged: item %d starts at frame %d < 0", b, st);
+        if (Tb < 2)
+            return fail(F5_EINVAL, "f5_vocos_decode_ragged: item %d has %ld frame(s) (frames [%d, %d)); need at least 2", b,
+                        std::max(0L, (long)ends_host[b] - st), st, ends_host[b]);
+        R += Tb;
+        lmax = std::max(lmax, (long)(Tb - 1) * c.hop_length);
+    }
+    if (wav_stride < lmax)
+        return fail(F5_EINVAL, "f5_vocos_decode_ragged: wav_stride %lld is less than the longest waveform (%ld samples)",
+                    (long long)wav_stride, lmax);
+    if (R > (1L << 24)) return fail(F5_EINVAL, "f5_vocos_decode_ragged: %ld frames in one call (at most 2^24: the GEMMs index rows as int)", R);
+    hipStream_t s = (hipStream_t)stream;
+    VWork w;
+    CHK(vocos_workspace(v, R, (size_t)3 * B + 1, &w));
+    // the segment table, the window starts and the gains go down through one pinned slot (held until the copy has run); the
+    // device copy is read by this call's kernels only, which are ahead of the next call's copy on the stream
+    char* hb = nullptr;
+    int slot = 0;
+    CHK(v->stage.acquire(((size_t)3 * B + 1) * 4, &hb, &slot));
+    int* rs = reinterpret_cast<int*>(hb);
+    int* ms = rs + B + 1;
+    float* gh = reinterpret_cast<float*>(ms + B);
+    rs[0] = 0;
+    for (int b = 0; b < B; ++b) {
+        ms[b] = starts_host ? starts_host[b] : 0;
+        rs[b + 1] = rs[b] + (ends_host[b] - ms[b]);
+        gh[b] = gain_host ? gain_host[b] : 1.0f;
+    }
+    HIPCHK(hipMemcpyAsync(w.tab, hb, ((size_t)3 * B + 1) * 4, hipMemcpyHostToDevice, s));
+    CHK(v->stage.release(slot, s));
+    const int* row_start = w.tab;
+    const int* mel_start = w.tab + B + 1;
+    const float* gain = reinterpret_cast<const float*>(w.tab + 2 * B + 1);
+
+    hipLaunchKernelGGL(im2col7_ragged_kernel, dim3((unsigned)std::min(R, 16384L)), dim3(256), 0, s, mel, (long)stride_b,
+                       (long)stride_c, (long)stride_t, row_start, mel_start, w.col, B, c.input_channels, (int)R, v->kemb);
+    KCHK();
+    CHK(vocos_rows(v, s, w, R, B, 0, row_start));
+    hipLaunchKernelGGL(istft_ola_ragged_kernel, dim3(ew_blocks(wav_stride), B), dim3(256), 0, s, w.fr, v->hann, row_start, gain,
+                       wav, (long)wav_stride, c.n_fft, c.hop_length);
     KCHK();
     return F5_OK;
 }

@@ -9,6 +9,8 @@
   load_vocoder                       utils_infer.py:114-137     local vocos checkpoint only (no network here)
   infer_batch_process / infer_process utils_infer.py:453-778    mono mix, RMS-to-0.1, duration formula, sample(),
                                                                  prompt slicing, fp32 vocoder input, rescale, cross-fade
+  synthesize_batch                   eval_infer_batch.py:190-212 a ragged batch: sample(), then ONE vocoder pass over every
+                                                                 item's generated frames (Vocos.decode_ragged)
 
 Out of scope here: pydub silence clipping, Whisper ASR, resampling (torchaudio is absent:
 prompts must already be at 24 kHz), pinyin / Korean G2P tokenisers (text is tokenised per character through
@@ -308,6 +310,30 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
         yield None, target_sample_rate, None
         return
     yield cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)
+
+
+def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, **sample_kw):
+    """The reference's batch loop (eval/eval_infer_batch.py:190-212) as one call: `model.sample(cond, text, duration, lens=lens,
+    **sample_kw)`, then every item's generated frames [lens_i, duration_i) through the vocoder in ONE ragged pass
+    (Vocos.decode_ragged) instead of one decode per item.  `duration_i` are the clamped totals sample() ran at.
+    Returns (wav f32[B, L_max], wav_lens, mel): wav[i, :wav_lens[i]] is item i's waveform (times gain[i] where given), zeros
+    behind it; mel is sample()'s output [B, N, 100], prompts included.  Vocos only."""
+    from .cfm import clamp_durations
+    from .utils import list_str_to_idx, list_str_to_tensor
+
+    if not hasattr(vocoder, "decode_ragged"):
+        raise NotImplementedError(f"synthesize_batch decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
+                                  "decode (BigVGAN: decode item by item)")
+    if sample_kw.get("vocoder") is not None:
+        raise TypeError("synthesize_batch: pass the vocoder as its second argument, not through sample()'s vocoder=")
+    if isinstance(text, list):
+        vocab = getattr(model, "vocab_char_map", None)
+        text = list_str_to_idx(text, vocab) if vocab is not None else list_str_to_tensor(text)
+    lens = torch.as_tensor(lens).to("cpu", torch.long)
+    ends = clamp_durations(text.to("cpu", torch.long), lens, duration, sample_kw.get("max_duration", 65536))
+    mel, _ = model.sample(cond, text, duration, lens=lens, **sample_kw)
+    wav, wav_lens = vocoder.decode_ragged(mel.to(torch.float32).permute(0, 2, 1), ends=ends.tolist(), starts=lens.tolist(), gain=gain)
+    return wav, wav_lens, mel
 
 
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,

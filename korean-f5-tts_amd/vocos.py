@@ -1,5 +1,6 @@
 """Vocos vocoder with the surface the reference's harness uses: `vocoder.decode(mel[B, 100, T]) -> wav[B, T']`
-(infer/utils_infer.py:114-137,702-703; eval/eval_infer_batch.py:206).  Arithmetic runs in libf5hip (csrc/vocos.hip).
+(infer/utils_infer.py:114-137,702-703; eval/eval_infer_batch.py:206), plus `decode_ragged` for a batch of windows of unequal
+length in one pass.  Arithmetic runs in libf5hip (csrc/vocos.hip).
 Parameter names are those of charactr/vocos-mel-24khz's `pytorch_model.bin` (backbone.* / head.*)."""
 from __future__ import annotations
 
@@ -122,6 +123,39 @@ class Vocos(nn.Module):
             _lib.check(_lib.load().f5_vocos_decode_strided(h, _ptr(mel), B, T, sb, sc, st, _ptr(wav), _stream_ptr(dev)),
                        "f5_vocos_decode")
         return wav
+
+    @torch.no_grad()
+    def decode_ragged(self, mel: torch.Tensor, ends, starts=None, gain=None) -> tuple[torch.Tensor, list[int]]:
+        """A ragged batch in one pass (f5_vocos_decode_ragged): item b is frames [starts[b], ends[b]) of row b of mel f32[B, C, T]
+        (any view, e.g. sample()'s output as .permute(0, 2, 1) with starts = the prompt lengths and ends = the durations).
+        Returns (wav f32[B, L_max], wav_lens): wav[b, :wav_lens[b]] is bit-identical to decode() of that slice alone
+        (times gain[b] where gains are given), zeros behind it; wav_lens[b] = (ends[b] - starts[b] - 1) * hop.
+        ends / starts: lists or CPU tensors of ints; starts=None: every item starts at frame 0."""
+        h = self._handle()
+        dev = self._anchor.device
+        if mel.device != dev or mel.dtype != torch.float32:
+            mel = mel.detach().to(device=dev, dtype=torch.float32)
+        B, Cc, T = mel.shape
+        assert Cc == self.cfg["input_channels"]
+        ends = [int(e) for e in (ends.tolist() if torch.is_tensor(ends) else ends)]
+        starts = None if starts is None else [int(s) for s in (starts.tolist() if torch.is_tensor(starts) else starts)]
+        gain = None if gain is None else [float(g) for g in (gain.tolist() if torch.is_tensor(gain) else gain)]
+        if len(ends) != B or (starts is not None and len(starts) != B) or (gain is not None and len(gain) != B):
+            raise ValueError(f"decode_ragged: ends / starts / gain must have one entry per batch row ({B})")
+        for b, e in enumerate(ends):
+            s0 = starts[b] if starts else 0
+            if s0 < 0 or e > T or e - s0 < 2:
+                raise ValueError(f"decode_ragged: item {b} is frames [{s0}, {e}) of {T}: need 0 <= start, end <= T and at least 2 frames")
+        hop = self.cfg["hop_length"]
+        wav_lens = [(e - (starts[b] if starts else 0) - 1) * hop for b, e in enumerate(ends)]
+        wav = torch.empty(B, max(wav_lens), device=dev, dtype=torch.float32)
+        sb, sc, st = mel.stride()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().f5_vocos_decode_ragged(
+                h, _ptr(mel), B, sb, sc, st, _lib.int_array(starts), _lib.int_array(ends),
+                None if gain is None else _lib.float_array(gain), _ptr(wav), wav.shape[1], _stream_ptr(dev)),
+                "f5_vocos_decode_ragged")
+        return wav, wav_lens
 
     def forward(self, mel):
         return self.decode(mel)
