@@ -14,6 +14,7 @@
  *   f5_vocos_decode  <- vocoder.decode(mel)                          infer/utils_infer.py:702-703 (third-party vocos)
  *   f5_vocos_decode_ragged <- the per-item vocoder loop of a batch   eval/eval_infer_batch.py:202-212
  *   f5_bigvgan_forward <- vocoder(mel) (third-party BigVGAN v2)      infer/utils_infer.py:138-152,705
+ *   f5_wave_crossfade <- the cross-fade concatenation of the chunks  infer/utils_infer.py:734-775
  *   f5_mel_forward   <- MelSpec.forward (vocos / bigvgan type)       model/modules.py:33-146
  *   f5_load_weight   <- load_checkpoint's state-dict assignment      infer/utils_infer.py:242-286
  * The reference-side binding (ctypes) is shown in INTEGRATION.md.
@@ -253,6 +254,26 @@ int f5_vocos_decode_strided(f5_vocos* v, const float* mel, int32_t B, int32_t T,
 int f5_vocos_decode_ragged(f5_vocos* v, const float* mel, int32_t B, int64_t stride_b, int64_t stride_c, int64_t stride_t,
                            const int32_t* starts_host /* NULL: all 0 */, const int32_t* ends_host,
                            const float* gain_host /* NULL: 1 */, float* wav, int64_t wav_stride, f5_stream stream);
+
+/* ------------------------------------------------------------------------------------- cross-fade concatenation
+ * The last stage of infer_batch_process (infer/utils_infer.py:734-775): the pieces of one long text, cross-faded into one
+ * waveform.  Piece i is wav[i * wav_stride + j], j < lens_host[i] (f32, device); nothing past lens_host[i] in a row is read.
+ * The result is the reference's left fold over the pieces.  Host plan, in exact integers:
+ *   L_0 = len_0;  for i >= 1: n_i = min(cross_fade_samples, L_{i-1}, len_i) (0 when cross_fade_samples <= 0),
+ *   off_i = L_{i-1} - n_i,  L_i = off_i + len_i;  total = L_{B-1}.
+ * Output sample p is a fold, in double, over the pieces that cover it (j = p - off_i, 0 <= j < len_i), in ascending i:
+ *   i > 0 and j < n_i:  v = v * fo + (double)x_i[j] * fi        otherwise:  v = (double)x_i[j];      out[p] = (float)v
+ * with numpy's linspace weights fi = j * step_i + 0.0, fo = j * (-step_i) + 1.0, step_i = 1.0 / (n_i - 1) computed on the host,
+ * the last fade element exactly fi = 1, fo = 0, and fo = 1, fi = 0 for n_i == 1.  Multiplies and adds are separate IEEE double
+ * operations, so out is, bit for bit, numpy's float64 result cast to float32 -- also where pieces shorter than the fade put
+ * more than two pieces over one sample.
+ * out[0, total) is written, each sample by one thread (deterministic); nothing at or past total is.  *out_len_host (may be NULL)
+ * receives total.  One kernel launch that takes the per-piece table as its argument: no allocation, no copy, no synchronisation,
+ * capturable; lens_host is free when the call returns.  That bounds B: 1 <= B <= 64.  F5_EINVAL, with nothing launched and a
+ * message naming the argument, for B out of range, a null wav / lens_host / out, a lens_host[i] < 1, wav_stride below the
+ * longest piece or out_cap < total. */
+int f5_wave_crossfade(const float* wav, int32_t B, int64_t wav_stride, const int32_t* lens_host, int32_t cross_fade_samples,
+                      float* out, int64_t out_cap, int64_t* out_len_host, f5_stream stream);
 
 /* ---------------------------------------------------------------------------------------------- BigVGAN
  * The vocoder of mel_spec_type="bigvgan" (infer/utils_infer.py:138-152: bigvgan.BigVGAN.from_pretrained(

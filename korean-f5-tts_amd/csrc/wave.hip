@@ -1,0 +1,116 @@
+// Waveform post-processing on gfx950.  f5_wave_crossfade: the cross-fade concatenation of the chunks of one long text
+// (infer/utils_infer.py:734-775), so that a batch of decoded chunks becomes one waveform without leaving the device.
+//
+// The reference folds the pieces from the left: final <- [final[:-n], final[-n:] * linspace(1, 0, n) + next[:n] * linspace(0, 1, n),
+// next[n:]] in float64.  Every output sample is a function of the samples of the pieces that cover it alone, so the fold runs per
+// output sample, over the covering pieces in ascending order, in double, and is rounded to f32 once at the end -- the bits of
+// numpy's result cast to float32 (the file is built with -ffp-contract=off: multiply, multiply, add as written).
+#include "internal.h"
+
+#define fail f5_fail
+
+namespace {
+constexpr int kMaxPieces = 64;
+constexpr int kThreads = 256;
+constexpr int kPerThread = 4;                       // consecutive samples per thread: one 16-byte store
+constexpr int kTile = kThreads * kPerThread;        // samples per block and round
+
+// The host plan, passed by value as a kernel argument (1.5 KiB): nothing to copy, nothing to keep alive, capturable.
+struct WavePlan {
+    long long off[kMaxPieces];   // position of the piece's first sample in the output
+    double step[kMaxPieces];     // 1 / (n - 1): numpy's linspace step (0 for n < 2)
+    int n[kMaxPieces];           // samples of the piece's head that fade in over what is already there
+    int len[kMaxPieces];
+};
+
+__global__ __launch_bounds__(kThreads) void wave_crossfade_kernel(const float* __restrict__ wav, long long wav_stride, int B,
+                                                                   const WavePlan pl, float* __restrict__ out, long long total,
+                                                                   long long ntiles, int out_aligned) {
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long t0 = tile * kTile, t1 = t0 + kTile;      // the block's span (block-uniform)
+        const long long p0 = t0 + (long long)threadIdx.x * kPerThread;
+        double v[kPerThread] = {0.0, 0.0, 0.0, 0.0};
+        for (int i = 0; i < B; ++i) {
+            const long long off = pl.off[i];
+            const int len = pl.len[i];
+            if (off >= t1 || off + len <= t0) continue;           // uniform: the piece does not touch this tile
+            const long long j0 = p0 - off;
+            if (j0 >= len || j0 + kPerThread <= 0) continue;
+            const float* x = wav + (long long)i * wav_stride;
+            float xv[kPerThread];
+            if (j0 >= 0 && j0 + kPerThread <= len) {
+                __builtin_memcpy(xv, x + j0, sizeof(xv));         // 4-byte aligned, inside the piece
+            } else {
+#pragma unroll
+                for (int e = 0; e < kPerThread; ++e) {
+                    const long long j = j0 + e;
+                    xv[e] = (j >= 0 && j < len) ? x[j] : 0.0f;    // nothing outside [0, len) is read
+                }
+            }
+            const int n = i > 0 ? pl.n[i] : 0;
+            const double step = pl.step[i];
+#pragma unroll
+            for (int e = 0; e < kPerThread; ++e) {
+                const long long j = j0 + e;
+                if (j < 0 || j >= len) continue;
+                if (j < n) {
+                    double fi, fo;
+                    if (n == 1) {
+                        fi = 0.0, fo = 1.0;
+                    } else if (j == n - 1) {
+                        fi = 1.0, fo = 0.0;                       // linspace sets its last element to `stop`
+                    } else {
+                        fi = (double)j * step + 0.0;
+                        fo = (double)j * (-step) + 1.0;
+                    }
+                    v[e] = v[e] * fo + (double)xv[e] * fi;
+                } else {
+                    v[e] = (double)xv[e];
+                }
+            }
+        }
+        if (p0 + kPerThread <= total && out_aligned) {
+            *reinterpret_cast<float4*>(out + p0) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < kPerThread; ++e)
+                if (p0 + e < total) out[p0 + e] = (float)v[e];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int f5_wave_crossfade(const float* wav, int32_t B, int64_t wav_stride, const int32_t* lens_host,
+                                 int32_t cross_fade_samples, float* out, int64_t out_cap, int64_t* out_len_host, f5_stream stream) {
+    if (B < 1 || B > kMaxPieces) return fail(F5_EINVAL, "f5_wave_crossfade: need 1 <= B <= %d pieces (B = %d)", kMaxPieces, B);
+    if (!wav) return fail(F5_EINVAL, "f5_wave_crossfade: wav is null");
+    if (!lens_host) return fail(F5_EINVAL, "f5_wave_crossfade: lens_host is null");
+    if (!out) return fail(F5_EINVAL, "f5_wave_crossfade: out is null");
+    WavePlan pl{};
+    long long L = 0;
+    int max_len = 0;
+    for (int i = 0; i < B; ++i) {
+        const int len = lens_host[i];
+        if (len < 1) return fail(F5_EINVAL, "f5_wave_crossfade: lens_host[%d] = %d; every piece needs at least 1 sample", i, len);
+        max_len = std::max(max_len, len);
+        long long n = 0;
+        if (i > 0 && cross_fade_samples > 0) n = std::min<long long>(std::min<long long>(cross_fade_samples, L), len);
+        pl.off[i] = L - n;
+        pl.n[i] = (int)n;
+        pl.len[i] = len;
+        pl.step[i] = n > 1 ? 1.0 / (double)(n - 1) : 0.0;
+        L = pl.off[i] + len;
+    }
+    if (wav_stride < max_len)
+        return fail(F5_EINVAL, "f5_wave_crossfade: wav_stride %lld is less than the longest piece (%d samples)", (long long)wav_stride,
+                    max_len);
+    if (out_cap < L)
+        return fail(F5_EINVAL, "f5_wave_crossfade: out_cap %lld is less than the %lld samples of the result", (long long)out_cap, L);
+    const long long ntiles = (L + kTile - 1) / kTile;
+    const int grid = (int)std::min<long long>(ntiles, 2048);
+    const int out_aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    wave_crossfade_kernel<<<grid, kThreads, 0, (hipStream_t)stream>>>(wav, (long long)wav_stride, B, pl, out, L, ntiles, out_aligned);
+    KCHK();
+    if (out_len_host) *out_len_host = L;
+    return F5_OK;
+}

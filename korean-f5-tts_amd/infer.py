@@ -11,6 +11,10 @@
                                                                  prompt slicing, fp32 vocoder input, rescale, cross-fade
   synthesize_batch                   eval_infer_batch.py:190-212 a ragged batch: sample(), then ONE vocoder pass over every
                                                                  item's generated frames (Vocos.decode_ragged)
+  synthesize_long                    utils_infer.py:711-775      the chunks of one long text as ragged batches (the reference hands them
+                                                                 to a ThreadPoolExecutor): one prompt mel, one sample() and one
+                                                                 decode_ragged per group of chunks, the cross-fade on the device
+                                                                 (f5_wave_crossfade); `batched=True` of infer_process
 
 Out of scope here: pydub silence clipping, Whisper ASR, resampling (torchaudio is absent:
 prompts must already be at 24 kHz), pinyin / Korean G2P tokenisers (text is tokenised per character through
@@ -246,11 +250,159 @@ def cross_fade_concat(waves: list[np.ndarray], cross_fade_duration_: float = cro
     return final
 
 
+MAX_CHUNKS = 64   # pieces of one f5_wave_crossfade call (its per-piece table travels as a kernel argument)
+
+
+def cross_fade_plan(lens: list[int], cross_fade_samples: int) -> tuple[list[int], list[int], int]:
+    """The integer plan of cross_fade_concat's left fold (the arithmetic f5_wave_crossfade does on the host): piece i starts at
+    offs[i] of the result and its first ns[i] samples fade in over what is already there; returns (offs, ns, total).
+    n_i = min(cross_fade_samples, length so far, len_i), 0 for the first piece and when cross_fade_samples <= 0."""
+    offs, ns, total = [], [], 0
+    for i, ln in enumerate(lens):
+        n = min(cross_fade_samples, total, ln) if i > 0 and cross_fade_samples > 0 else 0
+        offs.append(total - n)
+        ns.append(n)
+        total = offs[-1] + ln
+    return offs, ns, total
+
+
+def group_chunks(durations: list[int], batch_frames: int | None, max_chunks: int = MAX_CHUNKS) -> list[range]:
+    """Consecutive runs of chunks, in text order, that each run as one ragged batch: a batch costs its row count times its
+    longest row, so a run holds len(run) * max(durations in run) <= batch_frames and len(run) <= max_chunks.  A single chunk
+    over the budget is a run of its own; batch_frames=None: only max_chunks limits a run."""
+    runs, start, longest = [], 0, 0
+    for i, d in enumerate(durations):
+        count = i - start + 1
+        if count > 1 and (count > max_chunks or (batch_frames is not None and count * max(longest, d) > batch_frames)):
+            runs.append(range(start, i))
+            start, longest = i, 0
+        longest = max(longest, d)
+    if durations:
+        runs.append(range(start, len(durations)))
+    return runs
+
+
+def wave_crossfade(wav: torch.Tensor, lens: list[int], cross_fade_samples: int) -> torch.Tensor:
+    """cross_fade_concat on the device (f5_wave_crossfade): piece i is wav[i, :lens[i]] of an f32 [B, stride] device tensor,
+    B <= 64; returns f32[total], bit for bit cross_fade_concat(pieces, ...).astype(float32).  One launch, no synchronisation."""
+    import ctypes as C
+
+    from . import _lib
+    from .engine import _ptr, _stream_ptr
+
+    if wav.device.type != "cuda":
+        raise RuntimeError("the HIP cross-fade only runs on a GPU (there is no CPU path: cross_fade_concat is the host form)")
+    if wav.dim() != 2 or wav.dtype != torch.float32 or wav.stride(1) != 1 or len(lens) != wav.shape[0]:
+        raise ValueError("wave_crossfade: wav must be f32 [B, stride] with unit element stride and one length per row")
+    total = cross_fade_plan(lens, cross_fade_samples)[2]
+    out = torch.empty(total, device=wav.device, dtype=torch.float32)
+    n = C.c_int64()
+    with torch.cuda.device(wav.device):
+        _lib.check(_lib.load().f5_wave_crossfade(_ptr(wav), wav.shape[0], wav.stride(0), _lib.int_array(lens), int(cross_fade_samples),
+                                                 _ptr(out), total, C.byref(n), _stream_ptr(wav.device)), "f5_wave_crossfade")
+    assert n.value == total
+    return out
+
+
+def _require_text_tokenizer(model_obj, text_tokenizer):
+    tok_type = getattr(model_obj, "_tokenizer_type", "custom")
+    if text_tokenizer is None and isinstance(tok_type, str) and tok_type.startswith("kor_"):
+        raise NotImplementedError(f"model tokenizer type {tok_type!r}: pass text_tokenizer= (str -> list[str], the reference's "
+                                  "utils_infer.py:549-660 conversion) -- the Korean G2P / allophone front-end is not part of this engine")
+
+
+def _warn_untokenised(model_obj, toks, stacklevel):
+    vocab = getattr(model_obj, "vocab_char_map", None)
+    if vocab is not None:
+        missing = sum(1 for c in toks if c not in vocab)
+        if len(toks) >= 8 and missing > 0.3 * len(toks):
+            import warnings
+            warnings.warn(f"{missing} of {len(toks)} text tokens are not in the model's vocabulary (they all map to id 0): "
+                          "this checkpoint expects a tokenised input (text_tokenizer=)", RuntimeWarning, stacklevel=stacklevel)
+
+
+def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *, mel_spec_type=mel_spec_type, progress=None,
+                    target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
+                    sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
+                    text_tokenizer=None, batch_frames=None):
+    """The chunks of one long text as ragged batches instead of one B = 1 pass each (the reference submits them to a
+    ThreadPoolExecutor, utils_infer.py:725-732): the host arithmetic of infer_batch_process per chunk (prompt_numerics:
+    local_speed, the duration formula, the trailing-space rule), then
+      ONE prompt mel (`model_obj.mel_spec`), shared by every chunk;
+      per group of chunks (group_chunks over the durations sample() runs at, `batch_frames` = the budget of rows x longest row;
+      None: one group) ONE `model_obj.sample` with the prompt mel expanded to the group, per-item durations and the prompt's
+      frame count as every item's `lens`, and ONE `vocoder.decode_ragged` of each item's frames behind the prompt;
+      the RMS rescale `wave * rms / target_rms` on the packed rows, as the sequential path writes it;
+      ONE f5_wave_crossfade over the rows of every group.
+    Nothing is copied to the host: returns (wave f32[total], sample_rate, combined mel f32[100, T_total]), both on the device.
+    At most 64 chunks (ValueError); Vocos only (a vocoder without decode_ragged, e.g. BigVGAN: NotImplementedError).
+
+    Against the sequential path (infer_batch_process, batched=False):
+      * the waveform is f32; the sequential one is float64 wherever a cross-fade happened (numpy promotes).  The values are
+        the float64 ones rounded once to f32;
+      * a chunk's mel in a batch equals the same chunk run alone only where batch items cannot see each other's padding:
+        with `attn_mask_enabled=True` the backbone runs the valid rows only (RowPack).  With `attn_mask_enabled=False` (the
+        shipped configs) a shorter chunk attends over the padded frames up to the group's longest, exactly as in the
+        reference's own batch driver (eval/eval_infer_batch.py, cfm.py:155-158)."""
+    from .cfm import clamp_durations
+    from .utils import list_str_to_idx, list_str_to_tensor
+
+    _require_text_tokenizer(model_obj, text_tokenizer)
+    if not hasattr(vocoder, "decode_ragged"):
+        raise NotImplementedError(f"synthesize_long decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
+                                  "decode (BigVGAN: use the sequential path, batched=False)")
+    gen_text_batches = list(gen_text_batches)
+    if not gen_text_batches:
+        raise ValueError("synthesize_long: no text to synthesise")
+    if len(gen_text_batches) > MAX_CHUNKS:
+        raise ValueError(f"synthesize_long: {len(gen_text_batches)} chunks; one call cross-fades at most {MAX_CHUNKS} "
+                         "(split the text, or use the sequential path)")
+    audio, sr = ref_audio
+    device = device if device is not None else model_obj.device
+    texts, durations = [], []
+    for gen_text in gen_text_batches:
+        a, rms, rtext, ref_len, duration = prompt_numerics(audio, sr, ref_text, gen_text, speed, fix_duration, target_rms)
+        texts.append(text_tokenizer(rtext + gen_text) if text_tokenizer is not None else rtext + gen_text)
+        _warn_untokenised(model_obj, texts[-1], stacklevel=3)
+        durations.append(duration)
+    vocab = getattr(model_obj, "vocab_char_map", None)
+    idx = list_str_to_idx(texts, vocab) if vocab is not None else list_str_to_tensor(texts)
+    with torch.inference_mode():
+        cond = model_obj.mel_spec(a.to(device)).permute(0, 2, 1)                # [1, T, 100], T = ref_len + 1 (centre padding)
+        cond_len = cond.shape[1]
+        ends = clamp_durations(idx, torch.full((len(texts),), cond_len, dtype=torch.long), torch.tensor(durations)).tolist()
+        groups = group_chunks(ends, batch_frames)
+        rows, lens, specs = [], [], []
+        for run in (progress.tqdm(groups) if progress is not None and hasattr(progress, "tqdm") else groups):
+            B = len(run)
+            generated, _ = model_obj.sample(cond=cond.expand(B, -1, -1), text=[texts[k] for k in run],
+                                            duration=torch.tensor([durations[k] for k in run]),
+                                            lens=torch.full((B,), cond_len, dtype=torch.long), steps=nfe_step,
+                                            cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+            generated = generated.to(torch.float32)
+            wave, wave_lens = vocoder.decode_ragged(generated.permute(0, 2, 1), ends=[ends[k] for k in run], starts=[ref_len] * B)
+            if rms < target_rms:
+                wave = wave * rms / target_rms
+            rows.append(wave)
+            lens += wave_lens
+            specs += [generated[b, ref_len:ends[k]].permute(1, 0) for b, k in enumerate(run)]
+        if len(rows) == 1:
+            packed = rows[0]
+        else:
+            packed = torch.empty(len(lens), max(lens), device=rows[0].device, dtype=torch.float32)
+            r0 = 0
+            for wave in rows:
+                packed[r0:r0 + wave.shape[0], :wave.shape[1]] = wave
+                r0 += wave.shape[0]
+        cf = int(cross_fade_duration * target_sample_rate) if cross_fade_duration > 0 else 0
+        return wave_crossfade(packed, lens, cf), target_sample_rate, torch.cat(specs, dim=1)
+
+
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type,
                         progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                         nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                         speed=speed, fix_duration=fix_duration, device=None, streaming=False, chunk_size=2048, seed=None,
-                        text_tokenizer=None):
+                        text_tokenizer=None, batched=False, batch_frames=None):
     """A GENERATOR, as in the reference (utils_infer.py:504-522,711-778):
       streaming=False  yields ONE item (final_wave f32 numpy, sample_rate, combined mel [100, T_total]) -- the cross-faded
                        concatenation over the text batches; (None, sample_rate, None) when there is no batch
@@ -258,6 +410,12 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
       streaming=True   yields (wave[j : j + chunk_size], sample_rate) per chunk of every batch's waveform in turn, no cross-fade
                        (the socket server's mode, socket_server.py:138-177).
     `progress`: None or an object with `.tqdm(iterable)` (the reference passes the tqdm module).
+    batched=True (not a reference argument; Vocos only; not with streaming: ValueError) runs the text batches through
+    `synthesize_long` -- ragged batches of at most `batch_frames` (rows x longest row; None: one batch), the cross-fade on the
+    device -- and yields ONE item (wave.cpu().numpy(), sample_rate, spec.cpu().numpy()).  Two differences from batched=False,
+    which is unchanged: the waveform is f32 (the sequential one is float64 wherever a cross-fade happened), and a chunk's mel
+    equals the same chunk run alone only with `attn_mask_enabled=True`; with `attn_mask_enabled=False` (the shipped configs) a
+    shorter chunk attends over the batch's padded frames, as in the reference's batch driver (see synthesize_long).
 
     Text front-end: the reference turns `ref_text + gen_text` into tokens per `model_obj._tokenizer_type` -- for the kor_*
     types through Korean G2P / jamo decomposition / allophone rules (utils_infer.py:549-660: g2pk and the repo's own rule
@@ -265,26 +423,30 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     per character through `vocab_char_map` (the reference's "custom"/char path); a kor_* model therefore needs
     `text_tokenizer`: a callable str -> list[str] producing exactly the reference's tokens.  Without one this raises rather
     than synthesise from ids that are almost all 0 (raw Hangul is not in a jamo / allophone vocabulary)."""
+    if batched and streaming:
+        raise ValueError("infer_batch_process: batched=True yields one finished waveform; it cannot be combined with streaming=True")
     audio, sr = ref_audio
     device = device if device is not None else model_obj.device
-    tok_type = getattr(model_obj, "_tokenizer_type", "custom")
-    if text_tokenizer is None and isinstance(tok_type, str) and tok_type.startswith("kor_"):
-        raise NotImplementedError(f"model tokenizer type {tok_type!r}: pass text_tokenizer= (str -> list[str], the reference's "
-                                  "utils_infer.py:549-660 conversion) -- the Korean G2P / allophone front-end is not part of this engine")
+    _require_text_tokenizer(model_obj, text_tokenizer)
+    if batched:
+        gen_text_batches = list(gen_text_batches)
+        if not gen_text_batches:
+            yield None, target_sample_rate, None
+            return
+        wave, rate, spec = synthesize_long(
+            (audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type, progress=progress,
+            target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
+            sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=device, seed=seed,
+            text_tokenizer=text_tokenizer, batch_frames=batch_frames)
+        yield wave.cpu().numpy(), rate, spec.cpu().numpy()
+        return
 
     def process_batch(gen_text):
         """One text batch -> (wave f32 numpy [nw], generated mel numpy [100, T])   (utils_infer.py:541-709)."""
         a, rms, rtext, ref_len, duration = prompt_numerics(audio, sr, ref_text, gen_text, speed, fix_duration, target_rms)
         a = a.to(device)
         text_list = [text_tokenizer(rtext + gen_text)] if text_tokenizer is not None else [rtext + gen_text]
-        vocab = getattr(model_obj, "vocab_char_map", None)
-        if vocab is not None:
-            toks = text_list[0]
-            missing = sum(1 for c in toks if c not in vocab)
-            if len(toks) >= 8 and missing > 0.3 * len(toks):
-                import warnings
-                warnings.warn(f"{missing} of {len(toks)} text tokens are not in the model's vocabulary (they all map to id 0): "
-                              "this checkpoint expects a tokenised input (text_tokenizer=)", RuntimeWarning, stacklevel=2)
+        _warn_untokenised(model_obj, text_list[0], stacklevel=3)
         with torch.inference_mode():
             generated, _ = model_obj.sample(cond=a, text=text_list, duration=duration, steps=nfe_step,
                                             cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
@@ -339,9 +501,12 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
-                  text_tokenizer=None):
+                  text_tokenizer=None, batched=False, batch_frames=None):
     """ref_audio = (tensor [channels, nw], sample_rate) instead of a path (no torchaudio.load here); otherwise
-    utils_infer.py:453-498: max_chars from the prompt's bytes-per-second, chunk, infer_batch_process."""
+    utils_infer.py:453-498: max_chars from the prompt's bytes-per-second, chunk, infer_batch_process.
+    batched=True (default False: the sequential path, unchanged) runs the chunks as ragged batches of at most `batch_frames`
+    and cross-fades on the device (infer_batch_process, synthesize_long): the waveform is then f32 where the sequential one is
+    float64 after a cross-fade, and a chunk's mel equals the chunk run alone only with `attn_mask_enabled=True`."""
     audio, sr = ref_audio
     max_chars = int(len(ref_text.encode("utf-8")) / (audio.shape[-1] / sr) * (22 - audio.shape[-1] / sr) * speed)
     batches = chunk_text(gen_text, max_chars=max_chars)
@@ -351,4 +516,4 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
                                     progress=progress, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                                     nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                                     speed=speed, fix_duration=fix_duration, device=device, seed=seed,
-                                    text_tokenizer=text_tokenizer))
+                                    text_tokenizer=text_tokenizer, batched=batched, batch_frames=batch_frames))
