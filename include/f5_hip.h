@@ -16,6 +16,7 @@
  *   f5_bigvgan_forward <- vocoder(mel) (third-party BigVGAN v2)      infer/utils_infer.py:138-152,705
  *   f5_wave_crossfade <- the cross-fade concatenation of the chunks  infer/utils_infer.py:734-775
  *   f5_mel_forward   <- MelSpec.forward (vocos / bigvgan type)       model/modules.py:33-146
+ *   f5_mel_forward_ragged <- the per-prompt MelSpec loop + padded_mel_batch  eval/utils_eval.py:109-148
  *   f5_load_weight   <- load_checkpoint's state-dict assignment      infer/utils_infer.py:242-286
  * The reference-side binding (ctypes) is shown in INTEGRATION.md.
  */
@@ -323,6 +324,24 @@ int f5_mel_forward(f5_mel* m, const float* wav, int32_t B, int32_t nw, float* ou
  * |S| = sqrt(re^2 + im^2 + mag_eps).  f5_mel_forward is pad = n_fft / 2, mag_eps = 0. */
 int f5_mel_forward_ex(f5_mel* m, const float* wav, int32_t B, int32_t nw, int32_t pad, float mag_eps, float* out,
                       f5_stream stream);
+/* Ragged form (the prompts of eval/utils_eval.py:109-148, padded_mel_batch): B prompts of unequal length in ONE pass -- one
+ * reflect-pad launch, one DFT GEMM, one magnitude launch and one mel GEMM over the packed rows of every item, one unpack launch.
+ * Item b is wav[wav_start_host[b] .. wav_start_host[b] + nw_host[b]) and has T_b = (nw_b + 2 pad - n_fft) / hop + 1 frames;
+ * out[b * out_stride_b + t * n_mels + c] holds its log-mel for t < T_b, bit for bit what f5_mel_forward_ex(B = 1) gives for that
+ * item alone, and +0.0 for T_b <= t < T_out (F.pad(..., value=0)); nothing at or past b * out_stride_b + T_out * n_mels is written,
+ * nothing outside an item's samples is read.  pad and mag_eps as in f5_mel_forward_ex.  The host tables are free when the call
+ * returns (they go down in one copy through a pinned slot); no synchronisation and no allocation except the growth of the
+ * handle's workspace.
+ * f5_mel_ragged_plan is the row layout as pure host arithmetic (no HIP call): item b's padded signal of P_b = nw_b + 2 pad samples
+ * starts at sample row_start[b] * hop of one packed buffer and owns ceil(P_b / hop) rows (the first T_b are its frames, the rest
+ * are dead rows); row_start_out has B + 1 entries (the last is the row count R), frames_out[b] = T_b.
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the item: a null pointer, B <= 0, pad < 0,
+ * wav_start_b < 0, an item with nw_b <= pad or nw_b + 2 pad < n_fft, T_out < max T_b, out_stride_b < T_out * n_mels, R > 2^24.
+ * F5_ESTATE when the tables are not loaded. */
+int f5_mel_ragged_plan(int32_t n_fft, int32_t hop, int32_t pad, int32_t B, const int32_t* nw_host, int32_t* row_start_out,
+                       int32_t* frames_out);
+int f5_mel_forward_ragged(f5_mel* m, const float* wav, int32_t B, const int64_t* wav_start_host, const int32_t* nw_host, int32_t pad,
+                          float mag_eps, float* out, int64_t out_stride_b, int32_t T_out, f5_stream stream);
 
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;

@@ -20,19 +20,74 @@
 using namespace f5;
 #define fail f5_fail
 
+// sample of a signal of nw samples that element j of its reflect-padded form reads, -pad <= j < nw + pad with pad < nw
+static __device__ __forceinline__ int reflect_index(int j, int nw) {
+    if (j < 0) j = -j;                   // reflect (no edge repeat), torch pad_mode="reflect"
+    if (j >= nw) j = 2 * (nw - 1) - j;
+    return j;
+}
 // out rows have stride `ls` >= nw + 2*pad (a multiple of 4 floats so that every row stays 16-byte aligned)
 static __global__ void reflect_pad_kernel(const float* __restrict__ wav, float* __restrict__ out, int B, int nw, int pad, int ls) {
     const long total = (long)B * ls;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int b = (int)(i / ls);
-        int j = (int)(i % ls) - pad;
+        const int j = (int)(i % ls) - pad;
         float v = 0.f;
-        if (j < nw + pad) {
-            if (j < 0) j = -j;                   // reflect (no edge repeat), torch pad_mode="reflect"
-            if (j >= nw) j = 2 * (nw - 1) - j;
-            v = wav[(size_t)b * nw + j];
-        }
+        if (j < nw + pad) v = wav[(size_t)b * nw + reflect_index(j, nw)];
         out[i] = v;
+    }
+}
+// The packed signal of a ragged batch (f5_mel_ragged_plan): item b's reflect-padded samples start at element row_start[b] * hop
+// and own the rows up to row_start[b + 1]; the slack behind its nw_b + 2 pad samples and the n_fft elements behind the last
+// row are zeros, so that the frames that run out of an item (dead rows) are finite.  One block per packed row, striding: the
+// row -> item search is block-uniform.  Every one of the R * hop + n_fft elements is written, nothing outside
+// wav[wav_start[b] .. wav_start[b] + nw[b]) is read.
+static __global__ __launch_bounds__(256) void reflect_pad_ragged_kernel(const float* __restrict__ wav, float* __restrict__ out,
+                                                                        const long long* __restrict__ wav_start,
+                                                                        const int* __restrict__ row_start, const int* __restrict__ nw,
+                                                                        int B, int R, int hop, int pad, int n_fft) {
+    const int rows = R + (n_fft + hop - 1) / hop;   // the tail behind row R - 1 as rows of its own
+    const size_t total = (size_t)R * hop + n_fft;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {
+        const float* src = nullptr;
+        int n = 0, first = 0;
+        if (r < R) {
+            const int b = segment_of_row(row_start, B, r);
+            src = wav + wav_start[b];
+            n = nw[b];
+            first = (r - row_start[b]) * hop;   // < nw_b + 2 pad + hop: an int
+        }
+        for (int e = threadIdx.x; e < hop; e += blockDim.x) {
+            const size_t i = (size_t)r * hop + e;
+            if (i >= total) break;
+            const int j = first + e - pad;
+            float v = 0.f;
+            if (src && j < n + pad) v = src[reflect_index(j, n)];
+            out[i] = v;
+        }
+    }
+}
+// packed [R, C] -> out[b * stride_b + t * C + c] = t < frames[b] ? packed[row_start[b] + t, c] : +0.0 for t < T_out; one
+// thread per 4 channels (C % 4 == 0), 16-byte accesses when out and stride_b allow them (VEC), one writer per element
+template <bool VEC>
+static __global__ __launch_bounds__(256) void mel_unpack_ragged_kernel(const float* __restrict__ packed, float* __restrict__ out,
+                                                                       const int* __restrict__ row_start,
+                                                                       const int* __restrict__ frames, int B, int T_out, int C,
+                                                                       long stride_b) {
+    const int c4 = C / 4;
+    const long per_b = (long)T_out * c4, total = per_b * B;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per_b);
+        const long k = i % per_b;
+        const int t = (int)(k / c4), q = (int)(k % c4);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < frames[b]) v = reinterpret_cast<const float4*>(packed + ((size_t)row_start[b] + t) * C)[q];
+        float* dst = out + (size_t)b * stride_b + (size_t)t * C + 4 * q;
+        if (VEC) {
+            *reinterpret_cast<float4*>(dst) = v;
+        } else {
+            dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+        }
     }
 }
 // spec [T, lds] with re in [0, F), im in [F, 2F)  ->  mag [T, ldm], columns >= F zeroed
@@ -55,6 +110,8 @@ struct f5_mel {
     int n_fft = 0, hop = 0, n_mels = 0, F = 0, ns = 0, kf = 0;
     float *basis = nullptr, *fb = nullptr;
     Arena arena;
+    Staging stage;                    // pinned slots for the ragged call's per-item tables
+    std::vector<int32_t> plan_rows;   // ragged call: row_start[B + 1] | frames[B] (host; grows, never shrinks)
     ~f5_mel() {
         if (basis) (void)hipFree(basis);
         if (fb) (void)hipFree(fb);
@@ -145,5 +202,125 @@ extern "C" int f5_mel_forward_ex(f5_mel* m, const float* wav, int32_t B, int32_t
         HIPCHK(launch_gemm<float>(s, mag, m->kf, m->fb, m->kf, T, m->n_mels, m->kf,
                                   EpiStore<float>{out + (size_t)b * T * m->n_mels, m->n_mels, nullptr, F5_ACT_LOGCLAMP}));
     }
+    return F5_OK;
+}
+
+// The row layout of the ragged front-end (pure host arithmetic): item b's padded signal of P_b = nw_b + 2 pad samples starts at
+// sample row_start[b] * hop of the packed buffer and owns ceil(P_b / hop) rows, of which the first frames[b] are its frames.
+extern "C" int f5_mel_ragged_plan(int32_t n_fft, int32_t hop, int32_t pad, int32_t B, const int32_t* nw_host, int32_t* row_start_out,
+                                  int32_t* frames_out) {
+    if (!nw_host || !row_start_out || !frames_out) return fail(F5_EINVAL, "f5_mel_ragged_plan: null nw_host / row_start_out / frames_out");
+    if (n_fft <= 0 || hop <= 0) return fail(F5_EINVAL, "f5_mel_ragged_plan: need n_fft > 0 and hop > 0 (n_fft = %d, hop = %d)", n_fft, hop);
+    if (B <= 0) return fail(F5_EINVAL, "f5_mel_ragged_plan: need B >= 1 items (B = %d)", B);
+    if (pad < 0) return fail(F5_EINVAL, "f5_mel_ragged_plan: pad = %d < 0", pad);
+    long rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const long P = (long)nw_host[b] + 2L * pad;
+        if (nw_host[b] <= pad || P < n_fft)
+            return fail(F5_EINVAL, "f5_mel_ragged_plan: item %d has %d samples: too few for the reflect padding (%d) / one frame of %d", b,
+                        nw_host[b], pad, n_fft);
+        if (P > 0x7fffffffL - hop) return fail(F5_EINVAL, "f5_mel_ragged_plan: item %d has %d samples: its padded length overflows an int", b, nw_host[b]);
+        row_start_out[b] = (int32_t)rows;
+        frames_out[b] = (int32_t)((P - n_fft) / hop + 1);
+        rows += (P + hop - 1) / hop;
+        if (rows > (1L << 24))
+            return fail(F5_EINVAL, "f5_mel_ragged_plan: more than 2^24 packed rows at item %d (the GEMMs index rows as int)", b);
+    }
+    row_start_out[B] = (int32_t)rows;
+    return F5_OK;
+}
+
+// A list of prompts of unequal length -> the zero-padded mel batch, in ONE pass over the packed rows of every item:
+// item b = wav[wav_start_host[b] .. + nw_host[b]) -> out[b * out_stride_b + t * n_mels + c], t < T_out (rows >= T_b are +0.0)
+extern "C" int f5_mel_forward_ragged(f5_mel* m, const float* wav, int32_t B, const int64_t* wav_start_host, const int32_t* nw_host,
+                                     int32_t pad, float mag_eps, float* out, int64_t out_stride_b, int32_t T_out, f5_stream stream) {
+    if (!m) return fail(F5_EINVAL, "f5_mel_forward_ragged: null handle m");
+    if (!wav) return fail(F5_EINVAL, "f5_mel_forward_ragged: null wav");
+    if (!wav_start_host) return fail(F5_EINVAL, "f5_mel_forward_ragged: null wav_start_host");
+    if (!nw_host) return fail(F5_EINVAL, "f5_mel_forward_ragged: null nw_host");
+    if (!out) return fail(F5_EINVAL, "f5_mel_forward_ragged: null out");
+    if (B <= 0) return fail(F5_EINVAL, "f5_mel_forward_ragged: need B >= 1 items (B = %d)", B);
+    if (pad < 0) return fail(F5_EINVAL, "f5_mel_forward_ragged: pad = %d < 0", pad);
+    for (int b = 0; b < B; ++b)
+        if (wav_start_host[b] < 0)
+            return fail(F5_EINVAL, "f5_mel_forward_ragged: item %d starts at wav_start = %lld < 0", b, (long long)wav_start_host[b]);
+    m->plan_rows.resize((size_t)2 * B + 1);
+    int32_t* rs = m->plan_rows.data();
+    int32_t* frames = rs + B + 1;
+    if (f5_mel_ragged_plan(m->n_fft, m->hop, pad, B, nw_host, rs, frames) != F5_OK) return F5_EINVAL;   // (its message names the item)
+    const int R = rs[B];
+    int tmax = 0;
+    for (int b = 0; b < B; ++b) tmax = std::max(tmax, (int)frames[b]);
+    if (T_out < tmax) return fail(F5_EINVAL, "f5_mel_forward_ragged: T_out = %d is less than the longest item's %d frames", T_out, tmax);
+    if (out_stride_b < (int64_t)T_out * m->n_mels)
+        return fail(F5_EINVAL, "f5_mel_forward_ragged: out_stride_b = %lld is less than T_out * n_mels = %lld", (long long)out_stride_b,
+                    (long long)T_out * m->n_mels);
+    if (!m->basis || !m->fb) return fail(F5_ESTATE, "f5_mel_forward_ragged: aux.dft_basis / aux.mel_fb not loaded");
+    hipStream_t s = (hipStream_t)stream;
+    // device tables behind the buffers: wav_start[B] (int64) | row_start[B + 1] | nw[B] | frames[B]
+    const size_t tab_bytes = (size_t)B * 8 + ((size_t)3 * B + 1) * 4;
+    float *wp, *spec, *mag, *pk;
+    char* tab;
+    auto plan = [&](Arena& a) {
+        a.reset();
+        wp = a.take<float>((size_t)R * m->hop + m->n_fft);
+        spec = a.take<float>((size_t)R * m->ns);
+        mag = a.take<float>((size_t)R * m->kf);
+        pk = a.take<float>((size_t)R * m->n_mels);
+        tab = a.take<char>(tab_bytes);
+        return align_up(a.off, 256) + 256;
+    };
+    Arena dry;
+    const size_t need_b = plan(dry);
+    if (need_b > m->arena.cap) {   // the rectangular call's rule: the only synchronisation and allocation of a call
+        HIPCHK(hipDeviceSynchronize());
+        if (m->arena.base) (void)hipFree(m->arena.base);
+        m->arena.base = nullptr;
+        m->arena.cap = 0;
+        HIPCHK(hipMalloc((void**)&m->arena.base, need_b));
+        HIPCHK(hipMemset(m->arena.base, 0, need_b));
+        m->arena.cap = need_b;
+    }
+    (void)plan(m->arena);
+    // one pinned slot, one copy (held until the copy has run); the device tables are read by this call's kernels only
+    char* hb = nullptr;
+    int slot = 0;
+    CHK(m->stage.acquire(tab_bytes, &hb, &slot));
+    long long* h_ws = reinterpret_cast<long long*>(hb);
+    int* h_rs = reinterpret_cast<int*>(hb + (size_t)B * 8);
+    int* h_nw = h_rs + B + 1;
+    int* h_fr = h_nw + B;
+    for (int b = 0; b < B; ++b) {
+        h_ws[b] = wav_start_host[b];
+        h_rs[b] = rs[b];
+        h_nw[b] = nw_host[b];
+        h_fr[b] = frames[b];
+    }
+    h_rs[B] = R;
+    HIPCHK(hipMemcpyAsync(tab, hb, tab_bytes, hipMemcpyHostToDevice, s));
+    CHK(m->stage.release(slot, s));
+    const long long* d_ws = reinterpret_cast<const long long*>(tab);
+    const int* d_rs = reinterpret_cast<const int*>(tab + (size_t)B * 8);
+    const int* d_nw = d_rs + B + 1;
+    const int* d_fr = d_nw + B;
+
+    const int pad_rows = R + (m->n_fft + m->hop - 1) / m->hop;
+    hipLaunchKernelGGL(reflect_pad_ragged_kernel, dim3((unsigned)std::min(pad_rows, 16384)), dim3(256), 0, s, wav, wp, d_ws, d_rs, d_nw,
+                       B, R, m->hop, pad, m->n_fft);
+    KCHK();
+    // frames are a strided view of the packed signal: row r starts at r*hop (dead rows included: they cost a few rows per item)
+    HIPCHK(launch_gemm<float>(s, wp, m->hop, m->basis, m->n_fft, R, m->ns, m->n_fft, EpiStore<float>{spec, m->ns, nullptr, F5_ACT_NONE}));
+    hipLaunchKernelGGL(magnitude_kernel, dim3(ew_blocks((long)R * m->kf)), dim3(256), 0, s, spec, m->ns, mag, m->kf, (long)R, m->F,
+                       mag_eps);
+    KCHK();
+    HIPCHK(launch_gemm<float>(s, mag, m->kf, m->fb, m->kf, R, m->n_mels, m->kf, EpiStore<float>{pk, m->n_mels, nullptr, F5_ACT_LOGCLAMP}));
+    const long quads = (long)B * T_out * (m->n_mels / 4);
+    if ((reinterpret_cast<uintptr_t>(out) % 16) == 0 && out_stride_b % 4 == 0)
+        hipLaunchKernelGGL((mel_unpack_ragged_kernel<true>), dim3(ew_blocks(quads)), dim3(256), 0, s, pk, out, d_rs, d_fr, B, T_out,
+                           m->n_mels, (long)out_stride_b);
+    else
+        hipLaunchKernelGGL((mel_unpack_ragged_kernel<false>), dim3(ew_blocks(quads)), dim3(256), 0, s, pk, out, d_rs, d_fr, B, T_out,
+                           m->n_mels, (long)out_stride_b);
+    KCHK();
     return F5_OK;
 }

@@ -15,6 +15,8 @@
                                                                  to a ThreadPoolExecutor): one prompt mel, one sample() and one
                                                                  decode_ragged per group of chunks, the cross-fade on the device
                                                                  (f5_wave_crossfade); `batched=True` of infer_process
+  normalise_prompt / prompt_batch    eval/utils_eval.py:109-148  many speakers, one sentence each: the prompts' mels in ONE ragged
+  synthesize_prompts                 eval_infer_batch.py:183-212 pass (MelSpec.forward_ragged), then synthesize_batch per group
 
 Out of scope here: pydub silence clipping, Whisper ASR, resampling (torchaudio is absent:
 prompts must already be at 24 kHz), pinyin / Korean G2P tokenisers (text is tokenised per character through
@@ -211,10 +213,9 @@ def sinc_resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass
     return y.reshape(*waveform.shape[:-1], -1)
 
 
-def prompt_numerics(audio: torch.Tensor, sr: int, ref_text: str, gen_text: str, speed_: float = speed,
-                    fix_duration_=None, target_rms_: float = target_rms):
-    """The host arithmetic of process_batch (utils_infer.py:523-533,541-544,678-685) factored out so that it can be
-    pinned by hand-computed cases: returns (audio mono RMS-normalised [1, nw], rms, ref_audio_len, duration)."""
+def normalise_prompt(audio: torch.Tensor, sr: int, target_rms_: float = target_rms):
+    """A prompt as both drivers prepare it (utils_infer.py:523-533, eval/utils_eval.py:111-118): mono mix, RMS, the gain up to
+    target_rms when it is below, then resampling to 24 kHz, on the host.  Returns (audio f32[1, nw], rms of the mono input)."""
     if audio.shape[0] > 1:
         audio = torch.mean(audio, dim=0, keepdim=True)
     rms = torch.sqrt(torch.mean(torch.square(audio)))
@@ -222,6 +223,14 @@ def prompt_numerics(audio: torch.Tensor, sr: int, ref_text: str, gen_text: str, 
         audio = audio * target_rms_ / rms
     if sr != target_sample_rate:
         audio = sinc_resample(audio, sr, target_sample_rate)                   # utils_infer.py:530-532
+    return audio, float(rms)
+
+
+def prompt_numerics(audio: torch.Tensor, sr: int, ref_text: str, gen_text: str, speed_: float = speed,
+                    fix_duration_=None, target_rms_: float = target_rms):
+    """The host arithmetic of process_batch (utils_infer.py:523-533,541-544,678-685) factored out so that it can be
+    pinned by hand-computed cases: returns (audio mono RMS-normalised [1, nw], rms, ref_audio_len, duration)."""
+    audio, rms = normalise_prompt(audio, sr, target_rms_)
     if len(ref_text[-1].encode("utf-8")) == 1:
         ref_text = ref_text + " "
     local_speed = 0.3 if len(gen_text.encode("utf-8")) < 10 else speed_
@@ -232,7 +241,7 @@ def prompt_numerics(audio: torch.Tensor, sr: int, ref_text: str, gen_text: str, 
         ref_text_len = len(ref_text.encode("utf-8"))
         gen_text_len = len(gen_text.encode("utf-8"))
         duration = ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
-    return audio, float(rms), ref_text, ref_audio_len, duration
+    return audio, rms, ref_text, ref_audio_len, duration
 
 
 def cross_fade_concat(waves: list[np.ndarray], cross_fade_duration_: float = cross_fade_duration) -> np.ndarray:
@@ -496,6 +505,80 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
     mel, _ = model.sample(cond, text, duration, lens=lens, **sample_kw)
     wav, wav_lens = vocoder.decode_ragged(mel.to(torch.float32).permute(0, 2, 1), ends=ends.tolist(), starts=lens.tolist(), gain=gain)
     return wav, wav_lens, mel
+
+
+def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_spec, device=None):
+    """`get_inference_prompt` for one batch (eval/utils_eval.py:109-148, without the truth-duration branch and the bucketing,
+    which is batching.bucket_prompts): prompts is a list of (audio [channels, nw], sample_rate, ref_text), gen_texts the text to
+    speak with each.  normalise_prompt per item on the host, then ONE `mel_spec.forward_ragged` over every prompt.  Returns
+    dict(cond f32[B, T_max, n_mels] zero-padded (padded_mel_batch), lens = frames per prompt (ref_mel_len), durations =
+    total_mel_len per item, texts = prompt text + target text (trailing-space rule), rms per prompt)."""
+    from .batching import prompt_text_and_frames
+
+    prompts, gen_texts = list(prompts), list(gen_texts)
+    if not prompts or len(prompts) != len(gen_texts):
+        raise ValueError(f"prompt_batch: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt, at least one)")
+    audios, rms = [], []
+    for audio, sr, _ref_text in prompts:
+        a, r = normalise_prompt(audio, sr, target_rms)
+        audios.append(a)
+        rms.append(r)
+    mel, frames = mel_spec.forward_ragged(audios) if device is None else mel_spec.forward_ragged(audios, device=device)
+    texts, durations = [], []
+    for (_audio, _sr, ref_text), gen_text, n in zip(prompts, gen_texts, frames):
+        text, total = prompt_text_and_frames(n, ref_text, gen_text, speed)
+        texts.append(text)
+        durations.append(total)
+    return dict(cond=mel.permute(0, 2, 1), lens=list(frames), durations=durations, texts=texts, rms=rms)
+
+
+def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, target_rms=target_rms, nfe_step=nfe_step,
+                       cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, text_tokenizer=None,
+                       batch_frames=None, **sample_kw):
+    """The reference's batch job from raw prompt audio to waveforms (eval/utils_eval.py:109-148 + eval_infer_batch.py:183-212):
+    many speakers, one sentence each.  prompt_batch (ONE ragged mel pass over every prompt), then per group of items
+    (group_chunks over the totals sample() runs at; `batch_frames` = the budget of rows x longest row, None: groups of up to 64)
+    ONE synthesize_batch -- sample() and one ragged decode -- with the group's `cond` cut to its longest prompt, then the rescale
+    `wave * rms_i / target_rms` on exactly the rows with rms_i < target_rms, as the sequential path writes it (not a
+    decode_ragged gain: one multiply is not bit-equal to a multiply and a divide).
+    Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Vocos only."""
+    from .cfm import clamp_durations
+    from .utils import list_str_to_idx, list_str_to_tensor
+
+    _require_text_tokenizer(model, text_tokenizer)
+    if not hasattr(vocoder, "decode_ragged"):
+        raise NotImplementedError(f"synthesize_prompts decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
+                                  "decode (BigVGAN: decode item by item)")
+    prompts, gen_texts = list(prompts), list(gen_texts)
+    if not prompts:
+        raise ValueError("synthesize_prompts: no prompt to synthesise from")
+    if len(prompts) != len(gen_texts):
+        raise ValueError(f"synthesize_prompts: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt)")
+    with torch.inference_mode():
+        pb = prompt_batch(prompts, gen_texts, speed=speed, target_rms=target_rms, mel_spec=model.mel_spec, device=model.device)
+        texts = [text_tokenizer(t) for t in pb["texts"]] if text_tokenizer is not None else pb["texts"]
+        for t in texts:
+            _warn_untokenised(model, t, stacklevel=3)
+        vocab = getattr(model, "vocab_char_map", None)
+        idx = list_str_to_idx(texts, vocab) if vocab is not None else list_str_to_tensor(texts)
+        lens, durations, rms = pb["lens"], pb["durations"], pb["rms"]
+        ends = clamp_durations(idx.to("cpu", torch.long), torch.tensor(lens), torch.tensor(durations),
+                               sample_kw.get("max_duration", 65536)).tolist()
+        waves, mels = [], []
+        for run in group_chunks(ends, batch_frames):
+            glens = [lens[k] for k in run]
+            cond = pb["cond"][run.start:run.stop, :max(glens)].contiguous()
+            wav, wav_lens, mel = synthesize_batch(model, vocoder, cond, [texts[k] for k in run],
+                                                  torch.tensor([durations[k] for k in run]), lens=glens, steps=nfe_step,
+                                                  cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                                  **sample_kw)
+            for b, k in enumerate(run):
+                wave = wav[b, :wav_lens[b]]
+                if rms[k] < target_rms:
+                    wave = wave * rms[k] / target_rms
+                waves.append(wave)
+                mels.append(mel[b, lens[k]:ends[k]].to(torch.float32).permute(1, 0))
+        return waves, target_sample_rate, mels
 
 
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,

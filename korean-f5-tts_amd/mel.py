@@ -2,7 +2,8 @@
 torchaudio MelSpectrogram(n_fft=1024, win=1024, hop=256, n_mels=100, power=1, center=True, norm=None) then
 clamp(min=1e-5).log() (modules.py:78-104); mel_spec_type="bigvgan": reflect pad (n_fft - hop) / 2, stft(center=False),
 sqrt(re^2 + im^2 + 1e-9), librosa's slaney mel basis, log(clamp(., 1e-5)) (modules.py:33-75).  The arithmetic runs in libf5hip (csrc/mel.hip: strided-view STFT GEMM, magnitude, mel GEMM
-with a log epilogue); this file only builds the constant tables on the host.
+with a log epilogue); this file only builds the constant tables on the host.  `forward_ragged` is the reference's
+per-prompt loop + `padded_mel_batch` (eval/utils_eval.py:109-148, 17-25) as one pass over the packed rows of every prompt.
 
 torchaudio is not installed in the build container, so its HTK filterbank (`melscale_fbanks`, norm=None) is restated
 here from its published definition, and so is librosa's slaney filterbank (`librosa.filters.mel`, htk=False,
@@ -121,3 +122,58 @@ class MelSpec(nn.Module):
             _lib.check(_lib.load().f5_mel_forward_ex(h, C.c_void_p(wav.data_ptr()), B, nw, pad, eps, C.c_void_p(out.data_ptr()),
                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "f5_mel_forward")
         return out.permute(0, 2, 1)
+
+    def _variant(self):
+        """(reflect padding, magnitude epsilon) of the mel_spec_type."""
+        return (self.n_fft // 2, 0.0) if self.mel_spec_type == "vocos" else ((self.n_fft - self.hop_length) // 2, 1e-9)
+
+    @torch.no_grad()
+    def forward_ragged(self, wavs, device=None):
+        """Prompts of unequal length in one pass (f5_mel_forward_ragged): wavs is a list of f32 [nw_i] (or [1, nw_i]) tensors, on
+        the host or on a GPU -> (log-mel f32[B, n_mels, T_max], frames).  mel[i, :, :frames[i]] is bit for bit
+        `forward(wavs[i][None])[0]`, the columns behind it are +0.0 (`padded_mel_batch`); like `forward`, the return is a permuted
+        view of [B, T_max, n_mels].  Host tensors go down in ONE concatenated copy; device tensors are read where they are.
+        device: where host tensors go (default: the device tensors' device, else the current GPU)."""
+        wavs = [w.squeeze(0) if w.dim() == 2 and w.shape[0] == 1 else w for w in wavs]
+        if not wavs:
+            raise ValueError("forward_ragged: no waveform")
+        if any(w.dim() != 1 for w in wavs):
+            raise ValueError("forward_ragged: every waveform must be [nw] or [1, nw]")
+        on_gpu = [w.device for w in wavs if w.device.type == "cuda"]
+        if device is not None:
+            dev = torch.device(device)
+        elif on_gpu:
+            dev = on_gpu[0]
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        if dev.type != "cuda":
+            raise RuntimeError("the HIP mel front-end only runs on a GPU (there is no CPU path)")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if any(d != dev for d in on_gpu):
+            raise ValueError("forward_ragged: the waveforms are on different devices")
+        nws = [int(w.shape[0]) for w in wavs]
+        host = [i for i, w in enumerate(wavs) if w.device.type != "cuda"]
+        wavs = [w if w.device.type != "cuda" else w.to(torch.float32).contiguous() for w in wavs]
+        if host:
+            down = torch.cat([wavs[i].to(torch.float32) for i in host]).to(dev)
+            for i, piece in zip(host, down.split([nws[i] for i in host])):
+                wavs[i] = piece
+        # one base pointer and an element offset per item: the items stay where they are (every f32 tensor is 4-byte aligned)
+        base = min(w.data_ptr() for w in wavs)
+        starts = [(w.data_ptr() - base) // 4 for w in wavs]
+        lib = _lib.load()
+        B = len(wavs)
+        pad, eps = self._variant()
+        nw_arr = _lib.int_array(nws)
+        rows, frames = (C.c_int32 * (B + 1))(), (C.c_int32 * B)()
+        _lib.check(lib.f5_mel_ragged_plan(self.n_fft, self.hop_length, pad, B, nw_arr, rows, frames), "f5_mel_ragged_plan")
+        frames = list(frames)
+        T = max(frames)
+        out = torch.empty(B, T, self.n_mel_channels, device=dev, dtype=torch.float32)
+        h = self._handle(dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.f5_mel_forward_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), nw_arr, pad, eps,
+                                                 C.c_void_p(out.data_ptr()), T * self.n_mel_channels, T,
+                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "f5_mel_forward_ragged")
+        return out.permute(0, 2, 1), frames
