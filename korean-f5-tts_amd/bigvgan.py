@@ -9,12 +9,12 @@ import ctypes as C
 import math
 
 import torch
-from torch import nn
 
 from . import _lib
 from . import weights as W
+from ._lib import _ptr, _stream_ptr
 from .config import BIGVGAN_V2_24K
-from .engine import _dev_f32, _ptr, _stream_ptr
+from .native import NativeVocoder
 
 
 def kaiser_sinc_filter1d(cutoff: float, half_width: float, kernel_size: int) -> torch.Tensor:
@@ -29,19 +29,16 @@ def kaiser_sinc_filter1d(cutoff: float, half_width: float, kernel_size: int) -> 
     return (filt / filt.sum()).to(torch.float32)
 
 
-class BigVGAN(nn.Module):
+class BigVGAN(NativeVocoder):
+    _prefix, _load = "f5_bigvgan", "f5_bigvgan_load_weight"
+
     def __init__(self, cfg: dict = BIGVGAN_V2_24K, device=None, precision: str = "f32"):
         """precision: "f32" (f32 MFMA throughout) or "f16x3" (the wide stages' convolutions as split-f16 products, include/f5_hip.h
         F5_PREC_F16X3: f32-level results, ~2.5x the f32 GEMM rate)."""
-        super().__init__()
+        super().__init__(cfg)
         if precision not in ("f32", "f16x3"):
             raise ValueError("BigVGAN precision must be 'f32' or 'f16x3'")
         self.precision = precision
-        self.cfg = dict(cfg)
-        self._sd: dict[str, torch.Tensor] = {}
-        self._h = None
-        self._h_dev = None
-        self._anchor = nn.Parameter(torch.zeros(1), requires_grad=False)
         self.total_up = 1
         for u in self.cfg["upsample_rates"]:
             self.total_up *= u
@@ -50,13 +47,6 @@ class BigVGAN(nn.Module):
 
     def param_shapes(self):
         return W.bigvgan_param_shapes(self.cfg)
-
-    def init_synthetic(self, seed: int = 0):
-        self.load_state_dict(W.synthetic_state_dict(self.param_shapes(), seed=seed))
-        return self
-
-    def state_dict(self, *a, **k):
-        return dict(self._sd)
 
     def remove_weight_norm(self):
         """The reference calls this after loading (utils_infer.py:151); checkpoints given to load_state_dict are expected
@@ -70,37 +60,9 @@ class BigVGAN(nn.Module):
             g, v = sd.pop(k), sd.pop(base + ".weight_v")
             sd[base + ".weight"] = v * (g / v.flatten(1).norm(dim=1).view(-1, *([1] * (v.dim() - 1))))
         sd = {k: v for k, v in sd.items() if not k.endswith((".filter", ".lowpass.filter"))}   # filter buffers are recomputed
-        shapes = self.param_shapes()
-        missing = [k for k in shapes if k not in sd]
-        unexpected = [k for k in sd if k not in shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"bigvgan state dict mismatch: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        self._sd = {k: sd[k].detach().to("cpu", torch.float32) for k in shapes if k in sd}
-        self._drop_handle()
-        return nn.modules.module._IncompatibleKeys(missing, unexpected)
+        return self._set_state(sd, strict, "bigvgan")
 
-    def _drop_handle(self):
-        if self._h:
-            _lib.load().f5_bigvgan_destroy(self._h)
-        self._h = None
-        self._h_dev = None
-
-    def __del__(self):
-        try:
-            self._drop_handle()
-        except Exception:
-            pass
-
-    def _handle(self):
-        dev = self._anchor.device
-        if dev.type != "cuda":
-            raise RuntimeError("the HIP vocoder only runs on a GPU: call .to('cuda') first (there is no CPU path)")
-        if self._h is not None and self._h_dev == dev:
-            return self._h
-        self._drop_handle()
-        lib = _lib.load()
-        if not self._sd:
-            raise RuntimeError("no vocoder weights loaded")
+    def _create(self, lib, h):
         c = self.cfg
         cfg = _lib.f5_bigvgan_config()
         cfg.num_mels, cfg.upsample_initial_channel = c["num_mels"], c["upsample_initial_channel"]
@@ -115,18 +77,11 @@ class BigVGAN(nn.Module):
             cfg.resblock_dilations[m] = d
         cfg.use_tanh_at_final, cfg.use_bias_at_final = int(bool(c.get("use_tanh_at_final"))), int(bool(c.get("use_bias_at_final")))
         cfg.precision = _lib.PRECISIONS[self.precision]
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(lib.f5_bigvgan_create(C.byref(cfg), C.byref(h)), "f5_bigvgan_create")
-            st = _stream_ptr(dev)
-            f = kaiser_sinc_filter1d(0.25, 0.3, 12)     # Activation1d(up_ratio=2, down_ratio=2, kernel 12): cutoff 0.5/2, half width 0.6/2
-            for name, t in list(self._sd.items()) + [("aux.up_filter", f), ("aux.down_filter", f)]:
-                d = _dev_f32(t, dev)
-                _lib.check(lib.f5_bigvgan_load_weight(h, name.encode(), _ptr(d), _lib.shape_array(d.shape), d.dim(), st),
-                           f"f5_bigvgan_load_weight({name})")
-            _lib.check(lib.f5_bigvgan_finalize(h, st), "f5_bigvgan_finalize")
-        self._h, self._h_dev = h, dev
-        return h
+        return lib.f5_bigvgan_create(C.byref(cfg), C.byref(h))
+
+    def _aux_tables(self):
+        f = kaiser_sinc_filter1d(0.25, 0.3, 12)     # Activation1d(up_ratio=2, down_ratio=2, kernel 12): cutoff 0.5/2, half width 0.6/2
+        return [("aux.up_filter", f), ("aux.down_filter", f)]
 
     @torch.no_grad()
     def forward(self, mel: torch.Tensor) -> torch.Tensor:

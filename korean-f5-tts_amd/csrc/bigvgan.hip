@@ -11,7 +11,6 @@
 //                       12 upsampled samples around it, each a 6-tap sum over the input rows t-5 .. t+5 held in registers
 //   conv_post           Conv1d(C_last, 1, 7) + clamp / tanh, direct (168 MACs per sample)
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -348,10 +347,6 @@ static __global__ void bv_pack_convT_kernel(const float* __restrict__ in, float*
 
 // ------------------------------------------------------------------------------------------------ handle
 namespace {
-struct BT {
-    float* p = nullptr;
-    std::vector<int64_t> shape;
-};
 struct BConv { float *w = nullptr, *b = nullptr, *wn = nullptr; int ld = 0; bool split = false; };   // split: w in the split_planar layout (F5_PREC_F16X3)   // wn: bv_pack_narrow_kernel layout (C < 64 only)          // [Co, ld] tap-major, ld = round_up(k C, 32)
 struct BAct { float *alpha = nullptr, *beta = nullptr; };
 struct BRes { std::vector<BConv> c1, c2; std::vector<BAct> act; int k = 0; };
@@ -360,8 +355,8 @@ struct BUp { float *w = nullptr, *b = nullptr; int ci = 0, co = 0, k = 0, u = 0,
 
 struct f5_bigvgan {
     f5_bigvgan_config cfg{};
-    std::map<std::string, BT> raw;
-    std::vector<void*> owned;
+    WeightStore raw;
+    DevPool pool;   // what finalize built
     bool finalized = false;
     BConv pre;
     int kpre = 0;
@@ -371,11 +366,6 @@ struct f5_bigvgan {
     float *post_w = nullptr, *post_b = nullptr, *fu = nullptr, *fd = nullptr;
     int c_last = 0, total_up = 1;
     Arena arena;
-    ~f5_bigvgan() {
-        for (auto& kv : raw)
-            if (kv.second.p) (void)hipFree(kv.second.p);
-        for (void* p : owned) (void)hipFree(p);
-    }
 };
 
 extern "C" int f5_bigvgan_create(const f5_bigvgan_config* c, f5_bigvgan** out) {
@@ -407,60 +397,29 @@ extern "C" int f5_bigvgan_destroy(f5_bigvgan* v) {
 }
 extern "C" int f5_bigvgan_load_weight(f5_bigvgan* v, const char* name, const void* dev, const int64_t* shape, int32_t ndim,
                                       f5_stream stream) {
-    if (!v || !name || !dev || ndim < 0 || ndim > 4) return fail(F5_EINVAL, "f5_bigvgan_load_weight: bad arguments");
-    BT t;
-    t.shape.assign(shape, shape + ndim);
-    size_t n = 1;
-    for (auto d : t.shape) n *= (size_t)d;
-    auto it = v->raw.find(name);
-    if (it != v->raw.end()) {
-        (void)hipFree(it->second.p);
-        v->raw.erase(it);
-    }
-    HIPCHK(hipMalloc((void**)&t.p, std::max<size_t>(n * 4, 16)));
-    HIPCHK(hipMemcpyAsync(t.p, dev, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    v->raw[name] = t;
+    if (!v) return fail(F5_EINVAL, "f5_bigvgan_load_weight: bad arguments");
+    CHK(v->raw.put("f5_bigvgan_load_weight", name, dev, shape, ndim, (hipStream_t)stream));
     v->finalized = false;
     return F5_OK;
 }
 
-static int bneed(f5_bigvgan* v, const std::string& n, std::vector<int64_t> shape, const BT** out) {
-    auto it = v->raw.find(n);
-    if (it == v->raw.end()) return fail(F5_ESTATE, "missing bigvgan weight '%s'", n.c_str());
-    if (it->second.shape != shape) return fail(F5_EINVAL, "bigvgan weight '%s' has the wrong shape", n.c_str());
-    *out = &it->second;
-    return F5_OK;
-}
-static int balloc(f5_bigvgan* v, size_t n, float** out) {
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, std::max<size_t>(n * 4, 16)));
-    v->owned.push_back(p);
-    *out = (float*)p;
-    return F5_OK;
-}
-static int bcopy(f5_bigvgan* v, hipStream_t s, const std::string& n, std::vector<int64_t> shape, float** out) {
-    const BT* t = nullptr;
-    CHK(bneed(v, n, shape, &t));
-    size_t cnt = 1;
-    for (auto d : shape) cnt *= (size_t)d;
-    CHK(balloc(v, cnt, out));
-    HIPCHK(hipMemcpyAsync(*out, t->p, cnt * 4, hipMemcpyDeviceToDevice, s));
-    return F5_OK;
+static int weight_copy(f5_bigvgan* v, hipStream_t s, const std::string& n, std::vector<int64_t> shape, float** out) {
+    return v->pool.copy_of(v->raw, n, shape, "bigvgan", s, out);
 }
 // Conv1d weight [Co, Ci, k] (+ bias) -> tap-major GEMM operand [Co, round_up(k Ci, 32)]
 static int bconv(f5_bigvgan* v, hipStream_t s, const std::string& pfx, int Co, int Ci, int k, bool bias, BConv* c) {
-    const BT* t = nullptr;
-    CHK(bneed(v, pfx + ".weight", {Co, Ci, k}, &t));
+    const Tensor* t = nullptr;
+    CHK(v->raw.need(pfx + ".weight", {Co, Ci, k}, "bigvgan", &t));
     c->ld = round_up(k * Ci, 32);
-    CHK(balloc(v, (size_t)Co * c->ld, &c->w));
+    CHK(v->pool.alloc((size_t)Co * c->ld, &c->w));
     hipLaunchKernelGGL((conv_pack_kernel<float>), dim3(ew_blocks((long)Co * c->ld)), dim3(256), 0, s, t->p, c->w, (long)Co, Ci, k, c->ld);
     KCHK();
     c->b = nullptr;
-    if (bias) CHK(bcopy(v, s, pfx + ".bias", {Co}, &c->b));
+    if (bias) CHK(weight_copy(v, s, pfx + ".bias", {Co}, &c->b));
     c->wn = nullptr;
     if (Co == Ci && Ci % 4 == 0 && Ci < 64 && bias) {
         const int NT = (Co + 15) / 16, K = k * Ci;
-        CHK(balloc(v, (size_t)(K / 4) * NT * 64, &c->wn));
+        CHK(v->pool.alloc((size_t)(K / 4) * NT * 64, &c->wn));
         hipLaunchKernelGGL(bv_pack_narrow_kernel, dim3(ew_blocks((long)(K / 4) * NT * 64)), dim3(256), 0, s, c->w, c->wn, Co, c->ld, K, NT);
         KCHK();
     }
@@ -481,8 +440,7 @@ extern "C" int f5_bigvgan_finalize(f5_bigvgan* v, f5_stream stream) {
     if (!v) return fail(F5_EINVAL, "null bigvgan");
     hipStream_t s = (hipStream_t)stream;
     const f5_bigvgan_config& c = v->cfg;
-    for (void* p : v->owned) (void)hipFree(p);
-    v->owned.clear();
+    v->pool.clear();
     CHK(bconv(v, s, "conv_pre", c.upsample_initial_channel, c.num_mels, 7, true, &v->pre));
     v->ups.assign(c.num_upsamples, BUp{});
     v->res.assign((size_t)c.num_upsamples * c.num_kernels, BRes{});
@@ -491,9 +449,9 @@ extern "C" int f5_bigvgan_finalize(f5_bigvgan* v, f5_stream stream) {
         BUp& u = v->ups[i];
         u.ci = ch; u.co = ch / 2; u.k = c.upsample_kernel_sizes[i]; u.u = c.upsample_rates[i]; u.ld = round_up(ch, 32);
         const std::string p = "ups." + std::to_string(i) + ".0";
-        const BT* t = nullptr;
-        CHK(bneed(v, p + ".weight", {u.ci, u.co, u.k}, &t));
-        CHK(balloc(v, (size_t)u.k * u.co * u.ld, &u.w));
+        const Tensor* t = nullptr;
+        CHK(v->raw.need(p + ".weight", {u.ci, u.co, u.k}, "bigvgan", &t));
+        CHK(v->pool.alloc((size_t)u.k * u.co * u.ld, &u.w));
         hipLaunchKernelGGL(bv_pack_convT_kernel, dim3(ew_blocks((long)u.k * u.co * u.ld)), dim3(256), 0, s, t->p, u.w, u.ci, u.co, u.k, u.ld);
         KCHK();
         u.split = c.precision == F5_PREC_F16X3 && u.ci % 32 == 0;      // (K = ci must be whole K-tiles for the LDS-DMA kernels)
@@ -501,7 +459,7 @@ extern "C" int f5_bigvgan_finalize(f5_bigvgan* v, f5_stream stream) {
             hipLaunchKernelGGL(split_planar_kernel, dim3(ew_blocks((long)u.k * u.co * u.ld / 32)), dim3(256), 0, s, u.w, (long)u.k * u.co * u.ld / 32);
             KCHK();
         }
-        CHK(bcopy(v, s, p + ".bias", {u.co}, &u.b));
+        CHK(weight_copy(v, s, p + ".bias", {u.co}, &u.b));
         ch /= 2;
         for (int j = 0; j < c.num_kernels; ++j) {
             BRes& r = v->res[(size_t)i * c.num_kernels + j];
@@ -515,27 +473,25 @@ extern "C" int f5_bigvgan_finalize(f5_bigvgan* v, f5_stream stream) {
                 CHK(bconv(v, s, rp + ".convs2." + std::to_string(m), ch, ch, r.k, true, &r.c2[m]));
             }
             for (int a = 0; a < 2 * c.num_dilations; ++a) {
-                CHK(bcopy(v, s, rp + ".activations." + std::to_string(a) + ".act.alpha", {ch}, &r.act[a].alpha));
-                CHK(bcopy(v, s, rp + ".activations." + std::to_string(a) + ".act.beta", {ch}, &r.act[a].beta));
+                CHK(weight_copy(v, s, rp + ".activations." + std::to_string(a) + ".act.alpha", {ch}, &r.act[a].alpha));
+                CHK(weight_copy(v, s, rp + ".activations." + std::to_string(a) + ".act.beta", {ch}, &r.act[a].beta));
             }
         }
     }
-    CHK(bcopy(v, s, "activation_post.act.alpha", {v->c_last}, &v->post_act.alpha));
-    CHK(bcopy(v, s, "activation_post.act.beta", {v->c_last}, &v->post_act.beta));
+    CHK(weight_copy(v, s, "activation_post.act.alpha", {v->c_last}, &v->post_act.alpha));
+    CHK(weight_copy(v, s, "activation_post.act.beta", {v->c_last}, &v->post_act.beta));
     {   // conv_post [1, C, 7] -> [7][C]
-        const BT* t = nullptr;
-        CHK(bneed(v, "conv_post.weight", {1, v->c_last, 7}, &t));
-        CHK(balloc(v, (size_t)7 * v->c_last, &v->post_w));
+        const Tensor* t = nullptr;
+        CHK(v->raw.need("conv_post.weight", {1, v->c_last, 7}, "bigvgan", &t));
+        CHK(v->pool.alloc((size_t)7 * v->c_last, &v->post_w));
         hipLaunchKernelGGL((permute_last2_kernel<float>), dim3(ew_blocks(7L * v->c_last)), dim3(256), 0, s, t->p, v->post_w, 1L, v->c_last, 7);
         KCHK();
         v->post_b = nullptr;
-        if (c.use_bias_at_final) CHK(bcopy(v, s, "conv_post.bias", {1}, &v->post_b));
+        if (c.use_bias_at_final) CHK(weight_copy(v, s, "conv_post.bias", {1}, &v->post_b));
     }
-    CHK(bcopy(v, s, "aux.up_filter", {12}, &v->fu));
-    CHK(bcopy(v, s, "aux.down_filter", {12}, &v->fd));
+    CHK(weight_copy(v, s, "aux.up_filter", {12}, &v->fu));
+    CHK(weight_copy(v, s, "aux.down_filter", {12}, &v->fd));
     HIPCHK(hipStreamSynchronize(s));
-    for (auto& kv : v->raw)
-        if (kv.second.p) (void)hipFree(kv.second.p);
     v->raw.clear();
     v->finalized = true;
     return F5_OK;
@@ -589,15 +545,7 @@ extern "C" int f5_bigvgan_forward(f5_bigvgan* v, const float* mel, int32_t B, in
     };
     float *x, *r, *act, *t1, *col, *Z;
     Arena dry;
-    const size_t need_b = plan(dry, &x, &r, &act, &t1, &col, &Z);
-    if (need_b > v->arena.cap) {
-        HIPCHK(hipDeviceSynchronize());
-        if (v->arena.base) (void)hipFree(v->arena.base);
-        v->arena.base = nullptr;
-        v->arena.cap = 0;
-        HIPCHK(hipMalloc((void**)&v->arena.base, need_b));
-        v->arena.cap = need_b;
-    }
+    CHK(v->arena.reserve(plan(dry, &x, &r, &act, &t1, &col, &Z)));
     (void)plan(v->arena, &x, &r, &act, &t1, &col, &Z);
     const long Lout = (long)T * v->total_up;
     for (int b = 0; b < B; ++b) {

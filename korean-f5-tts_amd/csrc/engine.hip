@@ -112,7 +112,7 @@ extern "C" int f5_load_weight(f5_engine* e, const char* name, const void* dev, c
     e->clear_graphs();
     e->active = nullptr;   // the packed weights are about to be rebuilt: adapters made for them are stale
     e->adapt_gen++;
-    return e->ws.put(name, dev, shape, ndim, (hipStream_t)stream);
+    return e->ws.put("f5_load_weight", name, dev, shape, ndim, (hipStream_t)stream);
 }
 extern "C" int f5_finalize(f5_engine* e, f5_stream stream) {
     if (!e) return fail(F5_EINVAL, "null engine");
@@ -143,30 +143,18 @@ extern "C" int f5_finalize(f5_engine* e, f5_stream stream) {
         HIPCHK(hipMemcpy(e->base_table, tab.data(), tab.size() * sizeof(MergeDesc), hipMemcpyHostToDevice));
     }
     HIPCHK(hipStreamSynchronize(s));
-    // the raw fp32 copies are no longer needed
-    for (auto& kv : e->ws.t) {
-        if (kv.second.p) (void)hipFree(kv.second.p);
-        kv.second.p = nullptr;
-    }
-    e->ws.t.clear();
+    e->ws.clear();   // the raw fp32 copies are no longer needed
     e->finalized = true;
     return F5_OK;
 }
 int ensure_arena(f5_engine* e, int B, int N, int S) {
     B = std::max(B, e->res_B); N = std::max(N, e->res_N); S = std::max(S, e->res_S);
     const size_t need_b = F5_OPS(e, plan_bytes(e, B, N, S));
-    if (need_b > e->arena.cap) {
-        HIPCHK(hipDeviceSynchronize());
-        if (e->arena.base) (void)hipFree(e->arena.base);
-        e->arena.base = nullptr;
-        e->arena.cap = 0;
-        HIPCHK(hipMalloc((void**)&e->arena.base, need_b));
-        HIPCHK(hipMemset(e->arena.base, 0, need_b));  // padded K / V^T regions must never hold NaN bit patterns
-        e->arena.cap = need_b;
-        e->clear_graphs();                            // captured pointers are stale
-        e->uc_N = -1;                                 // ... and so is the cached unconditional text embedding
-    }
-    if (B != e->res_B || N != e->res_N || S != e->res_S) {   // the carve offsets move with the reservation
+    bool replaced = false;
+    CHK(e->arena.reserve(need_b, &replaced));
+    // a new block or a new reservation (the carve offsets move with it): captured pointers are stale, and so is the cached
+    // unconditional text embedding
+    if (replaced || B != e->res_B || N != e->res_N || S != e->res_S) {
         e->clear_graphs();
         e->uc_N = -1;
     }

@@ -26,43 +26,6 @@
 using namespace f5;
 #define fail f5_fail
 // ------------------------------------------------------------------------------------------- containers
-struct Tensor {
-    float* p = nullptr;
-    std::vector<int64_t> shape;
-    size_t numel() const {
-        size_t n = 1;
-        for (auto s : shape) n *= (size_t)s;
-        return n;
-    }
-};
-
-struct WeightStore {
-    std::map<std::string, Tensor> t;
-    ~WeightStore() {
-        for (auto& kv : t)
-            if (kv.second.p) (void)hipFree(kv.second.p);
-    }
-    int put(const char* name, const void* dev, const int64_t* shape, int ndim, hipStream_t s) {
-        if (!name || !dev || ndim < 0 || ndim > 4) return fail(F5_EINVAL, "f5_load_weight: bad arguments");
-        Tensor T;
-        T.shape.assign(shape, shape + ndim);
-        const size_t bytes = T.numel() * sizeof(float);
-        auto it = t.find(name);
-        if (it != t.end()) {
-            (void)hipFree(it->second.p);
-            t.erase(it);
-        }
-        HIPCHK(hipMalloc((void**)&T.p, bytes ? bytes : 4));
-        HIPCHK(hipMemcpyAsync(T.p, dev, bytes, hipMemcpyDeviceToDevice, s));
-        t[name] = T;
-        return F5_OK;
-    }
-    const Tensor* get(const std::string& n) const {
-        auto it = t.find(n);
-        return it == t.end() ? nullptr : &it->second;
-    }
-};
-
 // per-launch HIP-event profiler (off by default): one (start, stop) event pair per bracket on the launch stream
 struct Prof {
     enum { MAXEV = 65536 };

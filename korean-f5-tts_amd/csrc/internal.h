@@ -6,6 +6,9 @@
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
+#include <map>
+#include <string>
+#include <vector>
 
 #include "../../include/f5_hip.h"
 
@@ -35,11 +38,101 @@ struct Arena {
         if (base) (void)hipFree(base);
     }
     void reset() { off = 0; }
+    // The workspace rule of every stage: a call measures its plan on a dry-run Arena and reserves that many bytes here.  A block
+    // that is large enough stays; growth -- a device-wide synchronisation, a free and a hipMalloc -- is the only synchronisation and
+    // the only allocation of a call.  A new block is always zero-filled, so that no stage can read NaN bit patterns from padding
+    // it has not written (padded K / V^T regions, GEMM K padding, dead rows).  *replaced: pointers into the old block are stale.
+    int reserve(size_t need_b, bool* replaced = nullptr) {
+        if (replaced) *replaced = need_b > cap;
+        if (need_b <= cap) return F5_OK;
+        HIPCHK(hipDeviceSynchronize());
+        if (base) (void)hipFree(base);
+        base = nullptr;
+        cap = 0;
+        HIPCHK(hipMalloc((void**)&base, need_b));
+        HIPCHK(hipMemset(base, 0, need_b));
+        cap = need_b;
+        return F5_OK;
+    }
     template <typename U> U* take(size_t n) {
         off = align_up(off, 256);
         U* p = reinterpret_cast<U*>(base + off);
         off += n * sizeof(U);
         return p;
+    }
+};
+
+// Raw fp32 weights as the load entry points receive them, by state-dict name, until finalize has packed them.
+struct Tensor {
+    float* p = nullptr;
+    std::vector<int64_t> shape;
+    size_t numel() const {
+        size_t n = 1;
+        for (auto s : shape) n *= (size_t)s;
+        return n;
+    }
+};
+
+struct WeightStore {
+    std::map<std::string, Tensor> t;
+    ~WeightStore() { clear(); }
+    void clear() {
+        for (auto& kv : t)
+            if (kv.second.p) (void)hipFree(kv.second.p);
+        t.clear();
+    }
+    // device-to-device copy of one tensor, replacing an earlier one of that name (who: the calling entry point)
+    int put(const char* who, const char* name, const void* dev, const int64_t* shape, int ndim, hipStream_t s) {
+        if (!name || !dev || ndim < 0 || ndim > 4) return f5_fail(F5_EINVAL, "%s: bad arguments", who);
+        Tensor T;
+        T.shape.assign(shape, shape + ndim);
+        const size_t bytes = T.numel() * sizeof(float);
+        auto it = t.find(name);
+        if (it != t.end()) {
+            (void)hipFree(it->second.p);
+            t.erase(it);
+        }
+        HIPCHK(hipMalloc((void**)&T.p, std::max<size_t>(bytes, 16)));
+        HIPCHK(hipMemcpyAsync(T.p, dev, bytes, hipMemcpyDeviceToDevice, s));
+        t[name] = T;
+        return F5_OK;
+    }
+    const Tensor* get(const std::string& n) const {
+        auto it = t.find(n);
+        return it == t.end() ? nullptr : &it->second;
+    }
+    // the tensor of that name and exactly that shape (what: "vocos" / "bigvgan", for the message)
+    int need(const std::string& n, const std::vector<int64_t>& shape, const char* what, const Tensor** out) const {
+        const Tensor* x = get(n);
+        if (!x) return f5_fail(F5_ESTATE, "missing %s weight '%s'", what, n.c_str());
+        if (x->shape != shape) return f5_fail(F5_EINVAL, "%s weight '%s' has the wrong shape", what, n.c_str());
+        *out = x;
+        return F5_OK;
+    }
+};
+
+// The device buffers a finalize builds (packed weights, copies of the plain ones), freed together.
+struct DevPool {
+    std::vector<void*> bufs;
+    ~DevPool() { clear(); }
+    void clear() {
+        for (void* p : bufs) (void)hipFree(p);
+        bufs.clear();
+    }
+    template <typename U> int alloc(size_t n, U** out) {
+        void* p = nullptr;
+        HIPCHK(hipMalloc(&p, std::max<size_t>(n * sizeof(U), 16)));
+        bufs.push_back(p);
+        *out = reinterpret_cast<U*>(p);
+        return F5_OK;
+    }
+    int copy_of(const WeightStore& ws, const std::string& n, const std::vector<int64_t>& shape, const char* what, hipStream_t s,
+                float** out) {
+        const Tensor* x = nullptr;
+        CHK(ws.need(n, shape, what, &x));
+        CHK(alloc(x->numel(), out));
+        HIPCHK(hipMemcpyAsync(*out, x->p, x->numel() * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return F5_OK;
     }
 };
 
@@ -87,5 +180,14 @@ struct Staging {
         HIPCHK(hipEventRecord(ev[slot], s));
         used[slot] = true;
         return F5_OK;
+    }
+    // one table, one copy: fill(char* host) writes `bytes` into a slot, which is held until the copy to dev_dst has run
+    template <typename F> int upload(void* dev_dst, size_t bytes, hipStream_t s, F&& fill) {
+        char* hb = nullptr;
+        int slot = 0;
+        CHK(acquire(bytes, &hb, &slot));
+        fill(hb);
+        HIPCHK(hipMemcpyAsync(dev_dst, hb, bytes, hipMemcpyHostToDevice, s));
+        return release(slot, s);
     }
 };

@@ -9,7 +9,6 @@
 // mel_spec_type="bigvgan" (modules.py:33-75, get_bigvgan_mel_spectrogram) is the same pipeline with reflect padding
 // (n_fft - hop) / 2 and center=False (T = (nw + 2 pad - n_fft) / hop + 1), |S| = sqrt(re^2 + im^2 + 1e-9) and librosa's
 // slaney filterbank as the loaded table: f5_mel_forward_ex(pad, eps).
-#include <map>
 #include <string>
 #include <vector>
 
@@ -156,6 +155,53 @@ extern "C" int f5_mel_load(f5_mel* m, const char* name, const void* dev, const i
     HIPCHK(hipMemcpyAsync(*dst, dev, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return F5_OK;
 }
+namespace {
+// Workspace of one pass over R rows (frames): the rectangular call carves it for one item's T frames and reuses it item by
+// item, the ragged one for the packed rows of the whole batch, with the packed mel and the per-item tables behind it
+struct MelWork {
+    float *wp, *spec, *mag, *pk;
+    char* tab;
+};
+// The ragged call's per-item tables, wav_start[B] (int64) | row_start[B + 1] | nw[B] | frames[B]: one layout for the pinned
+// slot and for MelWork::tab
+struct MelTables {
+    long long* wav_start;
+    int *row_start, *nw, *frames;
+    MelTables(char* base, int B)
+        : wav_start(reinterpret_cast<long long*>(base)), row_start(reinterpret_cast<int*>(base + (size_t)B * 8)),
+          nw(row_start + B + 1), frames(nw + B) {}
+    static size_t bytes(int B) { return (size_t)B * 8 + ((size_t)3 * B + 1) * 4; }
+};
+}  // namespace
+
+// carves the workspace out of the handle's arena (Arena::reserve: growth is the only synchronisation of a call)
+static int mel_workspace(f5_mel* m, size_t signal_elems, int R, bool with_packed_out, size_t tab_bytes, MelWork* w) {
+    auto plan = [&](Arena& a) {
+        a.reset();
+        w->wp = a.take<float>(signal_elems);
+        w->spec = a.take<float>((size_t)R * m->ns);
+        w->mag = a.take<float>((size_t)R * m->kf);
+        w->pk = with_packed_out ? a.take<float>((size_t)R * m->n_mels) : nullptr;
+        w->tab = a.take<char>(tab_bytes);
+        return align_up(a.off, 256) + 256;
+    };
+    Arena dry;
+    CHK(m->arena.reserve(plan(dry)));
+    (void)plan(m->arena);
+    return F5_OK;
+}
+
+// STFT GEMM -> magnitude -> mel GEMM with the log epilogue over R frames.  The frames are a strided view of the padded
+// signal: row r starts at signal + r * hop (no im2col)
+static int mel_rows(f5_mel* m, hipStream_t s, const MelWork& w, const float* signal, int R, float mag_eps, float* out, int ld_out) {
+    HIPCHK(launch_gemm<float>(s, signal, m->hop, m->basis, m->n_fft, R, m->ns, m->n_fft, EpiStore<float>{w.spec, m->ns, nullptr, F5_ACT_NONE}));
+    hipLaunchKernelGGL(magnitude_kernel, dim3(ew_blocks((long)R * m->kf)), dim3(256), 0, s, w.spec, m->ns, w.mag, m->kf, (long)R, m->F,
+                       mag_eps);
+    KCHK();
+    HIPCHK(launch_gemm<float>(s, w.mag, m->kf, m->fb, m->kf, R, m->n_mels, m->kf, EpiStore<float>{out, ld_out, nullptr, F5_ACT_LOGCLAMP}));
+    return F5_OK;
+}
+
 // wav f32[B, nw] -> out f32[B, T, n_mels], T = nw / hop + 1 (center=True)
 extern "C" int f5_mel_forward(f5_mel* m, const float* wav, int32_t B, int32_t nw, float* out, f5_stream stream) {
     if (!m) return fail(F5_EINVAL, "f5_mel_forward: bad arguments");
@@ -170,38 +216,11 @@ extern "C" int f5_mel_forward_ex(f5_mel* m, const float* wav, int32_t B, int32_t
     if (nw <= pad || nw + 2 * pad < m->n_fft) return fail(F5_EINVAL, "f5_mel_forward: too few samples for the reflect padding / one frame");
     hipStream_t s = (hipStream_t)stream;
     const int T = (nw + 2 * pad - m->n_fft) / m->hop + 1, Lp = round_up(nw + 2 * pad, 4);
-    auto plan = [&](Arena& a, float** wp, float** spec, float** mag) {
-        a.reset();
-        *wp = a.take<float>((size_t)B * Lp + m->n_fft);
-        *spec = a.take<float>((size_t)T * m->ns);
-        *mag = a.take<float>((size_t)T * m->kf);
-        return align_up(a.off, 256) + 256;
-    };
-    float *wp, *spec, *mag;
-    Arena dry;
-    const size_t need_b = plan(dry, &wp, &spec, &mag);
-    if (need_b > m->arena.cap) {
-        HIPCHK(hipDeviceSynchronize());
-        if (m->arena.base) (void)hipFree(m->arena.base);
-        m->arena.base = nullptr;
-        m->arena.cap = 0;
-        HIPCHK(hipMalloc((void**)&m->arena.base, need_b));
-        HIPCHK(hipMemset(m->arena.base, 0, need_b));
-        m->arena.cap = need_b;
-    }
-    (void)plan(m->arena, &wp, &spec, &mag);
-    hipLaunchKernelGGL(reflect_pad_kernel, dim3(ew_blocks((long)B * Lp)), dim3(256), 0, s, wav, wp, B, nw, pad, Lp);
+    MelWork w;
+    CHK(mel_workspace(m, (size_t)B * Lp + m->n_fft, T, false, 0, &w));
+    hipLaunchKernelGGL(reflect_pad_kernel, dim3(ew_blocks((long)B * Lp)), dim3(256), 0, s, wav, w.wp, B, nw, pad, Lp);
     KCHK();
-    for (int b = 0; b < B; ++b) {
-        // frames are a strided view of the padded signal: row t starts at t*hop
-        HIPCHK(launch_gemm<float>(s, wp + (size_t)b * Lp, m->hop, m->basis, m->n_fft, T, m->ns, m->n_fft,
-                                  EpiStore<float>{spec, m->ns, nullptr, F5_ACT_NONE}));
-        hipLaunchKernelGGL(magnitude_kernel, dim3(ew_blocks((long)T * m->kf)), dim3(256), 0, s, spec, m->ns, mag, m->kf, (long)T, m->F,
-                           mag_eps);
-        KCHK();
-        HIPCHK(launch_gemm<float>(s, mag, m->kf, m->fb, m->kf, T, m->n_mels, m->kf,
-                                  EpiStore<float>{out + (size_t)b * T * m->n_mels, m->n_mels, nullptr, F5_ACT_LOGCLAMP}));
-    }
+    for (int b = 0; b < B; ++b) CHK(mel_rows(m, s, w, w.wp + (size_t)b * Lp, T, mag_eps, out + (size_t)b * T * m->n_mels, m->n_mels));
     return F5_OK;
 }
 
@@ -257,69 +276,33 @@ extern "C" int f5_mel_forward_ragged(f5_mel* m, const float* wav, int32_t B, con
                     (long long)T_out * m->n_mels);
     if (!m->basis || !m->fb) return fail(F5_ESTATE, "f5_mel_forward_ragged: aux.dft_basis / aux.mel_fb not loaded");
     hipStream_t s = (hipStream_t)stream;
-    // device tables behind the buffers: wav_start[B] (int64) | row_start[B + 1] | nw[B] | frames[B]
-    const size_t tab_bytes = (size_t)B * 8 + ((size_t)3 * B + 1) * 4;
-    float *wp, *spec, *mag, *pk;
-    char* tab;
-    auto plan = [&](Arena& a) {
-        a.reset();
-        wp = a.take<float>((size_t)R * m->hop + m->n_fft);
-        spec = a.take<float>((size_t)R * m->ns);
-        mag = a.take<float>((size_t)R * m->kf);
-        pk = a.take<float>((size_t)R * m->n_mels);
-        tab = a.take<char>(tab_bytes);
-        return align_up(a.off, 256) + 256;
-    };
-    Arena dry;
-    const size_t need_b = plan(dry);
-    if (need_b > m->arena.cap) {   // the rectangular call's rule: the only synchronisation and allocation of a call
-        HIPCHK(hipDeviceSynchronize());
-        if (m->arena.base) (void)hipFree(m->arena.base);
-        m->arena.base = nullptr;
-        m->arena.cap = 0;
-        HIPCHK(hipMalloc((void**)&m->arena.base, need_b));
-        HIPCHK(hipMemset(m->arena.base, 0, need_b));
-        m->arena.cap = need_b;
-    }
-    (void)plan(m->arena);
-    // one pinned slot, one copy (held until the copy has run); the device tables are read by this call's kernels only
-    char* hb = nullptr;
-    int slot = 0;
-    CHK(m->stage.acquire(tab_bytes, &hb, &slot));
-    long long* h_ws = reinterpret_cast<long long*>(hb);
-    int* h_rs = reinterpret_cast<int*>(hb + (size_t)B * 8);
-    int* h_nw = h_rs + B + 1;
-    int* h_fr = h_nw + B;
-    for (int b = 0; b < B; ++b) {
-        h_ws[b] = wav_start_host[b];
-        h_rs[b] = rs[b];
-        h_nw[b] = nw_host[b];
-        h_fr[b] = frames[b];
-    }
-    h_rs[B] = R;
-    HIPCHK(hipMemcpyAsync(tab, hb, tab_bytes, hipMemcpyHostToDevice, s));
-    CHK(m->stage.release(slot, s));
-    const long long* d_ws = reinterpret_cast<const long long*>(tab);
-    const int* d_rs = reinterpret_cast<const int*>(tab + (size_t)B * 8);
-    const int* d_nw = d_rs + B + 1;
-    const int* d_fr = d_nw + B;
+    MelWork w;
+    CHK(mel_workspace(m, (size_t)R * m->hop + m->n_fft, R, true, MelTables::bytes(B), &w));
+    // one pinned slot, one copy; the device tables are read by this call's kernels only
+    CHK(m->stage.upload(w.tab, MelTables::bytes(B), s, [&](char* host) {
+        const MelTables h(host, B);
+        for (int b = 0; b < B; ++b) {
+            h.wav_start[b] = wav_start_host[b];
+            h.row_start[b] = rs[b];
+            h.nw[b] = nw_host[b];
+            h.frames[b] = frames[b];
+        }
+        h.row_start[B] = R;
+    }));
+    const MelTables d(w.tab, B);
 
     const int pad_rows = R + (m->n_fft + m->hop - 1) / m->hop;
-    hipLaunchKernelGGL(reflect_pad_ragged_kernel, dim3((unsigned)std::min(pad_rows, 16384)), dim3(256), 0, s, wav, wp, d_ws, d_rs, d_nw,
-                       B, R, m->hop, pad, m->n_fft);
+    hipLaunchKernelGGL(reflect_pad_ragged_kernel, dim3((unsigned)std::min(pad_rows, 16384)), dim3(256), 0, s, wav, w.wp, d.wav_start,
+                       d.row_start, d.nw, B, R, m->hop, pad, m->n_fft);
     KCHK();
-    // frames are a strided view of the packed signal: row r starts at r*hop (dead rows included: they cost a few rows per item)
-    HIPCHK(launch_gemm<float>(s, wp, m->hop, m->basis, m->n_fft, R, m->ns, m->n_fft, EpiStore<float>{spec, m->ns, nullptr, F5_ACT_NONE}));
-    hipLaunchKernelGGL(magnitude_kernel, dim3(ew_blocks((long)R * m->kf)), dim3(256), 0, s, spec, m->ns, mag, m->kf, (long)R, m->F,
-                       mag_eps);
-    KCHK();
-    HIPCHK(launch_gemm<float>(s, mag, m->kf, m->fb, m->kf, R, m->n_mels, m->kf, EpiStore<float>{pk, m->n_mels, nullptr, F5_ACT_LOGCLAMP}));
+    // (dead rows included: they cost a few rows per item)
+    CHK(mel_rows(m, s, w, w.wp, R, mag_eps, w.pk, m->n_mels));
     const long quads = (long)B * T_out * (m->n_mels / 4);
     if ((reinterpret_cast<uintptr_t>(out) % 16) == 0 && out_stride_b % 4 == 0)
-        hipLaunchKernelGGL((mel_unpack_ragged_kernel<true>), dim3(ew_blocks(quads)), dim3(256), 0, s, pk, out, d_rs, d_fr, B, T_out,
+        hipLaunchKernelGGL((mel_unpack_ragged_kernel<true>), dim3(ew_blocks(quads)), dim3(256), 0, s, w.pk, out, d.row_start, d.frames, B, T_out,
                            m->n_mels, (long)out_stride_b);
     else
-        hipLaunchKernelGGL((mel_unpack_ragged_kernel<false>), dim3(ew_blocks(quads)), dim3(256), 0, s, pk, out, d_rs, d_fr, B, T_out,
+        hipLaunchKernelGGL((mel_unpack_ragged_kernel<false>), dim3(ew_blocks(quads)), dim3(256), 0, s, w.pk, out, d.row_start, d.frames, B, T_out,
                            m->n_mels, (long)out_stride_b);
     KCHK();
     return F5_OK;

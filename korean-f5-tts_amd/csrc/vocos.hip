@@ -6,7 +6,6 @@
 //                                hann window and 1/n_fft folded in; exact restatement of torch.istft's irfft * window)
 // followed by overlap-add / window-envelope normalisation / centre trim (torch.istft(center=True)).
 // f5_vocos_decode_ragged runs the same stages once over the packed frames of a batch of windows (ragged decode).
-#include <map>
 #include <string>
 #include <vector>
 
@@ -21,16 +20,19 @@ namespace {
 struct VBlock {
     float *dwk, *dwb, *lnw, *lnb, *w1, *b1, *w2, *b2, *gamma;
 };
-struct VT {
-    float* p = nullptr;
-    std::vector<int64_t> shape;
+// The ragged decode's per-item tables, row_start[B + 1] | mel_start[B] | gain[B]: one layout for the pinned slot and for VWork::tab
+struct VTables {
+    int *row_start, *mel_start;
+    float* gain;
+    VTables(void* base, int B) : row_start(static_cast<int*>(base)), mel_start(row_start + B + 1), gain(reinterpret_cast<float*>(mel_start + B)) {}
+    static size_t words(int B) { return (size_t)3 * B + 1; }
 };
 }  // namespace
 
 struct f5_vocos {
     f5_vocos_config cfg{};
-    std::map<std::string, VT> raw;
-    std::vector<void*> owned;
+    WeightStore raw;
+    DevPool pool;   // what finalize built
     bool finalized = false;
     int F = 0, K2 = 0, kemb = 0, head_n = 0;
     float *emb_w = nullptr, *emb_b = nullptr, *n0w = nullptr, *n0b = nullptr, *fnw = nullptr, *fnb = nullptr;
@@ -38,11 +40,6 @@ struct f5_vocos {
     std::vector<VBlock> blocks;
     Arena arena;
     Staging stage;   // pinned slots for the ragged decode's per-call tables
-    ~f5_vocos() {
-        for (auto& kv : raw)
-            if (kv.second.p) (void)hipFree(kv.second.p);
-        for (void* p : owned) (void)hipFree(p);
-    }
 };
 
 extern "C" int f5_vocos_create(const f5_vocos_config* c, f5_vocos** out) {
@@ -68,40 +65,9 @@ extern "C" int f5_vocos_destroy(f5_vocos* v) {
 }
 extern "C" int f5_vocos_load_weight(f5_vocos* v, const char* name, const void* dev, const int64_t* shape, int32_t ndim,
                                     f5_stream stream) {
-    if (!v || !name || !dev || ndim < 0 || ndim > 4) return fail(F5_EINVAL, "f5_vocos_load_weight: bad arguments");
-    VT t;
-    t.shape.assign(shape, shape + ndim);
-    size_t n = 1;
-    for (auto d : t.shape) n *= (size_t)d;
-    auto it = v->raw.find(name);
-    if (it != v->raw.end()) {
-        (void)hipFree(it->second.p);
-        v->raw.erase(it);
-    }
-    HIPCHK(hipMalloc((void**)&t.p, std::max<size_t>(n * 4, 16)));
-    HIPCHK(hipMemcpyAsync(t.p, dev, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    v->raw[name] = t;
+    if (!v) return fail(F5_EINVAL, "f5_vocos_load_weight: bad arguments");
+    CHK(v->raw.put("f5_vocos_load_weight", name, dev, shape, ndim, (hipStream_t)stream));
     v->finalized = false;
-    return F5_OK;
-}
-
-static int vneed(f5_vocos* v, const std::string& n, std::vector<int64_t> shape, const VT** out) {
-    auto it = v->raw.find(n);
-    if (it == v->raw.end()) return fail(F5_ESTATE, "missing vocos weight '%s'", n.c_str());
-    if (it->second.shape != shape) return fail(F5_EINVAL, "vocos weight '%s' has the wrong shape", n.c_str());
-    *out = &it->second;
-    return F5_OK;
-}
-static int vcopy(f5_vocos* v, hipStream_t s, const std::string& n, std::vector<int64_t> shape, float** out) {
-    const VT* t = nullptr;
-    CHK(vneed(v, n, shape, &t));
-    size_t cnt = 1;
-    for (auto d : shape) cnt *= (size_t)d;
-    void* p = nullptr;
-    HIPCHK(hipMalloc(&p, std::max<size_t>(cnt * 4, 16)));
-    v->owned.push_back(p);
-    HIPCHK(hipMemcpyAsync(p, t->p, cnt * 4, hipMemcpyDeviceToDevice, s));
-    *out = (float*)p;
     return F5_OK;
 }
 
@@ -110,69 +76,58 @@ extern "C" int f5_vocos_finalize(f5_vocos* v, f5_stream stream) {
     hipStream_t s = (hipStream_t)stream;
     const f5_vocos_config& c = v->cfg;
     const int C = c.input_channels, D = c.dim, I = c.intermediate_dim;
-    for (void* p : v->owned) (void)hipFree(p);
-    v->owned.clear();
+    v->pool.clear();
+    auto copy = [&](const std::string& n, std::vector<int64_t> shape, float** out) { return v->pool.copy_of(v->raw, n, shape, "vocos", s, out); };
     // embed conv [D, C, 7] -> [D, 7*C]
-    const VT* t = nullptr;
-    CHK(vneed(v, "backbone.embed.weight", {D, C, 7}, &t));
-    void* p = nullptr;
+    const Tensor* t = nullptr;
+    CHK(v->raw.need("backbone.embed.weight", {D, C, 7}, "vocos", &t));
     {
         Scratch<float> tmp;  // [D, 7*C] tap-major, then zero-padded to kemb columns
         HIPCHK(tmp.alloc((size_t)D * 7 * C));
         hipLaunchKernelGGL((permute_last2_kernel<float>), dim3(ew_blocks((long)D * 7 * C)), dim3(256), 0, s, t->p, tmp.p,
                            (long)D, C, 7);
-        HIPCHK(hipMalloc(&p, (size_t)D * v->kemb * 4));
-        v->owned.push_back(p);
-        v->emb_w = (float*)p;
+        CHK(v->pool.alloc((size_t)D * v->kemb, &v->emb_w));
         hipLaunchKernelGGL((cast_pad_kernel<float>), dim3(ew_blocks((long)D * v->kemb)), dim3(256), 0, s, tmp.p, 7 * C, D,
                            7 * C, v->emb_w, v->kemb, D);
         KCHK();
         HIPCHK(hipStreamSynchronize(s));
     }
-    CHK(vcopy(v, s, "backbone.embed.bias", {D}, &v->emb_b));
-    CHK(vcopy(v, s, "backbone.norm.weight", {D}, &v->n0w));
-    CHK(vcopy(v, s, "backbone.norm.bias", {D}, &v->n0b));
-    CHK(vcopy(v, s, "backbone.final_layer_norm.weight", {D}, &v->fnw));
-    CHK(vcopy(v, s, "backbone.final_layer_norm.bias", {D}, &v->fnb));
+    CHK(copy("backbone.embed.bias", {D}, &v->emb_b));
+    CHK(copy("backbone.norm.weight", {D}, &v->n0w));
+    CHK(copy("backbone.norm.bias", {D}, &v->n0b));
+    CHK(copy("backbone.final_layer_norm.weight", {D}, &v->fnw));
+    CHK(copy("backbone.final_layer_norm.bias", {D}, &v->fnb));
     v->blocks.resize(c.num_layers);
     for (int i = 0; i < c.num_layers; ++i) {
         const std::string pf = "backbone.convnext." + std::to_string(i);
         VBlock& b = v->blocks[i];
-        CHK(vneed(v, pf + ".dwconv.weight", {D, 1, 7}, &t));
-        HIPCHK(hipMalloc(&p, (size_t)7 * D * 4));
-        v->owned.push_back(p);
-        b.dwk = (float*)p;
+        CHK(v->raw.need(pf + ".dwconv.weight", {D, 1, 7}, "vocos", &t));
+        CHK(v->pool.alloc((size_t)7 * D, &b.dwk));
         hipLaunchKernelGGL((permute_last2_kernel<float>), dim3(ew_blocks(7L * D)), dim3(256), 0, s, t->p, b.dwk, 1L, D, 7);
         KCHK();
-        CHK(vcopy(v, s, pf + ".dwconv.bias", {D}, &b.dwb));
-        CHK(vcopy(v, s, pf + ".norm.weight", {D}, &b.lnw));
-        CHK(vcopy(v, s, pf + ".norm.bias", {D}, &b.lnb));
-        CHK(vcopy(v, s, pf + ".pwconv1.weight", {I, D}, &b.w1));
-        CHK(vcopy(v, s, pf + ".pwconv1.bias", {I}, &b.b1));
-        CHK(vcopy(v, s, pf + ".pwconv2.weight", {D, I}, &b.w2));
-        CHK(vcopy(v, s, pf + ".pwconv2.bias", {D}, &b.b2));
-        CHK(vcopy(v, s, pf + ".gamma", {D}, &b.gamma));
+        CHK(copy(pf + ".dwconv.bias", {D}, &b.dwb));
+        CHK(copy(pf + ".norm.weight", {D}, &b.lnw));
+        CHK(copy(pf + ".norm.bias", {D}, &b.lnb));
+        CHK(copy(pf + ".pwconv1.weight", {I, D}, &b.w1));
+        CHK(copy(pf + ".pwconv1.bias", {I}, &b.b1));
+        CHK(copy(pf + ".pwconv2.weight", {D, I}, &b.w2));
+        CHK(copy(pf + ".pwconv2.bias", {D}, &b.b2));
+        CHK(copy(pf + ".gamma", {D}, &b.gamma));
     }
     // head: [n_fft + 2, D] padded to head_n rows (zero rows / zero bias)
-    CHK(vneed(v, "head.out.weight", {c.n_fft + 2, D}, &t));
-    HIPCHK(hipMalloc(&p, (size_t)v->head_n * D * 4));
-    v->owned.push_back(p);
-    v->head_w = (float*)p;
+    CHK(v->raw.need("head.out.weight", {c.n_fft + 2, D}, "vocos", &t));
+    CHK(v->pool.alloc((size_t)v->head_n * D, &v->head_w));
     hipLaunchKernelGGL((cast_pad_kernel<float>), dim3(ew_blocks((long)v->head_n * D)), dim3(256), 0, s, t->p, D, c.n_fft + 2,
                        D, v->head_w, D, v->head_n);
     KCHK();
-    CHK(vneed(v, "head.out.bias", {c.n_fft + 2}, &t));
-    HIPCHK(hipMalloc(&p, (size_t)v->head_n * 4));
-    v->owned.push_back(p);
-    v->head_b = (float*)p;
+    CHK(v->raw.need("head.out.bias", {c.n_fft + 2}, "vocos", &t));
+    CHK(v->pool.alloc((size_t)v->head_n, &v->head_b));
     hipLaunchKernelGGL((cast_pad_kernel<float>), dim3(1), dim3(256), 0, s, t->p, c.n_fft + 2, 1, c.n_fft + 2, v->head_b,
                        v->head_n, 1);
     KCHK();
-    CHK(vcopy(v, s, "aux.hann", {c.n_fft}, &v->hann));
-    CHK(vcopy(v, s, "aux.idft_basis", {c.n_fft, v->K2}, &v->basis));
+    CHK(copy("aux.hann", {c.n_fft}, &v->hann));
+    CHK(copy("aux.idft_basis", {c.n_fft, v->K2}, &v->basis));
     HIPCHK(hipStreamSynchronize(s));
-    for (auto& kv : v->raw)
-        if (kv.second.p) (void)hipFree(kv.second.p);
     v->raw.clear();
     v->finalized = true;
     return F5_OK;
@@ -187,11 +142,11 @@ namespace {
 // Workspace of one decode over R rows (frames): the rectangular call has R = B * T, the ragged one R = sum of T_b packed rows
 struct VWork {
     float *col, *x, *t1, *h, *hd, *S, *fr;
-    int* tab;   // ragged only: row_start[B + 1] | mel_start[B] | gain[B] (f32 bits)
+    int* tab;   // ragged only: VTables
 };
 }  // namespace
 
-// carves the workspace out of the handle's arena, growing it (the only synchronisation of a decode) when it is too small
+// carves the workspace out of the handle's arena (Arena::reserve: growth is the only synchronisation of a decode)
 static int vocos_workspace(f5_vocos* v, long R, size_t ntab, VWork* w) {
     const f5_vocos_config& c = v->cfg;
     auto plan = [&](Arena& a) {
@@ -207,15 +162,7 @@ static int vocos_workspace(f5_vocos* v, long R, size_t ntab, VWork* w) {
         return align_up(a.off, 256) + 256;
     };
     Arena dry;
-    const size_t need_b = plan(dry);
-    if (need_b > v->arena.cap) {
-        HIPCHK(hipDeviceSynchronize());
-        if (v->arena.base) (void)hipFree(v->arena.base);
-        v->arena.base = nullptr;
-        v->arena.cap = 0;
-        HIPCHK(hipMalloc((void**)&v->arena.base, need_b));
-        v->arena.cap = need_b;
-    }
+    CHK(v->arena.reserve(plan(dry)));
     (void)plan(v->arena);
     return F5_OK;
 }
@@ -295,26 +242,21 @@ extern "C" int f5_vocos_decode_ragged(f5_vocos* v, const float* mel, int32_t B, 
     if (R > (1L << 24)) return fail(F5_EINVAL, "f5_vocos_decode_ragged: %ld frames in one call (at most 2^24: the GEMMs index rows as int)", R);
     hipStream_t s = (hipStream_t)stream;
     VWork w;
-    CHK(vocos_workspace(v, R, (size_t)3 * B + 1, &w));
-    // the segment table, the window starts and the gains go down through one pinned slot (held until the copy has run); the
-    // device copy is read by this call's kernels only, which are ahead of the next call's copy on the stream
-    char* hb = nullptr;
-    int slot = 0;
-    CHK(v->stage.acquire(((size_t)3 * B + 1) * 4, &hb, &slot));
-    int* rs = reinterpret_cast<int*>(hb);
-    int* ms = rs + B + 1;
-    float* gh = reinterpret_cast<float*>(ms + B);
-    rs[0] = 0;
-    for (int b = 0; b < B; ++b) {
-        ms[b] = starts_host ? starts_host[b] : 0;
-        rs[b + 1] = rs[b] + (ends_host[b] - ms[b]);
-        gh[b] = gain_host ? gain_host[b] : 1.0f;
-    }
-    HIPCHK(hipMemcpyAsync(w.tab, hb, ((size_t)3 * B + 1) * 4, hipMemcpyHostToDevice, s));
-    CHK(v->stage.release(slot, s));
-    const int* row_start = w.tab;
-    const int* mel_start = w.tab + B + 1;
-    const float* gain = reinterpret_cast<const float*>(w.tab + 2 * B + 1);
+    CHK(vocos_workspace(v, R, VTables::words(B), &w));
+    // the segment table, the window starts and the gains go down through one pinned slot; the device copy is read by this
+    // call's kernels only, which are ahead of the next call's copy on the stream
+    CHK(v->stage.upload(w.tab, VTables::words(B) * 4, s, [&](char* host) {
+        const VTables h(host, B);
+        h.row_start[0] = 0;
+        for (int b = 0; b < B; ++b) {
+            h.mel_start[b] = starts_host ? starts_host[b] : 0;
+            h.row_start[b + 1] = h.row_start[b] + (ends_host[b] - h.mel_start[b]);
+            h.gain[b] = gain_host ? gain_host[b] : 1.0f;
+        }
+    }));
+    const VTables d(w.tab, B);
+    const int *row_start = d.row_start, *mel_start = d.mel_start;
+    const float* gain = d.gain;
 
     hipLaunchKernelGGL(im2col7_ragged_kernel, dim3((unsigned)std::min(R, 16384L)), dim3(256), 0, s, mel, (long)stride_b,
                        (long)stride_c, (long)stride_t, row_start, mel_start, w.col, B, c.input_channels, (int)R, v->kemb);

@@ -10,19 +10,8 @@ import math
 import torch
 
 from . import _lib
+from ._lib import _dev_f32, _ptr, _stream_ptr  # noqa: F401  (`from .engine import _ptr` keeps working)
 from .config import normalize_arch
-
-
-def _stream_ptr(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: torch.Tensor | None) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
-def _dev_f32(t: torch.Tensor, device) -> torch.Tensor:
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
 def _h2d_async(t: torch.Tensor, device, dtype) -> torch.Tensor:

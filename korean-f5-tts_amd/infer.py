@@ -30,9 +30,9 @@ import re
 import numpy as np
 import torch
 
-from .cfm import CFM
+from .cfm import CFM, clamp_durations
 from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
-from .utils import load_vocab
+from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
 
 target_sample_rate = SAMPLE_RATE
@@ -128,20 +128,7 @@ def load_checkpoint(model, ckpt_path: str, device: str, dtype=None, use_ema: boo
     """Loads a reference checkpoint into a CFM whose backbone is a HIP backbone.  `dtype` is accepted for signature
     compatibility; the engine's operand precision is the backbone's `precision` (weights are kept in fp32 on the host
     and converted when they are uploaded)."""
-    if ckpt_path.split(".")[-1] == "safetensors":
-        from safetensors.torch import load_file
-
-        ckpt = load_file(ckpt_path, device="cpu")
-        ckpt = {"ema_model_state_dict": ckpt} if use_ema else {"model_state_dict": ckpt}
-    else:
-        ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
-    if use_ema:
-        sd = {k.replace("ema_model.", ""): v for k, v in ckpt["ema_model_state_dict"].items() if k not in ("initted", "step")}
-        for legacy in ("mel_spec.mel_stft.mel_scale.fb", "mel_spec.mel_stft.spectrogram.window"):
-            sd.pop(legacy, None)
-    else:
-        sd = ckpt["model_state_dict"]
-    model.load_state_dict(convert_peft_state_dict_to_plain(sd))
+    model.load_state_dict(convert_peft_state_dict_to_plain(_read_checkpoint_state_dict(ckpt_path, use_ema)))
     return model.to(device)
 
 
@@ -297,7 +284,7 @@ def wave_crossfade(wav: torch.Tensor, lens: list[int], cross_fade_samples: int) 
     import ctypes as C
 
     from . import _lib
-    from .engine import _ptr, _stream_ptr
+    from ._lib import _ptr, _stream_ptr
 
     if wav.device.type != "cuda":
         raise RuntimeError("the HIP cross-fade only runs on a GPU (there is no CPU path: cross_fade_concat is the host form)")
@@ -330,6 +317,31 @@ def _warn_untokenised(model_obj, toks, stacklevel):
                           "this checkpoint expects a tokenised input (text_tokenizer=)", RuntimeWarning, stacklevel=stacklevel)
 
 
+def _tokenise(model_obj, texts, text_tokenizer, stacklevel):
+    """The text front-end of the batch drivers: `text_tokenizer` per string where one is given, the untokenised-text warning
+    (stacklevel as the caller would pass it to warnings.warn: 3 = the frame that called the caller; None: no warning), then
+    ids through the model's vocabulary, or utf-8 bytes when it has none, exactly as CFM.sample does for list[str].
+    Returns (texts as sample() takes them, ids)."""
+    if text_tokenizer is not None:
+        texts = [text_tokenizer(t) for t in texts]
+    if stacklevel is not None:
+        for t in texts:
+            _warn_untokenised(model_obj, t, stacklevel=stacklevel + 1)
+    vocab = getattr(model_obj, "vocab_char_map", None)
+    return texts, (list_str_to_idx(texts, vocab) if vocab is not None else list_str_to_tensor(texts))
+
+
+def _require_ragged_vocoder(vocoder, who, hint):
+    if not hasattr(vocoder, "decode_ragged"):
+        raise NotImplementedError(f"{who} decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
+                                  f"decode (BigVGAN: {hint})")
+
+
+def _progress(progress, iterable):
+    """`progress`: None or an object with `.tqdm(iterable)` (the reference passes the tqdm module)."""
+    return progress.tqdm(iterable) if progress is not None and hasattr(progress, "tqdm") else iterable
+
+
 def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *, mel_spec_type=mel_spec_type, progress=None,
                     target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                     sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
@@ -353,13 +365,8 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
         with `attn_mask_enabled=True` the backbone runs the valid rows only (RowPack).  With `attn_mask_enabled=False` (the
         shipped configs) a shorter chunk attends over the padded frames up to the group's longest, exactly as in the
         reference's own batch driver (eval/eval_infer_batch.py, cfm.py:155-158)."""
-    from .cfm import clamp_durations
-    from .utils import list_str_to_idx, list_str_to_tensor
-
     _require_text_tokenizer(model_obj, text_tokenizer)
-    if not hasattr(vocoder, "decode_ragged"):
-        raise NotImplementedError(f"synthesize_long decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
-                                  "decode (BigVGAN: use the sequential path, batched=False)")
+    _require_ragged_vocoder(vocoder, "synthesize_long", "use the sequential path, batched=False")
     gen_text_batches = list(gen_text_batches)
     if not gen_text_batches:
         raise ValueError("synthesize_long: no text to synthesise")
@@ -371,18 +378,16 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
     texts, durations = [], []
     for gen_text in gen_text_batches:
         a, rms, rtext, ref_len, duration = prompt_numerics(audio, sr, ref_text, gen_text, speed, fix_duration, target_rms)
-        texts.append(text_tokenizer(rtext + gen_text) if text_tokenizer is not None else rtext + gen_text)
-        _warn_untokenised(model_obj, texts[-1], stacklevel=3)
+        texts.append(rtext + gen_text)
         durations.append(duration)
-    vocab = getattr(model_obj, "vocab_char_map", None)
-    idx = list_str_to_idx(texts, vocab) if vocab is not None else list_str_to_tensor(texts)
+    texts, idx = _tokenise(model_obj, texts, text_tokenizer, stacklevel=3)
     with torch.inference_mode():
         cond = model_obj.mel_spec(a.to(device)).permute(0, 2, 1)                # [1, T, 100], T = ref_len + 1 (centre padding)
         cond_len = cond.shape[1]
         ends = clamp_durations(idx, torch.full((len(texts),), cond_len, dtype=torch.long), torch.tensor(durations)).tolist()
         groups = group_chunks(ends, batch_frames)
         rows, lens, specs = [], [], []
-        for run in (progress.tqdm(groups) if progress is not None and hasattr(progress, "tqdm") else groups):
+        for run in _progress(progress, groups):
             B = len(run)
             generated, _ = model_obj.sample(cond=cond.expand(B, -1, -1), text=[texts[k] for k in run],
                                             duration=torch.tensor([durations[k] for k in run]),
@@ -465,7 +470,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                 wave = wave * rms / target_rms
             return wave.squeeze().cpu().numpy(), generated[0].cpu().numpy()
 
-    batches = progress.tqdm(gen_text_batches) if progress is not None and hasattr(progress, "tqdm") else gen_text_batches
+    batches = _progress(progress, gen_text_batches)
     if streaming:
         for gen_text in batches:
             wave, _spec = process_batch(gen_text)
@@ -489,17 +494,11 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
     (Vocos.decode_ragged) instead of one decode per item.  `duration_i` are the clamped totals sample() ran at.
     Returns (wav f32[B, L_max], wav_lens, mel): wav[i, :wav_lens[i]] is item i's waveform (times gain[i] where given), zeros
     behind it; mel is sample()'s output [B, N, 100], prompts included.  Vocos only."""
-    from .cfm import clamp_durations
-    from .utils import list_str_to_idx, list_str_to_tensor
-
-    if not hasattr(vocoder, "decode_ragged"):
-        raise NotImplementedError(f"synthesize_batch decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
-                                  "decode (BigVGAN: decode item by item)")
+    _require_ragged_vocoder(vocoder, "synthesize_batch", "decode item by item")
     if sample_kw.get("vocoder") is not None:
         raise TypeError("synthesize_batch: pass the vocoder as its second argument, not through sample()'s vocoder=")
     if isinstance(text, list):
-        vocab = getattr(model, "vocab_char_map", None)
-        text = list_str_to_idx(text, vocab) if vocab is not None else list_str_to_tensor(text)
+        text = _tokenise(model, text, None, stacklevel=None)[1]   # (as before: this driver does not warn)
     lens = torch.as_tensor(lens).to("cpu", torch.long)
     ends = clamp_durations(text.to("cpu", torch.long), lens, duration, sample_kw.get("max_duration", 65536))
     mel, _ = model.sample(cond, text, duration, lens=lens, **sample_kw)
@@ -542,13 +541,8 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
     `wave * rms_i / target_rms` on exactly the rows with rms_i < target_rms, as the sequential path writes it (not a
     decode_ragged gain: one multiply is not bit-equal to a multiply and a divide).
     Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Vocos only."""
-    from .cfm import clamp_durations
-    from .utils import list_str_to_idx, list_str_to_tensor
-
     _require_text_tokenizer(model, text_tokenizer)
-    if not hasattr(vocoder, "decode_ragged"):
-        raise NotImplementedError(f"synthesize_prompts decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
-                                  "decode (BigVGAN: decode item by item)")
+    _require_ragged_vocoder(vocoder, "synthesize_prompts", "decode item by item")
     prompts, gen_texts = list(prompts), list(gen_texts)
     if not prompts:
         raise ValueError("synthesize_prompts: no prompt to synthesise from")
@@ -556,11 +550,7 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
         raise ValueError(f"synthesize_prompts: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt)")
     with torch.inference_mode():
         pb = prompt_batch(prompts, gen_texts, speed=speed, target_rms=target_rms, mel_spec=model.mel_spec, device=model.device)
-        texts = [text_tokenizer(t) for t in pb["texts"]] if text_tokenizer is not None else pb["texts"]
-        for t in texts:
-            _warn_untokenised(model, t, stacklevel=3)
-        vocab = getattr(model, "vocab_char_map", None)
-        idx = list_str_to_idx(texts, vocab) if vocab is not None else list_str_to_tensor(texts)
+        texts, idx = _tokenise(model, pb["texts"], text_tokenizer, stacklevel=3)
         lens, durations, rms = pb["lens"], pb["durations"], pb["rms"]
         ends = clamp_durations(idx.to("cpu", torch.long), torch.tensor(lens), torch.tensor(durations),
                                sample_kw.get("max_duration", 65536)).tolist()

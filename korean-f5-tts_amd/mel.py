@@ -14,9 +14,10 @@ import ctypes as C
 import math
 
 import torch
-from torch import nn
 
 from . import _lib
+from ._lib import _ptr, _stream_ptr
+from .native import NativeModule
 
 
 def htk_mel_filterbank(n_freqs: int, n_mels: int, sample_rate: int, f_min: float = 0.0, f_max: float | None = None):
@@ -69,7 +70,10 @@ def stft_basis(n_fft: int) -> torch.Tensor:
     return B.to(torch.float32)
 
 
-class MelSpec(nn.Module):
+class MelSpec(NativeModule):
+    _prefix, _load, _finalize = "f5_mel", "f5_mel_load", False
+    _no_cpu = "the HIP mel front-end only runs on a GPU (there is no CPU path)"
+
     def __init__(self, n_fft=1024, hop_length=256, win_length=1024, n_mel_channels=100, target_sample_rate=24_000,
                  mel_spec_type="vocos"):
         super().__init__()
@@ -79,48 +83,31 @@ class MelSpec(nn.Module):
         self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
         self.n_mel_channels, self.target_sample_rate = n_mel_channels, target_sample_rate
         self.mel_spec_type = mel_spec_type
-        self._h = None
-        self._h_dev = None
 
-    def _handle(self, dev):
-        if self._h is not None and self._h_dev == dev:
-            return self._h
-        lib = _lib.load()
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(lib.f5_mel_create(self.n_fft, self.hop_length, self.n_mel_channels, C.byref(h)), "f5_mel_create")
-            Fb = self.n_fft // 2 + 1
-            kf = (Fb + 31) // 32 * 32
-            fb = torch.zeros(self.n_mel_channels, kf)
-            make_fb = htk_mel_filterbank if self.mel_spec_type == "vocos" else slaney_mel_filterbank
-            fb[:, :Fb] = make_fb(Fb, self.n_mel_channels, self.target_sample_rate)
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            for name, t in (("aux.dft_basis", stft_basis(self.n_fft)), ("aux.mel_fb", fb)):
-                d = t.to(dev).contiguous()
-                _lib.check(lib.f5_mel_load(h, name.encode(), C.c_void_p(d.data_ptr()), _lib.shape_array(d.shape), 2, st),
-                           f"f5_mel_load({name})")
-            torch.cuda.synchronize(dev)
-        self._h, self._h_dev = h, dev
-        return h
+    def _create(self, lib, h):
+        return lib.f5_mel_create(self.n_fft, self.hop_length, self.n_mel_channels, C.byref(h))
+
+    def _tensors(self):
+        Fb = self.n_fft // 2 + 1
+        fb = torch.zeros(self.n_mel_channels, (Fb + 31) // 32 * 32)
+        make_fb = htk_mel_filterbank if self.mel_spec_type == "vocos" else slaney_mel_filterbank
+        fb[:, :Fb] = make_fb(Fb, self.n_mel_channels, self.target_sample_rate)
+        return [("aux.dft_basis", stft_basis(self.n_fft)), ("aux.mel_fb", fb)]
 
     @torch.no_grad()
     def forward(self, wav: torch.Tensor) -> torch.Tensor:
         """wav f32[b, nw] (or [b, 1, nw]) on a GPU -> log-mel f32[b, n_mels, T] (the reference's layout)."""
         if wav.dim() == 3:
             wav = wav.squeeze(1)
-        if wav.device.type != "cuda":
-            raise RuntimeError("the HIP mel front-end only runs on a GPU (there is no CPU path)")
         dev = wav.device
+        h = self._handle(dev)
         wav = wav.to(torch.float32).contiguous()
         B, nw = wav.shape
-        vocos = self.mel_spec_type == "vocos"
-        pad, eps = (self.n_fft // 2, 0.0) if vocos else ((self.n_fft - self.hop_length) // 2, 1e-9)
+        pad, eps = self._variant()
         T = (nw + 2 * pad - self.n_fft) // self.hop_length + 1
         out = torch.empty(B, T, self.n_mel_channels, device=dev, dtype=torch.float32)
-        h = self._handle(dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().f5_mel_forward_ex(h, C.c_void_p(wav.data_ptr()), B, nw, pad, eps, C.c_void_p(out.data_ptr()),
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "f5_mel_forward")
+            _lib.check(_lib.load().f5_mel_forward_ex(h, _ptr(wav), B, nw, pad, eps, _ptr(out), _stream_ptr(dev)), "f5_mel_forward")
         return out.permute(0, 2, 1)
 
     def _variant(self):
@@ -147,7 +134,7 @@ class MelSpec(nn.Module):
         else:
             dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         if dev.type != "cuda":
-            raise RuntimeError("the HIP mel front-end only runs on a GPU (there is no CPU path)")
+            raise RuntimeError(self._no_cpu)
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         if any(d != dev for d in on_gpu):
@@ -173,7 +160,6 @@ class MelSpec(nn.Module):
         out = torch.empty(B, T, self.n_mel_channels, device=dev, dtype=torch.float32)
         h = self._handle(dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.f5_mel_forward_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), nw_arr, pad, eps,
-                                                 C.c_void_p(out.data_ptr()), T * self.n_mel_channels, T,
-                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "f5_mel_forward_ragged")
+            _lib.check(lib.f5_mel_forward_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), nw_arr, pad, eps, _ptr(out),
+                                                 T * self.n_mel_channels, T, _stream_ptr(dev)), "f5_mel_forward_ragged")
         return out.permute(0, 2, 1), frames

@@ -7,12 +7,12 @@ from __future__ import annotations
 import ctypes as C
 
 import torch
-from torch import nn
 
 from . import _lib
 from . import weights as W
+from ._lib import _ptr, _stream_ptr
 from .config import VOCOS_24K
-from .engine import _dev_f32, _ptr, _stream_ptr
+from .native import NativeVocoder
 
 
 def idft_basis(n_fft: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -37,76 +37,29 @@ def idft_basis(n_fft: int) -> tuple[torch.Tensor, torch.Tensor]:
     return torch.hann_window(n_fft, dtype=torch.float32), B.to(torch.float32)
 
 
-class Vocos(nn.Module):
+class Vocos(NativeVocoder):
+    _prefix, _load = "f5_vocos", "f5_vocos_load_weight"
+
     def __init__(self, cfg: dict = VOCOS_24K, device=None):
-        super().__init__()
-        self.cfg = dict(cfg)
-        self._sd: dict[str, torch.Tensor] = {}
-        self._h = None
-        self._h_dev = None
-        self._anchor = nn.Parameter(torch.zeros(1), requires_grad=False)
+        super().__init__(cfg)
         if device is not None:
             self.to(device)
 
     def param_shapes(self):
         return W.vocos_param_shapes(self.cfg)
 
-    def init_synthetic(self, seed: int = 0):
-        self.load_state_dict(W.synthetic_state_dict(self.param_shapes(), seed=seed))
-        return self
-
-    def state_dict(self, *a, **k):
-        return dict(self._sd)
-
     def load_state_dict(self, sd, strict=True, assign=False):
-        shapes = self.param_shapes()
-        sd = {k: v for k, v in sd.items() if not k.startswith("feature_extractor.")}
-        missing = [k for k in shapes if k not in sd]
-        unexpected = [k for k in sd if k not in shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"vocos state dict mismatch: missing {missing[:4]}, unexpected {unexpected[:4]}")
-        self._sd = {k: sd[k].detach().to("cpu", torch.float32) for k in shapes if k in sd}
-        self._drop_handle()
-        return nn.modules.module._IncompatibleKeys(missing, unexpected)
+        return self._set_state({k: v for k, v in sd.items() if not k.startswith("feature_extractor.")}, strict, "vocos")
 
-    def _drop_handle(self):
-        if self._h:
-            _lib.load().f5_vocos_destroy(self._h)
-        self._h = None
-        self._h_dev = None
-
-    def __del__(self):
-        try:
-            self._drop_handle()
-        except Exception:
-            pass
-
-    def _handle(self):
-        dev = self._anchor.device
-        if dev.type != "cuda":
-            raise RuntimeError("the HIP vocoder only runs on a GPU: call .to('cuda') first (there is no CPU path)")
-        if self._h is not None and self._h_dev == dev:
-            return self._h
-        self._drop_handle()
-        lib = _lib.load()
-        if not self._sd:
-            raise RuntimeError("no vocoder weights loaded")
+    def _create(self, lib, h):
         c = self.cfg
         cfg = _lib.f5_vocos_config()
         cfg.input_channels, cfg.dim, cfg.intermediate_dim = c["input_channels"], c["dim"], c["intermediate_dim"]
         cfg.num_layers, cfg.n_fft, cfg.hop_length = c["num_layers"], c["n_fft"], c["hop_length"]
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(lib.f5_vocos_create(C.byref(cfg), C.byref(h)), "f5_vocos_create")
-            st = _stream_ptr(dev)
-            win, basis = idft_basis(c["n_fft"])
-            for name, t in list(self._sd.items()) + [("aux.hann", win), ("aux.idft_basis", basis)]:
-                d = _dev_f32(t, dev)
-                _lib.check(lib.f5_vocos_load_weight(h, name.encode(), _ptr(d), _lib.shape_array(d.shape), d.dim(), st),
-                           f"f5_vocos_load_weight({name})")
-            _lib.check(lib.f5_vocos_finalize(h, st), "f5_vocos_finalize")
-        self._h, self._h_dev = h, dev
-        return h
+        return lib.f5_vocos_create(C.byref(cfg), C.byref(h))
+
+    def _aux_tables(self):
+        return zip(("aux.hann", "aux.idft_basis"), idft_basis(self.cfg["n_fft"]))
 
     @torch.no_grad()
     def decode(self, mel: torch.Tensor) -> torch.Tensor:
