@@ -348,6 +348,14 @@ int f5_mel_forward_ragged(f5_mel* m, const float* wav, int32_t B, const int64_t*
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */
 int f5k_gemm(int32_t prec, const float* A, const float* W, const float* bias, int32_t act, float* out, int32_t M,
              int32_t N, int32_t K, int32_t tile_m, int32_t tile_n, f5_stream stream);
+/* What launch_gemm decides for one problem, as pure host arithmetic (no HIP call, nothing launched): element size 2 or 4, the
+ * device row count present or not and the row count expected behind it (m_hint, 0: none), the operand form (0 plain, 1 W pre-split,
+ * 2 A and W pre-split), implicit conv or not, whether the epilogue admits the ping-pong tile, the forced cfg (-1 auto, -2 the
+ * register-staged kernel, else a tile id) and the values of F5_GEMM_CFG (-1: unset) / F5_GEMM_CFG_N (0: every N).
+ * plan[0] = number of launches (0: nothing to do, -1: the problem is refused), then per launch {kernel family (1 register-staged,
+ * 2 LDS-DMA ring, 3 ping-pong), tile id (family 1: BM * 1000 + BN), first row, row count}; unused entries are 0.  plan: int32[9]. */
+int f5k_gemm_plan(int32_t elem_size, int32_t M, int32_t N, int32_t K, int32_t has_m_limit, int32_t m_hint, int32_t operand_form,
+                  int32_t conv, int32_t pp_epilogue, int32_t force_cfg, int32_t env_cfg, int32_t env_cfg_n, int32_t* plan);
 /* q, k, v f32[Bp, H, N, 64] (q unscaled) -> out f32[Bp, N, H*64]; kv_lens HOST int32[Bp] or NULL */
 int f5k_attention(int32_t prec, const float* q, const float* k, const float* v, const int32_t* kv_lens_host,
                   float* out, int32_t Bp, int32_t H, int32_t N, f5_stream stream);

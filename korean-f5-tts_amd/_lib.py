@@ -105,6 +105,7 @@ SIGNATURES = {
     "f5_mel_ragged_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "f5_mel_forward_ragged": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), _i, _f, _p, C.c_int64, _i, _p]),
     "f5k_gemm": (_i, [_i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "f5k_gemm_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "f5k_attention": (_i, [_i, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),
     "f5k_convpos": (_i, [_i, _p, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),
     "f5k_layernorm_mod": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),

@@ -555,13 +555,13 @@ extern "C" int f5_bigvgan_forward(f5_bigvgan* v, const float* mel, int32_t B, in
         hipLaunchKernelGGL(im2col7_kernel, dim3(ew_blocks((long)T * v->kpre)), dim3(256), 0, s, mel + (size_t)b * sb, 0L, (long)sc, (long)st,
                            col, 1, c.num_mels, T, v->kpre);
         KCHK();
-        HIPCHK(launch_gemm<float>(s, col, v->kpre, v->pre.w, v->pre.ld, T, ch, v->kpre, EpiStore<float>{x, ch, v->pre.b, F5_ACT_NONE}, -1, nullptr, 0,
-                                  GemmConv{}, v->pre.split));
+        HIPCHK(launch_gemm<float>(s, col, v->kpre, v->pre.w, v->pre.ld, T, ch, v->kpre, EpiStore<float>{x, ch, v->pre.b, F5_ACT_NONE},
+                                  {v->pre.split ? GemmOperands::WSplit : GemmOperands::Plain}));
         for (int i = 0; i < c.num_upsamples; ++i) {
             const BUp& u = v->ups[i];
             // ConvTranspose1d: Z[L, k Co] = x[L, Ci] W'^T, then gather
-            HIPCHK(launch_gemm<float>(s, x, u.ci, u.w, u.ld, (int)L, u.k * u.co, u.ci, EpiStore<float>{Z, u.k * u.co, nullptr, F5_ACT_NONE}, -1, nullptr, 0,
-                                      GemmConv{}, u.split));
+            HIPCHK(launch_gemm<float>(s, x, u.ci, u.w, u.ld, (int)L, u.k * u.co, u.ci, EpiStore<float>{Z, u.k * u.co, nullptr, F5_ACT_NONE},
+                                      {u.split ? GemmOperands::WSplit : GemmOperands::Plain}));
             hipLaunchKernelGGL(bv_upsample_gather_kernel, dim3(ew_blocks(L * u.u * (u.co / 4))), dim3(256), 0, s, Z, u.b, x, L, u.co, u.k, u.u,
                                (u.k - u.u) / 2);
             KCHK();
@@ -578,11 +578,11 @@ extern "C" int f5_bigvgan_forward(f5_bigvgan* v, const float* mel, int32_t B, in
             auto conv = [&](const BConv& cw, int k, int d, const auto& epi) -> hipError_t {
                 if (narrow_ok && cw.wn && conv_narrow_ok(ch, k, d))
                     return launch_conv_narrow(s, acti, cw.wn, cw.b, epi_res(epi), epi_out(epi), L, ch, k, d);
-                // (split 2: the activation kernel wrote these rows pre-split -- planar1 / planar2 below)
-                if (implicit) return launch_gemm<float>(s, acti, ch, cw.w, cw.ld, (int)L, ch, cw.ld, epi, -1, nullptr, 0,
-                                                        GemmConv{ch / 32, d, (k - 1) / 2}, cw.split ? 2 : 0);
+                // (AWSplit: the activation kernel wrote these rows pre-split -- planar1 / planar2 below)
+                if (implicit) return launch_gemm<float>(s, acti, ch, cw.w, cw.ld, (int)L, ch, cw.ld, epi,
+                                                        {cw.split ? GemmOperands::AWSplit : GemmOperands::Plain, -1, nullptr, 0, GemmConv{ch / 32, d, (k - 1) / 2}});
                 hipLaunchKernelGGL(bv_im2col_kernel, dim3(ew_blocks(L * (cw.ld / 4))), dim3(256), 0, s, acti, col, L, ch, k, d, cw.ld);
-                return launch_gemm<float>(s, col, cw.ld, cw.w, cw.ld, (int)L, ch, cw.ld, epi, -1, nullptr, 0, GemmConv{}, cw.split);
+                return launch_gemm<float>(s, col, cw.ld, cw.w, cw.ld, (int)L, ch, cw.ld, epi, {cw.split ? GemmOperands::WSplit : GemmOperands::Plain});
             };
             for (int j = 0; j < c.num_kernels; ++j) {
                 const BRes& rb = v->res[(size_t)i * c.num_kernels + j];

@@ -19,7 +19,7 @@
 
 namespace f5 {
 
-// SPLIT (T = float, CPG % 32 == 0; F5_PREC_F16X3): products on the f16 pipe with split operands as in gemm2.h MODE 3 -- the weights
+// SPLIT (T = float, CPG % 32 == 0; F5_PREC_F16X3): products on the f16 pipe with split operands as in gemm2.h GemmOperands::WSplit -- the weights
 // arrive pre-split (split_planar_kernel: per 32-element K block, which lies inside one tap, chunk g = hi of k = 4g..4g+3,
 // 16+4g..16+4g+3, chunk 4+g = lo), the input window is split once while it is staged (per row: CPG f16 hi, then CPG f16 lo).
 template <typename T, int CPG, int NS, bool SPLIT = false>

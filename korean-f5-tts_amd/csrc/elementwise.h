@@ -155,7 +155,7 @@ static __global__ void unett_assemble_kernel(const float* __restrict__ h, const 
     }
 }
 // out[r, :] = [x[r, :] | skip[r, :]] converted to T   (unett.py:266: cat((x, skip), dim=-1))
-// planar (T = float, F5_PREC_F16X3): the row is written pre-split (store4_planar) -- the A operand of a MODE 5 / ping-pong GEMM
+// planar (T = float, F5_PREC_F16X3): the row is written pre-split (store4_planar) -- the A operand of an AWSplit GEMM (GemmOperands, ring or ping-pong)
 template <typename T>
 __global__ void cat2_kernel(const float* __restrict__ x, const float* __restrict__ skip, T* __restrict__ out, long rows, int D, int planar = 0) {
     const int d4 = D / 4;
@@ -719,7 +719,7 @@ static __global__ void istft_ola_ragged_kernel(const float* __restrict__ frames,
         wav[b * wav_stride + i] = i < L ? istft_ola_sample(fr, win, T, nfft, hop, (int)i) * g : 0.f;
 }
 
-// In place: W f32 [rows, ld] (ld % 32 == 0) -> per 32-element block the 128 bytes the split-operand GEMM reads (gemm2.h MODE 3):
+// In place: W f32 [rows, ld] (ld % 32 == 0) -> per 32-element block the 128 bytes the split-operand GEMM reads (gemm2.h GemmOperands::WSplit):
 // 16-byte chunk g = f16 hi of k = 4g..4g+3, 16+4g..16+4g+3; chunk 4 + g = f16 lo (w - hi) of the same k.  One thread per block.
 static __global__ void split_planar_kernel(float* __restrict__ w, long blocks) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < blocks; i += (long)gridDim.x * blockDim.x) {

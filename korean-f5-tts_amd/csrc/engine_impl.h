@@ -41,10 +41,10 @@ static inline bool conv_split(const f5_engine* e) { return e->split16 && convpos
 // every backbone GEMM goes through here (the time / text paths call launch_gemm<float> directly: always plain f32)
 template <typename T, typename Epi>
 static hipError_t egemm(const f5_engine* e, hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi,
-                        int force_cfg = -1, const int* m_limit = nullptr, int m_hint = 0, bool a_planar = false) {
-    // a_planar: the A operand was written pre-split by its producer (store4_planar: LayerNorm, attention, the GELU epilogue)
-    const int split = (std::is_same_v<T, float> && e->split16) ? (a_planar ? 2 : 1) : 0;
-    return launch_gemm<T>(s, A, lda, W, ldw, M, N, K, epi, force_cfg, m_limit, m_hint, GemmConv{}, split);
+                        const int* m_limit = nullptr, int m_hint = 0, bool a_split = false) {
+    // a_split: the A operand was written pre-split by its producer (store4_planar: LayerNorm, attention, the GELU epilogue)
+    const GemmOperands ops = !(std::is_same_v<T, float> && e->split16) ? GemmOperands::Plain : a_split ? GemmOperands::AWSplit : GemmOperands::WSplit;
+    return launch_gemm<T>(s, A, lda, W, ldw, M, N, K, epi, {ops, -1, m_limit, m_hint});
 }
 
 // W [N, K] f32 -> T [N, round_up(K, 8)]
@@ -460,8 +460,8 @@ struct FwdCtx {
     int pl() const { return e->split16 ? 1 : 0; }              // F5_PREC_F16X3: xn / ao / ffh are written pre-split (the A operands of the block GEMMs)
     double gflops(double n, double k) const { return 2.0 * (pk ? pk.rows_host : (double)rows) * n * k; }
     // one backbone GEMM over all rows, as a profiled launch
-    template <typename T, typename Epi> int gemm(const T* A, int lda, const LinW<T>& L, int n, int k, const Epi& epi, bool a_planar = false) const {
-        HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] { return egemm<T>(e, s, A, lda, L.w, L.ldw, rows, n, k, epi, -1, ml(), mh(), a_planar); }));
+    template <typename T, typename Epi> int gemm(const T* A, int lda, const LinW<T>& L, int n, int k, const Epi& epi, bool a_split = false) const {
+        HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] { return egemm<T>(e, s, A, lda, L.w, L.ldw, rows, n, k, epi, ml(), mh(), a_split); }));
         return F5_OK;
     }
     // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed)
@@ -507,8 +507,8 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
     if constexpr (std::is_same_v<U, float>) ablate_round(64, acat, acat, (long)rows * e->kin_pad);
     HIPCHK(pr.timed(PC_GEMM, s, f.gflops(D, e->kin), [&] {
         const EpiStore<float> epi{w.h, D, ip->b, F5_ACT_NONE};
-        if constexpr (std::is_same_v<U, T>) return egemm<T>(e, s, acat, e->kin_pad, ip->w, ip->ldw, rows, D, e->kin_pad, epi, -1, f.ml(), f.mh());
-        else return launch_gemm<float>(s, acat, e->kin_pad, ip->w, ip->ldw, rows, D, e->kin_pad, epi, -1, f.ml(), f.mh(), GemmConv{}, 1);
+        if constexpr (std::is_same_v<U, T>) return egemm<T>(e, s, acat, e->kin_pad, ip->w, ip->ldw, rows, D, e->kin_pad, epi, f.ml(), f.mh());
+        else return launch_gemm<float>(s, acat, e->kin_pad, ip->w, ip->ldw, rows, D, e->kin_pad, epi, {GemmOperands::WSplit, -1, f.ml(), f.mh()});
     }));
     const double conv_fl = f.gflops(D, (D / 16) * 31);
     HIPCHK(pr.timed(PC_CONV, s, conv_fl, [&] {
@@ -594,7 +594,7 @@ template <typename T, typename U> static int project_out(const FwdCtx& f, const 
     } else {
         HIPCHK(e->prof.timed(PC_GEMM, f.s, f.gflops(mel, D), [&] {
             return launch_gemm<float>(f.s, xn, D, P.proj_out_f.w, P.proj_out_f.ldw, f.rows, mel, D,
-                                      EpiStore<float>{pred, mel, P.proj_out_f.b, F5_ACT_NONE}, -1, f.ml(), f.mh(), GemmConv{}, 2);
+                                      EpiStore<float>{pred, mel, P.proj_out_f.b, F5_ACT_NONE}, {GemmOperands::AWSplit, -1, f.ml(), f.mh()});
         }));
         return F5_OK;
     }
@@ -655,7 +655,7 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
             float* cat_f = reinterpret_cast<float*>(w.cat2);
             HIPCHK(cat_skip(cat_f));
             HIPCHK(pr.timed(PC_GEMM, s, f.gflops(D, 2 * D), [&] {
-                return launch_gemm<float>(s, cat_f, 2 * D, P.long_skip_f.w, P.long_skip_f.ldw, rows, D, 2 * D, epi, -1, ml, mh, GemmConv{}, 1);
+                return launch_gemm<float>(s, cat_f, 2 * D, P.long_skip_f.w, P.long_skip_f.ldw, rows, D, 2 * D, epi, {GemmOperands::WSplit, -1, ml, mh});
             }));
         } else {
             HIPCHK(cat_skip(w.cat2));

@@ -104,7 +104,7 @@ template <typename T> struct Packed {
     LinW<T> proj_out;
     LinW<T> long_skip;             // F5_OPT_LONG_SKIP: Linear(2 D -> D, no bias) over [x | residual] (dit.py:205,323-324)
     LinW<float> long_skip_f;       // ... and its split-planar f32 copy for F5_PREC_F16P (the operand is the raw stream)
-    // F5_PREC_F16P: split-planar f32 copies of the input / output layers' weights (gemm2.h MODE 3 / 5, convpos.h SPLIT)
+    // F5_PREC_F16P: split-planar f32 copies of the input / output layers' weights (gemm2.h GemmOperands::WSplit / AWSplit, convpos.h SPLIT)
     LinW<float> in_proj_f, proj_out_f;
     float* conv_w_f[2] = {nullptr, nullptr};
     int conv_kp_f = 0;
@@ -233,7 +233,7 @@ struct f5_engine {
     f5_config cfg{};
     int inner = 0, kin = 0, kin_pad = 0, modN = 0;
     bool io_split = false;     // F5_PREC_F16P: the f16 engine with its input / output layers as split-f16 products on f32 operands
-    bool split16 = false;      // F5_PREC_F16X3: the f32 engine with the backbone GEMMs on the f16 pipe (gemm2.h MODE 3)
+    bool split16 = false;      // F5_PREC_F16X3: the f32 engine with the backbone GEMMs on the f16 pipe (gemm2.h GemmOperands::WSplit)
     Switches sw;
     WeightStore ws;
     std::vector<void*> owned;  // packed buffers

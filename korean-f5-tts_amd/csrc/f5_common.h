@@ -99,7 +99,7 @@ template <> __device__ __forceinline__ u32x2 pack4<f16_t>(float a, float b, floa
     return u32x2{cvt2_f16(a, b), cvt2_f16(c, d)};
 }
 
-// ---- F5_PREC_F16X3 helpers: x = hi + lo with hi = f16(x), lo = f16(x - hi) (gemm2.h MODE 3, attn.h) ----
+// ---- F5_PREC_F16X3 helpers: x = hi + lo with hi = f16(x), lo = f16(x - hi) (gemm2.h GemmOperands::WSplit, attn.h) ----
 __device__ __forceinline__ void split4_f16(const u32x4& c, u32x2& hi, u32x2& lo) {
     typedef __attribute__((ext_vector_type(2))) float v2f;
     typedef __attribute__((ext_vector_type(2))) _Float16 v2h;

@@ -530,20 +530,18 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const T* __restrict__ A, i
     }
 }
 
-// ---------------------------------------------------------------------------------------------- launcher
+// The operand form of a GEMM (gemm2.h, gemm3.h; F5_PREC_F16X3 runs the two split forms on f32 rows): Plain; WSplit = W pre-split into
+// f16 hi / lo planes (split_planar_kernel), A f32 and split in registers after the fragment read; AWSplit = A pre-split as well
+// (store4_planar by its producer): its two fragment reads are hi and lo.
+enum class GemmOperands { Plain, WSplit, AWSplit };
+// Diagnostic variants of the same kernels (tools only, outputs are garbage): the floors of the pipeline -- LDS-DMA only (no fragment
+// reads / MFMA), compute only (no DMA in the K loop) --, no epilogue, and 2 of 3 / 1 of 3 product terms of the split forms.
+enum class GemmDiag { None, DmaOnly, ComputeOnly, NoEpilogue, TwoOfThree, OneOfThree };
 
-struct GemmTile { int bm, bn; };
-
-inline GemmTile pick_tile(int M, int N) {
-    auto blocks = [&](int bm, int bn) { return (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    if (M > 64 && N > 64 && blocks(128, 128) >= 200) return {128, 128};
-    if (M > 64 && blocks(128, 64) >= 160) return {128, 64};
-    return {64, 64};
-}
-
+// One launcher per kernel (here, gemm2.h, gemm3.h), for the epilogue type it is given: launch_gemm makes a run-time activation static.
+// A: [M, K] (lda elements), W: [N, K] (ldw elements); K, lda, ldw multiples of 16/sizeof(T); N multiple of 4.
 template <typename T, int BM, int BN, typename Epi>
-inline hipError_t launch_gemm_tile_raw(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
-                                       const Epi& epi) {
+inline hipError_t launch_gemm1(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi) {
     constexpr int smem = 2 * (BM + BN) * GEMM_ROW_STRIDE;
     static bool attr_set = false;
     if (!attr_set) {
@@ -555,26 +553,6 @@ inline hipError_t launch_gemm_tile_raw(hipStream_t s, const T* A, int lda, const
     dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM);
     hipLaunchKernelGGL((gemm_tn_kernel<T, BM, BN, Epi>), grid, dim3(256), smem, s, A, lda, W, ldw, M, N, K, epi);
     return hipGetLastError();
-}
-
-template <typename T, int BM, int BN, typename Epi>
-inline hipError_t launch_gemm_tile(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
-                                   const Epi& epi) {
-    return with_static_act(epi, [&](const auto& e) {
-        return launch_gemm_tile_raw<T, BM, BN, std::decay_t<decltype(e)>>(s, A, lda, W, ldw, M, N, K, e);
-    });
-}
-
-// A: [M, K] (lda elements), W: [N, K] (ldw elements); K, lda, ldw multiples of 16/sizeof(T); N multiple of 4.
-template <typename T, typename Epi>
-inline hipError_t launch_gemm_v1(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
-                                 const Epi& epi, int force_bm = 0, int force_bn = 0) {
-    if (M <= 0 || N <= 0) return hipSuccess;
-    GemmTile t = pick_tile(M, N);
-    if (force_bm) t = {force_bm, force_bn};
-    if (t.bm == 128 && t.bn == 128) return launch_gemm_tile<T, 128, 128, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-    if (t.bm == 128 && t.bn == 64) return launch_gemm_tile<T, 128, 64, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-    return launch_gemm_tile<T, 64, 64, Epi>(s, A, lda, W, ldw, M, N, K, epi);
 }
 
 }  // namespace f5

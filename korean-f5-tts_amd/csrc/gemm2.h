@@ -23,8 +23,7 @@ __device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
                                      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 
-// MODE (diagnostic builds only): 0 = normal, 1 = LDS-DMA only (no fragment reads / MFMA), 2 = compute only (no DMA
-// in the K loop): the two floors of the pipeline.
+// OPS: the operand form, DIAG: a diagnostic variant (tools only) -- GemmOperands / GemmDiag, gemm.h.
 // Fragment reads issued as inline asm so that hipcc does not wait lgkmcnt(0) before the first MFMA (it does for every
 // compiler-visible ds_read_b128 on this toolchain): the waits below are placed by hand with counted lgkmcnt(N); the
 // fragments a wait retires are threaded through it as "+v" operands, so no MFMA can be scheduled above its wait.
@@ -69,7 +68,7 @@ __device__ __forceinline__ void wait_row(int kk, int i, u32x4 (&af)[2][MI], u32x
 #undef F5_WR
 }
 
-// ---- MODE 3: f32 operands, products on the f16 matrix pipe ("f16x3", F5_PREC_F16X3) -------------------------------------------
+// ---- GemmOperands::WSplit: f32 operands, products on the f16 matrix pipe ("f16x3", F5_PREC_F16X3) -------------------------------------------
 // a = a_hi + a_lo with a_hi = f16(a), a_lo = f16(a - a_hi): 22 significant bits (v_mfma_f32_16x16x32_f16 keeps f16 subnormal
 // inputs -- tools/f16_denorm.py -- so a_lo is good down to 2^-25 absolute);  a w ~= a_hi w_hi + a_lo w_hi + a_hi w_lo, every
 // product exact in the f32 accumulator, the dropped a_lo w_lo term ~2^-22 relative.  Three 16-cycle f16 MFMAs replace eight
@@ -105,7 +104,7 @@ __device__ __forceinline__ void tie(u32x4& a) { asm volatile("" : "+v"(a)); }
 // launch_gemm's remainder launch; the caller passes A already offset by m_base rows).
 struct GemmConv { int tpt = 0, dil = 0, half = 0, m_base = 0; };
 
-template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, int MODE = 0>
+template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, GemmOperands OPS = GemmOperands::Plain, GemmDiag DIAG = GemmDiag::None>
 __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restrict__ A, int lda, const T* __restrict__ W,
                                                   int ldw, int M, int N, int K, const Epi& epi, int xa, int xb,
                                                   const int* __restrict__ m_limit, const GemmConv cv = GemmConv{}) {
@@ -280,7 +279,7 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
     // (c) issuing the LDS-DMA pieces between MFMA rows instead of at the head of the block: out 9.1 -> 9.5 us;
     // (d) two K-tiles per barrier (ring of 6) for the small 128x64 / 64x64 wave tiles: out 10.0 -> 10.3, ff2 17.4 -> 17.1 us.
     // Floors of this loop for the 128x128 / 8-wave tile, per 64-deep K-step on a full chip (tools/gemm_scale.py with the
-    // diagnostic MODEs, K = 1024 -> 8192): bare MFMA issue 0.216 us (tools/mfma_rate_probe.py: 2.3-2.4 PFLOP/s at
+    // GemmDiag variants, K = 1024 -> 8192): bare MFMA issue 0.216 us (tools/mfma_rate_probe.py: 2.3-2.4 PFLOP/s at
     // 2.1-2.37 GHz); + one barrier per step 0.28; + the 12 fragment reads per wave (96 KB of LDS reads per step), however
     // they are scheduled (up front, register-pipelined a step ahead, or interleaved two per MFMA) 0.385-0.43; LDS-DMA
     // only 0.32; everything 0.51.  The fragment reads cost ~0.1 us of MFMA issue even when nothing waits on them, so
@@ -303,9 +302,9 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
 #pragma unroll
                 for (int i = 1; i < MI; ++i) lds_read_b128_asm(af[kk][i], sbu + a_row_off + i * 16 * GEMM_ROW_BYTES + co);
             }
-            // MODE 5: the A operand is ALREADY split in memory (store4_planar by its producer): its two fragment reads are hi and lo.
-            // (6, 7: tools/probe/gemm_split_probe.hip -- 2 of 3 / 1 of 3 MFMAs)
-            if constexpr (MODE == 3 || MODE >= 5) {
+            // AWSplit: the A operand is ALREADY split in memory (store4_planar by its producer): its two fragment reads are hi and lo.
+            // (TwoOfThree, OneOfThree: tools/probe/gemm_split_probe.hip -- 2 of 3 / 1 of 3 MFMAs)
+            if constexpr (OPS != GemmOperands::Plain) {
                 // row i needs both halves of a[i] and (i == 0) every w fragment: the last of them is read (MI + NJ) + NJ + i
 #pragma unroll
                 for (int i = 0; i < MI; ++i) {
@@ -317,12 +316,12 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
                         for (int j = 0; j < NJ; ++j) tie(wf[0][j]);
                     }
                     f16x8 ah, al;
-                    if constexpr (MODE == 5) { ah = __builtin_bit_cast(f16x8, af[0][i]); al = __builtin_bit_cast(f16x8, af[1][i]); }
+                    if constexpr (OPS == GemmOperands::AWSplit) { ah = __builtin_bit_cast(f16x8, af[0][i]); al = __builtin_bit_cast(f16x8, af[1][i]); }
                     else split8_f16(af[0][i], af[1][i], ah, al);
                     // term-major: consecutive MFMAs write different accumulators (a dependent MFMA waits out the whole
                     // pipeline of its predecessor)
 #pragma unroll
-                    for (int term = (MODE == 6 ? 1 : MODE == 7 ? 2 : 0); term < 3; ++term) {
+                    for (int term = (DIAG == GemmDiag::TwoOfThree ? 1 : DIAG == GemmDiag::OneOfThree ? 2 : 0); term < 3; ++term) {
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) {
                             const f16x8 w = __builtin_bit_cast(f16x8, wf[term == 0 ? 1 : 0][j]);   // lo hi hi
@@ -352,12 +351,12 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
         int stage = 0;
         {
             for (int kt = 0; kt < nkt; ++kt) {
-                if (MODE != 2) wait_tiles(nkt - 1 - kt);  // this wave's pieces of tile kt have landed (later tiles may be in flight) ...
+                if (DIAG != GemmDiag::ComputeOnly) wait_tiles(nkt - 1 - kt);  // this wave's pieces of tile kt have landed (later tiles may be in flight) ...
                 __builtin_amdgcn_s_barrier();     // ... and so have everyone else's; stage (kt-1)%NS is free again
                 int pf = stage + NS - 1;
                 if (pf >= NS) pf -= NS;
-                if (MODE != 2) issue(kt + NS - 1, pf);
-                if (MODE != 1) tile(stage);
+                if (DIAG != GemmDiag::ComputeOnly) issue(kt + NS - 1, pf);
+                if (DIAG != GemmDiag::DmaOnly) tile(stage);
                 stage = stage + 1 == NS ? 0 : stage + 1;
             }
         }
@@ -377,7 +376,7 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
         kloop(std::integral_constant<int, 0>{});
     }
 
-    if (MODE == 4 && K > 0) {  // diagnostic: no epilogue (K <= 0 never happens; keeps the accumulators alive)
+    if (DIAG == GemmDiag::NoEpilogue && K > 0) {  // diagnostic: no epilogue (K <= 0 never happens; keeps the accumulators alive)
         float sink = 0.f;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -412,13 +411,13 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
     }
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, int MODE = 0>
+template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, GemmOperands OPS = GemmOperands::Plain, GemmDiag DIAG = GemmDiag::None>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_tn_glds_kernel(const T* __restrict__ A, int lda,
                                                                    const T* __restrict__ W, int ldw, int M, int N, int K,
                                                                    Epi epi, int xa, int xb, const int* __restrict__ m_limit,
                                                                    const GemmConv cv) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gemm_tn_glds_body<T, BM, BN, WM, WN, NS, Epi, MODE>(smem, A, lda, W, ldw, M, N, K, epi, xa, xb, m_limit, cv);
+    gemm_tn_glds_body<T, BM, BN, WM, WN, NS, Epi, OPS, DIAG>(smem, A, lda, W, ldw, M, N, K, epi, xa, xb, m_limit, cv);
 }
 
 // chooses (xa, xb): tiles_m % xa == 0, tiles_n % xb == 0 and the number of rectangles a multiple of 8; prefers the most
@@ -444,13 +443,13 @@ inline void pick_xcd_rect(int tiles_m, int tiles_n, int* xa, int* xb) {
     if (*xa * *xb <= 1) *xa = *xb = 0;
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, int MODE = 0>
-inline hipError_t launch_gemm2_raw(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
-                                   const Epi& epi, const int* m_limit = nullptr, const GemmConv& cv = GemmConv{}) {
+template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, GemmOperands OPS = GemmOperands::Plain, GemmDiag DIAG = GemmDiag::None>
+inline hipError_t launch_gemm2(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
+                               const Epi& epi, const int* m_limit = nullptr, const GemmConv& cv = GemmConv{}) {
     constexpr int smem = NS * (BM + BN) * GEMM_ROW_BYTES;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_glds_kernel<T, BM, BN, WM, WN, NS, Epi, MODE>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_glds_kernel<T, BM, BN, WM, WN, NS, Epi, OPS, DIAG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         if (e != hipSuccess) return e;
         attr_set = true;
@@ -460,17 +459,9 @@ inline hipError_t launch_gemm2_raw(hipStream_t s, const T* A, int lda, const T* 
     // rectangle of tiles per XCD share: valid only when the grid splits into whole rectangles, 8 at a time
     int xa = 0, xb = 0;
     if (!m_limit) pick_xcd_rect((int)grid.y, (int)grid.x, &xa, &xb);
-    hipLaunchKernelGGL((gemm_tn_glds_kernel<T, BM, BN, WM, WN, NS, Epi, MODE>), grid, dim3(WM * WN * 64), smem, s, A, lda, W,
+    hipLaunchKernelGGL((gemm_tn_glds_kernel<T, BM, BN, WM, WN, NS, Epi, OPS, DIAG>), grid, dim3(WM * WN * 64), smem, s, A, lda, W,
                        ldw, M, N, K, epi, xa, xb, m_limit, cv);
     return hipGetLastError();
-}
-
-template <typename T, int BM, int BN, int WM, int WN, int NS, typename Epi, int MODE = 0>
-inline hipError_t launch_gemm2_cfg(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
-                                   const Epi& epi, const int* m_limit = nullptr, const GemmConv& cv = GemmConv{}) {
-    return with_static_act(epi, [&](const auto& e) {
-        return launch_gemm2_raw<T, BM, BN, WM, WN, NS, std::decay_t<decltype(e)>, MODE>(s, A, lda, W, ldw, M, N, K, e, m_limit, cv);
-    });
 }
 
 }  // namespace f5

@@ -38,11 +38,11 @@ template <int OFF> __device__ __forceinline__ void lds_read_b128_off(u32x4& dst,
 }
 __device__ __forceinline__ void reg_fence(u32x4& a) { asm volatile("" : "+v"(a)); }
 
-// DIAG (tools only; 0 in the product): 4 = no epilogue (the K loop + launch alone: what the epilogue of a shape costs by omission)
-// DIAG bit 8 (product, T = float): both operands PRE-SPLIT into f16 hi / lo planes (gemm2.h MODE 5, F5_PREC_F16X3: a 128-byte row is 32
-// elements, chunks 0-3 hi, 4-7 lo, so the two fragment reads of a row ARE hi and lo); a phase is then 24 f16 MFMAs -- per accumulator
-// and K-tile lo x hi, hi x lo, hi x hi, the order of gemm2's MODE 5 (bit-identical results).
-template <typename T, typename Epi, int DIAG = 0>
+// OPS (GemmOperands, gemm.h): Plain, or AWSplit with T = float -- both operands PRE-SPLIT into f16 hi / lo planes (F5_PREC_F16X3: a
+// 128-byte row is 32 elements, chunks 0-3 hi, 4-7 lo, so the two fragment reads of a row ARE hi and lo); a phase is then 24 f16 MFMAs
+// -- per accumulator and K-tile lo x hi, hi x lo, hi x hi, the order of gemm2.h's AWSplit form (bit-identical results).  There is no
+// WSplit form of this kernel.  DIAG (GemmDiag, tools only): NoEpilogue = the K loop + launch alone.
+template <typename T, typename Epi, GemmOperands OPS = GemmOperands::Plain, GemmDiag DIAG = GemmDiag::None>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const T* __restrict__ A, int lda, const T* __restrict__ W, int ldw, int M,
                                                       int N, int K, Epi epi, int xa, int xb, const int* __restrict__ m_limit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -135,10 +135,10 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const T* __restrict__ A, i
         auto mma_quadrant = [&](auto i0c, u32x4 (&bf)[2][2], auto j0c) {   // (compile-time tile origin: acc stays in registers)
             constexpr int i0 = decltype(i0c)::value, j0 = decltype(j0c)::value;
             __builtin_amdgcn_s_setprio(1);
-            if constexpr ((DIAG & 8) != 0) {
+            if constexpr (OPS == GemmOperands::AWSplit) {
                 static_assert(std::is_same_v<T, float>, "pre-split operands are f32 rows of f16 hi / lo planes");
 #pragma unroll
-                for (int term = 0; term < 3; ++term)      // term-major, as gemm2.h MODE 5: (w lo, a hi), (w hi, a lo), (w hi, a hi)
+                for (int term = 0; term < 3; ++term)      // term-major, as gemm2.h AWSplit: (w lo, a hi), (w hi, a lo), (w hi, a hi)
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const T* __restrict__ A, i
         kloop(std::false_type{});
     }
     if (wr == 0) __builtin_amdgcn_s_barrier();          // balances the follower's extra barrier
-    if constexpr ((DIAG & 7) == 4) {
+    if constexpr (DIAG == GemmDiag::NoEpilogue) {
         float sink = 0.f;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
@@ -323,13 +323,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const T* __restrict__ A, i
 template <typename Epi> inline bool gemm3_epilogue_ok(const Epi&) { return !Epi::kTransposes; }
 template <typename TO> inline bool gemm3_epilogue_ok(const EpiQKV<TO>& e) { return (2 * e.H * 64) % 256 == 0; }
 
-template <typename T, typename Epi, int DIAG = 0>
-inline hipError_t launch_gemm3_raw(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi,
-                                   const int* m_limit) {
+template <typename T, typename Epi, GemmOperands OPS = GemmOperands::Plain, GemmDiag DIAG = GemmDiag::None>
+inline hipError_t launch_gemm3(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi,
+                               const int* m_limit = nullptr) {
     constexpr int smem = 2 * 512 * GEMM_ROW_BYTES;   // 128 KiB
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<T, Epi, DIAG>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<T, Epi, OPS, DIAG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         if (e != hipSuccess) return e;
         attr_set = true;
@@ -338,16 +338,8 @@ inline hipError_t launch_gemm3_raw(hipStream_t s, const T* A, int lda, const T* 
     if (m_limit) grid.y = (grid.y + 7) / 8 * 8;   // (the device-side tile order deals row tiles in groups of 8)
     int xa = 0, xb = 0;
     if (!m_limit) pick_xcd_rect((int)grid.y, (int)grid.x, &xa, &xb);
-    hipLaunchKernelGGL((gemm_pp_kernel<T, Epi, DIAG>), grid, dim3(512), smem, s, A, lda, W, ldw, M, N, K, epi, xa, xb, m_limit);
+    hipLaunchKernelGGL((gemm_pp_kernel<T, Epi, OPS, DIAG>), grid, dim3(512), smem, s, A, lda, W, ldw, M, N, K, epi, xa, xb, m_limit);
     return hipGetLastError();
-}
-
-template <typename T, typename Epi, int DIAG = 0>
-inline hipError_t launch_gemm3(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi,
-                               const int* m_limit = nullptr) {
-    return with_static_act(epi, [&](const auto& e) {
-        return launch_gemm3_raw<T, std::decay_t<decltype(e)>, DIAG>(s, A, lda, W, ldw, M, N, K, e, m_limit);
-    });
 }
 
 }  // namespace f5

@@ -1,47 +1,20 @@
 // Kernel-level C entry points (f5k_*): each runs ONE kernel of the engine on fp32 inputs so that tests/ can compare it
 // with a torch fp32 restatement, and the micro-benchmarks can time it.  Scratch is allocated per call; every function
 // synchronises the stream before returning.
-#include <vector>
+#include "kapi_common.h"
 
-#include "attn2.h"
-#include "convpos.h"
-#include "elementwise.h"
-#include "gemm_dispatch.h"
-#include "internal.h"
-
-using namespace f5;
-#define fail f5_fail
-// precision dispatch of a function template call FN<T>(args...)
-#define F5K_BY_PREC(prec, FN, ...) \
-    ((prec) == F5_PREC_BF16 ? FN<bf16_t>(__VA_ARGS__) : (prec) == F5_PREC_F16 ? FN<f16_t>(__VA_ARGS__) : FN<float>(__VA_ARGS__))
-// F5_PREC_F16X3 runs the f32 instantiation with the W operand split (f5k_gemm / f5k_gemm_time only)
-static bool g_split16 = false;
-template <typename T> static hipError_t maybe_split(hipStream_t s, T* w, size_t elems) {
-    if constexpr (std::is_same_v<T, float>) {
-        if (g_split16) hipLaunchKernelGGL(split_planar_kernel, dim3(ew_blocks((long)(elems / 32))), dim3(256), 0, s, w, (long)(elems / 32));
-    }
-    return hipGetLastError();
-}
+// tile_m / tile_n of f5k_gemm / f5k_gemm_time as a forced cfg: tile_m > 0 a v1 tile (BM, BN), tile_m < 0 the tile id -tile_m, 0 auto
+static int forced_cfg(int tm, int tn) { return tm > 0 ? tm * 1000 + tn : tm < 0 ? -tm : -1; }
+static bool v1_tile(int cfg) { return gemm_tile(cfg) && gemm_tile(cfg)->family == GEMM_V1; }   // (K is then padded to 16 bytes only)
 
 template <typename T>
-static int gemm_impl(const float* A, const float* W, const float* bias, int act, float* out, int M, int N, int K, int tm,
-                     int tn, hipStream_t s) {
-    const int Kp = tm > 0 ? round_up(K, 8) : round_up(K, 128 / (int)sizeof(T));  // tm > 0 forces the v1 kernel
-    Scratch<T> a, w;
-    HIPCHK(a.alloc((size_t)M * Kp));
-    HIPCHK(w.alloc((size_t)N * Kp));
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)M * Kp)), dim3(256), 0, s, A, K, M, K, a.p, Kp, M);
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)N * Kp)), dim3(256), 0, s, W, K, N, K, w.p, Kp, N);
-    KCHK();
-    const bool split = g_split16 && std::is_same_v<T, float>;
-    if (split && tm > 0) return fail(F5_EINVAL, "f5k_gemm: the split-operand mode has no v1 kernel");
-    HIPCHK(maybe_split<T>(s, w.p, (size_t)N * Kp));
-    // F5_PREC_F16X3 with tn == 5: the A operand pre-split as well (what store4_planar producers hand the block GEMMs: MODE 5)
-    const bool a_planar = split && tm <= 0 && tn == 5;
-    if (a_planar) HIPCHK(maybe_split<T>(s, a.p, (size_t)M * Kp));
-    if (tm > 0) HIPCHK(launch_gemm_v1<T>(s, a.p, Kp, w.p, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}, tm, tn));
-    else HIPCHK(launch_gemm<T>(s, a.p, Kp, w.p, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}, tm < 0 ? -tm : -1, nullptr, 0, GemmConv{},
-                               a_planar ? 2 : (split ? 1 : 0)));
+static int gemm_impl(const float* A, const float* W, const float* bias, int act, float* out, int M, int N, int K, int cfg, GemmOperands ops,
+                     hipStream_t s) {
+    const int Kp = round_up(K, v1_tile(cfg) ? 8 : GEMM_ROW_BYTES / (int)sizeof(T));
+    if (cfg == G3_256x256_PP && !gemm_has_pingpong(sizeof(T), ops)) return fail(F5_EINVAL, "f5k_gemm: no ping-pong kernel (cfg 20) for these operands");
+    GemmStage<T> g;
+    CHK(g.stage(s, A, K, W, K, M, N, K, Kp, ops));
+    HIPCHK(launch_gemm<T>(s, g.a.p, Kp, g.w.p, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}, {ops, cfg}));
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
 }
@@ -49,21 +22,30 @@ static int gemm_impl(const float* A, const float* W, const float* bias, int act,
 extern "C" int f5k_gemm(int32_t prec, const float* A, const float* W, const float* bias, int32_t act, float* out, int32_t M,
                         int32_t N, int32_t K, int32_t tm, int32_t tn, f5_stream stream) {
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm: bad arguments (N %% 4 == 0)");
-    if (tm > 0 && !((tm == 128 && (tn == 128 || tn == 64)) || (tm == 64 && tn == 64))) return fail(F5_EINVAL, "f5k_gemm: bad tile");
-    if (tm < 0 && tm != -2 && tm != -8 && tm != -9 && tm != -10 && tm != -13 && tm != -20) return fail(F5_EINVAL, "f5k_gemm: bad v2 / v3 config id");
-    hipStream_t s = (hipStream_t)stream;
-    g_split16 = prec == F5_PREC_F16X3;
-    const int rc = F5K_BY_PREC(prec, gemm_impl, A, W, bias, act, out, M, N, K, tm, tn, s);
-    g_split16 = false;
-    return rc;
+    const int cfg = forced_cfg(tm, tn);
+    if (tm != 0 && (!gemm_tile(cfg) || v1_tile(cfg) != (tm > 0))) return fail(F5_EINVAL, "f5k_gemm: bad tile (tile_m > 0) or tile id (tile_m < 0)");
+    // F5_PREC_F16X3: the f32 instantiation with W pre-split; with tile_n == 5 A as well (what store4_planar producers hand the block GEMMs)
+    const GemmOperands ops = prec != F5_PREC_F16X3 ? GemmOperands::Plain : (tm <= 0 && tn == 5) ? GemmOperands::AWSplit : GemmOperands::WSplit;
+    if (ops != GemmOperands::Plain && tm > 0) return fail(F5_EINVAL, "f5k_gemm: the split-operand mode has no v1 kernel");
+    return F5K_BY_PREC(prec, gemm_impl, A, W, bias, act, out, M, N, K, cfg, ops, (hipStream_t)stream);
+}
+
+// launch_gemm's decision for one problem, without launching (plan_gemm, gemm_dispatch.h): pure host arithmetic, no HIP call
+extern "C" int f5k_gemm_plan(int32_t elem_size, int32_t M, int32_t N, int32_t K, int32_t has_m_limit, int32_t m_hint, int32_t operand_form,
+                             int32_t conv, int32_t pp_epilogue, int32_t force_cfg, int32_t env_cfg, int32_t env_cfg_n, int32_t* plan) {
+    if (!plan || (elem_size != 2 && elem_size != 4) || operand_form < 0 || operand_form > 2) return fail(F5_EINVAL, "f5k_gemm_plan: bad arguments");
+    const GemmPlan g = plan_gemm({elem_size, M, N, K, has_m_limit != 0, m_hint, (GemmOperands)operand_form, conv != 0, pp_epilogue != 0, force_cfg, env_cfg, env_cfg_n});
+    plan[0] = g.ok ? g.n : -1;
+    static_assert(sizeof(g.l) == 8 * sizeof(int32_t), "two launches of four ints");
+    memcpy(plan + 1, g.l, sizeof(g.l));   // (launches past n are zero)
+    return F5_OK;
 }
 
 template <typename T>
-static int gemm_time_impl(int M, int N, int K, int tm, int tn, int iters, float* avg_us, hipStream_t s) {
-    const int Kp = tm > 0 ? round_up(K, 8) : round_up(K, 128 / (int)sizeof(T));
-    Scratch<T> a, w, o;
-    HIPCHK(a.alloc((size_t)M * Kp));
-    HIPCHK(w.alloc((size_t)N * Kp));
+static int gemm_time_impl(int M, int N, int K, int cfg, GemmOperands ops, int iters, float* avg_us, hipStream_t s) {
+    const int Kp = round_up(K, v1_tile(cfg) ? 8 : GEMM_ROW_BYTES / (int)sizeof(T));
+    if (cfg == G3_256x256_PP && !gemm_has_pingpong(sizeof(T), ops)) return fail(F5_EINVAL, "f5k_gemm_time: no ping-pong kernel (cfg 20) for these operands");
+    Scratch<T> o;
     HIPCHK(o.alloc((size_t)M * N));
     // random-ish operand bits (bench on non-zero data: MI355X_MICROARCH "DVFS give-back")
     Scratch<float> tmp;
@@ -76,17 +58,12 @@ static int gemm_time_impl(int M, int N, int K, int tm, int tn, int iters, float*
         h[i] = ((x >> 8) & 0xFFFF) / 32768.0f - 1.0f;
     }
     HIPCHK(hipMemcpy(tmp.p, h.data(), nmax * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)M * Kp)), dim3(256), 0, s, tmp.p, Kp, M, Kp, a.p, Kp, M);
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)N * Kp)), dim3(256), 0, s, tmp.p, Kp, N, Kp, w.p, Kp, N);
-    KCHK();
+    GemmStage<T> g;
+    CHK(g.stage(s, tmp.p, Kp, tmp.p, Kp, M, N, Kp, Kp, GemmOperands::Plain));   // (timing only: the random W bits are used as they are)
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
-    auto go = [&]() -> hipError_t {
-        if (tm > 0) return launch_gemm_v1<T>(s, a.p, Kp, w.p, Kp, M, N, Kp, EpiStore<T>{o.p, N, nullptr, 0}, tm, tn);
-        return launch_gemm<T>(s, a.p, Kp, w.p, Kp, M, N, Kp, EpiStore<T>{o.p, N, nullptr, 0}, tm < 0 ? -tm : -1, nullptr, 0, GemmConv{},
-                              g_split16 && std::is_same_v<T, float>);
-    };
+    auto go = [&]() { return launch_gemm<T>(s, g.a.p, Kp, g.w.p, Kp, M, N, Kp, EpiStore<T>{o.p, N, nullptr, 0}, {ops, cfg}); };
     for (int i = 0; i < 3; ++i) HIPCHK(go());
     HIPCHK(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i) HIPCHK(go());
@@ -103,11 +80,8 @@ static int gemm_time_impl(int M, int N, int K, int tm, int tn, int iters, float*
 extern "C" int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tm, int32_t tn, int32_t iters,
                              float* avg_us, f5_stream stream) {
     if (!avg_us || M <= 0 || N <= 0 || K <= 0 || iters <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm_time: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    g_split16 = prec == F5_PREC_F16X3;   // (timing only: the random W bits are used as they are)
-    const int rc = F5K_BY_PREC(prec, gemm_time_impl, M, N, K, tm, tn, iters, avg_us, s);
-    g_split16 = false;
-    return rc;
+    const GemmOperands ops = prec == F5_PREC_F16X3 && tm <= 0 ? GemmOperands::WSplit : GemmOperands::Plain;   // (a v1 tile: plain f32)
+    return F5K_BY_PREC(prec, gemm_time_impl, M, N, K, forced_cfg(tm, tn), ops, iters, avg_us, (hipStream_t)stream);
 }
 
 // packs fp32 [Bp,H,N,64] q/k/v into the engine layouts (q scaled, v transposed) -- test-side glue only
@@ -131,7 +105,7 @@ template <typename T> __global__ void to_f32_kernel(const T* in, float* out, lon
 
 template <typename T>
 static int attn_impl(const float* q, const float* k, const float* v, const int32_t* lens_host, float* out, int Bp, int H, int N,
-                     hipStream_t s) {
+                     bool split16, hipStream_t s) {
     const int Npad = round_up(N, 64);
     const long rows = (long)Bp * H * N;
     Scratch<T> qd, kd, vd, od;
@@ -148,7 +122,7 @@ static int attn_impl(const float* q, const float* k, const float* v, const int32
     hipLaunchKernelGGL((pack_qkv_test_kernel<T>), dim3(ew_blocks(rows * 64)), dim3(256), 0, s, q, k, v, qd.p, kd.p, vd.p, rows,
                        N, Npad, attention_q_scale<T>());
     KCHK();
-    HIPCHK(launch_attention_any(s, qd.p, kd.p, vd.p, od.p, Bp, H, N, Npad, lens_host ? ld.p : nullptr, Bp, nullptr, nullptr, g_split16));
+    HIPCHK(launch_attention_any(s, qd.p, kd.p, vd.p, od.p, Bp, H, N, Npad, lens_host ? ld.p : nullptr, Bp, nullptr, nullptr, split16));
     hipLaunchKernelGGL((to_f32_kernel<T>), dim3(ew_blocks(rows * 64)), dim3(256), 0, s, od.p, out, rows * 64);
     KCHK();
     HIPCHK(hipStreamSynchronize(s));
@@ -158,16 +132,12 @@ static int attn_impl(const float* q, const float* k, const float* v, const int32
 extern "C" int f5k_attention(int32_t prec, const float* q, const float* k, const float* v, const int32_t* kv_lens_host,
                              float* out, int32_t Bp, int32_t H, int32_t N, f5_stream stream) {
     if (!q || !k || !v || !out || Bp <= 0 || H <= 0 || N <= 0) return fail(F5_EINVAL, "f5k_attention: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    g_split16 = prec == F5_PREC_F16X3;
-    const int rc = F5K_BY_PREC(prec, attn_impl, q, k, v, kv_lens_host, out, Bp, H, N, s);
-    g_split16 = false;
-    return rc;
+    return F5K_BY_PREC(prec, attn_impl, q, k, v, kv_lens_host, out, Bp, H, N, prec == F5_PREC_F16X3, (hipStream_t)stream);
 }
 
 template <typename T>
 static int convpos_impl(const float* x, const float* w, const float* bias, const float* res, const int32_t* lens_host, float* y,
-                        int Bp, int N, int D, hipStream_t s) {
+                        int Bp, int N, int D, bool split16, hipStream_t s) {
     const int cpg = D / 16, Kp = round_up(31 * cpg, GEMM_ROW_BYTES / (int)sizeof(T));
     Scratch<T> wp;
     Scratch<int> ld;
@@ -178,8 +148,8 @@ static int convpos_impl(const float* x, const float* w, const float* bias, const
     }
     hipLaunchKernelGGL((conv_pack_kernel<T>), dim3(ew_blocks((long)D * Kp)), dim3(256), 0, s, w, wp.p, (long)D, cpg, 31, Kp);
     KCHK();
-    const bool split = g_split16 && std::is_same_v<T, float> && convpos_can_split(D);
-    if (split) HIPCHK(maybe_split<T>(s, wp.p, (size_t)D * Kp));
+    const bool split = split16 && std::is_same_v<T, float> && convpos_can_split(D);
+    if (split) HIPCHK(split_planes(s, wp.p, (size_t)D * Kp));
     HIPCHK(launch_convpos<T>(s, x, wp.p, Kp, bias, res, y, Bp, N, D, lens_host ? ld.p : nullptr, Bp, nullptr, split));
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
@@ -189,11 +159,7 @@ extern "C" int f5k_convpos(int32_t prec, const float* x, const float* w, const f
                            const int32_t* lens_host, float* y, int32_t Bp, int32_t N, int32_t D, f5_stream stream) {
     if (!x || !w || !bias || !y || Bp <= 0 || N <= 0) return fail(F5_EINVAL, "f5k_convpos: bad arguments");
     if (D != 256 && D != 512 && D != 768 && D != 1024) return fail(F5_EINVAL, "f5k_convpos: D must be 256, 512, 768 or 1024");
-    hipStream_t s = (hipStream_t)stream;
-    g_split16 = prec == F5_PREC_F16X3;
-    const int rc = F5K_BY_PREC(prec, convpos_impl, x, w, bias, res, lens_host, y, Bp, N, D, s);
-    g_split16 = false;
-    return rc;
+    return F5K_BY_PREC(prec, convpos_impl, x, w, bias, res, lens_host, y, Bp, N, D, prec == F5_PREC_F16X3, (hipStream_t)stream);
 }
 
 extern "C" int f5k_layernorm_mod(const float* x, const float* scale, const float* shift, float* out, int32_t R, int32_t D,
@@ -251,11 +217,10 @@ extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* s
 // rotary table through rope_frag_kernel, packed rows through fill_rowmap_kernel, qk_norm through qknorm_rope_kernel.
 template <typename T, typename Epi>
 static int epi_gemm(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const Epi& epi, int cfg, const int* ml,
-                    int split) {
-    const bool v3_ok = ((sizeof(T) == 2 && !split) || split == 2) && gemm3_epilogue_ok(epi);
-    if (cfg == G3_256x256_PP && !v3_ok)
+                    GemmOperands ops) {
+    if (cfg == G3_256x256_PP && !(gemm_has_pingpong(sizeof(T), ops) && gemm3_epilogue_ok(epi)))
         return fail(F5_EINVAL, "f5k_gemm_epi: the ping-pong kernel (cfg 20) takes 16-bit or pre-split operands and a QKV split at 256 columns");
-    HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, cfg, ml, 0, GemmConv{}, split));
+    HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, {ops, cfg, ml}));
     return F5_OK;
 }
 
@@ -271,7 +236,7 @@ template <typename TO> static int copy_f32(hipStream_t s, const void* src, float
 
 template <typename T, typename TO>
 static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const float* bias, const f5k_epi& p, const int* ml,
-                   int split) {
+                   GemmOperands ops) {
     Scratch<float> frag;
     HIPCHK(frag.alloc((size_t)p.maxpos * 64));
     hipLaunchKernelGGL(rope_frag_kernel, dim3(ew_blocks((long)p.maxpos * 16)), dim3(256), 0, s, p.rope_cos, p.rope_sin, frag.p, (long)p.maxpos);
@@ -293,7 +258,7 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
     CHK(epi_gemm<T>(s, a, w, ld, M, N, K,
                     EpiQKV<TO>{q, k, static_cast<TO*>(p.out2), bias, frag.p, p.Nseq, p.Npad, p.H, norm ? 0 : p.pe_heads,
                                norm ? 1.0f : p.q_scale, rowmap.p},
-                    p.cfg, ml, split));
+                    p.cfg, ml, ops));
     if (norm) {
         const long qrows = (long)p.Bp * p.H * p.Nseq;
         hipLaunchKernelGGL((qknorm_rope_kernel<TO>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, q, k, p.gq, p.gk,
@@ -308,22 +273,11 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
 }
 
 template <typename T>
-static int gemm_epi_impl(const float* A, const float* W, const float* bias, int M, int N, int K, const f5k_epi& p, hipStream_t s) {
+static int gemm_epi_impl(const float* A, const float* W, const float* bias, int M, int N, int K, const f5k_epi& p, GemmOperands ops,
+                         hipStream_t s) {
     const int Kp = round_up(K, GEMM_ROW_BYTES / (int)sizeof(T));
-    Scratch<T> a, w;
-    HIPCHK(a.alloc((size_t)M * Kp));
-    HIPCHK(w.alloc((size_t)N * Kp));
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)M * Kp)), dim3(256), 0, s, A, K, M, K, a.p, Kp, M);
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)N * Kp)), dim3(256), 0, s, W, K, N, K, w.p, Kp, N);
-    KCHK();
-    int split = 0;
-    if constexpr (std::is_same_v<T, float>) {
-        if (g_split16) {
-            HIPCHK(maybe_split<T>(s, w.p, (size_t)N * Kp));
-            if (p.a_presplit) HIPCHK(maybe_split<T>(s, a.p, (size_t)M * Kp));
-            split = p.a_presplit ? 2 : 1;
-        }
-    }
+    GemmStage<T> g;
+    CHK(g.stage(s, A, K, W, K, M, N, K, Kp, ops));
     Scratch<int> ml;
     if (p.m_limit >= 0) {
         HIPCHK(ml.alloc(1));
@@ -334,12 +288,12 @@ static int gemm_epi_impl(const float* A, const float* W, const float* bias, int 
         case F5K_EPI_STORE:
             if (p.out16) {
                 if constexpr (sizeof(T) == 2) {
-                    CHK(epi_gemm<T>(s, a.p, w.p, Kp, M, N, Kp, EpiStore<T>{static_cast<T*>(p.out0), N, bias, p.act}, p.cfg, ml.p, split));
+                    CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp, EpiStore<T>{static_cast<T*>(p.out0), N, bias, p.act}, p.cfg, ml.p, ops));
                     CHK(copy_f32<T>(s, p.out0, p.out0_f32, p.n0));
                 }
             } else {   // planar 2: the plain store, then split_planar_kernel over the whole output (what planar 1 must equal)
-                CHK(epi_gemm<T>(s, a.p, w.p, Kp, M, N, Kp, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, p.planar == 1}, p.cfg,
-                                ml.p, split));
+                CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, p.planar == 1}, p.cfg,
+                                ml.p, ops));
                 if (p.planar == 2) {
                     hipLaunchKernelGGL(split_planar_kernel, dim3(ew_blocks((long)M * N / 32)), dim3(256), 0, s, static_cast<float*>(p.out0),
                                        (long)M * N / 32);
@@ -352,15 +306,15 @@ static int gemm_epi_impl(const float* A, const float* W, const float* bias, int 
                 HIPCHK(lens.alloc((size_t)p.nlens));
                 HIPCHK(hipMemcpy(lens.p, p.lens_host, (size_t)p.nlens * 4, hipMemcpyHostToDevice));
             }
-            CHK(epi_gemm<T>(s, a.p, w.p, Kp, M, N, Kp,
+            CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp,
                             EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p}, p.cfg,
-                            ml.p, split));
+                            ml.p, ops));
             break;
         default:   // QKV / QKNORM: the output type is the operand type, or f16 on f32 operands (the f16x3 attn16 path)
             if (p.out16) {
-                if constexpr (std::is_same_v<T, float>) CHK((epi_qkv<T, f16_t>(s, a.p, w.p, Kp, M, N, Kp, bias, p, ml.p, split)));
+                if constexpr (std::is_same_v<T, float>) CHK((epi_qkv<T, f16_t>(s, g.a.p, g.w.p, Kp, M, N, Kp, bias, p, ml.p, ops)));
             } else {
-                CHK((epi_qkv<T, T>(s, a.p, w.p, Kp, M, N, Kp, bias, p, ml.p, split)));
+                CHK((epi_qkv<T, T>(s, g.a.p, g.w.p, Kp, M, N, Kp, bias, p, ml.p, ops)));
             }
             break;
     }
@@ -373,8 +327,7 @@ extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const 
     if (!A || !W || !p || !p->out0 || M <= 0 || N <= 0 || K <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm_epi: bad arguments (N %% 4 == 0)");
     if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
         return fail(F5_EINVAL, "f5k_gemm_epi: precision must be f32, f16x3, bf16 or f16");
-    const int c = p->cfg;
-    if (c != -1 && c != G2_128x128_8W && c != G2_64x64_4W && c != G2_128x64_8W && c != G2_128x192_8W && c != G2_256x128_8W && c != G3_256x256_PP)
+    if (p->cfg != -1 && (!gemm_tile(p->cfg) || v1_tile(p->cfg)))
         return fail(F5_EINVAL, "f5k_gemm_epi: cfg must be -1, 2, 8, 9, 10, 13 or 20");
     if (p->m_limit < -1 || p->m_limit > M) return fail(F5_EINVAL, "f5k_gemm_epi: m_limit must be -1 or 0..M");
     if (p->a_presplit && prec != F5_PREC_F16X3) return fail(F5_EINVAL, "f5k_gemm_epi: a_presplit needs F5_PREC_F16X3");
@@ -413,9 +366,6 @@ extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const 
         }
         default: return fail(F5_EINVAL, "f5k_gemm_epi: unknown epilogue kind");
     }
-    hipStream_t s = (hipStream_t)stream;
-    g_split16 = prec == F5_PREC_F16X3;
-    const int rc = F5K_BY_PREC(prec, gemm_epi_impl, A, W, bias, M, N, K, *p, s);
-    g_split16 = false;
-    return rc;
+    const GemmOperands ops = prec != F5_PREC_F16X3 ? GemmOperands::Plain : p->a_presplit ? GemmOperands::AWSplit : GemmOperands::WSplit;
+    return F5K_BY_PREC(prec, gemm_epi_impl, A, W, bias, M, N, K, *p, ops, (hipStream_t)stream);
 }

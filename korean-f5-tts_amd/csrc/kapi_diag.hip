@@ -1,68 +1,51 @@
 // Diagnostic / micro-benchmark entry points (f5x_*, not in the public header): GEMM tile sweeps and pipeline floors, the DiT-block
 // GEMM sequence with its real epilogues, kernel-boundary costs, the grid-barrier and MFMA-rate probes.  Split from kapi.hip so
 // that the many diagnostic GEMM instantiations compile beside it, not after it.
-#include <vector>
-
-#include "attn2.h"
-#include "convpos.h"
-#include "elementwise.h"
-#include "gemm_dispatch.h"
-#include "internal.h"
-
-using namespace f5;
-#define fail f5_fail
-// precision dispatch of a function template call FN<T>(args...)
-#define F5K_BY_PREC(prec, FN, ...) \
-    ((prec) == F5_PREC_BF16 ? FN<bf16_t>(__VA_ARGS__) : (prec) == F5_PREC_F16 ? FN<f16_t>(__VA_ARGS__) : FN<float>(__VA_ARGS__))
+#include "kapi_common.h"
 
 // ------------------------------------------------------------------------------------ v2 (glds ring) GEMM
-#include "gemm2.h"
 static int g_cold_weights = 0;
 static int g_out_bf16 = 0;
 
+// cfg: a product ring / ping-pong tile id (kGemmTiles; 20 for every precision here) or one of the diagnostic-only shapes below
 template <typename T, typename Epi>
 static hipError_t gemm2_dispatch(int cfg, hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K,
-                                 const Epi& epi) {
-    switch (cfg) {
-        case 0: return launch_gemm2_cfg<T, 128, 128, 2, 2, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 1: return launch_gemm2_cfg<T, 128, 128, 2, 2, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 13: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 20: return launch_gemm3<T, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 420: return launch_gemm3<T, Epi, 4>(s, A, lda, W, ldw, M, N, K, epi);   // no epilogue
-        case 2: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 3: return launch_gemm2_cfg<T, 128, 64, 2, 2, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 5: return launch_gemm2_cfg<T, 64, 64, 2, 2, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 7: return launch_gemm2_cfg<T, 128, 128, 4, 2, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 8: return launch_gemm2_cfg<T, 64, 64, 2, 2, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 9: return launch_gemm2_cfg<T, 128, 64, 4, 2, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 10: return launch_gemm2_cfg<T, 128, 192, 2, 4, 3, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        case 11: return launch_gemm2_cfg<T, 128, 192, 2, 4, 4, Epi>(s, A, lda, W, ldw, M, N, K, epi);
-        // diagnostic floors of config 2 (outputs are garbage): 1xx = DMA only, 2xx = compute only
-        case 102: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi, 1>(s, A, lda, W, ldw, M, N, K, epi);
-        case 202: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi, 2>(s, A, lda, W, ldw, M, N, K, epi);
-        case 16: return launch_gemm2_cfg<T, 128, 128, 2, 4, 2, Epi>(s, A, lda, W, ldw, M, N, K, epi);   // 64 KB LDS: 2 workgroups per CU
-        case 17: return launch_gemm2_cfg<T, 256, 128, 4, 2, 2, Epi>(s, A, lda, W, ldw, M, N, K, epi);   // 96 KB
-        case 18: return launch_gemm2_cfg<T, 128, 128, 2, 2, 2, Epi>(s, A, lda, W, ldw, M, N, K, epi);   // 4 waves, 64 KB: 2 per CU
-        case 113: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi, 1>(s, A, lda, W, ldw, M, N, K, epi);
-        case 213: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi, 2>(s, A, lda, W, ldw, M, N, K, epi);
-        case 413: return launch_gemm2_cfg<T, 256, 128, 4, 2, 3, Epi, 4>(s, A, lda, W, ldw, M, N, K, epi);
-        case 402: return launch_gemm2_cfg<T, 128, 128, 2, 4, 4, Epi, 4>(s, A, lda, W, ldw, M, N, K, epi);  // no epilogue
-        case 409: return launch_gemm2_cfg<T, 128, 64, 4, 2, 4, Epi, 4>(s, A, lda, W, ldw, M, N, K, epi);
-        default: return hipErrorInvalidValue;
-    }
+                                 const Epi& dyn_epi) {
+    constexpr GemmOperands P = GemmOperands::Plain;
+    return with_static_act(dyn_epi, [&](const auto& epi) {
+        using E = std::decay_t<decltype(epi)>;
+        switch (cfg) {
+            case 0: return launch_gemm2<T, 128, 128, 2, 2, 3, E>(s, A, lda, W, ldw, M, N, K, epi);
+            case 1: return launch_gemm2<T, 128, 128, 2, 2, 4, E>(s, A, lda, W, ldw, M, N, K, epi);
+            case 20: return launch_gemm3<T, E>(s, A, lda, W, ldw, M, N, K, epi);
+            case 420: return launch_gemm3<T, E, P, GemmDiag::NoEpilogue>(s, A, lda, W, ldw, M, N, K, epi);
+            case 3: return launch_gemm2<T, 128, 64, 2, 2, 4, E>(s, A, lda, W, ldw, M, N, K, epi);
+            case 5: return launch_gemm2<T, 64, 64, 2, 2, 4, E>(s, A, lda, W, ldw, M, N, K, epi);
+            case 7: return launch_gemm2<T, 128, 128, 4, 2, 3, E>(s, A, lda, W, ldw, M, N, K, epi);
+            case 11: return launch_gemm2<T, 128, 192, 2, 4, 4, E>(s, A, lda, W, ldw, M, N, K, epi);
+            // diagnostic floors of config 2 (outputs are garbage): 1xx = DMA only, 2xx = compute only
+            case 102: return launch_gemm2<T, 128, 128, 2, 4, 4, E, P, GemmDiag::DmaOnly>(s, A, lda, W, ldw, M, N, K, epi);
+            case 202: return launch_gemm2<T, 128, 128, 2, 4, 4, E, P, GemmDiag::ComputeOnly>(s, A, lda, W, ldw, M, N, K, epi);
+            case 16: return launch_gemm2<T, 128, 128, 2, 4, 2, E>(s, A, lda, W, ldw, M, N, K, epi);   // 64 KB LDS: 2 workgroups per CU
+            case 17: return launch_gemm2<T, 256, 128, 4, 2, 2, E>(s, A, lda, W, ldw, M, N, K, epi);   // 96 KB
+            case 18: return launch_gemm2<T, 128, 128, 2, 2, 2, E>(s, A, lda, W, ldw, M, N, K, epi);   // 4 waves, 64 KB: 2 per CU
+            case 113: return launch_gemm2<T, 256, 128, 4, 2, 3, E, P, GemmDiag::DmaOnly>(s, A, lda, W, ldw, M, N, K, epi);
+            case 213: return launch_gemm2<T, 256, 128, 4, 2, 3, E, P, GemmDiag::ComputeOnly>(s, A, lda, W, ldw, M, N, K, epi);
+            case 413: return launch_gemm2<T, 256, 128, 4, 2, 3, E, P, GemmDiag::NoEpilogue>(s, A, lda, W, ldw, M, N, K, epi);
+            case 402: return launch_gemm2<T, 128, 128, 2, 4, 4, E, P, GemmDiag::NoEpilogue>(s, A, lda, W, ldw, M, N, K, epi);
+            case 409: return launch_gemm2<T, 128, 64, 4, 2, 4, E, P, GemmDiag::NoEpilogue>(s, A, lda, W, ldw, M, N, K, epi);
+        }
+        return launch_gemm_tile<T, P, E, true>(s, A, lda, W, ldw, M, N, K, epi, cfg, nullptr, GemmConv{});   // a product ring tile, or refused
+    });
 }
 
 template <typename T>
 static int gemm2_impl(const float* A, const float* W, const float* bias, int act, float* out, int M, int N, int K, int cfg,
                       int iters, float* avg_us, hipStream_t s) {
     const int Kp = round_up(K, 128 / (int)sizeof(T));
-    Scratch<T> a, w;
-    HIPCHK(a.alloc((size_t)M * Kp));
-    HIPCHK(w.alloc((size_t)N * Kp));
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)M * Kp)), dim3(256), 0, s, A, K, M, K, a.p, Kp, M);
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)N * Kp)), dim3(256), 0, s, W, K, N, K, w.p, Kp, N);
-    KCHK();
-    HIPCHK(gemm2_dispatch<T>(cfg, s, a.p, Kp, w.p, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}));
+    GemmStage<T> g;
+    CHK(g.stage(s, A, K, W, K, M, N, K, Kp));
+    HIPCHK(gemm2_dispatch<T>(cfg, s, g.a.p, Kp, g.w.p, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}));
     if (iters > 0 && avg_us) {
         // iters < 0 is not used; a NEGATIVE act selects "cold weights": the launches cycle through enough copies of W
         // to exceed the 256 MiB Infinity Cache, as the 22 layers x 4 projections of a DiT step do
@@ -73,20 +56,20 @@ static int gemm2_impl(const float* A, const float* W, const float* bias, int act
         if (cold) {
             HIPCHK(wc.alloc((size_t)ncopy * N * Kp));
             for (int c = 0; c < ncopy; ++c)
-                HIPCHK(hipMemcpyAsync(wc.p + (size_t)c * N * Kp, w.p, wbytes, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(wc.p + (size_t)c * N * Kp, g.w.p, wbytes, hipMemcpyDeviceToDevice, s));
         }
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0));
         HIPCHK(hipEventCreate(&e1));
         for (int i = 0; cold && i < ncopy; ++i)
-            HIPCHK(gemm2_dispatch<T>(cfg, s, a.p, Kp, wc.p + (size_t)(i % ncopy) * N * Kp, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}));
+            HIPCHK(gemm2_dispatch<T>(cfg, s, g.a.p, Kp, wc.p + (size_t)(i % ncopy) * N * Kp, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}));
         HIPCHK(hipEventRecord(e0, s));
         for (int i = 0; i < iters; ++i) {
-            const T* wp = cold ? wc.p + (size_t)(i % ncopy) * N * Kp : w.p;
+            const T* wp = cold ? wc.p + (size_t)(i % ncopy) * N * Kp : g.w.p;
             if (g_out_bf16)  // timing-only: reinterpret the fp32 output buffer as bf16 (half of it is written)
-                HIPCHK(gemm2_dispatch<T>(cfg, s, a.p, Kp, wp, Kp, M, N, Kp, EpiStore<bf16_t>{reinterpret_cast<bf16_t*>(out), N, bias, act}));
+                HIPCHK(gemm2_dispatch<T>(cfg, s, g.a.p, Kp, wp, Kp, M, N, Kp, EpiStore<bf16_t>{reinterpret_cast<bf16_t*>(out), N, bias, act}));
             else
-                HIPCHK(gemm2_dispatch<T>(cfg, s, a.p, Kp, wp, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}));
+                HIPCHK(gemm2_dispatch<T>(cfg, s, g.a.p, Kp, wp, Kp, M, N, Kp, EpiStore<float>{out, N, bias, act}));
         }
         HIPCHK(hipEventRecord(e1, s));
         HIPCHK(hipEventSynchronize(e1));
@@ -159,13 +142,13 @@ extern "C" int f5x_block_gemm_time(int32_t M, int32_t cfg, int32_t iters, float*
         const int c = (it + 2) % ncopy;
         HIPCHK(hipEventRecord(ev[0], s));
         HIPCHK(launch_gemm<T>(s, xn.p, D, wqkv.p + (size_t)c * 3 * D * D, D, M, 3 * D, D,
-                              EpiQKV<T>{q.p, k.p, vt.p, bias.p, rope.p, N, N, H, PE, 0.18f, nullptr}, cfg));
+                              EpiQKV<T>{q.p, k.p, vt.p, bias.p, rope.p, N, N, H, PE, 0.18f, nullptr}, {GemmOperands::Plain, cfg}));
         HIPCHK(hipEventRecord(ev[1], s));
-        HIPCHK(launch_gemm<T>(s, ao.p, D, wout.p + (size_t)c * D * D, D, M, D, D, EpiGateRes{x.p, x.p, D, bias.p, gate.p, D, N, nullptr}, cfg));
+        HIPCHK(launch_gemm<T>(s, ao.p, D, wout.p + (size_t)c * D * D, D, M, D, D, EpiGateRes{x.p, x.p, D, bias.p, gate.p, D, N, nullptr}, {GemmOperands::Plain, cfg}));
         HIPCHK(hipEventRecord(ev[2], s));
-        HIPCHK(launch_gemm<T>(s, xn.p, D, wff1.p + (size_t)c * F * D, D, M, F, D, EpiStore<T>{ffh.p, F, bias.p, F5_ACT_GELU_TANH}, cfg));
+        HIPCHK(launch_gemm<T>(s, xn.p, D, wff1.p + (size_t)c * F * D, D, M, F, D, EpiStore<T>{ffh.p, F, bias.p, F5_ACT_GELU_TANH}, {GemmOperands::Plain, cfg}));
         HIPCHK(hipEventRecord(ev[3], s));
-        HIPCHK(launch_gemm<T>(s, ffh.p, F, wff2.p + (size_t)c * D * F, F, M, D, F, EpiGateRes{x.p, x.p, D, bias.p, gate.p, D, N, nullptr}, cfg));
+        HIPCHK(launch_gemm<T>(s, ffh.p, F, wff2.p + (size_t)c * D * F, F, M, D, F, EpiGateRes{x.p, x.p, D, bias.p, gate.p, D, N, nullptr}, {GemmOperands::Plain, cfg}));
         HIPCHK(hipEventRecord(ev[4], s));
         HIPCHK(hipEventSynchronize(ev[4]));
         if (it >= 0)

@@ -29,6 +29,15 @@ def k_gemm(prec, A, W, bias=None, act=0, tile=(0, 0)):
     return out
 
 
+def k_gemm_plan(elem_size, M, N, K, has_m_limit=0, m_hint=0, form=0, conv=0, pp_epi=1, force_cfg=-1, env_cfg=-1, env_n=0):
+    """launch_gemm's decision (f5k_gemm_plan, no GPU needed): [] nothing to do, None refused, else a list of
+    (family, tile, first row, rows)."""
+    plan = (C.c_int32 * 9)()
+    _lib.check(_lib.load().f5k_gemm_plan(elem_size, M, N, K, has_m_limit, m_hint, form, conv, pp_epi, force_cfg, env_cfg, env_n, plan),
+               "f5k_gemm_plan")
+    return None if plan[0] < 0 else [tuple(plan[1 + 4 * i:5 + 4 * i]) for i in range(plan[0])]
+
+
 def k_attention(prec, q, k, v, lens=None):
     lib = _lib.load()
     Bp, H, N, _ = q.shape

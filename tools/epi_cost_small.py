@@ -1,5 +1,5 @@
 """What the epilogue costs at the C2 row count (M = 2,048; cold weights): each v2 tile with a plain bf16 / f32 store against the same
-kernel without its epilogue (gemm2.h MODE 4)."""
+kernel without its epilogue (gemm2.h, GemmDiag::NoEpilogue)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,4 +1,4 @@
-"""Split-operand GEMM (F5_PREC_F16X3, gemm2.h MODE 3): error against a float64 product next to the f32 and f16 kernels, every
+"""Split-operand GEMM (F5_PREC_F16X3, gemm2.h, GemmOperands::WSplit): error against a float64 product next to the f32 and f16 kernels, every
 tile configuration, then the rate at the shapes of C2 (M = 2048) and C3 (M = 16384).
 usage: python tools/split_check.py"""
 import ctypes as C
