@@ -17,6 +17,7 @@
  *   f5_wave_crossfade <- the cross-fade concatenation of the chunks  infer/utils_infer.py:734-775
  *   f5_mel_forward   <- MelSpec.forward (vocos / bigvgan type)       model/modules.py:33-146
  *   f5_mel_forward_ragged <- the per-prompt MelSpec loop + padded_mel_batch  eval/utils_eval.py:109-148
+ *   f5_mel_prepare_ragged <- the per-prompt mono mix, RMS, level and resample  infer/utils_infer.py:523-533, eval/utils_eval.py:111-118
  *   f5_load_weight   <- load_checkpoint's state-dict assignment      infer/utils_infer.py:242-286
  * The reference-side binding (ctypes) is shown in INTEGRATION.md.
  */
@@ -342,6 +343,46 @@ int f5_mel_ragged_plan(int32_t n_fft, int32_t hop, int32_t pad, int32_t B, const
                        int32_t* frames_out);
 int f5_mel_forward_ragged(f5_mel* m, const float* wav, int32_t B, const int64_t* wav_start_host, const int32_t* nw_host, int32_t pad,
                           float mag_eps, float* out, int64_t out_stride_b, int32_t T_out, f5_stream stream);
+
+/* ------------------------------------------------------------------------------------- prompt preparation
+ * What both drivers do to a prompt before its mel (infer/utils_infer.py:523-533, eval/utils_eval.py:111-118: mono mix, RMS, the
+ * gain up to target_rms, torchaudio Resample to the model's rate) for B prompts of any channel count, length and rate in ONE pass:
+ * a partial-sum launch, a finishing launch and a resample launch, one table copy, no host read.  Item b has C_b channels of n_b
+ * samples at sr_b Hz, laid out [C_b, n_b] row-major from base[start_host[b]].  The arithmetic contract, per item:
+ *   1. mono    m[j] = (x[0][j] + x[1][j] + ... in ascending channel order, f32) / C_b; the sample itself for C_b = 1
+ *              (bit for bit torch.mean(audio, dim=0) for C_b = 2, and for C_b = 3 on every one of 10^6 random triples)
+ *   2. rms     S = sum_j (double)m[j] * (double)m[j] in f64, in a fixed order: tiles of 2048 samples, inside a tile each of 256
+ *              threads adds its samples j = t, t + 256, ... and a fixed tree adds the threads; the tiles' sums are added in
+ *              ascending tile order by one thread.  No floating atomics: the value depends on the item alone.
+ *              rms_b = (float)sqrt(S / n_b) -> rms_out[b]
+ *   3. level   v[j] = (m[j] * target_rms) / rms_b where rms_b < target_rms (two f32 operations, as `audio * target_rms / rms`
+ *              evaluates), else v = m; decided on the device.  An all-zero prompt gives NaN, as those operations do.
+ *   4. resample (sr_b != target_sr)  g = gcd(sr_b, target_sr), orig = sr_b / g, new = target_sr / g,
+ *              width = ceil(6 * orig / (0.99 * min(orig, new))) evaluated in double, K = 2 width + orig taps:
+ *              y[i * new + p] = sum_k bank[p][k] * vpad[i * orig + k], k ascending from an accumulator of +0.0, every step an f32
+ *              multiply then an f32 add (no fused multiply-add); vpad is v behind `width` zeros and in front of zeros, the zeros
+ *              made by index logic.  L_b = ceil(new * n_b / orig) samples.  sr_b == target_sr: y = v, L_b = n_b.
+ * bank is the f32 cast of the float64 windowed-sinc kernel of torchaudio's Resample defaults (sinc_interp_hann, lowpass_filter_width 6,
+ * rolloff 0.99), computed by the caller on the host and handed over once per rate pair with f5_mel_resample_bank as f32[new, K]
+ * (row p = phase p); the handle keeps a device copy laid out [K, new] per (orig, new) until it is destroyed.  A pair that is
+ * already there is left alone (nothing is copied); *uploads_out of f5_mel_resample_bank_count counts the copies made so far.
+ * f5_mel_resample_bank synchronises (a copy from pageable memory, once per pair).
+ * f5_mel_prepare_plan is the packing as pure host arithmetic (no HIP call): len_out[b] = L_b, start_out[b] = the element of the
+ * packed output where item b starts (each rounded up to a multiple of 4), *total_out = the elements the packed output needs.
+ * f5_mel_prepare_ragged writes out[start_b .. start_b + L_b) for every item and rms_out[0 .. B); nothing else of out is written,
+ * nothing outside an item's C_b * n_b samples is read.  The host tables are free when the call returns (one copy through a
+ * pinned slot); no synchronisation and no allocation except the growth of the handle's workspace.
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the item: a null pointer, B < 1 or B > 65535,
+ * target_sr < 1, target_rms <= 0 (or NaN), start_b < 0, channels_b < 1, n_b < 1, sr_b < 1, a rate pair whose bank new * K exceeds 2^20
+ * elements (e.g. 24001 Hz), more than 2^30 tiles of work in one call, out_capacity below the plan's total, a bank of the
+ * wrong size.  F5_ESTATE: an item's rate pair has no bank yet. */
+int f5_mel_prepare_plan(int32_t B, const int32_t* n_host, const int32_t* sr_host, int32_t target_sr, int64_t* len_out,
+                        int64_t* start_out, int64_t* total_out);
+int f5_mel_resample_bank(f5_mel* m, int32_t sr, int32_t target_sr, const float* bank_host, int64_t numel, f5_stream stream);
+int f5_mel_resample_bank_count(f5_mel* m, int32_t* uploads_out);
+int f5_mel_prepare_ragged(f5_mel* m, const float* base, int32_t B, const int64_t* start_host, const int32_t* channels_host,
+                          const int32_t* n_host, const int32_t* sr_host, int32_t target_sr, float target_rms, float* out,
+                          int64_t out_capacity, float* rms_out, f5_stream stream);
 
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;

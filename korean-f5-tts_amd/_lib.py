@@ -104,6 +104,12 @@ SIGNATURES = {
     "f5_mel_forward_ex": (_i, [_p, _p, _i, _i, _i, _f, _p, _p]),
     "f5_mel_ragged_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "f5_mel_forward_ragged": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), _i, _f, _p, C.c_int64, _i, _p]),
+    "f5_mel_prepare_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                            C.POINTER(C.c_int64)]),
+    "f5_mel_resample_bank": (_i, [_p, _i, _i, _p, C.c_int64, _p]),
+    "f5_mel_resample_bank_count": (_i, [_p, C.POINTER(_i)]),
+    "f5_mel_prepare_ragged": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _f, _p,
+                              C.c_int64, _p, _p]),
     "f5k_gemm": (_i, [_i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "f5k_gemm_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "f5k_attention": (_i, [_i, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),

@@ -15,6 +15,7 @@
 #include "elementwise.h"
 #include "gemm_dispatch.h"
 #include "internal.h"
+#include "mel_handle.h"
 
 using namespace f5;
 #define fail f5_fail
@@ -104,18 +105,6 @@ static __global__ void magnitude_kernel(const float* __restrict__ spec, int lds,
         mag[i] = v;
     }
 }
-
-struct f5_mel {
-    int n_fft = 0, hop = 0, n_mels = 0, F = 0, ns = 0, kf = 0;
-    float *basis = nullptr, *fb = nullptr;
-    Arena arena;
-    Staging stage;                    // pinned slots for the ragged call's per-item tables
-    std::vector<int32_t> plan_rows;   // ragged call: row_start[B + 1] | frames[B] (host; grows, never shrinks)
-    ~f5_mel() {
-        if (basis) (void)hipFree(basis);
-        if (fb) (void)hipFree(fb);
-    }
-};
 
 extern "C" int f5_mel_create(int32_t n_fft, int32_t hop, int32_t n_mels, f5_mel** out) {
     if (!out || n_fft <= 0 || hop <= 0 || n_mels <= 0 || (n_fft % 32) || (hop % 4) || (n_mels % 4))

@@ -17,10 +17,15 @@
                                                                  (f5_wave_crossfade); `batched=True` of infer_process
   normalise_prompt / prompt_batch    eval/utils_eval.py:109-148  many speakers, one sentence each: the prompts' mels in ONE ragged
   synthesize_prompts                 eval_infer_batch.py:183-212 pass (MelSpec.forward_ragged), then synthesize_batch per group
+  sinc_resample                      utils_infer.py:530-532      torchaudio's Resample restated (torchaudio is absent): prompts at any
+                                                                 rate are brought to 24 kHz, on the host per prompt, or with
+                                                                 `prompt_on_device=True` (prompt_batch, synthesize_prompts,
+                                                                 synthesize_long) together with the mono mix, the RMS and the gain
+                                                                 in ONE pass on the device (MelSpec.prepare_ragged)
 
-Out of scope here: pydub silence clipping, Whisper ASR, resampling (torchaudio is absent:
-prompts must already be at 24 kHz), pinyin / Korean G2P tokenisers (text is tokenised per character through
-`vocab_char_map`, or as utf-8 bytes when the model has no vocabulary, exactly as CFM.sample does for list[str]).
+Out of scope here: pydub silence clipping, Whisper ASR, resampling of the OUTPUT, pinyin /
+Korean G2P tokenisers (text is tokenised per character through `vocab_char_map`, or as utf-8 bytes when the model has no
+vocabulary, exactly as CFM.sample does for list[str]).
 Only checkpoints are loaded with loaders that execute nothing from the file (safetensors, torch.load(weights_only=True)).
 """
 from __future__ import annotations
@@ -32,6 +37,7 @@ import torch
 
 from .cfm import CFM, clamp_durations
 from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
+from .mel import resample_kernel, resampled_length
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
 
@@ -182,16 +188,7 @@ def sinc_resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass
     import math
     if orig_freq == new_freq:
         return waveform
-    g = math.gcd(int(orig_freq), int(new_freq))
-    orig, new = int(orig_freq) // g, int(new_freq) // g
-    base_freq = min(orig, new) * rolloff
-    width = math.ceil(lowpass_filter_width * orig / base_freq)
-    idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
-    t = torch.arange(0, -new, -1, dtype=torch.float64)[:, None, None] / new + idx
-    t = (t * base_freq).clamp_(-lowpass_filter_width, lowpass_filter_width)
-    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
-    t = t * math.pi
-    kernels = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base_freq / orig)
+    kernels, orig, new, width = resample_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff)
     kernels = kernels.to(waveform.dtype)                                       # [new, 1, 2 width + orig]
     n = waveform.shape[-1]
     x = torch.nn.functional.pad(waveform.reshape(-1, n), (width, width + orig))
@@ -218,17 +215,36 @@ def prompt_numerics(audio: torch.Tensor, sr: int, ref_text: str, gen_text: str, 
     """The host arithmetic of process_batch (utils_infer.py:523-533,541-544,678-685) factored out so that it can be
     pinned by hand-computed cases: returns (audio mono RMS-normalised [1, nw], rms, ref_audio_len, duration)."""
     audio, rms = normalise_prompt(audio, sr, target_rms_)
+    ref_text, ref_audio_len, duration = text_numerics(audio.shape[-1], ref_text, gen_text, speed_, fix_duration_)
+    return audio, rms, ref_text, ref_audio_len, duration
+
+
+def text_numerics(nw: int, ref_text: str, gen_text: str, speed_: float = speed, fix_duration_=None):
+    """prompt_numerics behind the audio: from the prompt's sample count at 24 kHz (mel.resampled_length gives it without
+    touching the audio) to (ref_text with the trailing-space rule, ref_audio_len, duration)."""
     if len(ref_text[-1].encode("utf-8")) == 1:
         ref_text = ref_text + " "
     local_speed = 0.3 if len(gen_text.encode("utf-8")) < 10 else speed_
-    ref_audio_len = audio.shape[-1] // hop_length
+    ref_audio_len = nw // hop_length
     if fix_duration_ is not None:
         duration = int(fix_duration_ * target_sample_rate / hop_length)
     else:
         ref_text_len = len(ref_text.encode("utf-8"))
         gen_text_len = len(gen_text.encode("utf-8"))
         duration = ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed)
-    return audio, rms, ref_text, ref_audio_len, duration
+    return ref_text, ref_audio_len, duration
+
+
+def rescale_to_prompt(wave: torch.Tensor, rms, target_rms_: float = target_rms) -> torch.Tensor:
+    """The output rescale of both drivers, `wave * rms / target_rms` where the prompt's rms was below target_rms
+    (utils_infer.py:706-707).  rms as a python float (the host route): the branch as the reference writes it; as a 0-dim device
+    tensor (prompt_on_device): the same two operations selected by torch.where, bit-equal for the same rms, and nothing is read
+    back from the device."""
+    if isinstance(rms, torch.Tensor):
+        return torch.where(rms < target_rms_, wave * rms / target_rms_, wave)
+    if rms < target_rms_:
+        wave = wave * rms / target_rms_
+    return wave
 
 
 def cross_fade_concat(waves: list[np.ndarray], cross_fade_duration_: float = cross_fade_duration) -> np.ndarray:
@@ -345,7 +361,7 @@ def _progress(progress, iterable):
 def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *, mel_spec_type=mel_spec_type, progress=None,
                     target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                     sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
-                    text_tokenizer=None, batch_frames=None):
+                    text_tokenizer=None, batch_frames=None, prompt_on_device=False):
     """The chunks of one long text as ragged batches instead of one B = 1 pass each (the reference submits them to a
     ThreadPoolExecutor, utils_infer.py:725-732): the host arithmetic of infer_batch_process per chunk (prompt_numerics:
     local_speed, the duration formula, the trailing-space rule), then
@@ -357,6 +373,9 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
       ONE f5_wave_crossfade over the rows of every group.
     Nothing is copied to the host: returns (wave f32[total], sample_rate, combined mel f32[100, T_total]), both on the device.
     At most 64 chunks (ValueError); Vocos only (a vocoder without decode_ragged, e.g. BigVGAN: NotImplementedError).
+    prompt_on_device=True: the prompt's mono mix, RMS, gain and resampling run on the device (a B = 1
+    `model_obj.mel_spec.prepare_ragged`) instead of normalise_prompt on the host; the frame arithmetic comes from
+    mel.resampled_length and the rescale takes the device rms (rescale_to_prompt), so nothing is read back.
 
     Against the sequential path (infer_batch_process, batched=False):
       * the waveform is f32; the sequential one is float64 wherever a cross-fade happened (numpy promotes).  The values are
@@ -377,11 +396,18 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
     device = device if device is not None else model_obj.device
     texts, durations = [], []
     for gen_text in gen_text_batches:
-        a, rms, rtext, ref_len, duration = prompt_numerics(audio, sr, ref_text, gen_text, speed, fix_duration, target_rms)
+        if prompt_on_device:
+            rtext, ref_len, duration = text_numerics(resampled_length(audio.shape[-1], sr, target_sample_rate), ref_text, gen_text,
+                                                     speed, fix_duration)
+        else:
+            a, rms, rtext, ref_len, duration = prompt_numerics(audio, sr, ref_text, gen_text, speed, fix_duration, target_rms)
         texts.append(rtext + gen_text)
         durations.append(duration)
     texts, idx = _tokenise(model_obj, texts, text_tokenizer, stacklevel=3)
     with torch.inference_mode():
+        if prompt_on_device:
+            wavs, rms_dev = model_obj.mel_spec.prepare_ragged([audio], [sr], target_rms, device=device)
+            a, rms = wavs[0][None], rms_dev[0]
         cond = model_obj.mel_spec(a.to(device)).permute(0, 2, 1)                # [1, T, 100], T = ref_len + 1 (centre padding)
         cond_len = cond.shape[1]
         ends = clamp_durations(idx, torch.full((len(texts),), cond_len, dtype=torch.long), torch.tensor(durations)).tolist()
@@ -395,8 +421,7 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
                                             cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
             generated = generated.to(torch.float32)
             wave, wave_lens = vocoder.decode_ragged(generated.permute(0, 2, 1), ends=[ends[k] for k in run], starts=[ref_len] * B)
-            if rms < target_rms:
-                wave = wave * rms / target_rms
+            wave = rescale_to_prompt(wave, rms, target_rms)
             rows.append(wave)
             lens += wave_lens
             specs += [generated[b, ref_len:ends[k]].permute(1, 0) for b, k in enumerate(run)]
@@ -416,7 +441,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                         progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                         nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                         speed=speed, fix_duration=fix_duration, device=None, streaming=False, chunk_size=2048, seed=None,
-                        text_tokenizer=None, batched=False, batch_frames=None):
+                        text_tokenizer=None, batched=False, batch_frames=None, prompt_on_device=False):
     """A GENERATOR, as in the reference (utils_infer.py:504-522,711-778):
       streaming=False  yields ONE item (final_wave f32 numpy, sample_rate, combined mel [100, T_total]) -- the cross-faded
                        concatenation over the text batches; (None, sample_rate, None) when there is no batch
@@ -430,6 +455,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     which is unchanged: the waveform is f32 (the sequential one is float64 wherever a cross-fade happened), and a chunk's mel
     equals the same chunk run alone only with `attn_mask_enabled=True`; with `attn_mask_enabled=False` (the shipped configs) a
     shorter chunk attends over the batch's padded frames, as in the reference's batch driver (see synthesize_long).
+    prompt_on_device=True (with batched=True only: ValueError otherwise; the sequential path prepares its prompt on the host)
+    is handed to synthesize_long: the prompt is mixed, levelled and resampled on the device.
 
     Text front-end: the reference turns `ref_text + gen_text` into tokens per `model_obj._tokenizer_type` -- for the kor_*
     types through Korean G2P / jamo decomposition / allophone rules (utils_infer.py:549-660: g2pk and the repo's own rule
@@ -439,6 +466,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     than synthesise from ids that are almost all 0 (raw Hangul is not in a jamo / allophone vocabulary)."""
     if batched and streaming:
         raise ValueError("infer_batch_process: batched=True yields one finished waveform; it cannot be combined with streaming=True")
+    if prompt_on_device and not batched:
+        raise ValueError("infer_batch_process: prompt_on_device=True needs batched=True (the sequential path prepares its prompt on the host)")
     audio, sr = ref_audio
     device = device if device is not None else model_obj.device
     _require_text_tokenizer(model_obj, text_tokenizer)
@@ -451,7 +480,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
             (audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type, progress=progress,
             target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
             sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=device, seed=seed,
-            text_tokenizer=text_tokenizer, batch_frames=batch_frames)
+            text_tokenizer=text_tokenizer, batch_frames=batch_frames, prompt_on_device=prompt_on_device)
         yield wave.cpu().numpy(), rate, spec.cpu().numpy()
         return
 
@@ -506,22 +535,28 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
     return wav, wav_lens, mel
 
 
-def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_spec, device=None):
+def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_spec, device=None, prompt_on_device=False):
     """`get_inference_prompt` for one batch (eval/utils_eval.py:109-148, without the truth-duration branch and the bucketing,
     which is batching.bucket_prompts): prompts is a list of (audio [channels, nw], sample_rate, ref_text), gen_texts the text to
     speak with each.  normalise_prompt per item on the host, then ONE `mel_spec.forward_ragged` over every prompt.  Returns
     dict(cond f32[B, T_max, n_mels] zero-padded (padded_mel_batch), lens = frames per prompt (ref_mel_len), durations =
-    total_mel_len per item, texts = prompt text + target text (trailing-space rule), rms per prompt)."""
+    total_mel_len per item, texts = prompt text + target text (trailing-space rule), rms per prompt).
+    prompt_on_device=True: ONE `mel_spec.prepare_ragged` over every prompt (mono mix, RMS, gain and resampling on the device, the
+    raw audio down in one copy) instead of the normalise_prompt loop; `rms` is then a device f32[B] tensor and stays there."""
     from .batching import prompt_text_and_frames
 
     prompts, gen_texts = list(prompts), list(gen_texts)
     if not prompts or len(prompts) != len(gen_texts):
         raise ValueError(f"prompt_batch: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt, at least one)")
-    audios, rms = [], []
-    for audio, sr, _ref_text in prompts:
-        a, r = normalise_prompt(audio, sr, target_rms)
-        audios.append(a)
-        rms.append(r)
+    where = {} if device is None else dict(device=device)
+    if prompt_on_device:
+        audios, rms = mel_spec.prepare_ragged([p[0] for p in prompts], [p[1] for p in prompts], target_rms, **where)
+    else:
+        audios, rms = [], []
+        for audio, sr, _ref_text in prompts:
+            a, r = normalise_prompt(audio, sr, target_rms)
+            audios.append(a)
+            rms.append(r)
     mel, frames = mel_spec.forward_ragged(audios) if device is None else mel_spec.forward_ragged(audios, device=device)
     texts, durations = [], []
     for (_audio, _sr, ref_text), gen_text, n in zip(prompts, gen_texts, frames):
@@ -533,13 +568,16 @@ def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_
 
 def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, target_rms=target_rms, nfe_step=nfe_step,
                        cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, text_tokenizer=None,
-                       batch_frames=None, **sample_kw):
+                       batch_frames=None, prompt_on_device=False, **sample_kw):
     """The reference's batch job from raw prompt audio to waveforms (eval/utils_eval.py:109-148 + eval_infer_batch.py:183-212):
     many speakers, one sentence each.  prompt_batch (ONE ragged mel pass over every prompt), then per group of items
     (group_chunks over the totals sample() runs at; `batch_frames` = the budget of rows x longest row, None: groups of up to 64)
     ONE synthesize_batch -- sample() and one ragged decode -- with the group's `cond` cut to its longest prompt, then the rescale
     `wave * rms_i / target_rms` on exactly the rows with rms_i < target_rms, as the sequential path writes it (not a
     decode_ragged gain: one multiply is not bit-equal to a multiply and a divide).
+    prompt_on_device=True: the prompts are prepared on the device (prompt_batch), their rms stays there and the rescale selects
+    with torch.where (rescale_to_prompt): no per-item host arithmetic on audio and no device-to-host read before the waveforms
+    are returned.
     Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Vocos only."""
     _require_text_tokenizer(model, text_tokenizer)
     _require_ragged_vocoder(vocoder, "synthesize_prompts", "decode item by item")
@@ -549,7 +587,8 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
     if len(prompts) != len(gen_texts):
         raise ValueError(f"synthesize_prompts: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt)")
     with torch.inference_mode():
-        pb = prompt_batch(prompts, gen_texts, speed=speed, target_rms=target_rms, mel_spec=model.mel_spec, device=model.device)
+        pb = prompt_batch(prompts, gen_texts, speed=speed, target_rms=target_rms, mel_spec=model.mel_spec, device=model.device,
+                          prompt_on_device=prompt_on_device)
         texts, idx = _tokenise(model, pb["texts"], text_tokenizer, stacklevel=3)
         lens, durations, rms = pb["lens"], pb["durations"], pb["rms"]
         ends = clamp_durations(idx.to("cpu", torch.long), torch.tensor(lens), torch.tensor(durations),
@@ -563,10 +602,7 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
                                                   cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
                                                   **sample_kw)
             for b, k in enumerate(run):
-                wave = wav[b, :wav_lens[b]]
-                if rms[k] < target_rms:
-                    wave = wave * rms[k] / target_rms
-                waves.append(wave)
+                waves.append(rescale_to_prompt(wav[b, :wav_lens[b]], rms[k], target_rms))
                 mels.append(mel[b, lens[k]:ends[k]].to(torch.float32).permute(1, 0))
         return waves, target_sample_rate, mels
 
@@ -574,12 +610,13 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
-                  text_tokenizer=None, batched=False, batch_frames=None):
+                  text_tokenizer=None, batched=False, batch_frames=None, prompt_on_device=False):
     """ref_audio = (tensor [channels, nw], sample_rate) instead of a path (no torchaudio.load here); otherwise
     utils_infer.py:453-498: max_chars from the prompt's bytes-per-second, chunk, infer_batch_process.
     batched=True (default False: the sequential path, unchanged) runs the chunks as ragged batches of at most `batch_frames`
     and cross-fades on the device (infer_batch_process, synthesize_long): the waveform is then f32 where the sequential one is
-    float64 after a cross-fade, and a chunk's mel equals the chunk run alone only with `attn_mask_enabled=True`."""
+    float64 after a cross-fade, and a chunk's mel equals the chunk run alone only with `attn_mask_enabled=True`.
+    prompt_on_device=True (batched=True only): the prompt is mixed, levelled and resampled on the device."""
     audio, sr = ref_audio
     max_chars = int(len(ref_text.encode("utf-8")) / (audio.shape[-1] / sr) * (22 - audio.shape[-1] / sr) * speed)
     batches = chunk_text(gen_text, max_chars=max_chars)
@@ -589,4 +626,5 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
                                     progress=progress, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                                     nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                                     speed=speed, fix_duration=fix_duration, device=device, seed=seed,
-                                    text_tokenizer=text_tokenizer, batched=batched, batch_frames=batch_frames))
+                                    text_tokenizer=text_tokenizer, batched=batched, batch_frames=batch_frames,
+                                    prompt_on_device=prompt_on_device))

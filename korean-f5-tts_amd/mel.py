@@ -3,7 +3,10 @@ torchaudio MelSpectrogram(n_fft=1024, win=1024, hop=256, n_mels=100, power=1, ce
 clamp(min=1e-5).log() (modules.py:78-104); mel_spec_type="bigvgan": reflect pad (n_fft - hop) / 2, stft(center=False),
 sqrt(re^2 + im^2 + 1e-9), librosa's slaney mel basis, log(clamp(., 1e-5)) (modules.py:33-75).  The arithmetic runs in libf5hip (csrc/mel.hip: strided-view STFT GEMM, magnitude, mel GEMM
 with a log epilogue); this file only builds the constant tables on the host.  `forward_ragged` is the reference's
-per-prompt loop + `padded_mel_batch` (eval/utils_eval.py:109-148, 17-25) as one pass over the packed rows of every prompt.
+per-prompt loop + `padded_mel_batch` (eval/utils_eval.py:109-148, 17-25) as one pass over the packed rows of every prompt;
+`prepare_ragged` is what the drivers do to each prompt in front of it (mono mix, RMS, the gain up to target_rms, torchaudio's
+Resample to the model's rate; utils_infer.py:523-533) as one pass on the device (csrc/prompt.hip), from the windowed-sinc bank
+that `resample_kernel` builds here on the host.
 
 torchaudio is not installed in the build container, so its HTK filterbank (`melscale_fbanks`, norm=None) is restated
 here from its published definition, and so is librosa's slaney filterbank (`librosa.filters.mel`, htk=False,
@@ -11,6 +14,7 @@ norm="slaney") for the bigvgan variant -- PARITY UNPINNED for those two tables (
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 
 import torch
@@ -70,6 +74,38 @@ def stft_basis(n_fft: int) -> torch.Tensor:
     return B.to(torch.float32)
 
 
+def resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """The polyphase windowed-sinc kernel of torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults
+    (functional._get_sinc_resample_kernel, resampling_method="sinc_interp_hann"), restated from its published algorithm: returns
+    (kernels float64 [new, 1, 2 width + orig], orig, new, width) with orig, new the rates over their gcd.  infer.sinc_resample
+    convolves with its cast to the waveform's dtype; the device path (MelSpec.prepare_ragged) uploads its f32 cast."""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    orig, new = int(orig_freq) // g, int(new_freq) // g
+    base_freq = min(orig, new) * rolloff
+    width = math.ceil(lowpass_filter_width * orig / base_freq)
+    idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
+    t = torch.arange(0, -new, -1, dtype=torch.float64)[:, None, None] / new + idx
+    t = (t * base_freq).clamp_(-lowpass_filter_width, lowpass_filter_width)
+    window = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    kernels = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * window * (base_freq / orig)
+    return kernels, orig, new, width
+
+
+@functools.lru_cache(maxsize=32)
+def _resample_bank_f32(sr: int, target: int) -> torch.Tensor:
+    """f32 [new, 2 width + orig]: what f5_mel_resample_bank takes (computed once per rate pair and process)."""
+    return resample_kernel(sr, target)[0][:, 0].to(torch.float32).contiguous()
+
+
+def resampled_length(n: int, sr: int, target_sample_rate: int = 24_000) -> int:
+    """Samples a prompt of n samples at sr Hz has at the target rate, ceil(new * n / orig) in integers: the length of
+    infer.sinc_resample's result and of MelSpec.prepare_ragged's item, without a device read."""
+    g = math.gcd(int(sr), int(target_sample_rate))
+    orig, new = int(sr) // g, int(target_sample_rate) // g
+    return -(-new * int(n) // orig)
+
+
 class MelSpec(NativeModule):
     _prefix, _load, _finalize = "f5_mel", "f5_mel_load", False
     _no_cpu = "the HIP mel front-end only runs on a GPU (there is no CPU path)"
@@ -114,6 +150,24 @@ class MelSpec(NativeModule):
         """(reflect padding, magnitude epsilon) of the mel_spec_type."""
         return (self.n_fft // 2, 0.0) if self.mel_spec_type == "vocos" else ((self.n_fft - self.hop_length) // 2, 1e-9)
 
+    def _ragged_device(self, tensors, device, mixed):
+        """Where a ragged call runs: `device`, else the device tensors' device, else the current GPU (mixed: the message when
+        the device tensors disagree with it)."""
+        on_gpu = [w.device for w in tensors if w.device.type == "cuda"]
+        if device is not None:
+            dev = torch.device(device)
+        elif on_gpu:
+            dev = on_gpu[0]
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        if dev.type != "cuda":
+            raise RuntimeError(self._no_cpu)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if any(d != dev for d in on_gpu):
+            raise ValueError(mixed)
+        return dev
+
     @torch.no_grad()
     def forward_ragged(self, wavs, device=None):
         """Prompts of unequal length in one pass (f5_mel_forward_ragged): wavs is a list of f32 [nw_i] (or [1, nw_i]) tensors, on
@@ -126,19 +180,7 @@ class MelSpec(NativeModule):
             raise ValueError("forward_ragged: no waveform")
         if any(w.dim() != 1 for w in wavs):
             raise ValueError("forward_ragged: every waveform must be [nw] or [1, nw]")
-        on_gpu = [w.device for w in wavs if w.device.type == "cuda"]
-        if device is not None:
-            dev = torch.device(device)
-        elif on_gpu:
-            dev = on_gpu[0]
-        else:
-            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        if dev.type != "cuda":
-            raise RuntimeError(self._no_cpu)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if any(d != dev for d in on_gpu):
-            raise ValueError("forward_ragged: the waveforms are on different devices")
+        dev = self._ragged_device(wavs, device, "forward_ragged: the waveforms are on different devices")
         nws = [int(w.shape[0]) for w in wavs]
         host = [i for i, w in enumerate(wavs) if w.device.type != "cuda"]
         wavs = [w if w.device.type != "cuda" else w.to(torch.float32).contiguous() for w in wavs]
@@ -163,3 +205,55 @@ class MelSpec(NativeModule):
             _lib.check(lib.f5_mel_forward_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), nw_arr, pad, eps, _ptr(out),
                                                  T * self.n_mel_channels, T, _stream_ptr(dev)), "f5_mel_forward_ragged")
         return out.permute(0, 2, 1), frames
+
+    @torch.no_grad()
+    def prepare_ragged(self, audios, rates, target_rms=0.1, device=None):
+        """What the drivers do to every prompt before its mel -- mono mix, RMS, the gain up to target_rms where the RMS is below it,
+        resampling to `target_sample_rate` (infer.normalise_prompt per item) -- in one pass on the device (f5_mel_prepare_ragged;
+        the arithmetic contract is in include/f5_hip.h).  audios: a list of f32 [C_i, n_i] (or [n_i]) tensors, on the host or on a
+        GPU; rates: their sample rates.  Returns (wavs, rms): wavs[i] is a 1-D view of resampled_length(n_i, rates[i]) samples
+        into one packed device buffer, which forward_ragged reads in place; rms is a device f32[B] tensor (the RMS of each mono
+        input) that nothing here reads back.  Host tensors go down in ONE concatenated copy; device tensors are read where they
+        are (non-contiguous ones are made contiguous first).  A rate whose filter bank would exceed 2^20 elements (e.g. 24001 Hz)
+        is refused: resample that prompt on the host (infer.sinc_resample)."""
+        audios = [a[None] if a.dim() == 1 else a for a in audios]
+        rates = [int(r) for r in rates]
+        if not audios:
+            raise ValueError("prepare_ragged: no audio")
+        if len(rates) != len(audios):
+            raise ValueError(f"prepare_ragged: {len(audios)} audios for {len(rates)} rates (need one rate per audio)")
+        if any(a.dim() != 2 for a in audios):
+            raise ValueError("prepare_ragged: every audio must be [channels, n] or [n]")
+        dev = self._ragged_device(audios, device, "prepare_ragged: the audios are on different devices")
+        shapes = [(int(a.shape[0]), int(a.shape[1])) for a in audios]
+        host = [i for i, a in enumerate(audios) if a.device.type != "cuda"]
+        audios = [a if a.device.type != "cuda" else a.to(torch.float32).contiguous() for a in audios]
+        if host:
+            down = torch.cat([audios[i].to(torch.float32).reshape(-1) for i in host]).to(dev)
+            for i, piece in zip(host, down.split([shapes[i][0] * shapes[i][1] for i in host])):
+                audios[i] = piece
+        base = min(a.data_ptr() for a in audios)
+        starts = [(a.data_ptr() - base) // 4 for a in audios]
+        lib = _lib.load()
+        B = len(audios)
+        n_arr, sr_arr = _lib.int_array([n for _, n in shapes]), _lib.int_array(rates)
+        lens, offs, total = (C.c_int64 * B)(), (C.c_int64 * B)(), C.c_int64()
+        _lib.check(lib.f5_mel_prepare_plan(B, n_arr, sr_arr, self.target_sample_rate, lens, offs, C.byref(total)), "f5_mel_prepare_plan")
+        h = self._handle(dev)
+        out = torch.empty(total.value, device=dev, dtype=torch.float32)
+        rms = torch.empty(B, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            self._resample_banks(lib, h, dev, rates)
+            _lib.check(lib.f5_mel_prepare_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), _lib.int_array([c for c, _ in shapes]),
+                                                 n_arr, sr_arr, self.target_sample_rate, float(target_rms), _ptr(out), total.value,
+                                                 _ptr(rms), _stream_ptr(dev)), "f5_mel_prepare_ragged")
+        return [out[o:o + n] for o, n in zip(offs, lens)], rms
+
+    def _resample_banks(self, lib, h, dev, rates):
+        """Hands the handle the bank of every rate it has not seen (once per rate pair and handle; the handle keeps them)."""
+        known = h.__dict__.setdefault("_banks", set())
+        for sr in sorted(set(rates) - known - {self.target_sample_rate}):
+            bank = _resample_bank_f32(sr, self.target_sample_rate)
+            _lib.check(lib.f5_mel_resample_bank(h, sr, self.target_sample_rate, C.c_void_p(bank.data_ptr()), bank.numel(), _stream_ptr(dev)),
+                       "f5_mel_resample_bank")
+            known.add(sr)
