@@ -309,6 +309,23 @@ int f5_bigvgan_finalize(f5_bigvgan* v, f5_stream stream);
 /* mel addressed as mel[b * stride_b + c * stride_c + t * stride_t] (element strides) -> wav f32[B, T * prod(rates)] */
 int f5_bigvgan_forward(f5_bigvgan* v, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_c,
                        int64_t stride_t, float* wav, f5_stream stream);
+/* A ragged batch in ONE pass (the contract of f5_vocos_decode_ragged): item b is frames [starts_host[b], ends_host[b]) of batch
+ * row b of mel, T_b = end - start >= 1.  wav[b * wav_stride + i], i < T_b * prod(rates), is bit-identical to f5_bigvgan_forward on
+ * that slice alone (B = 1) in both precisions, times gain_host[b] as a separate f32 multiply (x 1.0f without gains); +0.0 fills
+ * the row up to wav_stride.  Frames outside an item's window and other items' frames are never read.  The items share one packed
+ * time axis (f5_bigvgan_ragged_plan).  The host tables go down in one copy through a pinned slot and are free when
+ * the call returns; no synchronisation except when the workspace grows.  F5_EINVAL with nothing launched, the message naming the
+ * item: T_b < 1, start < 0, wav_stride below the longest waveform, B <= 0 or B > 65535 (the grid's y range), a null mel / ends_host /
+ * wav, more than 2^24 packed rows at the last stage (the GEMMs index rows as int).  F5_ESTATE before finalize. */
+int f5_bigvgan_forward_ragged(f5_bigvgan* v, const float* mel, int32_t B, int64_t stride_b, int64_t stride_c, int64_t stride_t,
+                              const int32_t* starts_host /* NULL: all 0 */, const int32_t* ends_host,
+                              const float* gain_host /* NULL: 1 */, float* wav, int64_t wav_stride, f5_stream stream);
+/* The packed axis of that call, pure host arithmetic (no HIP call): item b of frames_host[b] >= 1 frames starts at frame
+ * row_start_out[b] (B + 1 entries; [B] = the packed frame count) and is followed by at least *gap_frames_out dead frames, where
+ * gap * rates[0] >= the widest resblock convolution's reach max (k - 1) / 2 * d; starts are rounded up so that an item's first row
+ * at every stage is a multiple of 8 (the activation kernel's tile).  F5_EINVAL as above (null pointer, B, T_b < 1, 2^24 rows). */
+int f5_bigvgan_ragged_plan(const f5_bigvgan_config* cfg, int32_t B, const int32_t* frames_host, int32_t* row_start_out,
+                           int32_t* gap_frames_out);
 
 /* ------------------------------------------------------------------------------------- prompt mel front-end
  * MelSpec.forward, mel_spec_type="vocos" (model/modules.py:78-146): wav f32[B, nw] -> log-mel f32[B, T, n_mels],

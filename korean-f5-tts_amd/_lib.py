@@ -97,6 +97,9 @@ SIGNATURES = {
     "f5_bigvgan_load_weight": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),
     "f5_bigvgan_finalize": (_i, [_p, _p]),
     "f5_bigvgan_forward": (_i, [_p, _p, _i, _i, C.c_int64, C.c_int64, C.c_int64, _p, _p]),
+    "f5_bigvgan_forward_ragged": (_i, [_p, _p, _i, C.c_int64, C.c_int64, C.c_int64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f), _p,
+                                  C.c_int64, _p]),
+    "f5_bigvgan_ragged_plan": (_i, [C.POINTER(f5_bigvgan_config), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "f5_mel_create": (_i, [_i, _i, _i, C.POINTER(_p)]),
     "f5_mel_destroy": (_i, [_p]),
     "f5_mel_load": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),

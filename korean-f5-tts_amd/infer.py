@@ -10,7 +10,7 @@
   infer_batch_process / infer_process utils_infer.py:453-778    mono mix, RMS-to-0.1, duration formula, sample(),
                                                                  prompt slicing, fp32 vocoder input, rescale, cross-fade
   synthesize_batch                   eval_infer_batch.py:190-212 a ragged batch: sample(), then ONE vocoder pass over every
-                                                                 item's generated frames (Vocos.decode_ragged)
+                                                                 item's generated frames (Vocos.decode_ragged, or BigVGAN.ragged())
   synthesize_long                    utils_infer.py:711-775      the chunks of one long text as ragged batches (the reference hands them
                                                                  to a ThreadPoolExecutor): one prompt mel, one sample() and one
                                                                  decode_ragged per group of chunks, the cross-fade on the device
@@ -349,8 +349,8 @@ def _tokenise(model_obj, texts, text_tokenizer, stacklevel):
 
 def _require_ragged_vocoder(vocoder, who, hint):
     if not hasattr(vocoder, "decode_ragged"):
-        raise NotImplementedError(f"{who} decodes through Vocos.decode_ragged; {type(vocoder).__name__} has no ragged "
-                                  f"decode (BigVGAN: {hint})")
+        raise NotImplementedError(f"{who} decodes through vocoder.decode_ragged; {type(vocoder).__name__} has no ragged "
+                                  f"decode (BigVGAN: {hint}, or pass `vocoder.ragged()`)")
 
 
 def _progress(progress, iterable):
@@ -372,7 +372,7 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
       the RMS rescale `wave * rms / target_rms` on the packed rows, as the sequential path writes it;
       ONE f5_wave_crossfade over the rows of every group.
     Nothing is copied to the host: returns (wave f32[total], sample_rate, combined mel f32[100, T_total]), both on the device.
-    At most 64 chunks (ValueError); Vocos only (a vocoder without decode_ragged, e.g. BigVGAN: NotImplementedError).
+    At most 64 chunks (ValueError); a vocoder without decode_ragged: NotImplementedError (plain BigVGAN: pass `.ragged()`).
     prompt_on_device=True: the prompt's mono mix, RMS, gain and resampling run on the device (a B = 1
     `model_obj.mel_spec.prepare_ragged`) instead of normalise_prompt on the host; the frame arithmetic comes from
     mel.resampled_length and the rescale takes the device rms (rescale_to_prompt), so nothing is read back.
@@ -408,7 +408,7 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
         if prompt_on_device:
             wavs, rms_dev = model_obj.mel_spec.prepare_ragged([audio], [sr], target_rms, device=device)
             a, rms = wavs[0][None], rms_dev[0]
-        cond = model_obj.mel_spec(a.to(device)).permute(0, 2, 1)                # [1, T, 100], T = ref_len + 1 (centre padding)
+        cond = model_obj.mel_spec(a.to(device)).permute(0, 2, 1)                # [1, T, 100], T = ref_len + 1 (centre padding; bigvgan type: ref_len)
         cond_len = cond.shape[1]
         ends = clamp_durations(idx, torch.full((len(texts),), cond_len, dtype=torch.long), torch.tensor(durations)).tolist()
         groups = group_chunks(ends, batch_frames)
@@ -449,7 +449,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
       streaming=True   yields (wave[j : j + chunk_size], sample_rate) per chunk of every batch's waveform in turn, no cross-fade
                        (the socket server's mode, socket_server.py:138-177).
     `progress`: None or an object with `.tqdm(iterable)` (the reference passes the tqdm module).
-    batched=True (not a reference argument; Vocos only; not with streaming: ValueError) runs the text batches through
+    batched=True (not a reference argument; plain BigVGAN: pass `.ragged()`; not with streaming: ValueError) runs the text batches through
     `synthesize_long` -- ragged batches of at most `batch_frames` (rows x longest row; None: one batch), the cross-fade on the
     device -- and yields ONE item (wave.cpu().numpy(), sample_rate, spec.cpu().numpy()).  Two differences from batched=False,
     which is unchanged: the waveform is f32 (the sequential one is float64 wherever a cross-fade happened), and a chunk's mel
@@ -520,9 +520,9 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, **sample_kw):
     """The reference's batch loop (eval/eval_infer_batch.py:190-212) as one call: `model.sample(cond, text, duration, lens=lens,
     **sample_kw)`, then every item's generated frames [lens_i, duration_i) through the vocoder in ONE ragged pass
-    (Vocos.decode_ragged) instead of one decode per item.  `duration_i` are the clamped totals sample() ran at.
+    (vocoder.decode_ragged: Vocos, or `BigVGAN.ragged()`) instead of one decode per item.  `duration_i` are the clamped totals sample() ran at.
     Returns (wav f32[B, L_max], wav_lens, mel): wav[i, :wav_lens[i]] is item i's waveform (times gain[i] where given), zeros
-    behind it; mel is sample()'s output [B, N, 100], prompts included.  Vocos only."""
+    behind it; mel is sample()'s output [B, N, 100], prompts included.  Plain BigVGAN: pass `.ragged()`."""
     _require_ragged_vocoder(vocoder, "synthesize_batch", "decode item by item")
     if sample_kw.get("vocoder") is not None:
         raise TypeError("synthesize_batch: pass the vocoder as its second argument, not through sample()'s vocoder=")
@@ -578,7 +578,7 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
     prompt_on_device=True: the prompts are prepared on the device (prompt_batch), their rms stays there and the rescale selects
     with torch.where (rescale_to_prompt): no per-item host arithmetic on audio and no device-to-host read before the waveforms
     are returned.
-    Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Vocos only."""
+    Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Plain BigVGAN: pass `.ragged()`."""
     _require_text_tokenizer(model, text_tokenizer)
     _require_ragged_vocoder(vocoder, "synthesize_prompts", "decode item by item")
     prompts, gen_texts = list(prompts), list(gen_texts)
