@@ -15,6 +15,8 @@
  *   f5_vocos_decode_ragged <- the per-item vocoder loop of a batch   eval/eval_infer_batch.py:202-212
  *   f5_bigvgan_forward <- vocoder(mel) (third-party BigVGAN v2)      infer/utils_infer.py:138-152,705
  *   f5_wave_crossfade <- the cross-fade concatenation of the chunks  infer/utils_infer.py:734-775
+ *   f5_edit_assemble <- speech editing's mel_cond torch.cat chain    infer/speech_edit.py:157-195
+ *   f5_wave_splice   <- (no counterpart) the original recording outside the edited spans of speech_edit.py's output
  *   f5_mel_forward   <- MelSpec.forward (vocos / bigvgan type)       model/modules.py:33-146
  *   f5_mel_forward_ragged <- the per-prompt MelSpec loop + padded_mel_batch  eval/utils_eval.py:109-148
  *   f5_mel_prepare_ragged <- the per-prompt mono mix, RMS, level and resample  infer/utils_infer.py:523-533, eval/utils_eval.py:111-118
@@ -276,6 +278,47 @@ int f5_vocos_decode_ragged(f5_vocos* v, const float* mel, int32_t B, int64_t str
  * longest piece or out_cap < total. */
 int f5_wave_crossfade(const float* wav, int32_t B, int64_t wav_stride, const int32_t* lens_host, int32_t cross_fade_samples,
                       float* out, int64_t out_cap, int64_t* out_len_host, f5_stream stream);
+
+/* --------------------------------------------------------------------------------------------- speech editing
+ * The data movement around CFM.sample(edit_mask=...) for a batch of recordings (infer/speech_edit.py).  A recording's edited
+ * timeline is a list of segments (dst, src, frames) in mel frames, three int32 each, ascending and disjoint in dst:
+ *   KEEP  src >= 0: frames [dst, dst + frames) of the result are frames [src, src + frames) of the original;
+ *   EDIT  src = -1: frames [dst, dst + frames) are zero frames that sample() fills in.
+ * Both calls read the tables of all items from host arrays (seg_count_host[b] segments for item b, packed one item after the other
+ * in segs_host), check them, and stage them for the kernel in a pinned slot of a per-device ring: ONE launch and one small
+ * host-to-device copy on `stream`, no synchronisation (a slot is waited for only when the call eight calls ago has not run yet),
+ * every host array free when the call returns; not capturable into a graph.  At most 64 items of at most 33 segments.
+ * F5_EINVAL, with nothing launched or staged and a message that starts with the function's name: a null pointer, B outside 1..64,
+ * a segment with frames < 1, with dst inside or before the segment in front of it, with a source range that leaves [0, T_b)
+ * (f5_wave_splice: src < 0), or with a destination range that leaves [0, D_b), D_b <= D_max (f5_wave_splice clips instead, below).
+ *
+ * f5_edit_assemble: cond f32 [B, D_max, row] (contiguous) from the packed original mels, item b at mel + b * mel_stride with
+ * frames_host[b] = T_b rows of `row` elements (T_b * row <= mel_stride).  Every output frame d of item b is
+ *   a bit copy of source frame src + (d - dst) where a KEEP segment covers d,  +0.0 in every element otherwise
+ * (an EDIT segment, a frame no segment covers, a frame at or behind dur_host[b] = D_b).  16-byte loads and stores when row and
+ * mel_stride are multiples of 4 and both bases are 16-byte aligned, element-wise otherwise; the same bits either way. */
+int f5_edit_assemble(const float* mel, int32_t B, int64_t mel_stride, int32_t row, const int32_t* frames_host,
+                     const int32_t* seg_count_host, const int32_t* segs_host, const int32_t* dur_host, float* cond, int32_t D_max,
+                     f5_stream stream);
+
+/* f5_wave_splice: out row b (out + b * out_stride, out_stride samples, all written) from the decoded waveform g = gen + b * gen_stride
+ * (L = len_host[b] samples, L <= gen_stride and L <= out_stride), the prepared original a = a_base + a_start_host[b]
+ * (n = a_len_host[b] samples at the model's rate) and the item's KEEP segments only.  Contract, in exact integers:
+ *   a KEEP segment (dst, src, frames) claims out[p0, p1):  p0 = dst * hop,  p1 = min((dst + frames) * hop, L, p0 + n - src * hop);
+ *   the source sample of p is q = src * hop + (p - p0); a segment with p1 <= p0 is dropped;
+ *   m = min(cross_fade_samples, (p1 - p0) / 2) (integer division); the head fades in over its first m samples if p0 > 0, the tail
+ *   fades out over its last m samples if p1 < L; at a fading position j = p - p0 (head) or j = p1 - 1 - p (tail)
+ *       out[p] = (float)((double)g[p] * fo + (double)a[q] * fi)
+ *   with f5_wave_crossfade's restatement of linspace(0, 1, m) and linspace(1, 0, m): m == 1: fi = 0, fo = 1; j == m - 1: fi = 1,
+ *   fo = 0; otherwise fi = j * step + 0.0, fo = j * (-step) + 1.0, step = 1.0 / (m - 1) computed on the host; multiplies and
+ *   adds are separate IEEE double operations;
+ *   every other claimed sample is a[q] bit for bit, every unclaimed sample of [0, L) is g[p] bit for bit, every sample of the row
+ *   at or behind L is +0.0.
+ * Nothing outside [0, L) of g or [0, n) of a is read.  Each sample is written by one thread (deterministic); a 16-byte store where
+ * the address allows, else per element.  1 <= hop <= 65536, cross_fade_samples >= 0. */
+int f5_wave_splice(const float* gen, int32_t B, int64_t gen_stride, const int32_t* len_host, const float* a_base,
+                   const int64_t* a_start_host, const int32_t* a_len_host, const int32_t* seg_count_host, const int32_t* segs_host,
+                   int32_t hop, int32_t cross_fade_samples, float* out, int64_t out_stride, f5_stream stream);
 
 /* ---------------------------------------------------------------------------------------------- BigVGAN
  * The vocoder of mel_spec_type="bigvgan" (infer/utils_infer.py:138-152: bigvgan.BigVGAN.from_pretrained(

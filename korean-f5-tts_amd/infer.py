@@ -22,8 +22,12 @@
                                                                  `prompt_on_device=True` (prompt_batch, synthesize_prompts,
                                                                  synthesize_long) together with the mono mix, the RMS and the gain
                                                                  in ONE pass on the device (MelSpec.prepare_ragged)
+  edit_plan / speech_edit            speech_edit.py:137-232      re-speak spans of recordings: the frame arithmetic on the host (edit.py), ONE
+  wave_splice                        (no reference counterpart)  ragged mel pass, ONE f5_edit_assemble for the batch's conditioning, per
+                                                                 group one sample(edit_mask=...) and one ragged decode; `splice=True`:
+                                                                 the original samples outside the edited spans (f5_wave_splice)
 
-Out of scope here: pydub silence clipping, Whisper ASR, resampling of the OUTPUT, pinyin /
+Out of scope here: pydub silence clipping, Whisper ASR, forced alignment, resampling of the OUTPUT, pinyin /
 Korean G2P tokenisers (text is tokenised per character through `vocab_char_map`, or as utf-8 bytes when the model has no
 vocabulary, exactly as CFM.sample does for list[str]).
 Only checkpoints are loaded with loaders that execute nothing from the file (safetensors, torch.load(weights_only=True)).
@@ -37,6 +41,7 @@ import torch
 
 from .cfm import CFM, clamp_durations
 from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
+from .edit import edit_mask, edit_plan, segment_table  # noqa: F401  (edit_plan / edit_mask are part of this module's surface)
 from .mel import resample_kernel, resampled_length
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
@@ -604,6 +609,109 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
             for b, k in enumerate(run):
                 waves.append(rescale_to_prompt(wav[b, :wav_lens[b]], rms[k], target_rms))
                 mels.append(mel[b, lens[k]:ends[k]].to(torch.float32).permute(1, 0))
+        return waves, target_sample_rate, mels
+
+
+def wave_splice(wav: torch.Tensor, wav_lens, originals, plans, cross_fade_samples: int, hop: int = hop_length) -> torch.Tensor:
+    """The original recording outside the edited spans (f5_wave_splice; the contract is in include/f5_hip.h): wav f32 [B, stride]
+    on a GPU with item b in wav[b, :wav_lens[b]] (decode_ragged's return), originals the prepared recordings as 1-D f32 device
+    tensors at the model's rate (normalise_prompt / prepare_ragged; read where they are), plans edit_plan's return per item.
+    Every KEEP segment's samples become the original's, cross-faded linearly over min(cross_fade_samples, half the segment)
+    samples at each end that is not an end of the waveform; everything else is wav's, +0.0 behind wav_lens[b].  Returns a new
+    tensor of wav's shape.  One launch, no synchronisation; at most 64 items."""
+    import ctypes as C
+
+    from . import _lib
+    from ._lib import _ptr, _stream_ptr
+
+    if wav.device.type != "cuda":
+        raise RuntimeError("the HIP waveform splice only runs on a GPU (there is no CPU path)")
+    B = wav.shape[0] if wav.dim() == 2 else -1
+    wav_lens, originals, plans = [int(n) for n in wav_lens], list(originals), list(plans)
+    if B < 0 or wav.dtype != torch.float32 or wav.stride(1) != 1 or not len(wav_lens) == len(originals) == len(plans) == B:
+        raise ValueError("wave_splice: wav must be f32 [B, stride] with unit element stride, with one length, one original and one "
+                         "plan per row")
+    if any(a.dim() != 1 or a.device != wav.device for a in originals):
+        raise ValueError("wave_splice: every original must be a 1-D tensor on wav's device")
+    originals = [a if a.dtype == torch.float32 and a.stride(0) == 1 else a.to(torch.float32).contiguous() for a in originals]
+    base = min(a.data_ptr() for a in originals)
+    starts = [(a.data_ptr() - base) // 4 for a in originals]
+    counts, flat = segment_table(plans, keep_only=True)
+    out = torch.empty(wav.shape, device=wav.device, dtype=torch.float32)
+    with torch.cuda.device(wav.device):
+        _lib.check(_lib.load().f5_wave_splice(_ptr(wav), B, wav.stride(0), _lib.int_array(wav_lens), C.c_void_p(base),
+                                              (C.c_int64 * B)(*starts), _lib.int_array([a.shape[0] for a in originals]),
+                                              _lib.int_array(counts), _lib.int_array(flat or [0]), int(hop), int(cross_fade_samples),
+                                              _ptr(out), out.stride(0), _stream_ptr(wav.device)), "f5_wave_splice")
+    return out
+
+
+def speech_edit(model, vocoder, items, *, target_rms=target_rms, nfe_step=nfe_step, cfg_strength=cfg_strength,
+                sway_sampling_coef=sway_sampling_coef, seed=None, text_tokenizer=None, batch_frames=None, prompt_on_device=False,
+                splice=False, splice_cross_fade=0.01, **sample_kw):
+    """The reference's speech editing script (infer/speech_edit.py) for a batch of recordings: items is a list of
+    (audio [C, n], sample_rate, target_text, parts_to_edit, fix_duration | None) -- the whole sentence the recording should say
+    instead, the spans to replace as (start, end) in seconds, and optionally the new length of each span.  Finding the spans
+    (forced alignment) is the caller's business.
+      every recording prepared as the script does (normalise_prompt per item on the host; prompt_on_device=True: ONE
+      `mel_spec.prepare_ragged`, the rms stays on the device), and down in one copy;
+      ONE `mel_spec.forward_ragged` over all of them, edit_plan per item on the host, ONE `mel_spec.edit_assemble`;
+      per group of items (group_chunks over the totals sample() runs at, `batch_frames` = the budget of rows x longest row; None:
+      groups of up to 64) ONE `model.sample(cond, text, duration=D, lens=D, edit_mask=mask)`, ONE `vocoder.decode_ragged` over
+      frames [0, ends_i) of every item and, with splice=True, ONE `wave_splice`: the samples of every kept span are the prepared
+      original's, cross-faded over splice_cross_fade seconds at the inner boundaries (0.01 s = 240 samples; a chosen value);
+      then the rescale `wave * rms / target_rms` where the recording was levelled up (rescale_to_prompt).
+    ends_i are the totals sample() ran at (clamp_durations): at least D_i + 1 -- the rule `max(text, lens) + 1` gives one
+    generated frame behind the recording, and it is decoded, as in the script.
+    Returns (waves: a list of 1-D f32 device tensors, sample_rate, mels: a list of [100, ends_i]); nothing is copied to the host.
+    A vocoder without decode_ragged: NotImplementedError (plain BigVGAN: pass `.ragged()`).
+
+    Text: tokenised as the other drivers do (per character through the model's vocabulary, utf-8 bytes without one, or
+    `text_tokenizer`).  The script's `final_text_list = [text_list]` nesting for non-pinyin tokenisers makes the whole sentence
+    ONE token; that is not reproduced here.
+    As in every batch driver, an item in a batch equals the item run alone only where items cannot see each other's padding:
+    with `attn_mask_enabled=True` the backbone runs the valid rows only and every item equals the item run alone; with
+    `attn_mask_enabled=False` (the shipped configs) a shorter item attends over the padded frames up to the group's longest,
+    as in the reference's own batch driver (eval/eval_infer_batch.py, cfm.py:155-158)."""
+    _require_text_tokenizer(model, text_tokenizer)
+    _require_ragged_vocoder(vocoder, "speech_edit", "decode item by item")
+    items = list(items)
+    if not items:
+        raise ValueError("speech_edit: no recording to edit")
+    for key in ("edit_mask", "lens", "steps", "vocoder"):
+        if key in sample_kw:
+            raise TypeError(f"speech_edit: {key}= is set by the driver, not through sample()'s keywords")
+    device, ms = model.device, model.mel_spec
+    with torch.inference_mode():
+        if prompt_on_device:
+            audios, rms = ms.prepare_ragged([it[0] for it in items], [it[1] for it in items], target_rms, device=device)
+        else:
+            host, rms = [], []
+            for audio, sr, *_ in items:
+                a, r = normalise_prompt(audio, sr, target_rms)
+                host.append(a.reshape(-1).to(torch.float32))
+                rms.append(r)
+            audios = list(torch.cat(host).to(device).split([a.shape[0] for a in host]))     # ONE copy; the splice reads them too
+        mel, frames = ms.forward_ragged(audios, device=device)
+        plans = [edit_plan(n, it[3], it[4], sample_rate=target_sample_rate, hop_length=hop_length) for n, it in zip(frames, items)]
+        cond, mask, D = ms.edit_assemble(mel, frames, plans)
+        texts, idx = _tokenise(model, [it[2] for it in items], text_tokenizer, stacklevel=3)
+        ends = clamp_durations(idx.to("cpu", torch.long), torch.tensor(D), torch.tensor(D), sample_kw.get("max_duration", 65536)).tolist()
+        cf = int(splice_cross_fade * target_sample_rate) if splice_cross_fade > 0 else 0
+        waves, mels = [], []
+        for run in group_chunks(ends, batch_frames):
+            gD = [D[k] for k in run]
+            generated, _ = model.sample(cond=cond[run.start:run.stop, :max(gD)].contiguous(), text=[texts[k] for k in run],
+                                        duration=torch.tensor(gD), lens=torch.tensor(gD), steps=nfe_step, cfg_strength=cfg_strength,
+                                        sway_sampling_coef=sway_sampling_coef, seed=seed,
+                                        edit_mask=mask[run.start:run.stop, :max(gD)], **sample_kw)
+            generated = generated.to(torch.float32)
+            wav, wav_lens = vocoder.decode_ragged(generated.permute(0, 2, 1), ends=[ends[k] for k in run])
+            if splice:
+                wav = wave_splice(wav, wav_lens, [audios[k] for k in run], [plans[k] for k in run], cf)
+            for b, k in enumerate(run):
+                waves.append(rescale_to_prompt(wav[b, :wav_lens[b]], rms[k], target_rms))
+                mels.append(generated[b, :ends[k]].permute(1, 0))
         return waves, target_sample_rate, mels
 
 

@@ -249,6 +249,41 @@ class MelSpec(NativeModule):
                                                  _ptr(rms), _stream_ptr(dev)), "f5_mel_prepare_ragged")
         return [out[o:o + n] for o, n in zip(offs, lens)], rms
 
+    @torch.no_grad()
+    def edit_assemble(self, mel, frames, plans):
+        """The conditioning of speech editing for a batch in one launch (f5_edit_assemble; the reference's torch.cat chain per
+        recording, infer/speech_edit.py:157-195).  mel: the original log-mels f32 [B, n_mels, T_max] as `forward_ragged` (or
+        `forward`) returns them -- the permuted view, whose storage [B, T_max, n_mels] is read in place; any other layout is copied
+        first; frames: T_i per item; plans: edit.edit_plan's return per item.  Returns (cond f32 [B, D_max, n_mels] -- KEEP frames
+        are bit copies of their source frames, EDIT frames and the frames behind D_i are +0.0 --, edit_mask bool [B, D_max] on
+        the host (True = keep; built there because CFM.sample reads it there), [D_i])."""
+        from .edit import MAX_ITEMS, edit_mask, segment_table
+
+        plans = list(plans)
+        frames = [int(t) for t in frames]
+        if mel.device.type != "cuda":
+            raise RuntimeError(self._no_cpu)
+        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError(f"edit_assemble: mel must be [B, {self.n_mel_channels}, T]")
+        B, row, T_max = mel.shape
+        if not 1 <= B <= MAX_ITEMS:
+            raise ValueError(f"edit_assemble: {B} recordings; one call takes 1 to {MAX_ITEMS}")
+        if len(frames) != B or len(plans) != B:
+            raise ValueError(f"edit_assemble: {len(frames)} frame counts and {len(plans)} plans for {B} recordings")
+        if any(t > T_max for t in frames):
+            raise ValueError(f"edit_assemble: frames {frames} exceed the mel's {T_max} columns")
+        rows = mel.permute(0, 2, 1)                                            # [B, T_max, n_mels]
+        if rows.dtype != torch.float32 or rows.stride(2) != 1 or rows.stride(1) != row or (B > 1 and rows.stride(0) < T_max * row):
+            rows = rows.to(torch.float32).contiguous()
+        D = [int(d) for _, d in plans]
+        counts, flat = segment_table(plans)
+        cond = torch.empty(B, max(D), row, device=mel.device, dtype=torch.float32)
+        with torch.cuda.device(mel.device):
+            _lib.check(_lib.load().f5_edit_assemble(_ptr(rows), B, rows.stride(0) if B > 1 else T_max * row, row, _lib.int_array(frames),
+                                                    _lib.int_array(counts), _lib.int_array(flat or [0]), _lib.int_array(D), _ptr(cond),
+                                                    max(D), _stream_ptr(mel.device)), "f5_edit_assemble")
+        return cond, edit_mask(plans), D
+
     def _resample_banks(self, lib, h, dev, rates):
         """Hands the handle the bank of every rate it has not seen (once per rate pair and handle; the handle keeps them)."""
         known = h.__dict__.setdefault("_banks", set())
