@@ -444,6 +444,57 @@ int f5_mel_prepare_ragged(f5_mel* m, const float* base, int32_t B, const int64_t
                           const int32_t* n_host, const int32_t* sr_host, int32_t target_sr, float target_rms, float* out,
                           int64_t out_capacity, float* rms_out, f5_stream stream);
 
+/* ------------------------------------------------------------------------------------- silence clipping
+ * What the reference drivers do to every prompt before anything else sees it (infer/utils_infer.py:348-361, 385-419: cut at pauses
+ * to at most 12 s, trim the silent edges, append 50 ms of silence) and, on request, to the result (:784-793, remove_silence), both
+ * through pydub on 16-bit samples.  The decisions are restated here as exact integer arithmetic; the range logic on top of the
+ * flags is host arithmetic (silence.py).  Item b has C channels of F frames at R Hz, laid out [C, F] row-major from
+ * base[start_host[b]], f32 (the layout of f5_mel_prepare_ragged).  The arithmetic contract:
+ *   16-bit view   q = clamp((int)rintf(x * qscale), -32768, 32767): an f32 multiply, round to nearest even; NaN gives 0.
+ *                 qscale = 32768 for prompts (the inverse of how a 16-bit file is loaded: exact for such files), 32767 for generated
+ *                 waves (libsndfile's float -> PCM_16 rule).
+ *   grid          pos(ms) = (R * ms) / 1000 in integers.  L = round(1000 * (F / R)) with Python's round on that double expression,
+ *                 computed by the caller (len_ms_host).  The analysis sees frames [0, pos(L)); frames at or past F read as 0 (pydub
+ *                 pads a slice's missing frames with silence); frames at or past pos(L) are never read.
+ *   energy        E(a, b) = sum of q^2 over all channels and frames [pos(a), pos(b)), in int64 (exact);
+ *                 cnt(a, b) = C * (pos(b) - pos(a)).  A window is silent at the integer threshold T iff E(a, b) < cnt(a, b) * (T + 1)^2,
+ *                 which is audioop.rms(window) <= T (rms 0 included).  T comes from the caller: floor(10^(dB / 20) * 32768) for
+ *                 detect_silence (-50 dB: 103, -40 dB: 327), the largest r with 20 * log10(r / 32768) < dB for the edge trim (-42 dB: 260).
+ *   query         (W, s, T, kind), W and s in ms, four int32 each in queries_host.  kind 0 (detect_silence): no start if L < W, else
+ *                 the starts 0, s, 2 s, ... <= L - W, and L - W itself behind them if (L - W) % s != 0; the window is [a, a + W).
+ *                 kind 1 (chunk grid): the starts 0, s, ... < L, the window [a, min(a + W, L)) (W = s = 10: detect_leading_silence;
+ *                 W = s = 1: the per-millisecond loop of remove_silence_edges).  One byte per start: 1 = silent.
+ *   segments      (dst, src, frames) triples in frames, ascending and disjoint in dst: frames [dst, dst + frames) of the signal are
+ *                 frames [src, src + frames) of the item; a source frame at or past F reads as 0, and so does every frame of the
+ *                 signal that no segment covers.
+ *   gather        out frame j of channel c = (float)q / 32768.0f of its source frame, +0.0 where that is at or past F or where no
+ *                 segment covers j; item b's output is [C, F_out] row-major from out[out_start_host[b]].  Nothing outside
+ *                 [0, C * F_out) of an item is written; one thread writes each sample.
+ * f5_silence_plan is the flag layout as pure host arithmetic (no HIP call): count_out[b * nq + k] flags of item b and query k start
+ * at start_out[b * nq + k] of the packed flag buffer, *total_out flags in all.
+ * f5_silence_analyse writes exactly those flags for a ragged batch: per-millisecond energies (the only launch that reads the
+ * audio), the exclusive prefix per item as a plain three-phase scan (tile sums inside the energy launch, a scan of the tile sums,
+ * an apply launch), and one flag launch for every query: four launches, one table copy through a pinned slot, no host read and no
+ * synchronisation except the growth of the per-device workspace.  No atomics: integer sums are exact in any order, so an item's
+ * flags are the same alone and in a batch.  seg_count_host != NULL: item b is read through its seg_count_host[b] segments (segs_host
+ * holds every item's triples one after the other) -- the signal is then the concatenation the table describes, not materialised.
+ * f5_wave_gather is the gather for the batch in one launch (16-byte stores where the destination is aligned).
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the item: a null pointer, B < 1 or B > 65535,
+ * nq < 1 or nq > 8, W or s outside [1, 2^24], T outside [0, 32767], kind not 0 or 1, L < 0 or L > 2^24, start_b < 0, C < 1, F < 1,
+ * C * F >= 2^31, R < 11025 or R > 384000 (below 11025 Hz pydub would resample the prompt up to its silent segments' rate: not
+ * built), qscale outside (0, 32768], more than 2^30 milliseconds in one call, a segment with frames < 1, src < 0, a dst inside or
+ * before the segment in front of it or (gather) an end past F_out, F_out < 0, an output range outside out_capacity,
+ * flags_capacity below the plan's total. */
+int f5_silence_plan(int32_t B, const int32_t* len_ms_host, int32_t nq, const int32_t* queries_host, int32_t* count_out,
+                    int64_t* start_out, int64_t* total_out);
+int f5_silence_analyse(const float* base, int32_t B, const int64_t* start_host, const int32_t* channels_host,
+                       const int32_t* frames_host, const int32_t* rate_host, const int32_t* len_ms_host, float qscale, int32_t nq,
+                       const int32_t* queries_host, const int32_t* seg_count_host, const int32_t* segs_host, uint8_t* flags,
+                       int64_t flags_capacity, f5_stream stream);
+int f5_wave_gather(const float* base, int32_t B, const int64_t* start_host, const int32_t* channels_host, const int32_t* frames_host,
+                   float qscale, const int32_t* seg_count_host, const int32_t* segs_host, const int32_t* out_frames_host,
+                   const int64_t* out_start_host, float* out, int64_t out_capacity, f5_stream stream);
+
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */

@@ -95,6 +95,11 @@ SIGNATURES = {
     "f5_edit_assemble": (_i, [_p, _i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, _i, _p]),
     "f5_wave_splice": (_i, [_p, _i, C.c_int64, C.POINTER(_i), _p, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                         _i, _i, _p, C.c_int64, _p]),
+    "f5_silence_plan": (_i, [_i, C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "f5_silence_analyse": (_i, [_p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _f, _i,
+                                C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, C.c_int64, _p]),
+    "f5_wave_gather": (_i, [_p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), _f, C.POINTER(_i), C.POINTER(_i),
+                            C.POINTER(_i), C.POINTER(C.c_int64), _p, C.c_int64, _p]),
     "f5_bigvgan_create": (_i, [C.POINTER(f5_bigvgan_config), C.POINTER(_p)]),
     "f5_bigvgan_destroy": (_i, [_p]),
     "f5_bigvgan_load_weight": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),

@@ -27,7 +27,14 @@
                                                                  group one sample(edit_mask=...) and one ragged decode; `splice=True`:
                                                                  the original samples outside the edited spans (f5_wave_splice)
 
-Out of scope here: pydub silence clipping, Whisper ASR, forced alignment, resampling of the OUTPUT, pinyin /
+  clip_prompts                       utils_infer.py:348-361,385-419 the prompt clip of preprocess_ref_audio_text (cut at pauses to at most
+                                                                 12 s, trim the silent edges, append 50 ms of silence) for a ragged batch
+                                                                 on the device (f5_silence_analyse, f5_wave_gather; the ranges on the
+                                                                 host, silence.py); `clip_silence=True` of the prompt_on_device drivers
+  remove_silence                     utils_infer.py:784-793      pauses of 1 s or more cut out of generated waveforms, on the device;
+                                                                 `remove_silence=True` of synthesize_prompts and the batched infer_process
+
+Out of scope here: Whisper ASR (an empty ref_text), forced alignment, resampling of the OUTPUT, pinyin /
 Korean G2P tokenisers (text is tokenised per character through `vocab_char_map`, or as utf-8 bytes when the model has no
 vocabulary, exactly as CFM.sample does for list[str]).
 Only checkpoints are loaded with loaders that execute nothing from the file (safetensors, torch.load(weights_only=True)).
@@ -41,6 +48,7 @@ import torch
 
 from .cfm import CFM, clamp_durations
 from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
+from . import silence as _silence
 from .edit import edit_mask, edit_plan, segment_table  # noqa: F401  (edit_plan / edit_mask are part of this module's surface)
 from .mel import resample_kernel, resampled_length
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
@@ -321,6 +329,190 @@ def wave_crossfade(wav: torch.Tensor, lens: list[int], cross_fade_samples: int) 
     return out
 
 
+def _device_items(audios, device, who):
+    """A list of [C_i, F_i] (or [F_i]) tensors as contiguous f32 device tensors: host tensors go down in ONE concatenated copy,
+    device tensors stay where they are.  Returns (tensors, [(C_i, F_i)], device)."""
+    audios = [a[None] if a.dim() == 1 else a for a in audios]
+    if not audios:
+        raise ValueError(f"{who}: no audio")
+    if any(a.dim() != 2 or a.shape[0] < 1 or a.shape[1] < 1 for a in audios):
+        raise ValueError(f"{who}: every audio must be [channels, frames] (or [frames]) with at least one frame")
+    on_gpu = [a.device for a in audios if a.device.type == "cuda"]
+    if device is not None:
+        dev = torch.device(device)
+    elif on_gpu:
+        dev = on_gpu[0]
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who} only runs on a GPU (there is no CPU path)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if any(d != dev for d in on_gpu):
+        raise ValueError(f"{who}: the audios are on different devices")
+    shapes = [(int(a.shape[0]), int(a.shape[1])) for a in audios]
+    host = [i for i, a in enumerate(audios) if a.device.type != "cuda"]
+    audios = [a if a.device.type != "cuda" else a.to(torch.float32).contiguous() for a in audios]
+    if host:
+        down = torch.cat([audios[i].to(torch.float32).reshape(-1) for i in host]).to(dev)
+        for i, piece in zip(host, down.split([shapes[i][0] * shapes[i][1] for i in host])):
+            audios[i] = piece
+    return audios, shapes, dev
+
+
+def _flat_tables(tables):
+    import ctypes as C
+
+    flat = [int(v) for t in tables for seg in t for v in seg]
+    return (C.c_int32 * len(tables))(*[len(t) for t in tables]), (C.c_int32 * max(len(flat), 1))(*flat)
+
+
+def silence_flags(items, shapes, rates, lens_ms, queries, qscale, tables=None):
+    """One f5_silence_analyse over a ragged batch and ONE small device-to-host read: items are contiguous f32 device tensors
+    holding [C_i, F_i] = shapes[i], lens_ms the length in ms of each analysed signal, queries (W, s, T, kind) tuples
+    (include/f5_hip.h), tables per item the (dst, src, frames) segments the item is read through (None: as it lies).
+    Returns flags[i][k]: a uint8 numpy array per item and query."""
+    import ctypes as C
+
+    from . import _lib
+    from ._lib import _ptr, _stream_ptr
+
+    lib, B, nq, dev = _lib.load(), len(items), len(queries), items[0].device
+    base = min(a.data_ptr() for a in items)
+    starts = (C.c_int64 * B)(*[(a.data_ptr() - base) // 4 for a in items])
+    q_arr = _lib.int_array([v for q in queries for v in q])
+    len_arr = _lib.int_array(lens_ms)
+    counts, offs, total = (C.c_int32 * (B * nq))(), (C.c_int64 * (B * nq))(), C.c_int64()
+    _lib.check(lib.f5_silence_plan(B, len_arr, nq, q_arr, counts, offs, C.byref(total)), "f5_silence_plan")
+    flags = torch.empty(max(total.value, 1), device=dev, dtype=torch.uint8)
+    seg_counts, seg_flat = _flat_tables(tables) if tables is not None else (None, None)
+    with torch.cuda.device(dev):
+        _lib.check(lib.f5_silence_analyse(C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
+                                          _lib.int_array([f for _, f in shapes]), _lib.int_array(rates), len_arr, float(qscale), nq, q_arr,
+                                          seg_counts, seg_flat, _ptr(flags), total.value, _stream_ptr(dev)), "f5_silence_analyse")
+    host = flags.cpu().numpy()
+    return [[host[offs[b * nq + k]:offs[b * nq + k] + counts[b * nq + k]] for k in range(nq)] for b in range(B)]
+
+
+def wave_gather(items, shapes, tables, out_frames, qscale):
+    """One f5_wave_gather: item i read through tables[i] into [C_i, out_frames[i]] of one packed device buffer (every item starts
+    on a 16-byte multiple).  Returns the views."""
+    import ctypes as C
+
+    from . import _lib
+    from ._lib import _ptr, _stream_ptr
+
+    B, dev = len(items), items[0].device
+    base = min(a.data_ptr() for a in items)
+    starts = (C.c_int64 * B)(*[(a.data_ptr() - base) // 4 for a in items])
+    offs, run = [], 0
+    for (c, _), n in zip(shapes, out_frames):
+        run = (run + 3) // 4 * 4
+        offs.append(run)
+        run += c * n
+    out = torch.empty(max(run, 1), device=dev, dtype=torch.float32)
+    seg_counts, seg_flat = _flat_tables(tables)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_wave_gather(C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
+                                              _lib.int_array([f for _, f in shapes]), float(qscale), seg_counts, seg_flat,
+                                              _lib.int_array(out_frames), (C.c_int64 * B)(*offs), _ptr(out), run, _stream_ptr(dev)),
+                   "f5_wave_gather")
+    return [out[o:o + c * n].view(c, n) for o, (c, _), n in zip(offs, shapes, out_frames)]
+
+
+def _check_rates(who, rates, count):
+    rates = [int(r) for r in rates]
+    if len(rates) != count:
+        raise ValueError(f"{who}: {count} audios for {len(rates)} rates (need one rate per audio)")
+    for r in rates:
+        if not _silence.MIN_RATE <= r <= _silence.MAX_RATE:
+            raise ValueError(f"{who}: a rate of {r} Hz; silence clipping takes {_silence.MIN_RATE} to {_silence.MAX_RATE} Hz (below "
+                             "11025 Hz pydub would resample the prompt up: clip such a prompt yourself)")
+    return rates
+
+
+def clip_prompts(audios, rates, device=None):
+    """What preprocess_ref_audio_text does to a prompt's audio before anything else sees it (utils_infer.py:385-419), for a batch:
+    cut at pauses to at most 12 s (split_on_silence at 1000 ms / -50 dB, then at 100 ms / -40 dB, then a hard cut), trim the
+    silent edges (remove_silence_edges at -42 dB) and append 50 ms of silence.  audios: a list of f32 [C_i, F_i] (or [F_i])
+    tensors, on the host or on a GPU; rates: their sample rates, 11025 to 384000 Hz.  Returns (clipped, frames): clipped[i] is a
+    [C_i, frames[i]] view into one packed device buffer, which MelSpec.prepare_ragged reads in place; every sample is the
+    16-bit value pydub would hold, q / 32768 (q = round-to-even of x * 32768, clamped).
+    Per batch: ONE f5_silence_analyse and one small read of its flags, the ranges on the host (silence.py), ONE analyse of the
+    clipped signals through their segment tables (they are not materialised) and one small read, ONE f5_wave_gather.  Prompts
+    whose rate is no multiple of 100 Hz and that lose leading silence need their trailing milliseconds on a shifted grid: one
+    more analyse over just those.  Each item's result is bit for bit what it gives alone.
+    A prompt without any sound comes out as the 50 ms of silence alone, at its own rate and channel count (the reference's is
+    551 frames of 11025 Hz mono)."""
+    S = _silence
+    items, shapes, dev = _device_items(list(audios), device, "clip_prompts")
+    rates = _check_rates("clip_prompts", rates, len(items))
+    B = len(items)
+    lens = [S.ms_len(f, r) for (_, f), r in zip(shapes, rates)]
+    first = silence_flags(items, shapes, rates, lens, S.CLIP_QUERIES, S.PROMPT_QSCALE)
+    signals = [S.prompt_clip_plan(first[b][0], first[b][1], shapes[b][1], rates[b])[0] for b in range(B)]
+    sig_ms = [S.ms_len(S.signal_frames(p), r) for p, r in zip(signals, rates)]
+    edges = silence_flags(items, shapes, rates, sig_ms, S.EDGE_QUERIES, S.PROMPT_QSCALE, [S.segment_table(p) for p in signals])
+    rests, ms_flags, shifted = [], [None] * B, []
+    for b in range(B):
+        lead = S.leading_trim(edges[b][0], sig_ms[b])
+        rest, same_grid = S.after_lead(signals[b], rates[b], lead)
+        rests.append(rest)
+        if same_grid:
+            ms_flags[b] = edges[b][1][lead:]
+        else:
+            shifted.append(b)
+    if shifted:
+        again = silence_flags([items[b] for b in shifted], [shapes[b] for b in shifted], [rates[b] for b in shifted],
+                              [S.ms_len(S.signal_frames(rests[b]), rates[b]) for b in shifted], S.EDGE_QUERIES[1:], S.PROMPT_QSCALE,
+                              [S.segment_table(rests[b]) for b in shifted])
+        for b, fl in zip(shifted, again):
+            ms_flags[b] = fl[0]
+    tables, frames = [], []
+    for b in range(B):
+        keep = S.trailing_cut(ms_flags[b], S.signal_frames(rests[b]), rates[b])
+        pieces, n = S.finish_prompt(rests[b], keep, rates[b])
+        tables.append(S.segment_table(pieces))
+        frames.append(n)
+    return wave_gather(items, shapes, tables, frames, S.PROMPT_QSCALE), frames
+
+
+def remove_silence(wavs, lens=None):
+    """remove_silence_for_generated_wav (utils_infer.py:784-793; the CLI's and the Gradio app's `remove_silence`) for a batch of
+    generated waveforms at 24 kHz, on the device: pauses of 1 s or more at -50 dB are cut out, 500 ms kept around each stretch of
+    sound.  wavs: an f32 [B, stride] device tensor with item b in wavs[b, :lens[b]] (decode_ragged's return), or a list of 1-D f32
+    device tensors (lens: None).  Returns (a list of 1-D views into one packed device buffer, their lengths); every sample is
+    q / 32768 of its source sample, q = round-to-even of x * 32767, clamped (libsndfile's float -> PCM_16 rule; soundfile is not
+    installed, so that rule is unpinned).  A waveform without any sound comes out empty.  ONE f5_silence_analyse, one small read
+    of its flags, ONE f5_wave_gather."""
+    S = _silence
+    if isinstance(wavs, torch.Tensor):
+        if wavs.dim() != 2 or lens is None or len(lens) != wavs.shape[0]:
+            raise ValueError("remove_silence: wavs must be [B, stride] with one length per row, or a list of 1-D tensors")
+        wavs = [wavs[b, :int(n)] for b, n in enumerate(lens)]
+    wavs = list(wavs)
+    if any(w.dim() != 1 for w in wavs):
+        raise ValueError("remove_silence: every waveform must be 1-D")
+    if any(w.device.type != "cuda" for w in wavs):
+        raise RuntimeError("remove_silence only runs on a GPU (there is no CPU path)")
+    out, out_lens = [w[:0] for w in wavs], [0] * len(wavs)
+    live = [i for i, w in enumerate(wavs) if w.shape[0] > 0]
+    if not live:
+        return out, out_lens
+    items, shapes, _dev = _device_items([wavs[i] for i in live], None, "remove_silence")
+    rates = [target_sample_rate] * len(items)
+    flags = silence_flags(items, shapes, rates, [S.ms_len(f, target_sample_rate) for _, f in shapes], S.REMOVE_QUERIES, S.WAVE_QSCALE)
+    plans = [S.remove_silence_plan(flags[k][0], shapes[k][1], target_sample_rate) for k in range(len(items))]
+    frames = [S.signal_frames(p) for p in plans]
+    views = wave_gather(items, shapes, [S.segment_table(p) for p in plans], frames, S.WAVE_QSCALE)
+    for i, v, n in zip(live, views, frames):
+        out[i], out_lens[i] = v.reshape(-1), n
+    return out, out_lens
+
+
+_remove_pauses = remove_silence   # (the drivers below have a keyword of that name)
+
+
 def _require_text_tokenizer(model_obj, text_tokenizer):
     tok_type = getattr(model_obj, "_tokenizer_type", "custom")
     if text_tokenizer is None and isinstance(tok_type, str) and tok_type.startswith("kor_"):
@@ -366,7 +558,7 @@ def _progress(progress, iterable):
 def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *, mel_spec_type=mel_spec_type, progress=None,
                     target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                     sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
-                    text_tokenizer=None, batch_frames=None, prompt_on_device=False):
+                    text_tokenizer=None, batch_frames=None, prompt_on_device=False, clip_silence=False):
     """The chunks of one long text as ragged batches instead of one B = 1 pass each (the reference submits them to a
     ThreadPoolExecutor, utils_infer.py:725-732): the host arithmetic of infer_batch_process per chunk (prompt_numerics:
     local_speed, the duration formula, the trailing-space rule), then
@@ -381,6 +573,8 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
     prompt_on_device=True: the prompt's mono mix, RMS, gain and resampling run on the device (a B = 1
     `model_obj.mel_spec.prepare_ragged`) instead of normalise_prompt on the host; the frame arithmetic comes from
     mel.resampled_length and the rescale takes the device rms (rescale_to_prompt), so nothing is read back.
+    clip_silence=True (needs prompt_on_device=True: ValueError otherwise): the prompt goes through clip_prompts first, as the
+    reference's preprocess_ref_audio_text does; every length below is then the clipped prompt's.
 
     Against the sequential path (infer_batch_process, batched=False):
       * the waveform is f32; the sequential one is float64 wherever a cross-fade happened (numpy promotes).  The values are
@@ -399,6 +593,10 @@ def synthesize_long(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, *
                          "(split the text, or use the sequential path)")
     audio, sr = ref_audio
     device = device if device is not None else model_obj.device
+    if clip_silence:
+        if not prompt_on_device:
+            raise ValueError("synthesize_long: clip_silence=True needs prompt_on_device=True (the clip runs on the device)")
+        audio = clip_prompts([audio], [sr], device=device)[0][0]
     texts, durations = [], []
     for gen_text in gen_text_batches:
         if prompt_on_device:
@@ -446,7 +644,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                         progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
                         nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                         speed=speed, fix_duration=fix_duration, device=None, streaming=False, chunk_size=2048, seed=None,
-                        text_tokenizer=None, batched=False, batch_frames=None, prompt_on_device=False):
+                        text_tokenizer=None, batched=False, batch_frames=None, prompt_on_device=False, clip_silence=False,
+                        remove_silence=False):
     """A GENERATOR, as in the reference (utils_infer.py:504-522,711-778):
       streaming=False  yields ONE item (final_wave f32 numpy, sample_rate, combined mel [100, T_total]) -- the cross-faded
                        concatenation over the text batches; (None, sample_rate, None) when there is no batch
@@ -462,6 +661,9 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     shorter chunk attends over the batch's padded frames, as in the reference's batch driver (see synthesize_long).
     prompt_on_device=True (with batched=True only: ValueError otherwise; the sequential path prepares its prompt on the host)
     is handed to synthesize_long: the prompt is mixed, levelled and resampled on the device.
+    clip_silence=True (with prompt_on_device=True only: ValueError otherwise): the prompt is clipped first (clip_prompts).
+    remove_silence=True (with batched=True only: ValueError otherwise): pauses of 1 s or more are cut out of the finished
+    waveform on the device, behind the cross-fade, as the reference's CLI does to the file it wrote (remove_silence).
 
     Text front-end: the reference turns `ref_text + gen_text` into tokens per `model_obj._tokenizer_type` -- for the kor_*
     types through Korean G2P / jamo decomposition / allophone rules (utils_infer.py:549-660: g2pk and the repo's own rule
@@ -473,6 +675,10 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
         raise ValueError("infer_batch_process: batched=True yields one finished waveform; it cannot be combined with streaming=True")
     if prompt_on_device and not batched:
         raise ValueError("infer_batch_process: prompt_on_device=True needs batched=True (the sequential path prepares its prompt on the host)")
+    if clip_silence and not prompt_on_device:
+        raise ValueError("infer_batch_process: clip_silence=True needs prompt_on_device=True (the clip runs on the device)")
+    if remove_silence and not batched:
+        raise ValueError("infer_batch_process: remove_silence=True needs batched=True (it runs on the device, behind the cross-fade)")
     audio, sr = ref_audio
     device = device if device is not None else model_obj.device
     _require_text_tokenizer(model_obj, text_tokenizer)
@@ -485,7 +691,9 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
             (audio, sr), ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type=mel_spec_type, progress=progress,
             target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
             sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=device, seed=seed,
-            text_tokenizer=text_tokenizer, batch_frames=batch_frames, prompt_on_device=prompt_on_device)
+            text_tokenizer=text_tokenizer, batch_frames=batch_frames, prompt_on_device=prompt_on_device, clip_silence=clip_silence)
+        if remove_silence:
+            wave = _remove_pauses([wave])[0][0]
         yield wave.cpu().numpy(), rate, spec.cpu().numpy()
         return
 
@@ -540,22 +748,30 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
     return wav, wav_lens, mel
 
 
-def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_spec, device=None, prompt_on_device=False):
+def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_spec, device=None, prompt_on_device=False,
+                 clip_silence=False):
     """`get_inference_prompt` for one batch (eval/utils_eval.py:109-148, without the truth-duration branch and the bucketing,
     which is batching.bucket_prompts): prompts is a list of (audio [channels, nw], sample_rate, ref_text), gen_texts the text to
     speak with each.  normalise_prompt per item on the host, then ONE `mel_spec.forward_ragged` over every prompt.  Returns
     dict(cond f32[B, T_max, n_mels] zero-padded (padded_mel_batch), lens = frames per prompt (ref_mel_len), durations =
     total_mel_len per item, texts = prompt text + target text (trailing-space rule), rms per prompt).
     prompt_on_device=True: ONE `mel_spec.prepare_ragged` over every prompt (mono mix, RMS, gain and resampling on the device, the
-    raw audio down in one copy) instead of the normalise_prompt loop; `rms` is then a device f32[B] tensor and stays there."""
+    raw audio down in one copy) instead of the normalise_prompt loop; `rms` is then a device f32[B] tensor and stays there.
+    clip_silence=True (needs prompt_on_device=True: ValueError otherwise): every prompt goes through clip_prompts first, as the
+    reference's preprocess_ref_audio_text does; lens and durations are then the clipped prompts'."""
     from .batching import prompt_text_and_frames
 
     prompts, gen_texts = list(prompts), list(gen_texts)
     if not prompts or len(prompts) != len(gen_texts):
         raise ValueError(f"prompt_batch: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt, at least one)")
     where = {} if device is None else dict(device=device)
+    if clip_silence and not prompt_on_device:
+        raise ValueError("prompt_batch: clip_silence=True needs prompt_on_device=True (the clip runs on the device)")
     if prompt_on_device:
-        audios, rms = mel_spec.prepare_ragged([p[0] for p in prompts], [p[1] for p in prompts], target_rms, **where)
+        raw, rates = [p[0] for p in prompts], [p[1] for p in prompts]
+        if clip_silence:
+            raw = clip_prompts(raw, rates, **where)[0]
+        audios, rms = mel_spec.prepare_ragged(raw, rates, target_rms, **where)
     else:
         audios, rms = [], []
         for audio, sr, _ref_text in prompts:
@@ -573,7 +789,7 @@ def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_
 
 def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, target_rms=target_rms, nfe_step=nfe_step,
                        cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=None, text_tokenizer=None,
-                       batch_frames=None, prompt_on_device=False, **sample_kw):
+                       batch_frames=None, prompt_on_device=False, clip_silence=False, remove_silence=False, **sample_kw):
     """The reference's batch job from raw prompt audio to waveforms (eval/utils_eval.py:109-148 + eval_infer_batch.py:183-212):
     many speakers, one sentence each.  prompt_batch (ONE ragged mel pass over every prompt), then per group of items
     (group_chunks over the totals sample() runs at; `batch_frames` = the budget of rows x longest row, None: groups of up to 64)
@@ -583,6 +799,8 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
     prompt_on_device=True: the prompts are prepared on the device (prompt_batch), their rms stays there and the rescale selects
     with torch.where (rescale_to_prompt): no per-item host arithmetic on audio and no device-to-host read before the waveforms
     are returned.
+    clip_silence=True (needs prompt_on_device=True): the prompts are clipped first (prompt_batch, clip_prompts).
+    remove_silence=True: pauses of 1 s or more are cut out of every finished waveform, in one pass over all of them (remove_silence).
     Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Plain BigVGAN: pass `.ragged()`."""
     _require_text_tokenizer(model, text_tokenizer)
     _require_ragged_vocoder(vocoder, "synthesize_prompts", "decode item by item")
@@ -593,7 +811,7 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
         raise ValueError(f"synthesize_prompts: {len(prompts)} prompts for {len(gen_texts)} texts (need one text per prompt)")
     with torch.inference_mode():
         pb = prompt_batch(prompts, gen_texts, speed=speed, target_rms=target_rms, mel_spec=model.mel_spec, device=model.device,
-                          prompt_on_device=prompt_on_device)
+                          prompt_on_device=prompt_on_device, clip_silence=clip_silence)
         texts, idx = _tokenise(model, pb["texts"], text_tokenizer, stacklevel=3)
         lens, durations, rms = pb["lens"], pb["durations"], pb["rms"]
         ends = clamp_durations(idx.to("cpu", torch.long), torch.tensor(lens), torch.tensor(durations),
@@ -609,6 +827,8 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
             for b, k in enumerate(run):
                 waves.append(rescale_to_prompt(wav[b, :wav_lens[b]], rms[k], target_rms))
                 mels.append(mel[b, lens[k]:ends[k]].to(torch.float32).permute(1, 0))
+        if remove_silence:
+            waves = _remove_pauses(waves)[0]
         return waves, target_sample_rate, mels
 
 
@@ -718,14 +938,22 @@ def speech_edit(model, vocoder, items, *, target_rms=target_rms, nfe_step=nfe_st
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
-                  text_tokenizer=None, batched=False, batch_frames=None, prompt_on_device=False):
+                  text_tokenizer=None, batched=False, batch_frames=None, prompt_on_device=False, clip_silence=False,
+                  remove_silence=False):
     """ref_audio = (tensor [channels, nw], sample_rate) instead of a path (no torchaudio.load here); otherwise
     utils_infer.py:453-498: max_chars from the prompt's bytes-per-second, chunk, infer_batch_process.
     batched=True (default False: the sequential path, unchanged) runs the chunks as ragged batches of at most `batch_frames`
     and cross-fades on the device (infer_batch_process, synthesize_long): the waveform is then f32 where the sequential one is
     float64 after a cross-fade, and a chunk's mel equals the chunk run alone only with `attn_mask_enabled=True`.
-    prompt_on_device=True (batched=True only): the prompt is mixed, levelled and resampled on the device."""
+    prompt_on_device=True (batched=True only): the prompt is mixed, levelled and resampled on the device.
+    clip_silence=True (prompt_on_device=True only): the prompt is clipped on the device first (clip_prompts), as
+    preprocess_ref_audio_text does before the reference calls this function, so max_chars comes from the clipped length.
+    remove_silence=True (batched=True only): pauses of 1 s or more are cut out of the result on the device (remove_silence)."""
     audio, sr = ref_audio
+    if clip_silence:
+        if not (batched and prompt_on_device):
+            raise ValueError("infer_process: clip_silence=True needs batched=True and prompt_on_device=True (the clip runs on the device)")
+        audio = clip_prompts([audio], [sr], device=device if device is not None else model_obj.device)[0][0]
     max_chars = int(len(ref_text.encode("utf-8")) / (audio.shape[-1] / sr) * (22 - audio.shape[-1] / sr) * speed)
     batches = chunk_text(gen_text, max_chars=max_chars)
     if show_info is not None:
@@ -735,4 +963,4 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
                                     nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                                     speed=speed, fix_duration=fix_duration, device=device, seed=seed,
                                     text_tokenizer=text_tokenizer, batched=batched, batch_frames=batch_frames,
-                                    prompt_on_device=prompt_on_device))
+                                    prompt_on_device=prompt_on_device, remove_silence=remove_silence))
