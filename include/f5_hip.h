@@ -514,6 +514,38 @@ int f5k_attention(int32_t prec, const float* q, const float* k, const float* v, 
 /* x f32[Bp, N, D]; w f32[D, D/16, 31]; y = mish(conv(x) + bias) (+ res); lens HOST int32[Bp] or NULL */
 int f5k_convpos(int32_t prec, const float* x, const float* w, const float* bias, const float* res,
                 const int32_t* lens_host, float* y, int32_t Bp, int32_t N, int32_t D, f5_stream stream);
+/* The attention launch in the forms the engine's attention_block makes it (csrc/engine_impl.h): batch row b reads
+ * lens[b % nlens], query blocks wholly past q_lens exit at once, packed output rows (RowPack).  f5k_attention is this call with
+ * kv_lens only, nlens = Bp, an f32 output of Bp * N rows and a zero fill. */
+typedef struct f5k_attn {
+    const int32_t* kv_lens_host;   /* HOST int32[nlens] or NULL: key-padding mask */
+    const int32_t* q_lens_host;    /* HOST int32[nlens] or NULL: query blocks wholly past it are not computed */
+    const int32_t* row_start_host; /* HOST int32[Bp + 1] or NULL: batch row b writes output rows row_start[b] + (0 .. min(N, span_b) - 1);
+                                      starts at 0, multiples of 4, spans <= round_up(N, 4) */
+    int32_t nlens;       /* entries of kv_lens_host / q_lens_host, 1 .. Bp (the CFG halves share one table: nlens = Bp / 2) */
+    int32_t mode;        /* 0: the precision's own kernel, output in its operand type (f32 for F5_PREC_F32 / F5_PREC_F16X3);
+                            1: F5_PREC_F16X3 only -- the f16 kernel on f16 q / k / v^T, output as pre-split f32 rows (store4_planar) */
+    int32_t hi_only;     /* F5_PREC_F16X3, mode 0: bit 0 = K Q^T as the plain f16 product, bit 1 = V^T P^T likewise */
+    int32_t o_planar;    /* F5_PREC_F16X3, mode 0: the f32 output rows stored pre-split */
+    float vt_pad_fill;   /* what V^T columns [N, round_up(N, 64)) hold (the engine never writes them); finite */
+    int32_t pad0;
+    void* out;           /* caller-owned [row_start[Bp] or Bp * N, H * 64] */
+    float* out_f32;      /* f32 copy of a 16-bit out over n_out elements, or NULL */
+    int64_t n_out;       /* elements of out (>= the rows above) */
+} f5k_attn;
+int f5k_attention_ex(int32_t prec, const float* q, const float* k, const float* v, int32_t Bp, int32_t H, int32_t N,
+                     const f5k_attn* p, f5_stream stream);
+/* The conv position embedding in the forms embed_input launches it: lens[b % nlens], packed rows of x / res / y. */
+typedef struct f5k_conv {
+    const int32_t* lens_host;      /* HOST int32[nlens] or NULL */
+    const int32_t* row_start_host; /* HOST int32[Bp + 1] or NULL: batch row b owns rows row_start[b] .. row_start[b + 1] - 1 of x / res / y;
+                                      starts at 0, multiples of 4, min(N, len_b) <= span_b <= round_up(N, 4) */
+    int32_t nlens;       /* entries of lens_host, 1 .. Bp */
+    int32_t pad0;
+    int64_t rows;        /* rows of x / res / y as allocated (>= row_start[Bp] or Bp * N) */
+} f5k_conv;
+int f5k_convpos_ex(int32_t prec, const float* x, const float* w, const float* bias, const float* res, float* y, int32_t Bp,
+                   int32_t N, int32_t D, const f5k_conv* p, f5_stream stream);
 /* LayerNorm(no affine, eps) * (1 + scale[b]) + shift[b]; x f32[R, D], scale/shift f32[R / rows_per_batch, D] */
 int f5k_layernorm_mod(const float* x, const float* scale, const float* shift, float* out, int32_t R, int32_t D,
                       int32_t rows_per_batch, float eps, f5_stream stream);

@@ -62,6 +62,19 @@ class f5k_epi(C.Structure):
          ("gq", _p), ("gk", _p), ("out0", _p), ("out1", _p), ("out2", _p), ("out0_f32", _p), ("out1_f32", _p), ("out2_f32", _p),
          ("n0", C.c_int64), ("n1", C.c_int64), ("n2", C.c_int64)]
 
+class f5k_attn(C.Structure):
+    """Launch-form parameters of f5k_attention_ex (include/f5_hip.h)."""
+    _fields_ = [("kv_lens_host", C.POINTER(C.c_int32)), ("q_lens_host", C.POINTER(C.c_int32)), ("row_start_host", C.POINTER(C.c_int32)),
+                ("nlens", C.c_int32), ("mode", C.c_int32), ("hi_only", C.c_int32), ("o_planar", C.c_int32), ("vt_pad_fill", C.c_float),
+                ("pad0", C.c_int32), ("out", _p), ("out_f32", _p), ("n_out", C.c_int64)]
+
+
+class f5k_conv(C.Structure):
+    """Launch-form parameters of f5k_convpos_ex (include/f5_hip.h)."""
+    _fields_ = [("lens_host", C.POINTER(C.c_int32)), ("row_start_host", C.POINTER(C.c_int32)), ("nlens", C.c_int32), ("pad0", C.c_int32),
+                ("rows", C.c_int64)]
+
+
 # name -> (restype, argtypes); mirrors include/f5_hip.h exactly (tests/test_abi.py checks the export list)
 SIGNATURES = {
     "f5_last_error": (C.c_char_p, []),
@@ -125,6 +138,8 @@ SIGNATURES = {
     "f5k_gemm_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "f5k_attention": (_i, [_i, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),
     "f5k_convpos": (_i, [_i, _p, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),
+    "f5k_attention_ex": (_i, [_i, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_attn), _p]),
+    "f5k_convpos_ex": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_conv), _p]),
     "f5k_layernorm_mod": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "f5k_layernorm_mod_ex": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _p]),
     "f5k_gemm_epi": (_i, [_i, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_epi), _p]),

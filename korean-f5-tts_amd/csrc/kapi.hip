@@ -103,63 +103,158 @@ template <typename T> __global__ void to_f32_kernel(const T* in, float* out, lon
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = (float)in[i];
 }
 
+template <typename T> __global__ void fill_test_kernel(T* p, long n, float v) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = from_f32<T>(v);
+}
+template <typename TO> static int copy_f32(hipStream_t s, const void* src, float* dst, int64_t n) {
+    if constexpr (!std::is_same_v<TO, float>) {
+        if (dst && n > 0) {
+            hipLaunchKernelGGL((to_f32_kernel<TO>), dim3(ew_blocks((long)n)), dim3(256), 0, s, static_cast<const TO*>(src), dst, (long)n);
+            KCHK();
+        }
+    }
+    return F5_OK;
+}
+// a host table of n ints on the device (null stays null)
+static int upload_ints(Scratch<int>& d, const int32_t* host, int n) {
+    if (!host) return F5_OK;
+    HIPCHK(d.alloc((size_t)n));
+    HIPCHK(hipMemcpy(d.p, host, (size_t)n * 4, hipMemcpyHostToDevice));
+    return F5_OK;
+}
+// a RowPack table as the engine builds it: from 0, multiples of 4, every span within [min_span(b), round_up(N, 4)]
+template <typename F> static bool row_start_ok(const int32_t* rs, int Bp, int N, F min_span) {
+    if (rs[0] != 0) return false;
+    for (int b = 0; b < Bp; ++b) {
+        const int cnt = rs[b + 1] - rs[b];
+        if (rs[b] % 4 || cnt < min_span(b) || cnt > round_up(N, 4)) return false;
+    }
+    return rs[Bp] % 4 == 0;
+}
+
+// One attention launch as attention_block (engine_impl.h) makes it.  T = the type of q / k / v^T; p.mode 1 (T = f16_t under
+// F5_PREC_F16X3): the f16 kernel writes pre-split f32 rows (Of) instead of T rows.
 template <typename T>
-static int attn_impl(const float* q, const float* k, const float* v, const int32_t* lens_host, float* out, int Bp, int H, int N,
-                     bool split16, hipStream_t s) {
+static int attn_body(const float* q, const float* k, const float* v, int Bp, int H, int N, const f5k_attn& p, bool split16, hipStream_t s) {
     const int Npad = round_up(N, 64);
     const long rows = (long)Bp * H * N;
-    Scratch<T> qd, kd, vd, od;
-    Scratch<int> ld;
+    const size_t vt_elems = (size_t)Bp * H * 64 * Npad;
+    Scratch<T> qd, kd, vd;
+    Scratch<int> kl, ql, rs;
     HIPCHK(qd.alloc(rows * 64));
     HIPCHK(kd.alloc(rows * 64));
-    HIPCHK(vd.alloc((size_t)Bp * H * 64 * Npad));
-    HIPCHK(od.alloc(rows * 64));
-    HIPCHK(hipMemsetAsync(vd.p, 0, (size_t)Bp * H * 64 * Npad * sizeof(T), s));
-    if (lens_host) {
-        HIPCHK(ld.alloc(Bp));
-        HIPCHK(hipMemcpy(ld.p, lens_host, (size_t)Bp * 4, hipMemcpyHostToDevice));
-    }
+    HIPCHK(vd.alloc(vt_elems));
+    CHK(upload_ints(kl, p.kv_lens_host, p.nlens));
+    CHK(upload_ints(ql, p.q_lens_host, p.nlens));
+    CHK(upload_ints(rs, p.row_start_host, Bp + 1));
+    // (the engine's V^T columns [N, Npad) hold whatever the arena held: here a value of the caller's choice)
+    hipLaunchKernelGGL((fill_test_kernel<T>), dim3(ew_blocks((long)vt_elems)), dim3(256), 0, s, vd.p, (long)vt_elems, p.vt_pad_fill);
     hipLaunchKernelGGL((pack_qkv_test_kernel<T>), dim3(ew_blocks(rows * 64)), dim3(256), 0, s, q, k, v, qd.p, kd.p, vd.p, rows,
                        N, Npad, attention_q_scale<T>());
     KCHK();
-    HIPCHK(launch_attention_any(s, qd.p, kd.p, vd.p, od.p, Bp, H, N, Npad, lens_host ? ld.p : nullptr, Bp, nullptr, nullptr, split16));
-    hipLaunchKernelGGL((to_f32_kernel<T>), dim3(ew_blocks(rows * 64)), dim3(256), 0, s, od.p, out, rows * 64);
-    KCHK();
+    if (p.mode == 1) {
+        if constexpr (std::is_same_v<T, f16_t>)
+            HIPCHK(launch_attention_v2<f16_t>(s, qd.p, kd.p, vd.p, nullptr, Bp, H, N, Npad, kl.p, p.nlens, ql.p, rs.p, static_cast<float*>(p.out)));
+    } else {
+        HIPCHK(launch_attention_any(s, qd.p, kd.p, vd.p, static_cast<T*>(p.out), Bp, H, N, Npad, kl.p, p.nlens, ql.p, rs.p, split16,
+                                    p.o_planar != 0, p.hi_only));
+        CHK(copy_f32<T>(s, p.out, p.out_f32, p.n_out));
+    }
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
+}
+
+static int attention_run(const char* who, int32_t prec, const float* q, const float* k, const float* v, int Bp, int H, int N,
+                         const f5k_attn* p, hipStream_t s) {
+    auto bad = [&](const char* what) { return fail(F5_EINVAL, "%s: %s", who, what); };
+    if (!q || !k || !v || !p || !p->out || Bp <= 0 || H <= 0 || N <= 0) return bad("bad arguments");
+    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
+        return bad("precision must be f32, f16x3, bf16 or f16");
+    const bool x3 = prec == F5_PREC_F16X3;
+    if (p->mode != 0 && p->mode != 1) return bad("mode must be 0 (the precision's own kernel) or 1 (attn16)");
+    if (p->mode == 1 && !x3) return bad("mode 1 (the f16 kernel writing pre-split f32 rows) exists under F5_PREC_F16X3 only");
+    if (p->hi_only < 0 || p->hi_only > 3 || ((p->hi_only || p->o_planar) && (!x3 || p->mode != 0)))
+        return bad("hi_only (0..3) and o_planar belong to the split kernel (F5_PREC_F16X3, mode 0)");
+    if (!(p->vt_pad_fill == p->vt_pad_fill) || p->vt_pad_fill - p->vt_pad_fill != 0.f) return bad("vt_pad_fill must be finite");
+    if ((p->kv_lens_host || p->q_lens_host) && (p->nlens < 1 || p->nlens > Bp)) return bad("nlens must be 1 .. Bp");
+    if (p->row_start_host && !row_start_ok(p->row_start_host, Bp, N, [](int) { return 0; }))
+        return bad("row_start must start at 0, in multiples of 4, at most round_up(N, 4) apart");
+    const int64_t out_rows = p->row_start_host ? p->row_start_host[Bp] : (int64_t)Bp * N;
+    if (p->n_out < out_rows * H * 64) return bad("out is smaller than the rows the launch may write");
+    if (p->mode == 1) return attn_body<f16_t>(q, k, v, Bp, H, N, *p, false, s);
+    return F5K_BY_PREC(prec, attn_body, q, k, v, Bp, H, N, *p, x3, s);
+}
+
+extern "C" int f5k_attention_ex(int32_t prec, const float* q, const float* k, const float* v, int32_t Bp, int32_t H, int32_t N,
+                                const f5k_attn* p, f5_stream stream) {
+    return attention_run("f5k_attention_ex", prec, q, k, v, Bp, H, N, p, (hipStream_t)stream);
 }
 
 extern "C" int f5k_attention(int32_t prec, const float* q, const float* k, const float* v, const int32_t* kv_lens_host,
                              float* out, int32_t Bp, int32_t H, int32_t N, f5_stream stream) {
-    if (!q || !k || !v || !out || Bp <= 0 || H <= 0 || N <= 0) return fail(F5_EINVAL, "f5k_attention: bad arguments");
-    return F5K_BY_PREC(prec, attn_impl, q, k, v, kv_lens_host, out, Bp, H, N, prec == F5_PREC_F16X3, (hipStream_t)stream);
+    if (!out || Bp <= 0 || H <= 0 || N <= 0) return fail(F5_EINVAL, "f5k_attention: bad arguments");
+    f5k_attn p{};
+    p.kv_lens_host = kv_lens_host;
+    p.nlens = Bp;
+    p.n_out = (int64_t)Bp * N * H * 64;
+    Scratch<uint16_t> o16;   // a 16-bit kernel's own output rows, copied to `out` as f32
+    if (prec == F5_PREC_BF16 || prec == F5_PREC_F16) {
+        HIPCHK(o16.alloc((size_t)p.n_out));
+        p.out = o16.p;
+        p.out_f32 = out;
+    } else {
+        p.out = out;
+    }
+    return attention_run("f5k_attention", prec, q, k, v, Bp, H, N, &p, (hipStream_t)stream);
 }
 
+// One conv position embedding launch as embed_input (engine_impl.h) makes it.
 template <typename T>
-static int convpos_impl(const float* x, const float* w, const float* bias, const float* res, const int32_t* lens_host, float* y,
-                        int Bp, int N, int D, bool split16, hipStream_t s) {
+static int convpos_body(const float* x, const float* w, const float* bias, const float* res, float* y, int Bp, int N, int D,
+                        const f5k_conv& p, bool split16, hipStream_t s) {
     const int cpg = D / 16, Kp = round_up(31 * cpg, GEMM_ROW_BYTES / (int)sizeof(T));
     Scratch<T> wp;
-    Scratch<int> ld;
+    Scratch<int> ld, rs;
     HIPCHK(wp.alloc((size_t)D * Kp));
-    if (lens_host) {
-        HIPCHK(ld.alloc(Bp));
-        HIPCHK(hipMemcpy(ld.p, lens_host, (size_t)Bp * 4, hipMemcpyHostToDevice));
-    }
+    CHK(upload_ints(ld, p.lens_host, p.nlens));
+    CHK(upload_ints(rs, p.row_start_host, Bp + 1));
     hipLaunchKernelGGL((conv_pack_kernel<T>), dim3(ew_blocks((long)D * Kp)), dim3(256), 0, s, w, wp.p, (long)D, cpg, 31, Kp);
     KCHK();
     const bool split = split16 && std::is_same_v<T, float> && convpos_can_split(D);
     if (split) HIPCHK(split_planes(s, wp.p, (size_t)D * Kp));
-    HIPCHK(launch_convpos<T>(s, x, wp.p, Kp, bias, res, y, Bp, N, D, lens_host ? ld.p : nullptr, Bp, nullptr, split));
+    HIPCHK(launch_convpos<T>(s, x, wp.p, Kp, bias, res, y, Bp, N, D, ld.p, p.nlens, rs.p, split));
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
 }
 
+static int convpos_run(const char* who, int32_t prec, const float* x, const float* w, const float* bias, const float* res, float* y,
+                       int Bp, int N, int D, const f5k_conv* p, hipStream_t s) {
+    auto bad = [&](const char* what) { return fail(F5_EINVAL, "%s: %s", who, what); };
+    if (!x || !w || !bias || !y || !p || Bp <= 0 || N <= 0) return bad("bad arguments");
+    if (D != 256 && D != 512 && D != 768 && D != 1024) return bad("D must be 256, 512, 768 or 1024");
+    if (p->lens_host && (p->nlens < 1 || p->nlens > Bp)) return bad("nlens must be 1 .. Bp");
+    auto len = [&](int b) { return p->lens_host ? std::min(N, std::max(0, (int)p->lens_host[b % p->nlens])) : N; };
+    if (p->lens_host)
+        for (int i = 0; i < p->nlens; ++i)
+            if (p->lens_host[i] < 0) return bad("lens must not be negative");
+    if (p->row_start_host && !row_start_ok(p->row_start_host, Bp, N, len))
+        return bad("row_start must start at 0, in multiples of 4, each span from the row's length to round_up(N, 4)");
+    if (p->rows < (p->row_start_host ? p->row_start_host[Bp] : (int64_t)Bp * N)) return bad("x / res / y have fewer rows than the launch touches");
+    return F5K_BY_PREC(prec, convpos_body, x, w, bias, res, y, Bp, N, D, *p, prec == F5_PREC_F16X3, s);
+}
+
+extern "C" int f5k_convpos_ex(int32_t prec, const float* x, const float* w, const float* bias, const float* res, float* y, int32_t Bp,
+                              int32_t N, int32_t D, const f5k_conv* p, f5_stream stream) {
+    return convpos_run("f5k_convpos_ex", prec, x, w, bias, res, y, Bp, N, D, p, (hipStream_t)stream);
+}
+
 extern "C" int f5k_convpos(int32_t prec, const float* x, const float* w, const float* bias, const float* res,
                            const int32_t* lens_host, float* y, int32_t Bp, int32_t N, int32_t D, f5_stream stream) {
-    if (!x || !w || !bias || !y || Bp <= 0 || N <= 0) return fail(F5_EINVAL, "f5k_convpos: bad arguments");
-    if (D != 256 && D != 512 && D != 768 && D != 1024) return fail(F5_EINVAL, "f5k_convpos: D must be 256, 512, 768 or 1024");
-    return F5K_BY_PREC(prec, convpos_impl, x, w, bias, res, lens_host, y, Bp, N, D, prec == F5_PREC_F16X3, (hipStream_t)stream);
+    f5k_conv p{};
+    p.lens_host = lens_host;
+    p.nlens = Bp;
+    p.rows = (int64_t)Bp * N;
+    return convpos_run("f5k_convpos", prec, x, w, bias, res, y, Bp, N, D, &p, (hipStream_t)stream);
 }
 
 extern "C" int f5k_layernorm_mod(const float* x, const float* scale, const float* shift, float* out, int32_t R, int32_t D,
@@ -221,16 +316,6 @@ static int epi_gemm(hipStream_t s, const T* a, const T* w, int ld, int M, int N,
     if (cfg == G3_256x256_PP && !(gemm_has_pingpong(sizeof(T), ops) && gemm3_epilogue_ok(epi)))
         return fail(F5_EINVAL, "f5k_gemm_epi: the ping-pong kernel (cfg 20) takes 16-bit or pre-split operands and a QKV split at 256 columns");
     HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, {ops, cfg, ml}));
-    return F5_OK;
-}
-
-template <typename TO> static int copy_f32(hipStream_t s, const void* src, float* dst, int64_t n) {
-    if constexpr (!std::is_same_v<TO, float>) {
-        if (dst && n > 0) {
-            hipLaunchKernelGGL((to_f32_kernel<TO>), dim3(ew_blocks((long)n)), dim3(256), 0, s, static_cast<const TO*>(src), dst, (long)n);
-            KCHK();
-        }
-    }
     return F5_OK;
 }
 

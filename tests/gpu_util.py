@@ -147,3 +147,61 @@ def k_gemm_epi(prec, A, W, bias, kind, outs, *, cfg=-1, a_presplit=False, m_limi
             setattr(p, f"n{i}", o.n)
     _lib.check(lib.f5k_gemm_epi(prec_id(prec), _p(A), _p(W), _p(bias), M, N, K, C.byref(p), _s()), "f5k_gemm_epi")
     return [o.value if c is None else c for o, c in zip(outs, cps)]
+
+
+# ---- the pre-split ("planar") f32 row layout of F5_PREC_F16X3, restated once for every test that reads it
+def _planar_order(device):
+    return torch.tensor([4 * g + s if s < 4 else 16 + 4 * g + s - 4 for g in range(4) for s in range(8)], device=device)
+
+
+def split_planar64(x):
+    """The layout split_planar_kernel writes, restated (per 32 floats: chunk g = f16 hi of k = 4g..4g+3, 16+4g..16+4g+3, chunk
+    4 + g = the f16 lo of the same k) -- used to cross-check the library's own split of a plain store."""
+    v = x.reshape(-1, 32)
+    v = v[:, _planar_order(x.device)]
+    hi = v.half()
+    lo = (v - hi.float()).half()
+    return torch.cat((hi, lo), dim=1).contiguous().view(torch.int32).view(x.shape)
+
+
+def planar_planes(bits):
+    """The inverse reading: int32 bits of pre-split rows -> (hi, lo) f16 tensors of the same shape in natural element order."""
+    h = bits.contiguous().view(torch.int16).view(torch.float16).reshape(-1, 64)
+    inv = torch.argsort(_planar_order(bits.device))
+    return h[:, :32][:, inv].reshape(bits.shape), h[:, 32:][:, inv].reshape(bits.shape)
+
+
+# ---- attention and conv-pos in the forms the engine launches them (tests/test_launch_forms_gpu.py)
+def k_attention_ex(prec, q, k, v, out, *, kv_lens=None, q_lens=None, row_start=None, mode=0, hi_only=0, o_planar=0, vt_pad_fill=0.0):
+    """f5k_attention_ex into the Guarded `out` ([rows, H * 64] of the mode's output type).  kv_lens / q_lens share one length."""
+    lib = _lib.load()
+    Bp, H, N, _ = q.shape
+    p = _lib.f5k_attn()
+    kl, ql, rs = _lib.int_array(kv_lens), _lib.int_array(q_lens), _lib.int_array(row_start)
+    if kl is not None:
+        p.kv_lens_host, p.nlens = kl, len(kv_lens)
+    if ql is not None:
+        p.q_lens_host, p.nlens = ql, len(q_lens)
+    if rs is not None:
+        p.row_start_host = rs
+    p.mode, p.hi_only, p.o_planar, p.vt_pad_fill = mode, hi_only, o_planar, vt_pad_fill
+    p.out, p.n_out = out.ptr(), out.n
+    _lib.check(lib.f5k_attention_ex(prec_id(prec), _p(q), _p(k), _p(v), Bp, H, N, C.byref(p), _s()), "f5k_attention_ex")
+    return out
+
+
+def k_convpos_ex(prec, x, w, bias, res, y, Bp, N, *, lens=None, row_start=None):
+    """f5k_convpos_ex: x / res f32 tensors and y a Guarded, all [rows, D] (rows = row_start[Bp] or more, or Bp * N)."""
+    lib = _lib.load()
+    rows, D = y.shape
+    assert x.shape == (rows, D) and (res is None or res.shape == (rows, D))
+    p = _lib.f5k_conv()
+    la, rs = _lib.int_array(lens), _lib.int_array(row_start)
+    if la is not None:
+        p.lens_host, p.nlens = la, len(lens)
+    if rs is not None:
+        p.row_start_host = rs
+    p.rows = rows
+    _lib.check(lib.f5k_convpos_ex(prec_id(prec), _p(x), _p(w), _p(bias), _p(res), C.c_void_p(y.ptr()), Bp, N, D, C.byref(p), _s()),
+               "f5k_convpos_ex")
+    return y

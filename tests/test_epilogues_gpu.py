@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import DEV, Guarded, k_gemm_epi, k_layernorm_mod_ex  # noqa: E402
+from gpu_util import DEV, Guarded, k_gemm_epi, k_layernorm_mod_ex, split_planar64  # noqa: E402
 
 from f5_tts_amd import _lib  # noqa: E402
 from oracle import f5_oracle as O  # noqa: E402
@@ -441,17 +441,6 @@ def test_presplit_a_matches_in_register_split(cfg):
     o1, _ = run_qkv("f16x3p", A, W, b, 2, 550, 4, 4, 0.125, cs, sn, cfg=cfg)
     for x, y, name in zip(o0, o1, "q k vt".split()):
         assert torch.equal(x.bits, y.bits), name
-
-
-def split_planar64(x):
-    """The layout split_planar_kernel writes, restated (per 32 floats: chunk g = f16 hi of k = 4g..4g+3, 16+4g..16+4g+3, chunk
-    4 + g = the f16 lo of the same k) -- used to cross-check the library's own split of the plain store."""
-    v = x.reshape(-1, 32)
-    idx = torch.tensor([4 * g + s if s < 4 else 16 + 4 * g + s - 4 for g in range(4) for s in range(8)], device=x.device)
-    v = v[:, idx]
-    hi = v.half()
-    lo = (v - hi.float()).half()
-    return torch.cat((hi, lo), dim=1).contiguous().view(torch.int32).view(x.shape)
 
 
 @pytest.mark.parametrize("cfg", [-1, 2, 8, 13])

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from gpu_util import DEV, k_attention, k_convpos, k_gemm, k_layernorm_mod  # noqa: E402
+from launch_oracle import as_operands  # noqa: E402
 
 
 def rel_err(a, b):
@@ -138,14 +139,10 @@ def test_attention_key_padding_mask_and_peaked_softmax(prec, tol):
     assert (out - ref).abs().max() < tol
 
 
-def _as_operands(prec, q, k, v):
-    """What the kernel multiplies: the 16-bit paths round k, v and q * attention_q_scale (dim_head^-0.5 * log2 e, attn2.h)
-    to the operand type.  With scores of magnitude 100+ that operand rounding moves the softmax far more than any
-    kernel-internal arithmetic, so the extreme-score cases compare against SDPA of the ROUNDED operands."""
-    if prec == "f32":
-        return q, k, v
-    qs = 0.125 * 1.4426950408889634
-    return rnd(prec, q * qs) / qs, rnd(prec, k), rnd(prec, v)
+# What the kernel multiplies: the 16-bit paths round k, v and q * attention_q_scale (dim_head^-0.5 * log2 e, attn2.h) to the operand
+# type.  With scores of magnitude 100+ that operand rounding moves the softmax far more than any kernel-internal arithmetic, so the
+# extreme-score cases compare against SDPA of the ROUNDED operands (restated once, with the f16x3 launch forms, in launch_oracle).
+_as_operands = as_operands
 
 
 @pytest.mark.parametrize("prec,tol", [("f32", 3e-5), ("f16x3", 1e-4), ("bf16", 2.5e-2), ("f16", 4e-3)])
