@@ -3,13 +3,13 @@
 //                     (speech_edit.py:157-195) as one launch -- every output frame is a bit copy of its source frame or +0.0;
 //   f5_wave_splice    outside the edited spans, the original recording instead of the vocoder's resynthesis of it, with a short
 //                     linear cross-fade at every inner boundary (no reference counterpart; the contract is in include/f5_hip.h).
-// Both take the segment table of every item from the host, validate it there, and hand it to the kernel through one staged copy
-// (a ring of pinned slots, each with its device twin, held until the kernel that reads it has run): no synchronisation, nothing
-// of the caller's to keep alive.  Built with -ffp-contract=off: the fade is multiply, multiply, add as written, in double.
+// Both take the segment table of every item from the host, validate it there (segments.h), and hand it to the kernel as every
+// ragged stage does: a table layout carved out of the workspace of the handle-less calls (CallState, internal.h), filled through one
+// pinned slot and one copy: no synchronisation unless the workspace grows, nothing of the caller's to keep alive.
+// Built with -ffp-contract=off: the fade is multiply, multiply, add as written, in double.
 #include <cstdint>
-#include <mutex>
 
-#include "internal.h"
+#include "segments.h"
 
 #define fail f5_fail
 
@@ -20,15 +20,6 @@ constexpr int kThreads = 256;
 constexpr int kPerThread = 4;                       // consecutive f32 per thread: one 16-byte access
 constexpr int kTile = kThreads * kPerThread;
 
-struct Seg {                                        // as the caller writes them: frames [dst, dst + frames) <- [src, src + frames)
-    int dst, src, frames;                           // src = -1: an EDIT segment (zero frames)
-};
-
-struct AssembleTable {                              // the device form: item b owns seg[first[b] .. first[b + 1])
-    int first[kMaxItems + 1];
-    Seg seg[kMaxItems * kMaxSegs];
-};
-
 struct SpliceSeg {                                  // a KEEP segment in samples, clipped (include/f5_hip.h)
     long long p0, p1, q0;                           // claims out[p0, p1); the source of p is a[q0 + (p - p0)]
     double step;                                    // 1 / (m - 1): linspace's step (0 for m < 2)
@@ -36,69 +27,43 @@ struct SpliceSeg {                                  // a KEEP segment in samples
     int ends;                                       // bit 0: the head fades in, bit 1: the tail fades out
 };
 
-struct SpliceTable {
-    int first[kMaxItems + 1];
-    int len[kMaxItems];                             // L_b
-    long long a_start[kMaxItems];
-    SpliceSeg seg[kMaxItems * kMaxSegs];
+// the device tables of one call, one layout for slot and device; item b owns seg[first[b] .. first[b + 1])
+struct AssembleTables {                             // first[B + 1] | seg[nseg]
+    int* first;
+    Seg* seg;
+    AssembleTables(char* base, int B) : first(reinterpret_cast<int*>(base)), seg(reinterpret_cast<Seg*>(first + B + 1)) {}
+    static size_t bytes(int B, int nseg) { return ((size_t)B + 1) * 4 + (size_t)std::max(nseg, 1) * sizeof(Seg); }
 };
-
-// Pinned slots and their device twins, per device.  A slot is reused only after the event recorded behind the kernel that read
-// its twin; growth frees the twin (hipFree waits for the device) and is the only allocation of a call.
-struct TableRing {
-    Staging host;
-    char* dev[Staging::NSLOT] = {};
-    size_t cap[Staging::NSLOT] = {};
-    int acquire(size_t bytes, char** hb, char** db, int* slot) {
-        CHK(host.acquire(bytes, hb, slot));
-        const int i = *slot;
-        if (bytes > cap[i]) {
-            if (dev[i]) (void)hipFree(dev[i]);
-            dev[i] = nullptr;
-            cap[i] = 0;
-            HIPCHK(hipMalloc((void**)&dev[i], std::max<size_t>(bytes, 4096)));
-            cap[i] = std::max<size_t>(bytes, 4096);
-        }
-        *db = dev[i];
-        return F5_OK;
-    }
+struct SpliceTables {                               // a_start[B] | seg[nseg] | first[B + 1] | len[B]: the 8-byte entries first
+    long long* a_start;
+    SpliceSeg* seg;
+    int* first;
+    int* len;                                       // L_b
+    SpliceTables(char* base, int B, int nseg)
+        : a_start(reinterpret_cast<long long*>(base)), seg(reinterpret_cast<SpliceSeg*>(a_start + B)),
+          first(reinterpret_cast<int*>(seg + std::max(nseg, 1))), len(first + B + 1) {}
+    static size_t bytes(int B, int nseg) { return (size_t)B * 8 + (size_t)std::max(nseg, 1) * sizeof(SpliceSeg) + (2 * (size_t)B + 1) * 4; }
 };
-
-std::mutex g_ring_mutex;
-std::map<int, TableRing*> g_rings;                  // by device ordinal; lives as long as the process
-
-int ring_of_current_device(TableRing** out) {
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    auto it = g_rings.find(dev);
-    if (it == g_rings.end()) it = g_rings.emplace(dev, new TableRing()).first;
-    *out = it->second;
-    return F5_OK;
-}
+static_assert(sizeof(SpliceSeg) % 8 == 0, "first follows the segments; the segments follow a_start and are 8-byte aligned");
 
 // ---------------------------------------------------------------------------------------------------- assembly
 // One thread per 16 bytes of the output (VEC) or per element; blockIdx.y is the item.  A frame that no segment covers, an EDIT
 // frame and a frame behind D_b are the same thing here: +0.0.
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void edit_assemble_kernel(const float* __restrict__ mel, long long mel_stride, int row,
-                                                                 const AssembleTable* __restrict__ tab, float* __restrict__ cond,
-                                                                 int D_max) {
+                                                                 const int* __restrict__ first, const Seg* __restrict__ segs,
+                                                                 float* __restrict__ cond, int D_max) {
     const int b = blockIdx.y;
     const int per_row = VEC ? row / 4 : row;        // work items per frame
     const long long n = (long long)D_max * per_row;
-    const int s0 = tab->first[b], s1 = tab->first[b + 1];
+    const Seg* my = segs + first[b];
+    const int count = first[b + 1] - first[b];
     const float* src_item = mel + (long long)b * mel_stride;
     float* dst_item = cond + (long long)b * D_max * row;
+    int hint = -1;
     for (long long w = (long long)blockIdx.x * kThreads + threadIdx.x; w < n; w += (long long)gridDim.x * kThreads) {
         const int d = (int)(w / per_row), c = (int)(w % per_row);
-        int from = -1;
-        for (int s = s0; s < s1; ++s) {
-            const Seg g = tab->seg[s];
-            if (d >= g.dst && d < g.dst + g.frames) {
-                from = g.src < 0 ? -1 : g.src + (d - g.dst);
-                break;
-            }
-        }
+        const int from = source_frame(my, count, d, &hint);
         if (VEC) {
             float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (from >= 0) v = *reinterpret_cast<const float4*>(src_item + (long long)from * row + 4 * c);
@@ -112,13 +77,15 @@ __global__ __launch_bounds__(kThreads) void edit_assemble_kernel(const float* __
 // ---------------------------------------------------------------------------------------------------- splice
 __global__ __launch_bounds__(kThreads) void wave_splice_kernel(const float* __restrict__ gen, long long gen_stride,
                                                                const float* __restrict__ a_base,
-                                                               const SpliceTable* __restrict__ tab, float* __restrict__ out,
+                                                               const long long* __restrict__ a_start,
+                                                               const SpliceSeg* __restrict__ segs, const int* __restrict__ first,
+                                                               const int* __restrict__ len, float* __restrict__ out,
                                                                long long out_stride) {
     const int b = blockIdx.y;
-    const long long L = tab->len[b];
-    const int s0 = tab->first[b], s1 = tab->first[b + 1];
+    const long long L = len[b];
+    const int s0 = first[b], s1 = first[b + 1];
     const float* g = gen + (long long)b * gen_stride;
-    const float* a = a_base + tab->a_start[b];
+    const float* a = a_base + a_start[b];
     float* orow = out + (long long)b * out_stride;
     const long long ntiles = (out_stride + kTile - 1) / kTile;
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -131,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void wave_splice_kernel(const float* __re
             v[e] = p < L ? g[p] : 0.0f;              // nothing at or past L of the generated row is read
         }
         for (int s = s0; s < s1; ++s) {
-            const SpliceSeg k = tab->seg[s];
+            const SpliceSeg k = segs[s];
             if (k.p1 <= pb || k.p0 >= pb + kPerThread) continue;
 #pragma unroll
             for (int e = 0; e < kPerThread; ++e) {
@@ -146,14 +113,7 @@ __global__ __launch_bounds__(kThreads) void wave_splice_kernel(const float* __re
                     v[e] = av;
                 } else {
                     double fi, fo;
-                    if (k.m == 1) {
-                        fi = 0.0, fo = 1.0;
-                    } else if (j == k.m - 1) {
-                        fi = 1.0, fo = 0.0;           // linspace sets its last element to `stop`
-                    } else {
-                        fi = (double)j * k.step + 0.0;
-                        fo = (double)j * (-k.step) + 1.0;
-                    }
+                    fade_weights(j, k.m, k.step, &fi, &fo);
                     v[e] = (float)((double)v[e] * fo + (double)av * fi);
                 }
             }
@@ -167,24 +127,6 @@ __global__ __launch_bounds__(kThreads) void wave_splice_kernel(const float* __re
                 if (pb + e < out_stride) o[e] = v[e];
         }
     }
-}
-
-// The checks both entry points share: item b's segments, in ascending and disjoint destination order.
-int check_segments(const char* who, int b, const int32_t* segs, int count, bool keep_only) {
-    long long prev_end = 0;
-    for (int s = 0; s < count; ++s) {
-        const long long dst = segs[3 * s], src = segs[3 * s + 1], frames = segs[3 * s + 2];
-        if (frames < 1) return fail(F5_EINVAL, "%s: item %d segment %d has %lld frames; need at least 1", who, b, s, frames);
-        if (dst + frames > INT32_MAX)
-            return fail(F5_EINVAL, "%s: item %d segment %d ends at frame %lld, past what 32 bits hold", who, b, s, dst + frames);
-        if (dst < prev_end)
-            return fail(F5_EINVAL, "%s: item %d segment %d starts at frame %lld, inside or before the segment in front of it", who, b, s,
-                        dst);
-        if (src < (keep_only ? 0 : -1))
-            return fail(F5_EINVAL, "%s: item %d segment %d has source frame %lld", who, b, s, src);
-        prev_end = dst + frames;
-    }
-    return F5_OK;
 }
 }  // namespace
 
@@ -200,8 +142,7 @@ extern "C" int f5_edit_assemble(const float* mel, int32_t B, int64_t mel_stride,
     if (!dur_host) return fail(F5_EINVAL, "%s: dur_host is null", who);
     if (!cond) return fail(F5_EINVAL, "%s: cond is null", who);
     if (row < 1 || D_max < 1) return fail(F5_EINVAL, "%s: row %d, D_max %d; need at least 1 of each", who, row, D_max);
-    std::vector<AssembleTable> built(1);
-    AssembleTable* tab = built.data();
+    std::vector<int> first((size_t)B + 1);
     int total = 0;
     for (int b = 0; b < B; ++b) {
         const int T = frames_host[b], D = dur_host[b], count = seg_count_host[b];
@@ -211,8 +152,7 @@ extern "C" int f5_edit_assemble(const float* mel, int32_t B, int64_t mel_stride,
         if (count < 0 || count > kMaxSegs)
             return fail(F5_EINVAL, "%s: item %d has %d segments; at most %d", who, b, count, kMaxSegs);
         const int32_t* segs = segs_host + 3 * (size_t)total;
-        CHK(check_segments(who, b, segs, count, false));
-        tab->first[b] = total;
+        CHK(check_segments(who, b, segs, count, -1, INT32_MAX));
         for (int s = 0; s < count; ++s) {
             const long long dst = segs[3 * s], src = segs[3 * s + 1], frames = segs[3 * s + 2];
             if (dst + frames > D)
@@ -220,32 +160,36 @@ extern "C" int f5_edit_assemble(const float* mel, int32_t B, int64_t mel_stride,
                             dst + frames, D, D_max);
             if (src >= 0 && src + frames > T)
                 return fail(F5_EINVAL, "%s: item %d segment %d reads frames [%lld, %lld) of %d", who, b, s, src, src + frames, T);
-            tab->seg[total + s] = Seg{(int)dst, (int)src, (int)frames};
         }
+        first[b] = total;
         total += count;
     }
-    for (int b = B; b <= kMaxItems; ++b) tab->first[b] = total;
-    const size_t bytes = offsetof(AssembleTable, seg) + sizeof(Seg) * (size_t)std::max(total, 1);
+    first[B] = total;
+    const size_t tab_bytes = AssembleTables::bytes(B, total);
 
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_ring_mutex);
-    TableRing* ring = nullptr;
-    CHK(ring_of_current_device(&ring));
-    char *hb = nullptr, *db = nullptr;
-    int slot = 0;
-    CHK(ring->acquire(sizeof(AssembleTable), &hb, &db, &slot));
-    __builtin_memcpy(hb, tab, bytes);
-    HIPCHK(hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
+    std::lock_guard<std::mutex> lock(call_state_mutex());
+    CallState* st = nullptr;
+    CHK(call_state_of_current_device(&st));
+    char* tab = nullptr;
+    CHK(st->reserve_tables(tab_bytes, &tab));
+    CHK(st->enter(s));
+    CHK(st->stage.upload(tab, tab_bytes, s, [&](char* host) {
+        const AssembleTables h(host, B);
+        for (int b = 0; b <= B; ++b) h.first[b] = first[b];
+        for (int k = 0; k < total; ++k) h.seg[k] = Seg{segs_host[3 * k], segs_host[3 * k + 1], segs_host[3 * k + 2]};
+    }));
+    const AssembleTables d(tab, B);
     const bool vec = row % 4 == 0 && mel_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(mel) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(cond) & 15) == 0;
     const long long n = (long long)D_max * (vec ? row / 4 : row);
     const dim3 grid((unsigned)std::min<long long>((n + kThreads - 1) / kThreads, 4096), (unsigned)B);
     if (vec)
-        edit_assemble_kernel<true><<<grid, kThreads, 0, s>>>(mel, (long long)mel_stride, row, (const AssembleTable*)db, cond, D_max);
+        edit_assemble_kernel<true><<<grid, kThreads, 0, s>>>(mel, (long long)mel_stride, row, d.first, d.seg, cond, D_max);
     else
-        edit_assemble_kernel<false><<<grid, kThreads, 0, s>>>(mel, (long long)mel_stride, row, (const AssembleTable*)db, cond, D_max);
+        edit_assemble_kernel<false><<<grid, kThreads, 0, s>>>(mel, (long long)mel_stride, row, d.first, d.seg, cond, D_max);
     KCHK();
-    return ring->host.release(slot, s);             // the slot and its twin are held until the kernel has run
+    return st->leave(s);
 }
 
 extern "C" int f5_wave_splice(const float* gen, int32_t B, int64_t gen_stride, const int32_t* len_host, const float* a_base,
@@ -265,9 +209,9 @@ extern "C" int f5_wave_splice(const float* gen, int32_t B, int64_t gen_stride, c
     if (hop < 1 || hop > 65536) return fail(F5_EINVAL, "%s: hop %d; need 1 <= hop <= 65536", who, hop);
     if (cross_fade_samples < 0) return fail(F5_EINVAL, "%s: cross_fade_samples %d is negative", who, cross_fade_samples);
     if (out_stride < 1) return fail(F5_EINVAL, "%s: out_stride %lld; need at least 1", who, (long long)out_stride);
-    std::vector<SpliceTable> built(1);
-    SpliceTable* tab = built.data();
-    int given = 0, total = 0;
+    std::vector<int> first((size_t)B + 1);
+    std::vector<SpliceSeg> kept;
+    int given = 0;
     for (int b = 0; b < B; ++b) {
         const long long L = len_host[b], n = a_len_host[b];
         const int count = seg_count_host[b];
@@ -279,10 +223,8 @@ extern "C" int f5_wave_splice(const float* gen, int32_t B, int64_t gen_stride, c
         if (count < 0 || count > kMaxSegs)
             return fail(F5_EINVAL, "%s: item %d has %d segments; at most %d", who, b, count, kMaxSegs);
         const int32_t* segs = segs_host + 3 * (size_t)given;
-        CHK(check_segments(who, b, segs, count, true));
-        tab->first[b] = total;
-        tab->len[b] = (int)L;
-        tab->a_start[b] = a_start_host[b];
+        CHK(check_segments(who, b, segs, count, 0, INT32_MAX));
+        first[b] = (int)kept.size();
         for (int s = 0; s < count; ++s) {
             const long long dst = segs[3 * s], src = segs[3 * s + 1], frames = segs[3 * s + 2];
             SpliceSeg k{};
@@ -293,25 +235,32 @@ extern "C" int f5_wave_splice(const float* gen, int32_t B, int64_t gen_stride, c
             k.m = (int)std::min<long long>(cross_fade_samples, (k.p1 - k.p0) / 2);
             k.ends = (k.p0 > 0 ? 1 : 0) | (k.p1 < L ? 2 : 0);
             k.step = k.m > 1 ? 1.0 / (double)(k.m - 1) : 0.0;
-            tab->seg[total++] = k;
+            kept.push_back(k);
         }
         given += count;
     }
-    for (int b = B; b <= kMaxItems; ++b) tab->first[b] = total;
-    const size_t bytes = offsetof(SpliceTable, seg) + sizeof(SpliceSeg) * (size_t)std::max(total, 1);
+    const int total = (int)kept.size();
+    first[B] = total;
+    const size_t tab_bytes = SpliceTables::bytes(B, total);
 
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_ring_mutex);
-    TableRing* ring = nullptr;
-    CHK(ring_of_current_device(&ring));
-    char *hb = nullptr, *db = nullptr;
-    int slot = 0;
-    CHK(ring->acquire(sizeof(SpliceTable), &hb, &db, &slot));
-    __builtin_memcpy(hb, tab, bytes);
-    HIPCHK(hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
+    std::lock_guard<std::mutex> lock(call_state_mutex());
+    CallState* st = nullptr;
+    CHK(call_state_of_current_device(&st));
+    char* tab = nullptr;
+    CHK(st->reserve_tables(tab_bytes, &tab));
+    CHK(st->enter(s));
+    CHK(st->stage.upload(tab, tab_bytes, s, [&](char* host) {
+        const SpliceTables h(host, B, total);
+        for (int b = 0; b < B; ++b) h.a_start[b] = a_start_host[b], h.len[b] = len_host[b];
+        for (int b = 0; b <= B; ++b) h.first[b] = first[b];
+        for (int k = 0; k < total; ++k) h.seg[k] = kept[k];
+    }));
+    const SpliceTables d(tab, B, total);
     const long long ntiles = (out_stride + kTile - 1) / kTile;
     const dim3 grid((unsigned)std::min<long long>(ntiles, 2048), (unsigned)B);
-    wave_splice_kernel<<<grid, kThreads, 0, s>>>(gen, (long long)gen_stride, a_base, (const SpliceTable*)db, out, (long long)out_stride);
+    wave_splice_kernel<<<grid, kThreads, 0, s>>>(gen, (long long)gen_stride, a_base, d.a_start, d.seg, d.first, d.len, out,
+                                                 (long long)out_stride);
     KCHK();
-    return ring->host.release(slot, s);
+    return st->leave(s);
 }

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -191,3 +192,45 @@ struct Staging {
         return release(slot, s);
     }
 };
+
+// The one workspace of the entry points that have no handle (silence.hip, edit.hip), per device, as long as the process lives: an
+// arena for a call's device tables and scratch under the workspace rule above, the pinned ring that carries the tables down, and
+// `done`, which orders a call behind the one before it when the two run on different streams (the workspace is shared); on one
+// stream it is a no-op.  A call holds call_state_mutex() from the lookup to leave().
+struct CallState {
+    Arena arena;
+    Staging stage;
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+    // the plan of a call whose workspace is its tables alone: measured, reserved, carved
+    int reserve_tables(size_t bytes, char** tab) {
+        CHK(arena.reserve(align_up(bytes, 256) + 256));
+        arena.reset();
+        *tab = arena.take<char>(bytes);
+        return F5_OK;
+    }
+    int enter(hipStream_t s) {
+        if (!done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        if (recorded) HIPCHK(hipStreamWaitEvent(s, done, 0));
+        return F5_OK;
+    }
+    int leave(hipStream_t s) {
+        HIPCHK(hipEventRecord(done, s));
+        recorded = true;
+        return F5_OK;
+    }
+};
+// (inline with function-local statics: one registry per program, also for a program that links a single translation unit)
+inline std::mutex& call_state_mutex() {
+    static std::mutex m;
+    return m;
+}
+inline int call_state_of_current_device(CallState** out) {
+    static std::map<int, CallState*> states;        // by device ordinal
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    auto it = states.find(dev);
+    if (it == states.end()) it = states.emplace(dev, new CallState()).first;
+    *out = it->second;
+    return F5_OK;
+}

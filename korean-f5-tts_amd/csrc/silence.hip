@@ -11,12 +11,11 @@
 //   wave_gather_kernel        the clipped waveform: every output frame is q / 32768 of its source frame, or +0.0
 // The scan is the plain three-phase one (tile sums, scan of tile sums, apply): no workgroup ever waits for another.  No atomics.
 // The per-call tables (items, tile and flag offsets, the segment tables) go through one pinned slot and one copy into the
-// workspace, which grows with use; no host read and no synchronisation otherwise.
+// workspace of the handle-less calls (CallState, internal.h), which grows with use; no host read and no synchronisation otherwise.
 #include <cmath>
 #include <cstdint>
-#include <mutex>
 
-#include "internal.h"
+#include "segments.h"
 
 #define fail f5_fail
 
@@ -35,9 +34,6 @@ struct Query {
 struct Queries {
     Query q[kMaxQueries];
 };
-struct Seg {                                        // frames [dst, dst + frames) of the signal <- [src, src + frames) of the item
-    int dst, src, frames;
-};
 struct Item {
     long long in_start;                             // elements from base
     long long slot_start;                           // analyse: first prefix slot; gather: first output element
@@ -45,36 +41,6 @@ struct Item {
     int seg_first, seg_count;                       // seg_count < 0: identity
     int vec, pad;                                   // analyse: the rows are 16-byte aligned
 };
-
-// One workspace and one pinned ring per device, as long as the process lives.  `done` orders a call behind the one before it when
-// the two run on different streams (the workspace is shared); on one stream it is a no-op.
-struct State {
-    Arena arena;
-    Staging stage;
-    hipEvent_t done = nullptr;
-    bool recorded = false;
-};
-std::mutex g_mutex;
-std::map<int, State*> g_states;
-
-int state_of_current_device(State** out) {
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    auto it = g_states.find(dev);
-    if (it == g_states.end()) it = g_states.emplace(dev, new State()).first;
-    *out = it->second;
-    return F5_OK;
-}
-int enter(State* st, hipStream_t s) {
-    if (!st->done) HIPCHK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
-    if (st->recorded) HIPCHK(hipStreamWaitEvent(s, st->done, 0));
-    return F5_OK;
-}
-int leave(State* st, hipStream_t s) {
-    HIPCHK(hipEventRecord(st->done, s));
-    st->recorded = true;
-    return F5_OK;
-}
 
 __host__ __device__ __forceinline__ long long ms_pos(int R, long long ms) { return ((long long)R * ms) / 1000; }
 
@@ -95,24 +61,6 @@ template <typename T> __device__ __forceinline__ int last_not_above(const T* __r
         else hi = mid - 1;
     }
     return lo;
-}
-
-// the source frame of frame v of the signal, -1 where no segment covers it; *hint: the segment found last (or -1)
-__device__ __forceinline__ int source_frame(const Seg* __restrict__ segs, int count, int v, int* hint) {
-    int k = *hint;
-    if (k < 0 || v < segs[k].dst || (k + 1 < count && v >= segs[k + 1].dst)) {
-        if (count < 1 || v < segs[0].dst) return -1;
-        int lo = 0, hi = count - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (segs[mid].dst <= v) lo = mid;
-            else hi = mid - 1;
-        }
-        k = lo;
-        *hint = k;
-    }
-    const Seg g = segs[k];
-    return v < g.dst + g.frames ? g.src + (v - g.dst) : -1;
 }
 
 // inclusive scan over the block's 256 values (Hillis-Steele in LDS); every thread of the block calls it
@@ -333,18 +281,7 @@ int check_item(const char* who, int b, int64_t start, int C, int F, const int32_
     const int count = seg_count_host[b];
     if (count < 0) return fail(F5_EINVAL, "%s: item %d has %d segments", who, b, count);
     if ((long long)*given + count > (1 << 26)) return fail(F5_EINVAL, "%s: more than 2^26 segments at item %d", who, b);
-    const int32_t* segs = segs_host + 3 * (size_t)*given;
-    long long prev_end = 0;
-    for (int s = 0; s < count; ++s) {
-        const long long dst = segs[3 * s], src = segs[3 * s + 1], frames = segs[3 * s + 2];
-        if (frames < 1) return fail(F5_EINVAL, "%s: item %d segment %d has %lld frames; need at least 1", who, b, s, frames);
-        if (src < 0 || src + frames > INT32_MAX) return fail(F5_EINVAL, "%s: item %d segment %d has source frame %lld", who, b, s, src);
-        if (dst < prev_end)
-            return fail(F5_EINVAL, "%s: item %d segment %d starts at frame %lld, inside or before the segment in front of it", who, b, s, dst);
-        if (dst + frames > dst_limit)
-            return fail(F5_EINVAL, "%s: item %d segment %d ends at frame %lld; the limit is %lld", who, b, s, dst + frames, dst_limit);
-        prev_end = dst + frames;
-    }
+    CHK(check_segments(who, b, segs_host + 3 * (size_t)*given, count, 0, dst_limit));
     *given += count;
     return F5_OK;
 }
@@ -424,9 +361,9 @@ extern "C" int f5_silence_analyse(const float* base, int32_t B, const int64_t* s
     const size_t tab_bytes = Tables::bytes(B, pairs, given);
 
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    State* st = nullptr;
-    CHK(state_of_current_device(&st));
+    std::lock_guard<std::mutex> lock(call_state_mutex());
+    CallState* st = nullptr;
+    CHK(call_state_of_current_device(&st));
     long long *slot_buf = nullptr, *tile_sum = nullptr;
     char* tab = nullptr;
     auto plan = [&](Arena& a) {
@@ -439,7 +376,7 @@ extern "C" int f5_silence_analyse(const float* base, int32_t B, const int64_t* s
     Arena dry;
     CHK(st->arena.reserve(plan(dry)));
     (void)plan(st->arena);
-    CHK(enter(st, s));
+    CHK(st->enter(s));
     CHK(st->stage.upload(tab, tab_bytes, s, [&](char* host) {
         const Tables h(host, B, pairs);
         for (int b = 0; b < B; ++b) h.items[b] = items[b];
@@ -462,7 +399,7 @@ extern "C" int f5_silence_analyse(const float* base, int32_t B, const int64_t* s
         silence_flags_kernel<<<dim3(grid), kThreads, 0, s>>>(d.items, d.flag_first, pairs, nq, qs, slot_buf, flags, (long long)total_flags);
         KCHK();
     }
-    return leave(st, s);
+    return st->leave(s);
 }
 
 extern "C" int f5_wave_gather(const float* base, int32_t B, const int64_t* start_host, const int32_t* channels_host,
@@ -509,19 +446,12 @@ extern "C" int f5_wave_gather(const float* base, int32_t B, const int64_t* start
     const size_t tab_bytes = Tables::bytes(B, 0, given);
 
     hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(g_mutex);
-    State* st = nullptr;
-    CHK(state_of_current_device(&st));
+    std::lock_guard<std::mutex> lock(call_state_mutex());
+    CallState* st = nullptr;
+    CHK(call_state_of_current_device(&st));
     char* tab = nullptr;
-    auto plan = [&](Arena& a) {
-        a.reset();
-        tab = a.take<char>(tab_bytes);
-        return align_up(a.off, 256) + 256;
-    };
-    Arena dry;
-    CHK(st->arena.reserve(plan(dry)));
-    (void)plan(st->arena);
-    CHK(enter(st, s));
+    CHK(st->reserve_tables(tab_bytes, &tab));
+    CHK(st->enter(s));
     CHK(st->stage.upload(tab, tab_bytes, s, [&](char* host) {
         const Tables h(host, B, 0);
         for (int b = 0; b < B; ++b) h.items[b] = items[b];
@@ -532,5 +462,5 @@ extern "C" int f5_wave_gather(const float* base, int32_t B, const int64_t* start
     const Tables d(tab, B, 0);
     wave_gather_kernel<<<dim3((unsigned)tiles), kThreads, 0, s>>>(base, d.items, d.tile_start, B, d.segs, qscale, out);
     KCHK();
-    return leave(st, s);
+    return st->leave(s);
 }

@@ -5,7 +5,7 @@
 // next[n:]] in float64.  Every output sample is a function of the samples of the pieces that cover it alone, so the fold runs per
 // output sample, over the covering pieces in ascending order, in double, and is rounded to f32 once at the end -- the bits of
 // numpy's result cast to float32 (the file is built with -ffp-contract=off: multiply, multiply, add as written).
-#include "internal.h"
+#include "segments.h"
 
 #define fail f5_fail
 
@@ -55,14 +55,7 @@ __global__ __launch_bounds__(kThreads) void wave_crossfade_kernel(const float* _
                 if (j < 0 || j >= len) continue;
                 if (j < n) {
                     double fi, fo;
-                    if (n == 1) {
-                        fi = 0.0, fo = 1.0;
-                    } else if (j == n - 1) {
-                        fi = 1.0, fo = 0.0;                       // linspace sets its last element to `stop`
-                    } else {
-                        fi = (double)j * step + 0.0;
-                        fo = (double)j * (-step) + 1.0;
-                    }
+                    fade_weights(j, n, step, &fi, &fo);
                     v[e] = v[e] * fo + (double)xv[e] * fi;
                 } else {
                     v[e] = (double)xv[e];

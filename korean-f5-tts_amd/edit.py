@@ -1,6 +1,6 @@
 """Host arithmetic of speech editing (the reference's infer/speech_edit.py:157-195): from the spans to replace, in seconds, to
 the segments of the edited timeline in mel frames, and from there to the edit mask CFM.sample takes.  Pure Python / host torch: the
-data movement is libf5hip's (csrc/edit.hip, through MelSpec.edit_assemble and infer.wave_splice)."""
+data movement is libf5hip's (csrc/edit.hip, through MelSpec.edit_assemble and wave.wave_splice)."""
 from __future__ import annotations
 
 import torch
@@ -69,11 +69,8 @@ def edit_mask(plans) -> torch.Tensor:
 
 
 def segment_table(plans, keep_only: bool = False):
-    """(counts per item, flat [dst, src, frames, ...]) as f5_edit_assemble / f5_wave_splice take them."""
-    counts, flat = [], []
-    for segments, _D in plans:
-        segs = [s for s in segments if s[1] >= 0] if keep_only else list(segments)
-        counts.append(len(segs))
-        for s in segs:
-            flat += [int(v) for v in s]
-    return counts, flat
+    """(counts per item, flat [dst, src, frames, ...]) as f5_edit_assemble / f5_wave_splice take them (wave.flat_segments);
+    keep_only: without the EDIT segments."""
+    from .wave import flat_segments   # (wave.py imports this module)
+
+    return flat_segments([[s for s in segments if s[1] >= 0 or not keep_only] for segments, _D in plans])

@@ -49,10 +49,11 @@ import torch
 from .cfm import CFM, clamp_durations
 from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
 from . import silence as _silence
-from .edit import edit_mask, edit_plan, segment_table  # noqa: F401  (edit_plan / edit_mask are part of this module's surface)
+from .edit import edit_mask, edit_plan  # noqa: F401  (part of this module's surface)
 from .mel import resample_kernel, resampled_length
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
+from .wave import cross_fade_plan, ragged_items, silence_flags, wave_crossfade, wave_gather, wave_splice  # noqa: F401  (the device calls: wave.py)
 
 target_sample_rate = SAMPLE_RATE
 n_mel_channels = MEL_DIM
@@ -278,19 +279,6 @@ def cross_fade_concat(waves: list[np.ndarray], cross_fade_duration_: float = cro
 MAX_CHUNKS = 64   # pieces of one f5_wave_crossfade call (its per-piece table travels as a kernel argument)
 
 
-def cross_fade_plan(lens: list[int], cross_fade_samples: int) -> tuple[list[int], list[int], int]:
-    """The integer plan of cross_fade_concat's left fold (the arithmetic f5_wave_crossfade does on the host): piece i starts at
-    offs[i] of the result and its first ns[i] samples fade in over what is already there; returns (offs, ns, total).
-    n_i = min(cross_fade_samples, length so far, len_i), 0 for the first piece and when cross_fade_samples <= 0."""
-    offs, ns, total = [], [], 0
-    for i, ln in enumerate(lens):
-        n = min(cross_fade_samples, total, ln) if i > 0 and cross_fade_samples > 0 else 0
-        offs.append(total - n)
-        ns.append(n)
-        total = offs[-1] + ln
-    return offs, ns, total
-
-
 def group_chunks(durations: list[int], batch_frames: int | None, max_chunks: int = MAX_CHUNKS) -> list[range]:
     """Consecutive runs of chunks, in text order, that each run as one ragged batch: a batch costs its row count times its
     longest row, so a run holds len(run) * max(durations in run) <= batch_frames and len(run) <= max_chunks.  A single chunk
@@ -305,119 +293,6 @@ def group_chunks(durations: list[int], batch_frames: int | None, max_chunks: int
     if durations:
         runs.append(range(start, len(durations)))
     return runs
-
-
-def wave_crossfade(wav: torch.Tensor, lens: list[int], cross_fade_samples: int) -> torch.Tensor:
-    """cross_fade_concat on the device (f5_wave_crossfade): piece i is wav[i, :lens[i]] of an f32 [B, stride] device tensor,
-    B <= 64; returns f32[total], bit for bit cross_fade_concat(pieces, ...).astype(float32).  One launch, no synchronisation."""
-    import ctypes as C
-
-    from . import _lib
-    from ._lib import _ptr, _stream_ptr
-
-    if wav.device.type != "cuda":
-        raise RuntimeError("the HIP cross-fade only runs on a GPU (there is no CPU path: cross_fade_concat is the host form)")
-    if wav.dim() != 2 or wav.dtype != torch.float32 or wav.stride(1) != 1 or len(lens) != wav.shape[0]:
-        raise ValueError("wave_crossfade: wav must be f32 [B, stride] with unit element stride and one length per row")
-    total = cross_fade_plan(lens, cross_fade_samples)[2]
-    out = torch.empty(total, device=wav.device, dtype=torch.float32)
-    n = C.c_int64()
-    with torch.cuda.device(wav.device):
-        _lib.check(_lib.load().f5_wave_crossfade(_ptr(wav), wav.shape[0], wav.stride(0), _lib.int_array(lens), int(cross_fade_samples),
-                                                 _ptr(out), total, C.byref(n), _stream_ptr(wav.device)), "f5_wave_crossfade")
-    assert n.value == total
-    return out
-
-
-def _device_items(audios, device, who):
-    """A list of [C_i, F_i] (or [F_i]) tensors as contiguous f32 device tensors: host tensors go down in ONE concatenated copy,
-    device tensors stay where they are.  Returns (tensors, [(C_i, F_i)], device)."""
-    audios = [a[None] if a.dim() == 1 else a for a in audios]
-    if not audios:
-        raise ValueError(f"{who}: no audio")
-    if any(a.dim() != 2 or a.shape[0] < 1 or a.shape[1] < 1 for a in audios):
-        raise ValueError(f"{who}: every audio must be [channels, frames] (or [frames]) with at least one frame")
-    on_gpu = [a.device for a in audios if a.device.type == "cuda"]
-    if device is not None:
-        dev = torch.device(device)
-    elif on_gpu:
-        dev = on_gpu[0]
-    else:
-        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who} only runs on a GPU (there is no CPU path)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if any(d != dev for d in on_gpu):
-        raise ValueError(f"{who}: the audios are on different devices")
-    shapes = [(int(a.shape[0]), int(a.shape[1])) for a in audios]
-    host = [i for i, a in enumerate(audios) if a.device.type != "cuda"]
-    audios = [a if a.device.type != "cuda" else a.to(torch.float32).contiguous() for a in audios]
-    if host:
-        down = torch.cat([audios[i].to(torch.float32).reshape(-1) for i in host]).to(dev)
-        for i, piece in zip(host, down.split([shapes[i][0] * shapes[i][1] for i in host])):
-            audios[i] = piece
-    return audios, shapes, dev
-
-
-def _flat_tables(tables):
-    import ctypes as C
-
-    flat = [int(v) for t in tables for seg in t for v in seg]
-    return (C.c_int32 * len(tables))(*[len(t) for t in tables]), (C.c_int32 * max(len(flat), 1))(*flat)
-
-
-def silence_flags(items, shapes, rates, lens_ms, queries, qscale, tables=None):
-    """One f5_silence_analyse over a ragged batch and ONE small device-to-host read: items are contiguous f32 device tensors
-    holding [C_i, F_i] = shapes[i], lens_ms the length in ms of each analysed signal, queries (W, s, T, kind) tuples
-    (include/f5_hip.h), tables per item the (dst, src, frames) segments the item is read through (None: as it lies).
-    Returns flags[i][k]: a uint8 numpy array per item and query."""
-    import ctypes as C
-
-    from . import _lib
-    from ._lib import _ptr, _stream_ptr
-
-    lib, B, nq, dev = _lib.load(), len(items), len(queries), items[0].device
-    base = min(a.data_ptr() for a in items)
-    starts = (C.c_int64 * B)(*[(a.data_ptr() - base) // 4 for a in items])
-    q_arr = _lib.int_array([v for q in queries for v in q])
-    len_arr = _lib.int_array(lens_ms)
-    counts, offs, total = (C.c_int32 * (B * nq))(), (C.c_int64 * (B * nq))(), C.c_int64()
-    _lib.check(lib.f5_silence_plan(B, len_arr, nq, q_arr, counts, offs, C.byref(total)), "f5_silence_plan")
-    flags = torch.empty(max(total.value, 1), device=dev, dtype=torch.uint8)
-    seg_counts, seg_flat = _flat_tables(tables) if tables is not None else (None, None)
-    with torch.cuda.device(dev):
-        _lib.check(lib.f5_silence_analyse(C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
-                                          _lib.int_array([f for _, f in shapes]), _lib.int_array(rates), len_arr, float(qscale), nq, q_arr,
-                                          seg_counts, seg_flat, _ptr(flags), total.value, _stream_ptr(dev)), "f5_silence_analyse")
-    host = flags.cpu().numpy()
-    return [[host[offs[b * nq + k]:offs[b * nq + k] + counts[b * nq + k]] for k in range(nq)] for b in range(B)]
-
-
-def wave_gather(items, shapes, tables, out_frames, qscale):
-    """One f5_wave_gather: item i read through tables[i] into [C_i, out_frames[i]] of one packed device buffer (every item starts
-    on a 16-byte multiple).  Returns the views."""
-    import ctypes as C
-
-    from . import _lib
-    from ._lib import _ptr, _stream_ptr
-
-    B, dev = len(items), items[0].device
-    base = min(a.data_ptr() for a in items)
-    starts = (C.c_int64 * B)(*[(a.data_ptr() - base) // 4 for a in items])
-    offs, run = [], 0
-    for (c, _), n in zip(shapes, out_frames):
-        run = (run + 3) // 4 * 4
-        offs.append(run)
-        run += c * n
-    out = torch.empty(max(run, 1), device=dev, dtype=torch.float32)
-    seg_counts, seg_flat = _flat_tables(tables)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().f5_wave_gather(C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
-                                              _lib.int_array([f for _, f in shapes]), float(qscale), seg_counts, seg_flat,
-                                              _lib.int_array(out_frames), (C.c_int64 * B)(*offs), _ptr(out), run, _stream_ptr(dev)),
-                   "f5_wave_gather")
-    return [out[o:o + c * n].view(c, n) for o, (c, _), n in zip(offs, shapes, out_frames)]
 
 
 def _check_rates(who, rates, count):
@@ -445,7 +320,14 @@ def clip_prompts(audios, rates, device=None):
     A prompt without any sound comes out as the 50 ms of silence alone, at its own rate and channel count (the reference's is
     551 frames of 11025 Hz mono)."""
     S = _silence
-    items, shapes, dev = _device_items(list(audios), device, "clip_prompts")
+    audios = [a[None] if a.dim() == 1 else a for a in audios]
+    if not audios:
+        raise ValueError("clip_prompts: no audio")
+    if any(a.dim() != 2 or a.shape[0] < 1 or a.shape[1] < 1 for a in audios):
+        raise ValueError("clip_prompts: every audio must be [channels, frames] (or [frames]) with at least one frame")
+    shapes = [(int(a.shape[0]), int(a.shape[1])) for a in audios]
+    items = ragged_items(audios, device, "clip_prompts only runs on a GPU (there is no CPU path)",
+                         "clip_prompts: the audios are on different devices")[0]
     rates = _check_rates("clip_prompts", rates, len(items))
     B = len(items)
     lens = [S.ms_len(f, r) for (_, f), r in zip(shapes, rates)]
@@ -499,7 +381,9 @@ def remove_silence(wavs, lens=None):
     live = [i for i, w in enumerate(wavs) if w.shape[0] > 0]
     if not live:
         return out, out_lens
-    items, shapes, _dev = _device_items([wavs[i] for i in live], None, "remove_silence")
+    items = ragged_items([wavs[i] for i in live], None, "remove_silence only runs on a GPU (there is no CPU path)",
+                         "remove_silence: the waveforms are on different devices")[0]
+    shapes = [(1, int(w.shape[0])) for w in items]
     rates = [target_sample_rate] * len(items)
     flags = silence_flags(items, shapes, rates, [S.ms_len(f, target_sample_rate) for _, f in shapes], S.REMOVE_QUERIES, S.WAVE_QSCALE)
     plans = [S.remove_silence_plan(flags[k][0], shapes[k][1], target_sample_rate) for k in range(len(items))]
@@ -830,40 +714,6 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
         if remove_silence:
             waves = _remove_pauses(waves)[0]
         return waves, target_sample_rate, mels
-
-
-def wave_splice(wav: torch.Tensor, wav_lens, originals, plans, cross_fade_samples: int, hop: int = hop_length) -> torch.Tensor:
-    """The original recording outside the edited spans (f5_wave_splice; the contract is in include/f5_hip.h): wav f32 [B, stride]
-    on a GPU with item b in wav[b, :wav_lens[b]] (decode_ragged's return), originals the prepared recordings as 1-D f32 device
-    tensors at the model's rate (normalise_prompt / prepare_ragged; read where they are), plans edit_plan's return per item.
-    Every KEEP segment's samples become the original's, cross-faded linearly over min(cross_fade_samples, half the segment)
-    samples at each end that is not an end of the waveform; everything else is wav's, +0.0 behind wav_lens[b].  Returns a new
-    tensor of wav's shape.  One launch, no synchronisation; at most 64 items."""
-    import ctypes as C
-
-    from . import _lib
-    from ._lib import _ptr, _stream_ptr
-
-    if wav.device.type != "cuda":
-        raise RuntimeError("the HIP waveform splice only runs on a GPU (there is no CPU path)")
-    B = wav.shape[0] if wav.dim() == 2 else -1
-    wav_lens, originals, plans = [int(n) for n in wav_lens], list(originals), list(plans)
-    if B < 0 or wav.dtype != torch.float32 or wav.stride(1) != 1 or not len(wav_lens) == len(originals) == len(plans) == B:
-        raise ValueError("wave_splice: wav must be f32 [B, stride] with unit element stride, with one length, one original and one "
-                         "plan per row")
-    if any(a.dim() != 1 or a.device != wav.device for a in originals):
-        raise ValueError("wave_splice: every original must be a 1-D tensor on wav's device")
-    originals = [a if a.dtype == torch.float32 and a.stride(0) == 1 else a.to(torch.float32).contiguous() for a in originals]
-    base = min(a.data_ptr() for a in originals)
-    starts = [(a.data_ptr() - base) // 4 for a in originals]
-    counts, flat = segment_table(plans, keep_only=True)
-    out = torch.empty(wav.shape, device=wav.device, dtype=torch.float32)
-    with torch.cuda.device(wav.device):
-        _lib.check(_lib.load().f5_wave_splice(_ptr(wav), B, wav.stride(0), _lib.int_array(wav_lens), C.c_void_p(base),
-                                              (C.c_int64 * B)(*starts), _lib.int_array([a.shape[0] for a in originals]),
-                                              _lib.int_array(counts), _lib.int_array(flat or [0]), int(hop), int(cross_fade_samples),
-                                              _ptr(out), out.stride(0), _stream_ptr(wav.device)), "f5_wave_splice")
-    return out
 
 
 def speech_edit(model, vocoder, items, *, target_rms=target_rms, nfe_step=nfe_step, cfg_strength=cfg_strength,

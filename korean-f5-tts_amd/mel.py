@@ -21,7 +21,9 @@ import torch
 
 from . import _lib
 from ._lib import _ptr, _stream_ptr
+from .edit import MAX_ITEMS, edit_mask, segment_table
 from .native import NativeModule
+from .wave import ragged_items
 
 
 def htk_mel_filterbank(n_freqs: int, n_mels: int, sample_rate: int, f_min: float = 0.0, f_max: float | None = None):
@@ -150,24 +152,6 @@ class MelSpec(NativeModule):
         """(reflect padding, magnitude epsilon) of the mel_spec_type."""
         return (self.n_fft // 2, 0.0) if self.mel_spec_type == "vocos" else ((self.n_fft - self.hop_length) // 2, 1e-9)
 
-    def _ragged_device(self, tensors, device, mixed):
-        """Where a ragged call runs: `device`, else the device tensors' device, else the current GPU (mixed: the message when
-        the device tensors disagree with it)."""
-        on_gpu = [w.device for w in tensors if w.device.type == "cuda"]
-        if device is not None:
-            dev = torch.device(device)
-        elif on_gpu:
-            dev = on_gpu[0]
-        else:
-            dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        if dev.type != "cuda":
-            raise RuntimeError(self._no_cpu)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if any(d != dev for d in on_gpu):
-            raise ValueError(mixed)
-        return dev
-
     @torch.no_grad()
     def forward_ragged(self, wavs, device=None):
         """Prompts of unequal length in one pass (f5_mel_forward_ragged): wavs is a list of f32 [nw_i] (or [1, nw_i]) tensors, on
@@ -180,17 +164,8 @@ class MelSpec(NativeModule):
             raise ValueError("forward_ragged: no waveform")
         if any(w.dim() != 1 for w in wavs):
             raise ValueError("forward_ragged: every waveform must be [nw] or [1, nw]")
-        dev = self._ragged_device(wavs, device, "forward_ragged: the waveforms are on different devices")
         nws = [int(w.shape[0]) for w in wavs]
-        host = [i for i, w in enumerate(wavs) if w.device.type != "cuda"]
-        wavs = [w if w.device.type != "cuda" else w.to(torch.float32).contiguous() for w in wavs]
-        if host:
-            down = torch.cat([wavs[i].to(torch.float32) for i in host]).to(dev)
-            for i, piece in zip(host, down.split([nws[i] for i in host])):
-                wavs[i] = piece
-        # one base pointer and an element offset per item: the items stay where they are (every f32 tensor is 4-byte aligned)
-        base = min(w.data_ptr() for w in wavs)
-        starts = [(w.data_ptr() - base) // 4 for w in wavs]
+        wavs, dev, base, starts = ragged_items(wavs, device, self._no_cpu, "forward_ragged: the waveforms are on different devices")
         lib = _lib.load()
         B = len(wavs)
         pad, eps = self._variant()
@@ -202,7 +177,7 @@ class MelSpec(NativeModule):
         out = torch.empty(B, T, self.n_mel_channels, device=dev, dtype=torch.float32)
         h = self._handle(dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.f5_mel_forward_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), nw_arr, pad, eps, _ptr(out),
+            _lib.check(lib.f5_mel_forward_ragged(h, C.c_void_p(base), B, starts, nw_arr, pad, eps, _ptr(out),
                                                  T * self.n_mel_channels, T, _stream_ptr(dev)), "f5_mel_forward_ragged")
         return out.permute(0, 2, 1), frames
 
@@ -224,16 +199,8 @@ class MelSpec(NativeModule):
             raise ValueError(f"prepare_ragged: {len(audios)} audios for {len(rates)} rates (need one rate per audio)")
         if any(a.dim() != 2 for a in audios):
             raise ValueError("prepare_ragged: every audio must be [channels, n] or [n]")
-        dev = self._ragged_device(audios, device, "prepare_ragged: the audios are on different devices")
         shapes = [(int(a.shape[0]), int(a.shape[1])) for a in audios]
-        host = [i for i, a in enumerate(audios) if a.device.type != "cuda"]
-        audios = [a if a.device.type != "cuda" else a.to(torch.float32).contiguous() for a in audios]
-        if host:
-            down = torch.cat([audios[i].to(torch.float32).reshape(-1) for i in host]).to(dev)
-            for i, piece in zip(host, down.split([shapes[i][0] * shapes[i][1] for i in host])):
-                audios[i] = piece
-        base = min(a.data_ptr() for a in audios)
-        starts = [(a.data_ptr() - base) // 4 for a in audios]
+        audios, dev, base, starts = ragged_items(audios, device, self._no_cpu, "prepare_ragged: the audios are on different devices")
         lib = _lib.load()
         B = len(audios)
         n_arr, sr_arr = _lib.int_array([n for _, n in shapes]), _lib.int_array(rates)
@@ -244,7 +211,7 @@ class MelSpec(NativeModule):
         rms = torch.empty(B, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             self._resample_banks(lib, h, dev, rates)
-            _lib.check(lib.f5_mel_prepare_ragged(h, C.c_void_p(base), B, (C.c_int64 * B)(*starts), _lib.int_array([c for c, _ in shapes]),
+            _lib.check(lib.f5_mel_prepare_ragged(h, C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
                                                  n_arr, sr_arr, self.target_sample_rate, float(target_rms), _ptr(out), total.value,
                                                  _ptr(rms), _stream_ptr(dev)), "f5_mel_prepare_ragged")
         return [out[o:o + n] for o, n in zip(offs, lens)], rms
@@ -257,8 +224,6 @@ class MelSpec(NativeModule):
         first; frames: T_i per item; plans: edit.edit_plan's return per item.  Returns (cond f32 [B, D_max, n_mels] -- KEEP frames
         are bit copies of their source frames, EDIT frames and the frames behind D_i are +0.0 --, edit_mask bool [B, D_max] on
         the host (True = keep; built there because CFM.sample reads it there), [D_i])."""
-        from .edit import MAX_ITEMS, edit_mask, segment_table
-
         plans = list(plans)
         frames = [int(t) for t in frames]
         if mel.device.type != "cuda":
@@ -280,7 +245,7 @@ class MelSpec(NativeModule):
         cond = torch.empty(B, max(D), row, device=mel.device, dtype=torch.float32)
         with torch.cuda.device(mel.device):
             _lib.check(_lib.load().f5_edit_assemble(_ptr(rows), B, rows.stride(0) if B > 1 else T_max * row, row, _lib.int_array(frames),
-                                                    _lib.int_array(counts), _lib.int_array(flat or [0]), _lib.int_array(D), _ptr(cond),
+                                                    counts, flat, _lib.int_array(D), _ptr(cond),
                                                     max(D), _stream_ptr(mel.device)), "f5_edit_assemble")
         return cond, edit_mask(plans), D
 

@@ -1,0 +1,153 @@
+"""The device waveform calls around sample() as Python functions (csrc/wave.hip, csrc/edit.hip, csrc/silence.hip): the cross-fade of
+decoded chunks, the splice of the original recording around edited spans, the silence flags and the gather of the clipped signal --
+and the two pieces of plumbing every ragged call of the audio side shares: `ragged_items` (a list of host or device tensors as
+device items under one base pointer) and `flat_segments` (segment tables as the C entry points read them).  The drivers that call
+these are in infer.py, which re-exports them."""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import _ptr, _stream_ptr
+from .config import HOP_LENGTH
+from .edit import segment_table
+
+
+def ragged_items(tensors, device, no_gpu: str, mixed: str):
+    """A list of tensors as the items of one ragged call: picks the device (`device`, else the device tensors' device, else the
+    current GPU), sends the host tensors down in ONE concatenated copy (each comes back as a flat 1-D piece of it) and leaves device
+    tensors where they are, as contiguous f32.  Returns (items, device, base, starts): one base pointer and a ctypes int64 array of
+    element offsets from it -- every f32 tensor is 4-byte aligned.  The caller checks shapes and hands over its own texts: no_gpu for
+    the RuntimeError when there is no GPU to run on, mixed for the ValueError when device tensors are not on the device."""
+    on_gpu = [t.device for t in tensors if t.device.type == "cuda"]
+    if device is not None:
+        dev = torch.device(device)
+    elif on_gpu:
+        dev = on_gpu[0]
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    if dev.type != "cuda":
+        raise RuntimeError(no_gpu)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if any(d != dev for d in on_gpu):
+        raise ValueError(mixed)
+    host = [i for i, t in enumerate(tensors) if t.device.type != "cuda"]
+    items = [t if t.device.type != "cuda" else t.to(torch.float32).contiguous() for t in tensors]
+    if host:
+        down = torch.cat([items[i].to(torch.float32).reshape(-1) for i in host]).to(dev)
+        for i, piece in zip(host, down.split([items[i].numel() for i in host])):
+            items[i] = piece
+    base = min(t.data_ptr() for t in items)
+    return items, dev, base, (C.c_int64 * len(items))(*[(t.data_ptr() - base) // 4 for t in items])
+
+
+def flat_segments(tables):
+    """Per-item lists of (dst, src, frames) as the entry points take them: (counts int32[B], flat triples int32[3 * total]), ctypes."""
+    flat = [int(v) for t in tables for seg in t for v in seg]
+    return (C.c_int32 * len(tables))(*[len(t) for t in tables]), (C.c_int32 * max(len(flat), 1))(*flat)
+
+
+def wave_crossfade(wav: torch.Tensor, lens: list[int], cross_fade_samples: int) -> torch.Tensor:
+    """cross_fade_concat on the device (f5_wave_crossfade): piece i is wav[i, :lens[i]] of an f32 [B, stride] device tensor,
+    B <= 64; returns f32[total], bit for bit cross_fade_concat(pieces, ...).astype(float32).  One launch, no synchronisation."""
+    if wav.device.type != "cuda":
+        raise RuntimeError("the HIP cross-fade only runs on a GPU (there is no CPU path: cross_fade_concat is the host form)")
+    if wav.dim() != 2 or wav.dtype != torch.float32 or wav.stride(1) != 1 or len(lens) != wav.shape[0]:
+        raise ValueError("wave_crossfade: wav must be f32 [B, stride] with unit element stride and one length per row")
+    total = cross_fade_plan(lens, cross_fade_samples)[2]
+    out = torch.empty(total, device=wav.device, dtype=torch.float32)
+    n = C.c_int64()
+    with torch.cuda.device(wav.device):
+        _lib.check(_lib.load().f5_wave_crossfade(_ptr(wav), wav.shape[0], wav.stride(0), _lib.int_array(lens), int(cross_fade_samples),
+                                                 _ptr(out), total, C.byref(n), _stream_ptr(wav.device)), "f5_wave_crossfade")
+    assert n.value == total
+    return out
+
+
+def cross_fade_plan(lens: list[int], cross_fade_samples: int) -> tuple[list[int], list[int], int]:
+    """The integer plan of cross_fade_concat's left fold (the arithmetic f5_wave_crossfade does on the host): piece i starts at
+    offs[i] of the result and its first ns[i] samples fade in over what is already there; returns (offs, ns, total).
+    n_i = min(cross_fade_samples, length so far, len_i), 0 for the first piece and when cross_fade_samples <= 0."""
+    offs, ns, total = [], [], 0
+    for i, ln in enumerate(lens):
+        n = min(cross_fade_samples, total, ln) if i > 0 and cross_fade_samples > 0 else 0
+        offs.append(total - n)
+        ns.append(n)
+        total = offs[-1] + ln
+    return offs, ns, total
+
+
+def _placed(items, who):
+    """(device, base, starts) of items that are on the device already."""
+    return ragged_items(items, None, f"{who} only runs on a GPU (there is no CPU path)", f"{who}: the items are on different devices")[1:]
+
+
+def silence_flags(items, shapes, rates, lens_ms, queries, qscale, tables=None):
+    """One f5_silence_analyse over a ragged batch and ONE small device-to-host read: items are contiguous f32 device tensors
+    holding [C_i, F_i] = shapes[i], lens_ms the length in ms of each analysed signal, queries (W, s, T, kind) tuples
+    (include/f5_hip.h), tables per item the (dst, src, frames) segments the item is read through (None: as it lies).
+    Returns flags[i][k]: a uint8 numpy array per item and query."""
+    lib, B, nq = _lib.load(), len(items), len(queries)
+    dev, base, starts = _placed(items, "silence_flags")
+    q_arr = _lib.int_array([v for q in queries for v in q])
+    len_arr = _lib.int_array(lens_ms)
+    counts, offs, total = (C.c_int32 * (B * nq))(), (C.c_int64 * (B * nq))(), C.c_int64()
+    _lib.check(lib.f5_silence_plan(B, len_arr, nq, q_arr, counts, offs, C.byref(total)), "f5_silence_plan")
+    flags = torch.empty(max(total.value, 1), device=dev, dtype=torch.uint8)
+    seg_counts, seg_flat = flat_segments(tables) if tables is not None else (None, None)
+    with torch.cuda.device(dev):
+        _lib.check(lib.f5_silence_analyse(C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
+                                          _lib.int_array([f for _, f in shapes]), _lib.int_array(rates), len_arr, float(qscale), nq, q_arr,
+                                          seg_counts, seg_flat, _ptr(flags), total.value, _stream_ptr(dev)), "f5_silence_analyse")
+    host = flags.cpu().numpy()
+    return [[host[offs[b * nq + k]:offs[b * nq + k] + counts[b * nq + k]] for k in range(nq)] for b in range(B)]
+
+
+def wave_gather(items, shapes, tables, out_frames, qscale):
+    """One f5_wave_gather: item i read through tables[i] into [C_i, out_frames[i]] of one packed device buffer (every item starts
+    on a 16-byte multiple).  Returns the views."""
+    B = len(items)
+    dev, base, starts = _placed(items, "wave_gather")
+    offs, run = [], 0
+    for (c, _), n in zip(shapes, out_frames):
+        run = (run + 3) // 4 * 4
+        offs.append(run)
+        run += c * n
+    out = torch.empty(max(run, 1), device=dev, dtype=torch.float32)
+    seg_counts, seg_flat = flat_segments(tables)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_wave_gather(C.c_void_p(base), B, starts, _lib.int_array([c for c, _ in shapes]),
+                                              _lib.int_array([f for _, f in shapes]), float(qscale), seg_counts, seg_flat,
+                                              _lib.int_array(out_frames), (C.c_int64 * B)(*offs), _ptr(out), run, _stream_ptr(dev)),
+                   "f5_wave_gather")
+    return [out[o:o + c * n].view(c, n) for o, (c, _), n in zip(offs, shapes, out_frames)]
+
+
+def wave_splice(wav: torch.Tensor, wav_lens, originals, plans, cross_fade_samples: int, hop: int = HOP_LENGTH) -> torch.Tensor:
+    """The original recording outside the edited spans (f5_wave_splice; the contract is in include/f5_hip.h): wav f32 [B, stride]
+    on a GPU with item b in wav[b, :wav_lens[b]] (decode_ragged's return), originals the prepared recordings as 1-D f32 device
+    tensors at the model's rate (normalise_prompt / prepare_ragged; read where they are), plans edit_plan's return per item.
+    Every KEEP segment's samples become the original's, cross-faded linearly over min(cross_fade_samples, half the segment)
+    samples at each end that is not an end of the waveform; everything else is wav's, +0.0 behind wav_lens[b].  Returns a new
+    tensor of wav's shape.  One launch, no synchronisation; at most 64 items."""
+    if wav.device.type != "cuda":
+        raise RuntimeError("the HIP waveform splice only runs on a GPU (there is no CPU path)")
+    B = wav.shape[0] if wav.dim() == 2 else -1
+    wav_lens, originals, plans = [int(n) for n in wav_lens], list(originals), list(plans)
+    if B < 0 or wav.dtype != torch.float32 or wav.stride(1) != 1 or not len(wav_lens) == len(originals) == len(plans) == B:
+        raise ValueError("wave_splice: wav must be f32 [B, stride] with unit element stride, with one length, one original and one "
+                         "plan per row")
+    mixed = "wave_splice: every original must be a 1-D tensor on wav's device"
+    if any(a.dim() != 1 or a.device != wav.device for a in originals):
+        raise ValueError(mixed)
+    originals, dev, base, starts = ragged_items(originals, wav.device, mixed, mixed)
+    counts, flat = segment_table(plans, keep_only=True)
+    out = torch.empty(wav.shape, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_wave_splice(_ptr(wav), B, wav.stride(0), _lib.int_array(wav_lens), C.c_void_p(base), starts,
+                                              _lib.int_array([a.shape[0] for a in originals]), counts, flat, int(hop),
+                                              int(cross_fade_samples), _ptr(out), out.stride(0), _stream_ptr(dev)), "f5_wave_splice")
+    return out
