@@ -15,6 +15,7 @@
  *   f5_vocos_decode_ragged <- the per-item vocoder loop of a batch   eval/eval_infer_batch.py:202-212
  *   f5_bigvgan_forward <- vocoder(mel) (third-party BigVGAN v2)      infer/utils_infer.py:138-152,705
  *   f5_wave_crossfade <- the cross-fade concatenation of the chunks  infer/utils_infer.py:734-775
+ *   f5_wave_join <- infer_cli.py:363-415, the multi-voice script: per-stretch cross-fades, np.concatenate between stretches
  *   f5_edit_assemble <- speech editing's mel_cond torch.cat chain    infer/speech_edit.py:157-195
  *   f5_wave_splice   <- (no counterpart) the original recording outside the edited spans of speech_edit.py's output
  *   f5_mel_forward   <- MelSpec.forward (vocos / bigvgan type)       model/modules.py:33-146
@@ -278,6 +279,35 @@ int f5_vocos_decode_ragged(f5_vocos* v, const float* mel, int32_t B, int64_t str
  * longest piece or out_cap < total. */
 int f5_wave_crossfade(const float* wav, int32_t B, int64_t wav_stride, const int32_t* lens_host, int32_t cross_fade_samples,
                       float* out, int64_t out_cap, int64_t* out_len_host, f5_stream stream);
+
+/* f5_wave_join: pieces joined into one waveform with a fade request per piece -- the multi-voice script of infer/infer_cli.py:363-415,
+ * where the chunks of one tagged stretch are cross-faded (infer/utils_infer.py:734-775) and the stretches are concatenated.
+ * Piece i is base[start_host[i] + j], j < lens_host[i] (f32, device): the pieces may lie in any order and in several tensors under
+ * one base pointer (f5_wave_gather's placement).  fade_host[i] >= 0 is the cross-fade requested, in samples, into what stands in
+ * front of piece i.  Host plan, in exact integers; R is the length of the current run:
+ *   piece 0, and every piece with fade_host[i] == 0, opens a run:  n_i = 0,  off_i = L_{i-1} (0 for i = 0),  R = len_i;
+ *   otherwise:  n_i = min(fade_host[i], R, len_i),  off_i = L_{i-1} - n_i,  R = R - n_i + len_i;
+ *   in both cases L_i = off_i + len_i;  total = L_{B-1}.
+ * R restarts with every run, so a run is the reference's left fold over that run alone (its len(final) is the stretch's length,
+ * not the script's).  Output sample p is a fold, in double, over the pieces that cover it (j = p - off_i, 0 <= j < len_i), in
+ * ascending i:
+ *   j < n_i:  v = v * fo + (double)x_i[j] * fi        otherwise:  v = (double)x_i[j];      out[p] = (float)v
+ * with numpy's linspace weights fi = j * step_i + 0.0, fo = j * (-step_i) + 1.0, step_i = 1.0 / (n_i - 1) computed on the host,
+ * the last fade element exactly fi = 1, fo = 0, and fo = 1, fi = 0 for n_i == 1.  Multiplies and adds are separate IEEE double
+ * operations and the result is rounded to f32 once, so out is, bit for bit, the concatenation of numpy's float64 fold of every
+ * run, cast to float32 -- also where pieces shorter than the fade put more than two pieces over one sample.
+ * out[0, total) is written, each sample by one thread (deterministic), with 16-byte stores where the address allows (the same
+ * bits either way); nothing at or past total is written and nothing outside [0, len_i) of a piece is read.  *out_len_host (may
+ * be NULL) receives total.  L_i never decreases (L_i - L_{i-1} = len_i - n_i >= 0) while off_i may (a short piece in front of a
+ * long fade), so a tile of the output finds its first piece by bisection over L and walks up while the minimum of off over the
+ * pieces still to come lies inside it: no tile loops over all pieces.  1 <= B <= 65535.
+ * The table goes through a pinned slot of the per-device ring into the workspace of the handle-less calls: ONE launch and one small
+ * host-to-device copy on `stream`, no synchronisation except when that workspace grows, every host array free when the call
+ * returns; not capturable into a graph.  F5_EINVAL, with nothing launched or staged and a message that starts with "f5_wave_join:"
+ * and names the argument or the piece: a null base / start_host / lens_host / fade_host / out, B out of range, a lens_host[i] < 1,
+ * a fade_host[i] < 0, a start_host[i] < 0, out_cap < total. */
+int f5_wave_join(const float* base, int32_t B, const int64_t* start_host, const int32_t* lens_host, const int32_t* fade_host,
+                 float* out, int64_t out_cap, int64_t* out_len_host, f5_stream stream);
 
 /* --------------------------------------------------------------------------------------------- speech editing
  * The data movement around CFM.sample(edit_mask=...) for a batch of recordings (infer/speech_edit.py).  A recording's edited

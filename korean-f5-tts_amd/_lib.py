@@ -105,6 +105,7 @@ SIGNATURES = {
     "f5_vocos_decode_ragged": (_i, [_p, _p, _i, C.c_int64, C.c_int64, C.c_int64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_f), _p,
                                C.c_int64, _p]),
     "f5_wave_crossfade": (_i, [_p, _i, C.c_int64, C.POINTER(_i), _i, _p, C.c_int64, C.POINTER(C.c_int64), _p]),
+    "f5_wave_join": (_i, [_p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), _p, C.c_int64, C.POINTER(C.c_int64), _p]),
     "f5_edit_assemble": (_i, [_p, _i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, _i, _p]),
     "f5_wave_splice": (_i, [_p, _i, C.c_int64, C.POINTER(_i), _p, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                         _i, _i, _p, C.c_int64, _p]),

@@ -34,6 +34,11 @@
   remove_silence                     utils_infer.py:784-793      pauses of 1 s or more cut out of generated waveforms, on the device;
                                                                  `remove_silence=True` of synthesize_prompts and the batched infer_process
 
+  parse_script / script_plan         infer_cli.py:363-383        the multi-voice script ("Multi-Speech"): [voice] tags, each stretch in its
+  prepare_voices / synthesize_script infer_cli.py:355-415        voice (script.py); every voice's prompt prepared ONCE and kept on the device
+                                                                 (VoiceBank), the chunks of all stretches as ragged batches with one prompt
+                                                                 per item, ONE f5_wave_join: cross-fades inside a stretch, none between
+
 Out of scope here: Whisper ASR (an empty ref_text), forced alignment, resampling of the OUTPUT, pinyin /
 Korean G2P tokenisers (text is tokenised per character through `vocab_char_map`, or as utf-8 bytes when the model has no
 vocabulary, exactly as CFM.sample does for list[str]).
@@ -51,9 +56,11 @@ from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
 from . import silence as _silence
 from .edit import edit_mask, edit_plan  # noqa: F401  (part of this module's surface)
 from .mel import resample_kernel, resampled_length
+from .script import parse_script, script_plan  # noqa: F401  (part of this module's surface)
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
-from .wave import cross_fade_plan, ragged_items, silence_flags, wave_crossfade, wave_gather, wave_splice  # noqa: F401  (the device calls: wave.py)
+from .wave import (cross_fade_plan, join_plan, ragged_items, silence_flags, wave_crossfade, wave_gather, wave_join,  # noqa: F401
+                   wave_splice)                                                   # (the device calls: wave.py)
 
 target_sample_rate = SAMPLE_RATE
 n_mel_channels = MEL_DIM
@@ -783,6 +790,126 @@ def speech_edit(model, vocoder, items, *, target_rms=target_rms, nfe_step=nfe_st
                 waves.append(rescale_to_prompt(wav[b, :wav_lens[b]], rms[k], target_rms))
                 mels.append(generated[b, :ends[k]].permute(1, 0))
         return waves, target_sample_rate, mels
+
+
+class VoiceBank:
+    """The prepared prompts of a set of voices (prepare_voices): on the device the padded log-mel `mel` f32 [V, T_max, 100] and
+    the RMS of every mono prompt `rms` f32 [V]; on the host what the plan needs -- `names`, `frames` (mel frames per voice, from
+    the host plan of the ragged mel pass; sample() takes its `lens` from the host), `samples` (prepared samples at 24 kHz),
+    `seconds` (the prompt's length as infer_process sees it), `ref_texts`, `speeds` (a voice's own speed, or None) -- and the
+    `target_rms` the prompts were levelled to.  Nothing here is ever read back from the device."""
+
+    def __init__(self, names, mel, rms, frames, samples, seconds, ref_texts, speeds, target_rms):
+        self.names, self.mel, self.rms, self.frames, self.samples = list(names), mel, rms, list(frames), list(samples)
+        self.seconds, self.ref_texts, self.speeds, self.target_rms = list(seconds), list(ref_texts), list(speeds), target_rms
+
+    def prompts(self):
+        """The voices as script_plan takes them."""
+        return {name: dict(seconds=self.seconds[v], samples=self.samples[v], ref_text=self.ref_texts[v], speed=self.speeds[v])
+                for v, name in enumerate(self.names)}
+
+
+def prepare_voices(model, voices, *, target_rms=target_rms, clip_silence=False, device=None) -> VoiceBank:
+    """What infer_cli.py:355-361 and infer_batch_process do to every voice's prompt, once for all voices: voices is
+    {name: dict(ref_audio=(tensor [C, n], sample_rate), ref_text=str, speed=optional)}.  ONE clip_prompts over all of them (with
+    clip_silence=True: preprocess_ref_audio_text's clip), ONE `mel_spec.prepare_ragged` (mono mix, RMS, gain, resampling) and ONE
+    `mel_spec.forward_ragged`; the audio goes down in one copy and is never read back.  The bank serves any number of
+    synthesize_script calls (the socket server's pattern: update_reference once, many requests)."""
+    if not voices:
+        raise ValueError("prepare_voices: no voice")
+    names = list(voices)
+    for name in names:
+        if not voices[name]["ref_text"]:
+            raise ValueError(f"prepare_voices: voice {name!r} has an empty ref_text (transcribing the prompt is not part of this engine)")
+    device = device if device is not None else model.device
+    raw, rates = [voices[n]["ref_audio"][0] for n in names], [int(voices[n]["ref_audio"][1]) for n in names]
+    with torch.inference_mode():
+        if clip_silence:
+            raw, counts = clip_prompts(raw, rates, device=device)
+        else:
+            counts = [int(a.shape[-1]) for a in raw]
+        wavs, rms = model.mel_spec.prepare_ragged(raw, rates, target_rms, device=device)
+        mel, frames = model.mel_spec.forward_ragged(wavs, device=device)
+    return VoiceBank(names, mel.permute(0, 2, 1), rms, frames, [int(w.shape[0]) for w in wavs],
+                     [n / sr for n, sr in zip(counts, rates)], [voices[n]["ref_text"] for n in names],
+                     [voices[n].get("speed") for n in names], target_rms)
+
+
+def synthesize_script(model, vocoder, voices, script, *, speed=speed, target_rms=target_rms, cross_fade_duration=cross_fade_duration,
+                      nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, fix_duration=fix_duration,
+                      seed=None, text_tokenizer=None, batch_frames=None, clip_silence=False, remove_silence=False, default="main"):
+    """The multi-voice script of infer_cli.py:348-425 (infer_gradio.py's "Multi-Speech") as ragged batches: `script` carries
+    [name] tags, each tagged stretch is spoken with that voice's prompt at that voice's own speed (parse_script), chunked as
+    infer_process chunks it (script_plan), and the stretches are concatenated -- where the reference runs one infer_process per
+    stretch, each preparing its prompt again.  Text in front of the first tag and unknown names go to the voice `default`.  voices: a VoiceBank (prepare_voices), or the dict prepare_voices takes: then only
+    the voices the script uses are prepared, with this call's target_rms and clip_silence (a bank keeps its own).  Then
+      per group of items (group_chunks over the totals sample() runs at, in script order; `batch_frames` = the budget of rows x
+      longest row, None: groups of up to 64) ONE `model.sample` -- cond = the bank's mel rows of the group's voices, cut to the
+      group's longest prompt (an index-select on the device), lens = each item's own prompt frames -- and ONE
+      `vocoder.decode_ragged` of each item's frames behind its own prompt; the rescale `wave * rms / target_rms` with each row's
+      own device rms (rescale_to_prompt);
+      ONE wave_join (f5_wave_join) over the rows of every group where they lie: the chunks of a stretch cross-faded, each
+      stretch's fade lengths from that stretch's own running length, plain concatenation between stretches;
+      remove_silence=True: pauses of 1 s or more cut out of the result (remove_silence).
+    Returns (wave f32[total], sample_rate, combined mel f32[100, T_total], segments), wave and mel on the device; segments is a
+    host list of (voice, text, start_sample, end_sample) per stretch in the joined waveform (before any pause is removed) -- what
+    the reference's save_chunk writes to files.  A stretch without text has start == end.  Any number of chunks up to 65535.
+    A vocoder without decode_ragged: NotImplementedError (plain BigVGAN: pass `.ragged()`); kor_* tokenisers need text_tokenizer=.
+
+    Against one infer_process per stretch:
+      * the waveform is f32; the sequential one is float64 wherever a cross-fade happened (numpy promotes).  The values are
+        the float64 ones rounded once to f32;
+      * a chunk's mel in a batch equals the same chunk run alone only where batch items cannot see each other's padding:
+        with `attn_mask_enabled=True` the backbone runs the valid rows only (RowPack).  With `attn_mask_enabled=False` (the
+        shipped configs) a shorter chunk attends over the padded frames up to the group's longest, exactly as in the
+        reference's own batch driver (eval/eval_infer_batch.py, cfm.py:155-158)."""
+    _require_text_tokenizer(model, text_tokenizer)
+    _require_ragged_vocoder(vocoder, "synthesize_script", "run infer_process per stretch")
+    names = voices.names if isinstance(voices, VoiceBank) else list(voices)
+    if default not in names:
+        raise ValueError(f"synthesize_script: the default voice {default!r} is not among the voices {names}")
+    stretches = parse_script(script, names, default)
+    if isinstance(voices, VoiceBank):
+        bank = voices
+    else:
+        used = {v for v, _ in stretches}
+        bank = prepare_voices(model, {n: voices[n] for n in names if n in used}, target_rms=target_rms, clip_silence=clip_silence)
+    plan = script_plan(stretches, bank.prompts(), speed=speed, fix_duration=fix_duration, cross_fade_duration=cross_fade_duration)
+    items, fades = plan["items"], plan["fades"]
+    if not items:
+        raise ValueError("synthesize_script: no stretch of the script has any text")
+    voice_of, durations = [it[0] for it in items], [it[3] for it in items]
+    lens = [bank.frames[v] for v in voice_of]
+    starts = [bank.samples[v] // hop_length for v in voice_of]                  # text_numerics' ref_audio_len
+    texts, idx = _tokenise(model, [it[2] for it in items], text_tokenizer, stacklevel=3)
+    with torch.inference_mode():
+        ends = clamp_durations(idx.to("cpu", torch.long), torch.tensor(lens), torch.tensor(durations)).tolist()
+        pieces, specs = [], []
+        for run in group_chunks(ends, batch_frames):
+            glens = [lens[k] for k in run]
+            rows = torch.tensor([voice_of[k] for k in run], device=bank.mel.device)
+            generated, _ = model.sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[texts[k] for k in run],
+                                        duration=torch.tensor([durations[k] for k in run]), lens=torch.tensor(glens), steps=nfe_step,
+                                        cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+            generated = generated.to(torch.float32)
+            wave, wave_lens = vocoder.decode_ragged(generated.permute(0, 2, 1), ends=[ends[k] for k in run],
+                                                    starts=[starts[k] for k in run])
+            wave = rescale_to_prompt(wave, bank.rms.index_select(0, rows)[:, None], bank.target_rms)
+            for b, k in enumerate(run):
+                pieces.append(wave[b, :wave_lens[b]])
+                specs.append(generated[b, starts[k]:ends[k]].permute(1, 0))
+        offs, _, total = join_plan([int(p.shape[0]) for p in pieces], fades)
+        segments, k = [], 0
+        for s, (voice, text) in enumerate(stretches):
+            first = k
+            while k < len(items) and items[k][1] == s:
+                k += 1
+            at = offs[first] if first < len(items) else total
+            segments.append((voice, text, at, offs[k - 1] + int(pieces[k - 1].shape[0]) if k > first else at))
+        wave = wave_join(pieces, fades)
+        if remove_silence:
+            wave = _remove_pauses([wave])[0][0]
+        return wave, target_sample_rate, torch.cat(specs, dim=1), segments
 
 
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,

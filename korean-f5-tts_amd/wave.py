@@ -1,5 +1,5 @@
 """The device waveform calls around sample() as Python functions (csrc/wave.hip, csrc/edit.hip, csrc/silence.hip): the cross-fade of
-decoded chunks, the splice of the original recording around edited spans, the silence flags and the gather of the clipped signal --
+decoded chunks, the join of a multi-voice script's pieces, the splice of the original recording around edited spans, the silence flags and the gather of the clipped signal --
 and the two pieces of plumbing every ragged call of the audio side shares: `ragged_items` (a list of host or device tensors as
 device items under one base pointer) and `flat_segments` (segment tables as the C entry points read them).  The drivers that call
 these are in infer.py, which re-exports them."""
@@ -83,6 +83,49 @@ def cross_fade_plan(lens: list[int], cross_fade_samples: int) -> tuple[list[int]
 def _placed(items, who):
     """(device, base, starts) of items that are on the device already."""
     return ragged_items(items, None, f"{who} only runs on a GPU (there is no CPU path)", f"{who}: the items are on different devices")[1:]
+
+
+def join_plan(lens: list[int], fades: list[int]) -> tuple[list[int], list[int], int]:
+    """cross_fade_plan with a fade request per piece (the arithmetic f5_wave_join does on the host): piece 0 and every piece with
+    fades[i] == 0 open a run, placed behind everything before it; any other piece fades in over n_i = min(fades[i], length of its
+    run so far, len_i) samples.  The running length restarts with every run, so a run is placed exactly as cross_fade_plan places
+    it alone.  Returns (offs, ns, total)."""
+    if len(lens) != len(fades):
+        raise ValueError(f"join_plan: {len(lens)} lengths for {len(fades)} fades (need one fade per piece)")
+    offs, ns, total, run = [], [], 0, 0
+    for i, (ln, fade) in enumerate(zip(lens, fades)):
+        opens = i == 0 or fade == 0
+        n = 0 if opens else min(fade, run, ln)
+        offs.append(total - n)
+        ns.append(n)
+        total = offs[-1] + ln
+        run = ln if opens else run - n + ln
+    return offs, ns, total
+
+
+def wave_join(items, fades) -> torch.Tensor:
+    """The pieces of a multi-voice script as one waveform (f5_wave_join; the contract is in include/f5_hip.h): items are 1-D f32
+    device tensors with unit stride, read where they lie (rows of several decode_ragged results, in any order), fades[i] >= 0 the
+    cross-fade in samples into what stands in front of piece i (0: plain concatenation, the piece opens a run).  Returns f32[total],
+    bit for bit np.concatenate([cross_fade_concat(run) for every run]).astype(float32).  One launch, no synchronisation; at most
+    65535 pieces."""
+    items, fades = list(items), [int(f) for f in fades]
+    if not items or len(items) != len(fades):
+        raise ValueError(f"wave_join: {len(items)} pieces for {len(fades)} fades (need one fade per piece, at least one piece)")
+    if any(t.dim() != 1 or t.dtype != torch.float32 or t.shape[0] < 1 or t.stride(0) != 1 for t in items):
+        raise ValueError("wave_join: every piece must be a 1-D f32 tensor with unit stride and at least one sample")
+    if any(t.device.type != "cuda" for t in items):
+        raise RuntimeError("wave_join only runs on a GPU (there is no CPU path: cross_fade_concat per run is the host form)")
+    lens = [int(t.shape[0]) for t in items]
+    dev, base, starts = _placed(items, "wave_join")
+    total = join_plan(lens, fades)[2]
+    out = torch.empty(total, device=dev, dtype=torch.float32)
+    n = C.c_int64()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_wave_join(C.c_void_p(base), len(items), starts, _lib.int_array(lens), _lib.int_array(fades), _ptr(out),
+                                            total, C.byref(n), _stream_ptr(dev)), "f5_wave_join")
+    assert n.value == total
+    return out
 
 
 def silence_flags(items, shapes, rates, lens_ms, queries, qscale, tables=None):
