@@ -474,6 +474,40 @@ int f5_mel_prepare_ragged(f5_mel* m, const float* base, int32_t B, const int64_t
                           const int32_t* n_host, const int32_t* sr_host, int32_t target_sr, float target_rms, float* out,
                           int64_t out_capacity, float* rms_out, f5_stream stream);
 
+/* ------------------------------------------------------------------------------------- delivery at the client's rate
+ * What stands between generated audio and a client (the reference's clients and eval/utils_eval.py:403-411 resample every generated
+ * file; a socket wants PCM16): a ragged batch of B <= 65535 streams of 24 kHz f32 audio, each read where it lies, resampled to
+ * out_rate and stored as f32 or 16-bit PCM in ONE launch.  Item b has n_b >= 0 samples from base[start_host[b]]; final_host[b] != 0
+ * says that the stream ends there, 0 that more samples will follow.  The arithmetic contract, per item:
+ *   geometry   g = gcd(24000, out_rate), orig = 24000 / g, new = out_rate / g, width = ceil(6 * orig / (0.99 * min(orig, new))) in
+ *              double, K = 2 width + orig (step 4 of f5_mel_prepare_ragged).
+ *   resample   y[i * new + p] = sum_k bank[p][k] * xpad[i * orig + k]: step 4 of f5_mel_prepare_ragged verbatim -- k ascending from
+ *              +0.0, an f32 multiply then an f32 add per tap, no fused multiply-add, bank the handle's (24000 -> out_rate) pair from
+ *              f5_mel_resample_bank.  xpad is the stream behind `width` zeros, and in front of zeros where it is final; the zeros are
+ *              index logic.  y[i * new + p] depends on the samples [i * orig - width, i * orig + width + orig - 1] alone.
+ *              out_rate == 24000: y = x.
+ *   lengths    len = ceil(new * n / orig) samples in all.  ready = the leading outputs whose taps are all there: len for a final
+ *              stream, else min(new * max(0, floor((n - width - orig) / orig) + 1), len).  An output below `ready` never changes as
+ *              the stream grows, so a stream delivered range by range is the finished stream delivered at once.
+ *   format     F5_PCM_F32 stores y.  F5_PCM_S16 stores the 16-bit view of generated audio (the silence stage's, qscale 32767):
+ *              t = y * 32767.f in f32; NaN gives 0, t <= -32768 gives -32768, t >= 32767 gives 32767, else (int)rintf(t) (ties to even).
+ *   output     the range [o0_b, o1_b) of y, 0 <= o0_b <= o1_b <= ready_b, goes to out elements [at_b, at_b + o1_b - o0_b), where at_b is
+ *              the running total rounded up to 16 bytes (4 f32 or 8 s16 elements): out_start_out[b] = at_b.  out_capacity counts
+ *              elements of the format.  Nothing else of out is written, nothing outside [0, n_b) of an item is read; each sample is
+ *              written by one thread, no atomics.  An empty range writes nothing.
+ * f5_wave_deliver_plan is len and ready for one stream as pure host arithmetic (no HIP call).
+ * The host tables are free when f5_wave_deliver returns (one copy through a pinned slot of the handle); no synchronisation and no
+ * allocation except the growth of the handle's workspace.  Calls on one handle are ordered by the caller's stream.
+ * F5_EINVAL, with nothing launched or staged and a message that starts with the function's name: a null pointer, B < 1 or
+ * B > 65535, out_rate outside [8000, 192000], a rate whose bank new * K exceeds 2^20 elements (8001 Hz is one), start_b < 0, n_b < 0,
+ * a range outside [0, ready_b], an unknown format, out_capacity below the plan's total.  F5_ESTATE: the pair has no bank yet. */
+#define F5_PCM_F32 0
+#define F5_PCM_S16 1
+int f5_wave_deliver_plan(int32_t out_rate, int64_t n, int32_t final, int64_t* len_out, int64_t* ready_out);
+int f5_wave_deliver(f5_mel* m, const float* base, int32_t B, const int64_t* start_host, const int32_t* n_host,
+                    const int32_t* final_host, const int64_t* o0_host, const int64_t* o1_host, int32_t out_rate, int32_t format,
+                    void* out, int64_t out_capacity, int64_t* out_start_out, f5_stream stream);
+
 /* ------------------------------------------------------------------------------------- silence clipping
  * What the reference drivers do to every prompt before anything else sees it (infer/utils_infer.py:348-361, 385-419: cut at pauses
  * to at most 12 s, trim the silent edges, append 50 ms of silence) and, on request, to the result (:784-793, remove_silence), both

@@ -17,6 +17,8 @@ PRECISIONS = {"f32": F5_PREC_F32, "fp32": F5_PREC_F32, "bf16": F5_PREC_BF16, "f1
 F5_BACKBONE_DIT, F5_BACKBONE_UNETT = 0, 1
 F5_ODE_EULER, F5_ODE_MIDPOINT = 0, 1
 ODE_METHODS = {"euler": F5_ODE_EULER, "midpoint": F5_ODE_MIDPOINT}
+F5_PCM_F32, F5_PCM_S16 = 0, 1
+PCM_FORMATS = {"f32": F5_PCM_F32, "s16": F5_PCM_S16}
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_MISH = 0, 1, 2, 3, 4
 PROFILE_CLASSES = ("gemm", "attention", "layernorm", "convpos", "misc", "text_encoder", "time_adaln")
 
@@ -135,6 +137,9 @@ SIGNATURES = {
     "f5_mel_resample_bank_count": (_i, [_p, C.POINTER(_i)]),
     "f5_mel_prepare_ragged": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _f, _p,
                               C.c_int64, _p, _p]),
+    "f5_wave_deliver_plan": (_i, [_i, C.c_int64, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "f5_wave_deliver": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                             _i, _i, _p, C.c_int64, C.POINTER(C.c_int64), _p]),
     "f5k_gemm": (_i, [_i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "f5k_gemm_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "f5k_attention": (_i, [_i, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),

@@ -1,5 +1,6 @@
-// The handle of the prompt stages (f5_mel): the mel front-end (mel.hip) and the preparation in front of it (prompt.hip) share its
-// workspace and staging ring; each call carves the arena anew, and calls on one handle are ordered by the caller's stream.
+// The handle of the prompt stages (f5_mel): the mel front-end (mel.hip), the preparation in front of it (prompt.hip) and the
+// delivery of generated audio at a client's rate (deliver.hip, which resamples with the same banks) share its workspace and
+// staging ring; each call carves the arena anew, and calls on one handle are ordered by the caller's stream.
 #pragma once
 #include <map>
 #include <utility>

@@ -10,44 +10,19 @@
 // The mono mix is computed twice (once per kernel) by the same instructions instead of being stored: an item's bits depend on
 // the item alone either way, and the stage keeps no signal-sized workspace.
 // The banks live transposed, [K, new]: consecutive output samples of a frame (consecutive phases) read consecutive words.
-#include <cmath>
-#include <numeric>
-
 #include "elementwise.h"
 #include "internal.h"
 #include "mel_handle.h"
+#include "resample.h"
 
 using namespace f5;
 #define fail f5_fail
 
 namespace {
 constexpr int RMS_TILE = 2048;      // samples per partial sum (part of the contract: it fixes the order of the f64 sum)
-constexpr int OUT_TILE = 1024;      // output samples a block aims at: 256 threads x 4
-constexpr int LDS_FLOATS = 8192;    // the staged window of a block, (F - 1) * orig + K samples, fits this or the block reads global
-constexpr long long MAX_BANK = 1LL << 20;
+constexpr int OUT_TILE = RS_OUT_TILE;
+constexpr int LDS_FLOATS = RS_LDS_FLOATS;   // a window that does not fit is read from global memory instead
 constexpr long long MAX_UNITS = 1LL << 30;   // tiles / blocks of one call (grid sizes and the segment tables are int)
-
-struct RatePair {
-    int orig = 1, nw = 1, width = 0, K = 1;   // orig == nw (== 1): the item is at the target rate already
-    bool same() const { return orig == nw; }
-};
-// orig, new and width exactly as infer.sinc_resample computes them (python evaluates the width in double); false: the bank
-// new * (2 width + orig) has more than 2^20 elements
-bool rate_pair(int sr, int target, RatePair* r) {
-    const int g = std::gcd(sr, target);
-    const int orig = sr / g, nw = target / g;
-    if (orig == nw) {
-        *r = RatePair();
-        return true;
-    }
-    const double base_freq = (double)std::min(orig, nw) * 0.99;
-    const double width = std::ceil((double)(6LL * orig) / base_freq);
-    if (width > (double)MAX_BANK) return false;
-    const long long K = 2 * (long long)width + orig;
-    if (K > MAX_BANK || K * nw > MAX_BANK) return false;
-    r->orig = orig; r->nw = nw; r->width = (int)width; r->K = (int)K;
-    return true;
-}
 
 struct PromptItem {
     long long in_start, out_start, out_len;   // elements from base / out; samples written
@@ -158,19 +133,12 @@ static __global__ __launch_bounds__(256) void prompt_resample_kernel(const float
             xi[q] = f * it.orig;
             bp[q] = (int)(l - (long long)f * it.nw);
         }
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!it.direct) {
-            for (int k = 0; k < it.K; ++k) {
-                const float* row = it.bank + (size_t)k * it.nw;
-                for (int q = 0; q < 4; ++q) acc[q] = acc[q] + row[bp[q]] * xs[xi[q] + k];
-            }
-        } else {
-            for (int k = 0; k < it.K; ++k) {
-                const float* row = it.bank + (size_t)k * it.nw;
-                for (int q = 0; q < 4; ++q)
-                    acc[q] = acc[q] + row[bp[q]] * levelled_sample(x, it.channels, it.n, win0 + xi[q] + k, scale, target_rms, rms);
-            }
-        }
+        float acc[4];
+        if (!it.direct)
+            resample_taps(it.bank, it.nw, it.K, xi, bp, [&](int e) { return xs[e]; }, acc);
+        else
+            resample_taps(it.bank, it.nw, it.K, xi, bp,
+                          [&](int e) { return levelled_sample(x, it.channels, it.n, win0 + e, scale, target_rms, rms); }, acc);
         float* dst = y + o_first + l0;
         if (l0 + 4 <= nout && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
             *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -280,9 +248,8 @@ extern "C" int f5_mel_prepare_ragged(f5_mel* m, const float* base, int32_t B, co
             direct[b] = 0;
             blks += (len[b] + OUT_TILE - 1) / OUT_TILE;
         } else {
-            int f = std::max(1, OUT_TILE / r.nw);
             direct[b] = r.K > LDS_FLOATS;
-            if (!direct[b]) f = std::min(f, (LDS_FLOATS - r.K) / r.orig + 1);
+            const int f = direct[b] ? std::max(1, OUT_TILE / r.nw) : frames_per_block(r);
             F[b] = f;
             const long long frames = (len[b] + r.nw - 1) / r.nw;
             blks += (frames + f - 1) / f;

@@ -1,5 +1,6 @@
-// The segment table of the waveform stages (edit.hip, silence.hip) and the linspace fade (wave.hip, edit.hip), once: the triple as
-// the caller writes it, the host check every entry point runs over an item's table, the device lookup, the fade weights.
+// The segment table of the waveform stages (edit.hip, silence.hip), the linspace fade (wave.hip, edit.hip) and the 16-bit view of a
+// sample (silence.hip, deliver.hip), once: the triple as the caller writes it, the host check every entry point runs over an item's
+// table, the device lookup, the quantiser, the fade weights.
 #pragma once
 #include <cstdint>
 
@@ -44,6 +45,14 @@ __device__ __forceinline__ int source_frame(const Seg* __restrict__ segs, int co
     }
     const Seg g = segs[k];
     return v < g.dst + g.frames && g.src >= 0 ? g.src + (v - g.dst) : -1;
+}
+
+// the 16-bit view of a sample (include/f5_hip.h): f32 multiply, round to nearest even, clamp; NaN is 0
+__device__ __forceinline__ int quantise(float x, float qscale) {
+    if (!(x == x)) return 0;
+    float v = rintf(x * qscale);
+    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
+    return (int)v;
 }
 
 // numpy's linspace(0, 1, n)[j] (*fi) and linspace(1, 0, n)[j] (*fo), j < n, step = 1 / (n - 1) from the host (0 for n < 2): separate

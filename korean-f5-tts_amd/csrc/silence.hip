@@ -44,14 +44,6 @@ struct Item {
 
 __host__ __device__ __forceinline__ long long ms_pos(int R, long long ms) { return ((long long)R * ms) / 1000; }
 
-// the 16-bit view of a sample (include/f5_hip.h): f32 multiply, round to nearest even, clamp; NaN is 0
-__device__ __forceinline__ int quantise(float x, float qscale) {
-    if (!(x == x)) return 0;
-    float v = rintf(x * qscale);
-    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
-    return (int)v;
-}
-
 // the last entry of start[0 .. n) that is <= r (start is ascending, start[0] <= r)
 template <typename T> __device__ __forceinline__ int last_not_above(const T* __restrict__ start, int n, T r) {
     int lo = 0, hi = n - 1;

@@ -39,7 +39,12 @@
                                                                  (VoiceBank), the chunks of all stretches as ragged batches with one prompt
                                                                  per item, ONE f5_wave_join: cross-fades inside a stretch, none between
 
-Out of scope here: Whisper ASR (an empty ref_text), forced alignment, resampling of the OUTPUT, pinyin /
+  deliver_waves / wave_deliver       eval/utils_eval.py:403-411  generated audio at a client's rate (8 to 192 kHz) as f32 or 16-bit PCM, on the
+                                                                 device (f5_wave_deliver): the resampler of the prompt stage, the other way
+  stream_chunks / open_stream        socket_server.py:72-177     the serving mode (stream.py): a voice prepared once, the first chunk of a
+                                                                 request short, packets at the client's rate while later chunks run
+
+Out of scope here: Whisper ASR (an empty ref_text), forced alignment, pinyin /
 Korean G2P tokenisers (text is tokenised per character through `vocab_char_map`, or as utf-8 bytes when the model has no
 vocabulary, exactly as CFM.sample does for list[str]).
 Only checkpoints are loaded with loaders that execute nothing from the file (safetensors, torch.load(weights_only=True)).
@@ -59,8 +64,9 @@ from .mel import resample_kernel, resampled_length
 from .script import parse_script, script_plan  # noqa: F401  (part of this module's surface)
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
-from .wave import (cross_fade_plan, join_plan, ragged_items, silence_flags, wave_crossfade, wave_gather, wave_join,  # noqa: F401
-                   wave_splice)                                                   # (the device calls: wave.py)
+from .stream import StreamSession, open_stream, packet_sizes, stream_chunks, stream_limits  # noqa: F401  (part of this module's surface)
+from .wave import (cross_fade_plan, deliver_plan, join_plan, ragged_items, silence_flags, wave_crossfade, wave_deliver,  # noqa: F401
+                   wave_gather, wave_join, wave_splice)                           # (the device calls: wave.py)
 
 target_sample_rate = SAMPLE_RATE
 n_mel_channels = MEL_DIM
@@ -637,6 +643,18 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
     mel, _ = model.sample(cond, text, duration, lens=lens, **sample_kw)
     wav, wav_lens = vocoder.decode_ragged(mel.to(torch.float32).permute(0, 2, 1), ends=ends.tolist(), starts=lens.tolist(), gain=gain)
     return wav, wav_lens, mel
+
+
+def deliver_waves(model, wav, lens, *, out_rate, sample_format="f32"):
+    """What synthesize_batch and synthesize_prompts return, at a client's rate and sample format: wav f32 [B, L_max] on the device
+    with item i in wav[i, :lens[i]] (or a list of 1-D waveforms; lens may then be None) -> a list of 1-D device tensors, f32 or
+    int16 ("s16"), each the finished item resampled from 24 kHz to out_rate (wave_deliver: ONE launch for the batch, the rows
+    read where they lie, nothing copied to the host)."""
+    if isinstance(wav, torch.Tensor):
+        if wav.dim() != 2 or lens is None or len(lens) != wav.shape[0]:
+            raise ValueError("deliver_waves: wav must be [B, L_max] with one length per row (or a list of 1-D waveforms)")
+        wav = [wav[b, :int(n)] for b, n in enumerate(lens)]
+    return wave_deliver(model.mel_spec, wav, out_rate=out_rate, sample_format=sample_format, final=True)
 
 
 def prompt_batch(prompts, gen_texts, *, speed=speed, target_rms=target_rms, mel_spec, device=None, prompt_on_device=False,

@@ -128,6 +128,67 @@ def wave_join(items, fades) -> torch.Tensor:
     return out
 
 
+def deliver_plan(out_rate: int, n: int, final: bool = True) -> tuple[int, int]:
+    """(len, ready) of a 24 kHz stream of n samples at out_rate (f5_wave_deliver_plan, pure host arithmetic): its length
+    there, and how many leading output samples are settled -- all of them once the stream is final, else those whose taps lie
+    inside the n samples.  A settled sample never changes as the stream grows."""
+    ln, ready = C.c_int64(), C.c_int64()
+    _lib.check(_lib.load().f5_wave_deliver_plan(int(out_rate), int(n), int(bool(final)), C.byref(ln), C.byref(ready)),
+               "f5_wave_deliver_plan")
+    return ln.value, ready.value
+
+
+def wave_deliver(mel_spec, items, *, out_rate: int, sample_format: str = "f32", ranges=None, final=True):
+    """Generated audio at a client's rate and sample format (f5_wave_deliver; the contract is in include/f5_hip.h): items are 1-D
+    f32 device tensors at 24 kHz with unit stride, read where they lie; `final` (one bool, or one per item) says whether an item
+    is a finished stream or the part of a growing one that exists so far; ranges[i] = (o0, o1) the output samples wanted, inside
+    [0, ready] of deliver_plan (None: everything that is settled).  mel_spec: the model's MelSpec, whose handle keeps the
+    (24000 -> out_rate) filter bank (the bank of a new rate is uploaded on its first use, which synchronises once).  Returns one
+    device tensor per item, f32 or int16 (sample_format "f32" / "s16": the 16-bit view of generated audio, y * 32767 rounded to
+    nearest even and clamped), views of one packed buffer.  One launch, no synchronisation; at most 65535 items."""
+    from .mel import _resample_bank_f32
+
+    items = list(items)
+    if not items:
+        raise ValueError("wave_deliver: no item")
+    if sample_format not in _lib.PCM_FORMATS:
+        raise ValueError(f"wave_deliver: sample_format {sample_format!r} (expected one of {sorted(_lib.PCM_FORMATS)})")
+    if mel_spec.target_sample_rate != 24_000:
+        raise ValueError(f"wave_deliver: the stage reads 24 kHz audio; this MelSpec runs at {mel_spec.target_sample_rate} Hz")
+    if any(t.dim() != 1 or t.dtype != torch.float32 or t.shape[0] < 1 or t.stride(0) != 1 for t in items):
+        raise ValueError("wave_deliver: every item must be a 1-D f32 tensor with unit stride and at least one sample")
+    if any(t.device.type != "cuda" for t in items):
+        raise RuntimeError("wave_deliver only runs on a GPU (there is no CPU path)")
+    B, out_rate = len(items), int(out_rate)
+    finals = [bool(final)] * B if isinstance(final, (bool, int)) else [bool(f) for f in final]
+    if len(finals) != B or (ranges is not None and len(ranges) != B):
+        raise ValueError(f"wave_deliver: {B} items need one `final` flag and one range each")
+    ns = [int(t.shape[0]) for t in items]
+    if ranges is None:
+        ranges = [(0, deliver_plan(out_rate, n, f)[1]) for n, f in zip(ns, finals)]
+    dev, base, starts = _placed(items, "wave_deliver")
+    fmt = _lib.PCM_FORMATS[sample_format]
+    per16 = 4 if fmt == _lib.F5_PCM_F32 else 8
+    total = 0
+    for o0, o1 in ranges:
+        total = (total + per16 - 1) // per16 * per16 + max(int(o1) - int(o0), 0)
+    out = torch.empty(max(total, 1), device=dev, dtype=torch.float32 if fmt == _lib.F5_PCM_F32 else torch.int16)
+    lib, h = _lib.load(), mel_spec._handle(dev)
+    at = (C.c_int64 * B)()
+    with torch.cuda.device(dev):
+        known = h.__dict__.setdefault("_deliver_banks", set())
+        if out_rate != 24_000 and out_rate not in known:
+            deliver_plan(out_rate, 0)                                     # (refuses the rate before a bank is built for it)
+            bank = _resample_bank_f32(24_000, out_rate)
+            _lib.check(lib.f5_mel_resample_bank(h, 24_000, out_rate, C.c_void_p(bank.data_ptr()), bank.numel(), _stream_ptr(dev)),
+                       "f5_mel_resample_bank")
+            known.add(out_rate)
+        _lib.check(lib.f5_wave_deliver(h, C.c_void_p(base), B, starts, _lib.int_array(ns), _lib.int_array(finals),
+                                       (C.c_int64 * B)(*[int(o0) for o0, _ in ranges]), (C.c_int64 * B)(*[int(o1) for _, o1 in ranges]),
+                                       out_rate, fmt, _ptr(out), total, at, _stream_ptr(dev)), "f5_wave_deliver")
+    return [out[a:a + int(o1) - int(o0)] for a, (o0, o1) in zip(at, ranges)]
+
+
 def silence_flags(items, shapes, rates, lens_ms, queries, qscale, tables=None):
     """One f5_silence_analyse over a ragged batch and ONE small device-to-host read: items are contiguous f32 device tensors
     holding [C_i, F_i] = shapes[i], lens_ms the length in ms of each analysed signal, queries (W, s, T, kind) tuples
