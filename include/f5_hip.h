@@ -662,6 +662,49 @@ typedef struct f5k_epi {
 } f5k_epi;
 int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const float* bias, int32_t M, int32_t N, int32_t K,
                  const f5k_epi* p, f5_stream stream);
+/* ---- The step glue of sample() (csrc/elementwise.h), each through the launch helper csrc/engine_impl.h itself calls.  Every pointer is
+ * a caller-owned DEVICE buffer of the stated shape (nothing is staged or copied); the call synchronises the stream.
+ * `prec` selects the element type T of a typed buffer: F5_PREC_F32 / F5_PREC_F16X3 float, F5_PREC_BF16 bf16, F5_PREC_F16 f16. */
+/* out T[rows, ldo] <- [x | cond or 0 | text] (pack_input_kernel): x, cond f32[B, N, mel], text_c / text_u f32[B, N, Dt]; batch rows
+ * b' >= B are the unconditional half.  rowmap NULL: the padded form, Bp * N rows.  Else the RowPack form: rowmap int2[*row_limit],
+ * row_limit int[1], lens int[B]; rows >= *row_limit and columns >= 2 mel + Dt are not written. */
+int f5k_pack_input(int32_t prec, const float* x, const float* cond, const float* text_c, const float* text_u, void* out, int32_t ldo,
+                   int32_t B, int32_t Bp, int32_t N, int32_t mel, int32_t Dt, int32_t drop_cond_first, const void* rowmap,
+                   const int32_t* row_limit, const int32_t* lens, f5_stream stream);
+/* rowmap int2[row_start[Bp]] <- (b', n) for every row of every segment; row_start int[Bp + 1] */
+int f5k_fill_rowmap(const int32_t* row_start, void* rowmap, int32_t Bp, f5_stream stream);
+/* One ODE update of y f32[B, N, mel] with dt = tgrid[step + 1] - tgrid[step] (tgrid f32, device) and v = p + (p - u) * cfg (use_cfg) or p:
+ * f5k_euler_cfg: y += dt * v in place, the new y also into traj_slot (or NULL); f5k_midpoint_half_cfg: y_mid = y + v * (dt / 2).
+ * row_start NULL: pred f32[(use_cfg ? 2 : 1), B, N, mel].  Else the RowPack form: pred f32[rows, mel] with the rows of batch row b' at
+ * row_start[b'] (int[(use_cfg ? 2 : 1) * B + 1]), lens int[B]; frames n >= lens[b] keep y (traj_slot / y_mid receive it). */
+int f5k_euler_cfg(float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start, const int32_t* lens,
+                  const float* tgrid, int32_t step, float cfg, int32_t use_cfg, float* traj_slot, f5_stream stream);
+int f5k_midpoint_half_cfg(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start,
+                          const int32_t* lens, const float* tgrid, int32_t step, float cfg, int32_t use_cfg, float* y_mid, f5_stream stream);
+/* out f32[rows, C] = rowmask[r] ? a[r] : (b ? b[r] : 0); rowmask uint8[rows]; out may be b */
+int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream);
+/* feat f32[S, 256] = [sin | cos] of (1000 t[s]) * freq[j]; t f32[S], freq f32[128] */
+int f5k_time_sinus(const float* t, const float* freq, float* feat, int32_t S, f5_stream stream);
+/* x_transformers RMSNorm: out T[R, D] = x / max(|x|_2, 1e-12) * sqrt(D) * g; x f32[R, D], g f32[D]; D % 4 == 0, D <= 2048.
+ * planar (T float, D % 32 == 0): rows stored pre-split */
+int f5k_xrmsnorm(int32_t prec, const float* x, void* out, int32_t R, int32_t D, const float* g, int32_t planar, f5_stream stream);
+/* UNetT glue.  assemble: x f32[Bp, N + 1, D] = [temb[b' * temb_stride] ; h[b']], h f32[Bp, N, D]; cat2: out T[rows, 2 D] = [x | skip]
+ * (planar as above); strip: out f32[Bp, N, C] = in[Bp, 1 + n, C] */
+int f5k_unett_assemble(const float* h, const float* temb, int32_t temb_stride, float* x, int32_t Bp, int32_t N, int32_t D, f5_stream stream);
+int f5k_cat2(int32_t prec, const float* x, const float* skip, void* out, int32_t rows, int32_t D, int32_t planar, f5_stream stream);
+int f5k_strip_first_token(const float* in, float* out, int32_t Bp, int32_t N, int32_t C, f5_stream stream);
+
+/* The work-buffer plan of an engine of config c, as pure host arithmetic (no HIP call, nothing launched, no device needed): the engine's
+ * own carve for the reservation (B, N, S) and its own placement of the side chain of a split-CFG (F5_SPLIT_CFG=1) call of
+ * call_B <= B utterances of call_N <= N frames, both on a dry-run arena.  *total_bytes: the arena size.  main_off / side_off
+ * int64[F5K_WORK_BUFFERS]: byte offset of each buffer in the order of F5K_WORK_NAMES, -1 where the config has no such buffer;
+ * side_off equals main_off for a buffer both chains share. */
+#define F5K_WORK_BUFFERS 39
+#define F5K_WORK_NAMES                                                                                                              \
+    "tdev feat th temb st mod lens lens_plain row_start rowmap step_cond text_c text_u tx_a tx_b tx_h1 grn_part uc acat h c1 x pred " \
+    "xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all"
+int f5k_work_plan(const f5_config* c, int32_t B, int32_t N, int32_t S, int32_t call_B, int32_t call_N, int64_t* total_bytes,
+                  int64_t* main_off, int64_t* side_off);
 /* repeated-launch timing of one GEMM shape (for bench/roofline): returns average microseconds per launch */
 int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tile_m, int32_t tile_n, int32_t iters,
                   float* avg_us, f5_stream stream);

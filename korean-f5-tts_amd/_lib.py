@@ -52,6 +52,9 @@ _i = C.c_int32
 _f = C.c_float
 
 F5K_EPI_STORE, F5K_EPI_GATE_RES, F5K_EPI_QKV, F5K_EPI_QKNORM = 0, 1, 2, 3
+# the buffers of f5k_work_plan, in its order (F5K_WORK_NAMES of include/f5_hip.h)
+F5K_WORK_NAMES = ("tdev feat th temb st mod lens lens_plain row_start rowmap step_cond text_c text_u tx_a tx_b tx_h1 grn_part uc acat h c1 x "
+                  "pred xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all").split()
 
 
 class f5k_epi(C.Structure):
@@ -149,6 +152,17 @@ SIGNATURES = {
     "f5k_layernorm_mod": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "f5k_layernorm_mod_ex": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _p]),
     "f5k_gemm_epi": (_i, [_i, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_epi), _p]),
+    "f5k_pack_input": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "f5k_fill_rowmap": (_i, [_p, _p, _i, _p]),
+    "f5k_euler_cfg": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _i, _p, _p]),
+    "f5k_midpoint_half_cfg": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _i, _p, _p]),
+    "f5k_select_rows": (_i, [_p, _p, _p, _p, C.c_int64, _i, _p]),
+    "f5k_time_sinus": (_i, [_p, _p, _p, _i, _p]),
+    "f5k_xrmsnorm": (_i, [_i, _p, _p, _i, _i, _p, _i, _p]),
+    "f5k_unett_assemble": (_i, [_p, _p, _i, _p, _i, _i, _i, _p]),
+    "f5k_cat2": (_i, [_i, _p, _p, _p, _i, _i, _i, _p]),
+    "f5k_strip_first_token": (_i, [_p, _p, _i, _i, _i, _p]),
+    "f5k_work_plan": (_i, [C.POINTER(f5_config), _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "f5k_gemm_time": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
     "f5_profile_enable": (_i, [_p, _i]),
     "f5_profile_read": (_i, [_p, C.POINTER(_f), C.POINTER(_i), C.POINTER(C.c_double), _i]),

@@ -6,6 +6,17 @@
 
 namespace f5 {
 
+// The launch_* helpers below, each next to its kernel, are the launches of sample()'s step glue: engine_impl.h and the kernel-level
+// entry points (kapi.hip f5k_*) both call them, so a test drives the grid and the arguments the engine uses.  They only enqueue; the
+// caller reads hipGetLastError().
+
+// blocks of a grid-stride launch over `total` work items: at most `cap`, the loop covers the rest
+inline int ew_blocks(long total, int per_block = 256, int cap = 4096) {
+    long b = (total + per_block - 1) / per_block;
+    if (b < 1) b = 1;
+    return (int)(b > cap ? cap : b);
+}
+
 // ------------------------------------------------------------------------------------------- LayerNorm
 // out[r, :] = LN(x[r, :]; eps) * A + B with either
 //   modulate: A = 1 + scale[b(r), :], B = shift[b(r), :]   (AdaLayerNorm, modules.py:314-320,335-341,680-693)
@@ -106,6 +117,10 @@ __global__ __launch_bounds__(256) void xrmsnorm_kernel(const float* __restrict__
         }
     }
 }
+template <typename TO>
+inline void launch_xrmsnorm(hipStream_t s, const float* x, TO* out, int rows, int D, const float* g, int planar) {
+    hipLaunchKernelGGL((xrmsnorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, x, D, out, D, rows, D, g, planar);
+}
 
 // --------------------------------------------------------------------------------- input-embedding operand
 // A[b', n, :] = [ x[b, n, :mel] | cond[b, n, :mel] (0 for the uncond half / drop_audio_cond) | text[b', n, :Dt] ]
@@ -138,6 +153,14 @@ __global__ void pack_input_kernel(const float* __restrict__ x, const float* __re
         store4(out + (size_t)row * ldo + c, v.x, v.y, v.z, v.w);
     }
 }
+// (the grid is that of the padded batch, Bp * N rows, also when a rowmap packs them)
+template <typename T>
+inline void launch_pack_input(hipStream_t s, const float* x, const float* cond, const float* text_c, const float* text_u, T* out, int ldo, int B,
+                              int Bp, int N, int mel, int Dt, int drop_cond_first, const int2* rowmap, const int* row_limit, const int* lens) {
+    const int rows = Bp * N, kin = 2 * mel + Dt;
+    hipLaunchKernelGGL((pack_input_kernel<T>), dim3(ew_blocks((long)rows * kin / 4)), dim3(256), 0, s, x, cond, text_c, text_u, out, ldo, B, Bp,
+                       N, mel, Dt, drop_cond_first, rowmap, row_limit, lens);
+}
 
 // ------------------------------------------------------------------------------------------ UNetT glue
 // x[b', 0, :] = t_emb[b' or shared]; x[b', 1 + n, :] = h[b', n, :]      (unett.py:244: cat([t[:, None], x], dim=1))
@@ -154,6 +177,10 @@ static __global__ void unett_assemble_kernel(const float* __restrict__ h, const 
         reinterpret_cast<float4*>(x)[i] = v;
     }
 }
+inline void launch_unett_assemble(hipStream_t s, const float* h, const float* temb, int temb_stride, float* x, int Bp, int N, int D) {
+    const int rows = Bp * (N + 1);
+    hipLaunchKernelGGL(unett_assemble_kernel, dim3(ew_blocks((long)rows * D / 4)), dim3(256), 0, s, h, temb, temb_stride, x, Bp, N, D);
+}
 // out[r, :] = [x[r, :] | skip[r, :]] converted to T   (unett.py:266: cat((x, skip), dim=-1))
 // planar (T = float, F5_PREC_F16X3): the row is written pre-split (store4_planar) -- the A operand of an AWSplit GEMM (GemmOperands, ring or ping-pong)
 template <typename T>
@@ -168,6 +195,9 @@ __global__ void cat2_kernel(const float* __restrict__ x, const float* __restrict
         store4_at(out + r * 2 * D, c * 4, planar, v.x, v.y, v.z, v.w);
     }
 }
+template <typename T> inline void launch_cat2(hipStream_t s, const float* x, const float* skip, T* out, int rows, int D, int planar) {
+    hipLaunchKernelGGL((cat2_kernel<T>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s, x, skip, out, (long)rows, D, planar);
+}
 // pred[b', n, :] = pred_all[b', 1 + n, :]     (unett.py:278: norm_out(x)[:, 1:, :])
 static __global__ void strip_first_token_kernel(const float* __restrict__ in, float* __restrict__ out, int Bp, int N, int C) {
     const int c4 = C / 4;
@@ -178,6 +208,10 @@ static __global__ void strip_first_token_kernel(const float* __restrict__ in, fl
         const int n = (int)(row % N), b = (int)(row / N);
         reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(in + ((size_t)b * (N + 1) + n + 1) * C)[c];
     }
+}
+inline void launch_strip_first_token(hipStream_t s, const float* in, float* out, int Bp, int N, int C) {
+    const int rows_in = Bp * N;
+    hipLaunchKernelGGL(strip_first_token_kernel, dim3(ew_blocks((long)rows_in * C / 4)), dim3(256), 0, s, in, out, Bp, N, C);
 }
 
 // ------------------------------------------------------------------------------------- CFG + Euler update
@@ -278,11 +312,35 @@ static __global__ void midpoint_half_cfg_packed_kernel(const float* __restrict__
         reinterpret_cast<float4*>(y_mid)[i] = yy;
     }
 }
+// One ODE update of B utterances as sample_body launches it: the packed form when the backbone ran on packed rows (row_start non-null).
+// y += dt * v into y and the trajectory slot (may be null) ...
+inline void launch_euler_cfg(hipStream_t s, float* y, const float* pred, int B, int N, int mel, const int* row_start, const int* lens,
+                             const float* tgrid, int step, float cfg, int use_cfg, float* traj_slot) {
+    const long n = (long)B * N * mel;
+    if (row_start)
+        hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, y, pred, B, N, mel, row_start, lens, tgrid, step,
+                           cfg, use_cfg, traj_slot);
+    else
+        hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, y, pred, n, tgrid, step, cfg, use_cfg, traj_slot);
+}
+// ... and y_mid = y + v * dt / 2
+inline void launch_midpoint_half_cfg(hipStream_t s, const float* y, const float* pred, int B, int N, int mel, const int* row_start,
+                                     const int* lens, const float* tgrid, int step, float cfg, int use_cfg, float* y_mid) {
+    const long n = (long)B * N * mel;
+    if (row_start)
+        hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, y, pred, B, N, mel, row_start, lens, tgrid,
+                           step, cfg, use_cfg, y_mid);
+    else
+        hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, y, pred, n, tgrid, step, cfg, use_cfg, y_mid);
+}
 
 // rowmap[row_start[b'] + n] = (b', n) for n < row_start[b' + 1] - row_start[b']   (one block per batch row)
 static __global__ void fill_rowmap_kernel(const int* __restrict__ row_start, int2* __restrict__ rowmap) {
     const int bp = blockIdx.x, r0 = row_start[bp], cnt = row_start[bp + 1] - r0;
     for (int n = threadIdx.x; n < cnt; n += blockDim.x) rowmap[r0 + n] = make_int2(bp, n);
+}
+inline void launch_fill_rowmap(hipStream_t s, const int* row_start, int2* rowmap, int Bp) {
+    hipLaunchKernelGGL(fill_rowmap_kernel, dim3(Bp), dim3(256), 0, s, row_start, rowmap);
 }
 
 // out = where(mask, a, b) row-wise: cfm.py:151-153 (step_cond) and :221-223 (final out)
@@ -298,6 +356,9 @@ static __global__ void select_rows_kernel(const float* a, const float* bsrc, con
         reinterpret_cast<float4*>(out)[i] = v;
     }
 }
+inline void launch_select_rows(hipStream_t s, const float* a, const float* b, const unsigned char* rowmask, float* out, long rows, int C) {
+    hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, a, b, rowmask, out, rows, C);
+}
 
 // ------------------------------------------------------------------------------------ time-step features
 // feat[s, j] = sin(arg), feat[s, 128 + j] = cos(arg), arg = (1000 * t[s]) * freq[j]   (modules.py:157-164)
@@ -309,6 +370,9 @@ static __global__ void time_sinus_kernel(const float* __restrict__ t, const floa
     const float arg = (1000.0f * t[s]) * freq[j];
     feat[(size_t)s * 2 * half + j] = sinf(arg);
     feat[(size_t)s * 2 * half + half + j] = cosf(arg);
+}
+inline void launch_time_sinus(hipStream_t s, const float* t, const float* freq, float* feat, int S) {
+    hipLaunchKernelGGL(time_sinus_kernel, dim3((S * 128 + 255) / 256), dim3(256), 0, s, t, freq, feat, S, 128);
 }
 
 static __global__ void act_kernel(const float* __restrict__ in, float* __restrict__ out, long n, int act) {
@@ -773,12 +837,6 @@ static __global__ __launch_bounds__(256) void rope_frag_kernel(const float* __re
 static __global__ void zero_lo_planar_kernel(float* __restrict__ w, long blocks) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < blocks * 4; i += (long)gridDim.x * blockDim.x)
         reinterpret_cast<float4*>(w + (i >> 2) * 32)[4 + (i & 3)] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-inline int ew_blocks(long total, int per_block = 256, int cap = 4096) {
-    long b = (total + per_block - 1) / per_block;
-    if (b < 1) b = 1;
-    return (int)(b > cap ? cap : b);
 }
 
 }  // namespace f5

@@ -166,6 +166,18 @@ extern "C" int f5_reserve(f5_engine* e, int32_t B, int32_t N, int32_t S) {
     if (!e || B <= 0 || N <= 0 || S <= 0) return fail(F5_EINVAL, "f5_reserve: bad arguments");
     return ensure_arena(e, B, N, S);
 }
+// The work-buffer plan of an engine of this config, as pure host arithmetic: the real carve_into and second_half on a dry-run arena.  The
+// engine object lives for the call only; no HIP call is made.
+extern "C" int f5k_work_plan(const f5_config* c, int32_t B, int32_t N, int32_t S, int32_t call_B, int32_t call_N, int64_t* total_bytes,
+                             int64_t* main_off, int64_t* side_off) {
+    if (!c || !total_bytes || !main_off || !side_off || B <= 0 || N <= 0 || S <= 0 || call_B <= 0 || call_B > B || call_N <= 0 || call_N > N)
+        return fail(F5_EINVAL, "f5k_work_plan: bad arguments (0 < call_B <= B, 0 < call_N <= N, S > 0)");
+    f5_engine* e = nullptr;
+    CHK(f5_create(c, &e));
+    *total_bytes = (int64_t)F5_OPS(e, work_plan(e, B, N, S, call_B, call_N, main_off, side_off));
+    delete e;   // (nothing of it ever reached a device: no synchronisation, unlike f5_destroy)
+    return F5_OK;
+}
 // Utterances per backbone call inside sample(): the ODE state of different utterances never interacts, so a large batch
 // is stepped in chunks whose activations (x 4 B, xn, q, k, v, ffh 2 B per element: ~17 KB per row) stay inside the 256 MB
 // Infinity Cache between the kernels of a block, instead of streaming every intermediate through HBM (C3: 65,536 rows).

@@ -376,7 +376,7 @@ template <typename T> static int run_time_path(f5_engine* e, Work<T>& w, int S, 
     Packed<T>& P = packed<T>(e);
     const int D = e->cfg.dim;
     return e->prof.timed(PC_TIME, s, [&]() -> int {
-        hipLaunchKernelGGL(time_sinus_kernel, dim3((S * 128 + 255) / 256), dim3(256), 0, s, w.tdev, P.time_freqs, w.feat, S, 128);
+        launch_time_sinus(s, w.tdev, P.time_freqs, w.feat, S);
         KCHK();
         HIPCHK(launch_gemm<float>(s, w.feat, 256, P.time0.w, P.time0.ldw, S, D, 256,
                                   EpiStore<float>{w.th, D, P.time0.b, F5_ACT_SILU}));
@@ -495,8 +495,8 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
         ip = &P.in_proj_f; cw = P.conv_w_f; kp = P.conv_kp_f; cs = convpos_can_split(D);
     }
     HIPCHK(pr.timed(PC_MISC, s, [&] {
-        hipLaunchKernelGGL((pack_input_kernel<U>), dim3(ew_blocks((long)rows * e->kin / 4)), dim3(256), 0, s, y, cond, text_first, text_second,
-                           acat, e->kin_pad, B, Bp, N, c.mel_dim, c.text_dim, drop_cond_first, pk.rowmap, f.ml(), f.lens_dev);
+        launch_pack_input<U>(s, y, cond, text_first, text_second, acat, e->kin_pad, B, Bp, N, c.mel_dim, c.text_dim, drop_cond_first, pk.rowmap,
+                             f.ml(), f.lens_dev);
         return hipGetLastError();
     }));
     auto ablate_round = [&](int bit, const float* src, float* to, long n) -> const float* {   // diagnostic F5_X3_ABLATE: an unsplit f32 operand as f16 sees it
@@ -645,8 +645,7 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
     if (long_skip) {   // x = long_skip_connection(cat((x, residual), dim=-1))   (dit.py:323-324)
         auto cat_skip = [&](auto* cat) {
             return pr.timed(PC_MISC, s, [&] {
-                hipLaunchKernelGGL((cat2_kernel<std::remove_pointer_t<decltype(cat)>>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s,
-                                   w.x, w.h, cat, (long)rows, D);
+                launch_cat2(s, w.x, w.h, cat, rows, D, 0);
                 return hipGetLastError();
             });
         };
@@ -694,16 +693,14 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
     const int half = c.depth / 2;
     auto slot = [&](int l) { return w.skips + (size_t)l * rows * D; };
     HIPCHK(pr.timed(PC_MISC, s, [&] {
-        hipLaunchKernelGGL(unett_assemble_kernel, dim3(ew_blocks((long)rows * D / 4)), dim3(256), 0, s, emb, temb, temb_stride,
-                           half > 0 ? slot(0) : w.x, Bp, N, D);
+        launch_unett_assemble(s, emb, temb, temb_stride, half > 0 ? slot(0) : w.x, Bp, N, D);
         return hipGetLastError();
     }));
     const FwdCtx f{e, s, B, Bp, Nt, rows, lens_dev, RowPack{}};   // the blocks: N + 1 tokens per row; lens_dev holds len + 1 for UNetT
     const int pl = f.pl();
     auto rmsnorm = [&](const float* x, auto* out, const float* g, int planar) {   // out (rows of T, or pre-split f32 rows) = RMSNorm(x) * g
         return pr.timed(PC_LN, s, [&] {
-            hipLaunchKernelGGL((xrmsnorm_kernel<std::remove_pointer_t<decltype(out)>>), dim3((rows + 3) / 4), dim3(256), 0, s, x, D, out, D, rows, D, g,
-                               planar);
+            launch_xrmsnorm(s, x, out, rows, D, g, planar);
             return hipGetLastError();
         });
     };
@@ -714,8 +711,7 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
         if (l >= half) {
             const float* skip = w.skips + (size_t)(c.depth - 1 - l) * rows * D;   // LIFO (skips.pop())
             HIPCHK(pr.timed(PC_MISC, s, [&] {
-                hipLaunchKernelGGL((cat2_kernel<T>), dim3(ew_blocks((long)rows * 2 * D / 4)), dim3(256), 0, s, w.x, skip, w.cat2,
-                                   (long)rows, D, pl);   // (F5_PREC_F16X3: pre-split, so that the projection runs on pre-split operands too)
+                launch_cat2(s, w.x, skip, w.cat2, rows, D, pl);   // (F5_PREC_F16X3: pre-split, so that the projection runs on pre-split operands too)
                 return hipGetLastError();
             }));
             f.ablate(512, w.cat2, 2 * D);   // diagnostic: ... and its A operand as plain f16
@@ -734,7 +730,7 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
         CHK((project_out<T, T>(f, w.xn, w.pred_all)));
     }
     HIPCHK(pr.timed(PC_MISC, s, [&] {
-        hipLaunchKernelGGL(strip_first_token_kernel, dim3(ew_blocks((long)rows_in * mel / 4)), dim3(256), 0, s, w.pred_all, w.pred, Bp, N, mel);
+        launch_strip_first_token(s, w.pred_all, w.pred, Bp, N, mel);
         return hipGetLastError();
     }));
     return F5_OK;
@@ -824,13 +820,14 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
     HIPCHK(hipMemcpyAsync(out, w.pred, (size_t)Bp * N * e->cfg.mel_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     return F5_OK;
 }
-// the second (unconditional) half of every [2B ...] activation buffer, as a Work of its own
-// (open finding, ADVICE.md first item: the offsets of acat and cat2 do not follow F5_PREC_F16P / F5_OPT_LONG_SKIP)
+// the second (unconditional) half of every [2B ...] activation buffer a DiT forward writes, as a Work of its own: behind the B * N rows
+// of the first half, in the element type the forward writes each buffer in (F5_PREC_F16P: acat and the long-skip cat2 hold f32 rows)
 template <typename T> static Work<T> second_half(const f5_engine* e, const Work<T>& w, int B, int N) {
     const f5_config& c = e->cfg;
     const size_t rows = (size_t)B * N;
     Work<T> h = w;
-    h.acat = w.acat + rows * e->kin_pad;
+    const size_t io = e->io_split ? sizeof(float) / sizeof(T) : 1;
+    h.acat = w.acat + rows * e->kin_pad * io;
     h.h = w.h + rows * c.dim;
     h.c1 = w.c1 + rows * c.dim;
     h.x = w.x + rows * c.dim;
@@ -841,6 +838,7 @@ template <typename T> static Work<T> second_half(const f5_engine* e, const Work<
     h.ao = w.ao + rows * e->inner;
     h.vt = w.vt + (size_t)B * c.heads * 64 * w.Npad;
     h.ffh = w.ffh + rows * c.ff_dim;
+    if (c.options & F5_OPT_LONG_SKIP) h.cat2 = w.cat2 + rows * 2 * c.dim * io;
     return h;
 }
 // The unconditional text embedding (every token replaced by the filler) of a single utterance depends only on the weights
@@ -862,8 +860,7 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
     const int64_t* text = reinterpret_cast<const int64_t*>(w.in_text);
     // step_cond = where(cond_mask, cond, 0)   (cfm.py:151-153)
     HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-        hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)nullptr,
-                           w.in_mask, w.step_cond, (long)B * N, mel);
+        launch_select_rows(s, w.in_cond, nullptr, w.in_mask, w.step_cond, (long)B * N, mel);
         return hipGetLastError();
     }));
     CHK(run_time_path<T>(e, w, p.evals * p.steps, s));  // features of every evaluation time
@@ -895,7 +892,7 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         if (!p.pack) break;
         const int* rs = w.row_start + p.row_start_at(k);
         packs[k.idx] = RowPack{rs, w.rowmap + p.rowmap_at(k), rs + p.halves * k.bc, k.rows, k.sq};
-        hipLaunchKernelGGL(fill_rowmap_kernel, dim3(p.halves * k.bc), dim3(256), 0, s, rs, w.rowmap + p.rowmap_at(k));
+        launch_fill_rowmap(s, rs, w.rowmap + p.rowmap_at(k), p.halves * k.bc);
         KCHK();
     }
     // one (CFG) evaluation of a chunk at state x with the vectors of time row `row`, into w.pred
@@ -917,29 +914,19 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
     // y_mid = y + f(t[i], y) * dt/2
     auto half_update = [&](const SamplePlan::Chunk& k, const RowPack& pk, int i) {
         const size_t yo = p.frame_at(k) * mel;
-        const long n = (long)k.bc * N * mel;
         return e->prof.timed(PC_MISC, s, [&] {
-            if (pk)
-                hipLaunchKernelGGL(midpoint_half_cfg_packed_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, k.bc, N, mel,
-                                   pk.row_start, lens_dev + p.lens_at(k), tgrid, i, p.cfg_strength, p.use_cfg ? 1 : 0, w.y_mid + yo);
-            else
-                hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, n, tgrid, i,
-                                   p.cfg_strength, p.use_cfg ? 1 : 0, w.y_mid + yo);
+            launch_midpoint_half_cfg(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr, tgrid, i,
+                                     p.cfg_strength, p.use_cfg ? 1 : 0, w.y_mid + yo);
             return hipGetLastError();
         });
     };
     // y += f * dt (f: Euler at t[i], y; midpoint at t[i] + dt/2, y_mid), copied to the trajectory slot of step i + 1
     auto full_update = [&](const SamplePlan::Chunk& k, const RowPack& pk, int i) {
         const size_t yo = p.frame_at(k) * mel;
-        const long n = (long)k.bc * N * mel;
         float* slot = p.want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
         return e->prof.timed(PC_MISC, s, [&] {
-            if (pk)
-                hipLaunchKernelGGL(euler_cfg_packed_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, k.bc, N, mel,
-                                   pk.row_start, lens_dev + p.lens_at(k), tgrid, i, p.cfg_strength, p.use_cfg ? 1 : 0, slot);
-            else
-                hipLaunchKernelGGL(euler_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, w.y + yo, w.pred, n, tgrid, i,
-                                   p.cfg_strength, p.use_cfg ? 1 : 0, slot);
+            launch_euler_cfg(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr, tgrid, i, p.cfg_strength,
+                             p.use_cfg ? 1 : 0, slot);
             return hipGetLastError();
         });
     };
@@ -956,8 +943,7 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         }
     // out = where(cond_mask, cond, y)   (cfm.py:221-223)
     HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-        hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(half / 4)), dim3(256), 0, s, w.in_cond, (const float*)w.y, w.in_mask,
-                           w.out_buf, (long)B * N, mel);
+        launch_select_rows(s, w.in_cond, w.y, w.in_mask, w.out_buf, (long)B * N, mel);
         return hipGetLastError();
     }));
     return F5_OK;
@@ -1093,4 +1079,25 @@ template <typename T> size_t EngineOps<T>::plan_bytes(const f5_engine* e, int B,
     Arena dry;  // base == nullptr: measures only
     Work<T> w;
     return carve_into<T>(e, dry, w, B, N, S);
+}
+// f5k_work_plan: where carve_into puts every buffer of Work<T> for the reservation (B, N, S), and where second_half puts the side chain of a
+// split-CFG call of call_B x call_N, as byte offsets into the arena (-1: not carved), in the order of F5K_WORK_NAMES (include/f5_hip.h)
+template <typename T>
+size_t EngineOps<T>::work_plan(const f5_engine* e, int B, int N, int S, int call_B, int call_N, int64_t* main_off, int64_t* side_off) {
+    Arena dry;
+    dry.base = reinterpret_cast<char*>((size_t)1 << 30);   // a dry run from a non-null address (nothing is dereferenced): null then means "not carved"
+    Work<T> w;
+    const size_t total = carve_into<T>(e, dry, w, B, N, S);
+    const Work<T> h = second_half<T>(e, w, call_B, call_N);
+    auto put = [&](int64_t* out, const Work<T>& v) {
+        const void* p[] = {v.tdev, v.feat, v.th, v.temb, v.st, v.mod, v.lens, v.lens_plain, v.row_start, v.rowmap, v.step_cond, v.text_c, v.text_u,
+                           v.tx_a, v.tx_b, v.tx_h1, v.grn_part, v.uc, v.acat, v.h, v.c1, v.x, v.pred, v.xn, v.q, v.k, v.ao, v.vt, v.ffh, v.in_cond,
+                           v.y, v.y_mid, v.out_buf, v.traj_buf, v.in_mask, v.in_text, v.cat2, v.skips, v.pred_all};
+        static_assert(sizeof(p) / sizeof(p[0]) == F5K_WORK_BUFFERS, "one entry per name of F5K_WORK_NAMES");
+        for (int i = 0; i < F5K_WORK_BUFFERS; ++i) out[i] = p[i] ? (int64_t)(static_cast<const char*>(p[i]) - dry.base) : -1;
+    };
+    put(main_off, w);
+    put(side_off, h);
+    dry.base = nullptr;   // (not an allocation: nothing to free)
+    return total;
 }

@@ -366,6 +366,7 @@ std::vector<float> time_table(const float* t_host, int steps, int method);
 template <typename T> struct EngineOps {
     static int finalize(f5_engine* e, hipStream_t s);
     static size_t plan_bytes(const f5_engine* e, int B, int N, int S);
+    static size_t work_plan(const f5_engine* e, int B, int N, int S, int call_B, int call_N, int64_t* main_off, int64_t* side_off);
     static int text_embed(f5_engine* e, const int64_t* text, int B, int nt, const int32_t* lens_host, int N, int drop_text,
                           float* out, hipStream_t s);
     static int forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,

@@ -333,7 +333,7 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
         HIPCHK(hipMemcpy(rs.p, p.row_start_host, ((size_t)p.Bp + 1) * 4, hipMemcpyHostToDevice));
         HIPCHK(rowmap.alloc((size_t)M));
         HIPCHK(hipMemsetAsync(rowmap.p, 0, (size_t)M * sizeof(int2), s));
-        hipLaunchKernelGGL(fill_rowmap_kernel, dim3(p.Bp), dim3(256), 0, s, rs.p, rowmap.p);
+        launch_fill_rowmap(s, rs.p, rowmap.p, p.Bp);
         KCHK();
         ml = rs.p + p.Bp;   // m_limit = row_start[Bp] (sample_body: RowPack::rows_dev)
     }
@@ -453,4 +453,101 @@ extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const 
     }
     const GemmOperands ops = prec != F5_PREC_F16X3 ? GemmOperands::Plain : p->a_presplit ? GemmOperands::AWSplit : GemmOperands::WSplit;
     return F5K_BY_PREC(prec, gemm_epi_impl, A, W, bias, M, N, K, *p, ops, (hipStream_t)stream);
+}
+
+// -------------------------------------------------------------------------------------------- step glue
+// The glue kernels of sample() through the launch helpers of elementwise.h, the ones engine_impl.h calls: device buffers in, device
+// buffers out, nothing staged.  Only the arguments' shape rules are checked here; the buffers' sizes are the caller's.
+static int glue_done(hipStream_t s) {
+    KCHK();
+    HIPCHK(hipStreamSynchronize(s));
+    return F5_OK;
+}
+static bool glue_prec_ok(int32_t prec) { return prec == F5_PREC_F32 || prec == F5_PREC_F16X3 || prec == F5_PREC_BF16 || prec == F5_PREC_F16; }
+
+template <typename T>
+static int pack_input_impl(const float* x, const float* cond, const float* tc, const float* tu, void* out, int ldo, int B, int Bp, int N, int mel,
+                           int Dt, int drop, const int2* rowmap, const int* row_limit, const int* lens, hipStream_t s) {
+    launch_pack_input<T>(s, x, cond, tc, tu, static_cast<T*>(out), ldo, B, Bp, N, mel, Dt, drop, rowmap, row_limit, lens);
+    return glue_done(s);
+}
+extern "C" int f5k_pack_input(int32_t prec, const float* x, const float* cond, const float* text_c, const float* text_u, void* out, int32_t ldo,
+                              int32_t B, int32_t Bp, int32_t N, int32_t mel, int32_t Dt, int32_t drop_cond_first, const void* rowmap,
+                              const int32_t* row_limit, const int32_t* lens, f5_stream stream) {
+    if (!x || !cond || !text_c || !text_u || !out || B <= 0 || (Bp != B && Bp != 2 * B) || N <= 0 || mel <= 0 || Dt <= 0 || mel % 4 || Dt % 4 ||
+        ldo < 2 * mel + Dt || ldo % 4)
+        return fail(F5_EINVAL, "f5k_pack_input: bad arguments (Bp = B or 2 B; mel, Dt, ldo %% 4 == 0; ldo >= 2 mel + Dt)");
+    if (!glue_prec_ok(prec)) return fail(F5_EINVAL, "f5k_pack_input: precision must be f32, f16x3, bf16 or f16");
+    if ((rowmap != nullptr) != (row_limit != nullptr) || (rowmap != nullptr) != (lens != nullptr))
+        return fail(F5_EINVAL, "f5k_pack_input: rowmap, row_limit and lens come together (RowPack) or not at all");
+    return F5K_BY_PREC(prec, pack_input_impl, x, cond, text_c, text_u, out, ldo, B, Bp, N, mel, Dt, drop_cond_first,
+                       static_cast<const int2*>(rowmap), row_limit, lens, (hipStream_t)stream);
+}
+extern "C" int f5k_fill_rowmap(const int32_t* row_start, void* rowmap, int32_t Bp, f5_stream stream) {
+    if (!row_start || !rowmap || Bp <= 0) return fail(F5_EINVAL, "f5k_fill_rowmap: bad arguments");
+    launch_fill_rowmap((hipStream_t)stream, row_start, static_cast<int2*>(rowmap), Bp);
+    return glue_done((hipStream_t)stream);
+}
+static int ode_args(const char* who, const void* y, const void* pred, int B, int N, int mel, const void* row_start, const void* lens,
+                    const void* tgrid, int step, const void* out, bool need_out) {
+    if (!y || !pred || !tgrid || (need_out && !out) || B <= 0 || N <= 0 || mel <= 0 || mel % 4 || step < 0 || (row_start != nullptr) != (lens != nullptr))
+        return fail(F5_EINVAL, "%s: bad arguments (mel %% 4 == 0; row_start and lens come together)", who);
+    return F5_OK;
+}
+extern "C" int f5k_euler_cfg(float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start, const int32_t* lens,
+                             const float* tgrid, int32_t step, float cfg, int32_t use_cfg, float* traj_slot, f5_stream stream) {
+    CHK(ode_args("f5k_euler_cfg", y, pred, B, N, mel, row_start, lens, tgrid, step, traj_slot, false));
+    launch_euler_cfg((hipStream_t)stream, y, pred, B, N, mel, row_start, lens, tgrid, step, cfg, use_cfg ? 1 : 0, traj_slot);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_midpoint_half_cfg(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start,
+                                     const int32_t* lens, const float* tgrid, int32_t step, float cfg, int32_t use_cfg, float* y_mid,
+                                     f5_stream stream) {
+    CHK(ode_args("f5k_midpoint_half_cfg", y, pred, B, N, mel, row_start, lens, tgrid, step, y_mid, true));
+    launch_midpoint_half_cfg((hipStream_t)stream, y, pred, B, N, mel, row_start, lens, tgrid, step, cfg, use_cfg ? 1 : 0, y_mid);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream) {
+    if (!a || !rowmask || !out || rows <= 0 || C <= 0 || C % 4) return fail(F5_EINVAL, "f5k_select_rows: bad arguments (C %% 4 == 0)");
+    launch_select_rows((hipStream_t)stream, a, b, rowmask, out, (long)rows, C);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_time_sinus(const float* t, const float* freq, float* feat, int32_t S, f5_stream stream) {
+    if (!t || !freq || !feat || S <= 0) return fail(F5_EINVAL, "f5k_time_sinus: bad arguments");
+    launch_time_sinus((hipStream_t)stream, t, freq, feat, S);
+    return glue_done((hipStream_t)stream);
+}
+template <typename TO> static int xrmsnorm_impl(const float* x, void* out, int R, int D, const float* g, int planar, hipStream_t s) {
+    launch_xrmsnorm<TO>(s, x, static_cast<TO*>(out), R, D, g, planar);
+    return glue_done(s);
+}
+// planar: pre-split rows exist for f32 rows of whole 32-element blocks only
+static bool planar_ok(int32_t prec, int planar, int D) {
+    return planar == 0 || (planar == 1 && (prec == F5_PREC_F32 || prec == F5_PREC_F16X3) && D % 32 == 0);
+}
+extern "C" int f5k_xrmsnorm(int32_t prec, const float* x, void* out, int32_t R, int32_t D, const float* g, int32_t planar, f5_stream stream) {
+    if (!x || !out || !g || R <= 0 || D <= 0 || D % 4 || D > 2048 || !glue_prec_ok(prec) || !planar_ok(prec, planar, D))
+        return fail(F5_EINVAL, "f5k_xrmsnorm: bad arguments (D %% 4 == 0, D <= 2048; planar: an f32 output and D %% 32 == 0)");
+    return F5K_BY_PREC(prec, xrmsnorm_impl, x, out, R, D, g, planar, (hipStream_t)stream);
+}
+extern "C" int f5k_unett_assemble(const float* h, const float* temb, int32_t temb_stride, float* x, int32_t Bp, int32_t N, int32_t D,
+                                  f5_stream stream) {
+    if (!h || !temb || !x || Bp <= 0 || N <= 0 || D <= 0 || D % 4 || (temb_stride != 0 && temb_stride != D))
+        return fail(F5_EINVAL, "f5k_unett_assemble: bad arguments (D %% 4 == 0, temb_stride 0 or D)");
+    launch_unett_assemble((hipStream_t)stream, h, temb, temb_stride, x, Bp, N, D);
+    return glue_done((hipStream_t)stream);
+}
+template <typename T> static int cat2_impl(const float* x, const float* skip, void* out, int rows, int D, int planar, hipStream_t s) {
+    launch_cat2<T>(s, x, skip, static_cast<T*>(out), rows, D, planar);
+    return glue_done(s);
+}
+extern "C" int f5k_cat2(int32_t prec, const float* x, const float* skip, void* out, int32_t rows, int32_t D, int32_t planar, f5_stream stream) {
+    if (!x || !skip || !out || rows <= 0 || D <= 0 || D % 4 || !glue_prec_ok(prec) || !planar_ok(prec, planar, D))
+        return fail(F5_EINVAL, "f5k_cat2: bad arguments (D %% 4 == 0; planar: an f32 output and D %% 32 == 0)");
+    return F5K_BY_PREC(prec, cat2_impl, x, skip, out, rows, D, planar, (hipStream_t)stream);
+}
+extern "C" int f5k_strip_first_token(const float* in, float* out, int32_t Bp, int32_t N, int32_t C, f5_stream stream) {
+    if (!in || !out || Bp <= 0 || N <= 0 || C <= 0 || C % 4) return fail(F5_EINVAL, "f5k_strip_first_token: bad arguments (C %% 4 == 0)");
+    launch_strip_first_token((hipStream_t)stream, in, out, Bp, N, C);
+    return glue_done((hipStream_t)stream);
 }

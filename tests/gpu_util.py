@@ -205,3 +205,132 @@ def k_convpos_ex(prec, x, w, bias, res, y, Bp, N, *, lens=None, row_start=None):
     _lib.check(lib.f5k_convpos_ex(prec_id(prec), _p(x), _p(w), _p(bias), _p(res), C.c_void_p(y.ptr()), Bp, N, D, C.byref(p), _s()),
                "f5k_convpos_ex")
     return y
+
+
+# ---- the step glue of sample() (tests/test_step_glue_gpu.py): device tensors in, Guarded buffers out, nothing staged by the library
+ELEM_DTYPE = {"f32": torch.float32, "f16x3": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+
+
+def _a(t):
+    """Device address of a tensor, a Guarded or None."""
+    return C.c_void_p(0 if t is None else t.ptr() if isinstance(t, Guarded) else t.data_ptr())
+
+
+def _f32(*ts):
+    for t in ts:
+        assert t is None or isinstance(t, Guarded) or (t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda)
+
+
+def k_fill_rowmap(row_start, rowmap, Bp):
+    """row_start: device int32 [Bp + 1]; rowmap: a Guarded f32-sized [rows, 2] whose .bits are the (b', n) pairs."""
+    assert row_start.dtype == torch.int32 and row_start.numel() == Bp + 1 and rowmap.shape[0] >= int(row_start[Bp])
+    _lib.check(_lib.load().f5k_fill_rowmap(_a(row_start), _a(rowmap), Bp, _s()), "f5k_fill_rowmap")
+    return rowmap
+
+
+def k_pack_input(prec, x, cond, text_c, text_u, out, Bp, drop_cond_first=0, rowmap=None, row_limit=None, lens=None):
+    """out: a Guarded [rows, ldo] of the precision's element type.  RowPack form: rowmap (Guarded or int32 tensor [rows, 2]),
+    row_limit (device int32 [1]) and lens (device int32 [B])."""
+    B, N, mel = x.shape
+    Dt = text_c.shape[-1]
+    _f32(x, cond, text_c, text_u)
+    assert cond.shape == x.shape and text_c.shape == text_u.shape == (B, N, Dt) and out.dtype == ELEM_DTYPE[prec]
+    rows, ldo = out.shape
+    if rowmap is None:
+        assert rows >= Bp * N
+    else:
+        lim = int(row_limit.item())
+        assert row_limit.dtype == lens.dtype == torch.int32 and lens.numel() == B and lim <= min(rows, rowmap.shape[0], Bp * N)
+    _lib.check(_lib.load().f5k_pack_input(prec_id(prec), _p(x), _p(cond), _p(text_c), _p(text_u), _a(out), ldo, B, Bp, N, mel, Dt,
+                                          int(drop_cond_first), _a(rowmap), _a(row_limit), _a(lens), _s()), "f5k_pack_input")
+    return out
+
+
+def _ode_args(y, pred, row_start, lens, tgrid, step, use_cfg):
+    B, N, mel = y.shape
+    halves = 2 if use_cfg else 1
+    _f32(pred, tgrid)
+    assert 0 <= step < tgrid.numel() - 1
+    if row_start is None:
+        assert pred.numel() >= halves * B * N * mel
+    else:
+        assert row_start.dtype == lens.dtype == torch.int32 and row_start.numel() == halves * B + 1 and lens.numel() == B
+        assert pred.shape[-1] == mel and pred.shape[0] >= int(row_start[-1])
+    return B, N, mel
+
+
+def k_euler_cfg(y, pred, tgrid, step, cfg, use_cfg, traj_slot=None, row_start=None, lens=None):
+    """y: a Guarded [B, N, mel] updated in place; traj_slot: a Guarded of the same shape or None."""
+    B, N, mel = _ode_args(y, pred, row_start, lens, tgrid, step, use_cfg)
+    assert traj_slot is None or traj_slot.shape == y.shape
+    _lib.check(_lib.load().f5k_euler_cfg(_a(y), _p(pred), B, N, mel, _a(row_start), _a(lens), _p(tgrid), step, float(cfg), int(use_cfg),
+                                         _a(traj_slot), _s()), "f5k_euler_cfg")
+    return y
+
+
+def k_midpoint_half_cfg(y, pred, tgrid, step, cfg, use_cfg, y_mid, row_start=None, lens=None):
+    """y: f32 tensor [B, N, mel]; y_mid: a Guarded of the same shape."""
+    _f32(y)
+    B, N, mel = _ode_args(y, pred, row_start, lens, tgrid, step, use_cfg)
+    assert y_mid.shape == y.shape
+    _lib.check(_lib.load().f5k_midpoint_half_cfg(_p(y), _p(pred), B, N, mel, _a(row_start), _a(lens), _p(tgrid), step, float(cfg),
+                                                 int(use_cfg), _a(y_mid), _s()), "f5k_midpoint_half_cfg")
+    return y_mid
+
+
+def k_select_rows(a, b, rowmask, out):
+    """out (a Guarded [rows, C]) = rowmask ? a : b; b None (zeros), a tensor, or `out` itself (the in-place use)."""
+    rows, Cc = out.shape
+    _f32(a, b)
+    assert a.shape == (rows, Cc) and rowmask.dtype == torch.uint8 and rowmask.numel() == rows and (b is None or b.shape == (rows, Cc))
+    _lib.check(_lib.load().f5k_select_rows(_p(a), _a(b), _p(rowmask), _a(out), rows, Cc, _s()), "f5k_select_rows")
+    return out
+
+
+def k_time_sinus(t, freq, feat):
+    _f32(t, freq)
+    S = t.numel()
+    assert freq.numel() == 128 and feat.shape == (S, 256)
+    _lib.check(_lib.load().f5k_time_sinus(_p(t), _p(freq), _a(feat), S, _s()), "f5k_time_sinus")
+    return feat
+
+
+def k_xrmsnorm(prec, x, g, out, planar=0):
+    R, D = x.shape
+    _f32(x, g)
+    assert g.numel() == D and out.shape == (R, D) and out.dtype == ELEM_DTYPE[prec]
+    _lib.check(_lib.load().f5k_xrmsnorm(prec_id(prec), _p(x), _a(out), R, D, _p(g), planar, _s()), "f5k_xrmsnorm")
+    return out
+
+
+def k_unett_assemble(h, temb, temb_stride, x):
+    Bp, N, D = h.shape
+    _f32(h, temb)
+    assert x.shape == (Bp, N + 1, D) and temb.numel() >= (Bp - 1) * temb_stride + D
+    _lib.check(_lib.load().f5k_unett_assemble(_p(h), _p(temb), temb_stride, _a(x), Bp, N, D, _s()), "f5k_unett_assemble")
+    return x
+
+
+def k_cat2(prec, x, skip, out, planar=0):
+    rows, D = x.shape
+    _f32(x, skip)
+    assert skip.shape == x.shape and out.shape == (rows, 2 * D) and out.dtype == ELEM_DTYPE[prec]
+    _lib.check(_lib.load().f5k_cat2(prec_id(prec), _p(x), _p(skip), _a(out), rows, D, planar, _s()), "f5k_cat2")
+    return out
+
+
+def k_strip_first_token(inp, out):
+    Bp, N1, Cc = inp.shape
+    _f32(inp)
+    assert out.shape == (Bp, N1 - 1, Cc)
+    _lib.check(_lib.load().f5k_strip_first_token(_p(inp), _a(out), Bp, N1 - 1, Cc, _s()), "f5k_strip_first_token")
+    return out
+
+
+def k_work_plan(cfg, B, N, S, call_B, call_N):
+    """f5k_work_plan (no GPU needed): (total bytes, {name: byte offset or None}, the same for the split-CFG side chain)."""
+    n = len(_lib.F5K_WORK_NAMES)
+    total, main, side = C.c_int64(), (C.c_int64 * n)(), (C.c_int64 * n)()
+    _lib.check(_lib.load().f5k_work_plan(C.byref(cfg), B, N, S, call_B, call_N, C.byref(total), main, side), "f5k_work_plan")
+    as_dict = lambda a: {k: (None if v < 0 else v) for k, v in zip(_lib.F5K_WORK_NAMES, a)}   # noqa: E731
+    return total.value, as_dict(main), as_dict(side)

@@ -150,17 +150,26 @@ def test_midpoint_chunked_batch_matches_reference_vectors(monkeypatch):
         assert e_traj < TOL_PARITY and e_out < TOL_PARITY
 
 
-def test_midpoint_split_cfg_is_bit_equal(monkeypatch):
+def split_cfg_is_bit_equal(monkeypatch, prec):
     for name in ("sample_b1_midpoint", "sample_b3_midpoint_attnmask"):
         meta, a, sd = fixture(name)
         monkeypatch.setenv("F5_PACK_ROWS", "0")   # (split CFG steps padded rows; compare like with like)
         monkeypatch.setenv("F5_SPLIT_CFG", "0")
-        base = run_case(meta, a, build_cfm(meta, sd, "f32"))
+        base = run_case(meta, a, build_cfm(meta, sd, prec))
         monkeypatch.setenv("F5_SPLIT_CFG", "1")
-        split = build_cfm(meta, sd, "f32")
+        split = build_cfm(meta, sd, prec)
         for _ in range(3):
             out, traj = run_case(meta, a, split)
-            assert torch.equal(traj, base[1]) and torch.equal(out, base[0]), f"{name}: F5_SPLIT_CFG=1 differs"
+            assert torch.equal(traj, base[1]) and torch.equal(out, base[0]), f"{name} {prec}: F5_SPLIT_CFG=1 differs"
+
+
+def test_midpoint_split_cfg_is_bit_equal(monkeypatch):
+    split_cfg_is_bit_equal(monkeypatch, "f32")
+
+
+def test_midpoint_split_cfg_is_bit_equal_f16p(monkeypatch):
+    """f16p packs its input rows as f32: the side chain's half of that buffer starts behind the main chain's f32 rows."""
+    split_cfg_is_bit_equal(monkeypatch, "f16p")
 
 
 def test_one_engine_alternating_methods_keeps_euler_bit_identical():

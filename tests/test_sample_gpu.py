@@ -98,6 +98,24 @@ def test_attn_mask_batch_unpacked_matches_reference_in_full(monkeypatch):
     assert e < TOL_PARITY and (out.cpu() - a["out"]).abs().max() < TOL_PARITY
 
 
+# F5_SPLIT_CFG=1 runs the two CFG halves as two concurrent stream chains, each in its own half of every work buffer
+# (second_half, csrc/engine_impl.h; tests/test_work_plan.py holds the halves disjoint without a GPU).  f16p packs its input rows
+# (acat) as f32 and long_skip_connection concatenates into cat2: the two buffers whose halves once overlapped.
+@pytest.mark.parametrize("name,prec", [("sample_b1_nfe16", "f32"), ("sample_b1_nfe16", "f16p"), ("sample_b3_attnmask", "f16p"),
+                                       ("sample_b2_options", "f32"), ("sample_b2_options", "f16p")])
+def test_split_cfg_is_bit_equal(monkeypatch, name, prec):
+    meta, a = load_golden(name)
+    sd = synthetic_weights(meta)
+    monkeypatch.setenv("F5_PACK_ROWS", "0")   # (split CFG steps padded rows; compare like with like)
+    monkeypatch.setenv("F5_SPLIT_CFG", "0")
+    base_out, base_traj = (t.cpu() for t in run_case(meta, a, build_cfm(meta, sd, prec)))
+    monkeypatch.setenv("F5_SPLIT_CFG", "1")
+    split = build_cfm(meta, sd, prec)
+    for rep in range(3):   # eager, then captured, then replayed
+        out, traj = (t.cpu() for t in run_case(meta, a, split))
+        assert torch.equal(traj, base_traj) and torch.equal(out, base_out), f"{name} {prec}: F5_SPLIT_CFG=1 differs (run {rep})"
+
+
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
 @pytest.mark.parametrize("name", ["sample_b1_nfe16", "sample_b3_masked", "sample_b3_attnmask", "sample_unett_b2", "sample_b2_options"])
 def test_sample_16bit_error_is_bounded_and_reported(name, prec):
