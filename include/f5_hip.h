@@ -508,6 +508,40 @@ int f5_wave_deliver(f5_mel* m, const float* base, int32_t B, const int64_t* star
                     const int32_t* final_host, const int64_t* o0_host, const int64_t* o1_host, int32_t out_rate, int32_t format,
                     void* out, int64_t out_capacity, int64_t* out_start_out, f5_stream stream);
 
+/* ------------------------------------------------------------------------------------- join and delivery for many streams
+ * What one tick of a server with many clients needs: for each of S <= 65535 streams, the pieces it has so far joined as
+ * f5_wave_join joins them, and of that joined stream a range delivered as f5_wave_deliver delivers it, each stream at its own rate
+ * and in its own format -- in ONE launch, without the joined stream or any per-rate buffer ever being written.  Stream s has
+ * piece_count_host[s] >= 1 pieces; start_host / lens_host / fade_host hold the pieces of all streams, stream after stream (at most
+ * 65535 in all), each as f5_wave_join takes it: base[start + j], j < len, f32 on the device, read where it lies.  Per stream:
+ *   joined    J_s is what f5_wave_join defines for the stream's pieces alone (its first piece, and every piece with a fade of 0,
+ *             opens a run; R restarts with every run): per sample the fold in double over the covering pieces in ascending order,
+ *             rounded to f32 once.  total_s is its length.
+ *   settled   n = settled_host[s], 0 <= n <= total_s (and below 2^31): the stream that is delivered is J_s[0, n).  final_host[s] != 0
+ *             says that it ends there.  A caller whose later pieces fade over at most f samples passes total_s - f while the stream
+ *             grows: no later piece reaches further back.
+ *   delivery  exactly f5_wave_deliver's for an item of n samples at rate_host[s] in format_host[s] (F5_PCM_F32 / F5_PCM_S16):
+ *             geometry, taps in ascending order from +0.0 with an f32 multiply then an f32 add, lengths and ready, the 16-bit view;
+ *             the range [o0_host[s], o1_host[s]) lies inside [0, ready_s].  The banks are the handle's (f5_mel_resample_bank), one
+ *             per rate that occurs.
+ *   output    the stream's bytes go to out + out_start_bytes_out[s], the running byte total rounded up to 16; out_capacity_bytes
+ *             counts bytes.  Nothing else of out is written, nothing outside a piece is read; each sample is written by one
+ *             thread, no atomics.  An empty range writes nothing.
+ * The bytes of stream s are, bit for bit, what f5_wave_deliver gives on the first n samples of f5_wave_join's result for the same
+ * pieces -- alone or in any batch, whatever the other streams are.  A block stages its window by folding it from the pieces
+ * (bisection to the first piece that reaches into it) where f5_wave_deliver loads it.
+ * ONE launch and one table copy through a pinned slot of the handle on `stream`, every host array free when the call returns; no
+ * synchronisation and no allocation except the growth of the handle's workspace.  Calls on one handle are ordered by the caller's
+ * stream.  F5_EINVAL, with nothing launched or staged and a message that starts with "f5_wave_emit:" and names the argument, the
+ * stream or the piece: every refusal of the two calls it composes (a null pointer, S out of range, a length < 1, a fade < 0, a
+ * start < 0, a rate outside [8000, 192000] or with a bank above 2^20 elements, an unknown format, a range outside [0, ready_s]), a
+ * piece_count < 1, more than 65535 pieces, settled outside [0, total_s], out_capacity_bytes below the plan's total.  F5_ESTATE: a
+ * rate has no bank yet. */
+int f5_wave_emit(f5_mel* m, const float* base, int32_t S, const int32_t* piece_count_host, const int64_t* start_host,
+                 const int32_t* lens_host, const int32_t* fade_host, const int64_t* settled_host, const int32_t* final_host,
+                 const int64_t* o0_host, const int64_t* o1_host, const int32_t* rate_host, const int32_t* format_host, void* out,
+                 int64_t out_capacity_bytes, int64_t* out_start_bytes_out, f5_stream stream);
+
 /* ------------------------------------------------------------------------------------- silence clipping
  * What the reference drivers do to every prompt before anything else sees it (infer/utils_infer.py:348-361, 385-419: cut at pauses
  * to at most 12 s, trim the silent edges, append 50 ms of silence) and, on request, to the result (:784-793, remove_silence), both

@@ -143,6 +143,9 @@ SIGNATURES = {
     "f5_wave_deliver_plan": (_i, [_i, C.c_int64, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "f5_wave_deliver": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                              _i, _i, _p, C.c_int64, C.POINTER(C.c_int64), _p]),
+    "f5_wave_emit": (_i, [_p, _p, _i, C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64),
+                          C.POINTER(_i), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), _p, C.c_int64,
+                          C.POINTER(C.c_int64), _p]),
     "f5k_gemm": (_i, [_i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "f5k_gemm_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "f5k_attention": (_i, [_i, _p, _p, _p, C.POINTER(_i), _p, _i, _i, _i, _p]),

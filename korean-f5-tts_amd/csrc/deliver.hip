@@ -7,70 +7,21 @@
 //                         logic), then per output sample the taps in ascending order; a stream at the output rate passes through.
 //                         A thread's four samples are aligned to the item's destination: one 16-byte (f32) or 8-byte (s16) store
 //                         inside the range, element stores at its two edges.
+#include "deliver.h"
 #include "elementwise.h"
 #include "mel_handle.h"
-#include "resample.h"
-#include "segments.h"
 
 using namespace f5;
 #define fail f5_fail
 
 namespace {
-constexpr int STREAM_RATE = 24000;
-constexpr long long MAX_UNITS = 1LL << 30;   // blocks of one call
-
-struct DeliverItem {
-    long long in_start, out_start, o0, o1;    // elements from base / out; the output range in samples of the resampled stream
-    const float* bank;                        // [K, new], null for a stream at the output rate
-    int n, orig, nw, width, K, F;             // F frames per block
-};
 struct DeliverTables {                        // items[B] | blk_start[B + 1]: one layout for the pinned slot and the device
     DeliverItem* items;
     int* blk_start;
     DeliverTables(char* base, int B) : items(reinterpret_cast<DeliverItem*>(base)), blk_start(reinterpret_cast<int*>(base + (size_t)B * sizeof(DeliverItem))) {}
     static size_t bytes(int B) { return (size_t)B * sizeof(DeliverItem) + ((size_t)B + 1) * 4; }
 };
-
-// the rate geometry of 24 kHz -> out_rate, or the refusal
-int deliver_rate(const char* who, int out_rate, RatePair* r) {
-    if (out_rate < 8000 || out_rate > 192000) return fail(F5_EINVAL, "%s: out_rate = %d (need 8000 <= out_rate <= 192000)", who, out_rate);
-    if (!rate_pair(STREAM_RATE, out_rate, r) || (!r->same() && r->K > RS_LDS_FLOATS))
-        return fail(F5_EINVAL, "%s: the resample bank of %d Hz -> %d Hz has more than 2^20 elements", who, STREAM_RATE, out_rate);
-    return F5_OK;
-}
-long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-void deliver_lengths(const RatePair& r, long long n, bool final, long long* len, long long* ready) {
-    *len = (r.nw * n + r.orig - 1) / r.orig;
-    // output frame i reads inputs up to i * orig + width + orig - 1
-    *ready = final ? *len : std::min(r.nw * std::max(0LL, floor_div(n - r.width - r.orig, r.orig) + 1), *len);
-}
 }  // namespace
-
-// four consecutive samples at element d of the item's output: one vector store where all four are inside [d0, d1) and the address
-// allows, element stores otherwise
-static __device__ __forceinline__ void store_quad(void* __restrict__ out, int format, long long at, long long d, long long d0, long long d1,
-                                                  const float (&v)[4]) {
-    const bool full = d >= d0 && d + 4 <= d1;
-    if (format == F5_PCM_F32) {
-        float* dst = reinterpret_cast<float*>(out) + at + d;
-        if (full && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-            for (int q = 0; q < 4; ++q)
-                if (d + q >= d0 && d + q < d1) dst[q] = v[q];
-        }
-    } else {
-        short* dst = reinterpret_cast<short*>(out) + at + d;
-        short s[4];
-        for (int q = 0; q < 4; ++q) s[q] = (short)quantise(v[q], 32767.0f);
-        if (full && (reinterpret_cast<uintptr_t>(dst) & 7) == 0) {
-            *reinterpret_cast<short4*>(dst) = make_short4(s[0], s[1], s[2], s[3]);
-        } else {
-            for (int q = 0; q < 4; ++q)
-                if (d + q >= d0 && d + q < d1) dst[q] = s[q];
-        }
-    }
-}
 
 static __global__ __launch_bounds__(256) void wave_deliver_kernel(const float* __restrict__ base, const DeliverItem* __restrict__ items,
                                                                   const int* __restrict__ blk_start, int B, int format, void* __restrict__ out) {
@@ -91,30 +42,13 @@ static __global__ __launch_bounds__(256) void wave_deliver_kernel(const float* _
         return;
     }
 
-    const long long frame0 = it.o0 / it.nw + tile * it.F;
-    const long long win0 = frame0 * it.orig - it.width;   // position in the unpadded stream of the window's first sample
-    const int win = (it.F - 1) * it.orig + it.K;          // <= RS_LDS_FLOATS by the host's choice of F
-    for (int e = threadIdx.x; e < win; e += 256) {
-        const long long j = win0 + e;
+    const DeliverWindow w = deliver_window(it, tile);
+    for (int e = threadIdx.x; e < w.win; e += 256) {
+        const long long j = w.win0 + e;
         xs[e] = (j >= 0 && j < it.n) ? x[j] : 0.f;
     }
     __syncthreads();
-    // the block's outputs as positions of the item's destination, and the quads aligned to it
-    const long long d0 = max(it.o0, frame0 * it.nw) - it.o0;
-    const long long d1 = min(it.o1, (frame0 + it.F) * it.nw) - it.o0;
-    for (long long d = (d0 & ~3LL) + 4 * (long long)threadIdx.x; d < d1; d += RS_OUT_TILE) {
-        int xi[4], bp[4];
-        for (int q = 0; q < 4; ++q) {
-            const long long dq = (d + q >= d0 && d + q < d1) ? d + q : d0;   // a lane outside the range repeats a valid sample and stores nothing
-            const long long o = it.o0 + dq;
-            const long long f = o / it.nw;
-            xi[q] = (int)(f - frame0) * it.orig;
-            bp[q] = (int)(o - f * it.nw);
-        }
-        float acc[4];
-        resample_taps(it.bank, it.nw, it.K, xi, bp, [&](int e) { return xs[e]; }, acc);
-        store_quad(out, format, it.out_start, d, d0, d1, acc);
-    }
+    deliver_from_window(it, w.frame0, xs, format, out);
 }
 
 extern "C" int f5_wave_deliver_plan(int32_t out_rate, int64_t n, int32_t final, int64_t* len_out, int64_t* ready_out) {
@@ -166,11 +100,8 @@ extern "C" int f5_wave_deliver(f5_mel* m, const float* base, int32_t B, const in
         at[b] = run;
         run += o1 - o0;
         blk_start[b] = (int)blks;
-        if (o1 > o0) {
-            if (r.same()) blks += (o1 - o0 + RS_OUT_TILE - 1) / RS_OUT_TILE;
-            else blks += ((o1 + r.nw - 1) / r.nw - o0 / r.nw + F - 1) / F;
-        }
-        if (blks > MAX_UNITS) return fail(F5_EINVAL, "%s: more than 2^30 blocks of work at item %d (split the batch)", who, b);
+        if (o1 > o0) blks += deliver_blocks(r, F, o0, o1);
+        if (blks > DELIVER_MAX_UNITS) return fail(F5_EINVAL, "%s: more than 2^30 blocks of work at item %d (split the batch)", who, b);
     }
     blk_start[B] = (int)blks;
     if (out_capacity < run)
@@ -179,7 +110,7 @@ extern "C" int f5_wave_deliver(f5_mel* m, const float* base, int32_t B, const in
     if (!r.same()) {
         auto it = m->bank_of.find(std::make_pair(r.orig, r.nw));
         if (it == m->bank_of.end())
-            return fail(F5_ESTATE, "%s: no resample bank for %d Hz -> %d Hz yet (f5_mel_resample_bank)", who, STREAM_RATE, out_rate);
+            return fail(F5_ESTATE, "%s: no resample bank for %d Hz -> %d Hz yet (f5_mel_resample_bank)", who, DELIVER_STREAM_RATE, out_rate);
         bank = it->second;
     }
     for (int b = 0; b < B; ++b) out_start_out[b] = at[b];

@@ -10,45 +10,16 @@
 // inside a tagged stretch, plain concatenation between stretches -- over up to 65535 pieces that lie anywhere under one base pointer.
 // Its table goes through the pinned slot and the workspace of the handle-less calls (CallState, internal.h); a tile finds its first
 // piece by bisection over the pieces' ends, which never decrease, and walks up while a later piece can still start inside it.
-#include "segments.h"
+#include "join.h"
 
+using namespace f5;
 #define fail f5_fail
 
 namespace {
 constexpr int kMaxPieces = 64;
 constexpr int kThreads = 256;
-constexpr int kPerThread = 4;                       // consecutive samples per thread: one 16-byte store
+constexpr int kPerThread = JOIN_PER_THREAD;         // consecutive samples per thread: one 16-byte store
 constexpr int kTile = kThreads * kPerThread;        // samples per block and round
-
-// One piece folded into the four samples [p0, p0 + 4) a thread holds: piece x covers [off, off + len) of the output and its first n
-// samples fade in over what v holds (the contract in include/f5_hip.h).  Nothing outside [0, len) of x is read.
-__device__ __forceinline__ void fold_piece(const float* __restrict__ x, long long off, int len, int n, double step, long long p0,
-                                           double (&v)[kPerThread]) {
-    const long long j0 = p0 - off;
-    if (j0 >= len || j0 + kPerThread <= 0) return;
-    float xv[kPerThread];
-    if (j0 >= 0 && j0 + kPerThread <= len) {
-        __builtin_memcpy(xv, x + j0, sizeof(xv));                 // 4-byte aligned, inside the piece
-    } else {
-#pragma unroll
-        for (int e = 0; e < kPerThread; ++e) {
-            const long long j = j0 + e;
-            xv[e] = (j >= 0 && j < len) ? x[j] : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < kPerThread; ++e) {
-        const long long j = j0 + e;
-        if (j < 0 || j >= len) continue;
-        if (j < n) {
-            double fi, fo;
-            fade_weights(j, n, step, &fi, &fo);
-            v[e] = v[e] * fo + (double)xv[e] * fi;
-        } else {
-            v[e] = (double)xv[e];
-        }
-    }
-}
 
 // the thread's four samples, rounded to f32 once: one 16-byte store where the address allows; nothing at or past total
 __device__ __forceinline__ void store_samples(float* __restrict__ out, long long p0, long long total, int out_aligned,
@@ -87,35 +58,14 @@ __global__ __launch_bounds__(kThreads) void wave_crossfade_kernel(const float* _
     }
 }
 
-// f5_wave_join's table, one entry per piece, in a pinned slot and then in the workspace (internal.h)
-struct JoinPiece {
-    long long src;               // first sample, in elements from base
-    long long off;               // position of the piece's first sample in the output
-    long long end;               // off + len = L_i: never decreases with i
-    long long low;               // min of off over this piece and every later one
-    double step;
-    int n, len;
-};
-
 __global__ __launch_bounds__(kThreads) void wave_join_kernel(const float* __restrict__ base, const JoinPiece* __restrict__ pieces, int B,
                                                               float* __restrict__ out, long long total, long long ntiles,
                                                               int out_aligned) {
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long t0 = tile * kTile, t1 = t0 + kTile;      // the block's span (block-uniform, like everything up to fold_piece)
         const long long p0 = t0 + (long long)threadIdx.x * kPerThread;
-        int lo = 0, hi = B - 1;                                   // the first piece that ends behind t0 (t0 < total = end[B - 1])
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (pieces[mid].end > t0) hi = mid;
-            else lo = mid + 1;
-        }
         double v[kPerThread] = {0.0, 0.0, 0.0, 0.0};
-        for (int i = lo; i < B; ++i) {
-            const JoinPiece pc = pieces[i];
-            if (pc.low >= t1) break;                              // neither this piece nor a later one starts inside the tile
-            if (pc.off >= t1) continue;
-            fold_piece(base + pc.src, pc.off, pc.len, pc.n, pc.step, p0, v);
-        }
+        fold_pieces(base, pieces, B, first_piece(pieces, B, t0), t1, p0, v);   // (t0 < total = end[B - 1])
         store_samples(out, p0, total, out_aligned, v);
     }
 }
@@ -166,25 +116,17 @@ extern "C" int f5_wave_join(const float* base, int32_t B, const int64_t* start_h
     if (!fade_host) return fail(F5_EINVAL, "%s: fade_host is null", who);
     if (!out) return fail(F5_EINVAL, "%s: out is null", who);
     std::vector<JoinPiece> pieces((size_t)B);
-    long long L = 0, R = 0;                                       // the result so far; the run so far
+    JoinRun run;
     for (int i = 0; i < B; ++i) {
         const int len = lens_host[i], fade = fade_host[i];
         if (len < 1) return fail(F5_EINVAL, "%s: lens_host[%d] = %d; every piece needs at least 1 sample", who, i, len);
         if (fade < 0) return fail(F5_EINVAL, "%s: fade_host[%d] = %d < 0", who, i, fade);
         if (start_host[i] < 0) return fail(F5_EINVAL, "%s: start_host[%d] = %lld < 0", who, i, (long long)start_host[i]);
-        const bool opens = i == 0 || fade == 0;                    // a piece that does not fade opens a run
-        const long long n = opens ? 0 : std::min<long long>(std::min<long long>(fade, R), len);
-        JoinPiece& pc = pieces[i];
-        pc.src = start_host[i];
-        pc.off = L - n;
-        pc.end = L = pc.off + len;
-        pc.step = n > 1 ? 1.0 / (double)(n - 1) : 0.0;
-        pc.n = (int)n, pc.len = len;
-        R = opens ? len : R - n + len;
+        run.place(i == 0, start_host[i], len, fade, &pieces[i]);
     }
+    const long long L = run.L;
     if (out_cap < L) return fail(F5_EINVAL, "%s: out_cap %lld is less than the %lld samples of the result", who, (long long)out_cap, L);
-    long long low = L;
-    for (int i = B - 1; i >= 0; --i) pieces[i].low = low = std::min(low, pieces[i].off);
+    run.close(pieces.data(), B);
     const size_t tab_bytes = (size_t)B * sizeof(JoinPiece);
 
     hipStream_t s = (hipStream_t)stream;

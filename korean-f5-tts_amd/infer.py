@@ -43,6 +43,9 @@
                                                                  device (f5_wave_deliver): the resampler of the prompt stage, the other way
   stream_chunks / open_stream        socket_server.py:72-177     the serving mode (stream.py): a voice prepared once, the first chunk of a
                                                                  request short, packets at the client's rate while later chunks run
+  open_pool / wave_emit              (no reference counterpart)  many clients at once: the chunks of different clients share one sample()
+                                                                 and one decode per tick (StreamPool, pool_tick), and ONE f5_wave_emit
+                                                                 joins and delivers every client's new audio at its own rate and format
 
 Out of scope here: Whisper ASR (an empty ref_text), forced alignment, pinyin /
 Korean G2P tokenisers (text is tokenised per character through `vocab_char_map`, or as utf-8 bytes when the model has no
@@ -64,9 +67,10 @@ from .mel import resample_kernel, resampled_length
 from .script import parse_script, script_plan  # noqa: F401  (part of this module's surface)
 from .utils import list_str_to_idx, list_str_to_tensor, load_vocab
 from .vocos import Vocos
-from .stream import StreamSession, open_stream, packet_sizes, stream_chunks, stream_limits  # noqa: F401  (part of this module's surface)
-from .wave import (cross_fade_plan, deliver_plan, join_plan, ragged_items, silence_flags, wave_crossfade, wave_deliver,  # noqa: F401
-                   wave_gather, wave_join, wave_splice)                           # (the device calls: wave.py)
+from .stream import (StreamPool, StreamSession, open_pool, open_stream, packet_sizes, pool_tick, request_plan,  # noqa: F401
+                     stream_chunks, stream_limits)                               # (part of this module's surface)
+from .wave import (cross_fade_plan, deliver_plan, emit_plan, join_plan, ragged_items, silence_flags, wave_crossfade,  # noqa: F401
+                   wave_deliver, wave_emit, wave_gather, wave_join, wave_splice)  # (the device calls: wave.py)
 
 target_sample_rate = SAMPLE_RATE
 n_mel_channels = MEL_DIM

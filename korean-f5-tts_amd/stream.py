@@ -2,7 +2,9 @@
 text split so that its first chunk is short, and the audio sent packet by packet while later chunks are still being generated.
 `stream_chunks` is the host text plan of generate_stream (socket_server.py:112-143); `StreamSession` (infer.open_stream) runs the
 chunks on the device path -- the voice from a VoiceBank, ragged sample(), decode_ragged, f5_wave_join, f5_wave_deliver -- and
-yields packets at the client's rate and sample format.  The TCP shell and the sound-card code of the server are not here."""
+yields packets at the client's rate and sample format.  `StreamPool` (infer.open_pool) serves many clients at once, which the
+reference's server does not: `pool_tick` puts waiting chunks of different clients into one ragged batch per tick, and one
+f5_wave_emit joins and delivers every touched request's new audio.  The TCP shell and the sound-card code of the server are not here."""
 from __future__ import annotations
 
 import torch
@@ -34,6 +36,25 @@ def stream_chunks(text: str, ref_text: str, ref_seconds: float, first_package: b
 def packet_sizes(count: int, chunk_size: int) -> list[int]:
     """The sizes `for j in range(0, count, chunk_size): wave[j:j + chunk_size]` gives: full packets, then one short one."""
     return [min(chunk_size, count - j) for j in range(0, count, chunk_size)]
+
+
+def request_plan(model, bank, v: int, text: str, first_package: bool, speed, fix_duration, text_tokenizer, stacklevel: int = 4) -> dict:
+    """The host plan of one request spoken with voice v of the bank (what a session and a pool's client both run): the chunks
+    (stream_chunks), the text and the total frames sample() runs each at (text_numerics, clamp_durations: as synthesize_script
+    plans a chunk).  Returns dict(chunks, texts, durations, ends); a text without chunks gives empty lists."""
+    from . import infer as I
+
+    chunks = stream_chunks(text, bank.ref_texts[v], bank.seconds[v], first_package)
+    texts, durations = [], []
+    for chunk in chunks:
+        rtext, _ref_len, duration = I.text_numerics(bank.samples[v], bank.ref_texts[v], chunk, speed, fix_duration)
+        texts.append(rtext + chunk)
+        durations.append(duration)
+    if not chunks:
+        return dict(chunks=[], texts=[], durations=[], ends=[])
+    texts, idx = I._tokenise(model, texts, text_tokenizer, stacklevel=stacklevel)
+    ends = I.clamp_durations(idx.to("cpu", torch.long), torch.tensor([bank.frames[v]] * len(chunks)), torch.tensor(durations)).tolist()
+    return dict(chunks=chunks, texts=texts, durations=durations, ends=ends)
 
 
 class StreamSession:
@@ -126,23 +147,17 @@ class StreamSession:
         at (text_numerics, clamp_durations: as synthesize_script plans a chunk), the groups as ranges of chunks."""
         from . import infer as I
 
-        bank, v = self.bank, self.voice
-        chunks = stream_chunks(text, bank.ref_texts[v], bank.seconds[v], self._first)
+        plan = request_plan(self.model, self.bank, self.voice, text, self._first, self._speed, self.fix_duration, self.text_tokenizer,
+                            stacklevel=5)
         self._first = False
-        texts, durations = [], []
-        for chunk in chunks:
-            rtext, _ref_len, duration = I.text_numerics(bank.samples[v], bank.ref_texts[v], chunk, self._speed, self.fix_duration)
-            texts.append(rtext + chunk)
-            durations.append(duration)
-        if not chunks:
-            return dict(chunks=[], texts=[], durations=[], ends=[], groups=[])
-        texts, idx = I._tokenise(self.model, texts, self.text_tokenizer, stacklevel=4)
-        ends = I.clamp_durations(idx.to("cpu", torch.long), torch.tensor([bank.frames[v]] * len(chunks)), torch.tensor(durations)).tolist()
-        if self.batch_frames is None:
-            groups = [range(i, i + 1) for i in range(len(chunks))]
+        ends = plan["ends"]
+        if not ends:
+            groups = []
+        elif self.batch_frames is None:
+            groups = [range(i, i + 1) for i in range(len(ends))]
         else:                                                               # the first chunk alone: its audio is what the client waits for
             groups = [range(0, 1)] + [range(r.start + 1, r.stop + 1) for r in I.group_chunks(ends[1:], self.batch_frames)]
-        return dict(chunks=chunks, texts=texts, durations=durations, ends=ends, groups=groups)
+        return dict(plan, groups=groups)
 
     def _enqueue(self, plan, g, pieces, state):
         """The device work of group g, all of it asynchronous: returns (pinned host tensor or None, event)."""
@@ -216,3 +231,277 @@ def open_stream(model, vocoder, voice, *, out_rate=SAMPLE_RATE, sample_format="f
                          cross_fade_duration=cross_fade_duration, batch_frames=batch_frames, lookahead=lookahead, nfe_step=nfe_step,
                          cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration,
                          seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the pool
+def pool_tick(waiting, batch_frames, max_items, first_alone, cursor):
+    """Which chunks run in the next tick of a StreamPool: a pure function of the queue.  `waiting` lists the requests that have
+    chunks waiting, in submission order, as (request id, index of its first waiting chunk, [frames sample() runs each waiting chunk
+    at, in the request's order]); ids are integers that ascend with submission.  Returns (items, cursor): the tick's rows as
+    (request id, chunk index) in row order, and the cursor for the tick after it.
+
+    The budget is that of group_chunks: a tick costs its row count times its longest row, so an item joins while
+    (rows + 1) * max(longest, its frames) <= batch_frames (None: no such limit) and rows + 1 <= max_items.  The first item of a tick
+    is always taken: a chunk over the budget runs alone.  The tick ends at the first item that does not fit -- nothing behind it is
+    tried, so nobody overtakes it.  A request's chunks are only ever taken in their own order.
+      * While a request whose first chunk (index 0) waits is in the queue and `first_alone` is set, the tick holds first chunks
+        only, in submission order (a client's first audio is what it waits for); the cursor stays.
+      * Otherwise round-robin: the requests in ascending id from the first id >= cursor, wrapping around, give one chunk each;
+        when all have given and the budget is not spent they give their next one, and so on.  The tick ends where an item does
+        not fit, and that request's id is the new cursor: the requests the tick did not reach are first in the next one, ahead of
+        every request it served.  So of two requests that wait through two round-robin ticks in a row, one never gets rows in both
+        while the other gets none -- no request is passed over twice in a row.  When everything waiting was taken the cursor stays."""
+    items, longest = [], 0
+
+    def fits(frames):
+        rows = len(items)
+        return rows == 0 or (rows < max_items and (batch_frames is None or (rows + 1) * max(longest, frames) <= batch_frames))
+
+    live = [w for w in waiting if w[2]]
+    firsts = [w for w in live if w[1] == 0]
+    if first_alone and firsts:
+        for rid, _, frames in firsts:
+            if not fits(frames[0]):
+                break
+            items.append((rid, 0))
+            longest = max(longest, frames[0])
+        return items, cursor
+    if not live:
+        return [], cursor
+    start = next((i for i, w in enumerate(live) if w[0] >= cursor), 0)
+    order = live[start:] + live[:start]
+    for depth in range(max(len(w[2]) for w in order)):
+        for rid, k, frames in order:
+            if depth >= len(frames):
+                continue
+            if not fits(frames[depth]):
+                return items, rid
+            items.append((rid, k + depth))
+            longest = max(longest, frames[depth])
+    return items, cursor
+
+
+class PoolRequest:
+    """One submitted text of a client (client.submit): `id` ascends with submission, `plan` is request_plan's dict, `voice` the
+    bank's row it is spoken with, `done` whether its last packet has been handed out (or it was cancelled with nothing under way)."""
+
+    def __init__(self, rid, client, voice, plan):
+        self.id, self.client, self.voice, self.plan = rid, client, voice, plan
+        self.next = 0                       # the first chunk that has not been put into a tick
+        self.stop = len(plan["ends"])       # chunks that run at all (cancel lowers it)
+        self.flying = 0                     # ticks enqueued whose bytes the host has not cut into packets yet
+        self.pieces, self.sent = [], 0      # the chunks' waveforms so far, on the device; samples delivered at the client's rate
+        self.done = self.stop == 0
+
+    def cancel(self):
+        """Drops the chunks that have not started.  What is under way still arrives; the stream is not finalised, so the last
+        `fade` samples of what ran (and the resampler's last taps) are never sent."""
+        self.stop = self.next
+        if self.flying == 0:
+            self.done = True
+
+
+class PoolClient:
+    """One client of a StreamPool (pool.connect): its voice, rate, format, packet size, cross-fade and first-package state."""
+
+    def __init__(self, pool, voice, out_rate, sample_format, chunk_size, cross_fade_duration, speed, fix_duration):
+        from . import infer as I
+
+        if sample_format not in ("f32", "s16"):
+            raise ValueError(f"connect: sample_format {sample_format!r} (expected 'f32' or 's16')")
+        if int(chunk_size) < 1:
+            raise ValueError(f"connect: chunk_size = {chunk_size} (need at least 1 sample per packet)")
+        I.deliver_plan(out_rate, 0)                                          # refuses a rate the device stage does not take
+        self.pool, self.out_rate, self.sample_format, self.chunk_size = pool, int(out_rate), sample_format, int(chunk_size)
+        self.fade = int(cross_fade_duration * SAMPLE_RATE) if cross_fade_duration > 0 else 0
+        self.speed, self.fix_duration = speed, fix_duration
+        self.update_reference(voice)
+
+    def update_reference(self, name):
+        """Another voice of the pool's bank for this client.  Re-arms the first package."""
+        bank = self.pool.bank
+        if name not in bank.names:
+            raise ValueError(f"connect: the bank has no voice {name!r} (it has {bank.names})")
+        self.voice = bank.names.index(name)
+        own = bank.speeds[self.voice]
+        base = 1.0 if self.speed is None else self.speed
+        self._speed = base if own is None else own
+        self._first = True
+
+    def reset(self):
+        """The client left: its next request is a first package again."""
+        self._first = True
+
+    def submit(self, text: str) -> PoolRequest:
+        """Plans the request (request_plan: exactly a session's plan, consuming the first package) and queues its chunks."""
+        pool = self.pool
+        plan = request_plan(pool.model, pool.bank, self.voice, text, self._first, self._speed, self.fix_duration, pool.text_tokenizer)
+        self._first = False
+        req = PoolRequest(pool._next_id, self, self.voice, plan)
+        pool._next_id += 1
+        if not req.done:
+            pool._requests.append(req)
+        return req
+
+
+class StreamPool:
+    """Many clients on one model (infer.open_pool builds it): the chunks of different clients' requests share ragged batches.  One
+    tick is, all asynchronous on the stream: ONE model.sample over the tick's items (pool_tick chooses them) with each item's own
+    voice row and prompt frames, as synthesize_script runs a group; ONE decode_ragged; the rescale to each prompt's level; ONE
+    wave_emit over every request the tick touched -- its pieces so far joined and the samples that have become settled delivered at
+    its client's rate and format, read where the pieces lie; ONE copy of the emitted bytes into a pinned buffer.  The host then
+    cuts each request's bytes into packets of its client's chunk_size.  Behind a tick a request is settled up to its joined length
+    minus its fade, and wholly after its last chunk, as in a StreamSession; concatenated, a request's packets are bit for bit
+    wave_deliver(wave_join(pieces, fades), final=True) at its client's rate.
+
+    `step()` runs one tick and returns [(request, [packets])] for the requests it touched ([] when nothing waits); `run()` yields
+    (request, packet, out_rate) until nothing waits.  Requests may be submitted between any two ticks.  `log` holds the batches as
+    run: per tick the (request id, chunk index) items in row order."""
+
+    def __init__(self, model, vocoder, voices, *, batch_frames, max_items, first_alone, lookahead, nfe_step, cfg_strength,
+                 sway_sampling_coef, seed, text_tokenizer, clip_silence):
+        from . import infer as I
+
+        I._require_text_tokenizer(model, text_tokenizer)
+        I._require_ragged_vocoder(vocoder, "open_pool", "stream through infer_batch_process(streaming=True)")
+        if int(lookahead) < 0:
+            raise ValueError(f"open_pool: lookahead = {lookahead} (need 0 or more ticks)")
+        if batch_frames is not None and int(batch_frames) < 1:
+            raise ValueError(f"open_pool: batch_frames = {batch_frames} (need None or a positive budget)")
+        if int(max_items) < 1:
+            raise ValueError(f"open_pool: max_items = {max_items} (need at least 1 row per tick)")
+        self.model, self.vocoder, self.text_tokenizer = model, vocoder, text_tokenizer
+        self.batch_frames, self.max_items = batch_frames, int(max_items)
+        self.first_alone, self.lookahead = bool(first_alone), int(lookahead)
+        self.sample_kw = dict(steps=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+        self._stats = dict(ticks=0, sample_calls=0, decode_calls=0, emit_launches=0, copies=0, packets=0, prompt_passes=0)
+        if isinstance(voices, dict):
+            self.bank = I.prepare_voices(model, voices, clip_silence=clip_silence)
+            self._stats["prompt_passes"] += 1
+        else:
+            self.bank = voices
+        self.log, self._requests, self._pending, self._outbox, self._cursor, self._next_id = [], [], [], [], 0, 0
+
+    def connect(self, voice, *, out_rate=SAMPLE_RATE, sample_format="f32", chunk_size=2048, cross_fade_duration=0.0, speed=None,
+                fix_duration=None) -> PoolClient:
+        """A client that speaks with `voice` of the pool's bank and receives packets of chunk_size samples at out_rate in
+        sample_format; cross_fade_duration: seconds the chunks of one of its requests fade into each other; speed: None is 1.0 (a
+        voice's own speed goes first, as in a session)."""
+        return PoolClient(self, voice, out_rate, sample_format, chunk_size, cross_fade_duration, speed, fix_duration)
+
+    def stats(self) -> dict:
+        """ticks run; sample_calls / decode_calls / emit_launches: model.sample, decode_ragged and wave_emit calls; copies: device
+        to host copies; packets handed out; prompt_passes: prompt preparations this pool ran."""
+        return dict(self._stats)
+
+    def idle(self) -> bool:
+        return not self._pending and not any(r.next < r.stop for r in self._requests)
+
+    # ---- a tick ------------------------------------------------------------------------------------------------------------
+    def _enqueue(self):
+        """The device work of the next tick, all of it asynchronous: None when nothing waits, else (touched requests with their
+        byte spans, pinned host tensor or None, event)."""
+        from . import infer as I
+
+        self._requests = [r for r in self._requests if r.next < r.stop or r.flying]
+        waiting = [(r.id, r.next, r.plan["ends"][r.next:r.stop]) for r in self._requests if r.next < r.stop]
+        # batch_frames=None is a session's: every chunk as its own B = 1 sample()
+        items, self._cursor = pool_tick(waiting, self.batch_frames, self.max_items if self.batch_frames is not None else 1,
+                                        self.first_alone, self._cursor)
+        if not items:
+            return None
+        by_id = {r.id: r for r in self._requests}
+        bank, run = self.bank, [(by_id[rid], k) for rid, k in items]
+        self.log.append(list(items))
+        glens = [bank.frames[r.voice] for r, _ in run]
+        rows = torch.tensor([r.voice for r, _ in run], device=bank.mel.device)
+        generated, _ = self.model.sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
+                                         duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens),
+                                         **self.sample_kw)
+        wave, wave_lens = self.vocoder.decode_ragged(generated.to(torch.float32).permute(0, 2, 1), ends=[r.plan["ends"][k] for r, k in run],
+                                                     starts=[bank.samples[r.voice] // HOP_LENGTH for r, _ in run])
+        wave = I.rescale_to_prompt(wave, bank.rms.index_select(0, rows)[:, None], bank.target_rms)
+        touched = []
+        for b, (r, k) in enumerate(run):
+            assert k == r.next, "a request's chunks run in order"
+            r.next += 1
+            r.pieces.append(wave[b, :wave_lens[b]])
+            if r not in touched:
+                touched.append(r)
+        streams = []
+        for r in touched:
+            c, last = r.client, r.next >= len(r.plan["ends"])
+            fades = [0] + [c.fade] * (len(r.pieces) - 1)
+            total = I.join_plan([int(p.shape[0]) for p in r.pieces], fades)[2]
+            settled = total if last else max(total - c.fade, 0)
+            ready = I.deliver_plan(c.out_rate, settled, last)[1]
+            streams.append(dict(pieces=r.pieces, fades=fades, settled=settled, final=last, range=(r.sent, max(ready, r.sent)),
+                                out_rate=c.out_rate, sample_format=c.sample_format))
+            r.sent = max(ready, r.sent)
+            r.flying += 1
+        _views, buf = I.wave_emit(self.model.mel_spec, streams)
+        starts, total = I.emit_plan(streams)
+        host = None
+        if total:
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            host.copy_(buf[:total], non_blocking=True)
+            self._stats["copies"] += 1
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(bank.mel.device))
+        for key in ("ticks", "sample_calls", "decode_calls", "emit_launches"):
+            self._stats[key] += 1
+        spans = [(r, a, st["range"][1] - st["range"][0]) for r, a, st in zip(touched, starts, streams)]
+        return spans, host, event
+
+    def step(self):
+        """One tick: enqueues the device work of up to 1 + lookahead ticks, waits for the oldest one's copy and returns
+        [(request, [packets])] for the requests it touched; [] when nothing waits and nothing is under way."""
+        import numpy as np
+
+        if self.idle():
+            return []
+        with torch.inference_mode(), torch.cuda.device(self.bank.mel.device):
+            while len(self._pending) <= self.lookahead:
+                tick = self._enqueue()
+                if tick is None:
+                    break
+                self._pending.append(tick)
+        if not self._pending:
+            return []
+        spans, host, event = self._pending.pop(0)
+        event.synchronize()
+        raw = host.numpy() if host is not None else None                    # (a view: the packets keep the pinned buffer alive)
+        out = []
+        for r, a, count in spans:
+            c = r.client
+            width, dtype = (4, np.float32) if c.sample_format == "f32" else (2, np.int16)
+            samples = raw[a:a + count * width].view(dtype) if count else np.empty(0, dtype)
+            packets = [samples[j:j + c.chunk_size] for j in range(0, count, c.chunk_size)]
+            self._stats["packets"] += len(packets)
+            r.flying -= 1
+            if r.flying == 0 and r.next >= r.stop:
+                r.done = True
+            out.append((r, packets))
+        return out
+
+    def run(self):
+        """(request, packet, out_rate) until nothing waits.  Closing the generator early leaves the pool usable: what is queued
+        stays queued and the packets of the current tick that were not handed out are kept; the next run() goes on from there."""
+        while self._outbox or not self.idle():
+            if not self._outbox:
+                self._outbox = [(r, packet) for r, packets in self.step() for packet in packets]
+                continue
+            r, packet = self._outbox.pop(0)
+            yield r, packet, r.client.out_rate
+
+
+def open_pool(model, vocoder, voices, *, batch_frames, max_items=64, first_alone=True, lookahead=0, nfe_step=32, cfg_strength=2.0,
+              sway_sampling_coef=-1.0, seed=None, text_tokenizer=None, clip_silence=False) -> StreamPool:
+    """A pool that serves many streaming clients from one model: voices is a VoiceBank or the dict prepare_voices takes (prepared
+    once, here).  batch_frames: the budget of a tick, rows x longest row (None: every chunk as its own B = 1 sample(), as in
+    open_stream; the ticks then share only the emit); max_items: rows of a tick at most; first_alone: a waiting first chunk keeps
+    later chunks out of its tick (pool_tick has the rule); lookahead: ticks enqueued ahead of the one the host waits for.  The
+    sampler settings are the pool's, because sample() takes them as scalars.  Refuses what open_stream refuses.  See StreamPool, and pool.connect for a client's side."""
+    return StreamPool(model, vocoder, voices, batch_frames=batch_frames, max_items=max_items, first_alone=first_alone,
+                      lookahead=lookahead, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
+                      seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence)

@@ -1,5 +1,6 @@
-"""The device waveform calls around sample() as Python functions (csrc/wave.hip, csrc/edit.hip, csrc/silence.hip): the cross-fade of
-decoded chunks, the join of a multi-voice script's pieces, the splice of the original recording around edited spans, the silence flags and the gather of the clipped signal --
+"""The device waveform calls around sample() as Python functions (csrc/wave.hip, csrc/deliver.hip, csrc/emit.hip, csrc/edit.hip,
+csrc/silence.hip): the cross-fade of decoded chunks, the join of a multi-voice script's pieces, the delivery at a client's rate, join
+and delivery for many streams in one launch, the splice of the original recording around edited spans, the silence flags and the gather of the clipped signal --
 and the two pieces of plumbing every ragged call of the audio side shares: `ragged_items` (a list of host or device tensors as
 device items under one base pointer) and `flat_segments` (segment tables as the C entry points read them).  The drivers that call
 these are in infer.py, which re-exports them."""
@@ -138,6 +139,90 @@ def deliver_plan(out_rate: int, n: int, final: bool = True) -> tuple[int, int]:
     return ln.value, ready.value
 
 
+def _deliver_bank(lib, h, dev, out_rate: int):
+    """The (24000 -> out_rate) filter bank in the handle h: uploaded on the rate's first use (which synchronises once), inside a
+    `torch.cuda.device(dev)` block."""
+    from .mel import _resample_bank_f32
+
+    known = h.__dict__.setdefault("_deliver_banks", set())
+    if out_rate != 24_000 and out_rate not in known:
+        deliver_plan(out_rate, 0)                                         # (refuses the rate before a bank is built for it)
+        bank = _resample_bank_f32(24_000, out_rate)
+        _lib.check(lib.f5_mel_resample_bank(h, 24_000, out_rate, C.c_void_p(bank.data_ptr()), bank.numel(), _stream_ptr(dev)),
+                   "f5_mel_resample_bank")
+        known.add(out_rate)
+
+
+def emit_plan(streams) -> tuple[list[int], int]:
+    """Where f5_wave_emit puts every stream: (byte offset per stream, bytes in all) -- the running byte total rounded up to 16 in
+    front of every stream, 4 bytes per f32 sample and 2 per s16 sample of its range."""
+    starts, run = [], 0
+    for st in streams:
+        o0, o1 = st["range"]
+        run = (run + 15) // 16 * 16
+        starts.append(run)
+        run += max(int(o1) - int(o0), 0) * (4 if _lib.PCM_FORMATS[st["sample_format"]] == _lib.F5_PCM_F32 else 2)
+    return starts, run
+
+
+def wave_emit(mel_spec, streams):
+    """Join and delivery for many streams in ONE launch (f5_wave_emit; the contract is in include/f5_hip.h): what a server tick
+    sends to its clients.  Every stream is a dict:
+      pieces         1-D f32 device tensors at 24 kHz with unit stride, read where they lie (wave_join's items);
+      fades          one per piece, the cross-fade in samples into what stands in front of it (0 opens a run);
+      settled        how many leading samples of the joined stream are delivered (0 .. join_plan's total);
+      final          whether the stream ends at `settled`;
+      range          (o0, o1): the output samples wanted, inside [0, ready] of deliver_plan(out_rate, settled, final);
+      out_rate, sample_format ("f32" / "s16"): the client's, each stream its own.
+    Returns (views, buffer): `buffer` one uint8 device tensor and views[s] stream s's samples in it, typed f32 or int16 -- bit for bit
+    wave_deliver(wave_join(pieces, fades)[:settled], ...) of that stream alone, without the joined waveform ever being written.
+    One copy of `buffer` brings every stream to the host; stream s's bytes start at emit_plan's offset.  The bank of a new rate is
+    uploaded on its first use (which synchronises once); otherwise one launch and no synchronisation.  At most 65535 streams and
+    65535 pieces in all."""
+    streams = list(streams)
+    if not streams:
+        raise ValueError("wave_emit: no stream")
+    if mel_spec.target_sample_rate != 24_000:
+        raise ValueError(f"wave_emit: the stage reads 24 kHz audio; this MelSpec runs at {mel_spec.target_sample_rate} Hz")
+    pieces, counts = [], []
+    for s, st in enumerate(streams):
+        if st["sample_format"] not in _lib.PCM_FORMATS:
+            raise ValueError(f"wave_emit: stream {s}: sample_format {st['sample_format']!r} (expected one of {sorted(_lib.PCM_FORMATS)})")
+        own = list(st["pieces"])
+        if not own or len(own) != len(st["fades"]):
+            raise ValueError(f"wave_emit: stream {s}: {len(own)} pieces for {len(st['fades'])} fades (need one fade per piece, at least "
+                             "one piece)")
+        pieces += own
+        counts.append(len(own))
+    if any(t.dim() != 1 or t.dtype != torch.float32 or t.shape[0] < 1 or t.stride(0) != 1 for t in pieces):
+        raise ValueError("wave_emit: every piece must be a 1-D f32 tensor with unit stride and at least one sample")
+    if any(t.device.type != "cuda" for t in pieces):
+        raise RuntimeError("wave_emit only runs on a GPU (there is no CPU path)")
+    S = len(streams)
+    dev, base, starts = _placed(pieces, "wave_emit")
+    at, total = emit_plan(streams)
+    out = torch.empty(max(total, 1), device=dev, dtype=torch.uint8)
+    lib, h = _lib.load(), mel_spec._handle(dev)
+    got = (C.c_int64 * S)()
+    i64 = lambda vals: (C.c_int64 * S)(*[int(v) for v in vals])   # noqa: E731
+    with torch.cuda.device(dev):
+        for rate in sorted({int(st["out_rate"]) for st in streams}):
+            _deliver_bank(lib, h, dev, rate)
+        _lib.check(lib.f5_wave_emit(h, C.c_void_p(base), S, _lib.int_array(counts), starts, _lib.int_array([t.shape[0] for t in pieces]),
+                                    _lib.int_array([f for st in streams for f in st["fades"]]), i64(st["settled"] for st in streams),
+                                    _lib.int_array([bool(st["final"]) for st in streams]), i64(st["range"][0] for st in streams),
+                                    i64(st["range"][1] for st in streams), _lib.int_array([st["out_rate"] for st in streams]),
+                                    _lib.int_array([_lib.PCM_FORMATS[st["sample_format"]] for st in streams]), _ptr(out), total, got,
+                                    _stream_ptr(dev)), "f5_wave_emit")
+    assert list(got) == at
+    views = []
+    for a, st in zip(at, streams):
+        f32 = _lib.PCM_FORMATS[st["sample_format"]] == _lib.F5_PCM_F32
+        count = max(int(st["range"][1]) - int(st["range"][0]), 0)
+        views.append(out[a:a + count * (4 if f32 else 2)].view(torch.float32 if f32 else torch.int16))
+    return views, out
+
+
 def wave_deliver(mel_spec, items, *, out_rate: int, sample_format: str = "f32", ranges=None, final=True):
     """Generated audio at a client's rate and sample format (f5_wave_deliver; the contract is in include/f5_hip.h): items are 1-D
     f32 device tensors at 24 kHz with unit stride, read where they lie; `final` (one bool, or one per item) says whether an item
@@ -146,8 +231,6 @@ def wave_deliver(mel_spec, items, *, out_rate: int, sample_format: str = "f32", 
     (24000 -> out_rate) filter bank (the bank of a new rate is uploaded on its first use, which synchronises once).  Returns one
     device tensor per item, f32 or int16 (sample_format "f32" / "s16": the 16-bit view of generated audio, y * 32767 rounded to
     nearest even and clamped), views of one packed buffer.  One launch, no synchronisation; at most 65535 items."""
-    from .mel import _resample_bank_f32
-
     items = list(items)
     if not items:
         raise ValueError("wave_deliver: no item")
@@ -176,13 +259,7 @@ def wave_deliver(mel_spec, items, *, out_rate: int, sample_format: str = "f32", 
     lib, h = _lib.load(), mel_spec._handle(dev)
     at = (C.c_int64 * B)()
     with torch.cuda.device(dev):
-        known = h.__dict__.setdefault("_deliver_banks", set())
-        if out_rate != 24_000 and out_rate not in known:
-            deliver_plan(out_rate, 0)                                     # (refuses the rate before a bank is built for it)
-            bank = _resample_bank_f32(24_000, out_rate)
-            _lib.check(lib.f5_mel_resample_bank(h, 24_000, out_rate, C.c_void_p(bank.data_ptr()), bank.numel(), _stream_ptr(dev)),
-                       "f5_mel_resample_bank")
-            known.add(out_rate)
+        _deliver_bank(lib, h, dev, out_rate)
         _lib.check(lib.f5_wave_deliver(h, C.c_void_p(base), B, starts, _lib.int_array(ns), _lib.int_array(finals),
                                        (C.c_int64 * B)(*[int(o0) for o0, _ in ranges]), (C.c_int64 * B)(*[int(o1) for _, o1 in ranges]),
                                        out_rate, fmt, _ptr(out), total, at, _stream_ptr(dev)), "f5_wave_deliver")
