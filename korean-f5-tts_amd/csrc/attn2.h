@@ -228,7 +228,9 @@ __global__ __launch_bounds__(512) void attn2_fwd_kernel(const T* __restrict__ Q,
                                                                const T* __restrict__ Vt, T* __restrict__ O, int H,
                                                                int N, int Npad, const int* __restrict__ kv_lens,
                                                                int nbatch_lens, const int* __restrict__ q_lens,
-                                                               const int* __restrict__ o_row_start, float* __restrict__ Of = nullptr) {
+                                                               const int* __restrict__ o_row_start, float* __restrict__ Of = nullptr,
+                                                               int wt = 0) {
+    // wt: write-through stores of O (f5_common.h "store policy"; the pre-split Of keeps plain stores)
     // Of (F5_PREC_F16X3, or null): the output as f32 rows PRE-SPLIT into f16 hi / lo planes (store4_planar) -- the A operand of the
     // out-projection's pre-split GEMM -- instead of T rows in O
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -357,6 +359,26 @@ __global__ __launch_bounds__(512) void attn2_fwd_kernel(const T* __restrict__ Q,
             const int q = q0 + qs * 16 + l15;
             // (o_row_start: output rows of a packed variable-length batch, RowPack: batch row b owns rows o_row_start[b] ..)
             const size_t orow = o_row_start ? (size_t)o_row_start[b] + q : (size_t)b * N + q;
+            if (wt && !Of) {
+                // two 16-column sub-tiles dt, dt + 1 exchange 8-byte pieces between the lane groups (regroup_pair16, every lane takes
+                // part): a lane stores 16 contiguous bytes, a wave instruction 16 rows x 64 B.  The same values, the same rows.
+                const bool in = q < (o_row_start ? min(N, o_row_start[b + 1] - o_row_start[b]) : N);
+#pragma unroll
+                for (int dt = 0; dt < 4; dt += 2) {
+                    u32x2 pk[2];
+#pragma unroll
+                    for (int d2 = 0; d2 < 2; ++d2) {
+                        float v[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            v[r] = (o[dt + d2][qs][r] * a0 + mb[(((dt + d2) * 2 + qs) * 4 + r) * 64 + lane] * a1) * inv;
+                        pk[d2] = pack4<T>(v[0], v[1], v[2], v[3]);
+                    }
+                    const u32x4 d = regroup_pair16(pk[0], pk[1]);
+                    if (in) store16_wt(O, (orow * (H * 64) + h * 64 + dt * 16 + g * 8) * 2, d);
+                }
+                continue;
+            }
             if (q < (o_row_start ? min(N, o_row_start[b + 1] - o_row_start[b]) : N)) {
                 T* dst = O + orow * (H * 64) + h * 64 + g * 4;
 #pragma unroll
@@ -383,7 +405,8 @@ template <> inline float attention_q_scale<f16_t>() { return attention_q_scale<b
 template <typename T>
 inline hipError_t launch_attention_v2(hipStream_t s, const T* Q, const T* K, const T* Vt, T* O, int Bp, int H,
                                       int N, int Npad, const int* kv_lens, int nbatch_lens, const int* q_lens, const int* o_row_start,
-                                      float* o_planar_f32 = nullptr) {
+                                      float* o_planar_f32 = nullptr, int wt = 0) {
+    wt = wt && (size_t)Bp * N * H * 64 * sizeof(T) < F5_WT_MAX_BYTES ? 1 : 0;   // (32-bit store offsets)
     constexpr int smem = 3 * 2 * 64 * 128;  // 48 KiB ring (>= 4 * 36 * 64 * 4 = 36 KiB merge scratch)
     dim3 grid(Bp * H, (N + 127) / 128);
     const int var = attn2_variant();
@@ -396,7 +419,7 @@ inline hipError_t launch_attention_v2(hipStream_t s, const T* Q, const T* K, con
             if (e != hipSuccess) return e;                                                                             \
             attr_set = true;                                                                                           \
         }                                                                                                              \
-        hipLaunchKernelGGL((attn2_fwd_kernel<T, V>), grid, dim3(512), smem, s, Q, K, Vt, O, H, N, Npad, kv_lens, nbatch_lens, q_lens, o_row_start, o_planar_f32); \
+        hipLaunchKernelGGL((attn2_fwd_kernel<T, V>), grid, dim3(512), smem, s, Q, K, Vt, O, H, N, Npad, kv_lens, nbatch_lens, q_lens, o_row_start, o_planar_f32, wt); \
     }
     if (var == 0) F5_ATTN2_LAUNCH(0)
     else if (var == 3) F5_ATTN2_LAUNCH(3)
@@ -410,17 +433,17 @@ inline hipError_t launch_attention_v2(hipStream_t s, const T* Q, const T* K, con
 //  batch row b as lens[b % nbl] and may be null)
 inline hipError_t launch_attention_any(hipStream_t s, const bf16_t* Q, const bf16_t* K, const bf16_t* Vt, bf16_t* O, int Bp,
                                        int H, int N, int Npad, const int* kv_lens, int nbl, const int* q_lens = nullptr,
-                                       const int* o_row_start = nullptr, bool /*split16*/ = false, bool /*o_planar*/ = false, int /*hi_only*/ = 0) {
-    return launch_attention_v2<bf16_t>(s, Q, K, Vt, O, Bp, H, N, Npad, kv_lens, nbl, q_lens, o_row_start);
+                                       const int* o_row_start = nullptr, bool /*split16*/ = false, bool /*o_planar*/ = false, int /*hi_only*/ = 0, int wt = 0) {
+    return launch_attention_v2<bf16_t>(s, Q, K, Vt, O, Bp, H, N, Npad, kv_lens, nbl, q_lens, o_row_start, nullptr, wt);
 }
 inline hipError_t launch_attention_any(hipStream_t s, const f16_t* Q, const f16_t* K, const f16_t* Vt, f16_t* O, int Bp,
                                        int H, int N, int Npad, const int* kv_lens, int nbl, const int* q_lens = nullptr,
-                                       const int* o_row_start = nullptr, bool /*split16*/ = false, bool /*o_planar*/ = false, int /*hi_only*/ = 0) {
-    return launch_attention_v2<f16_t>(s, Q, K, Vt, O, Bp, H, N, Npad, kv_lens, nbl, q_lens, o_row_start);
+                                       const int* o_row_start = nullptr, bool /*split16*/ = false, bool /*o_planar*/ = false, int /*hi_only*/ = 0, int wt = 0) {
+    return launch_attention_v2<f16_t>(s, Q, K, Vt, O, Bp, H, N, Npad, kv_lens, nbl, q_lens, o_row_start, nullptr, wt);
 }
 inline hipError_t launch_attention_any(hipStream_t s, const float* Q, const float* K, const float* Vt, float* O, int Bp, int H,
                                        int N, int Npad, const int* kv_lens, int nbl, const int* q_lens = nullptr,
-                                       const int* o_row_start = nullptr, bool split16 = false, bool o_planar = false, int hi_only = 0) {
+                                       const int* o_row_start = nullptr, bool split16 = false, bool o_planar = false, int hi_only = 0, int /*wt*/ = 0) {
     if (split16) return launch_attention_split(s, Q, K, Vt, O, Bp, H, N, Npad, kv_lens, nbl, q_lens, o_row_start, o_planar, hi_only);   // F5_PREC_F16X3
     return launch_attention<float>(s, Q, K, Vt, O, Bp, H, N, Npad, kv_lens, nbl, q_lens, o_row_start);
 }

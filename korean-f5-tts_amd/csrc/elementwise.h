@@ -28,12 +28,39 @@ inline int ew_blocks(long total, int per_block = 256, int cap = 4096) {
 // Cache, so every GEMM of a step otherwise starts with HBM-latency misses on its W tiles; this launch is latency-bound
 // and has the memory system to itself.
 struct Prefetch { const char* p0 = nullptr; size_t n0 = 0; const char* p1 = nullptr; size_t n1 = 0; };
+// Write-through form of a norm kernel's row store (f5_common.h "store policy"): lane -> columns 4 lane + 256 i, y[i] = the four results of
+// chunk i (the lane -> column map of the statistics is untouched).  16-bit rows: lanes 2p and 2p + 1 exchange halves of two whole chunks
+// i, i + 1 -- the even lane then holds 8 contiguous values of chunk i, the odd lane 8 of chunk i + 1 -- and store 16 bytes each; a
+// chunk without a whole partner keeps its 8-byte pieces.  f32 rows are 16 bytes per lane already (pre-split rows: two 8-byte pieces).
+template <typename TO>
+__device__ __forceinline__ void store_row_wt(TO* out, size_t row_off, const float4 (&y)[8], int D, int lane, int planar) {
+    if constexpr (sizeof(TO) == 2) {
+#pragma unroll
+        for (int i = 0; i < 8; i += 2) {
+            const u32x2 a = pack4<TO>(y[i].x, y[i].y, y[i].z, y[i].w), b = pack4<TO>(y[i + 1].x, y[i + 1].y, y[i + 1].z, y[i + 1].w);
+            if ((i + 2) * 256 <= D) {   // (wave-uniform: every lane takes part in the exchange)
+                const bool odd = lane & 1;
+                const u32x2 send = odd ? a : b;
+                const u32x2 recv = {(unsigned)__shfl_xor((int)send[0], 1, 64), (unsigned)__shfl_xor((int)send[1], 1, 64)};
+                const u32x4 d = odd ? u32x4{recv[0], recv[1], b[0], b[1]} : u32x4{a[0], a[1], recv[0], recv[1]};
+                store16_wt(out, (row_off + (i + (odd ? 1 : 0)) * 256 + (lane >> 1) * 8) * 2, d);
+            } else {
+                if (lane * 4 + i * 256 < D) store8_wt(out + row_off + lane * 4 + i * 256, a);
+                if (lane * 4 + (i + 1) * 256 < D) store8_wt(out + row_off + lane * 4 + (i + 1) * 256, b);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (lane * 4 + i * 256 < D) store4_at_wt(out, row_off, lane * 4 + i * 256, planar, y[i].x, y[i].y, y[i].z, y[i].w);
+    }
+}
 template <typename TO>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, TO* __restrict__ out,
                                                         int ldo, int R, int D, float eps, const float* __restrict__ A,
                                                         const float* __restrict__ Bv, int vec_stride,
                                                         int rows_per_batch, int modulate, Prefetch pf,
-                                                        const int* __restrict__ m_limit = nullptr, int planar = 0) {
+                                                        const int* __restrict__ m_limit = nullptr, int planar = 0, int wt = 0) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R || (m_limit && r >= *m_limit)) return;   // (m_limit: rows present in a packed batch, RowPack)
@@ -75,15 +102,28 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+    if (wt) {   // write-through stores: the same expressions, stored by store_row_wt
+        float4 y[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = lane * 4 + i * 256;
-        if (c < D) {
+        for (int i = 0; i < 8; ++i) {
             float4 a = ga[i];
             const float4 b = gb[i];
             if (modulate) { a.x += 1.f; a.y += 1.f; a.z += 1.f; a.w += 1.f; }
-            store4_at(out + (size_t)r * ldo, c, planar, (v[i].x - mean) * rstd * a.x + b.x, (v[i].y - mean) * rstd * a.y + b.y,
-                      (v[i].z - mean) * rstd * a.z + b.z, (v[i].w - mean) * rstd * a.w + b.w);
+            y[i] = make_float4((v[i].x - mean) * rstd * a.x + b.x, (v[i].y - mean) * rstd * a.y + b.y, (v[i].z - mean) * rstd * a.z + b.z,
+                               (v[i].w - mean) * rstd * a.w + b.w);
+        }
+        store_row_wt(out, (size_t)r * ldo, y, D, lane, planar);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = lane * 4 + i * 256;
+            if (c < D) {
+                float4 a = ga[i];
+                const float4 b = gb[i];
+                if (modulate) { a.x += 1.f; a.y += 1.f; a.z += 1.f; a.w += 1.f; }
+                store4_at(out + (size_t)r * ldo, c, planar, (v[i].x - mean) * rstd * a.x + b.x, (v[i].y - mean) * rstd * a.y + b.y,
+                          (v[i].z - mean) * rstd * a.z + b.z, (v[i].w - mean) * rstd * a.w + b.w);
+            }
         }
     }
 #pragma unroll
@@ -93,7 +133,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // x_transformers.RMSNorm as used by UNetT (unett.py:154,168,185): F.normalize(x, dim=-1) * sqrt(D) * g
 template <typename TO>
 __global__ __launch_bounds__(256) void xrmsnorm_kernel(const float* __restrict__ x, int ldx, TO* __restrict__ out, int ldo,
-                                                       int R, int D, const float* __restrict__ gvec, int planar = 0) {
+                                                       int R, int D, const float* __restrict__ gvec, int planar = 0, int wt = 0) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;
@@ -108,6 +148,17 @@ __global__ __launch_bounds__(256) void xrmsnorm_kernel(const float* __restrict__
     }
     const float nrm = fmaxf(sqrtf(wave_sum(q)), 1e-12f);
     const float sc = sqrtf((float)D) / nrm;
+    if (wt) {   // write-through stores: the same expressions, stored by store_row_wt
+        float4 y[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = lane * 4 + i * 256;
+            const float4 gg = c < D ? *reinterpret_cast<const float4*>(gvec + c) : make_float4(0, 0, 0, 0);
+            y[i] = make_float4(v[i].x * sc * gg.x, v[i].y * sc * gg.y, v[i].z * sc * gg.z, v[i].w * sc * gg.w);
+        }
+        store_row_wt(out, (size_t)r * ldo, y, D, lane, planar);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = lane * 4 + i * 256;
@@ -117,9 +168,12 @@ __global__ __launch_bounds__(256) void xrmsnorm_kernel(const float* __restrict__
         }
     }
 }
+// wt: write-through stores asked for (applied where the output is small enough for their 32-bit offsets)
+inline int wt_fits(int wt, size_t bytes) { return wt && bytes < F5_WT_MAX_BYTES ? 1 : 0; }
 template <typename TO>
-inline void launch_xrmsnorm(hipStream_t s, const float* x, TO* out, int rows, int D, const float* g, int planar) {
-    hipLaunchKernelGGL((xrmsnorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, x, D, out, D, rows, D, g, planar);
+inline void launch_xrmsnorm(hipStream_t s, const float* x, TO* out, int rows, int D, const float* g, int planar, int wt = 0) {
+    hipLaunchKernelGGL((xrmsnorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, x, D, out, D, rows, D, g, planar,
+                       wt_fits(wt, (size_t)rows * D * sizeof(TO)));
 }
 
 // --------------------------------------------------------------------------------- input-embedding operand

@@ -52,6 +52,7 @@ static Switches read_switches(const f5_config& c) {
     sw.weight_prefetch = flag("F5_WEIGHT_PREFETCH", true);
     if (const char* v = getenv("F5_X3_ABLATE")) sw.x3_ablate = c.precision == F5_PREC_F16X3 ? atoi(v) : 0;
     sw.x3_attn_split = flag("F5_X3_ATTN_SPLIT", false);
+    if (const char* v = getenv("F5_STORE_WT")) sw.store_wt = atoi(v) & F5_WT_ALL;
     if (const char* v = getenv("F5_LEN_BUCKET")) sw.len_bucket = (int)std::min(std::max(atol(v), -1L), 1L << 20);   // (f5_create refuses a bad granule)
     return sw;
 }

@@ -458,6 +458,9 @@ struct FwdCtx {
     const int* ml() const { return pk.rows_dev; }              // device row count of a packed batch, or null
     int mh() const { return pk ? (int)pk.rows_host : 0; }      // rows expected (the call's own lengths): tile choice only
     int pl() const { return e->split16 ? 1 : 0; }              // F5_PREC_F16X3: xn / ao / ffh are written pre-split (the A operands of the block GEMMs)
+    // write-through stores for class `bit` (F5_WT_*, Switches::store_wt): only in the latency-bound regime -- few rows, one round of tiles --
+    // where a kernel's whole output would otherwise sit dirty in L2 when it ends (the condition of the weight prefetch)
+    int wt(int bit) const { return rows <= 4096 && (e->sw.store_wt & bit) ? 1 : 0; }
     double gflops(double n, double k) const { return 2.0 * (pk ? pk.rows_host : (double)rows) * n * k; }
     // one backbone GEMM over all rows, as a profiled launch
     template <typename T, typename Epi> int gemm(const T* A, int lda, const LinW<T>& L, int n, int k, const Epi& epi, bool a_split = false) const {
@@ -567,7 +570,7 @@ static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, boo
         }
         HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
             return launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, N, w.Npad, attn_lens, B, f.lens_dev, pk.row_start, e->split16, pl,
-                                        e->sw.x3_attn_hi());
+                                        e->sw.x3_attn_hi(), f.wt(F5_WT_ATTN));
         }));
     }
     f.ablate(8, w.ao, inner);
@@ -578,7 +581,7 @@ static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, boo
 template <typename T> static int ff_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, const EpiGateRes& out_epi) {
     const int D = f.e->cfg.dim, F = f.e->cfg.ff_dim, pl = f.pl();
     f.ablate(16, w.xn, D);
-    CHK(f.gemm(w.xn, D, bw.ff1, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl}, pl));
+    CHK(f.gemm(w.xn, D, bw.ff1, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl, f.wt(F5_WT_STORE16)}, pl));
     f.ablate(32, w.ffh, F);
     return f.gemm(w.ffh, F, bw.ff2, D, F, out_epi, pl);
 }
@@ -630,7 +633,7 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
         using TO = std::remove_pointer_t<decltype(out)>;
         return pr.timed(PC_LN, s, [&] {
             hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, out, D, rows, D, 1e-6f, scale, shift,
-                               mod_stride, N, 1, pf, ml, planar);
+                               mod_stride, N, 1, pf, ml, planar, f.wt(F5_WT_LN));
             return hipGetLastError();
         });
     };
@@ -638,9 +641,9 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
         BlockW<T>& bw = P.blocks[l];
         const float* m = mod_row + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
         HIPCHK(adaln(w.xn, m + D, m, prefetch(bw.qkv, bw.out), pl));
-        CHK(attention_block<T>(f, w, bw, qk_norm, EpiGateRes{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens}));
+        CHK(attention_block<T>(f, w, bw, qk_norm, EpiGateRes{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens, f.wt(F5_WT_GATE_RES)}));
         HIPCHK(adaln(w.xn, m + 4 * D, m + 3 * D, prefetch(bw.ff1, bw.ff2), pl));
-        CHK(ff_block<T>(f, w, bw, EpiGateRes{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr}));
+        CHK(ff_block<T>(f, w, bw, EpiGateRes{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr, f.wt(F5_WT_GATE_RES)}));
     }
     if (long_skip) {   // x = long_skip_connection(cat((x, residual), dim=-1))   (dit.py:323-324)
         auto cat_skip = [&](auto* cat) {
@@ -700,7 +703,7 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
     const int pl = f.pl();
     auto rmsnorm = [&](const float* x, auto* out, const float* g, int planar) {   // out (rows of T, or pre-split f32 rows) = RMSNorm(x) * g
         return pr.timed(PC_LN, s, [&] {
-            launch_xrmsnorm(s, x, out, rows, D, g, planar);
+            launch_xrmsnorm(s, x, out, rows, D, g, planar, f.wt(F5_WT_LN));
             return hipGetLastError();
         });
     };
@@ -718,9 +721,9 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
             CHK(f.gemm(w.cat2, 2 * D, bw.skip, D, 2 * D, EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}, pl));
         }
         HIPCHK(rmsnorm(x_in, w.xn, bw.norm1_g, pl));
-        CHK(attention_block<T>(f, w, bw, false, EpiGateRes{w.x, x_in, D, bw.out.b, nullptr, 0, Nt, lens_dev}));
+        CHK(attention_block<T>(f, w, bw, false, EpiGateRes{w.x, x_in, D, bw.out.b, nullptr, 0, Nt, lens_dev, f.wt(F5_WT_GATE_RES)}));
         HIPCHK(rmsnorm(w.x, w.xn, bw.norm2_g, pl));
-        CHK(ff_block<T>(f, w, bw, EpiGateRes{x_out, w.x, D, bw.ff2.b, nullptr, 0, Nt, nullptr}));
+        CHK(ff_block<T>(f, w, bw, EpiGateRes{x_out, w.x, D, bw.ff2.b, nullptr, 0, Nt, nullptr, f.wt(F5_WT_GATE_RES)}));
     }
     if (e->io_split) {   // F5_PREC_F16P: final norm to pre-split f32 rows (in the skip stack's first slot: every skip has been popped) + split projection
         HIPCHK(rmsnorm(w.x, w.skips, P.norm_out_g, 1));

@@ -159,6 +159,9 @@ struct Switches {
     // [8, 1024]: an eligible sample() call (bucket_eligible, engine_impl.h) is planned at N rounded up to the granule and its true
     // length reaches the kernels through the device tables of RowPack, so one captured graph serves every N of a bucket.
     int len_bucket = 0;
+    // F5_STORE_WT=<mask of F5_WT_*, f5_common.h>: which classes of block kernel store write-through where a forward runs at <= 4,096 rows
+    // (FwdCtx::wt).  Results do not depend on it.  The default: the classes that paid on their own at C2.
+    int store_wt = F5_WT_DEFAULT;
 };
 inline bool valid_len_bucket(long g) { return g == 0 || (g >= 8 && g <= 1024 && g % 8 == 0); }
 

@@ -130,6 +130,74 @@ template <typename TO> __device__ __forceinline__ void store4_at(TO* row, int co
     store4(row + col, a, b, c, d);
 }
 
+// ---- store policy (F5_STORE_WT, DESIGN.md section 6 "C2: write-through stores") --------------------------------------------------------------
+// A kernel whose output fits the L2s leaves it there DIRTY; the next kernel runs on other XCDs, so the lines are written back in a serial
+// phase after the last workgroup has retired.  A write-through (sc1) store leaves L2 when it is issued, under the epilogue's own latency
+// chain.  The same values go to the same addresses; one mask bit per class of kernel, used only where a forward runs at few rows.
+// (bit 2, the QKV epilogue, has no write-through form: it lost at C2 -- gemm.h EpiQKV; the bit is ignored)
+enum { F5_WT_LN = 1, F5_WT_ATTN = 4, F5_WT_GATE_RES = 8, F5_WT_STORE16 = 16, F5_WT_ALL = 29, F5_WT_DEFAULT = F5_WT_ALL };
+// The kernel-level entry points (f5k_*) and the diagnostic tools take theirs from the process (kapi_diag.hip f5x_set_store_policy).
+inline int& store_policy() { static int m = 0; return m; }
+// buffer stores address `base` + a 32-bit byte offset: a write-through form is used only for outputs below this size
+constexpr size_t F5_WT_MAX_BYTES = (size_t)1 << 31;
+// Compiler-visible forms only (no inline asm fed from accumulators: hipcc then places the waits and hazards itself).  16 bytes: a raw
+// buffer store with the sc1 bit (`base` must be wave-uniform: it becomes the resource descriptor); 8 bytes: a relaxed agent-scope
+// atomic store, which is global_store_dwordx2 sc1.
+// a pointer every lane agrees on, as the compiler can see it (two scalar registers).  readfirstlane returns a SIGNED int: each half goes
+// through `unsigned`, or a low word with bit 31 set would sign-extend over the high word.
+template <typename T> __device__ __forceinline__ T* uniform_ptr(T* p) {
+    const size_t a = (size_t)p;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    return reinterpret_cast<T*>(((size_t)hi << 32) | (size_t)lo);
+}
+__device__ __forceinline__ void store16_wt(void* base, size_t byte_off, u32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000), (unsigned)byte_off, 0, 16);
+}
+__device__ __forceinline__ void store8_wt(void* p, u32x2 v) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+// write-through counterparts of store4 / store4_planar / store4_at: element `off` of `base` (wave-uniform), the same bytes
+__device__ __forceinline__ void store4_wt(float* base, size_t off, float a, float b, float c, float d) {
+    store16_wt(base, off * 4, __builtin_bit_cast(u32x4, f32x4{a, b, c, d}));
+}
+__device__ __forceinline__ void store4_wt(bf16_t* base, size_t off, float a, float b, float c, float d) { store8_wt(base + off, pack4<bf16_t>(a, b, c, d)); }
+__device__ __forceinline__ void store4_wt(f16_t* base, size_t off, float a, float b, float c, float d) { store8_wt(base + off, pack4<f16_t>(a, b, c, d)); }
+__device__ __forceinline__ void store4_planar_wt(float* base, size_t row_off, int col, float a, float b, float c, float d) {
+    u32x2 hi, lo;
+    split4_f16(__builtin_bit_cast(u32x4, f32x4{a, b, c, d}), hi, lo);
+    const int kk = col & 31;
+    char* p = reinterpret_cast<char*>(base + row_off + (col & ~31)) + ((kk & 15) >> 2) * 16 + (kk >> 4) * 8;
+    store8_wt(p, hi);
+    store8_wt(p + 64, lo);
+}
+template <typename TO> __device__ __forceinline__ void store4_at_wt(TO* base, size_t row_off, int col, int planar, float a, float b, float c, float d) {
+    if constexpr (std::is_same_v<TO, float>) {
+        if (planar) { store4_planar_wt(base, row_off, col, a, b, c, d); return; }
+    }
+    store4_wt(base, row_off + col, a, b, c, d);
+}
+// the policy as a compile-time choice of one call site (the plain form compiles to what it compiled to before there was a policy)
+template <bool WT, typename TO> __device__ __forceinline__ void store4_sel(TO* base, size_t off, float a, float b, float c, float d) {
+    if constexpr (WT) store4_wt(base, off, a, b, c, d);
+    else store4(base + off, a, b, c, d);
+}
+
+// Regroups the 8-byte pieces of TWO neighbouring 16-column accumulator sub-tiles (a = columns 0..15, b = 16..31 of the pair; lane group
+// g = lane >> 4 holds columns 4g..4g+3 of each) so that a lane holds 16 contiguous bytes: afterwards {a, b} of lane group g are the
+// columns 8g..8g+7 of the 32-column pair, same row.  Two half / row swaps per dword (gfx950), no LDS.  Every lane must be active.
+__device__ __forceinline__ u32x4 regroup_pair16(u32x2 a, u32x2 b) {
+    u32x4 r;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        auto h = __builtin_amdgcn_permlane32_swap(a[w], b[w], false, false);                 // a: (a0 a1 b0 b1)  b: (a2 a3 b2 b3) by lane group
+        auto q = __builtin_amdgcn_permlane16_swap((unsigned)h[0], (unsigned)h[1], false, false);   // a: (a0 a2 b0 b2)  b: (a1 a3 b1 b3)
+        r[w] = (unsigned)q[0];
+        r[2 + w] = (unsigned)q[1];
+    }
+    return r;
+}
+
 // eight f32 -> one 16-byte MFMA operand fragment of 16-bit type T
 template <typename T> __device__ __forceinline__ u32x4 pack8(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7);
 template <> __device__ __forceinline__ u32x4 pack8<bf16_t>(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7) {

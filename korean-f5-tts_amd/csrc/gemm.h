@@ -78,6 +78,8 @@ struct NoCtx {};
 template <typename TO, int ACT = -1> struct EpiStore {  // out = act(acc + bias)
     TO* out; int ldo; const float* bias; int act;
     int planar = 0;      // TO = float only: store pre-split for the next GEMM's A operand (f5_common.h store4_planar)
+    int wt = 0;          // write-through stores (the ring kernel's fragment-order path only; f5_common.h "store policy")
+    static constexpr bool kWT = sizeof(TO) == 2, kRegroup16 = kWT;   // (f32 outputs -- input projection, vocoders -- have no such form)
     struct RowCtx { TO* p; };
     struct ColCtx { float4 b; int n; };
     typedef NoCtx TRowCtx;
@@ -90,11 +92,28 @@ template <typename TO, int ACT = -1> struct EpiStore {  // out = act(acc + bias)
     }
     typedef NoCtx Pre;
     __device__ __forceinline__ NoCtx preload(const RowCtx&, const ColCtx&) const { return {}; }
+    template <bool WT = false>
     __device__ __forceinline__ void store(const RowCtx& r, const ColCtx& c, f32x4 v, const NoCtx&) const {
         const int a = ACT >= 0 ? ACT : act;
-        store4_at(r.p, c.n, planar, apply_act(v[0] + c.b.x, a), apply_act(v[1] + c.b.y, a), apply_act(v[2] + c.b.z, a),
-                  apply_act(v[3] + c.b.w, a));
+        if constexpr (WT)
+            store4_at_wt(out, (size_t)(r.p - out), c.n, planar, apply_act(v[0] + c.b.x, a), apply_act(v[1] + c.b.y, a),
+                         apply_act(v[2] + c.b.z, a), apply_act(v[3] + c.b.w, a));
+        else
+            store4_at(r.p, c.n, planar, apply_act(v[0] + c.b.x, a), apply_act(v[1] + c.b.y, a), apply_act(v[2] + c.b.z, a),
+                      apply_act(v[3] + c.b.w, a));
     }
+    // the regrouped write-through form (gemm2.h): the 8 bytes store() writes, where, and whether two sub-tiles may share 16-byte stores
+    __device__ __forceinline__ u32x2 pack(const RowCtx&, const ColCtx& c, f32x4 v, const NoCtx&) const {
+        const int a = ACT >= 0 ? ACT : act;
+        if constexpr (sizeof(TO) == 2)
+            return pack4<TO>(apply_act(v[0] + c.b.x, a), apply_act(v[1] + c.b.y, a), apply_act(v[2] + c.b.z, a), apply_act(v[3] + c.b.w, a));
+        else return u32x2{0u, 0u};
+    }
+    __device__ __forceinline__ bool pair_ok(int, int) const { return (ldo & 7) == 0; }
+    __device__ __forceinline__ bool keep(const RowCtx&) const { return true; }
+    __device__ __forceinline__ TO* dst_base(const ColCtx&) const { return out; }
+    __device__ __forceinline__ size_t dst_off(const RowCtx& r, const ColCtx& c) const { return (size_t)(r.p - out) + c.n; }
+    template <bool WT = false> __device__ __forceinline__ void tstore(const NoCtx&, const NoCtx&, f32x4) const {}
     static constexpr bool kStaged = sizeof(TO) == 2;
     __device__ __forceinline__ bool staged_ok(bool transposed) const { return !transposed; }
     template <int MI, int NJ>
@@ -125,19 +144,18 @@ template <typename TO, int ACT = -1> struct EpiStore {  // out = act(acc + bias)
     }
     __device__ __forceinline__ NoCtx trow(int, int) const { return {}; }
     __device__ __forceinline__ NoCtx tcol(int) const { return {}; }
-    __device__ __forceinline__ void tstore(const NoCtx&, const NoCtx&, f32x4) const {}
 };
 
 // f(epilogue-with-static-activation); any other epilogue type passes through unchanged
 template <typename Epi, typename F> inline hipError_t with_static_act(const Epi& e, F&& f) { return f(e); }
 template <typename TO, typename F> inline hipError_t with_static_act(const EpiStore<TO, -1>& e, F&& f) {
     switch (e.act) {
-        case F5_ACT_NONE: return f(EpiStore<TO, F5_ACT_NONE>{e.out, e.ldo, e.bias, e.act, e.planar});
-        case F5_ACT_GELU_TANH: return f(EpiStore<TO, F5_ACT_GELU_TANH>{e.out, e.ldo, e.bias, e.act, e.planar});
-        case F5_ACT_GELU_ERF: return f(EpiStore<TO, F5_ACT_GELU_ERF>{e.out, e.ldo, e.bias, e.act, e.planar});
-        case F5_ACT_SILU: return f(EpiStore<TO, F5_ACT_SILU>{e.out, e.ldo, e.bias, e.act, e.planar});
-        case F5_ACT_MISH: return f(EpiStore<TO, F5_ACT_MISH>{e.out, e.ldo, e.bias, e.act, e.planar});
-        case F5_ACT_LOGCLAMP: return f(EpiStore<TO, F5_ACT_LOGCLAMP>{e.out, e.ldo, e.bias, e.act, e.planar});
+        case F5_ACT_NONE: return f(EpiStore<TO, F5_ACT_NONE>{e.out, e.ldo, e.bias, e.act, e.planar, e.wt});
+        case F5_ACT_GELU_TANH: return f(EpiStore<TO, F5_ACT_GELU_TANH>{e.out, e.ldo, e.bias, e.act, e.planar, e.wt});
+        case F5_ACT_GELU_ERF: return f(EpiStore<TO, F5_ACT_GELU_ERF>{e.out, e.ldo, e.bias, e.act, e.planar, e.wt});
+        case F5_ACT_SILU: return f(EpiStore<TO, F5_ACT_SILU>{e.out, e.ldo, e.bias, e.act, e.planar, e.wt});
+        case F5_ACT_MISH: return f(EpiStore<TO, F5_ACT_MISH>{e.out, e.ldo, e.bias, e.act, e.planar, e.wt});
+        case F5_ACT_LOGCLAMP: return f(EpiStore<TO, F5_ACT_LOGCLAMP>{e.out, e.ldo, e.bias, e.act, e.planar, e.wt});
         default: return hipErrorInvalidValue;
     }
 }
@@ -148,6 +166,8 @@ template <typename TO, typename F> inline hipError_t with_static_act(const EpiSt
 struct EpiGateRes {
     float* x; const float* res; int ld; const float* bias; const float* gate; int gate_stride; int rows_per_batch;
     const int* lens;
+    int wt = 0;          // write-through stores (the ring kernel's fragment-order path only; f5_common.h "store policy")
+    static constexpr bool kWT = true, kRegroup16 = false;
     struct RowCtx { size_t off; const float* g; bool masked; };
     struct ColCtx { float4 b; int n; };
     typedef NoCtx TRowCtx;
@@ -167,6 +187,7 @@ struct EpiGateRes {
         return {*reinterpret_cast<const float4*>(res + rc.off + c.n),
                 rc.g ? *reinterpret_cast<const float4*>(rc.g + c.n) : make_float4(1, 1, 1, 1)};
     }
+    template <bool WT = false>
     __device__ __forceinline__ void store(const RowCtx& rc, const ColCtx& c, f32x4 v, const Pre& p) const {
         float4 r = p.r;
         if (!rc.masked) {
@@ -174,11 +195,12 @@ struct EpiGateRes {
             r.x += g.x * (v[0] + c.b.x); r.y += g.y * (v[1] + c.b.y);
             r.z += g.z * (v[2] + c.b.z); r.w += g.w * (v[3] + c.b.w);
         }
-        *reinterpret_cast<float4*>(x + rc.off + c.n) = r;
+        if constexpr (WT) store4_wt(x, rc.off + c.n, r.x, r.y, r.z, r.w);
+        else *reinterpret_cast<float4*>(x + rc.off + c.n) = r;
     }
     __device__ __forceinline__ NoCtx trow(int, int) const { return {}; }
     __device__ __forceinline__ NoCtx tcol(int) const { return {}; }
-    __device__ __forceinline__ void tstore(const NoCtx&, const NoCtx&, f32x4) const {}
+    template <bool WT = false> __device__ __forceinline__ void tstore(const NoCtx&, const NoCtx&, f32x4) const {}
     // Staged form: the RAW accumulators are turned (two halves of 64 rows x 256 B); a lane then owns 4 columns of one row per step:
     // 16 lanes x 16 B = one 256-byte piece of a row of x, read and written whole.  The 16 residual loads of a half are requested
     // before the half is staged; the (at most two) batch rows a half touches have their gate vectors and lengths loaded once.
@@ -245,6 +267,9 @@ template <typename TO> struct EpiQKV {
     TO* q; TO* k; TO* vt; const float* bias; const float* rope;
     int Nseq, Npad, H, pe_heads; float q_scale;
     const int2* rowmap = nullptr;
+    // No write-through form: built (q / k rows regrouped to 16 bytes, V^T in 8-byte pieces) and measured at C2, it LOST 0.6 ms per step
+    // against plain stores: the transposed third cannot be regrouped and 8-byte sc1 stores cost more than they save.
+    static constexpr bool kWT = false, kRegroup16 = false;
     struct RowCtx { size_t base; const float* cs; };      // base = (b*H*Nseq + pos) * 64; cs = the position's 64 table floats; null: drop
     struct ColCtx { float4 b; TO* dst; size_t hoff; int d; bool rot; float scale; };
     struct TRowCtx { size_t base; int pos; int b; bool fast; int m; int M; };

@@ -391,6 +391,52 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
     // merge the "pending load" state across the exec-masked bounds checks around each store -- puts `s_waitcnt vmcnt(0)` in
     // front of EVERY store: each store then waits for the previous one's round trip (4-12 serialized stores per lane).
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) only
+    // Write-through stores (epi.wt, wave-uniform; f5_common.h "store policy"): the same bytes to the same addresses, in a copy of the
+    // store run of its own so that the plain one below stays what it was.  16-bit outputs: two neighbouring sub-tiles j, j + 1
+    // exchange 8-byte pieces between the four lane groups of a row (regroup_pair16) and a lane stores 16 contiguous bytes -- only where
+    // both sub-tiles lie wholly inside N and on one output (pair_ok); any other sub-tile keeps its 8-byte pieces.  Rows past M store
+    // nothing in either form.  Only the tiles a few-row launch is given carry the copy: the 256x128 tile of the many-row batches
+    // (which spilled with it) ignores epi.wt and stores as it always did.
+    if constexpr (Epi::kWT && BM * BN <= 128 * 192) {
+        if (epi.wt) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if (trj[j]) continue;
+                bool paired = false;
+                if constexpr (Epi::kRegroup16) {
+                    const int j0 = j & ~1;
+                    if (j0 + 1 < NJ && !trj[j0] && !trj[j0 + 1] && nw + (j0 + 2) * 16 <= N && epi.pair_ok(nw + j0 * 16, nw + j0 * 16 + 16)) {
+                        paired = true;
+                        if (j == j0) {
+                            auto* base = uniform_ptr(epi.dst_base(cc[j0]));   // one output for the pair: the store's resource descriptor
+#pragma unroll
+                            for (int i = 0; i < MI; ++i) {
+                                const u32x4 d = regroup_pair16(epi.pack(rc[i], cc[j0], acc[i][j0], pre[i][j0]),
+                                                               epi.pack(rc[i], cc[j0 + 1], acc[i][j0 + 1], pre[i][j0 + 1]));
+                                const size_t off = (g >> 1 ? epi.dst_off(rc[i], cc[j0 + 1]) : epi.dst_off(rc[i], cc[j0])) + (g & 1) * 8 - g * 4;
+                                if (mw + i * 16 + l15 < M && epi.keep(rc[i])) store16_wt(base, off * 2, d);
+                            }
+                        }
+                    }
+                }
+                if (paired || nw + j * 16 + g * 4 >= N) continue;
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+                    if (mw + i * 16 + l15 < M) epi.template store<true>(rc[i], cc[j], acc[i][j], pre[i][j]);
+            }
+            if (any_tr) {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    const int n = nw + j * 16 + l15;
+                    if (!trj[j] || n >= N) continue;
+#pragma unroll
+                    for (int i = 0; i < MI; ++i)
+                        if (mw + i * 16 + g * 4 < M) epi.template tstore<true>(trc[i], tcc[j], acc[i][j]);
+                }
+            }
+            return;
+        }
+    }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int n = nw + j * 16 + g * 4;

@@ -157,7 +157,7 @@ static int attn_body(const float* q, const float* k, const float* v, int Bp, int
             HIPCHK(launch_attention_v2<f16_t>(s, qd.p, kd.p, vd.p, nullptr, Bp, H, N, Npad, kl.p, p.nlens, ql.p, rs.p, static_cast<float*>(p.out)));
     } else {
         HIPCHK(launch_attention_any(s, qd.p, kd.p, vd.p, static_cast<T*>(p.out), Bp, H, N, Npad, kl.p, p.nlens, ql.p, rs.p, split16,
-                                    p.o_planar != 0, p.hi_only));
+                                    p.o_planar != 0, p.hi_only, store_policy() & F5_WT_ATTN));
         CHK(copy_f32<T>(s, p.out, p.out_f32, p.n_out));
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -278,7 +278,7 @@ static int layernorm_ex_impl(const float* x, const float* scale, const float* sh
     }
     TO* o = static_cast<TO*>(out);
     hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((R + 3) / 4), dim3(256), 0, s, x, D, o, D, R, D, eps, scale, shift, D, rows_per_batch,
-                       1, Prefetch{}, m_limit >= 0 ? ml.p : nullptr, planar == 1);
+                       1, Prefetch{}, m_limit >= 0 ? ml.p : nullptr, planar == 1, wt_fits(store_policy() & F5_WT_LN, (size_t)R * D * sizeof(TO)));
     KCHK();
     if constexpr (std::is_same_v<TO, float>) {   // planar 2: the plain rows, then split_planar_kernel (what planar 1 must equal)
         if (planar == 2) {
@@ -373,7 +373,8 @@ static int gemm_epi_impl(const float* A, const float* W, const float* bias, int 
         case F5K_EPI_STORE:
             if (p.out16) {
                 if constexpr (sizeof(T) == 2) {
-                    CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp, EpiStore<T>{static_cast<T*>(p.out0), N, bias, p.act}, p.cfg, ml.p, ops));
+                    CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp, EpiStore<T>{static_cast<T*>(p.out0), N, bias, p.act, 0, wt_fits(store_policy() & F5_WT_STORE16, (size_t)M * N * sizeof(T))},
+                                    p.cfg, ml.p, ops));
                     CHK(copy_f32<T>(s, p.out0, p.out0_f32, p.n0));
                 }
             } else {   // planar 2: the plain store, then split_planar_kernel over the whole output (what planar 1 must equal)
@@ -392,8 +393,9 @@ static int gemm_epi_impl(const float* A, const float* W, const float* bias, int 
                 HIPCHK(hipMemcpy(lens.p, p.lens_host, (size_t)p.nlens * 4, hipMemcpyHostToDevice));
             }
             CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp,
-                            EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p}, p.cfg,
-                            ml.p, ops));
+                            EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p,
+                                       wt_fits(store_policy() & F5_WT_GATE_RES, (size_t)M * N * 4)},
+                            p.cfg, ml.p, ops));
             break;
         default:   // QKV / QKNORM: the output type is the operand type, or f16 on f32 operands (the f16x3 attn16 path)
             if (p.out16) {
@@ -518,7 +520,7 @@ extern "C" int f5k_time_sinus(const float* t, const float* freq, float* feat, in
     return glue_done((hipStream_t)stream);
 }
 template <typename TO> static int xrmsnorm_impl(const float* x, void* out, int R, int D, const float* g, int planar, hipStream_t s) {
-    launch_xrmsnorm<TO>(s, x, static_cast<TO*>(out), R, D, g, planar);
+    launch_xrmsnorm<TO>(s, x, static_cast<TO*>(out), R, D, g, planar, store_policy() & F5_WT_LN);
     return glue_done(s);
 }
 // planar: pre-split rows exist for f32 rows of whole 32-element blocks only

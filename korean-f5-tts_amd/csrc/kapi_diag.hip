@@ -87,6 +87,7 @@ static int gemm2_impl(const float* A, const float* W, const float* bias, int act
 extern "C" int f5x_set_xcd_mode(int32_t on) { xcd_mode() = on; return 0; }
 extern "C" int f5x_set_attn_variant(int32_t v) { attn2_variant() = v; return 0; }
 extern "C" int f5x_set_cold_weights(int32_t on) { g_cold_weights = on; return 0; }
+extern "C" int f5x_set_store_policy(int32_t mask) { store_policy() = mask & F5_WT_ALL; return 0; }
 extern "C" int f5x_set_out_bf16(int32_t on) { g_out_bf16 = on; return 0; }
 extern "C" int f5x_gemm2(int32_t prec, const float* A, const float* W, const float* bias, int32_t act, float* out, int32_t M,
                          int32_t N, int32_t K, int32_t cfg, int32_t iters, float* avg_us, f5_stream stream) {
@@ -365,6 +366,57 @@ extern "C" int f5x_mfma_rate_probe(int32_t blocks, int32_t threads, int32_t iter
 //   mode 1: bf16, row-major -- per instruction 8 rows x 128 contiguous bytes (what an LDS-transposed epilogue would do)
 //   mode 2: f32, fragment order -- 16 rows x 64 bytes (EpiGateRes: also READS the same pattern when `rd`)
 //   mode 3: f32, row-major -- 4 rows x 256 bytes
+// and, with a store POLICY (0 plain, 1 write-through = sc1, 2 nt) and a wave tile of `mi` x 16 rows (block tile 32 mi x 256: mi = 2
+// gives the 2,048-row outputs of C2 128-384 workgroups, as the product's tiles do), the per-lane widths of the few-row epilogues:
+//   mode 0: 16-bit fragment order, 8 B per lane, 32-byte pieces       mode 4: the same regrouped to 16 B per lane, 64-byte pieces
+//   mode 2: f32 fragment order, 16 B per lane
+//   mode 5: LayerNorm's row order (one wave per row, lane -> columns 4 lane + 256 i), 8 B per lane      mode 6: the same at 16 B per lane
+// Back-to-back launches: the write-back of what a launch leaves dirty in L2 is inside the per-launch time.
+template <int POL> __device__ __forceinline__ void probe_st8(void* base, size_t off, u32x2 v) {
+    char* p = reinterpret_cast<char*>(base) + off;
+    if constexpr (POL == 1) store8_wt(p, v);
+    else if constexpr (POL == 2) __builtin_nontemporal_store(v, reinterpret_cast<u32x2*>(p));
+    else *reinterpret_cast<u32x2*>(p) = v;
+}
+template <int POL> __device__ __forceinline__ void probe_st16(void* base, size_t off, u32x4 v) {
+    char* p = reinterpret_cast<char*>(base) + off;
+    if constexpr (POL == 1) store16_wt(base, off, v);
+    else if constexpr (POL == 2) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(p));
+    else *reinterpret_cast<u32x4*>(p) = v;
+}
+template <int POL>
+__global__ __launch_bounds__(512) void store_policy_kernel(void* out, int ld, int mode, int mi, int M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 2, wc = wave & 3;
+    const int l15 = lane & 15, g = lane >> 4;
+    if (mode >= 5) {   // one wave per 16-bit row of ld columns
+        const size_t r = (size_t)blockIdx.x * 8 + wave;
+        if (r >= (size_t)M) return;
+        if (mode == 5) {
+            for (int i = 0; i * 256 < ld; ++i) probe_st8<POL>(out, (r * ld + lane * 4 + i * 256) * 2, u32x2{0x3c003c00u + i, 0x3c003c00u});
+        } else {   // even lanes: chunk i, odd lanes: chunk i + 1, 8 columns each
+            for (int i = 0; i * 256 < ld; i += 2)
+                probe_st16<POL>(out, (r * ld + (i + (lane & 1)) * 256 + (lane >> 1) * 8) * 2, u32x4{0x3c003c00u + i, 0x3c003c00u, 1u, 2u});
+        }
+        return;
+    }
+    const size_t m0 = (size_t)blockIdx.y * 32 * mi + wr * 16 * mi, n0 = (size_t)blockIdx.x * 256 + wc * 64;
+    if (mode == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < mi; ++i)
+                probe_st8<POL>(out, ((m0 + i * 16 + l15) * ld + n0 + j * 16 + g * 4) * 2, u32x2{0x3c003c00u + i, 0x3c003c00u + j});
+    } else if (mode == 4) {
+#pragma unroll
+        for (int j = 0; j < 4; j += 2)
+            for (int i = 0; i < mi; ++i)
+                probe_st16<POL>(out, ((m0 + i * 16 + l15) * ld + n0 + j * 16 + g * 8) * 2, u32x4{0x3c003c00u + i, 0x3c003c00u + j, 1u, 2u});
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            for (int i = 0; i < mi; ++i)
+                probe_st16<POL>(out, ((m0 + i * 16 + l15) * ld + n0 + j * 16 + g * 4) * 4, u32x4{0x3f800000u + i, 0x40000000u + j, 1u, 2u});
+    }
+}
 __global__ __launch_bounds__(512) void store_pattern_kernel(void* out, int ld, int mode, int rd) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wr = wave >> 2, wc = wave & 3;
     const int l15 = lane & 15, g = lane >> 4;
@@ -403,8 +455,15 @@ __global__ __launch_bounds__(512) void store_pattern_kernel(void* out, int ld, i
         }
     }
 }
-extern "C" int f5x_store_pattern_probe(int32_t M, int32_t N, int32_t mode, int32_t rd, int32_t iters, float* avg_us, f5_stream stream) {
-    if (M % 256 || N % 256 || mode < 0 || mode > 3 || iters <= 0 || !avg_us) return fail(F5_EINVAL, "f5x_store_pattern_probe: bad arguments");
+// mi == 0: the many-row probe (256 x 256 tiles, modes 0-3, plain stores); mi > 0: store_policy_kernel (modes 0, 2, 4, 5, 6; policy 0 / 1 / 2)
+extern "C" int f5x_store_pattern_probe(int32_t M, int32_t N, int32_t mode, int32_t rd, int32_t policy, int32_t mi, int32_t iters, float* avg_us,
+                                       f5_stream stream) {
+    const bool pol = mi > 0;
+    if (M <= 0 || N <= 0 || N % 256 || iters <= 0 || !avg_us || (size_t)M * N * 4 >= F5_WT_MAX_BYTES ||
+        (!pol && (M % 256 || mode < 0 || mode > 3 || policy != 0)) ||
+        (pol && (mi > 8 || M % (32 * mi) || policy < 0 || policy > 2 || rd || !(mode == 0 || mode == 2 || (mode >= 4 && mode <= 6)) ||
+                 (mode == 6 && N % 512))))
+        return fail(F5_EINVAL, "f5x_store_pattern_probe: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     Scratch<float> buf;
     HIPCHK(buf.alloc((size_t)M * N));
@@ -412,9 +471,16 @@ extern "C" int f5x_store_pattern_probe(int32_t M, int32_t N, int32_t mode, int32
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(store_pattern_kernel, dim3(N / 256, M / 256), dim3(512), 0, s, buf.p, N, mode, rd);
+    auto launch = [&]() {
+        if (!pol) { hipLaunchKernelGGL(store_pattern_kernel, dim3(N / 256, M / 256), dim3(512), 0, s, buf.p, N, mode, rd); return; }
+        const dim3 grid = mode >= 5 ? dim3((M + 7) / 8) : dim3(N / 256, M / (32 * mi));
+        if (policy == 0) hipLaunchKernelGGL(store_policy_kernel<0>, grid, dim3(512), 0, s, buf.p, N, mode, mi, M);
+        else if (policy == 1) hipLaunchKernelGGL(store_policy_kernel<1>, grid, dim3(512), 0, s, buf.p, N, mode, mi, M);
+        else hipLaunchKernelGGL(store_policy_kernel<2>, grid, dim3(512), 0, s, buf.p, N, mode, mi, M);
+    };
+    for (int i = 0; i < 2; ++i) launch();
     HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(store_pattern_kernel, dim3(N / 256, M / 256), dim3(512), 0, s, buf.p, N, mode, rd);
+    for (int i = 0; i < iters; ++i) launch();
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
     KCHK();
