@@ -147,6 +147,25 @@ int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const ui
                   const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
                   const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream, int32_t method);
 
+/* f5_sample_ode with per-item sampler settings: every utterance of one ragged batch has its own time grid, step count and guidance.
+ *   t_items HOST f32[B][steps_max + 1]: item b integrates over t_items[b][0 .. steps_items[b]]; later entries are ignored.
+ *   steps_items HOST int32[B], each in [1, steps_max], the largest equal to steps_max.  cfg_items HOST f32[B].
+ *   method: F5_ODE_EULER or F5_ODE_MIDPOINT, for the whole batch.  The other arguments are f5_sample_ode's.
+ * The batch runs steps_max steps.  For i >= steps_items[b] item b's state is not touched -- the update is skipped, not multiplied by a
+ * zero dt -- and trajectory slot i + 1 receives the item's final state: traj f32[steps_max + 1, B, N, mel] or NULL.
+ * An item with cfg_items[b] < 1e-5f takes v = p, as cfm.py:167-178 does, for that item alone; if every item is below 1e-5f the
+ * backbone runs the conditional half only, as f5_sample_ode does.
+ * The values travel in device tables, so a captured graph is keyed on the shape (B, N, nt, steps_max, the number of distinct evaluation
+ * times, halves, lens, traj, chunking, method) and serves every guidance and every grid of that shape.  The body is the rectangular one:
+ * no RowPack (an attn_mask_enabled engine runs the masked padded form of F5_PACK_ROWS=0), no length bucket, no F5_SPLIT_CFG chains.
+ * A uniform call computes, bit for bit, what f5_sample_ode computes on its rectangular body.
+ * F5_EINVAL, with a message naming the item: a non-finite t or cfg, steps_items[b] outside [1, steps_max], max(steps_items) != steps_max;
+ * and f5_sample_ode's own rules (lens required when B > 1, lens in (0, N], an unknown method). */
+int f5_sample_items(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                    const int64_t* text, int32_t nt, const float* t_items, const int32_t* steps_items, int32_t steps_max,
+                    const float* cfg_items, const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream,
+                    int32_t method);
+
 /* Pre-sizes the activation arena (otherwise it grows on first use, which calls hipMalloc inside f5_sample).  The plan for
  * max_steps covers both solvers: a midpoint call with steps <= max_steps needs no regrowth. */
 int f5_reserve(f5_engine* e, int32_t max_batch, int32_t max_frames, int32_t max_steps);
@@ -715,6 +734,22 @@ int f5k_euler_cfg(float* y, const float* pred, int32_t B, int32_t N, int32_t mel
                   const float* tgrid, int32_t step, float cfg, int32_t use_cfg, float* traj_slot, f5_stream stream);
 int f5k_midpoint_half_cfg(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start,
                           const int32_t* lens, const float* tgrid, int32_t step, float cfg, int32_t use_cfg, float* y_mid, f5_stream stream);
+/* The updates of f5_sample_items: pred f32[(use_cfg ? 2 : 1), B, N, mel]; t_items f32[B, steps_max + 1], cfg_items f32[B], steps_items
+ * int[B] on the device.  Item b with step < steps_items[b]: dt from its own grid, v = p + (p - u) * cfg_items[b] (use_cfg and
+ * cfg_items[b] >= 1e-5) or p; else y is not touched (traj_slot / y_mid receive it). */
+int f5k_euler_cfg_items(float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items, const float* cfg_items,
+                        const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg, float* traj_slot, f5_stream stream);
+int f5k_midpoint_half_cfg_items(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items,
+                                const float* cfg_items, const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg,
+                                float* y_mid, f5_stream stream);
+/* dst f32[rows, width] = src[idx[r % nidx], :]; idx int[nidx] (device), width % 4 == 0.  The caller keeps idx inside src. */
+int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, int32_t rows, int32_t nidx, int32_t width, f5_stream stream);
+/* The time rows of an f5_sample_items call (host arithmetic, no device needed): the evaluation times of every live item -- Euler t[b][i];
+ * midpoint t[b][i] and t[b][i] + 0.5f * (t[b][i+1] - t[b][i]) -- walked evaluation-major, then item-major, deduplicated by f32 bit pattern
+ * in first-appearance order.  times_out f32[evals * steps_max * B] (the first *U are written), idx_out int32[evals * steps_max][B]: the
+ * row of every (evaluation, item), 0 for a finished item.  The table rules of f5_sample_items apply. */
+int f5k_item_time_rows(const float* t_items, const int32_t* steps_items, int32_t steps_max, int32_t B, int32_t method, float* times_out,
+                       int32_t* idx_out, int32_t* U);
 /* out f32[rows, C] = rowmask[r] ? a[r] : (b ? b[r] : 0); rowmask uint8[rows]; out may be b */
 int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream);
 /* feat f32[S, 256] = [sin | cos] of (1000 t[s]) * freq[j]; t f32[S], freq f32[128] */
@@ -731,12 +766,13 @@ int f5k_strip_first_token(const float* in, float* out, int32_t Bp, int32_t N, in
 /* The work-buffer plan of an engine of config c, as pure host arithmetic (no HIP call, nothing launched, no device needed): the engine's
  * own carve for the reservation (B, N, S) and its own placement of the side chain of a split-CFG (F5_SPLIT_CFG=1) call of
  * call_B <= B utterances of call_N <= N frames, both on a dry-run arena.  *total_bytes: the arena size.  main_off / side_off
- * int64[F5K_WORK_BUFFERS]: byte offset of each buffer in the order of F5K_WORK_NAMES, -1 where the config has no such buffer;
+ * int64[F5K_WORK_BUFFERS]: byte offset of each buffer in the order of F5K_WORK_NAMES, -1 where the config has no such buffer (and for the buffers of f5_sample_items, which
+ * an engine carves only once such a call has been made);
  * side_off equals main_off for a buffer both chains share. */
-#define F5K_WORK_BUFFERS 39
+#define F5K_WORK_BUFFERS 44
 #define F5K_WORK_NAMES                                                                                                              \
     "tdev feat th temb st mod lens lens_plain row_start rowmap step_cond text_c text_u tx_a tx_b tx_h1 grn_part uc acat h c1 x pred " \
-    "xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all"
+    "xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps it_idx"
 int f5k_work_plan(const f5_config* c, int32_t B, int32_t N, int32_t S, int32_t call_B, int32_t call_N, int64_t* total_bytes,
                   int64_t* main_off, int64_t* side_off);
 /* repeated-launch timing of one GEMM shape (for bench/roofline): returns average microseconds per launch */

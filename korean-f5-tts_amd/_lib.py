@@ -54,7 +54,8 @@ _f = C.c_float
 F5K_EPI_STORE, F5K_EPI_GATE_RES, F5K_EPI_QKV, F5K_EPI_QKNORM = 0, 1, 2, 3
 # the buffers of f5k_work_plan, in its order (F5K_WORK_NAMES of include/f5_hip.h)
 F5K_WORK_NAMES = ("tdev feat th temb st mod lens lens_plain row_start rowmap step_cond text_c text_u tx_a tx_b tx_h1 grn_part uc acat h c1 x "
-                  "pred xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all").split()
+                  "pred xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps "
+                  "it_idx").split()
 
 
 class f5k_epi(C.Structure):
@@ -92,6 +93,8 @@ SIGNATURES = {
     "f5_dit_forward": (_i, [_p, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), _i, _i, _i, _i, _i, _p, _p]),
     "f5_sample": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p]),
     "f5_sample_ode": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
+    "f5_sample_items": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), _i, C.POINTER(_f), C.POINTER(_i), _i, _i, _p, _p,
+                             _p, _i]),
     "f5_reserve": (_i, [_p, _i, _i, _i]),
     "f5_set_length_buckets": (_i, [_p, _i]),
     "f5_prepare_sample": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
@@ -159,6 +162,10 @@ SIGNATURES = {
     "f5k_fill_rowmap": (_i, [_p, _p, _i, _p]),
     "f5k_euler_cfg": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _i, _p, _p]),
     "f5k_midpoint_half_cfg": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _i, _p, _p]),
+    "f5k_euler_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "f5k_midpoint_half_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "f5k_mod_gather": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "f5k_item_time_rows": (_i, [C.POINTER(_f), C.POINTER(_i), _i, _i, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     "f5k_select_rows": (_i, [_p, _p, _p, _p, C.c_int64, _i, _p]),
     "f5k_time_sinus": (_i, [_p, _p, _p, _i, _p]),
     "f5k_xrmsnorm": (_i, [_i, _p, _p, _i, _i, _p, _i, _p]),

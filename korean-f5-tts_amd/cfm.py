@@ -25,6 +25,46 @@ def clamp_durations(text: torch.Tensor, lens: torch.Tensor, duration, max_durati
     return duration.clamp(max=max_duration)
 
 
+def per_item(name: str, value, batch: int) -> list:
+    """A sampler setting as a list of `batch` entries: a scalar (or None) is every item's value, a sequence is one value per item."""
+    if isinstance(value, (list, tuple)) or (isinstance(value, torch.Tensor) and value.ndim > 0):
+        vals = [v.item() if isinstance(v, torch.Tensor) else v for v in value]
+        if len(vals) != batch:
+            raise ValueError(f"sample_items: {name} has {len(vals)} entries for a batch of {batch}")
+        return vals
+    return [value.item() if isinstance(value, torch.Tensor) else value] * batch
+
+
+def is_per_item(*values) -> bool:
+    """Whether any of the sampler settings is given per item (a sequence) rather than once for the batch."""
+    return any(isinstance(v, (list, tuple)) or (isinstance(v, torch.Tensor) and v.ndim > 0) for v in values)
+
+
+def item_time_grids(steps: list, sway: list, use_epss=True) -> list[torch.Tensor]:
+    """One time grid per item: sample()'s own host arithmetic (cfm.py:211-216) with the item's step count and sway coefficient."""
+    grids = []
+    for n, sw in zip(steps, sway):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"sample_items: steps must be at least 1 (got {n})")
+        t = get_epss_timesteps(n, device="cpu", dtype=torch.float32) if use_epss else torch.linspace(0, 1, n + 1, dtype=torch.float32)
+        if sw is not None:
+            t = t + sw * (torch.cos(torch.pi / 2 * t) - 1 + t)
+        grids.append(t)
+    return grids
+
+
+def item_noise(durations: list, seeds: list, mel: int, device="cpu") -> torch.Tensor:
+    """y0 of a batch whose items carry their own seeds (cfm.py:196-201 per item): drawn in item order, each at its own length after
+    `manual_seed(seed)` when it has one, zero padded."""
+    y0 = []
+    for dur, seed in zip(durations, seeds):
+        if exists(seed):
+            torch.manual_seed(int(seed))
+        y0.append(torch.randn(int(dur), mel, device=device, dtype=torch.float32))
+    return pad_sequence(y0, padding_value=0, batch_first=True)
+
+
 class CFM(nn.Module):
     def __init__(self, transformer: nn.Module, sigma=0.0, odeint_kwargs: dict = dict(method="euler"),
                  audio_drop_prob=0.3, cond_drop_prob=0.2, num_channels=None, mel_spec_module: nn.Module | None = None,
@@ -122,6 +162,52 @@ class CFM(nn.Module):
         out, trajectory = eng.sample(None if no_ref_audio else cond, cond_mask, y0, text_cpu, t.tolist(), cfg_strength,
                                      lens=duration.tolist() if batch > 1 else None, want_traj=True,
                                      method=self.odeint_kwargs.get("method", "euler"))
+        self.transformer.clear_cache()
+        if exists(vocoder):
+            out = vocoder(out.permute(0, 2, 1))
+        return out, trajectory
+
+    @torch.no_grad()
+    def sample_items(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None,
+                     use_epss=True, max_duration=65536, vocoder=None, no_ref_audio=False, edit_mask=None):
+        """sample() with per-item settings: `steps`, `cfg_strength`, `sway_sampling_coef` and `seed` each take one value for the batch or
+        a sequence of one value per item (entries of the last two may be None).  One engine call (f5_sample_items) runs the batch for
+        max(steps) steps; an item with fewer steps keeps its final state from then on.  Returns (out, trajectory[max(steps) + 1, B, N, mel])."""
+        self.eval()
+        device = self.device
+        if cond.ndim == 2:
+            cond = self.mel_spec(cond.to(device))
+            cond = cond.permute(0, 2, 1)
+            assert cond.shape[-1] == self.num_channels
+        cond = cond.to(device=device, dtype=torch.float32)
+        batch, cond_seq_len = cond.shape[:2]
+        steps_i = [int(v) for v in per_item("steps", steps, batch)]
+        cfg_i = [float(v) for v in per_item("cfg_strength", cfg_strength, batch)]
+        sway_i = per_item("sway_sampling_coef", sway_sampling_coef, batch)
+        seed_i = per_item("seed", seed, batch)
+        if not exists(lens):
+            lens = torch.full((batch,), cond_seq_len, dtype=torch.long)
+        lens = lens.to("cpu", torch.long)
+
+        if isinstance(text, list):
+            text = list_str_to_idx(text, self.vocab_char_map) if exists(self.vocab_char_map) else list_str_to_tensor(text)
+            assert text.shape[0] == batch
+        text_cpu = text.to("cpu", torch.long)
+
+        cond_mask = lens_to_mask(lens)
+        if edit_mask is not None:
+            cond_mask = cond_mask & edit_mask.to("cpu")
+        duration = clamp_durations(text_cpu, lens, duration, max_duration)
+        N = int(duration.amax())
+        cond_mask = F.pad(cond_mask, (0, N - cond_mask.shape[-1]), value=False)
+
+        y0 = item_noise(duration.tolist(), seed_i, self.num_channels, self.noise_device if self.noise_device == "cpu" else device)
+        grids = item_time_grids(steps_i, sway_i, use_epss)
+
+        eng = self.transformer.engine()
+        out, trajectory = eng.sample_items(None if no_ref_audio else cond, cond_mask, y0, text_cpu, [t.tolist() for t in grids], cfg_i,
+                                           lens=duration.tolist() if batch > 1 else None, want_traj=True,
+                                           method=self.odeint_kwargs.get("method", "euler"))
         self.transformer.clear_cache()
         if exists(vocoder):
             out = vocoder(out.permute(0, 2, 1))

@@ -388,6 +388,89 @@ inline void launch_midpoint_half_cfg(hipStream_t s, const float* y, const float*
         hipLaunchKernelGGL(midpoint_half_cfg_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, s, y, pred, n, tgrid, step, cfg, use_cfg, y_mid);
 }
 
+// ------------------------------------------------------------------------------------- per-item sampler settings
+// f5_sample_items: every utterance b of the (rectangular) batch has its own grid t_items[b * (steps_max + 1) + 0 .. steps[b]], its own
+// guidance cfg_items[b] and its own step count.  The two updates above with b = frame / N; an utterance that has finished
+// (step >= steps[b]) is not touched -- no multiplication by a zero dt -- and the trajectory slot receives its final state.
+// An utterance with cfg_items[b] < 1e-5 takes v = p (cfm.py:167-178) although the batch ran both halves.
+static __global__ void euler_cfg_items_kernel(float* __restrict__ y, const float* __restrict__ pred, int B, int N, int mel,
+                                              const float* __restrict__ t_items, const float* __restrict__ cfg_items,
+                                              const int* __restrict__ steps_items, int steps_max, int step, int use_cfg,
+                                              float* __restrict__ traj_slot) {
+    const int c4n = mel / 4;
+    const long total = (long)B * N * c4n, half_elems = (long)B * N * mel;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / c4n / N);
+        float4 yy = reinterpret_cast<float4*>(y)[i];
+        if (step < steps_items[b]) {
+            const float* tg = t_items + (size_t)b * (steps_max + 1);
+            const float dt = tg[step + 1] - tg[step];
+            const float cfg = cfg_items[b];
+            const float4 p = reinterpret_cast<const float4*>(pred)[i];
+            float4 v = p;
+            if (use_cfg && !(cfg < 1e-5f)) {
+                const float4 u = reinterpret_cast<const float4*>(pred + half_elems)[i];
+                v.x = p.x + (p.x - u.x) * cfg; v.y = p.y + (p.y - u.y) * cfg;
+                v.z = p.z + (p.z - u.z) * cfg; v.w = p.w + (p.w - u.w) * cfg;
+            }
+            yy.x += dt * v.x; yy.y += dt * v.y; yy.z += dt * v.z; yy.w += dt * v.w;
+            reinterpret_cast<float4*>(y)[i] = yy;
+        }
+        if (traj_slot) reinterpret_cast<float4*>(traj_slot)[i] = yy;
+    }
+}
+// ... and the midpoint half step; a finished utterance gets y_mid = y (nothing reads it)
+static __global__ void midpoint_half_cfg_items_kernel(const float* __restrict__ y, const float* __restrict__ pred, int B, int N, int mel,
+                                                      const float* __restrict__ t_items, const float* __restrict__ cfg_items,
+                                                      const int* __restrict__ steps_items, int steps_max, int step, int use_cfg,
+                                                      float* __restrict__ y_mid) {
+    const int c4n = mel / 4;
+    const long total = (long)B * N * c4n, half_elems = (long)B * N * mel;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / c4n / N);
+        float4 yy = reinterpret_cast<const float4*>(y)[i];
+        if (step < steps_items[b]) {
+            const float* tg = t_items + (size_t)b * (steps_max + 1);
+            const float hdt = 0.5f * (tg[step + 1] - tg[step]);
+            const float cfg = cfg_items[b];
+            const float4 p = reinterpret_cast<const float4*>(pred)[i];
+            float4 v = p;
+            if (use_cfg && !(cfg < 1e-5f)) {
+                const float4 u = reinterpret_cast<const float4*>(pred + half_elems)[i];
+                v.x = p.x + (p.x - u.x) * cfg; v.y = p.y + (p.y - u.y) * cfg;
+                v.z = p.z + (p.z - u.z) * cfg; v.w = p.w + (p.w - u.w) * cfg;
+            }
+            yy.x += v.x * hdt; yy.y += v.y * hdt; yy.z += v.z * hdt; yy.w += v.w * hdt;
+        }
+        reinterpret_cast<float4*>(y_mid)[i] = yy;
+    }
+}
+// The tables of a chunk of B utterances start at the chunk's first utterance (t_items, cfg_items, steps_items already offset).
+inline void launch_euler_cfg_items(hipStream_t s, float* y, const float* pred, int B, int N, int mel, const float* t_items,
+                                   const float* cfg_items, const int* steps_items, int steps_max, int step, int use_cfg, float* traj_slot) {
+    hipLaunchKernelGGL(euler_cfg_items_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, pred, B, N, mel, t_items, cfg_items,
+                       steps_items, steps_max, step, use_cfg, traj_slot);
+}
+inline void launch_midpoint_half_cfg_items(hipStream_t s, const float* y, const float* pred, int B, int N, int mel, const float* t_items,
+                                           const float* cfg_items, const int* steps_items, int steps_max, int step, int use_cfg, float* y_mid) {
+    hipLaunchKernelGGL(midpoint_half_cfg_items_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, pred, B, N, mel, t_items,
+                       cfg_items, steps_items, steps_max, step, use_cfg, y_mid);
+}
+// dst[r, :] = src[idx[r % nidx], :] for r < rows: the time rows (AdaLN vectors, or the UNetT's time embedding) of one evaluation, one per
+// batch row of a chunk -- nidx utterances, the conditional half and then (rows = 2 nidx) the unconditional half.  width % 4 == 0.
+static __global__ void mod_gather_kernel(const float* __restrict__ src, const int* __restrict__ idx, float* __restrict__ dst, int rows,
+                                         int nidx, int width) {
+    const int w4 = width / 4;
+    const long total = (long)rows * w4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / w4), c = (int)(i % w4);
+        reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src + (size_t)idx[r % nidx] * width)[c];
+    }
+}
+inline void launch_mod_gather(hipStream_t s, const float* src, const int* idx, float* dst, int rows, int nidx, int width) {
+    hipLaunchKernelGGL(mod_gather_kernel, dim3(ew_blocks((long)rows * width / 4)), dim3(256), 0, s, src, idx, dst, rows, nidx, width);
+}
+
 // rowmap[row_start[b'] + n] = (b', n) for n < row_start[b' + 1] - row_start[b']   (one block per batch row)
 static __global__ void fill_rowmap_kernel(const int* __restrict__ row_start, int2* __restrict__ rowmap) {
     const int bp = blockIdx.x, r0 = row_start[bp], cnt = row_start[bp + 1] - r0;

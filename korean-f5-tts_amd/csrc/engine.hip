@@ -219,8 +219,9 @@ static int chunk_utts(const f5_engine* e, int B, int N, bool use_cfg, const int3
     return (int)((B + best_k - 1) / best_k);
 }
 SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk, int nt, int steps, int method,
-                       float cfg_strength, bool want_traj, int n_true) {
+                       float cfg_strength, bool want_traj, int n_true, bool items) {
     SamplePlan p;
+    p.items = items;
     // a length-bucket plan: every utterance has n_true frames; the chunking follows the bucket's ceiling alone (it is part of the key)
     const std::vector<int32_t> own(n_true > 0 ? B : 0, n_true), cap(n_true > 0 ? B : 0, N);
     if (n_true > 0) lens_host = own.data();
@@ -232,8 +233,9 @@ SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_hos
     p.halves = p.use_cfg ? 2 : 1;
     p.evals = method == F5_ODE_MIDPOINT ? 2 : 1;
     const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;
-    p.pack = n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg);
-    p.split = e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
+    // (a per-item call runs the rectangular body on one stream chain: batch row = row / N is what finds a row's time vectors)
+    p.pack = !items && (n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg));
+    p.split = !items && e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
     p.chunk = chunk ? chunk : chunk_utts(e, B, N, p.use_cfg, n_true > 0 ? cap.data() : p.pack ? lens_host : nullptr);
     for (int u0 = 0; u0 < B; u0 += p.chunk) {
         SamplePlan::Chunk k{(int)p.chunks.size(), u0, std::min(p.chunk, B - u0), 0, 0};
@@ -250,6 +252,12 @@ std::string graph_key(const SamplePlan& p) {
     unsigned cfg_bits;
     memcpy(&cfg_bits, &p.cfg_strength, 4);
     char kb[160];
+    // a per-item plan: guidance and grids live in device tables, so neither is part of the key -- one graph serves every setting of a shape
+    if (p.items) {
+        snprintf(kb, sizeof(kb), "I%d|%d|%d|%d|U%d|h%d|%d|%d|%d|m%d", p.B, p.N, p.nt, p.steps, p.U, p.halves, p.has_lens ? 1 : 0,
+                 p.want_traj ? 1 : 0, p.chunk, p.method);
+        return kb;
+    }
     // a length-bucket plan: the bucket's ceiling stands for N, and neither the call's own length nor its text length is part of the key
     if (p.n_true > 0) snprintf(kb, sizeof(kb), "L%d|%d|%d|%08x|%d|%d|m%d", p.B, p.N, p.steps, cfg_bits, p.want_traj ? 1 : 0, p.chunk, p.method);
     else
@@ -268,6 +276,61 @@ std::vector<float> time_table(const float* t_host, int steps, int method) {
     }
     tt.insert(tt.end(), t_host, t_host + steps + 1);
     return tt;
+}
+ItemTimeRows item_time_rows(const float* t_items, const int32_t* steps_items, int steps_max, int B, int method) {
+    const int evals = method == F5_ODE_MIDPOINT ? 2 : 1;
+    ItemTimeRows r;
+    r.idx.assign((size_t)evals * steps_max * B, 0);
+    std::map<uint32_t, int> seen;   // f32 bit pattern -> row
+    for (int ev = 0; ev < evals * steps_max; ++ev)
+        for (int b = 0; b < B; ++b) {
+            const int i = ev / evals;
+            if (i >= steps_items[b]) continue;
+            const float* t = t_items + (size_t)b * (steps_max + 1);
+            float v = t[i];
+            if (ev % evals) {
+                const float hdt = 0.5f * (t[i + 1] - t[i]);   // f32, in time_table's order
+                v = t[i] + hdt;
+            }
+            uint32_t bits;
+            memcpy(&bits, &v, 4);
+            auto it = seen.find(bits);
+            if (it == seen.end()) {
+                it = seen.emplace(bits, (int)r.times.size()).first;
+                r.times.push_back(v);
+            }
+            r.idx[(size_t)ev * B + b] = it->second;
+        }
+    return r;
+}
+// the argument rules of the per-item tables (f5_sample_items, f5k_item_time_rows); messages name the item
+static int check_items(const char* who, const float* t_items, const int32_t* steps_items, int steps_max, const float* cfg_items, int B,
+                       int method) {
+    if (method != F5_ODE_EULER && method != F5_ODE_MIDPOINT)
+        return fail(F5_EINVAL, "%s: unknown ODE method %d (F5_ODE_EULER = 0, F5_ODE_MIDPOINT = 1)", who, method);
+    if (!t_items || !steps_items || B <= 0 || steps_max <= 0) return fail(F5_EINVAL, "%s: bad arguments", who);
+    int mx = 0;
+    for (int b = 0; b < B; ++b) {
+        if (steps_items[b] < 1 || steps_items[b] > steps_max)
+            return fail(F5_EINVAL, "%s: item %d: steps_items = %d outside [1, steps_max = %d]", who, b, steps_items[b], steps_max);
+        mx = std::max(mx, steps_items[b]);
+        for (int i = 0; i <= steps_items[b]; ++i)
+            if (!std::isfinite(t_items[(size_t)b * (steps_max + 1) + i]))
+                return fail(F5_EINVAL, "%s: item %d: t_items[%d] is not finite", who, b, i);
+        if (cfg_items && !std::isfinite(cfg_items[b])) return fail(F5_EINVAL, "%s: item %d: cfg_items is not finite", who, b);
+    }
+    if (mx != steps_max) return fail(F5_EINVAL, "%s: the largest steps_items is %d, not steps_max = %d", who, mx, steps_max);
+    return F5_OK;
+}
+extern "C" int f5k_item_time_rows(const float* t_items, const int32_t* steps_items, int32_t steps_max, int32_t B, int32_t method,
+                                  float* times_out, int32_t* idx_out, int32_t* U) {
+    if (!times_out || !idx_out || !U) return fail(F5_EINVAL, "f5k_item_time_rows: bad arguments");
+    CHK(check_items("f5k_item_time_rows", t_items, steps_items, steps_max, nullptr, B, method));
+    const ItemTimeRows r = item_time_rows(t_items, steps_items, steps_max, B, method);
+    std::copy(r.times.begin(), r.times.end(), times_out);
+    std::copy(r.idx.begin(), r.idx.end(), idx_out);
+    *U = (int32_t)r.times.size();
+    return F5_OK;
 }
 static int check_ready(f5_engine* e, int B, int N) {
     if (!e) return fail(F5_EINVAL, "null engine");
@@ -315,6 +378,28 @@ extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, c
                          const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream) {
     return f5_sample_ode(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj,
                          stream, F5_ODE_EULER);
+}
+extern "C" int f5_sample_items(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                               const int64_t* text, int32_t nt, const float* t_items, const int32_t* steps_items, int32_t steps_max,
+                               const float* cfg_items, const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj,
+                               f5_stream stream, int32_t method) {
+    // (the table rules first: they need no engine state)
+    if (!cfg_items) return fail(F5_EINVAL, "f5_sample_items: bad arguments");
+    CHK(check_items("f5_sample_items", t_items, steps_items, steps_max, cfg_items, B, method));
+    CHK(check_ready(e, B, N));
+    if ((!cond && cond_frames > 0) || !cond_mask || !y0 || !text || !out || nt <= 0 || cond_frames < 0 || cond_frames > N)
+        return fail(F5_EINVAL, "f5_sample_items: bad arguments");
+    if (B > 1 && !lens_host) return fail(F5_EINVAL, "f5_sample_items: lens required when B > 1 (cfm.py:155-158)");
+    if (lens_host)
+        for (int i = 0; i < B; ++i)
+            if (lens_host[i] <= 0 || lens_host[i] > N) return fail(F5_EINVAL, "f5_sample_items: lens[%d]=%d out of (0, N]", i, lens_host[i]);
+    bool any_cfg = false;
+    for (int b = 0; b < B; ++b) any_cfg = any_cfg || !(cfg_items[b] < 1e-5f);
+    const ItemTimeRows rows = item_time_rows(t_items, steps_items, steps_max, B, method);
+    const ItemTables it{t_items, cfg_items, steps_items, &rows};
+    e->prof.clear();
+    return F5_OPS(e, sample_items(e, cond, cond_frames, cond_mask, y0, text, nt, it, steps_max, any_cfg, lens_host, B, N, out, traj,
+                                  (hipStream_t)stream, method));
 }
 
 // ------------------------------------------------------------------------------------- length buckets

@@ -311,7 +311,8 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     const size_t rows = Bp * Nt;
     // time rows: one per backbone evaluation -- S (Euler) or 2 S (midpoint) in sample(), Bp in forward() -- and behind the
     // evaluation times in tdev the grid t[0..S] (sample_body: the dt of every step)
-    const size_t SS = (size_t)std::max(2 * S + 1, (int)Bp + 1);
+    // (a per-item call has one row per DISTINCT evaluation time of the batch: f5_engine::res_U)
+    const size_t SS = (size_t)std::max(std::max(2 * S + 1, (int)Bp + 1), e->res_U);
     w.Npad = round_up((int)Nt, 64);
     w.tdev = a.take<float>(SS + (size_t)S + 1);
     w.feat = a.take<float>(SS * 256);
@@ -357,6 +358,16 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
         w.cat2 = a.take<T>(rows * 2 * D);
         w.skips = a.take<float>(rows * D * (c.depth / 2));
         w.pred_all = a.take<float>(rows * mel);
+    }
+    // f5_sample_items: behind everything else, and only once a per-item call has asked (an engine that never does keeps its arena)
+    w.mod_rows = w.it_t = w.it_cfg = nullptr;
+    w.it_steps = w.it_idx = nullptr;
+    if (e->res_items) {
+        w.mod_rows = a.take<float>(Bp * (c.backbone == F5_BACKBONE_DIT ? (size_t)e->modN : D));
+        w.it_t = a.take<float>((size_t)B * ((size_t)S + 1));
+        w.it_cfg = a.take<float>((size_t)B);
+        w.it_steps = a.take<int>((size_t)B);
+        w.it_idx = a.take<int>(2 * (size_t)S * B);
     }
     return align_up(a.off, 256) + 256;
 }
@@ -750,13 +761,23 @@ static int run_backbone(f5_engine* e, Work<T>& w, const float* y, const float* c
     return run_unett_forward<T>(e, w, y, cond, B, Bp, N, w.temb + (size_t)step_row * e->cfg.dim, per_row_time ? e->cfg.dim : 0,
                                 lens_dev, drop_cond_first, text_first, text_second, s);
 }
+// ... with one time row per batch row, gathered by the caller (mod_gather_kernel): rows [Bp, modN] (DiT) or [Bp, D] (UNetT)
+template <typename T>
+static int run_backbone_rows(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, const float* rows,
+                             const int* lens_dev, const float* text_first, const float* text_second, hipStream_t s) {
+    if (e->cfg.backbone == F5_BACKBONE_DIT)
+        return run_dit_forward<T>(e, w, y, cond, B, Bp, N, rows, e->modN, lens_dev, 0, text_first, text_second, s);
+    return run_unett_forward<T>(e, w, y, cond, B, Bp, N, rows, e->cfg.dim, lens_dev, 0, text_first, text_second, s);
+}
 // uploads the call's small tables through pinned staging: nT times to w.tdev and, where lengths are given, the plan's lens and
-// row_start tables (SamplePlan::Chunk) and lens_plain
+// row_start tables (SamplePlan::Chunk) and lens_plain; for a per-item call (it non-null) the grids, guidance, step counts and time-row indices
 template <typename T>
 static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, const int32_t* lens_host, const SamplePlan& p,
-                        hipStream_t s) {
+                        hipStream_t s, const ItemTables* it = nullptr) {
     const int B = p.B;
-    const size_t bytes = (size_t)nT * 4 + (size_t)3 * B * 4 + ((size_t)3 * B + 16) * 4 + 64;
+    const size_t n_grid = it ? (size_t)B * (p.steps + 1) : 0, n_idx = it ? it->rows->idx.size() : 0;
+    const size_t small_bytes = (size_t)nT * 4 + (size_t)3 * B * 4 + ((size_t)3 * B + 16) * 4 + 64;
+    const size_t bytes = small_bytes + (it ? (n_grid + 2 * (size_t)B + n_idx) * 4 : 0);
     char* hb = nullptr;
     int slot = 0;
     CHK(e->stage.acquire(bytes, &hb, &slot));
@@ -784,6 +805,20 @@ static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, c
         HIPCHK(hipMemcpyAsync(w.lens, lh, (size_t)2 * B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.lens_plain, lh + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.row_start, rs, (size_t)nrs * 4, hipMemcpyHostToDevice, s));
+    }
+    if (it) {
+        float* gh = reinterpret_cast<float*>(hb + small_bytes);
+        float* ch = gh + n_grid;
+        int* sh = reinterpret_cast<int*>(ch + B);
+        int* ih = sh + B;
+        memcpy(gh, it->t_items, n_grid * 4);
+        memcpy(ch, it->cfg_items, (size_t)B * 4);
+        memcpy(sh, it->steps_items, (size_t)B * 4);
+        memcpy(ih, it->rows->idx.data(), n_idx * 4);
+        HIPCHK(hipMemcpyAsync(w.it_t, gh, n_grid * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(w.it_cfg, ch, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(w.it_steps, sh, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(w.it_idx, ih, n_idx * 4, hipMemcpyHostToDevice, s));
     }
     return e->stage.release(slot, s);
 }
@@ -866,7 +901,7 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         launch_select_rows(s, w.in_cond, nullptr, w.in_mask, w.step_cond, (long)B * N, mel);
         return hipGetLastError();
     }));
-    CHK(run_time_path<T>(e, w, p.evals * p.steps, s));  // features of every evaluation time
+    CHK(run_time_path<T>(e, w, p.items ? p.U : p.evals * p.steps, s));  // features of every evaluation time
     const int* tlens = (c.backbone == F5_BACKBONE_DIT && p.has_lens) ? w.lens_plain : nullptr;
     CHK(run_text_embed<T>(e, w, text, B, p.nt, tlens, N, 0, w.text_c, s));
     if (p.use_cfg) {
@@ -903,6 +938,15 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         const size_t yo = p.frame_at(k) * mel, to = p.frame_at(k) * c.text_dim;
         const float *cond = w.step_cond + yo, *tc = w.text_c + to, *tu = w.text_u + to;
         const int* lens = lens_dev ? lens_dev + p.lens_at(k) : nullptr;
+        if (p.items) {   // per-item times: evaluation `row` reads, for every batch row of the chunk, the time row its item is at
+            const bool dit = c.backbone == F5_BACKBONE_DIT;
+            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                launch_mod_gather(s, dit ? w.mod : w.temb, w.it_idx + (size_t)row * B + k.u0, w.mod_rows, p.halves * k.bc, k.bc,
+                                  dit ? e->modN : c.dim);
+                return hipGetLastError();
+            }));
+            return run_backbone_rows<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, w.mod_rows, lens, tc, p.use_cfg ? tu : tc, s);
+        }
         if (!p.split) return run_backbone<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, row, 0, lens, 0, tc, p.use_cfg ? tu : tc, s, pk);
         // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
         hipStream_t s1 = e->side_stream;
@@ -918,6 +962,11 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
     auto half_update = [&](const SamplePlan::Chunk& k, const RowPack& pk, int i) {
         const size_t yo = p.frame_at(k) * mel;
         return e->prof.timed(PC_MISC, s, [&] {
+            if (p.items) {
+                launch_midpoint_half_cfg_items(s, w.y + yo, w.pred, k.bc, N, mel, w.it_t + (size_t)k.u0 * (p.steps + 1), w.it_cfg + k.u0,
+                                               w.it_steps + k.u0, p.steps, i, p.use_cfg ? 1 : 0, w.y_mid + yo);
+                return hipGetLastError();
+            }
             launch_midpoint_half_cfg(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr, tgrid, i,
                                      p.cfg_strength, p.use_cfg ? 1 : 0, w.y_mid + yo);
             return hipGetLastError();
@@ -928,6 +977,11 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         const size_t yo = p.frame_at(k) * mel;
         float* slot = p.want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
         return e->prof.timed(PC_MISC, s, [&] {
+            if (p.items) {
+                launch_euler_cfg_items(s, w.y + yo, w.pred, k.bc, N, mel, w.it_t + (size_t)k.u0 * (p.steps + 1), w.it_cfg + k.u0,
+                                       w.it_steps + k.u0, p.steps, i, p.use_cfg ? 1 : 0, slot);
+                return hipGetLastError();
+            }
             launch_euler_cfg(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr, tgrid, i, p.cfg_strength,
                              p.use_cfg ? 1 : 0, slot);
             return hipGetLastError();
@@ -973,6 +1027,39 @@ static void reserve_text(f5_engine* e, int nt) {
         e->clear_graphs();
     }
 }
+// The body of one planned call whose inputs are in the arena: replay the captured graph of its key, capture it when the signature has run
+// before, else run eagerly (and remember it).  N: the call's own frame count (the cached unconditional text embedding is kept per N).
+template <typename T> static int launch_sample_body(f5_engine* e, Work<T>& w, const SamplePlan& p, int N, hipStream_t s) {
+    const int B = p.B;
+    // ---- key: the signature, and whether the body reads the cached unconditional text embedding (a call that stores it runs eagerly)
+    const bool uc_ok = p.use_cfg && uc_cacheable(e, B, p.has_lens);
+    const bool uc_hit = uc_ok && e->uc_N == N;
+    const std::string base_key = graph_key(p), key = base_key + (uc_hit ? "|uc" : "|nouc");
+    // ---- body: replay the captured graph of this key, capture it when the signature has run before, else run eagerly (and remember it)
+    static const bool trace = getenv("F5_TRACE") && getenv("F5_TRACE")[0] == '1';   // diagnostic: which path a call takes
+    const auto t_body = std::chrono::steady_clock::now();
+    hipGraphExec_t exec = nullptr;
+    const char* how = "eager launches";
+    if (e->sw.graphs && !e->gc.disabled && !e->prof.on && !(uc_ok && !uc_hit)) {
+        if ((exec = e->gc.find(key))) {
+            how = "graph replay";
+            e->gc.stats.replays++;
+        } else if (e->gc.is_warm(base_key)) {
+            CHK(e->gc.capture(key, [&](hipStream_t cs) { return sample_body<T>(e, w, p, cs); }, &exec));
+            if (exec) how = "graph capture + instantiate + launch";
+        }
+    }
+    if (exec) HIPCHK(hipGraphLaunch(exec, s));
+    else {
+        CHK(sample_body<T>(e, w, p, s));
+        e->gc.stats.eager++;
+    }
+    if (trace)
+        fprintf(stderr, "libf5hip: sample %s [%s]: host %.3f ms\n", key.c_str(), how,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body).count());
+    if (!exec) e->gc.mark_warm(base_key);
+    return F5_OK;
+}
 // sample(): plan, stage the inputs into the arena, key, replay / capture / eager, copy the outputs
 template <typename T>
 int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
@@ -1014,33 +1101,7 @@ int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const
         HIPCHK(hipMemcpy2DAsync(w.in_text, (size_t)p.nt * sizeof(int64_t), text, (size_t)nt * sizeof(int64_t), (size_t)nt * sizeof(int64_t), B,
                                 hipMemcpyDeviceToDevice, s));
     }
-    // ---- key: the signature, and whether the body reads the cached unconditional text embedding (a call that stores it runs eagerly)
-    const bool uc_ok = p.use_cfg && uc_cacheable(e, B, p.has_lens);
-    const bool uc_hit = uc_ok && e->uc_N == N;
-    const std::string base_key = graph_key(p), key = base_key + (uc_hit ? "|uc" : "|nouc");
-    // ---- body: replay the captured graph of this key, capture it when the signature has run before, else run eagerly (and remember it)
-    static const bool trace = getenv("F5_TRACE") && getenv("F5_TRACE")[0] == '1';   // diagnostic: which path a call takes
-    const auto t_body = std::chrono::steady_clock::now();
-    hipGraphExec_t exec = nullptr;
-    const char* how = "eager launches";
-    if (e->sw.graphs && !e->gc.disabled && !e->prof.on && !(uc_ok && !uc_hit)) {
-        if ((exec = e->gc.find(key))) {
-            how = "graph replay";
-            e->gc.stats.replays++;
-        } else if (e->gc.is_warm(base_key)) {
-            CHK(e->gc.capture(key, [&](hipStream_t cs) { return sample_body<T>(e, w, p, cs); }, &exec));
-            if (exec) how = "graph capture + instantiate + launch";
-        }
-    }
-    if (exec) HIPCHK(hipGraphLaunch(exec, s));
-    else {
-        CHK(sample_body<T>(e, w, p, s));
-        e->gc.stats.eager++;
-    }
-    if (trace)
-        fprintf(stderr, "libf5hip: sample %s [%s]: host %.3f ms\n", key.c_str(), how,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body).count());
-    if (!exec) e->gc.mark_warm(base_key);
+    CHK(launch_sample_body<T>(e, w, p, N, s));
     // ---- outputs -> caller (a bucket's rows N .. Nc-1 stay behind)
     if (!bucket) {
         HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1050,6 +1111,42 @@ int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const
         if (traj)
             HIPCHK(hipMemcpy2DAsync(traj, row_in, w.traj_buf, row_arena, row_in, (size_t)(steps + 1) * B, hipMemcpyDeviceToDevice, s));
     }
+    return F5_OK;
+}
+// a per-item call's buffers and its time rows (one per distinct evaluation time) are part of the arena plan: a first call, or more rows, moves the carve offsets
+static void reserve_items(f5_engine* e, int U) {
+    if (!e->res_items || U > e->res_U) {
+        e->res_items = true;
+        e->res_U = std::max(e->res_U, U);
+        e->clear_graphs();
+        e->uc_N = -1;
+    }
+}
+// f5_sample_items: sample() with per-item grids, guidance and step counts in device tables; the rectangular body, exact N, no bucket
+template <typename T>
+int EngineOps<T>::sample_items(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
+                               int nt, const ItemTables& it, int steps_max, bool any_cfg, const int32_t* lens_host, int B, int N, float* out,
+                               float* traj, hipStream_t s, int method) {
+    reserve_text(e, nt);
+    SamplePlan p = plan_sample(e, B, N, lens_host, 0, nt, steps_max, method, any_cfg ? 1.f : 0.f, traj != nullptr, 0, true);
+    p.U = (int)it.rows->times.size();
+    reserve_items(e, p.U);
+    const int mel = e->cfg.mel_dim;
+    const long half = (long)B * N * mel;
+    CHK(ensure_arena(e, B, N, steps_max));
+    Work<T> w;
+    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
+    CHK(upload_small<T>(e, w, it.rows->times.data(), p.U, lens_host, p, s, &it));
+    if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));
+    if (cond_frames > 0)
+        HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
+                                (size_t)cond_frames * mel * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.y, y0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    CHK(launch_sample_body<T>(e, w, p, N, s));
+    HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps_max + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
     return F5_OK;
 }
 // f5_prepare_sample: one graph per length bucket of [n_min, n_max], captured and instantiated without a launch.  The arena is sized for
@@ -1095,7 +1192,8 @@ size_t EngineOps<T>::work_plan(const f5_engine* e, int B, int N, int S, int call
     auto put = [&](int64_t* out, const Work<T>& v) {
         const void* p[] = {v.tdev, v.feat, v.th, v.temb, v.st, v.mod, v.lens, v.lens_plain, v.row_start, v.rowmap, v.step_cond, v.text_c, v.text_u,
                            v.tx_a, v.tx_b, v.tx_h1, v.grn_part, v.uc, v.acat, v.h, v.c1, v.x, v.pred, v.xn, v.q, v.k, v.ao, v.vt, v.ffh, v.in_cond,
-                           v.y, v.y_mid, v.out_buf, v.traj_buf, v.in_mask, v.in_text, v.cat2, v.skips, v.pred_all};
+                           v.y, v.y_mid, v.out_buf, v.traj_buf, v.in_mask, v.in_text, v.cat2, v.skips, v.pred_all, v.mod_rows, v.it_t, v.it_cfg,
+                           v.it_steps, v.it_idx};
         static_assert(sizeof(p) / sizeof(p[0]) == F5K_WORK_BUFFERS, "one entry per name of F5K_WORK_NAMES");
         for (int i = 0; i < F5K_WORK_BUFFERS; ++i) out[i] = p[i] ? (int64_t)(static_cast<const char*>(p[i]) - dry.base) : -1;
     };

@@ -258,6 +258,8 @@ struct f5_engine {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int res_nt = 0;
+    bool res_items = false;    // a per-item call has run: the arena plan carries Work::mod_rows and the it_* tables ...
+    int res_U = 0;             // ... and this many time rows (the most distinct evaluation times a per-item call has had)
     // resident adapters (F5_OPT_ADAPTERS; adapter.hip)
     bool adapters_on = false;
     std::vector<AdaptTarget> targets;
@@ -308,6 +310,11 @@ template <typename T> struct Work {
     float* y_mid;     // F5_ODE_MIDPOINT: the state at the half step [B, N, mel]
     unsigned char* in_mask;
     long long* in_text;
+    // f5_sample_items (carved once a per-item call has asked for them, f5_engine::res_items; else null): the time rows of one evaluation
+    // gathered per batch row [2 B, modN | D], and the per-item tables -- grids [B, steps_max + 1], guidance [B], step counts [B] and
+    // the row of every (evaluation, item) in the time path's output [evals * steps_max, B]
+    float *mod_rows, *it_t, *it_cfg;
+    int *it_steps, *it_idx;
     int Npad;
 };
 
@@ -347,6 +354,10 @@ struct SamplePlan {
     int n_true = 0;
     bool split = false;   // F5_SPLIT_CFG=1: the halves as two stream chains (DiT with CFG, profiler off); one chunk, no packing
     int chunk = 0;
+    // f5_sample_items: per-item grids, guidance and step counts in device tables (Work::it_*).  steps is then the largest step count,
+    // U the rows of the time path (the distinct evaluation times of the call), and cfg_strength is not read.  Never packed, never split.
+    bool items = false;
+    int U = 0;
     std::vector<Chunk> chunks;
     // Where a chunk lives in the per-call tables.  Work::lens holds [bc][the same bc] per chunk whatever `halves` is; a chunk's
     // row_start table has halves * bc + 1 entries; rowmap is carved for 2 B rows of round_up(N, 4); state, cond and text are [B, N, *].
@@ -361,9 +372,24 @@ int ensure_arena(f5_engine* e, int B, int N, int S);
 // (text_embed / forward pass chunk = B: the whole batch as one chunk, both halves; 0: chunk_utts decides)
 // (n_true > 0: a length-bucket plan -- N is the bucket's ceiling, every utterance has n_true frames and lens_host is ignored)
 SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk = 0, int nt = 0, int steps = 0,
-                       int method = F5_ODE_EULER, float cfg_strength = 1.f, bool want_traj = false, int n_true = 0);
+                       int method = F5_ODE_EULER, float cfg_strength = 1.f, bool want_traj = false, int n_true = 0, bool items = false);
 std::string graph_key(const SamplePlan& p);
 std::vector<float> time_table(const float* t_host, int steps, int method);
+// The time rows of a per-item call: the evaluation times of every live item, walked evaluation-major and then item-major, deduplicated
+// by f32 bit pattern in first-appearance order -- for a uniform batch exactly time_table's evaluation rows, in its order.
+// idx [evals * steps_max][B]: the row of every (evaluation, item); a finished item points at row 0.
+struct ItemTimeRows {
+    std::vector<float> times;
+    std::vector<int32_t> idx;
+};
+ItemTimeRows item_time_rows(const float* t_items, const int32_t* steps_items, int steps_max, int B, int method);
+// the host tables of one f5_sample_items call, as upload_small sends them down
+struct ItemTables {
+    const float* t_items;        // [B][steps_max + 1]
+    const float* cfg_items;      // [B]
+    const int32_t* steps_items;  // [B]
+    const ItemTimeRows* rows;
+};
 
 // Entry points of one operand precision T (float: exact-f32 MFMA; bf16_t / f16_t: 16-bit MFMA operands, f32 accumulate).
 template <typename T> struct EngineOps {
@@ -378,6 +404,9 @@ template <typename T> struct EngineOps {
     static int sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
                       const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
                       float* traj, hipStream_t s, int method);
+    static int sample_items(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
+                            int nt, const ItemTables& it, int steps_max, bool any_cfg, const int32_t* lens_host, int B, int N, float* out,
+                            float* traj, hipStream_t s, int method);
     static int prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max, int steps, float cfg_strength, int method, bool want_traj);
 };
 extern template struct EngineOps<float>;

@@ -509,6 +509,34 @@ extern "C" int f5k_midpoint_half_cfg(const float* y, const float* pred, int32_t 
     launch_midpoint_half_cfg((hipStream_t)stream, y, pred, B, N, mel, row_start, lens, tgrid, step, cfg, use_cfg ? 1 : 0, y_mid);
     return glue_done((hipStream_t)stream);
 }
+static int items_args(const char* who, const void* y, const void* pred, int B, int N, int mel, const void* t_items, const void* cfg_items,
+                      const void* steps_items, int steps_max, int step, const void* out, bool need_out) {
+    if (!y || !pred || !t_items || !cfg_items || !steps_items || (need_out && !out) || B <= 0 || N <= 0 || mel <= 0 || mel % 4 || steps_max <= 0 ||
+        step < 0 || step >= steps_max)
+        return fail(F5_EINVAL, "%s: bad arguments (mel %% 4 == 0, 0 <= step < steps_max)", who);
+    return F5_OK;
+}
+extern "C" int f5k_euler_cfg_items(float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items, const float* cfg_items,
+                                   const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg, float* traj_slot,
+                                   f5_stream stream) {
+    CHK(items_args("f5k_euler_cfg_items", y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, traj_slot, false));
+    launch_euler_cfg_items((hipStream_t)stream, y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, use_cfg ? 1 : 0, traj_slot);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_midpoint_half_cfg_items(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items,
+                                           const float* cfg_items, const int32_t* steps_items, int32_t steps_max, int32_t step,
+                                           int32_t use_cfg, float* y_mid, f5_stream stream) {
+    CHK(items_args("f5k_midpoint_half_cfg_items", y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, y_mid, true));
+    launch_midpoint_half_cfg_items((hipStream_t)stream, y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, use_cfg ? 1 : 0,
+                                   y_mid);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, int32_t rows, int32_t nidx, int32_t width, f5_stream stream) {
+    if (!src || !idx || !dst || rows <= 0 || nidx <= 0 || width <= 0 || width % 4)
+        return fail(F5_EINVAL, "f5k_mod_gather: bad arguments (width %% 4 == 0)");
+    launch_mod_gather((hipStream_t)stream, src, idx, dst, rows, nidx, width);
+    return glue_done((hipStream_t)stream);
+}
 extern "C" int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream) {
     if (!a || !rowmask || !out || rows <= 0 || C <= 0 || C % 4) return fail(F5_EINVAL, "f5k_select_rows: bad arguments (C %% 4 == 0)");
     launch_select_rows((hipStream_t)stream, a, b, rowmask, out, (long)rows, C);

@@ -223,6 +223,34 @@ class Engine:
                        "f5_sample_ode")
         return out, traj
 
+    def sample_items(self, cond, cond_mask, y0, text, t_grids, cfg_strengths, lens=None, want_traj=True, method="euler"):
+        """sample() with per-item settings (f5_sample_items): t_grids a list of B grids (item b makes len(t_grids[b]) - 1 steps),
+        cfg_strengths a list of B floats.  The trajectory has max(steps) + 1 slots; an item that has finished keeps its final state."""
+        if method not in _lib.ODE_METHODS:
+            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
+        B, N, mel = y0.shape
+        if len(t_grids) != B or len(cfg_strengths) != B:
+            raise ValueError(f"sample_items: {len(t_grids)} grids and {len(cfg_strengths)} cfg strengths for a batch of {B}")
+        steps = [len(g) - 1 for g in t_grids]
+        steps_max = max(steps)
+        flat = []
+        for g in t_grids:   # rows of steps_max + 1; the engine ignores what follows an item's own grid
+            flat += [float(v) for v in g] + [0.0] * (steps_max + 1 - len(g))
+        cond_frames = 0 if cond is None else cond.shape[1]
+        if cond is not None:
+            cond = _h2d_async(cond, self.device, torch.float32)
+        y0 = _h2d_async(y0, self.device, torch.float32)
+        cm = _h2d_async(cond_mask, self.device, torch.uint8)
+        text = _h2d_async(text, self.device, torch.long)
+        out = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
+        traj = torch.empty(steps_max + 1, B, N, mel, device=self.device, dtype=torch.float32) if want_traj else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.f5_sample_items(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y0), _ptr(text), text.shape[1],
+                                                _lib.float_array(flat), _lib.int_array(steps), steps_max, _lib.float_array(cfg_strengths),
+                                                _lib.int_array(lens), B, N, _ptr(out), _ptr(traj), _stream_ptr(self.device),
+                                                _lib.ODE_METHODS[method]), "f5_sample_items")
+        return out, traj
+
     # ------------------------------------------------------------------ profiling
     def profile(self, on: bool):
         _lib.check(self.lib.f5_profile_enable(self._h, int(on)), "f5_profile_enable")

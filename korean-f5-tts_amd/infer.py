@@ -59,7 +59,7 @@ import re
 import numpy as np
 import torch
 
-from .cfm import CFM, clamp_durations
+from .cfm import CFM, clamp_durations, is_per_item
 from .config import HOP_LENGTH, MEL_DIM, N_FFT, SAMPLE_RATE
 from . import silence as _silence
 from .edit import edit_mask, edit_plan  # noqa: F401  (part of this module's surface)
@@ -631,12 +631,29 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     yield cross_fade_concat(waves, cross_fade_duration), target_sample_rate, np.concatenate(specs, axis=1)
 
 
+def _sampler_for(model, who, total, run, *, steps, cfg_strength, sway_sampling_coef, seed):
+    """The sampler call of one group of a batched driver: (model.sample, its four settings) as ever when all four are given once;
+    when any is a sequence -- one entry per item of the whole call, `total` of them -- (model.sample_items, the settings with every
+    sequence cut to the group's items `run`)."""
+    kw = dict(steps=steps, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+    if not is_per_item(*kw.values()):
+        return model.sample, kw
+    for name, v in kw.items():
+        if is_per_item(v):
+            if len(v) != total:
+                raise ValueError(f"{who}: {name} has {len(v)} entries for {total} items")
+            kw[name] = [v[k] for k in run]
+    return model.sample_items, kw
+
+
 def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, **sample_kw):
     """The reference's batch loop (eval/eval_infer_batch.py:190-212) as one call: `model.sample(cond, text, duration, lens=lens,
     **sample_kw)`, then every item's generated frames [lens_i, duration_i) through the vocoder in ONE ragged pass
     (vocoder.decode_ragged: Vocos, or `BigVGAN.ragged()`) instead of one decode per item.  `duration_i` are the clamped totals sample() ran at.
     Returns (wav f32[B, L_max], wav_lens, mel): wav[i, :wav_lens[i]] is item i's waveform (times gain[i] where given), zeros
-    behind it; mel is sample()'s output [B, N, 100], prompts included.  Plain BigVGAN: pass `.ragged()`."""
+    behind it; mel is sample()'s output [B, N, 100], prompts included.  Plain BigVGAN: pass `.ragged()`.
+    steps / cfg_strength / sway_sampling_coef / seed given as a sequence of B: the batch runs as `model.sample_items`, each item
+    with its own."""
     _require_ragged_vocoder(vocoder, "synthesize_batch", "decode item by item")
     if sample_kw.get("vocoder") is not None:
         raise TypeError("synthesize_batch: pass the vocoder as its second argument, not through sample()'s vocoder=")
@@ -644,7 +661,9 @@ def synthesize_batch(model, vocoder, cond, text, duration, *, lens, gain=None, *
         text = _tokenise(model, text, None, stacklevel=None)[1]   # (as before: this driver does not warn)
     lens = torch.as_tensor(lens).to("cpu", torch.long)
     ends = clamp_durations(text.to("cpu", torch.long), lens, duration, sample_kw.get("max_duration", 65536))
-    mel, _ = model.sample(cond, text, duration, lens=lens, **sample_kw)
+    four = ("steps", "cfg_strength", "sway_sampling_coef", "seed")
+    sample = model.sample_items if is_per_item(*(sample_kw.get(n) for n in four)) else model.sample
+    mel, _ = sample(cond, text, duration, lens=lens, **sample_kw)
     wav, wav_lens = vocoder.decode_ragged(mel.to(torch.float32).permute(0, 2, 1), ends=ends.tolist(), starts=lens.tolist(), gain=gain)
     return wav, wav_lens, mel
 
@@ -714,6 +733,7 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
     are returned.
     clip_silence=True (needs prompt_on_device=True): the prompts are clipped first (prompt_batch, clip_prompts).
     remove_silence=True: pauses of 1 s or more are cut out of every finished waveform, in one pass over all of them (remove_silence).
+    nfe_step / cfg_strength / sway_sampling_coef / seed: one value, or a sequence of one value per prompt (model.sample_items).
     Returns (waves: a list of 1-D f32 device tensors, sample_rate, mel: a list of [100, T_i] generated mels).  Plain BigVGAN: pass `.ragged()`."""
     _require_text_tokenizer(model, text_tokenizer)
     _require_ragged_vocoder(vocoder, "synthesize_prompts", "decode item by item")
@@ -733,10 +753,10 @@ def synthesize_prompts(model, vocoder, prompts, gen_texts, *, speed=speed, targe
         for run in group_chunks(ends, batch_frames):
             glens = [lens[k] for k in run]
             cond = pb["cond"][run.start:run.stop, :max(glens)].contiguous()
+            _, four = _sampler_for(model, "synthesize_prompts", len(prompts), run, steps=nfe_step, cfg_strength=cfg_strength,
+                                   sway_sampling_coef=sway_sampling_coef, seed=seed)
             wav, wav_lens, mel = synthesize_batch(model, vocoder, cond, [texts[k] for k in run],
-                                                  torch.tensor([durations[k] for k in run]), lens=glens, steps=nfe_step,
-                                                  cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed,
-                                                  **sample_kw)
+                                                  torch.tensor([durations[k] for k in run]), lens=glens, **four, **sample_kw)
             for b, k in enumerate(run):
                 waves.append(rescale_to_prompt(wav[b, :wav_lens[b]], rms[k], target_rms))
                 mels.append(mel[b, lens[k]:ends[k]].to(torch.float32).permute(1, 0))
@@ -876,6 +896,8 @@ def synthesize_script(model, vocoder, voices, script, *, speed=speed, target_rms
     Returns (wave f32[total], sample_rate, combined mel f32[100, T_total], segments), wave and mel on the device; segments is a
     host list of (voice, text, start_sample, end_sample) per stretch in the joined waveform (before any pause is removed) -- what
     the reference's save_chunk writes to files.  A stretch without text has start == end.  Any number of chunks up to 65535.
+    nfe_step / cfg_strength / sway_sampling_coef / seed: one value, or a sequence of one value per chunk in script order
+    (script_plan's items; model.sample_items).
     A vocoder without decode_ragged: NotImplementedError (plain BigVGAN: pass `.ragged()`); kor_* tokenisers need text_tokenizer=.
 
     Against one infer_process per stretch:
@@ -910,9 +932,10 @@ def synthesize_script(model, vocoder, voices, script, *, speed=speed, target_rms
         for run in group_chunks(ends, batch_frames):
             glens = [lens[k] for k in run]
             rows = torch.tensor([voice_of[k] for k in run], device=bank.mel.device)
-            generated, _ = model.sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[texts[k] for k in run],
-                                        duration=torch.tensor([durations[k] for k in run]), lens=torch.tensor(glens), steps=nfe_step,
-                                        cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=seed)
+            sample, four = _sampler_for(model, "synthesize_script", len(items), run, steps=nfe_step, cfg_strength=cfg_strength,
+                                        sway_sampling_coef=sway_sampling_coef, seed=seed)
+            generated, _ = sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[texts[k] for k in run],
+                                  duration=torch.tensor([durations[k] for k in run]), lens=torch.tensor(glens), **four)
             generated = generated.to(torch.float32)
             wave, wave_lens = vocoder.decode_ragged(generated.permute(0, 2, 1), ends=[ends[k] for k in run],
                                                     starts=[starts[k] for k in run])

@@ -301,11 +301,35 @@ class PoolRequest:
             self.done = True
 
 
-class PoolClient:
-    """One client of a StreamPool (pool.connect): its voice, rate, format, packet size, cross-fade and first-package state."""
+UNSET = object()   # connect(sway_sampling_coef=..., seed=...): "the pool's own value" (None is a value of both)
 
-    def __init__(self, pool, voice, out_rate, sample_format, chunk_size, cross_fade_duration, speed, fix_duration):
+
+class PoolClient:
+    """One client of a StreamPool (pool.connect): its voice, rate, format, packet size, cross-fade and first-package state, and the
+    sampler settings its chunks run with (`sample_kw`: the pool's, unless connect gave the client its own)."""
+
+    def __init__(self, pool, voice, out_rate, sample_format, chunk_size, cross_fade_duration, speed, fix_duration, nfe_step=None,
+                 cfg_strength=None, sway_sampling_coef=UNSET, seed=UNSET):
+        import math
+
         from . import infer as I
+
+        kw = dict(pool.sample_kw)
+        if nfe_step is not None:
+            if int(nfe_step) < 1:
+                raise ValueError(f"connect: nfe_step = {nfe_step} (need at least 1 step)")
+            kw["steps"] = int(nfe_step)
+        if cfg_strength is not None:
+            if not math.isfinite(float(cfg_strength)):
+                raise ValueError(f"connect: cfg_strength = {cfg_strength} (need a finite number)")
+            kw["cfg_strength"] = float(cfg_strength)
+        if sway_sampling_coef is not UNSET:
+            if sway_sampling_coef is not None and not math.isfinite(float(sway_sampling_coef)):
+                raise ValueError(f"connect: sway_sampling_coef = {sway_sampling_coef} (need None or a finite number)")
+            kw["sway_sampling_coef"] = sway_sampling_coef
+        if seed is not UNSET:
+            kw["seed"] = seed
+        self.sample_kw = kw
 
         if sample_format not in ("f32", "s16"):
             raise ValueError(f"connect: sample_format {sample_format!r} (expected 'f32' or 's16')")
@@ -346,7 +370,7 @@ class PoolClient:
 
 class StreamPool:
     """Many clients on one model (infer.open_pool builds it): the chunks of different clients' requests share ragged batches.  One
-    tick is, all asynchronous on the stream: ONE model.sample over the tick's items (pool_tick chooses them) with each item's own
+    tick is, all asynchronous on the stream: ONE model.sample (model.sample_items when its rows differ in sampler settings) over the tick's items (pool_tick chooses them) with each item's own
     voice row and prompt frames, as synthesize_script runs a group; ONE decode_ragged; the rescale to each prompt's level; ONE
     wave_emit over every request the tick touched -- its pieces so far joined and the samples that have become settled delivered at
     its client's rate and format, read where the pieces lie; ONE copy of the emitted bytes into a pinned buffer.  The host then
@@ -383,11 +407,13 @@ class StreamPool:
         self.log, self._requests, self._pending, self._outbox, self._cursor, self._next_id = [], [], [], [], 0, 0
 
     def connect(self, voice, *, out_rate=SAMPLE_RATE, sample_format="f32", chunk_size=2048, cross_fade_duration=0.0, speed=None,
-                fix_duration=None) -> PoolClient:
+                fix_duration=None, nfe_step=None, cfg_strength=None, sway_sampling_coef=UNSET, seed=UNSET) -> PoolClient:
         """A client that speaks with `voice` of the pool's bank and receives packets of chunk_size samples at out_rate in
         sample_format; cross_fade_duration: seconds the chunks of one of its requests fade into each other; speed: None is 1.0 (a
-        voice's own speed goes first, as in a session)."""
-        return PoolClient(self, voice, out_rate, sample_format, chunk_size, cross_fade_duration, speed, fix_duration)
+        voice's own speed goes first, as in a session).  nfe_step / cfg_strength / sway_sampling_coef / seed: the client's own
+        sampler settings; left out, the pool's.  Clients of different settings still share ticks (model.sample_items)."""
+        return PoolClient(self, voice, out_rate, sample_format, chunk_size, cross_fade_duration, speed, fix_duration, nfe_step,
+                          cfg_strength, sway_sampling_coef, seed)
 
     def stats(self) -> dict:
         """ticks run; sample_calls / decode_calls / emit_launches: model.sample, decode_ragged and wave_emit calls; copies: device
@@ -415,9 +441,14 @@ class StreamPool:
         self.log.append(list(items))
         glens = [bank.frames[r.voice] for r, _ in run]
         rows = torch.tensor([r.voice for r, _ in run], device=bank.mel.device)
-        generated, _ = self.model.sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
-                                         duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens),
-                                         **self.sample_kw)
+        # a tick whose rows all carry the pool's settings is one sample(); any other is one sample_items() with the rows' own
+        row_kw = [r.client.sample_kw for r, _ in run]
+        if all(kw == self.sample_kw for kw in row_kw):
+            sample, kw = self.model.sample, self.sample_kw
+        else:
+            sample, kw = self.model.sample_items, {name: [rk[name] for rk in row_kw] for name in self.sample_kw}
+        generated, _ = sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
+                              duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens), **kw)
         wave, wave_lens = self.vocoder.decode_ragged(generated.to(torch.float32).permute(0, 2, 1), ends=[r.plan["ends"][k] for r, k in run],
                                                      starts=[bank.samples[r.voice] // HOP_LENGTH for r, _ in run])
         wave = I.rescale_to_prompt(wave, bank.rms.index_select(0, rows)[:, None], bank.target_rms)
@@ -501,7 +532,7 @@ def open_pool(model, vocoder, voices, *, batch_frames, max_items=64, first_alone
     once, here).  batch_frames: the budget of a tick, rows x longest row (None: every chunk as its own B = 1 sample(), as in
     open_stream; the ticks then share only the emit); max_items: rows of a tick at most; first_alone: a waiting first chunk keeps
     later chunks out of its tick (pool_tick has the rule); lookahead: ticks enqueued ahead of the one the host waits for.  The
-    sampler settings are the pool's, because sample() takes them as scalars.  Refuses what open_stream refuses.  See StreamPool, and pool.connect for a client's side."""
+    sampler settings are the pool's defaults: pool.connect may give a client its own.  Refuses what open_stream refuses.  See StreamPool, and pool.connect for a client's side."""
     return StreamPool(model, vocoder, voices, batch_frames=batch_frames, max_items=max_items, first_alone=first_alone,
                       lookahead=lookahead, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
                       seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence)
