@@ -166,6 +166,30 @@ int f5_sample_items(f5_engine* e, const float* cond, int32_t cond_frames, const 
                     const float* cfg_items, const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream,
                     int32_t method);
 
+/* Some steps of an f5_sample_items solve as a call of their own, so that a batch can be re-formed between two slices: the state stays
+ * in device memory, rows that have made their steps leave, new rows join, N follows the rows that are there.
+ *   t_items HOST f32[B][count + 1]: the sub-grid of this slice, item b's full grid from the step it is at; steps_items HOST int32[B],
+ *   each in [1, count], the largest equal to count: the steps item b makes here.  cfg_items, lens_host, method: f5_sample_items'.
+ *   rows_host HOST int32[B]: the row of prev_state f32[prev_B, prev_N, mel] (a previous call's state_out) item b continues from, or
+ *   -1 for an item that begins here and takes y_new[b] (y_new f32[B, N, mel]; rows of continuing items are not read).
+ *   prev_state may be NULL when every row is -1, y_new when none is.
+ * The start state is staged by one launch: y[b, n] = prev_state[rows[b], n] for n < min(N, prev_N), +0.0 for n >= prev_N (frames the
+ * previous batch did not have start as the zero padding of y0 does), frames n >= N of the previous state are dropped.  A continuing
+ * row keeps every frame it had, pad frames included, so a chain of slices at fixed composition computes bit for bit what the one
+ * f5_sample_items call computes.  prev_state is the caller's tensor, never the arena: other engine calls may run between two slices.
+ *   state_out f32[B, N, mel]: the raw state after the slice.  out = where(cond_mask, cond, state): meaningful for the items whose
+ *   last step was in this slice.
+ * The time path runs over the distinct evaluation times of the slice.  The body and its graph key are f5_sample_items' without a
+ * trajectory (count in the place of steps_max): the key holds no position in a grid, no guidance and nothing of prev_*, the staging
+ * is eager like every input copy, and one captured graph serves every slice of a shape.
+ * F5_EINVAL, with a message naming the item, nothing launched and nothing staged: count < 1, steps_items[b] outside [1, count],
+ * max(steps_items) != count, rows_host[b] outside [-1, prev_B), a previous row named twice, a row >= 0 with prev_state NULL, a -1
+ * with y_new NULL; and f5_sample_items' own rules. */
+int f5_sample_span(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y_new,
+                   const float* prev_state, int32_t prev_B, int32_t prev_N, const int32_t* rows_host, const int64_t* text, int32_t nt,
+                   const float* t_items, const int32_t* steps_items, int32_t count, const float* cfg_items, const int32_t* lens_host,
+                   int32_t B, int32_t N, float* out, float* state_out, f5_stream stream, int32_t method);
+
 /* Pre-sizes the activation arena (otherwise it grows on first use, which calls hipMalloc inside f5_sample).  The plan for
  * max_steps covers both solvers: a midpoint call with steps <= max_steps needs no regrowth. */
 int f5_reserve(f5_engine* e, int32_t max_batch, int32_t max_frames, int32_t max_steps);
@@ -742,6 +766,11 @@ int f5k_euler_cfg_items(float* y, const float* pred, int32_t B, int32_t N, int32
 int f5k_midpoint_half_cfg_items(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items,
                                 const float* cfg_items, const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg,
                                 float* y_mid, f5_stream stream);
+/* The staging of f5_sample_span: y f32[B, N, mel] = prev_state[rows[b], n] (n < prev_N, else +0.0) where rows[b] >= 0, y_new[b, n]
+ * where rows[b] == -1.  rows int32[B] on the device, rows_host the same table on the host (the rules of f5_sample_span's rows_host
+ * are checked on it); prev_state f32[prev_B, prev_N, mel] and y_new f32[B, N, mel] on the device, NULL where no row reads them. */
+int f5k_span_stage(float* y, const float* prev_state, int32_t prev_B, int32_t prev_N, const float* y_new, const int32_t* rows,
+                   const int32_t* rows_host, int32_t B, int32_t N, int32_t mel, f5_stream stream);
 /* dst f32[rows, width] = src[idx[r % nidx], :]; idx int[nidx] (device), width % 4 == 0.  The caller keeps idx inside src. */
 int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, int32_t rows, int32_t nidx, int32_t width, f5_stream stream);
 /* The time rows of an f5_sample_items call (host arithmetic, no device needed): the evaluation times of every live item -- Euler t[b][i];

@@ -95,6 +95,8 @@ SIGNATURES = {
     "f5_sample_ode": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_sample_items": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), _i, C.POINTER(_f), C.POINTER(_i), _i, _i, _p, _p,
                              _p, _i]),
+    "f5_sample_span": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, C.POINTER(_i), _p, _i, C.POINTER(_f), C.POINTER(_i), _i, C.POINTER(_f),
+                            C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_reserve": (_i, [_p, _i, _i, _i]),
     "f5_set_length_buckets": (_i, [_p, _i]),
     "f5_prepare_sample": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
@@ -165,6 +167,7 @@ SIGNATURES = {
     "f5k_euler_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
     "f5k_midpoint_half_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
     "f5k_mod_gather": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "f5k_span_stage": (_i, [_p, _p, _i, _i, _p, _p, C.POINTER(_i), _i, _i, _i, _p]),
     "f5k_item_time_rows": (_i, [C.POINTER(_f), C.POINTER(_i), _i, _i, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     "f5k_select_rows": (_i, [_p, _p, _p, _p, C.c_int64, _i, _p]),
     "f5k_time_sinus": (_i, [_p, _p, _p, _i, _p]),

@@ -65,6 +65,14 @@ def item_noise(durations: list, seeds: list, mel: int, device="cpu") -> torch.Te
     return pad_sequence(y0, padding_value=0, batch_first=True)
 
 
+class SpanResult:
+    """What CFM.sample_span returns: `out` [B, N, mel] (an item's result once it is done), `state` [B, N, mel] (the raw ODE state:
+    the next call's prev[0]) and `done`, a list of B bools, true where the item's last step was run."""
+
+    def __init__(self, out, state, done):
+        self.out, self.state, self.done = out, state, done
+
+
 class CFM(nn.Module):
     def __init__(self, transformer: nn.Module, sigma=0.0, odeint_kwargs: dict = dict(method="euler"),
                  audio_drop_prob=0.3, cond_drop_prob=0.2, num_channels=None, mel_spec_module: nn.Module | None = None,
@@ -212,3 +220,79 @@ class CFM(nn.Module):
         if exists(vocoder):
             out = vocoder(out.permute(0, 2, 1))
         return out, trajectory
+
+    @torch.no_grad()
+    def sample_span(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None, start, count,
+                    prev=None, use_epss=True, max_duration=65536, no_ref_audio=False, edit_mask=None):
+        """Some steps of a sample_items() solve, so that a batch can be re-formed between two calls: item b, whose settings are
+        sample_items' (`steps`, `cfg_strength`, `sway_sampling_coef`, `seed`: one value or one per item), runs its steps
+        [start[b], min(start[b] + count, steps[b])) in one engine call (f5_sample_span).  prev = (state, rows): the `state` a
+        previous call returned and, per item, its row there, or -1 for an item that begins here -- such an item has start 0 and
+        gets item_noise's draw for it alone.  prev=None: every item begins here.  The batch runs at N = max(duration) of the items
+        it holds now.  The grids are item_time_grids' grids, sliced.  Returns a SpanResult: `out` (where(cond_mask, cond, state):
+        an item's result once it is `done`), `state` [B, N, mel] and `done`, per item whether its last step was run."""
+        self.eval()
+        device = self.device
+        if cond.ndim == 2:
+            cond = self.mel_spec(cond.to(device))
+            cond = cond.permute(0, 2, 1)
+            assert cond.shape[-1] == self.num_channels
+        cond = cond.to(device=device, dtype=torch.float32)
+        batch, cond_seq_len = cond.shape[:2]
+        steps_i = [int(v) for v in per_item("steps", steps, batch)]
+        cfg_i = [float(v) for v in per_item("cfg_strength", cfg_strength, batch)]
+        sway_i = per_item("sway_sampling_coef", sway_sampling_coef, batch)
+        seed_i = per_item("seed", seed, batch)
+        count = int(count)
+        if count < 1:
+            raise ValueError(f"sample_span: count = {count} (a slice runs at least one step)")
+        start_i = [int(v) for v in start]
+        if len(start_i) != batch:
+            raise ValueError(f"sample_span: start has {len(start_i)} entries for a batch of {batch}")
+        state, rows = (None, [-1] * batch) if prev is None else prev
+        rows = [int(r) for r in rows]
+        if len(rows) != batch:
+            raise ValueError(f"sample_span: rows has {len(rows)} entries for a batch of {batch}")
+        if not exists(lens):
+            lens = torch.full((batch,), cond_seq_len, dtype=torch.long)
+        lens = lens.to("cpu", torch.long)
+
+        if isinstance(text, list):
+            text = list_str_to_idx(text, self.vocab_char_map) if exists(self.vocab_char_map) else list_str_to_tensor(text)
+            assert text.shape[0] == batch
+        text_cpu = text.to("cpu", torch.long)
+
+        cond_mask = lens_to_mask(lens)
+        if edit_mask is not None:
+            cond_mask = cond_mask & edit_mask.to("cpu")
+        duration = clamp_durations(text_cpu, lens, duration, max_duration)
+        N = int(duration.amax())
+        cond_mask = F.pad(cond_mask, (0, N - cond_mask.shape[-1]), value=False)
+        durs = duration.tolist()
+
+        for b in range(batch):
+            if not 0 <= start_i[b] < steps_i[b]:
+                raise ValueError(f"sample_span: item {b}: start = {start_i[b]} outside [0, steps = {steps_i[b]})")
+            if rows[b] < 0 and start_i[b] != 0:
+                raise ValueError(f"sample_span: item {b} begins here (row -1) but start = {start_i[b]}")
+            if rows[b] >= 0 and (state is None or state.shape[1] < durs[b]):
+                have = "no previous state" if state is None else f"the previous state has {state.shape[1]} frames"
+                raise ValueError(f"sample_span: item {b} continues row {rows[b]} at {durs[b]} frames, but {have}")
+        run = [min(count, n - a) for n, a in zip(steps_i, start_i)]
+        # the sub-grids: the items' own grids, sliced on the host (nothing is computed again in another arithmetic)
+        grids = [t[a:a + r + 1] for t, a, r in zip(item_time_grids(steps_i, sway_i, use_epss), start_i, run)]
+
+        fresh = [b for b in range(batch) if rows[b] < 0]
+        y_new = None
+        if fresh:
+            noise_device = self.noise_device if self.noise_device == "cpu" else device
+            drawn = item_noise([durs[b] for b in fresh], [seed_i[b] for b in fresh], self.num_channels, noise_device)
+            y_new = torch.zeros(batch, N, self.num_channels, device=drawn.device, dtype=torch.float32)
+            y_new[fresh, :drawn.shape[1]] = drawn
+
+        eng = self.transformer.engine()
+        out, new_state = eng.sample_span(None if no_ref_audio else cond, cond_mask, y_new, state, rows, text_cpu,
+                                         [t.tolist() for t in grids], cfg_i, lens=durs if batch > 1 else None,
+                                         method=self.odeint_kwargs.get("method", "euler"))
+        self.transformer.clear_cache()
+        return SpanResult(out, new_state, [a + r == n for a, r, n in zip(start_i, run, steps_i)])

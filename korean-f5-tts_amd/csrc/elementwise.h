@@ -471,6 +471,29 @@ inline void launch_mod_gather(hipStream_t s, const float* src, const int* idx, f
     hipLaunchKernelGGL(mod_gather_kernel, dim3(ew_blocks((long)rows * width / 4)), dim3(256), 0, s, src, idx, dst, rows, nidx, width);
 }
 
+// f5_sample_span: the start state of a slice.  y[b, n, :] for b < B, n < N is prev[rows[b], n, :] where rows[b] >= 0 and n < prev_N, +0.0
+// where rows[b] >= 0 and n >= prev_N (a frame the previous batch did not have), and y_new[b, n, :] where rows[b] == -1.  One float4
+// per lane, consecutive lanes on consecutive addresses of y and, inside a row, of the source; mel % 4 == 0.  prev / y_new may be null
+// when no row reads them.
+static __global__ void span_stage_kernel(float* __restrict__ y, const float* __restrict__ prev, const float* __restrict__ y_new,
+                                         const int* __restrict__ rows, int B, int N, int prev_N, int mel) {
+    const int c4n = mel / 4;
+    const long per_row = (long)N * c4n, total = (long)B * per_row, keep = (long)(prev_N < N ? prev_N : N) * c4n;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / per_row);
+        const long j = i - (long)b * per_row;   // float4 index inside the row: n * c4n + c
+        const int r = rows[b];
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < 0) v = reinterpret_cast<const float4*>(y_new)[i];
+        else if (j < keep) v = reinterpret_cast<const float4*>(prev)[(long)r * prev_N * c4n + j];
+        reinterpret_cast<float4*>(y)[i] = v;
+    }
+}
+inline void launch_span_stage(hipStream_t s, float* y, const float* prev, const float* y_new, const int* rows, int B, int N, int prev_N,
+                              int mel) {
+    hipLaunchKernelGGL(span_stage_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, prev, y_new, rows, B, N, prev_N, mel);
+}
+
 // rowmap[row_start[b'] + n] = (b', n) for n < row_start[b' + 1] - row_start[b']   (one block per batch row)
 static __global__ void fill_rowmap_kernel(const int* __restrict__ row_start, int2* __restrict__ rowmap) {
     const int bp = blockIdx.x, r0 = row_start[bp], cnt = row_start[bp + 1] - r0;

@@ -401,6 +401,50 @@ extern "C" int f5_sample_items(f5_engine* e, const float* cond, int32_t cond_fra
     return F5_OPS(e, sample_items(e, cond, cond_frames, cond_mask, y0, text, nt, it, steps_max, any_cfg, lens_host, B, N, out, traj,
                                   (hipStream_t)stream, method));
 }
+// the rules of a slice's row table (f5_sample_span, f5k_span_stage); messages name the item
+int check_span_rows(const char* who, const int32_t* rows_host, int B, const void* prev_state, int prev_B, int prev_N, const void* y_new) {
+    if (!rows_host || B <= 0) return fail(F5_EINVAL, "%s: bad arguments", who);
+    std::vector<char> taken(prev_B > 0 ? prev_B : 0, 0);
+    for (int b = 0; b < B; ++b) {
+        const int r = rows_host[b];
+        if (r < -1 || r >= std::max(prev_B, 0))
+            return fail(F5_EINVAL, "%s: item %d: rows = %d outside [-1, prev_B = %d)", who, b, r, prev_B);
+        if (r < 0) {
+            if (!y_new) return fail(F5_EINVAL, "%s: item %d begins here (rows = -1) but y_new is NULL", who, b);
+            continue;
+        }
+        if (!prev_state || prev_N <= 0)
+            return fail(F5_EINVAL, "%s: item %d continues row %d but there is no previous state (prev_state NULL or prev_N < 1)", who, b, r);
+        if (taken[r]) return fail(F5_EINVAL, "%s: item %d: row %d of the previous state is named twice", who, b, r);
+        taken[r] = 1;
+    }
+    return F5_OK;
+}
+extern "C" int f5_sample_span(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y_new,
+                              const float* prev_state, int32_t prev_B, int32_t prev_N, const int32_t* rows_host, const int64_t* text,
+                              int32_t nt, const float* t_items, const int32_t* steps_items, int32_t count, const float* cfg_items,
+                              const int32_t* lens_host, int32_t B, int32_t N, float* out, float* state_out, f5_stream stream,
+                              int32_t method) {
+    // (the table rules first: they need no engine state)
+    if (count < 1) return fail(F5_EINVAL, "f5_sample_span: count = %d (a slice runs at least one step)", count);
+    if (!cfg_items) return fail(F5_EINVAL, "f5_sample_span: bad arguments");
+    CHK(check_items("f5_sample_span", t_items, steps_items, count, cfg_items, B, method));
+    CHK(check_span_rows("f5_sample_span", rows_host, B, prev_state, prev_B, prev_N, y_new));
+    CHK(check_ready(e, B, N));
+    if ((!cond && cond_frames > 0) || !cond_mask || !text || !out || !state_out || nt <= 0 || cond_frames < 0 || cond_frames > N)
+        return fail(F5_EINVAL, "f5_sample_span: bad arguments");
+    if (B > 1 && !lens_host) return fail(F5_EINVAL, "f5_sample_span: lens required when B > 1 (cfm.py:155-158)");
+    if (lens_host)
+        for (int i = 0; i < B; ++i)
+            if (lens_host[i] <= 0 || lens_host[i] > N) return fail(F5_EINVAL, "f5_sample_span: lens[%d]=%d out of (0, N]", i, lens_host[i]);
+    bool any_cfg = false;
+    for (int b = 0; b < B; ++b) any_cfg = any_cfg || !(cfg_items[b] < 1e-5f);
+    const ItemTimeRows rows = item_time_rows(t_items, steps_items, count, B, method);
+    const ItemTables it{t_items, cfg_items, steps_items, &rows, rows_host};
+    e->prof.clear();
+    return F5_OPS(e, sample_span(e, cond, cond_frames, cond_mask, y_new, prev_state, prev_N, text, nt, it, count, any_cfg, lens_host, B, N, out,
+                                 state_out, (hipStream_t)stream, method));
+}
 
 // ------------------------------------------------------------------------------------- length buckets
 extern "C" int f5_set_length_buckets(f5_engine* e, int32_t granule) {

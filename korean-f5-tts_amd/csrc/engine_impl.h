@@ -777,7 +777,7 @@ static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, c
     const int B = p.B;
     const size_t n_grid = it ? (size_t)B * (p.steps + 1) : 0, n_idx = it ? it->rows->idx.size() : 0;
     const size_t small_bytes = (size_t)nT * 4 + (size_t)3 * B * 4 + ((size_t)3 * B + 16) * 4 + 64;
-    const size_t bytes = small_bytes + (it ? (n_grid + 2 * (size_t)B + n_idx) * 4 : 0);
+    const size_t bytes = small_bytes + (it ? (n_grid + 3 * (size_t)B + n_idx) * 4 : 0);
     char* hb = nullptr;
     int slot = 0;
     CHK(e->stage.acquire(bytes, &hb, &slot));
@@ -819,6 +819,11 @@ static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, c
         HIPCHK(hipMemcpyAsync(w.it_cfg, ch, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.it_steps, sh, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.it_idx, ih, n_idx * 4, hipMemcpyHostToDevice, s));
+        if (it->span_rows) {   // f5_sample_span: the staging kernel's row table, in the rowmap (a per-item body is never packed)
+            int* rh = ih + n_idx;
+            memcpy(rh, it->span_rows, (size_t)B * 4);
+            HIPCHK(hipMemcpyAsync(w.rowmap, rh, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        }
     }
     return e->stage.release(slot, s);
 }
@@ -1147,6 +1152,37 @@ int EngineOps<T>::sample_items(f5_engine* e, const float* cond, int cond_frames,
     CHK(launch_sample_body<T>(e, w, p, N, s));
     HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps_max + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return F5_OK;
+}
+// f5_sample_span: steps of a per-item solve as a call of their own.  sample_items' plan and body on the sub-grids of the slice; the start
+// state is staged from the caller's previous state tensor (another N, another row order) or, for a row that begins here, from y_new,
+// by one span_stage_kernel launch straight into w.y; the raw state comes back beside `out`.  The staging is eager, so the body's key
+// is sample_items' key without a trajectory: one captured graph serves every slice of a shape.
+template <typename T>
+int EngineOps<T>::sample_span(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y_new,
+                              const float* prev_state, int prev_N, const int64_t* text, int nt, const ItemTables& it, int count, bool any_cfg,
+                              const int32_t* lens_host, int B, int N, float* out, float* state_out, hipStream_t s, int method) {
+    reserve_text(e, nt);
+    SamplePlan p = plan_sample(e, B, N, lens_host, 0, nt, count, method, any_cfg ? 1.f : 0.f, false, 0, true);
+    p.U = (int)it.rows->times.size();
+    reserve_items(e, p.U);
+    const int mel = e->cfg.mel_dim;
+    const long half = (long)B * N * mel;
+    CHK(ensure_arena(e, B, N, count));
+    Work<T> w;
+    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
+    CHK(upload_small<T>(e, w, it.rows->times.data(), p.U, lens_host, p, s, &it));
+    if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));
+    if (cond_frames > 0)
+        HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
+                                (size_t)cond_frames * mel * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+    launch_span_stage(s, w.y, prev_state, y_new, reinterpret_cast<const int*>(w.rowmap), B, N, prev_N, mel);
+    KCHK();
+    HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    CHK(launch_sample_body<T>(e, w, p, N, s));
+    HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(state_out, w.y, half * sizeof(float), hipMemcpyDeviceToDevice, s));
     return F5_OK;
 }
 // f5_prepare_sample: one graph per length bucket of [n_min, n_max], captured and instantiated without a launch.  The arena is sized for

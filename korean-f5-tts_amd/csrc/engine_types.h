@@ -389,6 +389,7 @@ struct ItemTables {
     const float* cfg_items;      // [B]
     const int32_t* steps_items;  // [B]
     const ItemTimeRows* rows;
+    const int32_t* span_rows = nullptr;   // f5_sample_span: [B], the row of prev_state an item continues from, or -1
 };
 
 // Entry points of one operand precision T (float: exact-f32 MFMA; bf16_t / f16_t: 16-bit MFMA operands, f32 accumulate).
@@ -407,6 +408,9 @@ template <typename T> struct EngineOps {
     static int sample_items(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
                             int nt, const ItemTables& it, int steps_max, bool any_cfg, const int32_t* lens_host, int B, int N, float* out,
                             float* traj, hipStream_t s, int method);
+    static int sample_span(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y_new,
+                           const float* prev_state, int prev_N, const int64_t* text, int nt, const ItemTables& it, int count, bool any_cfg,
+                           const int32_t* lens_host, int B, int N, float* out, float* state_out, hipStream_t s, int method);
     static int prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max, int steps, float cfg_strength, int method, bool want_traj);
 };
 extern template struct EngineOps<float>;

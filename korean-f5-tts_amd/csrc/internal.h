@@ -14,6 +14,9 @@
 #include "../../include/f5_hip.h"
 
 int f5_fail(int code, const char* fmt, ...);  // records the thread-local message returned by f5_last_error()
+// The rules of a slice's row table (engine.hip; f5_sample_span and f5k_span_stage): rows_host[b] in [-1, prev_B), no previous row named
+// twice, a previous state where a row continues, y_new where one begins.
+int check_span_rows(const char* who, const int32_t* rows_host, int B, const void* prev_state, int prev_B, int prev_N, const void* y_new);
 
 #define HIPCHK(expr)                                                                                         \
     do {                                                                                                     \

@@ -537,6 +537,14 @@ extern "C" int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, 
     launch_mod_gather((hipStream_t)stream, src, idx, dst, rows, nidx, width);
     return glue_done((hipStream_t)stream);
 }
+extern "C" int f5k_span_stage(float* y, const float* prev_state, int32_t prev_B, int32_t prev_N, const float* y_new, const int32_t* rows,
+                              const int32_t* rows_host, int32_t B, int32_t N, int32_t mel, f5_stream stream) {
+    if (!y || !rows || !rows_host || B <= 0 || N <= 0 || mel <= 0 || mel % 4)
+        return fail(F5_EINVAL, "f5k_span_stage: bad arguments (mel %% 4 == 0)");
+    CHK(check_span_rows("f5k_span_stage", rows_host, B, prev_state, prev_B, prev_N, y_new));
+    launch_span_stage((hipStream_t)stream, y, prev_state, y_new, rows, B, N, prev_N, mel);
+    return glue_done((hipStream_t)stream);
+}
 extern "C" int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream) {
     if (!a || !rowmask || !out || rows <= 0 || C <= 0 || C % 4) return fail(F5_EINVAL, "f5k_select_rows: bad arguments (C %% 4 == 0)");
     launch_select_rows((hipStream_t)stream, a, b, rowmask, out, (long)rows, C);

@@ -251,6 +251,48 @@ class Engine:
                                                 _lib.ODE_METHODS[method]), "f5_sample_items")
         return out, traj
 
+    def sample_span(self, cond, cond_mask, y_new, prev_state, rows, text, t_grids, cfg_strengths, lens=None, method="euler"):
+        """Some steps of a sample_items solve (f5_sample_span): t_grids a list of B sub-grids (item b makes len(t_grids[b]) - 1 steps
+        here), rows[b] the row of prev_state [prev_B, prev_N, mel] item b continues from, or -1 for an item that starts from
+        y_new[b] ([B, N, mel]; None when no item starts).  N is cond_mask's ([B, N]).  Returns (out, state), both [B, N, mel]: the
+        raw state is the next slice's prev_state."""
+        if method not in _lib.ODE_METHODS:
+            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
+        B = len(t_grids)
+        rows = [int(r) for r in rows]
+        if len(rows) != B or len(cfg_strengths) != B:
+            raise ValueError(f"sample_span: {len(rows)} rows and {len(cfg_strengths)} cfg strengths for a batch of {B}")
+        N, mel = cond_mask.shape[1], self.mel_dim
+        steps = [len(g) - 1 for g in t_grids]
+        count = max(steps)
+        flat = []
+        for g in t_grids:   # rows of count + 1; the engine ignores what follows an item's own sub-grid
+            flat += [float(v) for v in g] + [0.0] * (count + 1 - len(g))
+        cond_frames = 0 if cond is None else cond.shape[1]
+        if cond is not None:
+            cond = _h2d_async(cond, self.device, torch.float32)
+        if y_new is not None:
+            y_new = _h2d_async(y_new, self.device, torch.float32)
+            if tuple(y_new.shape) != (B, N, mel):
+                raise ValueError(f"sample_span: y_new is {tuple(y_new.shape)}, not {(B, N, mel)}")
+        prev_B = prev_N = 0
+        if prev_state is not None:
+            prev_state = _h2d_async(prev_state, self.device, torch.float32)
+            if prev_state.ndim != 3 or prev_state.shape[2] != mel:
+                raise ValueError(f"sample_span: prev_state is {tuple(prev_state.shape)}, not [prev_B, prev_N, {mel}]")
+            prev_B, prev_N = prev_state.shape[:2]
+        cm = _h2d_async(cond_mask, self.device, torch.uint8)
+        text = _h2d_async(text, self.device, torch.long)
+        out = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
+        state = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.f5_sample_span(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y_new), _ptr(prev_state), prev_B, prev_N,
+                                               _lib.int_array(rows), _ptr(text), text.shape[1], _lib.float_array(flat),
+                                               _lib.int_array(steps), count, _lib.float_array(cfg_strengths), _lib.int_array(lens), B, N,
+                                               _ptr(out), _ptr(state), _stream_ptr(self.device), _lib.ODE_METHODS[method]),
+                       "f5_sample_span")
+        return out, state
+
     # ------------------------------------------------------------------ profiling
     def profile(self, on: bool):
         _lib.check(self.lib.f5_profile_enable(self._h, int(on)), "f5_profile_enable")

@@ -4,7 +4,9 @@ text split so that its first chunk is short, and the audio sent packet by packet
 chunks on the device path -- the voice from a VoiceBank, ragged sample(), decode_ragged, f5_wave_join, f5_wave_deliver -- and
 yields packets at the client's rate and sample format.  `StreamPool` (infer.open_pool) serves many clients at once, which the
 reference's server does not: `pool_tick` puts waiting chunks of different clients into one ragged batch per tick, and one
-f5_wave_emit joins and delivers every touched request's new audio.  The TCP shell and the sound-card code of the server are not here."""
+f5_wave_emit joins and delivers every touched request's new audio; with `slice_steps` a tick is a few steps of the solve
+(CFM.sample_span) and `pool_slice` re-forms the batch between ticks: finished rows leave, waiting chunks join.  The TCP shell and
+the sound-card code of the server are not here."""
 from __future__ import annotations
 
 import torch
@@ -281,6 +283,87 @@ def pool_tick(waiting, batch_frames, max_items, first_alone, cursor):
     return items, cursor
 
 
+def pool_slice(under_way, waiting, batch_frames, max_items, first_alone, cursor):
+    """Which rows run in the next tick of a StreamPool that solves in slices (open_pool(slice_steps=...)): a pure function of the
+    rows under way and the queue.  `under_way` lists the chunks whose solve has begun and not ended, in the order they joined, as
+    (request id, chunk index, frames); `waiting` is pool_tick's list.  Returns (items, cursor): the tick's rows as (request id,
+    chunk index) in row order -- rows under way first, then the chunks that join -- and the cursor for the tick after it.
+
+    The budget is pool_tick's, over both kinds of row alike: an item is taken while (rows + 1) * max(longest, its frames) <=
+    batch_frames (None: no such limit) and rows + 1 <= max_items.  The first item of a tick is always taken.  The tick ends at the
+    first item that does not fit -- nothing behind it is tried, so nobody overtakes it: a row under way that does not fit keeps
+    every later row and every waiting chunk out.
+      * While a first chunk (index 0) waits or is under way and `first_alone` is set, the tick holds first chunks only: those under
+        way in the order they joined, then the waiting ones in submission order; the cursor stays.  Every other row under way is
+        parked: it is not in the tick, keeps its state and its position, and is taken again once no first chunk is left.
+      * Otherwise every row under way in the order it joined, and then the waiting chunks by pool_tick's round-robin: the requests
+        in ascending id from the first id >= cursor, wrapping around, give one chunk each, then their next one, and so on.  Where
+        a waiting item does not fit the tick ends and that request's id is the new cursor, so pool_tick's property holds: of two
+        requests that wait through two round-robin ticks in a row, one never gets rows in both while the other gets none.  When
+        everything waiting was taken, or a row under way did not fit, the cursor stays."""
+    items, longest = [], 0
+
+    def fits(frames):
+        rows = len(items)
+        return rows == 0 or (rows < max_items and (batch_frames is None or (rows + 1) * max(longest, frames) <= batch_frames))
+
+    live = [w for w in waiting if w[2]]
+    firsts = [w for w in live if w[1] == 0]
+    if first_alone and (firsts or any(k == 0 for _, k, _ in under_way)):
+        for rid, k, frames in [(rid, k, f) for rid, k, f in under_way if k == 0] + [(rid, 0, f[0]) for rid, _, f in firsts]:
+            if not fits(frames):
+                break
+            items.append((rid, k))
+            longest = max(longest, frames)
+        return items, cursor
+    for rid, k, frames in under_way:
+        if not fits(frames):
+            return items, cursor
+        items.append((rid, k))
+        longest = max(longest, frames)
+    if not live:
+        return items, cursor
+    start = next((i for i, w in enumerate(live) if w[0] >= cursor), 0)
+    order = live[start:] + live[:start]
+    for depth in range(max(len(w[2]) for w in order)):
+        for rid, k, frames in order:
+            if depth >= len(frames):
+                continue
+            if not fits(frames[depth]):
+                return items, rid
+            items.append((rid, k + depth))
+            longest = max(longest, frames[depth])
+    return items, cursor
+
+
+def span_prev(sources):
+    """The `prev` of a model.sample_span call whose rows come from these places: per row (state tensor, row in it), or (None, -1)
+    for a row that begins.  Returns (state, rows) -- None for the state when every row begins.  Rows that continue from one tensor
+    use it as it is; rows from several tensors (a parked row resumes beside rows of a later tick) are gathered into one, each at
+    the longest tensor's frame count, zero padded: what the engine's staging does with frames a previous state did not have."""
+    tensors = []
+    for t, _ in sources:
+        if t is not None and not any(t is u for u in tensors):
+            tensors.append(t)
+    if len(tensors) <= 1:
+        return (tensors[0] if tensors else None), [row for _, row in sources]
+    frames = max(t.shape[1] for t in tensors)
+    kept = [(t, row) for t, row in sources if t is not None]
+    state = torch.zeros(len(kept), frames, tensors[0].shape[2], device=tensors[0].device, dtype=tensors[0].dtype)
+    for j, (t, row) in enumerate(kept):
+        state[j, :t.shape[1]] = t[row]
+    at = iter(range(len(kept)))
+    return state, [-1 if t is None else next(at) for t, _ in sources]
+
+
+class SliceRow:
+    """A chunk whose solve is under way in a pool that solves in slices: its request and chunk index, the state tensor that holds
+    its row and the row, the steps it has made, and the sampler settings it joined with."""
+
+    def __init__(self, req, k):
+        self.req, self.k, self.state, self.row, self.made, self.kw = req, k, None, -1, 0, dict(req.client.sample_kw)
+
+
 class PoolRequest:
     """One submitted text of a client (client.submit): `id` ascends with submission, `plan` is request_plan's dict, `voice` the
     bank's row it is spoken with, `done` whether its last packet has been handed out (or it was cancelled with nothing under way)."""
@@ -290,6 +373,7 @@ class PoolRequest:
         self.next = 0                       # the first chunk that has not been put into a tick
         self.stop = len(plan["ends"])       # chunks that run at all (cancel lowers it)
         self.flying = 0                     # ticks enqueued whose bytes the host has not cut into packets yet
+        self.under_way = 0                  # chunks whose solve has begun and not ended (a pool that solves in slices)
         self.pieces, self.sent = [], 0      # the chunks' waveforms so far, on the device; samples delivered at the client's rate
         self.done = self.stop == 0
 
@@ -297,7 +381,7 @@ class PoolRequest:
         """Drops the chunks that have not started.  What is under way still arrives; the stream is not finalised, so the last
         `fade` samples of what ran (and the resampler's last taps) are never sent."""
         self.stop = self.next
-        if self.flying == 0:
+        if self.flying == 0 and self.under_way == 0:
             self.done = True
 
 
@@ -380,10 +464,17 @@ class StreamPool:
 
     `step()` runs one tick and returns [(request, [packets])] for the requests it touched ([] when nothing waits); `run()` yields
     (request, packet, out_rate) until nothing waits.  Requests may be submitted between any two ticks.  `log` holds the batches as
-    run: per tick the (request id, chunk index) items in row order."""
+    run: per tick the (request id, chunk index) items in row order.
+
+    slice_steps = k (None: everything above, call for call): a tick is ONE model.sample_span of at most k steps over the rows
+    pool_slice chooses -- the rows under way, whose state stays on the device between ticks, and the waiting chunks that join.
+    The rows whose last step a tick ran, and only these, are decoded, rescaled, emitted and copied as above; a tick that ends no
+    row emits nothing and step() returns [] for it.  While a first chunk waits or is under way (first_alone) the other rows are
+    parked.  `spans` holds, beside `log`, per tick the (first step, steps run) of each row.  stats(): ticks and sample_calls
+    count every slice; decode_calls, emit_launches and copies only the ticks that ended a row."""
 
     def __init__(self, model, vocoder, voices, *, batch_frames, max_items, first_alone, lookahead, nfe_step, cfg_strength,
-                 sway_sampling_coef, seed, text_tokenizer, clip_silence):
+                 sway_sampling_coef, seed, text_tokenizer, clip_silence, slice_steps=None):
         from . import infer as I
 
         I._require_text_tokenizer(model, text_tokenizer)
@@ -394,6 +485,10 @@ class StreamPool:
             raise ValueError(f"open_pool: batch_frames = {batch_frames} (need None or a positive budget)")
         if int(max_items) < 1:
             raise ValueError(f"open_pool: max_items = {max_items} (need at least 1 row per tick)")
+        if slice_steps is not None and (isinstance(slice_steps, bool) or int(slice_steps) != slice_steps or int(slice_steps) < 1):
+            raise ValueError(f"open_pool: slice_steps = {slice_steps} (need None or a whole number of steps, at least 1)")
+        self.slice_steps = None if slice_steps is None else int(slice_steps)
+        self.spans, self._rows = [], []     # slice_steps: per tick the (start, steps run) of each row; the rows under way
         self.model, self.vocoder, self.text_tokenizer = model, vocoder, text_tokenizer
         self.batch_frames, self.max_items = batch_frames, int(max_items)
         self.first_alone, self.lookahead = bool(first_alone), int(lookahead)
@@ -421,14 +516,12 @@ class StreamPool:
         return dict(self._stats)
 
     def idle(self) -> bool:
-        return not self._pending and not any(r.next < r.stop for r in self._requests)
+        return not self._pending and not self._rows and not any(r.next < r.stop for r in self._requests)
 
     # ---- a tick ------------------------------------------------------------------------------------------------------------
     def _enqueue(self):
         """The device work of the next tick, all of it asynchronous: None when nothing waits, else (touched requests with their
         byte spans, pinned host tensor or None, event)."""
-        from . import infer as I
-
         self._requests = [r for r in self._requests if r.next < r.stop or r.flying]
         waiting = [(r.id, r.next, r.plan["ends"][r.next:r.stop]) for r in self._requests if r.next < r.stop]
         # batch_frames=None is a session's: every chunk as its own B = 1 sample()
@@ -449,19 +542,80 @@ class StreamPool:
             sample, kw = self.model.sample_items, {name: [rk[name] for rk in row_kw] for name in self.sample_kw}
         generated, _ = sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
                               duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens), **kw)
+        for r, k in run:
+            assert k == r.next, "a request's chunks run in order"
+            r.next += 1
+        for key in ("ticks", "sample_calls"):
+            self._stats[key] += 1
+        return self._deliver(run, generated, rows)
+
+    def _enqueue_slice(self):
+        """_enqueue for a pool that solves in slices: one model.sample_span of at most slice_steps steps over the rows pool_slice
+        chooses; the rows whose last step it ran, and only these, are delivered.  A tick that ends no row gives ([], None, event)."""
+        self._requests = [r for r in self._requests if r.next < r.stop or r.flying or r.under_way]
+        waiting = [(r.id, r.next, r.plan["ends"][r.next:r.stop]) for r in self._requests if r.next < r.stop]
+        under_way = [(row.req.id, row.k, row.req.plan["ends"][row.k]) for row in self._rows]
+        items, self._cursor = pool_slice(under_way, waiting, self.batch_frames, self.max_items if self.batch_frames is not None else 1,
+                                         self.first_alone, self._cursor)
+        if not items:
+            return None
+        by_id, known = {r.id: r for r in self._requests}, {(row.req.id, row.k): row for row in self._rows}
+        chosen = []
+        for rid, k in items:
+            row = known.get((rid, k))
+            if row is None:                                                 # a waiting chunk joins
+                r = by_id[rid]
+                assert k == r.next, "a request's chunks run in order"
+                r.next += 1
+                r.under_way += 1
+                row = SliceRow(r, k)
+                self._rows.append(row)
+            chosen.append(row)
+        bank, run = self.bank, [(row.req, row.k) for row in chosen]
+        self.log.append(list(items))
+        glens = [bank.frames[r.voice] for r, _ in run]
+        rows = torch.tensor([r.voice for r, _ in run], device=bank.mel.device)
+        state, prev_rows = span_prev([(row.state, row.row) for row in chosen])
+        start = [row.made for row in chosen]
+        res = self.model.sample_span(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
+                                     duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens),
+                                     start=start, count=self.slice_steps, prev=None if state is None else (state, prev_rows),
+                                     **{name: [row.kw[name] for row in chosen] for name in self.sample_kw})
+        self.spans.append([(a, min(self.slice_steps, int(row.kw["steps"]) - a)) for a, row in zip(start, chosen)])
+        for key in ("ticks", "sample_calls"):
+            self._stats[key] += 1
+        ended = []
+        for b, (row, (_, made)) in enumerate(zip(chosen, self.spans[-1])):
+            row.state, row.row, row.made = res.state, b, row.made + made
+            if res.done[b]:
+                ended.append(b)
+                row.req.under_way -= 1
+                self._rows.remove(row)
+        if not ended:
+            return [], None, self._mark()
+        if len(ended) == len(chosen):
+            return self._deliver(run, res.out, rows)
+        pick = torch.tensor(ended, device=bank.mel.device)
+        return self._deliver([run[b] for b in ended], res.out.index_select(0, pick), rows.index_select(0, pick))
+
+    def _deliver(self, run, generated, rows):
+        """The rest of a tick for the rows `run` whose solve has ended, generated[b] the mel of run[b] and rows[b] its voice:
+        decode_ragged, the rescale, wave_emit and the copy.  Returns what _enqueue returns."""
+        from . import infer as I
+
+        bank = self.bank
         wave, wave_lens = self.vocoder.decode_ragged(generated.to(torch.float32).permute(0, 2, 1), ends=[r.plan["ends"][k] for r, k in run],
                                                      starts=[bank.samples[r.voice] // HOP_LENGTH for r, _ in run])
         wave = I.rescale_to_prompt(wave, bank.rms.index_select(0, rows)[:, None], bank.target_rms)
         touched = []
         for b, (r, k) in enumerate(run):
-            assert k == r.next, "a request's chunks run in order"
-            r.next += 1
+            assert k == len(r.pieces), "a request's chunks end in order"
             r.pieces.append(wave[b, :wave_lens[b]])
             if r not in touched:
                 touched.append(r)
         streams = []
         for r in touched:
-            c, last = r.client, r.next >= len(r.plan["ends"])
+            c, last = r.client, len(r.pieces) >= len(r.plan["ends"])      # (len(r.pieces) is r.next unless a later chunk is under way)
             fades = [0] + [c.fade] * (len(r.pieces) - 1)
             total = I.join_plan([int(p.shape[0]) for p in r.pieces], fades)[2]
             settled = total if last else max(total - c.fade, 0)
@@ -477,12 +631,17 @@ class StreamPool:
             host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
             host.copy_(buf[:total], non_blocking=True)
             self._stats["copies"] += 1
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(bank.mel.device))
-        for key in ("ticks", "sample_calls", "decode_calls", "emit_launches"):
+        event = self._mark()
+        for key in ("decode_calls", "emit_launches"):
             self._stats[key] += 1
         spans = [(r, a, st["range"][1] - st["range"][0]) for r, a, st in zip(touched, starts, streams)]
         return spans, host, event
+
+    def _mark(self):
+        """An event behind everything the tick has put on the stream."""
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(self.bank.mel.device))
+        return event
 
     def step(self):
         """One tick: enqueues the device work of up to 1 + lookahead ticks, waits for the oldest one's copy and returns
@@ -493,7 +652,7 @@ class StreamPool:
             return []
         with torch.inference_mode(), torch.cuda.device(self.bank.mel.device):
             while len(self._pending) <= self.lookahead:
-                tick = self._enqueue()
+                tick = self._enqueue() if self.slice_steps is None else self._enqueue_slice()
                 if tick is None:
                     break
                 self._pending.append(tick)
@@ -510,7 +669,7 @@ class StreamPool:
             packets = [samples[j:j + c.chunk_size] for j in range(0, count, c.chunk_size)]
             self._stats["packets"] += len(packets)
             r.flying -= 1
-            if r.flying == 0 and r.next >= r.stop:
+            if r.flying == 0 and r.under_way == 0 and r.next >= r.stop:
                 r.done = True
             out.append((r, packets))
         return out
@@ -527,12 +686,14 @@ class StreamPool:
 
 
 def open_pool(model, vocoder, voices, *, batch_frames, max_items=64, first_alone=True, lookahead=0, nfe_step=32, cfg_strength=2.0,
-              sway_sampling_coef=-1.0, seed=None, text_tokenizer=None, clip_silence=False) -> StreamPool:
+              sway_sampling_coef=-1.0, seed=None, text_tokenizer=None, clip_silence=False, slice_steps=None) -> StreamPool:
     """A pool that serves many streaming clients from one model: voices is a VoiceBank or the dict prepare_voices takes (prepared
     once, here).  batch_frames: the budget of a tick, rows x longest row (None: every chunk as its own B = 1 sample(), as in
     open_stream; the ticks then share only the emit); max_items: rows of a tick at most; first_alone: a waiting first chunk keeps
-    later chunks out of its tick (pool_tick has the rule); lookahead: ticks enqueued ahead of the one the host waits for.  The
+    later chunks out of its tick (pool_tick has the rule); lookahead: ticks enqueued ahead of the one the host waits for;
+    slice_steps: None, or the steps a tick runs at most -- the pool then solves in slices and re-forms the batch between them
+    (StreamPool has the rules).  The
     sampler settings are the pool's defaults: pool.connect may give a client its own.  Refuses what open_stream refuses.  See StreamPool, and pool.connect for a client's side."""
     return StreamPool(model, vocoder, voices, batch_frames=batch_frames, max_items=max_items, first_alone=first_alone,
                       lookahead=lookahead, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                      seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence)
+                      seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence, slice_steps=slice_steps)
