@@ -7,6 +7,8 @@ Training (`forward`, cfm.py:231-302) is out of scope.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -33,6 +35,12 @@ def per_item(name: str, value, batch: int) -> list:
             raise ValueError(f"sample_items: {name} has {len(vals)} entries for a batch of {batch}")
         return vals
     return [value.item() if isinstance(value, torch.Tensor) else value] * batch
+
+
+def item_settings(steps, cfg_strength, sway_sampling_coef, seed, batch: int) -> tuple[list, list, list, list]:
+    """The four sampler settings of sample_items() / sample_span(), each as a list of `batch` entries."""
+    return ([int(v) for v in per_item("steps", steps, batch)], [float(v) for v in per_item("cfg_strength", cfg_strength, batch)],
+            per_item("sway_sampling_coef", sway_sampling_coef, batch), per_item("seed", seed, batch))
 
 
 def is_per_item(*values) -> bool:
@@ -63,6 +71,17 @@ def item_noise(durations: list, seeds: list, mel: int, device="cpu") -> torch.Te
             torch.manual_seed(int(seed))
         y0.append(torch.randn(int(dur), mel, device=device, dtype=torch.float32))
     return pad_sequence(y0, padding_value=0, batch_first=True)
+
+
+class SampleInputs(NamedTuple):
+    """What CFM's three sampler methods make of their shared arguments before anything differs between them."""
+    cond: torch.Tensor        # f32 [B, cond_seq_len, mel] on the model's device
+    text_cpu: torch.Tensor    # long [B, nt], -1 padded
+    cond_mask: torch.Tensor   # bool [B, N] on the host: the prompt frames that are kept (lens, less the edit_mask's spans)
+    duration: torch.Tensor    # long [B] on the host (clamp_durations)
+    N: int
+    batch: int
+    cond_seq_len: int
 
 
 class SpanResult:
@@ -112,10 +131,8 @@ class CFM(nn.Module):
     def state_dict(self, *a, **k):
         return {"transformer." + n: t for n, t in self.transformer.state_dict().items()}
 
-    @torch.no_grad()
-    def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
-               seed: int | None = None, max_duration=65536, vocoder=None, use_epss=True, no_ref_audio=False,
-               duplicate_test=False, t_inter=0.1, edit_mask=None):
+    def _prepare(self, cond, text, duration, lens, max_duration, edit_mask) -> SampleInputs:
+        """The argument handling sample(), sample_items() and sample_span() share (cfm.py:103-147)."""
         self.eval()
         device = self.device
         if cond.ndim == 2:  # raw wave -> mel (cfm.py:106-109)
@@ -138,26 +155,41 @@ class CFM(nn.Module):
             cond_mask = cond_mask & edit_mask.to("cpu")
         duration = clamp_durations(text_cpu, lens, duration, max_duration)
         N = int(duration.amax())
-
-        if duplicate_test:
-            test_cond = F.pad(cond, (0, 0, cond_seq_len, N - 2 * cond_seq_len), value=0.0)
         # cond = F.pad(cond, (0, 0, 0, N - cond_seq_len)) (cfm.py:145) happens inside the engine: the prompt goes down
         # unpadded with its frame count; no_ref_audio (cfm.py:146-147: an all-zero cond) is "zero prompt frames"
         cond_mask = F.pad(cond_mask, (0, N - cond_mask.shape[-1]), value=False)   # (host tensor)
+        return SampleInputs(cond, text_cpu, cond_mask, duration, N, batch, cond_seq_len)
+
+    @property
+    def _noise_device(self):
+        return self.noise_device if self.noise_device == "cpu" else self.device
+
+    def _finish(self, out, vocoder):
+        self.transformer.clear_cache()
+        if exists(vocoder):
+            out = vocoder(out.permute(0, 2, 1))
+        return out
+
+    @torch.no_grad()
+    def sample(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None,
+               seed: int | None = None, max_duration=65536, vocoder=None, use_epss=True, no_ref_audio=False,
+               duplicate_test=False, t_inter=0.1, edit_mask=None):
+        a = self._prepare(cond, text, duration, lens, max_duration, edit_mask)
+        if duplicate_test:
+            test_cond = F.pad(a.cond, (0, 0, a.cond_seq_len, a.N - 2 * a.cond_seq_len), value=0.0)
 
         # noise (cfm.py:196-201): same seed for every sample, drawn per sample at its own length, zero padded
         y0 = []
-        for dur in duration.tolist():
+        for dur in a.duration.tolist():
             if exists(seed):
                 torch.manual_seed(seed)
-            y0.append(torch.randn(dur, self.num_channels, device=self.noise_device if self.noise_device == "cpu" else device,
-                                  dtype=torch.float32))
+            y0.append(torch.randn(dur, self.num_channels, device=self._noise_device, dtype=torch.float32))
         y0 = pad_sequence(y0, padding_value=0, batch_first=True)   # stays where it was drawn; Engine.sample copies it asynchronously
 
         t_start = 0
         if duplicate_test:
             t_start = t_inter
-            y0 = (1 - t_start) * y0.to(device) + t_start * test_cond
+            y0 = (1 - t_start) * y0.to(self.device) + t_start * test_cond
             steps = int(steps * (1 - t_start))
         if t_start == 0 and use_epss:
             t = get_epss_timesteps(steps, device="cpu", dtype=torch.float32)
@@ -167,13 +199,10 @@ class CFM(nn.Module):
             t = t + sway_sampling_coef * (torch.cos(torch.pi / 2 * t) - 1 + t)
 
         eng = self.transformer.engine()
-        out, trajectory = eng.sample(None if no_ref_audio else cond, cond_mask, y0, text_cpu, t.tolist(), cfg_strength,
-                                     lens=duration.tolist() if batch > 1 else None, want_traj=True,
+        out, trajectory = eng.sample(None if no_ref_audio else a.cond, a.cond_mask, y0, a.text_cpu, t.tolist(), cfg_strength,
+                                     lens=a.duration.tolist() if a.batch > 1 else None, want_traj=True,
                                      method=self.odeint_kwargs.get("method", "euler"))
-        self.transformer.clear_cache()
-        if exists(vocoder):
-            out = vocoder(out.permute(0, 2, 1))
-        return out, trajectory
+        return self._finish(out, vocoder), trajectory
 
     @torch.no_grad()
     def sample_items(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None,
@@ -181,45 +210,16 @@ class CFM(nn.Module):
         """sample() with per-item settings: `steps`, `cfg_strength`, `sway_sampling_coef` and `seed` each take one value for the batch or
         a sequence of one value per item (entries of the last two may be None).  One engine call (f5_sample_items) runs the batch for
         max(steps) steps; an item with fewer steps keeps its final state from then on.  Returns (out, trajectory[max(steps) + 1, B, N, mel])."""
-        self.eval()
-        device = self.device
-        if cond.ndim == 2:
-            cond = self.mel_spec(cond.to(device))
-            cond = cond.permute(0, 2, 1)
-            assert cond.shape[-1] == self.num_channels
-        cond = cond.to(device=device, dtype=torch.float32)
-        batch, cond_seq_len = cond.shape[:2]
-        steps_i = [int(v) for v in per_item("steps", steps, batch)]
-        cfg_i = [float(v) for v in per_item("cfg_strength", cfg_strength, batch)]
-        sway_i = per_item("sway_sampling_coef", sway_sampling_coef, batch)
-        seed_i = per_item("seed", seed, batch)
-        if not exists(lens):
-            lens = torch.full((batch,), cond_seq_len, dtype=torch.long)
-        lens = lens.to("cpu", torch.long)
-
-        if isinstance(text, list):
-            text = list_str_to_idx(text, self.vocab_char_map) if exists(self.vocab_char_map) else list_str_to_tensor(text)
-            assert text.shape[0] == batch
-        text_cpu = text.to("cpu", torch.long)
-
-        cond_mask = lens_to_mask(lens)
-        if edit_mask is not None:
-            cond_mask = cond_mask & edit_mask.to("cpu")
-        duration = clamp_durations(text_cpu, lens, duration, max_duration)
-        N = int(duration.amax())
-        cond_mask = F.pad(cond_mask, (0, N - cond_mask.shape[-1]), value=False)
-
-        y0 = item_noise(duration.tolist(), seed_i, self.num_channels, self.noise_device if self.noise_device == "cpu" else device)
+        a = self._prepare(cond, text, duration, lens, max_duration, edit_mask)
+        steps_i, cfg_i, sway_i, seed_i = item_settings(steps, cfg_strength, sway_sampling_coef, seed, a.batch)
+        y0 = item_noise(a.duration.tolist(), seed_i, self.num_channels, self._noise_device)
         grids = item_time_grids(steps_i, sway_i, use_epss)
 
         eng = self.transformer.engine()
-        out, trajectory = eng.sample_items(None if no_ref_audio else cond, cond_mask, y0, text_cpu, [t.tolist() for t in grids], cfg_i,
-                                           lens=duration.tolist() if batch > 1 else None, want_traj=True,
+        out, trajectory = eng.sample_items(None if no_ref_audio else a.cond, a.cond_mask, y0, a.text_cpu, [t.tolist() for t in grids], cfg_i,
+                                           lens=a.duration.tolist() if a.batch > 1 else None, want_traj=True,
                                            method=self.odeint_kwargs.get("method", "euler"))
-        self.transformer.clear_cache()
-        if exists(vocoder):
-            out = vocoder(out.permute(0, 2, 1))
-        return out, trajectory
+        return self._finish(out, vocoder), trajectory
 
     @torch.no_grad()
     def sample_span(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None, start, count,
@@ -231,18 +231,9 @@ class CFM(nn.Module):
         gets item_noise's draw for it alone.  prev=None: every item begins here.  The batch runs at N = max(duration) of the items
         it holds now.  The grids are item_time_grids' grids, sliced.  Returns a SpanResult: `out` (where(cond_mask, cond, state):
         an item's result once it is `done`), `state` [B, N, mel] and `done`, per item whether its last step was run."""
-        self.eval()
-        device = self.device
-        if cond.ndim == 2:
-            cond = self.mel_spec(cond.to(device))
-            cond = cond.permute(0, 2, 1)
-            assert cond.shape[-1] == self.num_channels
-        cond = cond.to(device=device, dtype=torch.float32)
-        batch, cond_seq_len = cond.shape[:2]
-        steps_i = [int(v) for v in per_item("steps", steps, batch)]
-        cfg_i = [float(v) for v in per_item("cfg_strength", cfg_strength, batch)]
-        sway_i = per_item("sway_sampling_coef", sway_sampling_coef, batch)
-        seed_i = per_item("seed", seed, batch)
+        a = self._prepare(cond, text, duration, lens, max_duration, edit_mask)
+        batch, durs = a.batch, a.duration.tolist()
+        steps_i, cfg_i, sway_i, seed_i = item_settings(steps, cfg_strength, sway_sampling_coef, seed, batch)
         count = int(count)
         if count < 1:
             raise ValueError(f"sample_span: count = {count} (a slice runs at least one step)")
@@ -253,23 +244,6 @@ class CFM(nn.Module):
         rows = [int(r) for r in rows]
         if len(rows) != batch:
             raise ValueError(f"sample_span: rows has {len(rows)} entries for a batch of {batch}")
-        if not exists(lens):
-            lens = torch.full((batch,), cond_seq_len, dtype=torch.long)
-        lens = lens.to("cpu", torch.long)
-
-        if isinstance(text, list):
-            text = list_str_to_idx(text, self.vocab_char_map) if exists(self.vocab_char_map) else list_str_to_tensor(text)
-            assert text.shape[0] == batch
-        text_cpu = text.to("cpu", torch.long)
-
-        cond_mask = lens_to_mask(lens)
-        if edit_mask is not None:
-            cond_mask = cond_mask & edit_mask.to("cpu")
-        duration = clamp_durations(text_cpu, lens, duration, max_duration)
-        N = int(duration.amax())
-        cond_mask = F.pad(cond_mask, (0, N - cond_mask.shape[-1]), value=False)
-        durs = duration.tolist()
-
         for b in range(batch):
             if not 0 <= start_i[b] < steps_i[b]:
                 raise ValueError(f"sample_span: item {b}: start = {start_i[b]} outside [0, steps = {steps_i[b]})")
@@ -278,21 +252,20 @@ class CFM(nn.Module):
             if rows[b] >= 0 and (state is None or state.shape[1] < durs[b]):
                 have = "no previous state" if state is None else f"the previous state has {state.shape[1]} frames"
                 raise ValueError(f"sample_span: item {b} continues row {rows[b]} at {durs[b]} frames, but {have}")
-        run = [min(count, n - a) for n, a in zip(steps_i, start_i)]
+        run = [min(count, n - s) for n, s in zip(steps_i, start_i)]
         # the sub-grids: the items' own grids, sliced on the host (nothing is computed again in another arithmetic)
-        grids = [t[a:a + r + 1] for t, a, r in zip(item_time_grids(steps_i, sway_i, use_epss), start_i, run)]
+        grids = [t[s:s + r + 1] for t, s, r in zip(item_time_grids(steps_i, sway_i, use_epss), start_i, run)]
 
         fresh = [b for b in range(batch) if rows[b] < 0]
         y_new = None
         if fresh:
-            noise_device = self.noise_device if self.noise_device == "cpu" else device
-            drawn = item_noise([durs[b] for b in fresh], [seed_i[b] for b in fresh], self.num_channels, noise_device)
-            y_new = torch.zeros(batch, N, self.num_channels, device=drawn.device, dtype=torch.float32)
+            drawn = item_noise([durs[b] for b in fresh], [seed_i[b] for b in fresh], self.num_channels, self._noise_device)
+            y_new = torch.zeros(batch, a.N, self.num_channels, device=drawn.device, dtype=torch.float32)
             y_new[fresh, :drawn.shape[1]] = drawn
 
         eng = self.transformer.engine()
-        out, new_state = eng.sample_span(None if no_ref_audio else cond, cond_mask, y_new, state, rows, text_cpu,
+        out, new_state = eng.sample_span(None if no_ref_audio else a.cond, a.cond_mask, y_new, state, rows, a.text_cpu,
                                          [t.tolist() for t in grids], cfg_i, lens=durs if batch > 1 else None,
                                          method=self.odeint_kwargs.get("method", "euler"))
         self.transformer.clear_cache()
-        return SpanResult(out, new_state, [a + r == n for a, r, n in zip(start_i, run, steps_i)])
+        return SpanResult(out, new_state, [s + r == n for s, r, n in zip(start_i, run, steps_i)])

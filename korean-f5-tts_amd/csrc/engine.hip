@@ -218,25 +218,39 @@ static int chunk_utts(const f5_engine* e, int B, int N, bool use_cfg, const int3
     }
     return (int)((B + best_k - 1) / best_k);
 }
-SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk, int nt, int steps, int method,
-                       float cfg_strength, bool want_traj, int n_true, bool items) {
+PlanOptions plan_options(const SampleCall& c) {
+    PlanOptions o;
+    o.nt = c.nt; o.steps = c.steps; o.method = c.method; o.cfg_strength = c.cfg_strength;
+    o.want_traj = c.traj != nullptr;
+    if (c.per_item) {
+        o.items = true;
+        o.U = (int)c.items.rows->times.size();
+        bool any_cfg = false;
+        for (int b = 0; b < c.B; ++b) any_cfg = any_cfg || !(c.items.cfg_items[b] < 1e-5f);
+        o.cfg_strength = any_cfg ? 1.f : 0.f;
+    }
+    return o;
+}
+SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, const PlanOptions& o) {
     SamplePlan p;
-    p.items = items;
+    const int n_true = o.n_true;
+    p.items = o.items;
+    p.U = o.U;
     // a length-bucket plan: every utterance has n_true frames; the chunking follows the bucket's ceiling alone (it is part of the key)
     const std::vector<int32_t> own(n_true > 0 ? B : 0, n_true), cap(n_true > 0 ? B : 0, N);
     if (n_true > 0) lens_host = own.data();
     p.n_true = n_true;
-    p.B = B; p.N = N; p.nt = nt; p.steps = steps; p.method = method; p.cfg_strength = cfg_strength;
-    p.use_cfg = !(cfg_strength < 1e-5f);
+    p.B = B; p.N = N; p.nt = o.nt; p.steps = o.steps; p.method = o.method; p.cfg_strength = o.cfg_strength;
+    p.use_cfg = !(o.cfg_strength < 1e-5f);
     p.has_lens = lens_host != nullptr;
-    p.want_traj = want_traj;
+    p.want_traj = o.want_traj;
     p.halves = p.use_cfg ? 2 : 1;
-    p.evals = method == F5_ODE_MIDPOINT ? 2 : 1;
+    p.evals = o.method == F5_ODE_MIDPOINT ? 2 : 1;
     const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;
     // (a per-item call runs the rectangular body on one stream chain: batch row = row / N is what finds a row's time vectors)
-    p.pack = !items && (n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg));
-    p.split = !items && e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
-    p.chunk = chunk ? chunk : chunk_utts(e, B, N, p.use_cfg, n_true > 0 ? cap.data() : p.pack ? lens_host : nullptr);
+    p.pack = !o.items && (n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg));
+    p.split = !o.items && e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
+    p.chunk = o.chunk ? o.chunk : chunk_utts(e, B, N, p.use_cfg, n_true > 0 ? cap.data() : p.pack ? lens_host : nullptr);
     for (int u0 = 0; u0 < B; u0 += p.chunk) {
         SamplePlan::Chunk k{(int)p.chunks.size(), u0, std::min(p.chunk, B - u0), 0, 0};
         for (int i = 0; lens_host && i < k.bc; ++i) {
@@ -332,16 +346,16 @@ extern "C" int f5k_item_time_rows(const float* t_items, const int32_t* steps_ite
     *U = (int32_t)r.times.size();
     return F5_OK;
 }
-static int check_ready(f5_engine* e, int B, int N) {
-    if (!e) return fail(F5_EINVAL, "null engine");
-    if (!e->finalized) return fail(F5_ESTATE, "f5_finalize has not been called");
-    if (B <= 0 || N <= 0) return fail(F5_EINVAL, "B and N must be positive");
-    if (N + 1 > e->cfg.max_pos) return fail(F5_EINVAL, "N=%d exceeds the rotary table (%d rows)", N, e->cfg.max_pos);
+static int check_ready(const char* who, f5_engine* e, int B, int N) {
+    if (!e) return fail(F5_EINVAL, "%s: null engine", who);
+    if (!e->finalized) return fail(F5_ESTATE, "%s: f5_finalize has not been called", who);
+    if (B <= 0 || N <= 0) return fail(F5_EINVAL, "%s: B and N must be positive", who);
+    if (N + 1 > e->cfg.max_pos) return fail(F5_EINVAL, "%s: N=%d exceeds the rotary table (%d rows)", who, N, e->cfg.max_pos);
     return F5_OK;
 }
 extern "C" int f5_text_embed(f5_engine* e, const int64_t* text, int32_t B, int32_t nt, const int32_t* lens_host,
                              int32_t N, int32_t drop_text, float* out, f5_stream stream) {
-    CHK(check_ready(e, B, N));
+    CHK(check_ready("f5_text_embed", e, B, N));
     if (!text || !out || nt <= 0) return fail(F5_EINVAL, "f5_text_embed: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     return F5_OPS(e, text_embed(e, text, B, nt, lens_host, N, drop_text, out, s));
@@ -349,57 +363,10 @@ extern "C" int f5_text_embed(f5_engine* e, const int64_t* text, int32_t B, int32
 extern "C" int f5_dit_forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int32_t nt,
                               const float* time_host, const int32_t* lens_host, int32_t B, int32_t N, int32_t cfg_infer,
                               int32_t drop_audio_cond, int32_t drop_text, float* out, f5_stream stream) {
-    CHK(check_ready(e, B, N));
+    CHK(check_ready("f5_dit_forward", e, B, N));
     if (!x || !cond || !text || !time_host || !out || nt <= 0) return fail(F5_EINVAL, "f5_dit_forward: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     return F5_OPS(e, forward(e, x, cond, text, nt, time_host, lens_host, B, N, cfg_infer, drop_audio_cond, drop_text, out, s));
-}
-extern "C" int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
-                             const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
-                             const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream,
-                             int32_t method) {
-    if (method != F5_ODE_EULER && method != F5_ODE_MIDPOINT)
-        return fail(F5_EINVAL, "f5_sample_ode: unknown ODE method %d (F5_ODE_EULER = 0, F5_ODE_MIDPOINT = 1)", method);
-    CHK(check_ready(e, B, N));
-    if ((!cond && cond_frames > 0) || !cond_mask || !y0 || !text || !t_host || !out || nt <= 0 || steps <= 0 || cond_frames < 0 ||
-        cond_frames > N)
-        return fail(F5_EINVAL, "f5_sample: bad arguments");
-    if (B > 1 && !lens_host) return fail(F5_EINVAL, "f5_sample: lens required when B > 1 (cfm.py:155-158)");
-    if (lens_host)
-        for (int i = 0; i < B; ++i)
-            if (lens_host[i] <= 0 || lens_host[i] > N) return fail(F5_EINVAL, "lens[%d]=%d out of (0, N]", i, lens_host[i]);
-    hipStream_t s = (hipStream_t)stream;
-    e->prof.clear();
-    return F5_OPS(e, sample(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj, s,
-                            method));
-}
-extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
-                         const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
-                         const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream) {
-    return f5_sample_ode(e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj,
-                         stream, F5_ODE_EULER);
-}
-extern "C" int f5_sample_items(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
-                               const int64_t* text, int32_t nt, const float* t_items, const int32_t* steps_items, int32_t steps_max,
-                               const float* cfg_items, const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj,
-                               f5_stream stream, int32_t method) {
-    // (the table rules first: they need no engine state)
-    if (!cfg_items) return fail(F5_EINVAL, "f5_sample_items: bad arguments");
-    CHK(check_items("f5_sample_items", t_items, steps_items, steps_max, cfg_items, B, method));
-    CHK(check_ready(e, B, N));
-    if ((!cond && cond_frames > 0) || !cond_mask || !y0 || !text || !out || nt <= 0 || cond_frames < 0 || cond_frames > N)
-        return fail(F5_EINVAL, "f5_sample_items: bad arguments");
-    if (B > 1 && !lens_host) return fail(F5_EINVAL, "f5_sample_items: lens required when B > 1 (cfm.py:155-158)");
-    if (lens_host)
-        for (int i = 0; i < B; ++i)
-            if (lens_host[i] <= 0 || lens_host[i] > N) return fail(F5_EINVAL, "f5_sample_items: lens[%d]=%d out of (0, N]", i, lens_host[i]);
-    bool any_cfg = false;
-    for (int b = 0; b < B; ++b) any_cfg = any_cfg || !(cfg_items[b] < 1e-5f);
-    const ItemTimeRows rows = item_time_rows(t_items, steps_items, steps_max, B, method);
-    const ItemTables it{t_items, cfg_items, steps_items, &rows};
-    e->prof.clear();
-    return F5_OPS(e, sample_items(e, cond, cond_frames, cond_mask, y0, text, nt, it, steps_max, any_cfg, lens_host, B, N, out, traj,
-                                  (hipStream_t)stream, method));
 }
 // the rules of a slice's row table (f5_sample_span, f5k_span_stage); messages name the item
 int check_span_rows(const char* who, const int32_t* rows_host, int B, const void* prev_state, int prev_B, int prev_N, const void* y_new) {
@@ -420,30 +387,85 @@ int check_span_rows(const char* who, const int32_t* rows_host, int B, const void
     }
     return F5_OK;
 }
+// The argument rules of a sampler call; every message begins with the entry point's name.  First what needs no engine (the method, the
+// per-item tables, a slice's rows), then the engine, then pointers and lengths.
+static int check_sample_call(f5_engine* e, const SampleCall& c) {
+    if (c.per_item) {
+        if (c.span && c.steps < 1) return fail(F5_EINVAL, "%s: count = %d (a slice runs at least one step)", c.who, c.steps);
+        if (!c.items.cfg_items) return fail(F5_EINVAL, "%s: bad arguments", c.who);
+        CHK(check_items(c.who, c.items.t_items, c.items.steps_items, c.steps, c.items.cfg_items, c.B, c.method));
+    } else if (c.method != F5_ODE_EULER && c.method != F5_ODE_MIDPOINT)
+        return fail(F5_EINVAL, "%s: unknown ODE method %d (F5_ODE_EULER = 0, F5_ODE_MIDPOINT = 1)", c.who, c.method);
+    if (c.span) CHK(check_span_rows(c.who, c.rows_host, c.B, c.prev_state, c.prev_B, c.prev_N, c.y_new));
+    CHK(check_ready(c.who, e, c.B, c.N));
+    const bool times_ok = c.per_item || (c.t_host && c.steps > 0);
+    const bool ends_ok = c.span ? c.state_out != nullptr : c.y0 != nullptr;   // (a slice's start state: check_span_rows; a trajectory may be NULL)
+    if ((!c.cond && c.cond_frames > 0) || !c.cond_mask || !c.text || !c.out || !times_ok || !ends_ok || c.nt <= 0 || c.cond_frames < 0 ||
+        c.cond_frames > c.N)
+        return fail(F5_EINVAL, "%s: bad arguments", c.who);
+    if (c.B > 1 && !c.lens_host) return fail(F5_EINVAL, "%s: lens required when B > 1 (cfm.py:155-158)", c.who);
+    for (int i = 0; c.lens_host && i < c.B; ++i)
+        if (c.lens_host[i] <= 0 || c.lens_host[i] > c.N) return fail(F5_EINVAL, "%s: lens[%d]=%d out of (0, N]", c.who, i, c.lens_host[i]);
+    return F5_OK;
+}
+static int run_sample_call(f5_engine* e, SampleCall& c) {
+    CHK(check_sample_call(e, c));
+    ItemTimeRows rows;
+    if (c.per_item) {
+        rows = item_time_rows(c.items.t_items, c.items.steps_items, c.steps, c.B, c.method);
+        c.items.rows = &rows;
+    }
+    e->prof.clear();
+    return F5_OPS(e, run_sample(e, c));
+}
+static void per_item_times(SampleCall& c, const float* t_items, const int32_t* steps_items, int steps_max, const float* cfg_items) {
+    c.per_item = true;
+    c.items.t_items = t_items; c.items.steps_items = steps_items; c.items.cfg_items = cfg_items;
+    c.steps = steps_max;
+}
+static int sample_uniform(const char* who, f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0,
+                          const int64_t* text, int nt, const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B,
+                          int N, float* out, float* traj, f5_stream stream, int method) {
+    SampleCall c{who, cond, cond_frames, cond_mask, text, nt, lens_host, B, N, out, (hipStream_t)stream, method};
+    c.t_host = t_host; c.steps = steps; c.cfg_strength = cfg_strength;
+    c.y0 = y0;
+    c.traj = traj;
+    return run_sample_call(e, c);
+}
+extern "C" int f5_sample_ode(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                             const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
+                             const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream,
+                             int32_t method) {
+    return sample_uniform("f5_sample_ode", e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out,
+                          traj, stream, method);
+}
+extern "C" int f5_sample(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                         const int64_t* text, int32_t nt, const float* t_host, int32_t steps, float cfg_strength,
+                         const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj, f5_stream stream) {
+    return sample_uniform("f5_sample", e, cond, cond_frames, cond_mask, y0, text, nt, t_host, steps, cfg_strength, lens_host, B, N, out, traj,
+                          stream, F5_ODE_EULER);
+}
+extern "C" int f5_sample_items(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y0,
+                               const int64_t* text, int32_t nt, const float* t_items, const int32_t* steps_items, int32_t steps_max,
+                               const float* cfg_items, const int32_t* lens_host, int32_t B, int32_t N, float* out, float* traj,
+                               f5_stream stream, int32_t method) {
+    SampleCall c{"f5_sample_items", cond, cond_frames, cond_mask, text, nt, lens_host, B, N, out, (hipStream_t)stream, method};
+    per_item_times(c, t_items, steps_items, steps_max, cfg_items);
+    c.y0 = y0;
+    c.traj = traj;
+    return run_sample_call(e, c);
+}
 extern "C" int f5_sample_span(f5_engine* e, const float* cond, int32_t cond_frames, const uint8_t* cond_mask, const float* y_new,
                               const float* prev_state, int32_t prev_B, int32_t prev_N, const int32_t* rows_host, const int64_t* text,
                               int32_t nt, const float* t_items, const int32_t* steps_items, int32_t count, const float* cfg_items,
                               const int32_t* lens_host, int32_t B, int32_t N, float* out, float* state_out, f5_stream stream,
                               int32_t method) {
-    // (the table rules first: they need no engine state)
-    if (count < 1) return fail(F5_EINVAL, "f5_sample_span: count = %d (a slice runs at least one step)", count);
-    if (!cfg_items) return fail(F5_EINVAL, "f5_sample_span: bad arguments");
-    CHK(check_items("f5_sample_span", t_items, steps_items, count, cfg_items, B, method));
-    CHK(check_span_rows("f5_sample_span", rows_host, B, prev_state, prev_B, prev_N, y_new));
-    CHK(check_ready(e, B, N));
-    if ((!cond && cond_frames > 0) || !cond_mask || !text || !out || !state_out || nt <= 0 || cond_frames < 0 || cond_frames > N)
-        return fail(F5_EINVAL, "f5_sample_span: bad arguments");
-    if (B > 1 && !lens_host) return fail(F5_EINVAL, "f5_sample_span: lens required when B > 1 (cfm.py:155-158)");
-    if (lens_host)
-        for (int i = 0; i < B; ++i)
-            if (lens_host[i] <= 0 || lens_host[i] > N) return fail(F5_EINVAL, "f5_sample_span: lens[%d]=%d out of (0, N]", i, lens_host[i]);
-    bool any_cfg = false;
-    for (int b = 0; b < B; ++b) any_cfg = any_cfg || !(cfg_items[b] < 1e-5f);
-    const ItemTimeRows rows = item_time_rows(t_items, steps_items, count, B, method);
-    const ItemTables it{t_items, cfg_items, steps_items, &rows, rows_host};
-    e->prof.clear();
-    return F5_OPS(e, sample_span(e, cond, cond_frames, cond_mask, y_new, prev_state, prev_N, text, nt, it, count, any_cfg, lens_host, B, N, out,
-                                 state_out, (hipStream_t)stream, method));
+    SampleCall c{"f5_sample_span", cond, cond_frames, cond_mask, text, nt, lens_host, B, N, out, (hipStream_t)stream, method};
+    per_item_times(c, t_items, steps_items, count, cfg_items);
+    c.span = true;
+    c.y_new = y_new; c.prev_state = prev_state; c.prev_B = prev_B; c.prev_N = prev_N; c.rows_host = rows_host;
+    c.state_out = state_out;
+    return run_sample_call(e, c);
 }
 
 // ------------------------------------------------------------------------------------- length buckets

@@ -769,11 +769,13 @@ static int run_backbone_rows(f5_engine* e, Work<T>& w, const float* y, const flo
         return run_dit_forward<T>(e, w, y, cond, B, Bp, N, rows, e->modN, lens_dev, 0, text_first, text_second, s);
     return run_unett_forward<T>(e, w, y, cond, B, Bp, N, rows, e->cfg.dim, lens_dev, 0, text_first, text_second, s);
 }
-// uploads the call's small tables through pinned staging: nT times to w.tdev and, where lengths are given, the plan's lens and
-// row_start tables (SamplePlan::Chunk) and lens_plain; for a per-item call (it non-null) the grids, guidance, step counts and time-row indices
+// uploads a call's small tables through pinned staging: nT times to w.tdev and, where lengths are given, the plan's lens and
+// row_start tables (SamplePlan::Chunk) and lens_plain; for a per-item sampler call the grids, guidance, step counts and time-row
+// indices, and a slice's row table.  call: the sampler call, or null (text_embed, forward: times and lengths are all there is)
 template <typename T>
-static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, const int32_t* lens_host, const SamplePlan& p,
-                        hipStream_t s, const ItemTables* it = nullptr) {
+static int upload_small(f5_engine* e, Work<T>& w, const SamplePlan& p, const float* t_host, int nT, const int32_t* lens_host,
+                        const SampleCall* call, hipStream_t s) {
+    const ItemTables* it = call && call->per_item ? &call->items : nullptr;
     const int B = p.B;
     const size_t n_grid = it ? (size_t)B * (p.steps + 1) : 0, n_idx = it ? it->rows->idx.size() : 0;
     const size_t small_bytes = (size_t)nT * 4 + (size_t)3 * B * 4 + ((size_t)3 * B + 16) * 4 + 64;
@@ -819,9 +821,9 @@ static int upload_small(f5_engine* e, Work<T>& w, const float* t_host, int nT, c
         HIPCHK(hipMemcpyAsync(w.it_cfg, ch, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.it_steps, sh, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.it_idx, ih, n_idx * 4, hipMemcpyHostToDevice, s));
-        if (it->span_rows) {   // f5_sample_span: the staging kernel's row table, in the rowmap (a per-item body is never packed)
+        if (call->span) {   // the staging kernel's row table, in the rowmap (a per-item body is never packed)
             int* rh = ih + n_idx;
-            memcpy(rh, it->span_rows, (size_t)B * 4);
+            memcpy(rh, call->rows_host, (size_t)B * 4);
             HIPCHK(hipMemcpyAsync(w.rowmap, rh, (size_t)B * 4, hipMemcpyHostToDevice, s));
         }
     }
@@ -833,7 +835,7 @@ int EngineOps<T>::text_embed(f5_engine* e, const int64_t* text, int B, int nt, c
     CHK(ensure_arena(e, B, N, 1));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
-    CHK(upload_small<T>(e, w, nullptr, 0, lens_host, plan_sample(e, B, N, lens_host, B), s));
+    CHK(upload_small<T>(e, w, plan_sample(e, B, N, lens_host, PlanOptions::whole_batch(B)), nullptr, 0, lens_host, nullptr, s));
     const bool per_sample = lens_host && e->cfg.backbone == F5_BACKBONE_DIT;  // unett.py embeds at the padded length
     return run_text_embed<T>(e, w, text, B, nt, per_sample ? w.lens_plain : nullptr, N, drop_text, out, s);
 }
@@ -847,7 +849,7 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     std::vector<float> tt(Bp);
     for (int i = 0; i < Bp; ++i) tt[i] = time_host[i % B];
-    CHK(upload_small<T>(e, w, tt.data(), Bp, lens_host, plan_sample(e, B, N, lens_host, B), s));
+    CHK(upload_small<T>(e, w, plan_sample(e, B, N, lens_host, PlanOptions::whole_batch(B)), tt.data(), Bp, lens_host, nullptr, s));
     const int* lens_dev = lens_host ? w.lens : nullptr;
     CHK(run_time_path<T>(e, w, Bp, s));
     // UNetT embeds text at the padded length for every sample (unett.py:196-215), DiT at each sample's own length
@@ -1065,59 +1067,6 @@ template <typename T> static int launch_sample_body(f5_engine* e, Work<T>& w, co
     if (!exec) e->gc.mark_warm(base_key);
     return F5_OK;
 }
-// sample(): plan, stage the inputs into the arena, key, replay / capture / eager, copy the outputs
-template <typename T>
-int EngineOps<T>::sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
-                         const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
-                         float* traj, hipStream_t s, int method) {
-    reserve_text(e, nt);
-    int Nc = N;   // frames per utterance in the arena: N, or the ceiling of N's length bucket
-    const bool bucket = bucket_eligible<T>(e, lens_host, B, N, &Nc);
-    const SamplePlan p = plan_sample(e, B, Nc, lens_host, 0, bucket ? e->res_nt : nt, steps, method, cfg_strength, traj != nullptr, bucket ? N : 0);
-    const int mel = e->cfg.mel_dim;
-    const long half = (long)B * Nc * mel;
-    CHK(ensure_arena(e, B, Nc, steps));
-    Work<T> w;
-    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
-    // ---- inputs -> arena (eager, on the caller's stream)
-    const std::vector<float> tt = time_table(t_host, steps, method);
-    const std::vector<int32_t> own(bucket ? B : 0, N);
-    CHK(upload_small<T>(e, w, tt.data(), (int)tt.size(), bucket ? own.data() : lens_host, p, s));
-    const size_t row_in = (size_t)N * mel * sizeof(float), row_arena = (size_t)Nc * mel * sizeof(float);   // one utterance, caller's / arena's
-    if (cond_frames < Nc) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
-    if (cond_frames > 0)
-        HIPCHK(hipMemcpy2DAsync(w.in_cond, row_arena, cond, (size_t)cond_frames * mel * sizeof(float),
-                                (size_t)cond_frames * mel * sizeof(float), B, hipMemcpyDeviceToDevice, s));
-    if (!bucket) {
-        HIPCHK(hipMemcpyAsync(w.y, y0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    } else {
-        // The frames N .. Nc-1 of state and mask are written as zero (the two select_rows launches of the body read them; nothing reads
-        // what they produce), and the text sits in rows of res_nt tokens filled with -1: the filler, which is what a shorter text is
-        // padded with anyway (dit.py:87-89), so the body reads the same tokens whatever the call's own text length.
-        if (N < Nc) {
-            HIPCHK(hipMemsetAsync(w.y, 0, half * sizeof(float), s));
-            HIPCHK(hipMemsetAsync(w.in_mask, 0, (size_t)B * Nc, s));
-        }
-        HIPCHK(hipMemcpy2DAsync(w.y, row_arena, y0, row_in, row_in, B, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpy2DAsync(w.in_mask, (size_t)Nc, cond_mask, (size_t)N, (size_t)N, B, hipMemcpyDeviceToDevice, s));
-        if (nt < p.nt) HIPCHK(hipMemsetAsync(w.in_text, 0xFF, (size_t)B * p.nt * sizeof(int64_t), s));
-        HIPCHK(hipMemcpy2DAsync(w.in_text, (size_t)p.nt * sizeof(int64_t), text, (size_t)nt * sizeof(int64_t), (size_t)nt * sizeof(int64_t), B,
-                                hipMemcpyDeviceToDevice, s));
-    }
-    CHK(launch_sample_body<T>(e, w, p, N, s));
-    // ---- outputs -> caller (a bucket's rows N .. Nc-1 stay behind)
-    if (!bucket) {
-        HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    } else {
-        HIPCHK(hipMemcpy2DAsync(out, row_in, w.out_buf, row_arena, row_in, B, hipMemcpyDeviceToDevice, s));
-        if (traj)
-            HIPCHK(hipMemcpy2DAsync(traj, row_in, w.traj_buf, row_arena, row_in, (size_t)(steps + 1) * B, hipMemcpyDeviceToDevice, s));
-    }
-    return F5_OK;
-}
 // a per-item call's buffers and its time rows (one per distinct evaluation time) are part of the arena plan: a first call, or more rows, moves the carve offsets
 static void reserve_items(f5_engine* e, int U) {
     if (!e->res_items || U > e->res_U) {
@@ -1127,62 +1076,64 @@ static void reserve_items(f5_engine* e, int U) {
         e->uc_N = -1;
     }
 }
-// f5_sample_items: sample() with per-item grids, guidance and step counts in device tables; the rectangular body, exact N, no bucket
-template <typename T>
-int EngineOps<T>::sample_items(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
-                               int nt, const ItemTables& it, int steps_max, bool any_cfg, const int32_t* lens_host, int B, int N, float* out,
-                               float* traj, hipStream_t s, int method) {
-    reserve_text(e, nt);
-    SamplePlan p = plan_sample(e, B, N, lens_host, 0, nt, steps_max, method, any_cfg ? 1.f : 0.f, traj != nullptr, 0, true);
-    p.U = (int)it.rows->times.size();
-    reserve_items(e, p.U);
-    const int mel = e->cfg.mel_dim;
-    const long half = (long)B * N * mel;
-    CHK(ensure_arena(e, B, N, steps_max));
-    Work<T> w;
-    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
-    CHK(upload_small<T>(e, w, it.rows->times.data(), p.U, lens_host, p, s, &it));
-    if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));
-    if (cond_frames > 0)
-        HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
-                                (size_t)cond_frames * mel * sizeof(float), B, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.y, y0, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    CHK(launch_sample_body<T>(e, w, p, N, s));
-    HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (traj) HIPCHK(hipMemcpyAsync(traj, w.traj_buf, (size_t)(steps_max + 1) * half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return F5_OK;
+// `rows` rows of `width` bytes from pitch `spitch` to pitch `dpitch`, device to device: one flat copy where both pitches are the width
+static hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipStream_t s) {
+    if (dpitch == width && spitch == width) return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDeviceToDevice, s);
+    return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice, s);
 }
-// f5_sample_span: steps of a per-item solve as a call of their own.  sample_items' plan and body on the sub-grids of the slice; the start
-// state is staged from the caller's previous state tensor (another N, another row order) or, for a row that begins here, from y_new,
-// by one span_stage_kernel launch straight into w.y; the raw state comes back beside `out`.  The staging is eager, so the body's key
-// is sample_items' key without a trajectory: one captured graph serves every slice of a shape.
-template <typename T>
-int EngineOps<T>::sample_span(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y_new,
-                              const float* prev_state, int prev_N, const int64_t* text, int nt, const ItemTables& it, int count, bool any_cfg,
-                              const int32_t* lens_host, int B, int N, float* out, float* state_out, hipStream_t s, int method) {
+// Every sampler call (f5_sample, f5_sample_ode, f5_sample_items, f5_sample_span): plan, stage the inputs into the arena, key, replay /
+// capture / eager (launch_sample_body), copy the outputs.  The staging is eager, on the caller's stream, so none of it is part of the
+// body's key: one captured graph serves every setting of a per-item shape, and every slice of it.
+template <typename T> int EngineOps<T>::run_sample(f5_engine* e, const SampleCall& c) {
+    const int B = c.B, N = c.N, nt = c.nt, mel = e->cfg.mel_dim;
+    hipStream_t s = c.stream;
     reserve_text(e, nt);
-    SamplePlan p = plan_sample(e, B, N, lens_host, 0, nt, count, method, any_cfg ? 1.f : 0.f, false, 0, true);
-    p.U = (int)it.rows->times.size();
-    reserve_items(e, p.U);
-    const int mel = e->cfg.mel_dim;
-    const long half = (long)B * N * mel;
-    CHK(ensure_arena(e, B, N, count));
+    // ---- (a) the plan: per-item tables on the rectangular body at the exact N, or one grid for the batch, in N's length bucket if it takes one
+    int Nc = N;   // frames per utterance in the arena: N, or the ceiling of N's length bucket
+    const bool bucket = !c.per_item && bucket_eligible<T>(e, c.lens_host, B, N, &Nc);
+    PlanOptions o = plan_options(c);
+    if (bucket) {
+        o.nt = e->res_nt;
+        o.n_true = N;
+    }
+    const SamplePlan p = plan_sample(e, B, Nc, c.lens_host, o);
+    if (c.per_item) reserve_items(e, p.U);
+    CHK(ensure_arena(e, B, Nc, c.steps));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
-    CHK(upload_small<T>(e, w, it.rows->times.data(), p.U, lens_host, p, s, &it));
-    if (cond_frames < N) HIPCHK(hipMemsetAsync(w.in_cond, 0, half * sizeof(float), s));
-    if (cond_frames > 0)
-        HIPCHK(hipMemcpy2DAsync(w.in_cond, (size_t)N * mel * sizeof(float), cond, (size_t)cond_frames * mel * sizeof(float),
-                                (size_t)cond_frames * mel * sizeof(float), B, hipMemcpyDeviceToDevice, s));
-    launch_span_stage(s, w.y, prev_state, y_new, reinterpret_cast<const int*>(w.rowmap), B, N, prev_N, mel);
-    KCHK();
-    HIPCHK(hipMemcpyAsync(w.in_mask, cond_mask, (size_t)B * N, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(w.in_text, text, (size_t)B * nt * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    // ---- inputs -> arena
+    const std::vector<float> grid = c.per_item ? std::vector<float>() : time_table(c.t_host, c.steps, c.method);
+    const std::vector<float>& times = c.per_item ? c.items.rows->times : grid;
+    const std::vector<int32_t> own(bucket ? B : 0, N);
+    CHK(upload_small<T>(e, w, p, times.data(), (int)times.size(), bucket ? own.data() : c.lens_host, &c, s));
+    const size_t frame = (size_t)mel * sizeof(float), row_in = N * frame, row_arena = Nc * frame;   // one utterance, caller's / arena's
+    const size_t half = (size_t)B * row_arena;
+    if (c.cond_frames < Nc) HIPCHK(hipMemsetAsync(w.in_cond, 0, half, s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
+    if (c.cond_frames > 0)   // (the prompt's own pitch is its frame count)
+        HIPCHK(hipMemcpy2DAsync(w.in_cond, row_arena, c.cond, c.cond_frames * frame, c.cond_frames * frame, B, hipMemcpyDeviceToDevice, s));
+    // A bucket's frames N .. Nc-1 of state and mask are written as zero (the two select_rows launches of the body read them; nothing reads
+    // what they produce), and its text sits in rows of res_nt tokens filled with -1: the filler, which is what a shorter text is
+    // padded with anyway (dit.py:87-89), so the body reads the same tokens whatever the call's own text length.
+    if (N < Nc) {
+        HIPCHK(hipMemsetAsync(w.y, 0, half, s));
+        HIPCHK(hipMemsetAsync(w.in_mask, 0, (size_t)B * Nc, s));
+    }
+    // ---- (b) the start state: the caller's y0, or the rows of a previous state (another N, another row order) and of y_new, by one launch
+    if (c.span) {
+        launch_span_stage(s, w.y, c.prev_state, c.y_new, reinterpret_cast<const int*>(w.rowmap), B, N, c.prev_N, mel);
+        KCHK();
+    } else
+        HIPCHK(copy_rows(w.y, row_arena, c.y0, row_in, row_in, B, s));
+    HIPCHK(copy_rows(w.in_mask, (size_t)Nc, c.cond_mask, (size_t)N, (size_t)N, B, s));
+    if (nt < p.nt) HIPCHK(hipMemsetAsync(w.in_text, 0xFF, (size_t)B * p.nt * sizeof(int64_t), s));
+    HIPCHK(copy_rows(w.in_text, p.nt * sizeof(int64_t), c.text, nt * sizeof(int64_t), nt * sizeof(int64_t), B, s));
     CHK(launch_sample_body<T>(e, w, p, N, s));
-    HIPCHK(hipMemcpyAsync(out, w.out_buf, half * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(state_out, w.y, half * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // ---- outputs -> caller (a bucket's rows N .. Nc-1 stay behind)
+    HIPCHK(copy_rows(c.out, row_in, w.out_buf, row_arena, row_in, B, s));
+    // ---- (c) beside `out`: a slice's raw state, or the trajectory
+    if (c.span) HIPCHK(copy_rows(c.state_out, row_in, w.y, row_arena, row_in, B, s));
+    else if (c.traj)
+        HIPCHK(copy_rows(c.traj, row_in, w.traj_buf, row_arena, row_in, (size_t)(c.steps + 1) * B, s));
     return F5_OK;
 }
 // f5_prepare_sample: one graph per length bucket of [n_min, n_max], captured and instantiated without a launch.  The arena is sized for
@@ -1198,8 +1149,11 @@ int EngineOps<T>::prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max,
     e->gc.capacity = std::max<size_t>(e->gc.capacity, (size_t)(c1 - c0) / g + 1);
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
+    PlanOptions o;   // the plan run_sample makes of a call of nc frames in the bucket of ceiling nc
+    o.nt = e->res_nt; o.steps = steps; o.method = method; o.cfg_strength = cfg_strength; o.want_traj = want_traj;
     for (int nc = c0; nc <= c1; nc += g) {
-        const SamplePlan p = plan_sample(e, B, nc, nullptr, 0, e->res_nt, steps, method, cfg_strength, want_traj, nc);
+        o.n_true = nc;
+        const SamplePlan p = plan_sample(e, B, nc, nullptr, o);
         const std::string key = graph_key(p) + "|nouc";
         if (e->gc.find(key)) continue;
         hipGraphExec_t exec = nullptr;

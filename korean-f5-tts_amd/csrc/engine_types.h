@@ -369,10 +369,22 @@ struct SamplePlan {
 
 // ------------------------------------------------------------------------------------ shared host helpers (engine.hip)
 int ensure_arena(f5_engine* e, int B, int N, int S);
-// (text_embed / forward pass chunk = B: the whole batch as one chunk, both halves; 0: chunk_utts decides)
-// (n_true > 0: a length-bucket plan -- N is the bucket's ceiling, every utterance has n_true frames and lens_host is ignored)
-SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, int chunk = 0, int nt = 0, int steps = 0,
-                       int method = F5_ODE_EULER, float cfg_strength = 1.f, bool want_traj = false, int n_true = 0, bool items = false);
+// what plan_sample is told beside the batch's shape and lengths; the defaults are a plan that only lays out the length tables
+struct PlanOptions {
+    int chunk = 0;        // utterances per chunk; 0: chunk_utts decides (text_embed / forward: the whole batch as one chunk, both halves)
+    int nt = 0, steps = 0, method = F5_ODE_EULER;
+    float cfg_strength = 1.f;
+    bool want_traj = false;
+    int n_true = 0;       // > 0: a length-bucket plan -- N is the bucket's ceiling, every utterance has n_true frames and lens_host is ignored
+    bool items = false;   // a per-item plan of U time rows (cfg_strength: 1 when any item is guided, else 0)
+    int U = 0;
+    static PlanOptions whole_batch(int B) {
+        PlanOptions o;
+        o.chunk = B;
+        return o;
+    }
+};
+SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_host, const PlanOptions& o);
 std::string graph_key(const SamplePlan& p);
 std::vector<float> time_table(const float* t_host, int steps, int method);
 // The time rows of a per-item call: the evaluation times of every live item, walked evaluation-major and then item-major, deduplicated
@@ -383,14 +395,45 @@ struct ItemTimeRows {
     std::vector<int32_t> idx;
 };
 ItemTimeRows item_time_rows(const float* t_items, const int32_t* steps_items, int steps_max, int B, int method);
-// the host tables of one f5_sample_items call, as upload_small sends them down
+// the host tables of a per-item call, as upload_small sends them down
 struct ItemTables {
-    const float* t_items;        // [B][steps_max + 1]
-    const float* cfg_items;      // [B]
-    const int32_t* steps_items;  // [B]
-    const ItemTimeRows* rows;
-    const int32_t* span_rows = nullptr;   // f5_sample_span: [B], the row of prev_state an item continues from, or -1
+    const float* t_items = nullptr;        // [B][steps + 1]
+    const float* cfg_items = nullptr;      // [B]
+    const int32_t* steps_items = nullptr;  // [B]
+    const ItemTimeRows* rows = nullptr;    // (made from the three once they have passed their checks)
 };
+// One sampler call as the ABI hands it over.  f5_sample, f5_sample_ode, f5_sample_items and f5_sample_span each fill one; engine.hip
+// checks it (check_sample_call) and EngineOps<T>::run_sample runs it.  Three things differ between the entry points, and only these:
+struct SampleCall {
+    // what every entry point has, in the order the entry points brace-initialise it
+    const char* who;   // the entry point, for messages
+    const float* cond;   // [B, cond_frames, mel]
+    int cond_frames;
+    const uint8_t* cond_mask;
+    const int64_t* text;
+    int nt;
+    const int32_t* lens_host;
+    int B, N;
+    float* out;
+    hipStream_t stream;
+    int method;
+    // 1. the times: one grid t_host [steps + 1] and one guidance strength for the batch, or (per_item) tables, steps being the largest count
+    bool per_item = false;
+    const float* t_host = nullptr;
+    int steps = 0;
+    float cfg_strength = 0.f;
+    ItemTables items;
+    // 2. the start state: y0 [B, N, mel], or (span) row rows_host[b] of prev_state [prev_B, prev_N, mel], -1 standing for y_new[b]
+    bool span = false;
+    const float* y0 = nullptr;
+    const float *y_new = nullptr, *prev_state = nullptr;
+    int prev_B = 0, prev_N = 0;
+    const int32_t* rows_host = nullptr;   // [B]
+    // 3. what comes back beside `out`: the trajectory [steps + 1, B, N, mel] (or nothing), or (span) the raw state [B, N, mel]
+    float* traj = nullptr;
+    float* state_out = nullptr;
+};
+PlanOptions plan_options(const SampleCall& c);   // the plan of a call at its own N and text length (a length bucket changes nt and n_true)
 
 // Entry points of one operand precision T (float: exact-f32 MFMA; bf16_t / f16_t: 16-bit MFMA operands, f32 accumulate).
 template <typename T> struct EngineOps {
@@ -402,15 +445,7 @@ template <typename T> struct EngineOps {
     static int forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
                        const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
                        hipStream_t s);
-    static int sample(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text, int nt,
-                      const float* t_host, int steps, float cfg_strength, const int32_t* lens_host, int B, int N, float* out,
-                      float* traj, hipStream_t s, int method);
-    static int sample_items(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y0, const int64_t* text,
-                            int nt, const ItemTables& it, int steps_max, bool any_cfg, const int32_t* lens_host, int B, int N, float* out,
-                            float* traj, hipStream_t s, int method);
-    static int sample_span(f5_engine* e, const float* cond, int cond_frames, const uint8_t* cond_mask, const float* y_new,
-                           const float* prev_state, int prev_N, const int64_t* text, int nt, const ItemTables& it, int count, bool any_cfg,
-                           const int32_t* lens_host, int B, int N, float* out, float* state_out, hipStream_t s, int method);
+    static int run_sample(f5_engine* e, const SampleCall& c);
     static int prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max, int steps, float cfg_strength, int method, bool want_traj);
 };
 extern template struct EngineOps<float>;

@@ -200,21 +200,36 @@ class Engine:
                                                _stream_ptr(self.device)), "f5_dit_forward")
         return out
 
+    def _stage_call(self, cond, cond_mask, text, B, method):
+        """What every sampler call begins with: the method check, cond, cond_mask and text on the device, and `out`.
+        Returns (cond, cond_frames, cond_mask, text, out); N is cond_mask's ([B, N])."""
+        if method not in _lib.ODE_METHODS:
+            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
+        cond_frames = 0 if cond is None else cond.shape[1]
+        if cond is not None:
+            cond = _h2d_async(cond, self.device, torch.float32)
+        cm = _h2d_async(cond_mask, self.device, torch.uint8)
+        text = _h2d_async(text, self.device, torch.long)
+        out = torch.empty(B, cond_mask.shape[1], self.mel_dim, device=self.device, dtype=torch.float32)
+        return cond, cond_frames, cm, text, out
+
+    @staticmethod
+    def _flat_grids(t_grids):
+        """B grids as rows of max(steps) + 1 (the engine ignores what follows an item's own grid): (flat, steps, max(steps))."""
+        steps = [len(g) - 1 for g in t_grids]
+        flat = []
+        for g in t_grids:
+            flat += [float(v) for v in g] + [0.0] * (max(steps) + 1 - len(g))
+        return flat, steps, max(steps)
+
     def sample(self, cond, cond_mask, y0, text, t_grid, cfg_strength, lens=None, want_traj=True, method="euler"):
         """cond f32[B,Nc,mel] (Nc <= N: the engine zero-pads, cfm.py:145; None = no_ref_audio), cond_mask bool[B,N],
         y0 f32[B,N,mel], text i64[B,nt], t_grid list[float]; method "euler" (1 backbone evaluation per step) or
         "midpoint" (2 per step), torchdiffeq's fixed-grid solvers on the same grid."""
-        if method not in _lib.ODE_METHODS:
-            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
         B, N, mel = y0.shape
-        cond_frames = 0 if cond is None else cond.shape[1]
         steps = len(t_grid) - 1
-        if cond is not None:
-            cond = _h2d_async(cond, self.device, torch.float32)
+        cond, cond_frames, cm, text, out = self._stage_call(cond, cond_mask, text, B, method)
         y0 = _h2d_async(y0, self.device, torch.float32)
-        cm = _h2d_async(cond_mask, self.device, torch.uint8)
-        text = _h2d_async(text, self.device, torch.long)
-        out = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
         traj = torch.empty(steps + 1, B, N, mel, device=self.device, dtype=torch.float32) if want_traj else None
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_sample_ode(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y0), _ptr(text), text.shape[1],
@@ -226,23 +241,12 @@ class Engine:
     def sample_items(self, cond, cond_mask, y0, text, t_grids, cfg_strengths, lens=None, want_traj=True, method="euler"):
         """sample() with per-item settings (f5_sample_items): t_grids a list of B grids (item b makes len(t_grids[b]) - 1 steps),
         cfg_strengths a list of B floats.  The trajectory has max(steps) + 1 slots; an item that has finished keeps its final state."""
-        if method not in _lib.ODE_METHODS:
-            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
         B, N, mel = y0.shape
         if len(t_grids) != B or len(cfg_strengths) != B:
             raise ValueError(f"sample_items: {len(t_grids)} grids and {len(cfg_strengths)} cfg strengths for a batch of {B}")
-        steps = [len(g) - 1 for g in t_grids]
-        steps_max = max(steps)
-        flat = []
-        for g in t_grids:   # rows of steps_max + 1; the engine ignores what follows an item's own grid
-            flat += [float(v) for v in g] + [0.0] * (steps_max + 1 - len(g))
-        cond_frames = 0 if cond is None else cond.shape[1]
-        if cond is not None:
-            cond = _h2d_async(cond, self.device, torch.float32)
+        cond, cond_frames, cm, text, out = self._stage_call(cond, cond_mask, text, B, method)
+        flat, steps, steps_max = self._flat_grids(t_grids)
         y0 = _h2d_async(y0, self.device, torch.float32)
-        cm = _h2d_async(cond_mask, self.device, torch.uint8)
-        text = _h2d_async(text, self.device, torch.long)
-        out = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
         traj = torch.empty(steps_max + 1, B, N, mel, device=self.device, dtype=torch.float32) if want_traj else None
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_sample_items(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y0), _ptr(text), text.shape[1],
@@ -256,21 +260,13 @@ class Engine:
         here), rows[b] the row of prev_state [prev_B, prev_N, mel] item b continues from, or -1 for an item that starts from
         y_new[b] ([B, N, mel]; None when no item starts).  N is cond_mask's ([B, N]).  Returns (out, state), both [B, N, mel]: the
         raw state is the next slice's prev_state."""
-        if method not in _lib.ODE_METHODS:
-            raise ValueError(f"unknown ODE method {method!r}: expected one of {sorted(_lib.ODE_METHODS)}")
         B = len(t_grids)
         rows = [int(r) for r in rows]
         if len(rows) != B or len(cfg_strengths) != B:
             raise ValueError(f"sample_span: {len(rows)} rows and {len(cfg_strengths)} cfg strengths for a batch of {B}")
         N, mel = cond_mask.shape[1], self.mel_dim
-        steps = [len(g) - 1 for g in t_grids]
-        count = max(steps)
-        flat = []
-        for g in t_grids:   # rows of count + 1; the engine ignores what follows an item's own sub-grid
-            flat += [float(v) for v in g] + [0.0] * (count + 1 - len(g))
-        cond_frames = 0 if cond is None else cond.shape[1]
-        if cond is not None:
-            cond = _h2d_async(cond, self.device, torch.float32)
+        cond, cond_frames, cm, text, out = self._stage_call(cond, cond_mask, text, B, method)
+        flat, steps, count = self._flat_grids(t_grids)
         if y_new is not None:
             y_new = _h2d_async(y_new, self.device, torch.float32)
             if tuple(y_new.shape) != (B, N, mel):
@@ -281,9 +277,6 @@ class Engine:
             if prev_state.ndim != 3 or prev_state.shape[2] != mel:
                 raise ValueError(f"sample_span: prev_state is {tuple(prev_state.shape)}, not [prev_B, prev_N, {mel}]")
             prev_B, prev_N = prev_state.shape[:2]
-        cm = _h2d_async(cond_mask, self.device, torch.uint8)
-        text = _h2d_async(text, self.device, torch.long)
-        out = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
         state = torch.empty(B, N, mel, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_sample_span(self._h, _ptr(cond), cond_frames, _ptr(cm), _ptr(y_new), _ptr(prev_state), prev_B, prev_N,

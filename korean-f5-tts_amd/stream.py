@@ -519,6 +519,14 @@ class StreamPool:
         return not self._pending and not self._rows and not any(r.next < r.stop for r in self._requests)
 
     # ---- a tick ------------------------------------------------------------------------------------------------------------
+    def _batch_of(self, run):
+        """The rows `run` ([(request, chunk)]) as the sampler's cond, text, duration and lens keywords, and the rows' voices."""
+        bank = self.bank
+        glens = [bank.frames[r.voice] for r, _ in run]
+        rows = torch.tensor([r.voice for r, _ in run], device=bank.mel.device)
+        return dict(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
+                    duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens)), rows
+
     def _enqueue(self):
         """The device work of the next tick, all of it asynchronous: None when nothing waits, else (touched requests with their
         byte spans, pinned host tensor or None, event)."""
@@ -530,18 +538,16 @@ class StreamPool:
         if not items:
             return None
         by_id = {r.id: r for r in self._requests}
-        bank, run = self.bank, [(by_id[rid], k) for rid, k in items]
+        run = [(by_id[rid], k) for rid, k in items]
         self.log.append(list(items))
-        glens = [bank.frames[r.voice] for r, _ in run]
-        rows = torch.tensor([r.voice for r, _ in run], device=bank.mel.device)
+        batch, rows = self._batch_of(run)
         # a tick whose rows all carry the pool's settings is one sample(); any other is one sample_items() with the rows' own
         row_kw = [r.client.sample_kw for r, _ in run]
         if all(kw == self.sample_kw for kw in row_kw):
             sample, kw = self.model.sample, self.sample_kw
         else:
             sample, kw = self.model.sample_items, {name: [rk[name] for rk in row_kw] for name in self.sample_kw}
-        generated, _ = sample(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
-                              duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens), **kw)
+        generated, _ = sample(**batch, **kw)
         for r, k in run:
             assert k == r.next, "a request's chunks run in order"
             r.next += 1
@@ -573,13 +579,10 @@ class StreamPool:
             chosen.append(row)
         bank, run = self.bank, [(row.req, row.k) for row in chosen]
         self.log.append(list(items))
-        glens = [bank.frames[r.voice] for r, _ in run]
-        rows = torch.tensor([r.voice for r, _ in run], device=bank.mel.device)
+        batch, rows = self._batch_of(run)
         state, prev_rows = span_prev([(row.state, row.row) for row in chosen])
         start = [row.made for row in chosen]
-        res = self.model.sample_span(cond=bank.mel[:, :max(glens)].index_select(0, rows), text=[r.plan["texts"][k] for r, k in run],
-                                     duration=torch.tensor([r.plan["durations"][k] for r, k in run]), lens=torch.tensor(glens),
-                                     start=start, count=self.slice_steps, prev=None if state is None else (state, prev_rows),
+        res = self.model.sample_span(**batch, start=start, count=self.slice_steps, prev=None if state is None else (state, prev_rows),
                                      **{name: [row.kw[name] for row in chosen] for name in self.sample_kw})
         self.spans.append([(a, min(self.slice_steps, int(row.kw["steps"]) - a)) for a, row in zip(start, chosen)])
         for key in ("ticks", "sample_calls"):

@@ -92,9 +92,19 @@ class _Engine:
     def __init__(self):
         self.calls = []
 
+    def sample(self, cond, cond_mask, y0, text, t_grid, cfg_strength, lens=None, want_traj=True, method="euler"):
+        self.calls.append(dict(name="sample", cond=cond, cond_mask=cond_mask, y0=y0, text=text, t_grids=[t_grid] * y0.shape[0],
+                               cfgs=[cfg_strength] * y0.shape[0], lens=lens, method=method))
+        return torch.zeros(y0.shape), torch.zeros(len(t_grid), *y0.shape)
+
+    def sample_items(self, cond, cond_mask, y0, text, t_grids, cfgs, lens=None, want_traj=True, method="euler"):
+        self.calls.append(dict(name="sample_items", cond=cond, cond_mask=cond_mask, y0=y0, text=text, t_grids=t_grids, cfgs=cfgs, lens=lens,
+                               method=method))
+        return torch.zeros(y0.shape), torch.zeros(max(len(g) for g in t_grids), *y0.shape)
+
     def sample_span(self, cond, cond_mask, y_new, prev_state, rows, text, t_grids, cfgs, lens=None, method="euler"):
-        self.calls.append(dict(cond=cond, cond_mask=cond_mask, y_new=y_new, prev_state=prev_state, rows=rows, text=text, t_grids=t_grids,
-                               cfgs=cfgs, lens=lens, method=method))
+        self.calls.append(dict(name="sample_span", cond=cond, cond_mask=cond_mask, y_new=y_new, prev_state=prev_state, rows=rows, text=text,
+                               t_grids=t_grids, cfgs=cfgs, lens=lens, method=method))
         state = torch.zeros(cond_mask.shape[0], cond_mask.shape[1], 100)
         return state, state
 
@@ -189,6 +199,47 @@ def test_sample_span_refusals():
         m.sample_span(cond, text, dur, duplicate_test=True, **ok)
     with pytest.raises(TypeError):
         m.sample_span(cond, text, dur, lens=lens, **KW)                  # start and count have no default
+
+
+@pytest.mark.parametrize("no_ref_audio", [False, True])
+def test_the_three_entry_points_hand_the_engine_the_same_call(no_ref_audio):
+    """CFM.sample, .sample_items with scalar settings and .sample_span(start=0, count=steps) of one ragged batch: the same cond,
+    cond_mask, text and lens, bitwise equal grids, equal noise."""
+    m, eng = host_model()
+    cond, text, dur, lens = batch()
+    edit = torch.ones(3, 12, dtype=torch.bool)
+    edit[0, 3:6] = edit[2, 8] = False                                   # prompt frames to re-speak: inside lens 12 and 9
+    steps = 4
+    kw = dict(lens=lens, steps=steps, cfg_strength=2.0, sway_sampling_coef=-1.0, seed=5, no_ref_audio=no_ref_audio, edit_mask=edit)
+    m.sample(cond, text, dur, **kw)
+    m.sample_items(cond, text, dur, **kw)
+    res = m.sample_span(cond, text, dur, start=[0, 0, 0], count=steps, **kw)
+    assert res.done == [True] * 3
+    assert [c["name"] for c in eng.calls] == ["sample", "sample_items", "sample_span"]
+    want_mask = torch.zeros(3, 40, dtype=torch.bool)
+    for b, n in enumerate(lens.tolist()):
+        want_mask[b, :n] = edit[b, :n]
+    first = eng.calls[0]
+    assert first["cond_mask"].dtype == torch.bool and first["cond_mask"].shape == (3, 40) and torch.equal(first["cond_mask"], want_mask)
+    assert not want_mask[0, 3:6].any() and not want_mask[2, 8] and want_mask.sum() == 12 + 7 + 9 - 4
+    assert first["cond"] is None if no_ref_audio else torch.equal(first["cond"], cond)
+    assert first["lens"] == [40, 21, 33] and first["cfgs"] == [2.0] * 3
+    for call in eng.calls[1:]:
+        assert call["cond"] is None if no_ref_audio else torch.equal(call["cond"], first["cond"]), call["name"]
+        assert call["cond_mask"].dtype == torch.bool and torch.equal(call["cond_mask"], first["cond_mask"]), call["name"]
+        assert call["text"].dtype == first["text"].dtype and torch.equal(call["text"], first["text"]), call["name"]
+        assert call["lens"] == first["lens"] and call["cfgs"] == first["cfgs"] and call["method"] == first["method"], call["name"]
+        assert [bits(g) for g in call["t_grids"]] == [bits(g) for g in first["t_grids"]], call["name"]
+    assert len(first["t_grids"][0]) == steps + 1
+    y_items, y_span = eng.calls[1]["y0"], eng.calls[2]["y_new"]
+    assert y_items.shape == (3, 40, 100) and torch.equal(y_span, y_items) and torch.equal(first["y0"], y_items)
+    assert eng.calls[2]["prev_state"] is None and eng.calls[2]["rows"] == [-1] * 3
+    # B = 1: no lens for any of the three
+    kw1 = dict(kw, lens=lens[:1], edit_mask=edit[:1])
+    m.sample(cond[:1], text[:1], dur[:1], **kw1)
+    m.sample_items(cond[:1], text[:1], dur[:1], **kw1)
+    m.sample_span(cond[:1], text[:1], dur[:1], start=[0], count=steps, **kw1)
+    assert [c["lens"] for c in eng.calls[3:]] == [None] * 3 and all(c["cond_mask"].shape == (1, 40) for c in eng.calls[3:])
 
 
 # ------------------------------------------------------------------------------------------------ null handles
