@@ -217,6 +217,29 @@ int f5_set_length_buckets(f5_engine* e, int32_t granule);
  * engine can be eligible.  Host work only (allocates); `stream` is not used. */
 int f5_prepare_sample(f5_engine* e, int32_t B, int32_t n_min, int32_t n_max, int32_t nt_max, int32_t steps, float cfg_strength,
                       int32_t method, int32_t want_traj, f5_stream stream);
+/* ---------------------------------------------------------------------------------------- isolated rows
+ * With the shipped configs (attn_mask_enabled = 0) a row of a rectangular batch attends over the batch's padding and has its text
+ * embedded at the batch's N, so what f5_sample_items / f5_sample_span compute for an item depends on the items beside it.  With
+ * isolated rows on, both run on the packed (RowPack) body with every row's own length in the device tables: the text is embedded per
+ * row at lens[b], conv-pos and attention keys are masked at lens[b] whatever attn_mask_enabled says, and everything else is row-wise
+ * -- inside its own frames every row is, bit for bit, what the same item gives alone at B = 1, in any batch and any row order.
+ * Frames past lens[b] of out / state_out / traj keep their staged value.  lens_host == NULL means every row has N frames.
+ *
+ * With f5_set_length_buckets on, an isolated call is planned at N_cap = N rounded up to the granule (rows staged at the arena's
+ * pitch, frames N .. N_cap-1 of state and mask zero, the text in rows of filler) and at the distinct evaluation times rounded up to
+ * a power of two (the rows behind the call's own repeat its last time; no index points at them), so that the graph key
+ * "P B|N_cap|steps|U_cap|halves|traj|chunk|method" holds no exact length, text length or time count.  With buckets off the key takes
+ * the same form at N rounded up to 4 (the granule of a packed batch row: rows that fill their N would otherwise pack into more
+ * rows than B x N), with the exact text length appended.
+ *
+ * Isolation is a promise: an f5_sample_items / f5_sample_span call that cannot keep it is F5_EINVAL with a message naming the
+ * reason and nothing launched -- the UNetT backbone, F5_SPLIT_CFG=1, F5_OPT_TEXT_AVG_UPSAMPLE, or N_cap outside the rotary or text
+ * position tables.  F5_PACK_ROWS=0 does not turn it off (that switch is about f5_sample).  f5_sample, f5_sample_ode and
+ * f5_prepare_sample are untouched.  on: 0 = off (the default: every key, launch and result as without this function). */
+int f5_set_isolated_rows(f5_engine* e, int32_t on);
+/* The graph cache holds n graphs, 16 (the default) <= n <= 64, oldest out first; anything else is F5_EINVAL.  For an engine whose
+ * calls vary in B as well as in length bucket.  f5_set_length_buckets puts it back to 16; f5_prepare_sample only ever raises it. */
+int f5_set_graph_capacity(f5_engine* e, int32_t n);
 /* out[0..3] = f5_sample bodies captured into a graph (the capturing call launches its graph, and counts here only), replayed from the
  * cache, launched eagerly, and graphs pushed out of the cache by a newer one -- since f5_create or the last reset.  out == NULL
  * resets the four counters.  Reads four integers: no device work. */
@@ -766,11 +789,24 @@ int f5k_euler_cfg_items(float* y, const float* pred, int32_t B, int32_t N, int32
 int f5k_midpoint_half_cfg_items(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items,
                                 const float* cfg_items, const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg,
                                 float* y_mid, f5_stream stream);
+/* The updates of an isolated f5_sample_items call (f5_set_isolated_rows): the per-item rules above on the RowPack form of f5k_euler_cfg --
+ * pred f32[rows, mel] with the rows of batch row b' at row_start[b'] (int[(use_cfg ? 2 : 1) * B + 1]), lens int[B], both required.
+ * Item b with step < steps_items[b], frames n < lens[b]: updated; everything else of y is not written (traj_slot / y_mid receive y). */
+int f5k_euler_cfg_items_packed(float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start, const int32_t* lens,
+                               const float* t_items, const float* cfg_items, const int32_t* steps_items, int32_t steps_max, int32_t step,
+                               int32_t use_cfg, float* traj_slot, f5_stream stream);
+int f5k_midpoint_half_cfg_items_packed(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start,
+                                       const int32_t* lens, const float* t_items, const float* cfg_items, const int32_t* steps_items,
+                                       int32_t steps_max, int32_t step, int32_t use_cfg, float* y_mid, f5_stream stream);
 /* The staging of f5_sample_span: y f32[B, N, mel] = prev_state[rows[b], n] (n < prev_N, else +0.0) where rows[b] >= 0, y_new[b, n]
  * where rows[b] == -1.  rows int32[B] on the device, rows_host the same table on the host (the rules of f5_sample_span's rows_host
  * are checked on it); prev_state f32[prev_B, prev_N, mel] and y_new f32[B, N, mel] on the device, NULL where no row reads them. */
 int f5k_span_stage(float* y, const float* prev_state, int32_t prev_B, int32_t prev_N, const float* y_new, const int32_t* rows,
                    const int32_t* rows_host, int32_t B, int32_t N, int32_t mel, f5_stream stream);
+/* The same into rows `pitch` >= N frames apart (a length bucket's arena): y f32[B, pitch, mel], of which the frames n < N of every row
+ * are written and the others are not touched.  prev_state and y_new keep their own pitches, prev_N and N. */
+int f5k_span_stage_pitched(float* y, int32_t pitch, const float* prev_state, int32_t prev_B, int32_t prev_N, const float* y_new,
+                           const int32_t* rows, const int32_t* rows_host, int32_t B, int32_t N, int32_t mel, f5_stream stream);
 /* dst f32[rows, width] = src[idx[r % nidx], :]; idx int[nidx] (device), width % 4 == 0.  The caller keeps idx inside src. */
 int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, int32_t rows, int32_t nidx, int32_t width, f5_stream stream);
 /* The time rows of an f5_sample_items call (host arithmetic, no device needed): the evaluation times of every live item -- Euler t[b][i];

@@ -99,6 +99,8 @@ SIGNATURES = {
                             C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_reserve": (_i, [_p, _i, _i, _i]),
     "f5_set_length_buckets": (_i, [_p, _i]),
+    "f5_set_isolated_rows": (_i, [_p, _i]),
+    "f5_set_graph_capacity": (_i, [_p, _i]),
     "f5_prepare_sample": (_i, [_p, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "f5_graph_stats": (_i, [_p, C.POINTER(_i)]),
     "f5_adapter_create": (_i, [_p, C.POINTER(_p)]),
@@ -166,8 +168,11 @@ SIGNATURES = {
     "f5k_midpoint_half_cfg": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _f, _i, _p, _p]),
     "f5k_euler_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
     "f5k_midpoint_half_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "f5k_euler_cfg_items_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "f5k_midpoint_half_cfg_items_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "f5k_mod_gather": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "f5k_span_stage": (_i, [_p, _p, _i, _i, _p, _p, C.POINTER(_i), _i, _i, _i, _p]),
+    "f5k_span_stage_pitched": (_i, [_p, _i, _p, _i, _i, _p, _p, C.POINTER(_i), _i, _i, _i, _p]),
     "f5k_item_time_rows": (_i, [C.POINTER(_f), C.POINTER(_i), _i, _i, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i)]),
     "f5k_select_rows": (_i, [_p, _p, _p, _p, C.c_int64, _i, _p]),
     "f5k_time_sinus": (_i, [_p, _p, _p, _i, _p]),

@@ -28,6 +28,8 @@ class _HipBackbone(nn.Module):
     def __init__(self, *, mel_dim=100, text_num_embeds=256, precision="parity", device=None, max_pos=8192, **arch):
         super().__init__()
         self.length_bucket = 0              # granule of the length-bucketed sample() graphs; 0: off (set_length_buckets)
+        self.isolated_rows = False          # sample_items() / sample_span() on packed rows, each row as if alone (set_isolated_rows)
+        self.graph_capacity = 0             # graphs the engine's cache holds; 0: the engine's default of 16 (set_graph_capacity)
         # "parity" (the default): the fastest operand precision measured inside the 1e-3 mel bar of the fp32 CPU path for THIS backbone
         # (DESIGN.md section 3): DiT "f16p" (f16 blocks, split-f16 input / output layers); the E2-TTS UNetT has no AdaLN gates and
         # every one of its GEMM classes costs ~1e-3 in plain f16, so it gets "f16x3" (split-f16 GEMM products, f16 attention products)
@@ -96,6 +98,10 @@ class _HipBackbone(nn.Module):
             e.load_state_dict(self._sd)
             if self.length_bucket:
                 e.set_length_buckets(self.length_bucket)
+            if self.isolated_rows:
+                e.set_isolated_rows(True)
+            if self.graph_capacity:
+                e.set_graph_capacity(self.graph_capacity)
             self._engine = e
             for name, (pairs, full) in self._adapters.items():
                 self._adapter_handles[name] = e.new_adapter(pairs, full)
@@ -120,6 +126,31 @@ class _HipBackbone(nn.Module):
         self.length_bucket = granule
         if self._engine is not None:
             self._engine.set_length_buckets(granule)
+            if self.graph_capacity:                      # (the engine's setter puts the cache back to 16 graphs)
+                self._engine.set_graph_capacity(self.graph_capacity)
+
+    # ---- isolated rows -------------------------------------------------------------------------------------------
+    def set_isolated_rows(self, on: bool):
+        """sample_items() and sample_span() run every row as if it were alone in the batch: on packed rows, with the row's own length
+        masking attention keys and conv-pos whatever `attn_mask_enabled` says, and in the engine's length buckets when those are on.
+        Inside its own frames a row then equals the same item at B = 1, bit for bit, in any batch.  A call that cannot keep that
+        (F5_SPLIT_CFG=1, text_embedding_average_upsampling, a length past the position tables) raises instead of running
+        rectangular.  sample() is untouched.  Off by default; survives engine rebuilds."""
+        if on and self.backbone_name != "DiT":
+            raise NotImplementedError("isolated rows run on packed rows, which are built for the DiT backbone only")
+        self.isolated_rows = bool(on)
+        if self._engine is not None:
+            self._engine.set_isolated_rows(self.isolated_rows)
+
+    def set_graph_capacity(self, n: int):
+        """The engine's graph cache holds n graphs (16 to 64), for callers whose batches vary in size as well as in length bucket.
+        Survives engine rebuilds and set_length_buckets."""
+        n = int(n)
+        if not 16 <= n <= 64:
+            raise ValueError(f"graph capacity {n}: expected 16 to 64 graphs")
+        self.graph_capacity = n
+        if self._engine is not None:
+            self._engine.set_graph_capacity(n)
 
     def prepare_sample(self, batch: int, n_min: int, n_max: int, nt_max: int, steps: int, cfg_strength: float, *,
                        method: str = "euler", want_traj: bool = True):

@@ -55,12 +55,13 @@ __device__ __forceinline__ void store_row_wt(TO* out, size_t row_off, const floa
             if (lane * 4 + i * 256 < D) store4_at_wt(out, row_off, lane * 4 + i * 256, planar, y[i].x, y[i].y, y[i].z, y[i].w);
     }
 }
-template <typename TO>
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, TO* __restrict__ out,
-                                                        int ldo, int R, int D, float eps, const float* __restrict__ A,
-                                                        const float* __restrict__ Bv, int vec_stride,
-                                                        int rows_per_batch, int modulate, Prefetch pf,
-                                                        const int* __restrict__ m_limit = nullptr, int planar = 0, int wt = 0) {
+// The body of the two LayerNorm kernels below.  ROWS: row r's vectors are those of batch row rowmap[r].x (a packed batch whose batch rows
+// have their own vectors), not of r / rows_per_batch.
+template <typename TO, bool ROWS>
+__device__ __forceinline__ void layernorm_body(const float* __restrict__ x, int ldx, TO* __restrict__ out, int ldo, int R, int D, float eps,
+                                               const float* __restrict__ A, const float* __restrict__ Bv, int vec_stride,
+                                               int rows_per_batch, int modulate, const Prefetch& pf, const int* __restrict__ m_limit,
+                                               int planar, int wt, const int2* __restrict__ rowmap) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R || (m_limit && r >= *m_limit)) return;   // (m_limit: rows present in a packed batch, RowPack)
@@ -68,7 +69,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     float4 v[8], ga[8], gb[8];
     // the modulation / affine vectors do not depend on the statistics: request them together with the row so that the
     // kernel is ONE memory round trip deep, not two
-    const size_t vb = (size_t)(rows_per_batch > 0 ? r / rows_per_batch : 0) * vec_stride;
+    size_t vb;
+    if constexpr (ROWS) vb = (size_t)rowmap[r].x * vec_stride;   // (r < *m_limit: a row fill_rowmap_kernel has written)
+    else vb = (size_t)(rows_per_batch > 0 ? r / rows_per_batch : 0) * vec_stride;
     const float a0 = modulate ? 0.f : 1.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -128,6 +131,23 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(pfv[i]));   // keep the prefetch loads; nothing uses their data
+}
+template <typename TO>
+__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, int ldx, TO* __restrict__ out,
+                                                        int ldo, int R, int D, float eps, const float* __restrict__ A,
+                                                        const float* __restrict__ Bv, int vec_stride,
+                                                        int rows_per_batch, int modulate, Prefetch pf,
+                                                        const int* __restrict__ m_limit = nullptr, int planar = 0, int wt = 0) {
+    layernorm_body<TO, false>(x, ldx, out, ldo, R, D, eps, A, Bv, vec_stride, rows_per_batch, modulate, pf, m_limit, planar, wt, nullptr);
+}
+// ... of a per-item call on packed rows (every batch row has its own AdaLN vectors): a kernel of its own, so that the one every other
+// forward launches keeps its arguments and its code
+template <typename TO>
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ x, int ldx, TO* __restrict__ out, int ldo, int R,
+                                                             int D, float eps, const float* __restrict__ A, const float* __restrict__ Bv,
+                                                             int vec_stride, Prefetch pf, const int* __restrict__ m_limit,
+                                                             const int2* __restrict__ rowmap, int planar, int wt) {
+    layernorm_body<TO, true>(x, ldx, out, ldo, R, D, eps, A, Bv, vec_stride, 0, 1, pf, m_limit, planar, wt, rowmap);
 }
 
 // x_transformers.RMSNorm as used by UNetT (unett.py:154,168,185): F.normalize(x, dim=-1) * sqrt(D) * g
@@ -445,16 +465,91 @@ static __global__ void midpoint_half_cfg_items_kernel(const float* __restrict__ 
         reinterpret_cast<float4*>(y_mid)[i] = yy;
     }
 }
-// The tables of a chunk of B utterances start at the chunk's first utterance (t_items, cfg_items, steps_items already offset).
-inline void launch_euler_cfg_items(hipStream_t s, float* y, const float* pred, int B, int N, int mel, const float* t_items,
-                                   const float* cfg_items, const int* steps_items, int steps_max, int step, int use_cfg, float* traj_slot) {
-    hipLaunchKernelGGL(euler_cfg_items_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, pred, B, N, mel, t_items, cfg_items,
-                       steps_items, steps_max, step, use_cfg, traj_slot);
+// The per-item updates when the backbone ran on PACKED rows (an isolated per-item call, f5_set_isolated_rows): the index shape of
+// euler_cfg_packed_kernel -- pred[r, :] with r = row_start[b] + n, the unconditional half at row_start[B + b] + n, only n < lens[b] --
+// and the per-item part of euler_cfg_items_kernel.  A finished item and the frames past an item's own length are not written; the
+// trajectory slot receives y as it stands.
+static __global__ void euler_cfg_items_packed_kernel(float* __restrict__ y, const float* __restrict__ pred, int B, int N, int mel,
+                                                     const int* __restrict__ row_start, const int* __restrict__ lens,
+                                                     const float* __restrict__ t_items, const float* __restrict__ cfg_items,
+                                                     const int* __restrict__ steps_items, int steps_max, int step, int use_cfg,
+                                                     float* __restrict__ traj_slot) {
+    const int c4n = mel / 4;
+    const long total = (long)B * N * c4n;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4n);
+        const long fr = i / c4n;
+        const int n = (int)(fr % N), b = (int)(fr / N);
+        float4 yy = reinterpret_cast<float4*>(y)[i];
+        if (step < steps_items[b] && n < lens[b]) {
+            const float* tg = t_items + (size_t)b * (steps_max + 1);
+            const float dt = tg[step + 1] - tg[step];
+            const float cfg = cfg_items[b];
+            const float4 p = reinterpret_cast<const float4*>(pred + ((size_t)row_start[b] + n) * mel)[c];
+            float4 v = p;
+            if (use_cfg && !(cfg < 1e-5f)) {
+                const float4 u = reinterpret_cast<const float4*>(pred + ((size_t)row_start[B + b] + n) * mel)[c];
+                v.x = p.x + (p.x - u.x) * cfg; v.y = p.y + (p.y - u.y) * cfg;
+                v.z = p.z + (p.z - u.z) * cfg; v.w = p.w + (p.w - u.w) * cfg;
+            }
+            yy.x += dt * v.x; yy.y += dt * v.y; yy.z += dt * v.z; yy.w += dt * v.w;
+            reinterpret_cast<float4*>(y)[i] = yy;
+        }
+        if (traj_slot) reinterpret_cast<float4*>(traj_slot)[i] = yy;
+    }
 }
-inline void launch_midpoint_half_cfg_items(hipStream_t s, const float* y, const float* pred, int B, int N, int mel, const float* t_items,
-                                           const float* cfg_items, const int* steps_items, int steps_max, int step, int use_cfg, float* y_mid) {
-    hipLaunchKernelGGL(midpoint_half_cfg_items_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, pred, B, N, mel, t_items,
-                       cfg_items, steps_items, steps_max, step, use_cfg, y_mid);
+// ... and the midpoint half step; a finished item and the frames past an item's length get y_mid = y
+static __global__ void midpoint_half_cfg_items_packed_kernel(const float* __restrict__ y, const float* __restrict__ pred, int B, int N,
+                                                             int mel, const int* __restrict__ row_start, const int* __restrict__ lens,
+                                                             const float* __restrict__ t_items, const float* __restrict__ cfg_items,
+                                                             const int* __restrict__ steps_items, int steps_max, int step, int use_cfg,
+                                                             float* __restrict__ y_mid) {
+    const int c4n = mel / 4;
+    const long total = (long)B * N * c4n;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % c4n);
+        const long fr = i / c4n;
+        const int n = (int)(fr % N), b = (int)(fr / N);
+        float4 yy = reinterpret_cast<const float4*>(y)[i];
+        if (step < steps_items[b] && n < lens[b]) {
+            const float* tg = t_items + (size_t)b * (steps_max + 1);
+            const float hdt = 0.5f * (tg[step + 1] - tg[step]);
+            const float cfg = cfg_items[b];
+            const float4 p = reinterpret_cast<const float4*>(pred + ((size_t)row_start[b] + n) * mel)[c];
+            float4 v = p;
+            if (use_cfg && !(cfg < 1e-5f)) {
+                const float4 u = reinterpret_cast<const float4*>(pred + ((size_t)row_start[B + b] + n) * mel)[c];
+                v.x = p.x + (p.x - u.x) * cfg; v.y = p.y + (p.y - u.y) * cfg;
+                v.z = p.z + (p.z - u.z) * cfg; v.w = p.w + (p.w - u.w) * cfg;
+            }
+            yy.x += v.x * hdt; yy.y += v.y * hdt; yy.z += v.z * hdt; yy.w += v.w * hdt;
+        }
+        reinterpret_cast<float4*>(y_mid)[i] = yy;
+    }
+}
+// One per-item ODE update of a chunk of B utterances as sample_body launches it: the packed form when the backbone ran on packed rows
+// (row_start non-null; lens comes with it).  The tables start at the chunk's first utterance (t_items, cfg_items, steps_items already offset).
+inline void launch_euler_cfg_items(hipStream_t s, float* y, const float* pred, int B, int N, int mel, const int* row_start, const int* lens,
+                                   const float* t_items, const float* cfg_items, const int* steps_items, int steps_max, int step, int use_cfg,
+                                   float* traj_slot) {
+    const dim3 grid(ew_blocks((long)B * N * mel / 4));
+    if (row_start)
+        hipLaunchKernelGGL(euler_cfg_items_packed_kernel, grid, dim3(256), 0, s, y, pred, B, N, mel, row_start, lens, t_items, cfg_items,
+                           steps_items, steps_max, step, use_cfg, traj_slot);
+    else
+        hipLaunchKernelGGL(euler_cfg_items_kernel, grid, dim3(256), 0, s, y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step,
+                           use_cfg, traj_slot);
+}
+inline void launch_midpoint_half_cfg_items(hipStream_t s, const float* y, const float* pred, int B, int N, int mel, const int* row_start,
+                                           const int* lens, const float* t_items, const float* cfg_items, const int* steps_items,
+                                           int steps_max, int step, int use_cfg, float* y_mid) {
+    const dim3 grid(ew_blocks((long)B * N * mel / 4));
+    if (row_start)
+        hipLaunchKernelGGL(midpoint_half_cfg_items_packed_kernel, grid, dim3(256), 0, s, y, pred, B, N, mel, row_start, lens, t_items,
+                           cfg_items, steps_items, steps_max, step, use_cfg, y_mid);
+    else
+        hipLaunchKernelGGL(midpoint_half_cfg_items_kernel, grid, dim3(256), 0, s, y, pred, B, N, mel, t_items, cfg_items, steps_items,
+                           steps_max, step, use_cfg, y_mid);
 }
 // dst[r, :] = src[idx[r % nidx], :] for r < rows: the time rows (AdaLN vectors, or the UNetT's time embedding) of one evaluation, one per
 // batch row of a chunk -- nidx utterances, the conditional half and then (rows = 2 nidx) the unconditional half.  width % 4 == 0.
@@ -475,10 +570,13 @@ inline void launch_mod_gather(hipStream_t s, const float* src, const int* idx, f
 // where rows[b] >= 0 and n >= prev_N (a frame the previous batch did not have), and y_new[b, n, :] where rows[b] == -1.  One float4
 // per lane, consecutive lanes on consecutive addresses of y and, inside a row, of the source; mel % 4 == 0.  prev / y_new may be null
 // when no row reads them.
+// pitch >= N: the frames between two rows of y (a length bucket stages rows of N frames at the bucket's ceiling; the frames N .. pitch-1
+// of a row are not written here).  prev and y_new keep their own pitches, prev_N and N.
 static __global__ void span_stage_kernel(float* __restrict__ y, const float* __restrict__ prev, const float* __restrict__ y_new,
-                                         const int* __restrict__ rows, int B, int N, int prev_N, int mel) {
+                                         const int* __restrict__ rows, int B, int N, int prev_N, int mel, int pitch) {
     const int c4n = mel / 4;
     const long per_row = (long)N * c4n, total = (long)B * per_row, keep = (long)(prev_N < N ? prev_N : N) * c4n;
+    const long skip = (long)(pitch - N) * c4n;   // float4s between the end of a row and the start of the next
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int b = (int)(i / per_row);
         const long j = i - (long)b * per_row;   // float4 index inside the row: n * c4n + c
@@ -486,12 +584,13 @@ static __global__ void span_stage_kernel(float* __restrict__ y, const float* __r
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (r < 0) v = reinterpret_cast<const float4*>(y_new)[i];
         else if (j < keep) v = reinterpret_cast<const float4*>(prev)[(long)r * prev_N * c4n + j];
-        reinterpret_cast<float4*>(y)[i] = v;
+        reinterpret_cast<float4*>(y)[i + (long)b * skip] = v;
     }
 }
 inline void launch_span_stage(hipStream_t s, float* y, const float* prev, const float* y_new, const int* rows, int B, int N, int prev_N,
-                              int mel) {
-    hipLaunchKernelGGL(span_stage_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, prev, y_new, rows, B, N, prev_N, mel);
+                              int mel, int pitch) {
+    hipLaunchKernelGGL(span_stage_kernel, dim3(ew_blocks((long)B * N * mel / 4)), dim3(256), 0, s, y, prev, y_new, rows, B, N, prev_N, mel,
+                       pitch);
 }
 
 // rowmap[row_start[b'] + n] = (b', n) for n < row_start[b' + 1] - row_start[b']   (one block per batch row)

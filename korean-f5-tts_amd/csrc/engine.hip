@@ -237,7 +237,7 @@ SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_hos
     p.items = o.items;
     p.U = o.U;
     // a length-bucket plan: every utterance has n_true frames; the chunking follows the bucket's ceiling alone (it is part of the key)
-    const std::vector<int32_t> own(n_true > 0 ? B : 0, n_true), cap(n_true > 0 ? B : 0, N);
+    const std::vector<int32_t> own(n_true > 0 ? B : 0, n_true), cap(n_true > 0 || o.isolated ? B : 0, N);
     if (n_true > 0) lens_host = own.data();
     p.n_true = n_true;
     p.B = B; p.N = N; p.nt = o.nt; p.steps = o.steps; p.method = o.method; p.cfg_strength = o.cfg_strength;
@@ -247,10 +247,13 @@ SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_hos
     p.halves = p.use_cfg ? 2 : 1;
     p.evals = o.method == F5_ODE_MIDPOINT ? 2 : 1;
     const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;
-    // (a per-item call runs the rectangular body on one stream chain: batch row = row / N is what finds a row's time vectors)
-    p.pack = !o.items && (n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg));
+    // (a per-item call runs on one stream chain, and on the rectangular body -- batch row = row / N finds a row's time vectors -- unless
+    //  it is isolated: then on packed rows, whatever F5_PACK_ROWS says, and the rowmap's batch row finds them)
+    p.bucket = o.isolated && o.bucket;
+    p.pack = o.isolated || (!o.items && (n_true > 0 || (p.has_lens && e->sw.pack_rows && e->cfg.attn_mask_enabled && dit && !e->sw.split_cfg)));
     p.split = !o.items && e->sw.split_cfg && p.use_cfg && dit && !e->prof.on;
-    p.chunk = o.chunk ? o.chunk : chunk_utts(e, B, N, p.use_cfg, n_true > 0 ? cap.data() : p.pack ? lens_host : nullptr);
+    // (an isolated plan's key holds no length, so its chunking follows N alone, as a bucket plan's does)
+    p.chunk = o.chunk ? o.chunk : chunk_utts(e, B, N, p.use_cfg, n_true > 0 || o.isolated ? cap.data() : p.pack ? lens_host : nullptr);
     for (int u0 = 0; u0 < B; u0 += p.chunk) {
         SamplePlan::Chunk k{(int)p.chunks.size(), u0, std::min(p.chunk, B - u0), 0, 0};
         for (int i = 0; lens_host && i < k.bc; ++i) {
@@ -267,6 +270,14 @@ std::string graph_key(const SamplePlan& p) {
     memcpy(&cfg_bits, &p.cfg_strength, 4);
     char kb[160];
     // a per-item plan: guidance and grids live in device tables, so neither is part of the key -- one graph serves every setting of a shape
+    // an isolated per-item plan: packed rows, every length in device tables; N is the bucket's ceiling and U the power-of-two ceiling of the
+    // call's distinct times, so neither the call's own N, nor a length, nor its text length (the staging capacity; exact without buckets,
+    // and then part of the key) is in it
+    if (p.items && p.pack) {
+        int n = snprintf(kb, sizeof(kb), "P%d|%d|%d|U%d|h%d|%d|%d|m%d", p.B, p.N, p.steps, p.U, p.halves, p.want_traj ? 1 : 0, p.chunk, p.method);
+        if (!p.bucket) snprintf(kb + n, sizeof(kb) - n, "|t%d", p.nt);
+        return kb;
+    }
     if (p.items) {
         snprintf(kb, sizeof(kb), "I%d|%d|%d|%d|U%d|h%d|%d|%d|%d|m%d", p.B, p.N, p.nt, p.steps, p.U, p.halves, p.has_lens ? 1 : 0,
                  p.want_traj ? 1 : 0, p.chunk, p.method);
@@ -476,6 +487,23 @@ extern "C" int f5_set_length_buckets(f5_engine* e, int32_t granule) {
     e->sw.len_bucket = granule;
     e->clear_graphs();
     e->gc.capacity = GraphCache::DEFAULT_CAPACITY;
+    return F5_OK;
+}
+extern "C" int f5_set_isolated_rows(f5_engine* e, int32_t on) {
+    if (!e) return fail(F5_EINVAL, "f5_set_isolated_rows: null engine");
+    e->sw.isolated_rows = on != 0;   // (the keys of isolated and rectangular plans differ: no graph goes stale)
+    return F5_OK;
+}
+extern "C" int f5_set_graph_capacity(f5_engine* e, int32_t n) {
+    if (!e) return fail(F5_EINVAL, "f5_set_graph_capacity: null engine");
+    if (n < GraphCache::DEFAULT_CAPACITY || n > GraphCache::MAX_CAPACITY)
+        return fail(F5_EINVAL, "f5_set_graph_capacity: %d graphs outside [%d, %d]", n, (int)GraphCache::DEFAULT_CAPACITY,
+                    (int)GraphCache::MAX_CAPACITY);
+    e->gc.capacity = (size_t)n;
+    while (e->gc.graphs.size() > e->gc.capacity) {   // oldest out first, as a capture makes room
+        e->gc.evict(0);
+        e->gc.stats.evictions++;
+    }
     return F5_OK;
 }
 extern "C" int f5_prepare_sample(f5_engine* e, int32_t B, int32_t n_min, int32_t n_max, int32_t nt_max, int32_t steps, float cfg_strength,

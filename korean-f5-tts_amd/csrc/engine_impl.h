@@ -538,8 +538,8 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
 }
 
 // Attention sub-block on the normed stream w.xn: QKV projection, attention, out-projection with the caller's residual epilogue.
-template <typename T>
-static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, bool qk_norm, const EpiGateRes& out_epi) {
+template <typename T, typename Epi>
+static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, bool qk_norm, const Epi& out_epi) {
     f5_engine* e = f.e;
     hipStream_t s = f.s;
     Packed<T>& P = packed<T>(e);
@@ -589,7 +589,7 @@ static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, boo
 }
 
 // Feed-forward pair on the normed stream w.xn: FF1 with GELU(tanh), FF2 with the caller's residual epilogue.
-template <typename T> static int ff_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, const EpiGateRes& out_epi) {
+template <typename T, typename Epi> static int ff_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, const Epi& out_epi) {
     const int D = f.e->cfg.dim, F = f.e->cfg.ff_dim, pl = f.pl();
     f.ablate(16, w.xn, D);
     CHK(f.gemm(w.xn, D, bw.ff1, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl, f.wt(F5_WT_STORE16)}, pl));
@@ -615,7 +615,8 @@ template <typename T, typename U> static int project_out(const FwdCtx& f, const 
 }
 
 // One DiT forward over Bp packed rows (dit.py:297-327).  mod_row: AdaLN vectors of this step; mod_stride: distance
-// between batch rows' vectors (0 when every row shares the time step, as in sample()).
+// between batch rows' vectors (0 when every row shares the time step, as in sample()).  A packed batch with mod_stride != 0 (a per-item
+// call on packed rows) finds a row's vectors through the rowmap's batch row: layernorm_rows_kernel and EpiGateResRows.
 template <typename T>
 static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N,
                            const float* mod_row, int mod_stride, const int* lens_dev, int drop_cond_first,
@@ -640,9 +641,14 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
         return wpf ? Prefetch{(const char*)a.w, (size_t)a.N * a.ldw * sizeof(T), (const char*)b.w, (size_t)b.N * b.ldw * sizeof(T)} : Prefetch{};
     };
     // AdaLN LayerNorm of the stream into out (rows of T, or pre-split f32 rows): out = LN(x) * (1 + scale) + shift
+    const bool row_mods = pk && mod_stride != 0;   // every batch row of a packed batch has its own vectors
     auto adaln = [&](auto* out, const float* scale, const float* shift, const Prefetch& pf, int planar) {
         using TO = std::remove_pointer_t<decltype(out)>;
         return pr.timed(PC_LN, s, [&] {
+            if (row_mods)
+                hipLaunchKernelGGL((layernorm_rows_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, out, D, rows, D, 1e-6f, scale,
+                                   shift, mod_stride, pf, ml, pk.rowmap, planar, f.wt(F5_WT_LN));
+            else
             hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, out, D, rows, D, 1e-6f, scale, shift,
                                mod_stride, N, 1, pf, ml, planar, f.wt(F5_WT_LN));
             return hipGetLastError();
@@ -651,10 +657,14 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
     for (int l = 0; l < c.depth; ++l) {
         BlockW<T>& bw = P.blocks[l];
         const float* m = mod_row + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        const EpiGateRes attn_epi{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens, f.wt(F5_WT_GATE_RES)};
+        const EpiGateRes ff_epi{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr, f.wt(F5_WT_GATE_RES)};
         HIPCHK(adaln(w.xn, m + D, m, prefetch(bw.qkv, bw.out), pl));
-        CHK(attention_block<T>(f, w, bw, qk_norm, EpiGateRes{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens, f.wt(F5_WT_GATE_RES)}));
+        if (row_mods) CHK(attention_block<T>(f, w, bw, qk_norm, EpiGateResRows{attn_epi, pk.rowmap}));
+        else CHK(attention_block<T>(f, w, bw, qk_norm, attn_epi));
         HIPCHK(adaln(w.xn, m + 4 * D, m + 3 * D, prefetch(bw.ff1, bw.ff2), pl));
-        CHK(ff_block<T>(f, w, bw, EpiGateRes{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr, f.wt(F5_WT_GATE_RES)}));
+        if (row_mods) CHK(ff_block<T>(f, w, bw, EpiGateResRows{ff_epi, pk.rowmap}));
+        else CHK(ff_block<T>(f, w, bw, ff_epi));
     }
     if (long_skip) {   // x = long_skip_connection(cat((x, residual), dim=-1))   (dit.py:323-324)
         auto cat_skip = [&](auto* cat) {
@@ -764,9 +774,10 @@ static int run_backbone(f5_engine* e, Work<T>& w, const float* y, const float* c
 // ... with one time row per batch row, gathered by the caller (mod_gather_kernel): rows [Bp, modN] (DiT) or [Bp, D] (UNetT)
 template <typename T>
 static int run_backbone_rows(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, const float* rows,
-                             const int* lens_dev, const float* text_first, const float* text_second, hipStream_t s) {
+                             const int* lens_dev, const float* text_first, const float* text_second, hipStream_t s,
+                             const RowPack& pk = RowPack{}) {
     if (e->cfg.backbone == F5_BACKBONE_DIT)
-        return run_dit_forward<T>(e, w, y, cond, B, Bp, N, rows, e->modN, lens_dev, 0, text_first, text_second, s);
+        return run_dit_forward<T>(e, w, y, cond, B, Bp, N, rows, e->modN, lens_dev, 0, text_first, text_second, s, pk);
     return run_unett_forward<T>(e, w, y, cond, B, Bp, N, rows, e->cfg.dim, lens_dev, 0, text_first, text_second, s);
 }
 // uploads a call's small tables through pinned staging: nT times to w.tdev and, where lengths are given, the plan's lens and
@@ -821,7 +832,7 @@ static int upload_small(f5_engine* e, Work<T>& w, const SamplePlan& p, const flo
         HIPCHK(hipMemcpyAsync(w.it_cfg, ch, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.it_steps, sh, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(w.it_idx, ih, n_idx * 4, hipMemcpyHostToDevice, s));
-        if (call->span) {   // the staging kernel's row table, in the rowmap (a per-item body is never packed)
+        if (call->span) {   // the staging kernel's row table, in the rowmap (the staging runs before the body, which fills the rowmap of a packed plan)
             int* rh = ih + n_idx;
             memcpy(rh, call->rows_host, (size_t)B * 4);
             HIPCHK(hipMemcpyAsync(w.rowmap, rh, (size_t)B * 4, hipMemcpyHostToDevice, s));
@@ -952,7 +963,7 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
                                   dit ? e->modN : c.dim);
                 return hipGetLastError();
             }));
-            return run_backbone_rows<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, w.mod_rows, lens, tc, p.use_cfg ? tu : tc, s);
+            return run_backbone_rows<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, w.mod_rows, lens, tc, p.use_cfg ? tu : tc, s, pk);
         }
         if (!p.split) return run_backbone<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, row, 0, lens, 0, tc, p.use_cfg ? tu : tc, s, pk);
         // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
@@ -970,8 +981,9 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         const size_t yo = p.frame_at(k) * mel;
         return e->prof.timed(PC_MISC, s, [&] {
             if (p.items) {
-                launch_midpoint_half_cfg_items(s, w.y + yo, w.pred, k.bc, N, mel, w.it_t + (size_t)k.u0 * (p.steps + 1), w.it_cfg + k.u0,
-                                               w.it_steps + k.u0, p.steps, i, p.use_cfg ? 1 : 0, w.y_mid + yo);
+                launch_midpoint_half_cfg_items(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr,
+                                               w.it_t + (size_t)k.u0 * (p.steps + 1), w.it_cfg + k.u0, w.it_steps + k.u0, p.steps, i,
+                                               p.use_cfg ? 1 : 0, w.y_mid + yo);
                 return hipGetLastError();
             }
             launch_midpoint_half_cfg(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr, tgrid, i,
@@ -985,8 +997,9 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         float* slot = p.want_traj ? w.traj_buf + (size_t)(i + 1) * half + yo : nullptr;
         return e->prof.timed(PC_MISC, s, [&] {
             if (p.items) {
-                launch_euler_cfg_items(s, w.y + yo, w.pred, k.bc, N, mel, w.it_t + (size_t)k.u0 * (p.steps + 1), w.it_cfg + k.u0,
-                                       w.it_steps + k.u0, p.steps, i, p.use_cfg ? 1 : 0, slot);
+                launch_euler_cfg_items(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr,
+                                       w.it_t + (size_t)k.u0 * (p.steps + 1), w.it_cfg + k.u0, w.it_steps + k.u0, p.steps, i,
+                                       p.use_cfg ? 1 : 0, slot);
                 return hipGetLastError();
             }
             launch_euler_cfg(s, w.y + yo, w.pred, k.bc, N, mel, pk.row_start, pk ? lens_dev + p.lens_at(k) : nullptr, tgrid, i, p.cfg_strength,
@@ -1026,6 +1039,31 @@ template <typename T> static bool bucket_eligible(f5_engine* e, const int32_t* l
     if (nc + 1 > c.max_pos || (c.conv_layers > 0 && nc > packed<T>(e).text_pos_rows)) return false;
     *n_cap = nc;
     return true;
+}
+// An isolated per-item call (Switches::isolated_rows): every row as if it were alone in the batch, which the packed body gives -- the text
+// embedded per row at its own length, conv-pos and attention keys masked there, everything else row-wise.  That is a promise, so a call
+// that cannot run on the packed body is refused, naming the reason, instead of running rectangular: the UNetT (never packed),
+// F5_SPLIT_CFG (steps padded rows per half), text_embedding_average_upsampling (stays on the exact path, as for length buckets) and a
+// ceiling outside the rotary or text position tables.  *n_cap: the frames the call is planned at -- its length bucket's ceiling, or N rounded up to 4.
+template <typename T> static int isolated_ceiling(f5_engine* e, const char* who, int N, int* n_cap) {
+    const f5_config& c = e->cfg;
+    if (c.backbone != F5_BACKBONE_DIT)
+        return fail(F5_EINVAL, "%s: isolated rows (f5_set_isolated_rows) run on packed rows, which the UNetT backbone does not have", who);
+    if (e->sw.split_cfg) return fail(F5_EINVAL, "%s: isolated rows (f5_set_isolated_rows) cannot run with F5_SPLIT_CFG=1 (it steps padded rows)", who);
+    if (c.options & F5_OPT_TEXT_AVG_UPSAMPLE)
+        return fail(F5_EINVAL, "%s: isolated rows (f5_set_isolated_rows) cannot run with text_embedding_average_upsampling "
+                               "(F5_OPT_TEXT_AVG_UPSAMPLE stays on the exact path)", who);
+    // Without buckets the ceiling is N rounded up to 4, the granule of a packed batch row: the launch geometry is that of B rows of the
+    // ceiling, and rows that fill their N (a B = 1 call always does) would otherwise pack into more rows than it has.
+    const int g = e->sw.len_bucket, nc = round_up(N, g > 0 ? g : 4);
+    if (nc + 1 > c.max_pos)
+        return fail(F5_EINVAL, "%s: isolated rows: N=%d is planned at %d frames, which exceeds the rotary table (max_pos = %d rows)", who, N, nc,
+                    c.max_pos);
+    if (c.conv_layers > 0 && nc > packed<T>(e).text_pos_rows)
+        return fail(F5_EINVAL, "%s: isolated rows: N=%d is planned at %d frames, which exceeds aux.text_pos (%d rows)", who, N, nc,
+                    packed<T>(e).text_pos_rows);
+    *n_cap = nc;
+    return F5_OK;
 }
 // the text staging buffer is part of the arena plan: a longer text moves the carve offsets
 static void reserve_text(f5_engine* e, int nt) {
@@ -1087,25 +1125,36 @@ static hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t sp
 template <typename T> int EngineOps<T>::run_sample(f5_engine* e, const SampleCall& c) {
     const int B = c.B, N = c.N, nt = c.nt, mel = e->cfg.mel_dim;
     hipStream_t s = c.stream;
-    reserve_text(e, nt);
-    // ---- (a) the plan: per-item tables on the rectangular body at the exact N, or one grid for the batch, in N's length bucket if it takes one
+    // ---- (a) the plan: per-item tables on the rectangular body at the exact N -- or, isolated, on packed rows with every row's own length --
+    // or one grid for the batch; in N's length bucket if the call takes one
     int Nc = N;   // frames per utterance in the arena: N, or the ceiling of N's length bucket
-    const bool bucket = !c.per_item && bucket_eligible<T>(e, c.lens_host, B, N, &Nc);
+    const bool iso = c.per_item && e->sw.isolated_rows;
+    if (iso) CHK(isolated_ceiling<T>(e, c.who, N, &Nc));   // (refused before anything is reserved, staged or launched)
+    reserve_text(e, nt);
+    const bool bucket = iso ? e->sw.len_bucket > 0 : !c.per_item && bucket_eligible<T>(e, c.lens_host, B, N, &Nc);
     PlanOptions o = plan_options(c);
-    if (bucket) {
-        o.nt = e->res_nt;
-        o.n_true = N;
+    if (bucket) o.nt = e->res_nt;
+    if (bucket && !iso) o.n_true = N;
+    std::vector<float> times_iso;     // an isolated call's time rows, the last one repeated up to the next power of two
+    std::vector<int32_t> lens_iso;    // ... and its lengths (lens_host NULL: every row has N frames)
+    if (iso) {
+        o.isolated = true;
+        o.bucket = bucket;
+        while (o.U & (o.U - 1)) o.U += o.U & -o.U;
+        times_iso = c.items.rows->times;
+        times_iso.resize((size_t)o.U, times_iso.back());
+        lens_iso = c.lens_host ? std::vector<int32_t>(c.lens_host, c.lens_host + B) : std::vector<int32_t>((size_t)B, N);
     }
-    const SamplePlan p = plan_sample(e, B, Nc, c.lens_host, o);
+    const SamplePlan p = plan_sample(e, B, Nc, iso ? lens_iso.data() : c.lens_host, o);
     if (c.per_item) reserve_items(e, p.U);
     CHK(ensure_arena(e, B, Nc, c.steps));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     // ---- inputs -> arena
     const std::vector<float> grid = c.per_item ? std::vector<float>() : time_table(c.t_host, c.steps, c.method);
-    const std::vector<float>& times = c.per_item ? c.items.rows->times : grid;
-    const std::vector<int32_t> own(bucket ? B : 0, N);
-    CHK(upload_small<T>(e, w, p, times.data(), (int)times.size(), bucket ? own.data() : c.lens_host, &c, s));
+    const std::vector<float>& times = iso ? times_iso : c.per_item ? c.items.rows->times : grid;
+    const std::vector<int32_t> own(bucket && !iso ? B : 0, N);
+    CHK(upload_small<T>(e, w, p, times.data(), (int)times.size(), iso ? lens_iso.data() : bucket ? own.data() : c.lens_host, &c, s));
     const size_t frame = (size_t)mel * sizeof(float), row_in = N * frame, row_arena = Nc * frame;   // one utterance, caller's / arena's
     const size_t half = (size_t)B * row_arena;
     if (c.cond_frames < Nc) HIPCHK(hipMemsetAsync(w.in_cond, 0, half, s));   // F.pad(cond, ..., N - cond_seq_len) (cfm.py:145)
@@ -1120,7 +1169,7 @@ template <typename T> int EngineOps<T>::run_sample(f5_engine* e, const SampleCal
     }
     // ---- (b) the start state: the caller's y0, or the rows of a previous state (another N, another row order) and of y_new, by one launch
     if (c.span) {
-        launch_span_stage(s, w.y, c.prev_state, c.y_new, reinterpret_cast<const int*>(w.rowmap), B, N, c.prev_N, mel);
+        launch_span_stage(s, w.y, c.prev_state, c.y_new, reinterpret_cast<const int*>(w.rowmap), B, N, c.prev_N, mel, Nc);
         KCHK();
     } else
         HIPCHK(copy_rows(w.y, row_arena, c.y0, row_in, row_in, B, s));

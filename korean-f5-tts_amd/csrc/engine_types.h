@@ -162,6 +162,10 @@ struct Switches {
     // F5_STORE_WT=<mask of F5_WT_*, f5_common.h>: which classes of block kernel store write-through where a forward runs at <= 4,096 rows
     // (FwdCtx::wt).  Results do not depend on it.  The default: the classes that paid on their own at C2.
     int store_wt = F5_WT_DEFAULT;
+    // f5_set_isolated_rows (off by default; no environment variable): f5_sample_items and f5_sample_span run on the packed body with each
+    // row's own length in the device tables -- every row as if it were alone in the batch, whatever attn_mask_enabled says -- and, with
+    // len_bucket on, at N's bucket ceiling.  A call that cannot keep that promise is refused (isolated_ceiling, engine_impl.h).
+    bool isolated_rows = false;
 };
 inline bool valid_len_bucket(long g) { return g == 0 || (g >= 8 && g <= 1024 && g % 8 == 0); }
 
@@ -347,7 +351,7 @@ struct SamplePlan {
     bool use_cfg = true, has_lens = false, want_traj = false;
     int halves = 2;       // batch rows per utterance in a backbone call: cond + uncond, or 1 without CFG
     int evals = 1;        // backbone evaluations per step (midpoint: 2)
-    bool pack = false;    // RowPack: attn_mask_enabled DiT batches with lengths, unless F5_PACK_ROWS=0 or F5_SPLIT_CFG=1; every bucket plan
+    bool pack = false;    // RowPack: attn_mask_enabled DiT batches with lengths, unless F5_PACK_ROWS=0 or F5_SPLIT_CFG=1; every bucket plan; every isolated plan
     // Length bucket (Switches::len_bucket): N above is the bucket's ceiling -- arena layout, launch grids, the graph key -- and every
     // utterance has n_true <= N frames, which only the device tables (lens, lens_plain, row_start) and the copies around the body know.
     // nt is then the capacity of the text staging buffer (f5_engine::res_nt), filled with -1 behind the call's tokens.  0: no bucket.
@@ -355,9 +359,13 @@ struct SamplePlan {
     bool split = false;   // F5_SPLIT_CFG=1: the halves as two stream chains (DiT with CFG, profiler off); one chunk, no packing
     int chunk = 0;
     // f5_sample_items: per-item grids, guidance and step counts in device tables (Work::it_*).  steps is then the largest step count,
-    // U the rows of the time path (the distinct evaluation times of the call), and cfg_strength is not read.  Never packed, never split.
+    // U the rows of the time path (the distinct evaluation times of the call), and cfg_strength is not read.  Never split; packed when
+    // isolated (Switches::isolated_rows): has_lens is then set, U is the call's count rounded up to a power of two (the rows behind the
+    // call's own repeat its last time; no index points at them), and with `bucket` N is the ceiling of the call's length bucket and nt
+    // the capacity of the text staging buffer, as in a bucket plan of sample() -- but every utterance keeps its own length.
     bool items = false;
     int U = 0;
+    bool bucket = false;
     std::vector<Chunk> chunks;
     // Where a chunk lives in the per-call tables.  Work::lens holds [bc][the same bc] per chunk whatever `halves` is; a chunk's
     // row_start table has halves * bc + 1 entries; rowmap is carved for 2 B rows of round_up(N, 4); state, cond and text are [B, N, *].
@@ -378,6 +386,8 @@ struct PlanOptions {
     int n_true = 0;       // > 0: a length-bucket plan -- N is the bucket's ceiling, every utterance has n_true frames and lens_host is ignored
     bool items = false;   // a per-item plan of U time rows (cfg_strength: 1 when any item is guided, else 0)
     int U = 0;
+    bool isolated = false;   // a per-item plan on packed rows: lens_host holds every utterance's own length (never null) and N is the arena's
+    bool bucket = false;     // ... and N is a length bucket's ceiling, nt the text staging capacity
     static PlanOptions whole_batch(int B) {
         PlanOptions o;
         o.chunk = B;

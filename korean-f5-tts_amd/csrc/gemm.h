@@ -252,6 +252,19 @@ struct EpiGateRes {
     }
 };
 
+// EpiGateRes on a PACKED batch (RowPack) whose batch rows have their own gate vectors -- a per-item call on packed rows: row m's batch
+// row is rowmap[m].x, not m / rows_per_batch.  A type of its own, so that the kernels of every other forward are the ones they always
+// were.  A packed batch has no padded rows to leave untouched (lens is not read), and a run of 64 rows may hold many batch rows, so
+// the staged form (two gate vectors per half) does not apply.  The kernels read rows below the device row count only, which
+// fill_rowmap_kernel has written.
+struct EpiGateResRows : EpiGateRes {
+    const int2* rowmap;
+    __device__ __forceinline__ RowCtx row(int m) const {
+        return {(size_t)m * ld, gate ? gate + (size_t)rowmap[m].x * gate_stride : nullptr, false};
+    }
+    __device__ __forceinline__ bool staged_ok(bool) const { return false; }
+};
+
 // Fused QKV projection epilogue (modules.py:469-497): bias, interleaved-pair rotary on the first `pe_heads` heads of
 // q and k, q pre-scaled by dim_head^-0.5, head split.  q,k -> [B', H, Nseq, 64]; v -> TRANSPOSED [B', H, 64, Npad]
 // (so that both attention B-operands are K-contiguous).  16-column sub-tiles of the V third use the transposed

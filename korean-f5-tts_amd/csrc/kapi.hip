@@ -520,15 +520,36 @@ extern "C" int f5k_euler_cfg_items(float* y, const float* pred, int32_t B, int32
                                    const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg, float* traj_slot,
                                    f5_stream stream) {
     CHK(items_args("f5k_euler_cfg_items", y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, traj_slot, false));
-    launch_euler_cfg_items((hipStream_t)stream, y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, use_cfg ? 1 : 0, traj_slot);
+    launch_euler_cfg_items((hipStream_t)stream, y, pred, B, N, mel, nullptr, nullptr, t_items, cfg_items, steps_items, steps_max, step,
+                           use_cfg ? 1 : 0, traj_slot);
     return glue_done((hipStream_t)stream);
 }
 extern "C" int f5k_midpoint_half_cfg_items(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const float* t_items,
                                            const float* cfg_items, const int32_t* steps_items, int32_t steps_max, int32_t step,
                                            int32_t use_cfg, float* y_mid, f5_stream stream) {
     CHK(items_args("f5k_midpoint_half_cfg_items", y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, y_mid, true));
-    launch_midpoint_half_cfg_items((hipStream_t)stream, y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, use_cfg ? 1 : 0,
-                                   y_mid);
+    launch_midpoint_half_cfg_items((hipStream_t)stream, y, pred, B, N, mel, nullptr, nullptr, t_items, cfg_items, steps_items, steps_max, step,
+                                   use_cfg ? 1 : 0, y_mid);
+    return glue_done((hipStream_t)stream);
+}
+// (the packed forms: row_start and lens are device tables the caller owns, as for f5k_euler_cfg -- the caller keeps them inside pred)
+extern "C" int f5k_euler_cfg_items_packed(float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start,
+                                          const int32_t* lens, const float* t_items, const float* cfg_items, const int32_t* steps_items,
+                                          int32_t steps_max, int32_t step, int32_t use_cfg, float* traj_slot, f5_stream stream) {
+    CHK(items_args("f5k_euler_cfg_items_packed", y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, traj_slot, false));
+    if (!row_start || !lens) return fail(F5_EINVAL, "f5k_euler_cfg_items_packed: bad arguments (row_start and lens are required)");
+    launch_euler_cfg_items((hipStream_t)stream, y, pred, B, N, mel, row_start, lens, t_items, cfg_items, steps_items, steps_max, step,
+                           use_cfg ? 1 : 0, traj_slot);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_midpoint_half_cfg_items_packed(const float* y, const float* pred, int32_t B, int32_t N, int32_t mel, const int32_t* row_start,
+                                                  const int32_t* lens, const float* t_items, const float* cfg_items,
+                                                  const int32_t* steps_items, int32_t steps_max, int32_t step, int32_t use_cfg, float* y_mid,
+                                                  f5_stream stream) {
+    CHK(items_args("f5k_midpoint_half_cfg_items_packed", y, pred, B, N, mel, t_items, cfg_items, steps_items, steps_max, step, y_mid, true));
+    if (!row_start || !lens) return fail(F5_EINVAL, "f5k_midpoint_half_cfg_items_packed: bad arguments (row_start and lens are required)");
+    launch_midpoint_half_cfg_items((hipStream_t)stream, y, pred, B, N, mel, row_start, lens, t_items, cfg_items, steps_items, steps_max, step,
+                                   use_cfg ? 1 : 0, y_mid);
     return glue_done((hipStream_t)stream);
 }
 extern "C" int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, int32_t rows, int32_t nidx, int32_t width, f5_stream stream) {
@@ -542,7 +563,15 @@ extern "C" int f5k_span_stage(float* y, const float* prev_state, int32_t prev_B,
     if (!y || !rows || !rows_host || B <= 0 || N <= 0 || mel <= 0 || mel % 4)
         return fail(F5_EINVAL, "f5k_span_stage: bad arguments (mel %% 4 == 0)");
     CHK(check_span_rows("f5k_span_stage", rows_host, B, prev_state, prev_B, prev_N, y_new));
-    launch_span_stage((hipStream_t)stream, y, prev_state, y_new, rows, B, N, prev_N, mel);
+    launch_span_stage((hipStream_t)stream, y, prev_state, y_new, rows, B, N, prev_N, mel, N);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_span_stage_pitched(float* y, int32_t pitch, const float* prev_state, int32_t prev_B, int32_t prev_N, const float* y_new,
+                                      const int32_t* rows, const int32_t* rows_host, int32_t B, int32_t N, int32_t mel, f5_stream stream) {
+    if (!y || !rows || !rows_host || B <= 0 || N <= 0 || mel <= 0 || mel % 4 || pitch < N)
+        return fail(F5_EINVAL, "f5k_span_stage_pitched: bad arguments (mel %% 4 == 0, pitch >= N)");
+    CHK(check_span_rows("f5k_span_stage_pitched", rows_host, B, prev_state, prev_B, prev_N, y_new));
+    launch_span_stage((hipStream_t)stream, y, prev_state, y_new, rows, B, N, prev_N, mel, pitch);
     return glue_done((hipStream_t)stream);
 }
 extern "C" int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream) {

@@ -123,6 +123,14 @@ class Engine:
         captured graph serves every length of a bucket (include/f5_hip.h).  Clears the graph cache."""
         _lib.check(self.lib.f5_set_length_buckets(self._h, int(granule)), "f5_set_length_buckets")
 
+    def set_isolated_rows(self, on: bool):
+        """sample_items() / sample_span() on packed rows, every row as if it were alone in the batch (f5_set_isolated_rows)."""
+        _lib.check(self.lib.f5_set_isolated_rows(self._h, int(bool(on))), "f5_set_isolated_rows")
+
+    def set_graph_capacity(self, n: int):
+        """The graph cache holds n graphs, 16 <= n <= 64 (f5_set_graph_capacity); set_length_buckets puts it back to 16."""
+        _lib.check(self.lib.f5_set_graph_capacity(self._h, int(n)), "f5_set_graph_capacity")
+
     def prepare_sample(self, batch: int, n_min: int, n_max: int, nt_max: int, steps: int, cfg_strength: float, *,
                        method: str = "euler", want_traj: bool = True):
         """Captures the graphs of every length bucket in [n_min, n_max] ahead of the first request (needs length buckets)."""

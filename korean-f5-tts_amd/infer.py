@@ -170,15 +170,21 @@ def load_checkpoint(model, ckpt_path: str, device: str, dtype=None, use_ema: boo
 
 
 def load_model(model_cls, model_cfg: dict, ckpt_path: str | None, mel_spec_type=mel_spec_type, vocab_file: str = "",
-               ode_method=ode_method, use_ema=True, device="cuda", precision="parity", length_bucket=0, **_ignored):
+               ode_method=ode_method, use_ema=True, device="cuda", precision="parity", length_bucket=0, isolated_rows=False,
+               **_ignored):
     """CFM(transformer=model_cls(**model_cfg, text_num_embeds=vocab_size + 1, mel_dim=100), ...) + load_checkpoint.
     `ckpt_path=None` keeps whatever weights the caller loads afterwards (e.g. init_synthetic()).
     length_bucket (not a reference argument; DiT only): granule, in frames, of the length-bucketed sample() graphs -- one
-    captured graph per bucket serves the varying durations of infer_process's chunks (0: off)."""
+    captured graph per bucket serves the varying durations of infer_process's chunks (0: off).
+    isolated_rows (not a reference argument; DiT only): sample_items() / sample_span() -- and with them synthesize_batch, synthesize_prompts,
+    synthesize_script and the stream pool where they run per-item -- compute every row as if it were alone in its batch
+    (DiT.set_isolated_rows)."""
     vocab_char_map, vocab_size = load_vocab(vocab_file) if vocab_file else (None, 256)
     tr = model_cls(**model_cfg, text_num_embeds=vocab_size + 1, mel_dim=n_mel_channels, precision=precision)
     if length_bucket:
         tr.set_length_buckets(length_bucket)
+    if isolated_rows:
+        tr.set_isolated_rows(True)
     model = CFM(transformer=tr,
                 mel_spec_kwargs=dict(n_fft=n_fft, hop_length=hop_length, win_length=win_length,
                                      n_mel_channels=n_mel_channels, target_sample_rate=target_sample_rate,

@@ -236,7 +236,15 @@ def open_stream(model, vocoder, voice, *, out_rate=SAMPLE_RATE, sample_format="f
 
 
 # ---------------------------------------------------------------------------------------------------------------- the pool
-def pool_tick(waiting, batch_frames, max_items, first_alone, cursor):
+def tick_cost(frames, packed):
+    """What a tick of rows of these frame counts costs against batch_frames: rows x longest row, or (packed: the rows run on packed
+    rows, as an isolated pool's do) the sum of the rows' frames, each rounded up to 4 as the packed layout rounds them."""
+    if packed:
+        return sum(-(-f // 4) * 4 for f in frames)
+    return len(frames) * max(frames) if frames else 0
+
+
+def pool_tick(waiting, batch_frames, max_items, first_alone, cursor, packed=False):
     """Which chunks run in the next tick of a StreamPool: a pure function of the queue.  `waiting` lists the requests that have
     chunks waiting, in submission order, as (request id, index of its first waiting chunk, [frames sample() runs each waiting chunk
     at, in the request's order]); ids are integers that ascend with submission.  Returns (items, cursor): the tick's rows as
@@ -252,11 +260,16 @@ def pool_tick(waiting, batch_frames, max_items, first_alone, cursor):
         when all have given and the budget is not spent they give their next one, and so on.  The tick ends where an item does
         not fit, and that request's id is the new cursor: the requests the tick did not reach are first in the next one, ahead of
         every request it served.  So of two requests that wait through two round-robin ticks in a row, one never gets rows in both
-        while the other gets none -- no request is passed over twice in a row.  When everything waiting was taken the cursor stays."""
-    items, longest = [], 0
+        while the other gets none -- no request is passed over twice in a row.  When everything waiting was taken the cursor stays.
+
+    packed=True (a pool with isolate=True, whose ticks run on packed rows): a tick costs the sum of its rows' frames, each rounded up
+    to 4 (tick_cost), so an item joins while that sum with its own frames stays <= batch_frames; everything else is as above."""
+    items, longest, taken = [], 0, []
 
     def fits(frames):
         rows = len(items)
+        if packed:
+            return rows == 0 or (rows < max_items and (batch_frames is None or tick_cost(taken + [frames], True) <= batch_frames))
         return rows == 0 or (rows < max_items and (batch_frames is None or (rows + 1) * max(longest, frames) <= batch_frames))
 
     live = [w for w in waiting if w[2]]
@@ -266,6 +279,7 @@ def pool_tick(waiting, batch_frames, max_items, first_alone, cursor):
             if not fits(frames[0]):
                 break
             items.append((rid, 0))
+            taken.append(frames[0])
             longest = max(longest, frames[0])
         return items, cursor
     if not live:
@@ -279,11 +293,12 @@ def pool_tick(waiting, batch_frames, max_items, first_alone, cursor):
             if not fits(frames[depth]):
                 return items, rid
             items.append((rid, k + depth))
+            taken.append(frames[depth])
             longest = max(longest, frames[depth])
     return items, cursor
 
 
-def pool_slice(under_way, waiting, batch_frames, max_items, first_alone, cursor):
+def pool_slice(under_way, waiting, batch_frames, max_items, first_alone, cursor, packed=False):
     """Which rows run in the next tick of a StreamPool that solves in slices (open_pool(slice_steps=...)): a pure function of the
     rows under way and the queue.  `under_way` lists the chunks whose solve has begun and not ended, in the order they joined, as
     (request id, chunk index, frames); `waiting` is pool_tick's list.  Returns (items, cursor): the tick's rows as (request id,
@@ -300,11 +315,15 @@ def pool_slice(under_way, waiting, batch_frames, max_items, first_alone, cursor)
         in ascending id from the first id >= cursor, wrapping around, give one chunk each, then their next one, and so on.  Where
         a waiting item does not fit the tick ends and that request's id is the new cursor, so pool_tick's property holds: of two
         requests that wait through two round-robin ticks in a row, one never gets rows in both while the other gets none.  When
-        everything waiting was taken, or a row under way did not fit, the cursor stays."""
-    items, longest = [], 0
+        everything waiting was taken, or a row under way did not fit, the cursor stays.
+
+    packed=True: pool_tick's packed budget -- the sum of the rows' frames, each rounded up to 4 -- over both kinds of row alike."""
+    items, longest, taken = [], 0, []
 
     def fits(frames):
         rows = len(items)
+        if packed:
+            return rows == 0 or (rows < max_items and (batch_frames is None or tick_cost(taken + [frames], True) <= batch_frames))
         return rows == 0 or (rows < max_items and (batch_frames is None or (rows + 1) * max(longest, frames) <= batch_frames))
 
     live = [w for w in waiting if w[2]]
@@ -314,12 +333,14 @@ def pool_slice(under_way, waiting, batch_frames, max_items, first_alone, cursor)
             if not fits(frames):
                 break
             items.append((rid, k))
+            taken.append(frames)
             longest = max(longest, frames)
         return items, cursor
     for rid, k, frames in under_way:
         if not fits(frames):
             return items, cursor
         items.append((rid, k))
+        taken.append(frames)
         longest = max(longest, frames)
     if not live:
         return items, cursor
@@ -332,6 +353,7 @@ def pool_slice(under_way, waiting, batch_frames, max_items, first_alone, cursor)
             if not fits(frames[depth]):
                 return items, rid
             items.append((rid, k + depth))
+            taken.append(frames[depth])
             longest = max(longest, frames[depth])
     return items, cursor
 
@@ -474,7 +496,7 @@ class StreamPool:
     count every slice; decode_calls, emit_launches and copies only the ticks that ended a row."""
 
     def __init__(self, model, vocoder, voices, *, batch_frames, max_items, first_alone, lookahead, nfe_step, cfg_strength,
-                 sway_sampling_coef, seed, text_tokenizer, clip_silence, slice_steps=None):
+                 sway_sampling_coef, seed, text_tokenizer, clip_silence, slice_steps=None, isolate=False):
         from . import infer as I
 
         I._require_text_tokenizer(model, text_tokenizer)
@@ -488,6 +510,11 @@ class StreamPool:
         if slice_steps is not None and (isinstance(slice_steps, bool) or int(slice_steps) != slice_steps or int(slice_steps) < 1):
             raise ValueError(f"open_pool: slice_steps = {slice_steps} (need None or a whole number of steps, at least 1)")
         self.slice_steps = None if slice_steps is None else int(slice_steps)
+        self.isolate = bool(isolate)
+        if self.isolate:   # every row as if alone in its tick: the model's switch (raises for a backbone without packed rows), and room for the ticks' graphs
+            tr = getattr(model, "transformer", model)
+            tr.set_isolated_rows(True)
+            tr.set_graph_capacity(64)
         self.spans, self._rows = [], []     # slice_steps: per tick the (start, steps run) of each row; the rows under way
         self.model, self.vocoder, self.text_tokenizer = model, vocoder, text_tokenizer
         self.batch_frames, self.max_items = batch_frames, int(max_items)
@@ -512,8 +539,9 @@ class StreamPool:
 
     def stats(self) -> dict:
         """ticks run; sample_calls / decode_calls / emit_launches: model.sample, decode_ragged and wave_emit calls; copies: device
-        to host copies; packets handed out; prompt_passes: prompt preparations this pool ran."""
-        return dict(self._stats)
+        to host copies; packets handed out; prompt_passes: prompt preparations this pool ran; isolated: True, for a pool opened
+        with isolate=True (any other pool's dict is the one it always was: read it with .get("isolated", False), or pool.isolate)."""
+        return dict(self._stats, isolated=True) if self.isolate else dict(self._stats)
 
     def idle(self) -> bool:
         return not self._pending and not self._rows and not any(r.next < r.stop for r in self._requests)
@@ -534,7 +562,7 @@ class StreamPool:
         waiting = [(r.id, r.next, r.plan["ends"][r.next:r.stop]) for r in self._requests if r.next < r.stop]
         # batch_frames=None is a session's: every chunk as its own B = 1 sample()
         items, self._cursor = pool_tick(waiting, self.batch_frames, self.max_items if self.batch_frames is not None else 1,
-                                        self.first_alone, self._cursor)
+                                        self.first_alone, self._cursor, packed=self.isolate)
         if not items:
             return None
         by_id = {r.id: r for r in self._requests}
@@ -543,7 +571,8 @@ class StreamPool:
         batch, rows = self._batch_of(run)
         # a tick whose rows all carry the pool's settings is one sample(); any other is one sample_items() with the rows' own
         row_kw = [r.client.sample_kw for r, _ in run]
-        if all(kw == self.sample_kw for kw in row_kw):
+        # (an isolated pool always takes sample_items: the model's switch is about the per-item calls)
+        if not self.isolate and all(kw == self.sample_kw for kw in row_kw):
             sample, kw = self.model.sample, self.sample_kw
         else:
             sample, kw = self.model.sample_items, {name: [rk[name] for rk in row_kw] for name in self.sample_kw}
@@ -562,7 +591,7 @@ class StreamPool:
         waiting = [(r.id, r.next, r.plan["ends"][r.next:r.stop]) for r in self._requests if r.next < r.stop]
         under_way = [(row.req.id, row.k, row.req.plan["ends"][row.k]) for row in self._rows]
         items, self._cursor = pool_slice(under_way, waiting, self.batch_frames, self.max_items if self.batch_frames is not None else 1,
-                                         self.first_alone, self._cursor)
+                                         self.first_alone, self._cursor, packed=self.isolate)
         if not items:
             return None
         by_id, known = {r.id: r for r in self._requests}, {(row.req.id, row.k): row for row in self._rows}
@@ -689,14 +718,18 @@ class StreamPool:
 
 
 def open_pool(model, vocoder, voices, *, batch_frames, max_items=64, first_alone=True, lookahead=0, nfe_step=32, cfg_strength=2.0,
-              sway_sampling_coef=-1.0, seed=None, text_tokenizer=None, clip_silence=False, slice_steps=None) -> StreamPool:
+              sway_sampling_coef=-1.0, seed=None, text_tokenizer=None, clip_silence=False, slice_steps=None, isolate=False) -> StreamPool:
     """A pool that serves many streaming clients from one model: voices is a VoiceBank or the dict prepare_voices takes (prepared
     once, here).  batch_frames: the budget of a tick, rows x longest row (None: every chunk as its own B = 1 sample(), as in
     open_stream; the ticks then share only the emit); max_items: rows of a tick at most; first_alone: a waiting first chunk keeps
     later chunks out of its tick (pool_tick has the rule); lookahead: ticks enqueued ahead of the one the host waits for;
     slice_steps: None, or the steps a tick runs at most -- the pool then solves in slices and re-forms the batch between them
-    (StreamPool has the rules).  The
+    (StreamPool has the rules); isolate: every row of a tick is computed as if it were alone in it -- a client's audio does not depend on
+    who shares its tick, and equals a session's (batch_frames=None) bit for bit, also with `attn_mask_enabled=False`.  It turns on the
+    model's isolated rows (DiT.set_isolated_rows; DiT only) and a graph cache of 64, every tick runs as model.sample_items /
+    model.sample_span on packed rows, and batch_frames budgets a tick by the sum of its rows' frames, each rounded up to 4 (what a
+    packed tick costs), not rows x longest row.  The
     sampler settings are the pool's defaults: pool.connect may give a client its own.  Refuses what open_stream refuses.  See StreamPool, and pool.connect for a client's side."""
     return StreamPool(model, vocoder, voices, batch_frames=batch_frames, max_items=max_items, first_alone=first_alone,
                       lookahead=lookahead, nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                      seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence, slice_steps=slice_steps)
+                      seed=seed, text_tokenizer=text_tokenizer, clip_silence=clip_silence, slice_steps=slice_steps, isolate=isolate)
