@@ -64,6 +64,14 @@ extern "C" {
 
 #define F5_BACKBONE_DIT 0
 #define F5_BACKBONE_UNETT 1
+#define F5_BACKBONE_MMDIT 2 /* MMDiT(...) (mmdit.py:85-127): two streams -- text c [B, nt, D], audio x [B, N, D] -- with their own weights and
+                               AdaLN vectors, joined in one attention over nt + N keys.  Read from f5_config: dim, depth, heads, dim_head, ff_dim,
+                               mel_dim, text_num_embeds, text_mask_padding and F5_OPT_QK_RMSNORM (text_dim, conv_layers, pe_attn_head and
+                               attn_mask_enabled are not: the text is embedded at width dim, every head is rotated, a mask that is given
+                               is always applied).  aux.text_pos [>= nt, dim] is its sinus table.  A batch runs rectangular, padding rows
+                               computed (its input conv is unmasked).  f5_text_embed writes [B, nt, dim] and ignores N and lens.  Refused,
+                               with the reason: the other F5_OPT_* bits, texts of more than 1024 tokens, F5_SPLIT_CFG=1, length buckets,
+                               isolated rows, f5_sample_items, f5_sample_span, f5_prepare_sample and the adapter calls. */
 
 typedef struct f5_engine f5_engine;
 typedef struct f5_vocos f5_vocos;
@@ -840,6 +848,10 @@ int f5k_strip_first_token(const float* in, float* out, int32_t Bp, int32_t N, in
     "xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps it_idx"
 int f5k_work_plan(const f5_config* c, int32_t B, int32_t N, int32_t S, int32_t call_B, int32_t call_N, int64_t* total_bytes,
                   int64_t* main_off, int64_t* side_off);
+/* Diagnostic taps of the MMDiT forward (tests): `taps` (device f32, or NULL to switch them off) receives, from every later
+ * f5_dit_forward of this engine, the audio embedding [Bp, N, D], then per block the text stream c [Bp, nt, D] (not in the last block,
+ * which drops it) and the audio stream x [Bp, N, D], back to back; Bp = B, or 2 B with cfg_infer.  sample() never writes them. */
+int f5k_mmdit_taps(f5_engine* e, float* taps);
 /* repeated-launch timing of one GEMM shape (for bench/roofline): returns average microseconds per launch */
 int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tile_m, int32_t tile_n, int32_t iters,
                   float* avg_us, f5_stream stream);

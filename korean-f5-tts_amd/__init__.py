@@ -5,14 +5,14 @@ for gfx950 in csrc/, reached through the C-ABI declared in include/f5_hip.h (cty
 """
 from . import adapters, config, edit, mel, utils, weights  # noqa: F401
 
-__all__ = ["config", "weights", "adapters", "edit", "mel", "utils", "CFM", "DiT", "UNetT", "Vocos", "BigVGAN", "lib", "infer", "dist", "batching"]
+__all__ = ["config", "weights", "adapters", "edit", "mel", "utils", "CFM", "DiT", "UNetT", "MMDiT", "Vocos", "BigVGAN", "lib", "infer", "dist", "batching"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require the built library (CPU-only tooling)
     if name in ("CFM",):
         from .cfm import CFM
         return CFM
-    if name in ("DiT", "UNetT"):
+    if name in ("DiT", "UNetT", "MMDiT"):
         from . import backbones
         return getattr(backbones, name)
     if name == "Vocos":

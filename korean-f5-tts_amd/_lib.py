@@ -14,7 +14,8 @@ F5_OPT_QK_RMSNORM, F5_OPT_LONG_SKIP, F5_OPT_TEXT_AVG_UPSAMPLE, F5_OPT_ADAPTERS =
 F5_PREC_F32, F5_PREC_BF16, F5_PREC_F16, F5_PREC_F16X3, F5_PREC_F16P = 0, 1, 2, 3, 4
 PRECISIONS = {"f32": F5_PREC_F32, "fp32": F5_PREC_F32, "bf16": F5_PREC_BF16, "f16": F5_PREC_F16, "fp16": F5_PREC_F16,
               "f16x3": F5_PREC_F16X3, "f16p": F5_PREC_F16P, "parity": F5_PREC_F16P}
-F5_BACKBONE_DIT, F5_BACKBONE_UNETT = 0, 1
+F5_BACKBONE_DIT, F5_BACKBONE_UNETT, F5_BACKBONE_MMDIT = 0, 1, 2
+BACKBONES = {"DiT": F5_BACKBONE_DIT, "UNetT": F5_BACKBONE_UNETT, "MMDiT": F5_BACKBONE_MMDIT}
 F5_ODE_EULER, F5_ODE_MIDPOINT = 0, 1
 ODE_METHODS = {"euler": F5_ODE_EULER, "midpoint": F5_ODE_MIDPOINT}
 F5_PCM_F32, F5_PCM_S16 = 0, 1
@@ -181,6 +182,7 @@ SIGNATURES = {
     "f5k_cat2": (_i, [_i, _p, _p, _p, _i, _i, _i, _p]),
     "f5k_strip_first_token": (_i, [_p, _p, _i, _i, _i, _p]),
     "f5k_work_plan": (_i, [C.POINTER(f5_config), _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "f5k_mmdit_taps": (_i, [_p, _p]),
     "f5k_gemm_time": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
     "f5_profile_enable": (_i, [_p, _i]),
     "f5_profile_read": (_i, [_p, C.POINTER(_f), C.POINTER(_i), C.POINTER(C.c_double), _i]),

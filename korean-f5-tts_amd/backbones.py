@@ -33,6 +33,7 @@ class _HipBackbone(nn.Module):
         # "parity" (the default): the fastest operand precision measured inside the 1e-3 mel bar of the fp32 CPU path for THIS backbone
         # (DESIGN.md section 3): DiT "f16p" (f16 blocks, split-f16 input / output layers); the E2-TTS UNetT has no AdaLN gates and
         # every one of its GEMM classes costs ~1e-3 in plain f16, so it gets "f16x3" (split-f16 GEMM products, f16 attention products)
+        # the MMDiT: "f16x3" too -- against the reference's vectors at its fixtures' weight scale f16p reaches 1.5e-3
         if precision == "parity":
             precision = "f16p" if self.backbone_name == "DiT" else "f16x3"
         arch.pop("dropout", None)
@@ -55,7 +56,7 @@ class _HipBackbone(nn.Module):
 
     # ---- shapes / state dict -------------------------------------------------------------------------
     def param_shapes(self):
-        fn = W.dit_param_shapes if self.backbone_name == "DiT" else W.unett_param_shapes
+        fn = {"DiT": W.dit_param_shapes, "UNetT": W.unett_param_shapes, "MMDiT": W.mmdit_param_shapes}[self.backbone_name]
         return fn(self.arch, self.text_num_embeds, self.mel_dim)
 
     def init_synthetic(self, seed: int = 0):
@@ -246,3 +247,22 @@ class UNetT(_HipBackbone):
         if skip_connect_type != "concat":
             raise NotImplementedError("only skip_connect_type='concat' (the E2TTS configs) is built")
         super().__init__(**kw)
+
+
+class MMDiT(_HipBackbone):
+    """The reference's MMDiT (backbones/mmdit.py:85-213): a text stream and an audio stream with their own weights, joined in one
+    attention per block.  Constructor keywords are the reference's; `dropout` is accepted and ignored.  A batch runs rectangular
+    (the input conv is unmasked), so the packed-row features -- length buckets, isolated rows, per-item and sliced solves -- and the
+    resident adapters stay with the DiT."""
+    backbone_name = "MMDiT"
+
+    def __init__(self, *, dim, depth=8, heads=8, dim_head=64, dropout=0.1, ff_mult=4, mel_dim=100, text_num_embeds=256,
+                 text_mask_padding=True, qk_norm=None, precision="parity", device=None, max_pos=8192):
+        if qk_norm not in (None, "rms_norm"):
+            raise ValueError(f"Unimplemented qk_norm: {qk_norm}")                       # modules.py:404
+        if dim_head != 64:
+            raise ValueError(f"dim_head must be 64 (got {dim_head}): the attention kernels are built for it")
+        # (the text stream has the model's width; there is no ConvNeXt, every head is rotated, a mask that is given is applied)
+        super().__init__(mel_dim=mel_dim, text_num_embeds=text_num_embeds, precision=precision, device=device, max_pos=max_pos,
+                         dim=dim, depth=depth, heads=heads, dim_head=dim_head, ff_mult=ff_mult, text_dim=dim, conv_layers=0,
+                         text_mask_padding=text_mask_padding, qk_norm=qk_norm, pe_attn_head=None, attn_mask_enabled=True)

@@ -204,12 +204,17 @@ class CFM(nn.Module):
                                      method=self.odeint_kwargs.get("method", "euler"))
         return self._finish(out, vocoder), trajectory
 
+    def _no_mmdit(self):
+        if getattr(self.transformer, "backbone_name", None) == "MMDiT":
+            raise NotImplementedError("per-item and sliced solves are built for the DiT and UNetT backbones, not the MMDiT")
+
     @torch.no_grad()
     def sample_items(self, cond, text, duration, *, lens=None, steps=32, cfg_strength=1.0, sway_sampling_coef=None, seed=None,
                      use_epss=True, max_duration=65536, vocoder=None, no_ref_audio=False, edit_mask=None):
         """sample() with per-item settings: `steps`, `cfg_strength`, `sway_sampling_coef` and `seed` each take one value for the batch or
         a sequence of one value per item (entries of the last two may be None).  One engine call (f5_sample_items) runs the batch for
         max(steps) steps; an item with fewer steps keeps its final state from then on.  Returns (out, trajectory[max(steps) + 1, B, N, mel])."""
+        self._no_mmdit()
         a = self._prepare(cond, text, duration, lens, max_duration, edit_mask)
         steps_i, cfg_i, sway_i, seed_i = item_settings(steps, cfg_strength, sway_sampling_coef, seed, a.batch)
         y0 = item_noise(a.duration.tolist(), seed_i, self.num_channels, self._noise_device)
@@ -231,6 +236,7 @@ class CFM(nn.Module):
         gets item_noise's draw for it alone.  prev=None: every item begins here.  The batch runs at N = max(duration) of the items
         it holds now.  The grids are item_time_grids' grids, sliced.  Returns a SpanResult: `out` (where(cond_mask, cond, state):
         an item's result once it is `done`), `state` [B, N, mel] and `done`, per item whether its last step was run."""
+        self._no_mmdit()
         a = self._prepare(cond, text, duration, lens, max_duration, edit_mask)
         batch, durs = a.batch, a.duration.tolist()
         steps_i, cfg_i, sway_i, seed_i = item_settings(steps, cfg_strength, sway_sampling_coef, seed, batch)

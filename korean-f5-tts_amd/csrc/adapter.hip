@@ -13,6 +13,7 @@ static int live_engine(f5_adapter* a, f5_engine** out) {
 
 extern "C" int f5_adapter_create(f5_engine* e, f5_adapter** out) {
     if (!e || !out) return fail(F5_EINVAL, "f5_adapter_create: null argument");
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) return fail(F5_EINVAL, "f5_adapter_create: resident adapters are built for the DiT backbone, not the MMDiT");
     if (!e->adapters_on) return fail(F5_ESTATE, "f5_adapter_create: the engine was created without F5_OPT_ADAPTERS");
     if (!e->finalized) return fail(F5_ESTATE, "f5_adapter_create: f5_finalize has not been called");
     f5_adapter* a = new f5_adapter();
@@ -136,6 +137,7 @@ extern "C" int f5_adapter_put_tensor(f5_adapter* a, const char* name, const void
 
 extern "C" int f5_set_adapter(f5_engine* e, f5_adapter* a, f5_stream stream) {
     if (!e) return fail(F5_EINVAL, "null engine");
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) return fail(F5_EINVAL, "f5_set_adapter: resident adapters are built for the DiT backbone, not the MMDiT");
     if (!e->adapters_on) return fail(F5_ESTATE, "f5_set_adapter: the engine was created without F5_OPT_ADAPTERS");
     if (!e->finalized) return fail(F5_ESTATE, "f5_set_adapter: f5_finalize has not been called");
     if (a) {

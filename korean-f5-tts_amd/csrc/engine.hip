@@ -69,19 +69,30 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
         return fail(F5_EINVAL, "bad precision");
     if (c->precision == F5_PREC_F16X3 && c->ff_dim % 32)
         return fail(F5_EINVAL, "F5_PREC_F16X3 needs ff_dim %% 32 == 0 (whole 32-element blocks of the split operand layout; got %d)", c->ff_dim);
-    if (c->backbone != F5_BACKBONE_DIT && c->backbone != F5_BACKBONE_UNETT) return fail(F5_EINVAL, "bad backbone");
+    if (c->backbone != F5_BACKBONE_DIT && c->backbone != F5_BACKBONE_UNETT && c->backbone != F5_BACKBONE_MMDIT) return fail(F5_EINVAL, "bad backbone");
     if (c->backbone == F5_BACKBONE_UNETT && (c->depth % 2)) return fail(F5_EINVAL, "UNetT depth must be even");
     if (c->text_dim > 2048 || c->dim > 2048) return fail(F5_EINVAL, "dims > 2048 unsupported");
     if (c->options & ~(F5_OPT_QK_RMSNORM | F5_OPT_LONG_SKIP | F5_OPT_TEXT_AVG_UPSAMPLE | F5_OPT_ADAPTERS)) return fail(F5_EINVAL, "unknown option bits %d", c->options);
-    if (c->options && c->backbone != F5_BACKBONE_DIT) return fail(F5_EINVAL, "F5_OPT_* are options of the DiT backbone (dit.py:160-166)");
+    if (c->backbone == F5_BACKBONE_MMDIT) {   // mmdit.py:86-99: of the options only qk_norm is a constructor argument
+        if (c->options & F5_OPT_LONG_SKIP) return fail(F5_EINVAL, "f5_create: the MMDiT backbone has no long skip connection (F5_OPT_LONG_SKIP is a DiT option)");
+        if (c->options & F5_OPT_TEXT_AVG_UPSAMPLE)
+            return fail(F5_EINVAL, "f5_create: the MMDiT backbone does not stretch its text to the audio length (F5_OPT_TEXT_AVG_UPSAMPLE is a DiT option)");
+        if (c->options & F5_OPT_ADAPTERS) return fail(F5_EINVAL, "f5_create: resident adapters (F5_OPT_ADAPTERS) are built for the DiT backbone, not the MMDiT");
+        const char* sc = getenv("F5_SPLIT_CFG");
+        if (sc && sc[0] == '1') return fail(F5_EINVAL, "f5_create: F5_SPLIT_CFG=1 steps the DiT's halves as two chains; the MMDiT backbone runs packed CFG only");
+    } else if (c->options && c->backbone != F5_BACKBONE_DIT) return fail(F5_EINVAL, "F5_OPT_* are options of the DiT backbone (dit.py:160-166)");
     if ((c->options & F5_OPT_TEXT_AVG_UPSAMPLE) && !c->text_mask_padding)
         return fail(F5_EINVAL, "text_embedding_average_upsampling requires text_mask_padding to be True (dit.py:41-42)");
     f5_engine* e = new f5_engine();
     e->cfg = *c;
     e->inner = c->heads * 64;
-    e->kin = 2 * c->mel_dim + c->text_dim;
+    const bool mmdit = c->backbone == F5_BACKBONE_MMDIT;
+    if (mmdit) e->cfg.text_dim = c->dim;   // (the text stream has the model's width; f5_config.text_dim is not read)
+    if (mmdit) e->cfg.conv_layers = 0;     // (mmdit.py:30-61: no ConvNeXt blocks behind the lookup)
+    e->kin = 2 * c->mel_dim + (mmdit ? 0 : c->text_dim);   // mmdit.py:70: the text has no part in the input projection
     e->kin_pad = round_up(e->kin, 64);  // whole 128-byte K-tiles for the LDS-DMA GEMM (pad columns stay zero)
-    e->modN = (6 * c->depth + 2) * c->dim;
+    // per block 6 D (DiT), or x's 6 D then c's 6 D -- 2 D in the last, context_pre_only block -- (MMDiT); then the final norm's 2 D
+    e->modN = (mmdit ? 12 * c->depth - 2 : 6 * c->depth + 2) * c->dim;
     e->split16 = c->precision == F5_PREC_F16X3;
     e->io_split = c->precision == F5_PREC_F16P;
     e->sw = read_switches(*c);
@@ -246,7 +257,7 @@ SamplePlan plan_sample(const f5_engine* e, int B, int N, const int32_t* lens_hos
     p.want_traj = o.want_traj;
     p.halves = p.use_cfg ? 2 : 1;
     p.evals = o.method == F5_ODE_MIDPOINT ? 2 : 1;
-    const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;
+    const bool dit = e->cfg.backbone == F5_BACKBONE_DIT;   // (the MMDiT runs rectangular on one chain: never packed, never split)
     // (a per-item call runs on one stream chain, and on the rectangular body -- batch row = row / N finds a row's time vectors -- unless
     //  it is isolated: then on packed rows, whatever F5_PACK_ROWS says, and the rowmap's batch row finds them)
     p.bucket = o.isolated && o.bucket;
@@ -364,10 +375,17 @@ static int check_ready(const char* who, f5_engine* e, int B, int N) {
     if (N + 1 > e->cfg.max_pos) return fail(F5_EINVAL, "%s: N=%d exceeds the rotary table (%d rows)", who, N, e->cfg.max_pos);
     return F5_OK;
 }
+// the MMDiT's text positions come from a sinus table of 1024 rows (mmdit.py:37-38)
+static int check_mmdit_text(const char* who, const f5_engine* e, int nt) {
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT && nt > 1024)
+        return fail(F5_EINVAL, "%s: nt=%d exceeds the MMDiT text position table (1024 rows)", who, nt);
+    return F5_OK;
+}
 extern "C" int f5_text_embed(f5_engine* e, const int64_t* text, int32_t B, int32_t nt, const int32_t* lens_host,
                              int32_t N, int32_t drop_text, float* out, f5_stream stream) {
     CHK(check_ready("f5_text_embed", e, B, N));
     if (!text || !out || nt <= 0) return fail(F5_EINVAL, "f5_text_embed: bad arguments");
+    CHK(check_mmdit_text("f5_text_embed", e, nt));
     hipStream_t s = (hipStream_t)stream;
     return F5_OPS(e, text_embed(e, text, B, nt, lens_host, N, drop_text, out, s));
 }
@@ -376,6 +394,7 @@ extern "C" int f5_dit_forward(f5_engine* e, const float* x, const float* cond, c
                               int32_t drop_audio_cond, int32_t drop_text, float* out, f5_stream stream) {
     CHK(check_ready("f5_dit_forward", e, B, N));
     if (!x || !cond || !text || !time_host || !out || nt <= 0) return fail(F5_EINVAL, "f5_dit_forward: bad arguments");
+    CHK(check_mmdit_text("f5_dit_forward", e, nt));
     hipStream_t s = (hipStream_t)stream;
     return F5_OPS(e, forward(e, x, cond, text, nt, time_host, lens_host, B, N, cfg_infer, drop_audio_cond, drop_text, out, s));
 }
@@ -420,7 +439,10 @@ static int check_sample_call(f5_engine* e, const SampleCall& c) {
     return F5_OK;
 }
 static int run_sample_call(f5_engine* e, SampleCall& c) {
+    if (e && c.per_item && e->cfg.backbone == F5_BACKBONE_MMDIT)
+        return fail(F5_EINVAL, "%s: per-item and sliced solves are built for the DiT and UNetT backbones, not the MMDiT", c.who);
     CHK(check_sample_call(e, c));
+    CHK(check_mmdit_text(c.who, e, c.nt));
     ItemTimeRows rows;
     if (c.per_item) {
         rows = item_time_rows(c.items.t_items, c.items.steps_items, c.steps, c.B, c.method);
@@ -479,11 +501,20 @@ extern "C" int f5_sample_span(f5_engine* e, const float* cond, int32_t cond_fram
     return run_sample_call(e, c);
 }
 
+extern "C" int f5k_mmdit_taps(f5_engine* e, float* taps) {
+    if (!e) return fail(F5_EINVAL, "f5k_mmdit_taps: null engine");
+    if (e->cfg.backbone != F5_BACKBONE_MMDIT) return fail(F5_EINVAL, "f5k_mmdit_taps: the engine's backbone is not the MMDiT");
+    e->mm_taps = taps;
+    return F5_OK;
+}
+
 // ------------------------------------------------------------------------------------- length buckets
 extern "C" int f5_set_length_buckets(f5_engine* e, int32_t granule) {
     if (!e) return fail(F5_EINVAL, "null engine");
     if (!valid_len_bucket(granule))
         return fail(F5_EINVAL, "f5_set_length_buckets: granule %d is neither 0 (off) nor a multiple of 8 in [8, 1024]", granule);
+    if (granule && e->cfg.backbone == F5_BACKBONE_MMDIT)
+        return fail(F5_EINVAL, "f5_set_length_buckets: length buckets run on packed rows, which the MMDiT backbone does not have");
     e->sw.len_bucket = granule;
     e->clear_graphs();
     e->gc.capacity = GraphCache::DEFAULT_CAPACITY;
@@ -491,6 +522,8 @@ extern "C" int f5_set_length_buckets(f5_engine* e, int32_t granule) {
 }
 extern "C" int f5_set_isolated_rows(f5_engine* e, int32_t on) {
     if (!e) return fail(F5_EINVAL, "f5_set_isolated_rows: null engine");
+    if (on && e->cfg.backbone == F5_BACKBONE_MMDIT)
+        return fail(F5_EINVAL, "f5_set_isolated_rows: isolated rows run on packed rows, which the MMDiT backbone does not have");
     e->sw.isolated_rows = on != 0;   // (the keys of isolated and rectangular plans differ: no graph goes stale)
     return F5_OK;
 }

@@ -145,7 +145,10 @@ static int reg_linear_f32(f5_engine* e, const std::string& p, const LinW<float>&
 template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStream_t s) {
     const f5_config& c = e->cfg;
     const int D = c.dim, Dt = c.text_dim, F = c.ff_dim, inner = e->inner, mel = c.mel_dim;
-    const bool dit = c.backbone == F5_BACKBONE_DIT;
+    const bool dit = c.backbone == F5_BACKBONE_DIT, mmdit = c.backbone == F5_BACKBONE_MMDIT;
+    // the input embedding's names: DiT / UNetT InputEmbedding (dit.py:121-140), MMDiT AudioEmbedding (mmdit.py:67-79)
+    const std::string in_proj_n = mmdit ? "audio_embed.linear" : "input_embed.proj";
+    const std::string conv_n = mmdit ? "audio_embed.conv_pos_embed.conv1d." : "input_embed.conv_pos_embed.conv1d.";
     // aux tables
     const Tensor* t = nullptr;
     if (!(t = e->ws.get("aux.rope_cos")) || t->shape.size() != 2 || t->shape[1] != 32 || t->shape[0] < 1)
@@ -164,7 +167,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     // text encoder
     CHK(copy_vec(e, s, "text_embed.text_embed.weight", {c.text_num_embeds + 1, Dt}, &P.E));
     CHK(reg_target(e, "text_embed.text_embed.weight", false, c.text_num_embeds + 1, Dt, Dt, P.E, MK_F32));
-    if (c.conv_layers > 0) {
+    if (c.conv_layers > 0 || mmdit) {   // (the MMDiT adds the sinus row to the bare lookup, mmdit.py:50-56)
         if (!(t = e->ws.get("aux.text_pos")) || t->shape.size() != 2 || t->shape[1] != Dt)
             return fail(F5_ESTATE, "missing/invalid aux.text_pos [P, text_dim]");
         P.text_pos_rows = (int)t->shape[0];
@@ -195,7 +198,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         CHK(reg_linear_f32(e, p + ".pwconv2", tb.pw2, Dt, 2 * Dt));
     }
     // input embedding
-    CHK(pack_linear_bb<T>(e, s, "input_embed.proj.weight", "input_embed.proj.bias", D, e->kin, &P.in_proj));
+    CHK(pack_linear_bb<T>(e, s, in_proj_n + ".weight", in_proj_n + ".bias", D, e->kin, &P.in_proj));
     auto zlo = [&](int bit, LinW<T>& L) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves zeroed) for a class
         if (e->sw.x3_ablate & bit) zero_lo_planar(s, L.w, (size_t)L.N * L.ldw);
     };
@@ -203,7 +206,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     const int cpg = D / 16;
     P.conv_kp = round_up(31 * cpg, GEMM_ROW_BYTES / (int)sizeof(T));   // whole K-tiles, zero padded (convpos.h)
     for (int j = 0; j < 2; ++j) {
-        const std::string p = "input_embed.conv_pos_embed.conv1d." + std::to_string(j * 2);
+        const std::string p = conv_n + std::to_string(j * 2);
         const Tensor* w = nullptr;
         CHK(need(e->ws, p + ".weight", {D, cpg, 31}, &w));
         CHK(dev_alloc(e, &P.conv_w[j], (size_t)D * P.conv_kp));
@@ -218,9 +221,9 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     std::vector<std::string> modp;
     for (int i = 0; i < c.depth; ++i) {
         BlockW<T>& b = P.blocks[i];
-        const std::string p = dit ? "transformer_blocks." + std::to_string(i) : "layers." + std::to_string(i);
-        const std::string at = dit ? p + ".attn" : p + ".2";
-        const std::string ff = dit ? p + ".ff" : p + ".4";
+        const std::string p = dit || mmdit ? "transformer_blocks." + std::to_string(i) : "layers." + std::to_string(i);
+        const std::string at = dit || mmdit ? p + ".attn" : p + ".2";
+        const std::string ff = dit ? p + ".ff" : mmdit ? p + ".ff_x" : p + ".4";
         CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q", at + ".to_k", at + ".to_v"}, inner, D, &b.qkv));
         CHK(pack_linear_bb<T>(e, s, at + ".to_out.0.weight", at + ".to_out.0.bias", D, inner, &b.out));
         if (dit) {   // the reference's LoRA targets (train/train_lora.py); q / k / v are row ranges of the fused operand
@@ -240,7 +243,21 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
             CHK(copy_vec(e, s, at + ".q_norm.weight", {64}, &b.qn));
             CHK(copy_vec(e, s, at + ".k_norm.weight", {64}, &b.kn));
         }
-        if (dit) {
+        if (mmdit) {   // the text stream's own weights; the last block is context_pre_only (modules.py:721-739)
+            const bool last = i == c.depth - 1;
+            CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q_c", at + ".to_k_c", at + ".to_v_c"}, inner, D, &b.qkv_c));
+            if (!last) {
+                CHK(pack_linear_bb<T>(e, s, at + ".to_out_c.weight", at + ".to_out_c.bias", D, inner, &b.out_c));
+                CHK(pack_linear_bb<T>(e, s, p + ".ff_c.ff.0.0.weight", p + ".ff_c.ff.0.0.bias", F, D, &b.ff1_c));
+                CHK(pack_linear_bb<T>(e, s, p + ".ff_c.ff.2.weight", p + ".ff_c.ff.2.bias", D, F, &b.ff2_c));
+            }
+            if (c.options & F5_OPT_QK_RMSNORM) {
+                CHK(copy_vec(e, s, at + ".c_q_norm.weight", {64}, &b.qn_c));
+                CHK(copy_vec(e, s, at + ".c_k_norm.weight", {64}, &b.kn_c));
+            }
+            modp.push_back(p + ".attn_norm_x.linear");
+            modp.push_back(p + ".attn_norm_c.linear");
+        } else if (dit) {
             modp.push_back(p + ".attn_norm.linear");
         } else {
             CHK(copy_vec(e, s, p + ".1.g", {D}, &b.norm1_g));
@@ -252,26 +269,31 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
             }
         }
     }
-    if (dit) {
+    if (dit || mmdit) {
         // stacked AdaLN: rows [l*6D, (l+1)*6D) = layer l (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp);
         // last 2D rows = norm_out (scale, shift).  Always f32.
+        // (MMDiT: per block attn_norm_x's 6 D then attn_norm_c's 6 D -- the last block's attn_norm_c is an AdaLayerNorm_Final of
+        //  2 D, (scale, shift) -- so every slot but that one and norm_out has 6 D rows and the slots stay back to back)
         LinW<float>& M = P.mod;
         M.N = e->modN;
         M.K = D;
         M.ldw = D;
         CHK(dev_alloc(e, &M.w, (size_t)M.N * D));
         CHK(dev_alloc(e, &M.b, (size_t)M.N));
-        for (int i = 0; i <= c.depth; ++i) {
-            const bool last = i == c.depth;
-            const std::string p = last ? std::string("norm_out.linear") : modp[i];
-            const int rows = last ? 2 * D : 6 * D;
+        modp.push_back("norm_out.linear");
+        size_t row0 = 0;
+        for (size_t i = 0; i < modp.size(); ++i) {
+            const bool final2 = i + 1 == modp.size() || (mmdit && i + 2 == modp.size());
+            const std::string& p = modp[i];
+            const int rows = final2 ? 2 * D : 6 * D;
             const Tensor *w = nullptr, *b = nullptr;
             CHK(need(e->ws, p + ".weight", {rows, D}, &w));
             CHK(need(e->ws, p + ".bias", {rows}, &b));
-            HIPCHK(hipMemcpyAsync(M.w + (size_t)i * 6 * D * D, w->p, (size_t)rows * D * sizeof(float),
-                                  hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(M.b + (size_t)i * 6 * D, b->p, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(M.w + row0 * D, w->p, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(M.b + row0, b->p, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+            row0 += rows;
         }
+        if ((int)row0 != e->modN) return fail(F5_ESTATE, "AdaLN stack: %zu rows packed, %d planned", row0, e->modN);
     } else {
         CHK(copy_vec(e, s, "norm_out.g", {D}, &P.norm_out_g));
     }
@@ -281,11 +303,11 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         if (e->io_split) CHK((pack_linear<float, true>(e, s, "long_skip_connection.weight", "", D, 2 * D, &P.long_skip_f)));
     }
     if (e->io_split) {   // F5_PREC_F16P: the input / output layers once more, as split-planar f32 operands
-        CHK((pack_linear<float, true>(e, s, "input_embed.proj.weight", "input_embed.proj.bias", D, e->kin, &P.in_proj_f)));
+        CHK((pack_linear<float, true>(e, s, in_proj_n + ".weight", in_proj_n + ".bias", D, e->kin, &P.in_proj_f)));
         CHK((pack_linear<float, true>(e, s, "proj_out.weight", "proj_out.bias", mel, D, &P.proj_out_f)));
         P.conv_kp_f = round_up(31 * cpg, GEMM_ROW_BYTES / (int)sizeof(float));
         for (int j = 0; j < 2; ++j) {
-            const std::string p = "input_embed.conv_pos_embed.conv1d." + std::to_string(j * 2);
+            const std::string p = conv_n + std::to_string(j * 2);
             const Tensor* w = nullptr;
             CHK(need(e->ws, p + ".weight", {D, cpg, 31}, &w));
             CHK(dev_alloc(e, &P.conv_w_f[j], (size_t)D * P.conv_kp_f));
@@ -297,7 +319,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     }
     zlo(256, P.proj_out);
     // (F5_PREC_F16P holds the input projection twice: f16 rows and the split-planar f32 operand the forward reads)
-    CHK(reg_target(e, "input_embed.proj.weight", true, D, e->kin, P.in_proj.ldw, P.in_proj.w, merge_kind<T>(e),
+    CHK(reg_target(e, in_proj_n + ".weight", true, D, e->kin, P.in_proj.ldw, P.in_proj.w, merge_kind<T>(e),
                    e->io_split ? P.in_proj_f.w : nullptr, e->io_split ? MK_PLANAR : MK_NONE));
     HIPCHK(hipGetLastError());
     return F5_OK;
@@ -309,11 +331,15 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     const size_t Bp = 2 * (size_t)B, D = c.dim, Dt = c.text_dim, F = c.ff_dim, mel = c.mel_dim;
     const size_t Nt = c.backbone == F5_BACKBONE_UNETT ? N + 1 : N;  // UNetT prepends the time token
     const size_t rows = Bp * Nt;
+    // MMDiT: q / k / ao / vt hold the joint sequence of NT text and N audio positions per batch row; text_c / text_u the text stream's
+    // embedding [B, NT, D] (there is no stretched [B, N, Dt] text)
+    const bool mmdit = c.backbone == F5_BACKBONE_MMDIT;
+    const size_t jrows = mmdit ? Bp * (Nt + NT) : rows, text_el = mmdit ? NT * D : (size_t)N * Dt;
     // time rows: one per backbone evaluation -- S (Euler) or 2 S (midpoint) in sample(), Bp in forward() -- and behind the
     // evaluation times in tdev the grid t[0..S] (sample_body: the dt of every step)
     // (a per-item call has one row per DISTINCT evaluation time of the batch: f5_engine::res_U)
     const size_t SS = (size_t)std::max(std::max(2 * S + 1, (int)Bp + 1), e->res_U);
-    w.Npad = round_up((int)Nt, 64);
+    w.Npad = round_up((int)(mmdit ? Nt + NT : Nt), 64);
     w.tdev = a.take<float>(SS + (size_t)S + 1);
     w.feat = a.take<float>(SS * 256);
     w.th = a.take<float>(SS * D);
@@ -325,8 +351,8 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     w.row_start = a.take<int>(Bp + (size_t)B + 16);
     w.rowmap = a.take<int2>(Bp * (size_t)round_up(N, 4));
     w.step_cond = a.take<float>((size_t)B * N * mel);
-    w.text_c = a.take<float>((size_t)B * N * Dt);
-    w.text_u = a.take<float>((size_t)B * N * Dt);
+    w.text_c = a.take<float>((size_t)B * text_el);
+    w.text_u = a.take<float>((size_t)B * text_el);
     w.tx_a = a.take<float>((size_t)B * N * Dt);
     w.tx_b = a.take<float>((size_t)B * N * Dt);
     w.tx_h1 = a.take<float>((size_t)B * N * 2 * Dt);
@@ -338,9 +364,9 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     w.x = a.take<float>(rows * D);
     w.pred = a.take<float>(Bp * N * mel);
     w.xn = a.take<T>(rows * D);
-    w.q = a.take<T>(rows * e->inner);
-    w.k = a.take<T>(rows * e->inner);
-    w.ao = a.take<T>(rows * e->inner);
+    w.q = a.take<T>(jrows * e->inner);
+    w.k = a.take<T>(jrows * e->inner);
+    w.ao = a.take<T>(jrows * e->inner);
     w.vt = a.take<T>(Bp * c.heads * 64 * w.Npad);
     w.ffh = a.take<T>(rows * F);
     w.in_cond = a.take<float>((size_t)B * N * mel);
@@ -358,6 +384,17 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
         w.cat2 = a.take<T>(rows * 2 * D);
         w.skips = a.take<float>(rows * D * (c.depth / 2));
         w.pred_all = a.take<float>(rows * mel);
+    }
+    w.mm_c = nullptr;
+    w.mm_cn = w.mm_aox = w.mm_aoc = w.mm_ffc = nullptr;
+    w.mm_lens = nullptr;
+    if (mmdit) {
+        w.mm_c = a.take<float>(Bp * NT * D);
+        w.mm_cn = a.take<T>(Bp * NT * D);
+        w.mm_aox = a.take<T>(rows * e->inner);
+        w.mm_aoc = a.take<T>(Bp * NT * e->inner);
+        w.mm_ffc = a.take<T>(Bp * NT * F);
+        w.mm_lens = a.take<int>(Bp + 16);
     }
     // f5_sample_items: behind everything else, and only once a per-item call has asked (an engine that never does keeps its arena)
     w.mod_rows = w.it_t = w.it_cfg = nullptr;
@@ -392,7 +429,7 @@ template <typename T> static int run_time_path(f5_engine* e, Work<T>& w, int S, 
         HIPCHK(launch_gemm<float>(s, w.feat, 256, P.time0.w, P.time0.ldw, S, D, 256,
                                   EpiStore<float>{w.th, D, P.time0.b, F5_ACT_SILU}));
         HIPCHK(launch_gemm<float>(s, w.th, D, P.time2.w, P.time2.ldw, S, D, D, EpiStore<float>{w.temb, D, P.time2.b, F5_ACT_NONE}));
-        if (e->cfg.backbone == F5_BACKBONE_DIT) {
+        if (e->cfg.backbone != F5_BACKBONE_UNETT) {   // DiT and MMDiT: the whole AdaLN stack of every evaluation time
             hipLaunchKernelGGL(act_kernel, dim3(ew_blocks((long)S * D)), dim3(256), 0, s, w.temb, w.st, (long)S * D, F5_ACT_SILU);
             KCHK();
             HIPCHK(launch_gemm<float>(s, w.st, D, P.mod.w, P.mod.ldw, S, e->modN, D,
@@ -410,6 +447,17 @@ static int run_text_embed(f5_engine* e, Work<T>& w, const int64_t* text, int B, 
     const f5_config& c = e->cfg;
     const int Dt = c.text_dim;
     const bool dit = c.backbone == F5_BACKBONE_DIT;
+    if (c.backbone == F5_BACKBONE_MMDIT) {
+        // mmdit.py:40-61: lookup + the sinus row of the token's own position + (mask_padding) zero rows where the ORIGINAL token is the
+        // filler, drop_text replacing the tokens after that mask was taken: text_embed_kernel's arithmetic at "N" = nt, no lengths
+        if (nt > P.text_pos_rows) return fail(F5_EINVAL, "nt=%d exceeds aux.text_pos (%d rows)", nt, P.text_pos_rows);
+        return e->prof.timed(PC_TEXT, s, [&]() -> int {
+            hipLaunchKernelGGL(text_embed_kernel, dim3(ew_blocks((long)B * nt * Dt / 4)), dim3(256), 0, s, (const long long*)text, nt, P.E,
+                               P.text_pos, out, B, nt, Dt, (const int*)nullptr, drop_text, c.text_mask_padding, 1, P.text_pos_rows);
+            KCHK();
+            return F5_OK;
+        });
+    }
     const long rows = (long)B * N;
     if (c.conv_layers > 0 && dit && N > P.text_pos_rows) return fail(F5_EINVAL, "N=%d exceeds aux.text_pos rows", N);
     return e->prof.timed(PC_TEXT, s, [&]() -> int {
@@ -509,7 +557,7 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
         ip = &P.in_proj_f; cw = P.conv_w_f; kp = P.conv_kp_f; cs = convpos_can_split(D);
     }
     HIPCHK(pr.timed(PC_MISC, s, [&] {
-        launch_pack_input<U>(s, y, cond, text_first, text_second, acat, e->kin_pad, B, Bp, N, c.mel_dim, c.text_dim, drop_cond_first, pk.rowmap,
+        launch_pack_input<U>(s, y, cond, text_first, text_second, acat, e->kin_pad, B, Bp, N, c.mel_dim, e->kin - 2 * c.mel_dim, drop_cond_first, pk.rowmap,
                              f.ml(), f.lens_dev);
         return hipGetLastError();
     }));
@@ -760,14 +808,164 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
     return F5_OK;
 }
 
+// One MMDiT forward over Bp batch rows (mmdit.py:172-213, MMDiTBlock modules.py:743-771, JointAttnProcessor modules.py:555-645): the
+// audio stream x [Bp, N, D] (w.x) and the text stream c [Bp, nt, D] (w.mm_c) have their own weights and AdaLN vectors and meet only
+// inside one softmax over nt + N keys.  text_first / text_second: the text embeddings [B, nt, D] of the two halves.
+//
+// Joint layout (mmdit.h): TEXT FIRST -- positions [0, nt) are c, [nt, nt + N) are x -- so that the valid keys of batch row b, every
+// text key (padded text rows included: the reference never masks them) and the audio keys below lens[b], are the prefix nt + lens[b]
+// and the attention kernels run as they are.  q, k and v^T of both streams land in the joint image straight from the two QKV GEMM
+// epilogues (EpiQKV<T, true>: destination offset and layout length apart from the rotary position, which counts from 0 per stream).
+// The batch runs rectangular: the input conv is called without a mask (mmdit.py:78), so padded frames reach valid ones and are computed.
+//
+// Launches per block (a condition, not a measurement): 4 LayerNorm (x and c before the attention, x and c before the FF), 2 QKV,
+// 1 attention, 1 split of its output into the two dense out-projection operands, 2 out-projections, 4 FF GEMMs = 14, plus 2
+// norm-rope launches with qk_norm.  The last block (context_pre_only) has no text out-projection, LayerNorm or FF: 3 LayerNorm, 2 QKV,
+// 1 attention, 1 split, 1 out-projection, 2 FF GEMMs = 10.  Per forward, ahead of the blocks: one launch that zeroes v^T (its Lpad tail columns
+// and whatever the arena held are read by the attention's last key tile, multiplied by zero probabilities) and, with lengths, one
+// launch that makes the joint key lengths.
+template <typename T>
+static int run_mmdit_forward(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, int nt,
+                             const float* mod_row, int mod_stride, const int* lens_dev, int drop_cond_first,
+                             const float* text_first, const float* text_second, hipStream_t s, float* taps = nullptr) {
+    Packed<T>& P = packed<T>(e);
+    const f5_config& c = e->cfg;
+    const int D = c.dim, F = c.ff_dim, inner = e->inner, H = c.heads, L = nt + N;
+    auto tap = [&](const float* src, size_t n) -> int {   // f5k_mmdit_taps (diagnostic): the next intermediate, behind the last one
+        if (!taps) return F5_OK;
+        HIPCHK(hipMemcpyAsync(taps, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        taps += n;
+        return F5_OK;
+    };
+    if (nt <= 0 || nt > std::max(e->res_nt, 1) || L > w.Npad) return fail(F5_ESTATE, "MMDiT forward: nt=%d outside the arena's text reservation", nt);
+    Prof& pr = e->prof;
+    // the audio embedding: no text columns, the conv unmasked
+    const FwdCtx in{e, s, B, Bp, N, Bp * N, nullptr, RowPack{}};
+    if (e->io_split) CHK((embed_input<T, float>(in, w, y, cond, drop_cond_first, nullptr, nullptr, w.x)));
+    else CHK((embed_input<T, T>(in, w, y, cond, drop_cond_first, nullptr, nullptr, w.x)));
+    CHK(tap(w.x, (size_t)Bp * N * D));
+    const FwdCtx fx{e, s, B, Bp, N, Bp * N, lens_dev, RowPack{}};      // the audio stream's rows
+    const FwdCtx fc{e, s, B, Bp, nt, Bp * nt, nullptr, RowPack{}};     // the text stream's rows
+    const int pl = fx.pl();
+    // c = cat(c_cond, c_uncond) (mmdit.py:194), or the one half of a forward without cfg_infer
+    const size_t half_c = (size_t)B * nt * D * sizeof(float);
+    HIPCHK(hipMemcpyAsync(w.mm_c, text_first, half_c, hipMemcpyDeviceToDevice, s));
+    if (Bp > B) HIPCHK(hipMemcpyAsync(w.mm_c + (size_t)B * nt * D, text_second, half_c, hipMemcpyDeviceToDevice, s));
+    HIPCHK(pr.timed(PC_MISC, s, [&] {   // (Npad is a multiple of 64 elements: whole 16-byte pieces)
+        const long n16 = (long)((size_t)Bp * H * 64 * w.Npad * sizeof(T) / 16);
+        hipLaunchKernelGGL(zero_fill16_kernel, dim3(ew_blocks(n16)), dim3(256), 0, s, reinterpret_cast<uint4*>(w.vt), n16);
+        return hipGetLastError();
+    }));
+    const int* kv_lens = nullptr;
+    if (lens_dev) {   // mask = pad(mask, (0, nt), value=True) (modules.py:617), text first: the key prefix nt + len
+        HIPCHK(pr.timed(PC_MISC, s, [&] {
+            hipLaunchKernelGGL(joint_lens_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, lens_dev, w.mm_lens, Bp, nt);
+            return hipGetLastError();
+        }));
+        kv_lens = w.mm_lens;
+    }
+    const bool qk_norm = (c.options & F5_OPT_QK_RMSNORM) != 0;
+    // AdaLN LayerNorm of a stream (rows of n tokens per batch row) into out: LN(x) * (1 + scale) + shift
+    auto adaln = [&](const FwdCtx& f, const float* x, auto* out, const float* scale, const float* shift, int planar) {
+        using TO = std::remove_pointer_t<decltype(out)>;
+        return pr.timed(PC_LN, s, [&] {
+            hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((f.rows + 3) / 4), dim3(256), 0, s, x, D, out, D, f.rows, D, 1e-6f, scale, shift,
+                               mod_stride, f.N, 1, Prefetch{}, (const int*)nullptr, planar, f.wt(F5_WT_LN));
+            return hipGetLastError();
+        });
+    };
+    // F5_PREC_F16X3 with plain-f16 attention products (as attention_block): q / k / v^T leave the QKV epilogues as f16
+    bool attn16 = false;
+    if constexpr (std::is_same_v<T, float>) attn16 = e->split16 && e->sw.x3_attn_hi() == 3 && !qk_norm;
+    // one stream's QKV projection into the joint image at layout offset `off`
+    auto qkv = [&](const FwdCtx& f, const T* a, const LinW<T>& lw, int off) -> int {
+        const QKVJointLayout jl{L, off};
+        if constexpr (std::is_same_v<T, float>) {
+            if (attn16) {
+                f16_t *q = reinterpret_cast<f16_t*>(w.q), *k = reinterpret_cast<f16_t*>(w.k), *vt = reinterpret_cast<f16_t*>(w.vt);
+                return f.gemm(a, D, lw, 3 * inner, D,
+                              EpiQKV<f16_t, true>{q, k, vt, lw.b, P.rope_frag, f.N, w.Npad, H, H, attention_q_scale<f16_t>(), nullptr, jl}, pl);
+            }
+        }
+        return f.gemm(a, D, lw, 3 * inner, D,
+                      EpiQKV<T, true>{w.q, w.k, w.vt, lw.b, P.rope_frag, f.N, w.Npad, H, qk_norm ? 0 : H,
+                                      qk_norm ? 1.0f : attention_q_scale<T>(), nullptr, jl}, pl);
+    };
+    // qk_norm: RMSNorm with the stream's own gains BEFORE the rotary embedding (modules.py:588-608); the epilogue left q / k raw
+    auto norm_rope = [&](const FwdCtx& f, const float* gq, const float* gk, int off) {
+        const long qrows = (long)Bp * H * f.N;
+        return pr.timed(PC_MISC, s, [&] {
+            hipLaunchKernelGGL((qknorm_rope_joint_kernel<T>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, w.q, w.k, gq, gk,
+                               P.rope_cos, P.rope_sin, qrows, f.N, L, off, attention_q_scale<T>(), 1e-6f);
+            return hipGetLastError();
+        });
+    };
+    const double attn_fl = 4.0 * H * 64 * (double)Bp * L * L;
+    const int row16 = inner * (int)sizeof(T) / 16;
+    for (int l = 0; l < c.depth; ++l) {
+        BlockW<T>& bw = P.blocks[l];
+        const bool last = l == c.depth - 1;   // context_pre_only: c is normed, attended to, and dropped
+        const float* mx = mod_row + (size_t)l * 12 * D;   // x: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        const float* mc = mx + 6 * D;                     // c: the same six; in the last block (scale, shift) of an AdaLayerNorm_Final
+        HIPCHK(adaln(fx, w.x, w.xn, mx + D, mx, pl));
+        HIPCHK(adaln(fc, w.mm_c, w.mm_cn, last ? mc : mc + D, last ? mc + D : mc, pl));
+        CHK(qkv(fc, w.mm_cn, bw.qkv_c, 0));
+        CHK(qkv(fx, w.xn, bw.qkv, nt));
+        if (qk_norm) {
+            HIPCHK(norm_rope(fc, bw.qn_c, bw.kn_c, 0));
+            HIPCHK(norm_rope(fx, bw.qn, bw.kn, nt));
+        }
+        // every query row is computed (q_lens null): no row of ao is left as the arena held it
+        HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
+            if constexpr (std::is_same_v<T, float>) {
+                if (attn16)
+                    return launch_attention_v2<f16_t>(s, reinterpret_cast<f16_t*>(w.q), reinterpret_cast<f16_t*>(w.k), reinterpret_cast<f16_t*>(w.vt),
+                                                      nullptr, Bp, H, L, w.Npad, kv_lens, Bp, nullptr, nullptr, w.ao);
+            }
+            return launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, L, w.Npad, kv_lens, Bp, nullptr, nullptr, e->split16, pl, e->sw.x3_attn_hi(),
+                                        fx.wt(F5_WT_ATTN));
+        }));
+        HIPCHK(pr.timed(PC_MISC, s, [&] {
+            hipLaunchKernelGGL(joint_split_kernel, dim3(ew_blocks((long)Bp * L * row16)), dim3(256), 0, s, reinterpret_cast<const uint4*>(w.ao),
+                               last ? nullptr : reinterpret_cast<uint4*>(w.mm_aoc), reinterpret_cast<uint4*>(w.mm_aox), Bp, nt, N, row16);
+            return hipGetLastError();
+        }));
+        if (!last) {   // the text stream: never gated by length (modules.py:643)
+            CHK(fc.gemm(w.mm_aoc, inner, bw.out_c, D, inner,
+                        EpiGateRes{w.mm_c, w.mm_c, D, bw.out_c.b, mc + 2 * D, mod_stride, nt, nullptr, fc.wt(F5_WT_GATE_RES)}, pl));
+            HIPCHK(adaln(fc, w.mm_c, w.mm_cn, mc + 4 * D, mc + 3 * D, pl));
+            CHK(fc.gemm(w.mm_cn, D, bw.ff1_c, F, D, EpiStore<T>{w.mm_ffc, F, bw.ff1_c.b, F5_ACT_GELU_TANH, pl, fc.wt(F5_WT_STORE16)}, pl));
+            CHK(fc.gemm(w.mm_ffc, F, bw.ff2_c, D, F,
+                        EpiGateRes{w.mm_c, w.mm_c, D, bw.ff2_c.b, mc + 5 * D, mod_stride, nt, nullptr, fc.wt(F5_WT_GATE_RES)}, pl));
+        }
+        // the audio stream: padded rows get no attention residual (x.masked_fill(~mask, 0), modules.py:640-642) but do get the FF's
+        CHK(fx.gemm(w.mm_aox, inner, bw.out, D, inner,
+                    EpiGateRes{w.x, w.x, D, bw.out.b, mx + 2 * D, mod_stride, N, lens_dev, fx.wt(F5_WT_GATE_RES)}, pl));
+        HIPCHK(adaln(fx, w.x, w.xn, mx + 4 * D, mx + 3 * D, pl));
+        CHK(ff_block<T>(fx, w, bw, EpiGateRes{w.x, w.x, D, bw.ff2.b, mx + 5 * D, mod_stride, N, nullptr, fx.wt(F5_WT_GATE_RES)}));
+        if (!last) CHK(tap(w.mm_c, (size_t)Bp * nt * D));
+        CHK(tap(w.x, (size_t)Bp * N * D));
+    }
+    const float* mf = mod_row + ((size_t)c.depth * 12 - 4) * D;   // norm_out: (scale, shift)
+    if (e->io_split) {   // F5_PREC_F16P: final norm to pre-split f32 rows (in c1, free since the conv embedding) + split output projection
+        HIPCHK(adaln(fx, w.x, w.c1, mf, mf + D, 1));
+        return project_out<T, float>(fx, w.c1, w.pred);
+    }
+    HIPCHK(adaln(fx, w.x, w.xn, mf, mf + D, pl));
+    return project_out<T, T>(fx, w.xn, w.pred);
+}
+
 // dispatches one backbone forward; `step_row` selects the time step's vectors inside the per-call tables
 template <typename T>
 static int run_backbone(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, int step_row,
                         int per_row_time, const int* lens_dev, int drop_cond_first, const float* text_first,
-                        const float* text_second, hipStream_t s, const RowPack& pk = RowPack{}) {
+                        const float* text_second, hipStream_t s, const RowPack& pk = RowPack{}, int nt = 0, float* taps = nullptr) {
     if (e->cfg.backbone == F5_BACKBONE_DIT)
         return run_dit_forward<T>(e, w, y, cond, B, Bp, N, w.mod + (size_t)step_row * e->modN, per_row_time ? e->modN : 0,
                                   lens_dev, drop_cond_first, text_first, text_second, s, pk);
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT)   // (nt: the text stream's length; the other backbones stretch their text to N)
+        return run_mmdit_forward<T>(e, w, y, cond, B, Bp, N, nt, w.mod + (size_t)step_row * e->modN, per_row_time ? e->modN : 0,
+                                    lens_dev, drop_cond_first, text_first, text_second, s, taps);
     return run_unett_forward<T>(e, w, y, cond, B, Bp, N, w.temb + (size_t)step_row * e->cfg.dim, per_row_time ? e->cfg.dim : 0,
                                 lens_dev, drop_cond_first, text_first, text_second, s);
 }
@@ -779,6 +977,13 @@ static int run_backbone_rows(f5_engine* e, Work<T>& w, const float* y, const flo
     if (e->cfg.backbone == F5_BACKBONE_DIT)
         return run_dit_forward<T>(e, w, y, cond, B, Bp, N, rows, e->modN, lens_dev, 0, text_first, text_second, s, pk);
     return run_unett_forward<T>(e, w, y, cond, B, Bp, N, rows, e->cfg.dim, lens_dev, 0, text_first, text_second, s);
+}
+// the text staging buffer is part of the arena plan: a longer text moves the carve offsets
+static void reserve_text(f5_engine* e, int nt) {
+    if (nt > e->res_nt) {
+        e->res_nt = nt;
+        e->clear_graphs();
+    }
 }
 // uploads a call's small tables through pinned staging: nT times to w.tdev and, where lengths are given, the plan's lens and
 // row_start tables (SamplePlan::Chunk) and lens_plain; for a per-item sampler call the grids, guidance, step counts and time-row
@@ -843,6 +1048,7 @@ static int upload_small(f5_engine* e, Work<T>& w, const SamplePlan& p, const flo
 template <typename T>
 int EngineOps<T>::text_embed(f5_engine* e, const int64_t* text, int B, int nt, const int32_t* lens_host, int N, int drop_text,
                              float* out, hipStream_t s) {
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) reserve_text(e, nt);   // (its text buffers are sized by the longest text seen)
     CHK(ensure_arena(e, B, N, 1));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
@@ -855,6 +1061,7 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
                           const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
                           hipStream_t s) {
     const int Bp = cfg_infer ? 2 * B : B;
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) reserve_text(e, nt);
     CHK(ensure_arena(e, B, N, Bp));
     Work<T> w;
     carve<T>(e, w, e->res_B, e->res_N, e->res_S);
@@ -868,10 +1075,10 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
     if (cfg_infer) {
         CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 0, w.text_c, s));
         CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 1, w.text_u, s));
-        CHK(run_backbone<T>(e, w, x, cond, B, Bp, N, 0, 1, lens_dev, 0, w.text_c, w.text_u, s));
+        CHK(run_backbone<T>(e, w, x, cond, B, Bp, N, 0, 1, lens_dev, 0, w.text_c, w.text_u, s, RowPack{}, nt, e->mm_taps));
     } else {
         CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, drop_text, w.text_c, s));
-        CHK(run_backbone<T>(e, w, x, cond, B, Bp, N, 0, 1, lens_dev, drop_audio_cond, w.text_c, w.text_c, s));
+        CHK(run_backbone<T>(e, w, x, cond, B, Bp, N, 0, 1, lens_dev, drop_audio_cond, w.text_c, w.text_c, s, RowPack{}, nt, e->mm_taps));
     }
     HIPCHK(hipMemcpyAsync(out, w.pred, (size_t)Bp * N * e->cfg.mel_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     return F5_OK;
@@ -901,6 +1108,7 @@ template <typename T> static Work<T> second_half(const f5_engine* e, const Work<
 // and N -- unless text_mask_padding zeroes the rows whose ORIGINAL token is the filler (dit.py:90-91,104-108: the mask is
 // taken before drop_text), which makes it a function of the call's text: no cache then.
 static bool uc_cacheable(const f5_engine* e, int B, bool has_lens) {
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) return false;   // (its text stream is [nt, D], a lookup: nothing worth keeping)
     return B == 1 && !has_lens && !(e->cfg.text_mask_padding && e->cfg.conv_layers > 0) && !(e->cfg.options & F5_OPT_TEXT_AVG_UPSAMPLE);
 }
 
@@ -953,7 +1161,8 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
     }
     // one (CFG) evaluation of a chunk at state x with the vectors of time row `row`, into w.pred
     auto eval = [&](const SamplePlan::Chunk& k, const RowPack& pk, const float* x, int row) -> int {
-        const size_t yo = p.frame_at(k) * mel, to = p.frame_at(k) * c.text_dim;
+        const bool mmdit = c.backbone == F5_BACKBONE_MMDIT;   // (its text embeddings are [B, nt, D])
+        const size_t yo = p.frame_at(k) * mel, to = mmdit ? (size_t)k.u0 * p.nt * c.dim : p.frame_at(k) * c.text_dim;
         const float *cond = w.step_cond + yo, *tc = w.text_c + to, *tu = w.text_u + to;
         const int* lens = lens_dev ? lens_dev + p.lens_at(k) : nullptr;
         if (p.items) {   // per-item times: evaluation `row` reads, for every batch row of the chunk, the time row its item is at
@@ -965,7 +1174,7 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
             }));
             return run_backbone_rows<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, w.mod_rows, lens, tc, p.use_cfg ? tu : tc, s, pk);
         }
-        if (!p.split) return run_backbone<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, row, 0, lens, 0, tc, p.use_cfg ? tu : tc, s, pk);
+        if (!p.split) return run_backbone<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, row, 0, lens, 0, tc, p.use_cfg ? tu : tc, s, pk, p.nt);
         // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
         hipStream_t s1 = e->side_stream;
         HIPCHK(hipEventRecord(e->ev_fork, s));            // x (and, first time, the text embeddings) ready
@@ -1064,13 +1273,6 @@ template <typename T> static int isolated_ceiling(f5_engine* e, const char* who,
                     packed<T>(e).text_pos_rows);
     *n_cap = nc;
     return F5_OK;
-}
-// the text staging buffer is part of the arena plan: a longer text moves the carve offsets
-static void reserve_text(f5_engine* e, int nt) {
-    if (nt > e->res_nt) {
-        e->res_nt = nt;
-        e->clear_graphs();
-    }
 }
 // The body of one planned call whose inputs are in the arena: replay the captured graph of its key, capture it when the signature has run
 // before, else run eagerly (and remember it).  N: the call's own frame count (the cached unconditional text embedding is kept per N).

@@ -22,6 +22,7 @@
 #include "convpos.h"
 #include "elementwise.h"
 #include "gemm_dispatch.h"
+#include "mmdit.h"
 
 using namespace f5;
 #define fail f5_fail
@@ -85,6 +86,10 @@ template <typename T> struct BlockW {
     float* norm1_g = nullptr;          // UNetT RMSNorm gains
     float* norm2_g = nullptr;
     float *qn = nullptr, *kn = nullptr;   // F5_OPT_QK_RMSNORM: gains of the RMSNorm on q / k [64]
+    // MMDiT: the text stream's own weights (to_q_c / to_k_c / to_v_c fused, to_out_c, ff_c, c_q_norm / c_k_norm); the last,
+    // context_pre_only block has neither out_c nor ff1_c / ff2_c
+    LinW<T> qkv_c, out_c, ff1_c, ff2_c;
+    float *qn_c = nullptr, *kn_c = nullptr;
 };
 
 struct TextBlockW {
@@ -262,6 +267,7 @@ struct f5_engine {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int res_nt = 0;
+    float* mm_taps = nullptr;  // f5k_mmdit_taps (diagnostic): where f5_dit_forward copies the MMDiT's intermediates; sample() never does
     bool res_items = false;    // a per-item call has run: the arena plan carries Work::mod_rows and the it_* tables ...
     int res_U = 0;             // ... and this many time rows (the most distinct evaluation times a per-item call has had)
     // resident adapters (F5_OPT_ADAPTERS; adapter.hip)
@@ -319,6 +325,12 @@ template <typename T> struct Work {
     // the row of every (evaluation, item) in the time path's output [evals * steps_max, B]
     float *mod_rows, *it_t, *it_cfg;
     int *it_steps, *it_idx;
+    // MMDiT (carved for that backbone only; else null): the text stream c [2 B * nt, D] f32, its normed rows, the two dense halves of the
+    // split attention output, c's FF hidden rows and the joint key lengths nt + len.  text_c / text_u hold [B, nt, D] there, and q / k /
+    // ao / vt the joint sequence of nt + N positions.
+    float* mm_c;
+    T *mm_cn, *mm_aox, *mm_aoc, *mm_ffc;
+    int* mm_lens;
     int Npad;
 };
 

@@ -272,7 +272,9 @@ struct EpiGateResRows : EpiGateRes {
 // rowmap (may be null): GEMM row m is (batch row, position) = rowmap[m] (packed variable-length batches, RowPack) instead
 // of (m / Nseq, m % Nseq); every utterance then starts at a multiple of 4 rows, and positions >= Nseq (alignment rows
 // of the longest utterance) are dropped.
-template <typename TO> struct EpiQKV {
+struct QKVJointLayout { int Lseq, off; };
+struct QKVOwnLayout {};
+template <typename TO, bool JOINT = false> struct EpiQKV {
     // rope: the rotary table in FRAGMENT order (rope_frag_kernel, elementwise.h): [maxpos][g = 0..3][j = 0..3]{cos, cos, sin, sin} of the
     // pairs (j*8 + g*2, +1) -- the 4 columns j*16 + g*4 .. +3 of a head that one accumulator lane owns need ONE 16-byte load, and a lane's
     // four sub-tiles j are 64 contiguous bytes (two tables of [maxpos][32] cost four 8-byte loads per sub-tile pair: all-heads rotary,
@@ -280,6 +282,12 @@ template <typename TO> struct EpiQKV {
     TO* q; TO* k; TO* vt; const float* bias; const float* rope;
     int Nseq, Npad, H, pe_heads; float q_scale;
     const int2* rowmap = nullptr;
+    // JOINT (the MMDiT's two-stream attention): this GEMM's rows are ONE stream of a joint sequence of jl.Lseq positions per batch row;
+    // the stream's position p (the rotary position, from 0) lands at layout position jl.off + p of q / k [B', H, Lseq, 64] and of
+    // v^T [B', H, 64, Npad].  Nseq stays the stream's own length (rows per batch row of this GEMM).  Never with a rowmap.
+    std::conditional_t<JOINT, QKVJointLayout, QKVOwnLayout> jl{};
+    __device__ __forceinline__ int lay_len() const { if constexpr (JOINT) return jl.Lseq; else return Nseq; }
+    __device__ __forceinline__ int lay_off() const { if constexpr (JOINT) return jl.off; else return 0; }
     // No write-through form: built (q / k rows regrouped to 16 bytes, V^T in 8-byte pieces) and measured at C2, it LOST 0.6 ms per step
     // against plain stores: the transposed third cannot be regrouped and 8-byte sc1 stores cost more than they save.
     static constexpr bool kWT = false, kRegroup16 = false;
@@ -293,12 +301,12 @@ template <typename TO> struct EpiQKV {
         int b = m / Nseq, pos = m - b * Nseq;
         if (rowmap) { const int2 bp = rowmap[m]; b = bp.x; pos = bp.y; }
         if (pos >= Nseq) return {0, nullptr};
-        return {((size_t)b * H * Nseq + pos) * 64, rope + pos * 64};
+        return {((size_t)b * H * lay_len() + pos + lay_off()) * 64, rope + pos * 64};
     }
     __device__ __forceinline__ ColCtx col(int n) const {
         const int inner = H * 64;
         const int which = n >= inner ? 1 : 0, c = n - which * inner, h = c >> 6, d = c & 63;
-        return {*reinterpret_cast<const float4*>(bias + n), which ? k : q, (size_t)h * Nseq * 64 + d, d, h < pe_heads,
+        return {*reinterpret_cast<const float4*>(bias + n), which ? k : q, (size_t)h * lay_len() * 64 + d, d, h < pe_heads,
                 which ? 1.0f : q_scale};
     }
     struct Pre { float2 cs, sn; };
@@ -322,10 +330,10 @@ template <typename TO> struct EpiQKV {
     // whether rotary applies is wave-uniform and the no-rotary heads (15 of 16 with pe_attn_head = 1) load nothing but the bias;
     // rotary heads request the cos / sin pairs of 2 fragment rows at a time (4: the kernel spills).  V^T: staging row = head dim (64 of them, 128 positions
     // x 2 B), out: 16 lanes x 16 B = 256 contiguous bytes of one V^T row; needs 8 aligned rows to be 8 consecutive positions of one
-    // utterance (no packing, Nseq % 8 == 0).
+    // utterance (no packing, Nseq % 8 == 0) that start at a 16-byte boundary of the V^T row (a joint stream's offset % 8 == 0).
     static constexpr bool kStaged = sizeof(TO) == 2;
     __device__ __forceinline__ bool staged_ok(bool transposed) const {
-        return Nseq >= 8 && (!transposed || (rowmap == nullptr && (Nseq & 7) == 0));
+        return Nseq >= 8 && (!transposed || (rowmap == nullptr && (Nseq & 7) == 0 && (lay_off() & 7) == 0));
     }
     template <int MI, int NJ>
     __device__ __forceinline__ void staged(char* slice, int lane, int mw, int nw, const f32x4 (&acc)[MI][NJ], bool transposed) const {
@@ -348,7 +356,7 @@ template <typename TO> struct EpiQKV {
                 }
                 const int rr = lane >> 4, ch = lane & 15;
                 const int m = mw + ch * 8, b = m / Nseq, pos = m - b * Nseq;
-                TO* dst = vt + (size_t)b * H * 64 * Npad + (size_t)(nw - 2 * H * 64 + rr) * Npad + pos;
+                TO* dst = vt + (size_t)b * H * 64 * Npad + (size_t)(nw - 2 * H * 64 + rr) * Npad + pos + lay_off();
 #pragma unroll
                 for (int p = 0; p < 16; ++p) {
                     const int r = p * 4 + rr;
@@ -401,7 +409,7 @@ template <typename TO> struct EpiQKV {
                     }
             }
             const int rr = lane >> 3, ch = lane & 7;
-            TO* dsth = (which ? k : q) + (size_t)h * Nseq * 64 + ch * 8;
+            TO* dsth = (which ? k : q) + (size_t)h * lay_len() * 64 + ch * 8;
             if (rowmap) {
                 int2 bp[16];
 #pragma unroll
@@ -419,7 +427,7 @@ template <typename TO> struct EpiQKV {
 #pragma unroll
                 for (int p = 0; p < 16; ++p) {
                     const int r = p * 8 + rr;
-                    *reinterpret_cast<u32x4*>(dsth + ((size_t)b * H * Nseq + pos) * 64) = *reinterpret_cast<const u32x4*>(slice + r * 128 + ((ch ^ (r & 7)) << 4));
+                    *reinterpret_cast<u32x4*>(dsth + ((size_t)b * H * lay_len() + pos + lay_off()) * 64) = *reinterpret_cast<const u32x4*>(slice + r * 128 + ((ch ^ (r & 7)) << 4));
                     pos += 8;
                     if (pos >= Nseq) { pos -= Nseq; ++b; }
                 }
@@ -432,7 +440,7 @@ template <typename TO> struct EpiQKV {
             const int2 bp = rowmap[m];   // (alignment rows at positions >= Nseq are dropped, as row() drops them for q / k)
             return {(size_t)bp.x * H * 64 * Npad + bp.y, bp.y, bp.x, m + 3 < M && bp.y + 3 < Nseq, m, M};
         }
-        return {(size_t)b * H * 64 * Npad + pos, pos, b, (pos & 3) == 0 && pos + 3 < Nseq, m, M};
+        return {(size_t)b * H * 64 * Npad + pos + lay_off(), pos, b, ((pos + lay_off()) & 3) == 0 && pos + 3 < Nseq, m, M};
     }
     __device__ __forceinline__ TColCtx tcol(int n) const {
         const int c = n - 2 * H * 64;  // = h*64 + d
@@ -448,7 +456,7 @@ template <typename TO> struct EpiQKV {
                 if (mm < r.M) {
                     int bb = mm / Nseq, pp = mm - bb * Nseq;
                     if (rowmap) { const int2 bp = rowmap[mm]; bb = bp.x; pp = bp.y; }
-                    if (pp < Nseq) vt[(size_t)bb * H * 64 * Npad + c.hoff + pp] = from_f32<TO>(v[rr] + c.b);
+                    if (pp < Nseq) vt[(size_t)bb * H * 64 * Npad + c.hoff + pp + lay_off()] = from_f32<TO>(v[rr] + c.b);
                 }
             }
         }

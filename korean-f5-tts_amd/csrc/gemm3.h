@@ -321,7 +321,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const T* __restrict__ A, i
 
 // can this epilogue's transposed region only start at a multiple of the 256-column block tile?
 template <typename Epi> inline bool gemm3_epilogue_ok(const Epi&) { return !Epi::kTransposes; }
-template <typename TO> inline bool gemm3_epilogue_ok(const EpiQKV<TO>& e) { return (2 * e.H * 64) % 256 == 0; }
+template <typename TO, bool J> inline bool gemm3_epilogue_ok(const EpiQKV<TO, J>& e) { return (2 * e.H * 64) % 256 == 0; }
 
 template <typename T, typename Epi, GemmOperands OPS = GemmOperands::Plain, GemmDiag DIAG = GemmDiag::None>
 inline hipError_t launch_gemm3(hipStream_t s, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const Epi& epi,

@@ -58,7 +58,7 @@ class Engine:
         self.text_num_embeds = text_num_embeds
         self.max_pos = max_pos
         cfg = _lib.f5_config()
-        cfg.backbone = _lib.F5_BACKBONE_DIT if backbone == "DiT" else _lib.F5_BACKBONE_UNETT
+        cfg.backbone = _lib.BACKBONES[backbone]
         cfg.precision = _lib.PRECISIONS[precision]
         cfg.dim, cfg.depth, cfg.heads, cfg.dim_head = a["dim"], a["depth"], a["heads"], a["dim_head"]
         cfg.ff_dim = int(a["dim"] * a["ff_mult"])
@@ -69,7 +69,9 @@ class Engine:
         cfg.text_num_embeds, cfg.mel_dim, cfg.max_pos = text_num_embeds, mel_dim, max_pos
         if a.get("qk_norm") not in (None, "rms_norm"):
             raise ValueError(f"Unimplemented qk_norm: {a['qk_norm']}")                       # modules.py:404
-        if (a.get("qk_norm") or a.get("long_skip_connection") or a.get("text_embedding_average_upsampling")) and backbone != "DiT":
+        if a.get("qk_norm") and backbone == "UNetT":
+            raise _lib.F5Error("qk_norm / long_skip_connection / text_embedding_average_upsampling are DiT options")
+        if (a.get("long_skip_connection") or a.get("text_embedding_average_upsampling")) and backbone != "DiT":
             raise _lib.F5Error("qk_norm / long_skip_connection / text_embedding_average_upsampling are DiT options")
         if a.get("text_embedding_average_upsampling") and not a["text_mask_padding"]:
             raise AssertionError("text_embedding_average_upsampling requires text_mask_padding to be True")   # dit.py:41-42
@@ -103,6 +105,8 @@ class Engine:
         text_rows = 0
         if a["conv_layers"] > 0:
             text_rows = 8192 if self.backbone == "DiT" else 4096  # dit.py:46 / unett.py:46
+        if self.backbone == "MMDiT":
+            text_rows = 1024                                      # mmdit.py:37-38 (the reference's buffer is non-persistent: built here)
         tables = aux_tables(a["dim_head"], self.max_pos, a["text_dim"], text_rows)
         with torch.cuda.device(self.device):
             st = _stream_ptr(self.device)
@@ -187,6 +191,8 @@ class Engine:
         B, nt = text.shape
         text = text.to(device=self.device, dtype=torch.long).contiguous()
         out = torch.empty(B, N, self.arch["text_dim"], device=self.device, dtype=torch.float32)
+        if self.backbone == "MMDiT":   # the text stream itself: [B, nt, dim], not stretched to N
+            out = torch.empty(B, nt, self.arch["dim"], device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.f5_text_embed(self._h, _ptr(text), B, nt, _lib.int_array(lens), N, int(drop_text),
                                               _ptr(out), _stream_ptr(self.device)), "f5_text_embed")
@@ -207,6 +213,10 @@ class Engine:
                                                int(drop_audio_cond), int(drop_text), _ptr(out),
                                                _stream_ptr(self.device)), "f5_dit_forward")
         return out
+
+    def mmdit_taps(self, buf: torch.Tensor | None):
+        """Diagnostic (tests): later forward() calls of an MMDiT engine copy their intermediates into `buf` (f5k_mmdit_taps); None: off."""
+        _lib.check(self.lib.f5k_mmdit_taps(self._h, _ptr(buf)), "f5k_mmdit_taps")
 
     def _stage_call(self, cond, cond_mask, text, B, method):
         """What every sampler call begins with: the method check, cond, cond_mask and text on the device, and `out`.

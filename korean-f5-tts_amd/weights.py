@@ -106,6 +106,63 @@ def unett_param_shapes(arch: dict, text_num_embeds: int, mel_dim: int = 100) -> 
     return s
 
 
+def mmdit_param_shapes(arch: dict, text_num_embeds: int, mel_dim: int = 100) -> dict[str, tuple]:
+    """The state dict of the reference's MMDiT (backbones/mmdit.py:85-127; MMDiTBlock modules.py:703-741, Attention with a context
+    stream modules.py:393-422).  The last block is context_pre_only: its attn_norm_c is an AdaLayerNorm_Final ([2 D, D]) and it has
+    neither to_out_c nor ff_c.  The text embedding's sinus table is a non-persistent buffer and not part of it."""
+    a = normalize_arch(arch, mel_dim)
+    D, F = a["dim"], int(a["dim"] * a["ff_mult"])
+    inner = a["heads"] * a["dim_head"]
+    s: dict[str, tuple] = {}
+    s["time_embed.time_mlp.0.weight"] = (D, 256)
+    s["time_embed.time_mlp.0.bias"] = (D,)
+    s["time_embed.time_mlp.2.weight"] = (D, D)
+    s["time_embed.time_mlp.2.bias"] = (D,)
+    s["text_embed.text_embed.weight"] = (text_num_embeds + 1, D)
+    s["audio_embed.linear.weight"] = (D, 2 * mel_dim)
+    s["audio_embed.linear.bias"] = (D,)
+    for j in (0, 2):
+        s[f"audio_embed.conv_pos_embed.conv1d.{j}.weight"] = (D, D // 16, 31)
+        s[f"audio_embed.conv_pos_embed.conv1d.{j}.bias"] = (D,)
+    for i in range(a["depth"]):
+        p = f"transformer_blocks.{i}"
+        last = i == a["depth"] - 1
+        s[p + ".attn_norm_c.linear.weight"] = ((2 if last else 6) * D, D)
+        s[p + ".attn_norm_c.linear.bias"] = ((2 if last else 6) * D,)
+        s[p + ".attn_norm_x.linear.weight"] = (6 * D, D)
+        s[p + ".attn_norm_x.linear.bias"] = (6 * D,)
+        for n in ("to_q", "to_k", "to_v"):
+            s[f"{p}.attn.{n}.weight"] = (inner, D)
+            s[f"{p}.attn.{n}.bias"] = (inner,)
+        if a.get("qk_norm") is not None:
+            s[p + ".attn.q_norm.weight"] = (a["dim_head"],)
+            s[p + ".attn.k_norm.weight"] = (a["dim_head"],)
+        for n in ("to_q_c", "to_k_c", "to_v_c"):
+            s[f"{p}.attn.{n}.weight"] = (inner, D)
+            s[f"{p}.attn.{n}.bias"] = (inner,)
+        if a.get("qk_norm") is not None:
+            s[p + ".attn.c_q_norm.weight"] = (a["dim_head"],)
+            s[p + ".attn.c_k_norm.weight"] = (a["dim_head"],)
+        s[p + ".attn.to_out.0.weight"] = (D, inner)
+        s[p + ".attn.to_out.0.bias"] = (D,)
+        if not last:
+            s[p + ".attn.to_out_c.weight"] = (D, inner)
+            s[p + ".attn.to_out_c.bias"] = (D,)
+            s[p + ".ff_c.ff.0.0.weight"] = (F, D)
+            s[p + ".ff_c.ff.0.0.bias"] = (F,)
+            s[p + ".ff_c.ff.2.weight"] = (D, F)
+            s[p + ".ff_c.ff.2.bias"] = (D,)
+        s[p + ".ff_x.ff.0.0.weight"] = (F, D)
+        s[p + ".ff_x.ff.0.0.bias"] = (F,)
+        s[p + ".ff_x.ff.2.weight"] = (D, F)
+        s[p + ".ff_x.ff.2.bias"] = (D,)
+    s["norm_out.linear.weight"] = (2 * D, D)
+    s["norm_out.linear.bias"] = (2 * D,)
+    s["proj_out.weight"] = (mel_dim, D)
+    s["proj_out.bias"] = (mel_dim,)
+    return s
+
+
 def vocos_param_shapes(v: dict) -> dict[str, tuple]:
     """Parameter names of charactr/vocos-mel-24khz's `pytorch_model.bin` (backbone.* / head.*)."""
     C, D, I, L = v["input_channels"], v["dim"], v["intermediate_dim"], v["num_layers"]
