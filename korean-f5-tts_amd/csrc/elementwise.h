@@ -865,19 +865,23 @@ static __global__ __launch_bounds__(256) void text_avg_upsample_kernel(const lon
     }
 }
 
-// qk_norm = "rms_norm" (modules.py:397-404,481-497): q and k, as the QKV epilogue left them WITHOUT rotary and scale
-// ([Bp, H, N, 64] each), get RMSNorm(64, eps) with their own gain, then the rotary embedding on the first pe_heads heads, then q its
-// softmax scale -- in place.  16 lanes per (batch row, head, position): 4 consecutive dims per lane = two rotary pairs.
+// qk_norm = "rms_norm" (modules.py:397-404,481-497; the MMDiT's joint attention modules.py:588-608): the Ns positions of one stream
+// in q and k, as the QKV epilogue left them WITHOUT rotary and scale, get RMSNorm(64, eps) with the stream's own gains, then the
+// rotary embedding at the stream's own position (from 0) on the first pe_heads heads, then q its softmax scale -- in place.
+// q / k are [Bp, H, L, 64] and the stream sits at layout positions [off, off + Ns): L = Ns, off = 0 for a backbone with one stream,
+// (nt + N, 0) and (nt + N, nt) for the text and audio streams of the MMDiT's joint image (mmdit.h).
+// 16 lanes per (batch row, head, position): 4 consecutive dims per lane = two rotary pairs.
 template <typename T>
 __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ q, T* __restrict__ k, const float* __restrict__ gq,
                                                           const float* __restrict__ gk, const float* __restrict__ rope_cos,
-                                                          const float* __restrict__ rope_sin, long rows, int N, int H, int pe_heads,
-                                                          float q_scale, float eps) {
+                                                          const float* __restrict__ rope_sin, long rows, int Ns, int L, int off, int H,
+                                                          int pe_heads, float q_scale, float eps) {
     const long gid = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const long r = gid >> 4;                              // (b * H + h) * N + pos
+    const long r = gid >> 4;                              // (b * H + h) * Ns + pos
     if (r >= rows) return;
     const int d = (int)(gid & 15) * 4;
-    const int pos = (int)(r % N), h = (int)((r / N) % H);
+    const int pos = (int)(r % Ns), h = (int)((r / Ns) % H);
+    const long dst = (r / Ns) * L + off + pos;            // row of the layout
     float2 cs = make_float2(1, 1), sn = make_float2(0, 0);
     const bool rot = h < pe_heads;
     if (rot) {
@@ -886,7 +890,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ q, T* 
     }
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
-        T* p = (which ? k : q) + r * 64 + d;
+        T* p = (which ? k : q) + dst * 64 + d;
         const float4 g = *reinterpret_cast<const float4*>((which ? gk : gq) + d);
         float a0 = to_f32(p[0]), a1 = to_f32(p[1]), a2 = to_f32(p[2]), a3 = to_f32(p[3]);
         float ss = (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
@@ -901,6 +905,16 @@ __global__ __launch_bounds__(256) void qknorm_rope_kernel(T* __restrict__ q, T* 
         const float sc = which ? 1.0f : q_scale;
         store4(p, a0 * sc, a1 * sc, a2 * sc, a3 * sc);
     }
+}
+// the one launch of it (the engine's qkv_project and the kernel-level API): Bp * H * Ns rows of 16 lanes
+template <typename T>
+static hipError_t launch_qknorm_rope(hipStream_t s, T* q, T* k, const float* gq, const float* gk, const float* rope_cos, const float* rope_sin,
+                                     int Bp, int H, int Ns, int L, int off, int pe_heads, float q_scale, float eps) {
+    if (Bp <= 0 || H <= 0 || Ns <= 0 || off < 0 || off + Ns > L) return hipErrorInvalidValue;   // (the stream lies inside the layout)
+    const long rows = (long)Bp * H * Ns;
+    hipLaunchKernelGGL((qknorm_rope_kernel<T>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, s, q, k, gq, gk, rope_cos, rope_sin, rows,
+                       Ns, L, off, H, pe_heads, q_scale, eps);
+    return hipGetLastError();
 }
 
 // --------------------------------------------------------------------------------------- weight repacking

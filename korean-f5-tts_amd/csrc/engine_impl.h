@@ -142,9 +142,28 @@ static int reg_linear_f32(f5_engine* e, const std::string& p, const LinW<float>&
     return reg_target(e, p + ".bias", false, 1, N, N, L.b, MK_F32);
 }
 
+// One stream's weights of the block whose attention module is `at`: to_q / to_k / to_v + sfx fused, the out-projection `out`, the
+// feed-forward `ff` and (qk_norm) the gains at + norm + "q_norm" / "k_norm".  pre_only: the stream ends in this block's attention.
+template <typename T>
+static int pack_stream(f5_engine* e, hipStream_t s, StreamW<T>& w, const std::string& at, const std::string& sfx, const std::string& out,
+                       const std::string& ff, const std::string& norm, bool pre_only) {
+    const int D = e->cfg.dim, F = e->cfg.ff_dim, inner = e->inner;
+    CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q" + sfx, at + ".to_k" + sfx, at + ".to_v" + sfx}, inner, D, &w.qkv));
+    if (!pre_only) {
+        CHK(pack_linear_bb<T>(e, s, out + ".weight", out + ".bias", D, inner, &w.out));
+        CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &w.ff1));
+        CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &w.ff2));
+    }
+    if (e->cfg.options & F5_OPT_QK_RMSNORM) {
+        CHK(copy_vec(e, s, norm + "q_norm.weight", {64}, &w.qn));
+        CHK(copy_vec(e, s, norm + "k_norm.weight", {64}, &w.kn));
+    }
+    return F5_OK;
+}
+
 template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStream_t s) {
     const f5_config& c = e->cfg;
-    const int D = c.dim, Dt = c.text_dim, F = c.ff_dim, inner = e->inner, mel = c.mel_dim;
+    const int D = c.dim, Dt = c.text_dim, inner = e->inner, mel = c.mel_dim;
     const bool dit = c.backbone == F5_BACKBONE_DIT, mmdit = c.backbone == F5_BACKBONE_MMDIT;
     // the input embedding's names: DiT / UNetT InputEmbedding (dit.py:121-140), MMDiT AudioEmbedding (mmdit.py:67-79)
     const std::string in_proj_n = mmdit ? "audio_embed.linear" : "input_embed.proj";
@@ -224,37 +243,20 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         const std::string p = dit || mmdit ? "transformer_blocks." + std::to_string(i) : "layers." + std::to_string(i);
         const std::string at = dit || mmdit ? p + ".attn" : p + ".2";
         const std::string ff = dit ? p + ".ff" : mmdit ? p + ".ff_x" : p + ".4";
-        CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q", at + ".to_k", at + ".to_v"}, inner, D, &b.qkv));
-        CHK(pack_linear_bb<T>(e, s, at + ".to_out.0.weight", at + ".to_out.0.bias", D, inner, &b.out));
+        CHK(pack_stream<T>(e, s, b.x, at, "", at + ".to_out.0", ff, at + ".", false));
         if (dit) {   // the reference's LoRA targets (train/train_lora.py); q / k / v are row ranges of the fused operand
             const char* qkv_names[3] = {".to_q.weight", ".to_k.weight", ".to_v.weight"};
             for (int j = 0; j < 3; ++j)
-                CHK(reg_target(e, at + qkv_names[j], true, inner, D, b.qkv.ldw, b.qkv.w + (size_t)j * inner * b.qkv.ldw, merge_kind<T>(e)));
-            CHK(reg_target(e, at + ".to_out.0.weight", true, D, inner, b.out.ldw, b.out.w, merge_kind<T>(e)));
+                CHK(reg_target(e, at + qkv_names[j], true, inner, D, b.x.qkv.ldw, b.x.qkv.w + (size_t)j * inner * b.x.qkv.ldw, merge_kind<T>(e)));
+            CHK(reg_target(e, at + ".to_out.0.weight", true, D, inner, b.x.out.ldw, b.x.out.w, merge_kind<T>(e)));
         }
-        CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &b.ff1));
-        CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &b.ff2));
-        zlo(1, b.qkv);
-        zlo(8, b.out);
-        zlo(16, b.ff1);
-        zlo(32, b.ff2);
+        zlo(1, b.x.qkv);
+        zlo(8, b.x.out);
+        zlo(16, b.x.ff1);
+        zlo(32, b.x.ff2);
         HIPCHK(hipGetLastError());
-        if (c.options & F5_OPT_QK_RMSNORM) {
-            CHK(copy_vec(e, s, at + ".q_norm.weight", {64}, &b.qn));
-            CHK(copy_vec(e, s, at + ".k_norm.weight", {64}, &b.kn));
-        }
         if (mmdit) {   // the text stream's own weights; the last block is context_pre_only (modules.py:721-739)
-            const bool last = i == c.depth - 1;
-            CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q_c", at + ".to_k_c", at + ".to_v_c"}, inner, D, &b.qkv_c));
-            if (!last) {
-                CHK(pack_linear_bb<T>(e, s, at + ".to_out_c.weight", at + ".to_out_c.bias", D, inner, &b.out_c));
-                CHK(pack_linear_bb<T>(e, s, p + ".ff_c.ff.0.0.weight", p + ".ff_c.ff.0.0.bias", F, D, &b.ff1_c));
-                CHK(pack_linear_bb<T>(e, s, p + ".ff_c.ff.2.weight", p + ".ff_c.ff.2.bias", D, F, &b.ff2_c));
-            }
-            if (c.options & F5_OPT_QK_RMSNORM) {
-                CHK(copy_vec(e, s, at + ".c_q_norm.weight", {64}, &b.qn_c));
-                CHK(copy_vec(e, s, at + ".c_k_norm.weight", {64}, &b.kn_c));
-            }
+            CHK(pack_stream<T>(e, s, b.c, at, "_c", at + ".to_out_c", p + ".ff_c", at + ".c_", i == c.depth - 1));
             modp.push_back(p + ".attn_norm_x.linear");
             modp.push_back(p + ".attn_norm_c.linear");
         } else if (dit) {
@@ -506,7 +508,7 @@ static int run_text_embed(f5_engine* e, Work<T>& w, const int64_t* text, int B, 
     });
 }
 
-// ---------------------------------------------------------------------------------- stages shared by both backbones
+// ---------------------------------------------------------------------------------- stages shared by the three backbones
 // What the stages of one forward share: the engine, the stream, the geometry and (DiT) the tables of a packed batch.
 struct FwdCtx {
     f5_engine* e;
@@ -526,9 +528,12 @@ struct FwdCtx {
         HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] { return egemm<T>(e, s, A, lda, L.w, L.ldw, rows, n, k, epi, ml(), mh(), a_split); }));
         return F5_OK;
     }
-    // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed)
+    // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed).  The hooks of the shared stages act on the
+    // x stream only: finalize_t never ablates the MMDiT text stream's weights, so the text stream's context turns them off (x3 = false)
+    // and its activations stay whole too.
+    bool x3 = true;
     template <typename T> void ablate(int bit, T* a, int k) const {
-        if (e->sw.x3_ablate & bit) zero_lo_planar(s, a, (size_t)rows * k);
+        if (x3 && (e->sw.x3_ablate & bit)) zero_lo_planar(s, a, (size_t)rows * k);
     }
 };
 
@@ -585,64 +590,107 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
     return F5_OK;
 }
 
-// Attention sub-block on the normed stream w.xn: QKV projection, attention, out-projection with the caller's residual epilogue.
-template <typename T, typename Epi>
-static int attention_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, bool qk_norm, const Epi& out_epi) {
-    f5_engine* e = f.e;
-    hipStream_t s = f.s;
-    Packed<T>& P = packed<T>(e);
-    Prof& pr = e->prof;
-    const f5_config& c = e->cfg;
-    const int D = c.dim, inner = e->inner, H = c.heads, B = f.B, Bp = f.Bp, N = f.N, pl = f.pl();
-    const RowPack& pk = f.pk;
-    const int pe_heads = c.pe_attn_head < 0 ? H : c.pe_attn_head;
-    // (a packed batch masks its keys whatever attn_mask_enabled says: a length-bucket plan packs utterances that fill their whole length,
-    //  for which masked and unmasked attention coincide)
-    const int* attn_lens = ((c.attn_mask_enabled || pk) && f.lens_dev) ? f.lens_dev : nullptr;
-    const double attn_fl = 4.0 * H * 64 * (pk ? pk.sq_host : (double)Bp * N * N);
-    f.ablate(1, w.xn, D);
-    // F5_PREC_F16X3 with plain-f16 attention products (x3_attn_hi == 3): q / k / v^T leave the QKV epilogue as f16 and the fast
-    // 16-bit attention kernel writes its output pre-split for the out-projection (the f32 buffers are reused at half their size)
-    bool attn16 = false;
-    if constexpr (std::is_same_v<T, float>) {
-        attn16 = e->split16 && e->sw.x3_attn_hi() == 3 && !qk_norm;
-        if (attn16) {
-            f16_t *q = reinterpret_cast<f16_t*>(w.q), *k = reinterpret_cast<f16_t*>(w.k), *vt = reinterpret_cast<f16_t*>(w.vt);
-            CHK(f.gemm(w.xn, D, bw.qkv, 3 * inner, D,
-                       EpiQKV<f16_t>{q, k, vt, bw.qkv.b, P.rope_frag, N, w.Npad, H, pe_heads, attention_q_scale<f16_t>(), pk.rowmap}, pl));
-            HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
-                return launch_attention_v2<f16_t>(s, q, k, vt, nullptr, Bp, H, N, w.Npad, attn_lens, B, f.lens_dev, pk.row_start, w.ao);
-            }));
-        }
-    }
-    if (!attn16) {
-        CHK(f.gemm(w.xn, D, bw.qkv, 3 * inner, D,
-                   EpiQKV<T>{w.q, w.k, w.vt, bw.qkv.b, P.rope_frag, N, w.Npad, H, qk_norm ? 0 : pe_heads,
-                             qk_norm ? 1.0f : attention_q_scale<T>(), pk.rowmap}, pl));
-        if (qk_norm) {   // RMSNorm on q / k comes BEFORE the rotary embedding (modules.py:481-497): the epilogue left both raw
-            const long qrows = (long)Bp * H * N;
-            HIPCHK(pr.timed(PC_MISC, s, [&] {
-                hipLaunchKernelGGL((qknorm_rope_kernel<T>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, w.q, w.k, bw.qn, bw.kn,
-                                   P.rope_cos, P.rope_sin, qrows, N, H, pe_heads, attention_q_scale<T>(), 1e-6f);
-                return hipGetLastError();
-            }));
-        }
-        HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
-            return launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, N, w.Npad, attn_lens, B, f.lens_dev, pk.row_start, e->split16, pl,
-                                        e->sw.x3_attn_hi(), f.wt(F5_WT_ATTN));
-        }));
-    }
-    f.ablate(8, w.ao, inner);
-    return f.gemm(w.ao, inner, bw.out, D, inner, out_epi, pl);
+// AdaLN LayerNorm of the residual stream x into out (rows of T, or pre-split f32 rows): out = LN(x) * (1 + scale) + shift.  mod_stride:
+// distance between batch rows' vectors (0: shared).  A packed batch with its own vectors per batch row finds them through the rowmap.
+// pf: weights to prefetch from the launch (see layernorm_kernel).
+template <typename TO>
+static hipError_t adaln_norm(const FwdCtx& f, const float* x, TO* out, const float* scale, const float* shift, int mod_stride, const Prefetch& pf,
+                             int planar) {
+    const int D = f.e->cfg.dim, rows = f.rows;
+    return f.e->prof.timed(PC_LN, f.s, [&] {
+        if (f.pk && mod_stride != 0)
+            hipLaunchKernelGGL((layernorm_rows_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, out, D, rows, D, 1e-6f, scale, shift,
+                               mod_stride, pf, f.ml(), f.pk.rowmap, planar, f.wt(F5_WT_LN));
+        else
+            hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, out, D, rows, D, 1e-6f, scale, shift,
+                               mod_stride, f.N, 1, pf, f.ml(), planar, f.wt(F5_WT_LN));
+        return hipGetLastError();
+    });
 }
 
-// Feed-forward pair on the normed stream w.xn: FF1 with GELU(tanh), FF2 with the caller's residual epilogue.
-template <typename T, typename Epi> static int ff_block(const FwdCtx& f, Work<T>& w, const BlockW<T>& bw, const Epi& out_epi) {
+// The attention operands q / k / v^T in the type the QKV epilogue writes and the attention kernel reads them -- the one place that decides
+// it.  F5_PREC_F16X3 with plain-f16 attention products (x3_attn_hi == 3, no qk_norm): f16, in the f32 buffers at half their size, and
+// the fast 16-bit attention kernel writes its output pre-split for the out-projection.  Everything else: T.  fn(q, k, vt) is called once.
+template <typename T, typename Fn> static int with_attn_operands(const f5_engine* e, const Work<T>& w, bool qk_norm, Fn&& fn) {
+    if constexpr (std::is_same_v<T, float>) {
+        if (e->split16 && e->sw.x3_attn_hi() == 3 && !qk_norm)
+            return fn(reinterpret_cast<f16_t*>(w.q), reinterpret_cast<f16_t*>(w.k), reinterpret_cast<f16_t*>(w.vt));
+    }
+    return fn(w.q, w.k, w.vt);
+}
+
+// QKV projection of one stream's normed rows xn into q / k / v^T.  place: QKVOwnLayout -- the stream is the whole sequence (packed rows
+// through f.pk's rowmap) -- or QKVJointLayout{L, off} -- the stream's f.N positions land at [off, off + f.N) of a joint sequence of L,
+// every head rotated (the MMDiT's joint attention).  With qk_norm the epilogue leaves q / k raw and the norm-rope launch follows:
+// RMSNorm comes BEFORE the rotary embedding (modules.py:481-497, 588-608).
+template <typename T, typename Place>
+static int qkv_project(const FwdCtx& f, Work<T>& w, T* xn, const StreamW<T>& sw, bool qk_norm, const Place& place) {
+    constexpr bool joint = std::is_same_v<Place, QKVJointLayout>;
+    f5_engine* e = f.e;
+    Packed<T>& P = packed<T>(e);
+    const f5_config& c = e->cfg;
+    const int D = c.dim, inner = e->inner, H = c.heads;
+    const int pe_heads = joint || c.pe_attn_head < 0 ? H : c.pe_attn_head;
+    int L = f.N, off = 0;
+    if constexpr (joint) L = place.Lseq, off = place.off;
+    f.ablate(1, xn, D);
+    return with_attn_operands<T>(e, w, qk_norm, [&](auto* q, auto* k, auto* vt) -> int {
+        using TO = std::remove_pointer_t<decltype(q)>;
+        CHK(f.gemm(xn, D, sw.qkv, 3 * inner, D,
+                   EpiQKV<TO, joint>{q, k, vt, sw.qkv.b, P.rope_frag, f.N, w.Npad, H, qk_norm ? 0 : pe_heads,
+                                     qk_norm ? 1.0f : attention_q_scale<TO>(), f.pk.rowmap, place}, f.pl()));
+        if (qk_norm)
+            HIPCHK(e->prof.timed(PC_MISC, f.s, [&] {
+                return launch_qknorm_rope<TO>(f.s, q, k, sw.qn, sw.kn, P.rope_cos, P.rope_sin, f.Bp, H, f.N, L, off, pe_heads, attention_q_scale<TO>(), 1e-6f);
+            }));
+        return F5_OK;
+    });
+}
+
+// Attention over L positions per batch row into w.ao.  kv_lens: key lengths of `len_rows` batch rows (batch row b reads entry
+// b % len_rows), or null: every key; q_lens: query lengths, or null: every query row is computed.  Packed rows through f.pk.
+template <typename T> static int attend(const FwdCtx& f, Work<T>& w, bool qk_norm, int L, const int* kv_lens, int len_rows, const int* q_lens) {
+    f5_engine* e = f.e;
+    const int H = e->cfg.heads, Bp = f.Bp;
+    const double fl = 4.0 * H * 64 * (f.pk ? f.pk.sq_host : (double)Bp * L * L);
+    return with_attn_operands<T>(e, w, qk_norm, [&](auto* q, auto* k, auto* vt) -> int {
+        using TO = std::remove_pointer_t<decltype(q)>;
+        HIPCHK(e->prof.timed(PC_ATTN, f.s, fl, [&] {
+            if constexpr (std::is_same_v<TO, T>)
+                return launch_attention_any(f.s, q, k, vt, w.ao, Bp, H, L, w.Npad, kv_lens, len_rows, q_lens, f.pk.row_start, e->split16, f.pl(),
+                                            e->sw.x3_attn_hi(), f.wt(F5_WT_ATTN));
+            else
+                return launch_attention_v2<f16_t>(f.s, q, k, vt, nullptr, Bp, H, L, w.Npad, kv_lens, len_rows, q_lens, f.pk.row_start, w.ao);
+        }));
+        return F5_OK;
+    });
+}
+
+// Out-projection of a stream's attention rows ao with the caller's residual epilogue.
+template <typename T, typename Epi> static int out_project(const FwdCtx& f, T* ao, const StreamW<T>& sw, const Epi& out_epi) {
+    const int D = f.e->cfg.dim, inner = f.e->inner;
+    f.ablate(8, ao, inner);
+    return f.gemm(ao, inner, sw.out, D, inner, out_epi, f.pl());
+}
+
+// Attention sub-block of a backbone with one stream, on the normed stream w.xn: QKV projection, attention, out-projection.
+template <typename T, typename Epi>
+static int attention_block(const FwdCtx& f, Work<T>& w, const StreamW<T>& sw, bool qk_norm, const Epi& out_epi) {
+    // (a packed batch masks its keys whatever attn_mask_enabled says: a length-bucket plan packs utterances that fill their whole length,
+    //  for which masked and unmasked attention coincide)
+    const int* attn_lens = ((f.e->cfg.attn_mask_enabled || f.pk) && f.lens_dev) ? f.lens_dev : nullptr;
+    CHK(qkv_project<T>(f, w, w.xn, sw, qk_norm, QKVOwnLayout{}));
+    CHK(attend<T>(f, w, qk_norm, f.N, attn_lens, f.B, f.lens_dev));
+    return out_project<T>(f, w.ao, sw, out_epi);
+}
+
+// Feed-forward pair on a stream's normed rows sb.xn: FF1 with GELU(tanh) into sb.ffh, FF2 with the caller's residual epilogue.
+template <typename T, typename Epi> static int ff_block(const FwdCtx& f, const StreamBuf<T>& sb, const StreamW<T>& sw, const Epi& out_epi) {
     const int D = f.e->cfg.dim, F = f.e->cfg.ff_dim, pl = f.pl();
-    f.ablate(16, w.xn, D);
-    CHK(f.gemm(w.xn, D, bw.ff1, F, D, EpiStore<T>{w.ffh, F, bw.ff1.b, F5_ACT_GELU_TANH, pl, f.wt(F5_WT_STORE16)}, pl));
-    f.ablate(32, w.ffh, F);
-    return f.gemm(w.ffh, F, bw.ff2, D, F, out_epi, pl);
+    f.ablate(16, sb.xn, D);
+    CHK(f.gemm(sb.xn, D, sw.ff1, F, D, EpiStore<T>{sb.ffh, F, sw.ff1.b, F5_ACT_GELU_TANH, pl, f.wt(F5_WT_STORE16)}, pl));
+    f.ablate(32, sb.ffh, F);
+    return f.gemm(sb.ffh, F, sw.ff2, D, F, out_epi, pl);
 }
 
 // Output projection of the normed stream xn into pred.  U = T: w.xn as the final norm left it; U = float (F5_PREC_F16P): pre-split f32
@@ -662,57 +710,76 @@ template <typename T, typename U> static int project_out(const FwdCtx& f, const 
     }
 }
 
-// One DiT forward over Bp packed rows (dit.py:297-327).  mod_row: AdaLN vectors of this step; mod_stride: distance
-// between batch rows' vectors (0 when every row shares the time step, as in sample()).  A packed batch with mod_stride != 0 (a per-item
-// call on packed rows) finds a row's vectors through the rowmap's batch row: layernorm_rows_kernel and EpiGateResRows.
-template <typename T>
-static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N,
-                           const float* mod_row, int mod_stride, const int* lens_dev, int drop_cond_first,
-                           const float* text_first, const float* text_second, hipStream_t s, const RowPack& pk = RowPack{}) {
+// The tail of every forward: final norm of the stream, output projection into pred.  norm(out, planar): the caller's AdaLN / RMSNorm of
+// its residual stream.  F5_PREC_F16P (e->io_split): normed to pre-split f32 rows in free_f32, a buffer of [rows, D] floats the caller no
+// longer needs, and projected as a product of two pre-split operands; otherwise through w.xn.
+template <typename T, typename Norm> static int finish(const FwdCtx& f, Work<T>& w, float* free_f32, float* pred, const Norm& norm) {
+    if (f.e->io_split) {
+        HIPCHK(norm(free_f32, 1));
+        return project_out<T, float>(f, free_f32, pred);
+    }
+    HIPCHK(norm(w.xn, f.pl()));
+    f.ablate(256, w.xn, f.e->cfg.dim);
+    return project_out<T, T>(f, w.xn, pred);
+}
+
+// What one backbone forward is called with (run_backbone).
+struct ForwardArgs {
+    const float *y, *cond;       // state and conditioning audio [B, N, mel]
+    int B, Bp, N;                // Bp = B, or 2 B: the conditional half, then the unconditional half
+    // time rows: the AdaLN vectors [modN] (DiT, MMDiT) or the time embedding [D] (UNetT) of batch row b at time_rows + b * time_stride;
+    // stride 0: one row shared by every batch row, as in sample()
+    const float* time_rows;
+    int time_stride;
+    const int* lens_dev;         // per-batch-row lengths, or null
+    int drop_cond_first;         // whether the first half drops cond too (the second always does)
+    const float *text_first, *text_second;   // text embeddings of the two halves: [B, N, Dt], MMDiT [B, nt, D]
+    int nt;                      // MMDiT: the text stream's length (the other backbones stretch their text to N)
+    RowPack pk;                  // packed variable-length batch (DiT only), or empty
+    float* taps;                 // f5k_mmdit_taps (diagnostic), or null
+};
+// width of one time row, and the table sample() and forward() keep them in (run_time_path)
+static int time_width(const f5_engine* e) { return e->cfg.backbone == F5_BACKBONE_UNETT ? e->cfg.dim : e->modN; }
+template <typename T> static const float* time_table_dev(const f5_engine* e, const Work<T>& w) {
+    return e->cfg.backbone == F5_BACKBONE_UNETT ? w.temb : w.mod;
+}
+
+// One DiT forward over Bp packed rows (dit.py:297-327).  a.time_rows: AdaLN vectors of this step.  A packed batch with a time stride (a
+// per-item call on packed rows) finds a row's vectors through the rowmap's batch row: layernorm_rows_kernel and EpiGateResRows.
+template <typename T> static int run_dit_forward(f5_engine* e, Work<T>& w, const ForwardArgs& a, hipStream_t s) {
     Packed<T>& P = packed<T>(e);
     const f5_config& c = e->cfg;
-    const int D = c.dim, rows = Bp * N;
-    const FwdCtx f{e, s, B, Bp, N, rows, lens_dev, pk};
+    const int D = c.dim, N = a.N, rows = a.Bp * N, mod_stride = a.time_stride;
+    const RowPack& pk = a.pk;
+    const FwdCtx f{e, s, a.B, a.Bp, N, rows, a.lens_dev, pk};
     const int* ml = f.ml();
     const int mh = f.mh(), pl = f.pl();
-    const int* gate_lens = pk ? nullptr : lens_dev; // (a packed batch has no padded rows to leave untouched)
+    const int* gate_lens = pk ? nullptr : a.lens_dev; // (a packed batch has no padded rows to leave untouched)
     Prof& pr = e->prof;
-    if (e->io_split) CHK((embed_input<T, float>(f, w, y, cond, drop_cond_first, text_first, text_second, w.x)));
-    else CHK((embed_input<T, T>(f, w, y, cond, drop_cond_first, text_first, text_second, w.x, true)));
+    if (e->io_split) CHK((embed_input<T, float>(f, w, a.y, a.cond, a.drop_cond_first, a.text_first, a.text_second, w.x)));
+    else CHK((embed_input<T, T>(f, w, a.y, a.cond, a.drop_cond_first, a.text_first, a.text_second, w.x, true)));
     const bool long_skip = (c.options & F5_OPT_LONG_SKIP) != 0;
     if (long_skip)   // residual = x (dit.py:313-314); h is free once the conv embedding has used it as its own residual
         HIPCHK(hipMemcpyAsync(w.h, w.x, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     const bool qk_norm = (c.options & F5_OPT_QK_RMSNORM) != 0;
     // weight prefetch from the LayerNorm launches (see layernorm_kernel): only where the GEMMs are latency-bound
     const bool wpf = rows <= 4096 && e->sw.weight_prefetch;
-    auto prefetch = [&](const LinW<T>& a, const LinW<T>& b) {   // the weights of the two GEMMs behind a LayerNorm
-        return wpf ? Prefetch{(const char*)a.w, (size_t)a.N * a.ldw * sizeof(T), (const char*)b.w, (size_t)b.N * b.ldw * sizeof(T)} : Prefetch{};
+    auto prefetch = [&](const LinW<T>& g0, const LinW<T>& g1) {   // the weights of the two GEMMs behind a LayerNorm
+        return wpf ? Prefetch{(const char*)g0.w, (size_t)g0.N * g0.ldw * sizeof(T), (const char*)g1.w, (size_t)g1.N * g1.ldw * sizeof(T)} : Prefetch{};
     };
-    // AdaLN LayerNorm of the stream into out (rows of T, or pre-split f32 rows): out = LN(x) * (1 + scale) + shift
     const bool row_mods = pk && mod_stride != 0;   // every batch row of a packed batch has its own vectors
-    auto adaln = [&](auto* out, const float* scale, const float* shift, const Prefetch& pf, int planar) {
-        using TO = std::remove_pointer_t<decltype(out)>;
-        return pr.timed(PC_LN, s, [&] {
-            if (row_mods)
-                hipLaunchKernelGGL((layernorm_rows_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, out, D, rows, D, 1e-6f, scale,
-                                   shift, mod_stride, pf, ml, pk.rowmap, planar, f.wt(F5_WT_LN));
-            else
-            hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, w.x, D, out, D, rows, D, 1e-6f, scale, shift,
-                               mod_stride, N, 1, pf, ml, planar, f.wt(F5_WT_LN));
-            return hipGetLastError();
-        });
-    };
+    const StreamBuf<T> sb{w.x, w.xn, w.ffh, w.ao};
     for (int l = 0; l < c.depth; ++l) {
-        BlockW<T>& bw = P.blocks[l];
-        const float* m = mod_row + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        const EpiGateRes attn_epi{w.x, w.x, D, bw.out.b, m + 2 * D, mod_stride, N, gate_lens, f.wt(F5_WT_GATE_RES)};
-        const EpiGateRes ff_epi{w.x, w.x, D, bw.ff2.b, m + 5 * D, mod_stride, N, nullptr, f.wt(F5_WT_GATE_RES)};
-        HIPCHK(adaln(w.xn, m + D, m, prefetch(bw.qkv, bw.out), pl));
-        if (row_mods) CHK(attention_block<T>(f, w, bw, qk_norm, EpiGateResRows{attn_epi, pk.rowmap}));
-        else CHK(attention_block<T>(f, w, bw, qk_norm, attn_epi));
-        HIPCHK(adaln(w.xn, m + 4 * D, m + 3 * D, prefetch(bw.ff1, bw.ff2), pl));
-        if (row_mods) CHK(ff_block<T>(f, w, bw, EpiGateResRows{ff_epi, pk.rowmap}));
-        else CHK(ff_block<T>(f, w, bw, ff_epi));
+        const StreamW<T>& sw = P.blocks[l].x;
+        const float* m = a.time_rows + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        const EpiGateRes attn_epi{w.x, w.x, D, sw.out.b, m + 2 * D, mod_stride, N, gate_lens, f.wt(F5_WT_GATE_RES)};
+        const EpiGateRes ff_epi{w.x, w.x, D, sw.ff2.b, m + 5 * D, mod_stride, N, nullptr, f.wt(F5_WT_GATE_RES)};
+        HIPCHK(adaln_norm(f, w.x, w.xn, m + D, m, mod_stride, prefetch(sw.qkv, sw.out), pl));
+        if (row_mods) CHK(attention_block<T>(f, w, sw, qk_norm, EpiGateResRows{attn_epi, pk.rowmap}));
+        else CHK(attention_block<T>(f, w, sw, qk_norm, attn_epi));
+        HIPCHK(adaln_norm(f, w.x, w.xn, m + 4 * D, m + 3 * D, mod_stride, prefetch(sw.ff1, sw.ff2), pl));
+        if (row_mods) CHK(ff_block<T>(f, sb, sw, EpiGateResRows{ff_epi, pk.rowmap}));
+        else CHK(ff_block<T>(f, sb, sw, ff_epi));
     }
     if (long_skip) {   // x = long_skip_connection(cat((x, residual), dim=-1))   (dit.py:323-324)
         auto cat_skip = [&](auto* cat) {
@@ -733,39 +800,32 @@ static int run_dit_forward(f5_engine* e, Work<T>& w, const float* y, const float
             CHK(f.gemm(w.cat2, 2 * D, P.long_skip, D, 2 * D, epi));
         }
     }
-    const float* mf = mod_row + (size_t)c.depth * 6 * D;  // (scale, shift)
-    if (e->io_split) {   // F5_PREC_F16P: final norm to f32 (pre-split rows in c1, free since the conv embedding) + split output projection
-        HIPCHK(adaln(w.c1, mf, mf + D, Prefetch{}, 1));
-        return project_out<T, float>(f, w.c1, w.pred);
-    }
-    HIPCHK(adaln(w.xn, mf, mf + D, Prefetch{}, pl));
-    f.ablate(256, w.xn, D);
-    return project_out<T, T>(f, w.xn, w.pred);
+    const float* mf = a.time_rows + (size_t)c.depth * 6 * D;  // (scale, shift)
+    // (F5_PREC_F16P: the pre-split rows go to c1, free since the conv embedding)
+    return finish<T>(f, w, w.c1, w.pred, [&](auto* out, int planar) { return adaln_norm(f, w.x, out, mf, mf + D, mod_stride, Prefetch{}, planar); });
 }
 
 // One UNetT forward over Bp packed rows (unett.py:217-280): time token prepended (N + 1 tokens per row), concat skip
-// connections, x_transformers RMSNorm, no AdaLN.  temb: time embedding rows ([1, D] shared when temb_stride == 0).
-template <typename T>
-static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N,
-                             const float* temb, int temb_stride, const int* lens_dev, int drop_cond_first,
-                             const float* text_first, const float* text_second, hipStream_t s) {
+// connections, x_transformers RMSNorm, no AdaLN.  a.time_rows: time embedding rows.
+template <typename T> static int run_unett_forward(f5_engine* e, Work<T>& w, const ForwardArgs& a, hipStream_t s) {
     Packed<T>& P = packed<T>(e);
     const f5_config& c = e->cfg;
-    const int D = c.dim, mel = c.mel_dim;
+    const int D = c.dim, mel = c.mel_dim, B = a.B, Bp = a.Bp, N = a.N;
     const int Nt = N + 1;
     const int rows_in = Bp * N, rows = Bp * Nt;
+    const int* lens_dev = a.lens_dev;
     Prof& pr = e->prof;
     float* emb = reinterpret_cast<float*>(w.cat2);  // [rows, 2D] of T >= [rows_in, D] f32; free until the first concat; conv input and output must not alias
     // the input embedding runs on the N frames of every row, unpacked and (unett.py:99-100: conv_pos_embed is called WITHOUT a mask) unmasked
     const FwdCtx in{e, s, B, Bp, N, rows_in, nullptr, RowPack{}};
-    if (e->io_split) CHK((embed_input<T, float>(in, w, y, cond, drop_cond_first, text_first, text_second, emb)));
-    else CHK((embed_input<T, T>(in, w, y, cond, drop_cond_first, text_first, text_second, emb)));
+    if (e->io_split) CHK((embed_input<T, float>(in, w, a.y, a.cond, a.drop_cond_first, a.text_first, a.text_second, emb)));
+    else CHK((embed_input<T, T>(in, w, a.y, a.cond, a.drop_cond_first, a.text_first, a.text_second, emb)));
     // The skip stack needs no copies: the stream entering block l < depth/2 is WRITTEN into skip slot l (by the assemble kernel / the
     // FF2 epilogue of block l - 1), the block's first residual update reads it there and writes w.x, and nothing writes the slot again.
     const int half = c.depth / 2;
     auto slot = [&](int l) { return w.skips + (size_t)l * rows * D; };
     HIPCHK(pr.timed(PC_MISC, s, [&] {
-        launch_unett_assemble(s, emb, temb, temb_stride, half > 0 ? slot(0) : w.x, Bp, N, D);
+        launch_unett_assemble(s, emb, a.time_rows, a.time_stride, half > 0 ? slot(0) : w.x, Bp, N, D);
         return hipGetLastError();
     }));
     const FwdCtx f{e, s, B, Bp, Nt, rows, lens_dev, RowPack{}};   // the blocks: N + 1 tokens per row; lens_dev holds len + 1 for UNetT
@@ -776,6 +836,7 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
             return hipGetLastError();
         });
     };
+    const StreamBuf<T> sb{w.x, w.xn, w.ffh, w.ao};
     for (int l = 0; l < c.depth; ++l) {
         BlockW<T>& bw = P.blocks[l];
         const float* x_in = l < half ? slot(l) : w.x;            // the stream entering the block (= skips.append(x), unett.py:258-259)
@@ -790,17 +851,12 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
             CHK(f.gemm(w.cat2, 2 * D, bw.skip, D, 2 * D, EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}, pl));
         }
         HIPCHK(rmsnorm(x_in, w.xn, bw.norm1_g, pl));
-        CHK(attention_block<T>(f, w, bw, false, EpiGateRes{w.x, x_in, D, bw.out.b, nullptr, 0, Nt, lens_dev, f.wt(F5_WT_GATE_RES)}));
+        CHK(attention_block<T>(f, w, bw.x, false, EpiGateRes{w.x, x_in, D, bw.x.out.b, nullptr, 0, Nt, lens_dev, f.wt(F5_WT_GATE_RES)}));
         HIPCHK(rmsnorm(w.x, w.xn, bw.norm2_g, pl));
-        CHK(ff_block<T>(f, w, bw, EpiGateRes{x_out, w.x, D, bw.ff2.b, nullptr, 0, Nt, nullptr, f.wt(F5_WT_GATE_RES)}));
+        CHK(ff_block<T>(f, sb, bw.x, EpiGateRes{x_out, w.x, D, bw.x.ff2.b, nullptr, 0, Nt, nullptr, f.wt(F5_WT_GATE_RES)}));
     }
-    if (e->io_split) {   // F5_PREC_F16P: final norm to pre-split f32 rows (in the skip stack's first slot: every skip has been popped) + split projection
-        HIPCHK(rmsnorm(w.x, w.skips, P.norm_out_g, 1));
-        CHK((project_out<T, float>(f, w.skips, w.pred_all)));
-    } else {
-        HIPCHK(rmsnorm(w.x, w.xn, P.norm_out_g, pl));
-        CHK((project_out<T, T>(f, w.xn, w.pred_all)));
-    }
+    // (F5_PREC_F16P: the pre-split rows go to the skip stack's first slot: every skip has been popped)
+    CHK(finish<T>(f, w, w.skips, w.pred_all, [&](auto* out, int planar) { return rmsnorm(w.x, out, P.norm_out_g, planar); }));
     HIPCHK(pr.timed(PC_MISC, s, [&] {
         launch_strip_first_token(s, w.pred_all, w.pred, Bp, N, mel);
         return hipGetLastError();
@@ -810,27 +866,26 @@ static int run_unett_forward(f5_engine* e, Work<T>& w, const float* y, const flo
 
 // One MMDiT forward over Bp batch rows (mmdit.py:172-213, MMDiTBlock modules.py:743-771, JointAttnProcessor modules.py:555-645): the
 // audio stream x [Bp, N, D] (w.x) and the text stream c [Bp, nt, D] (w.mm_c) have their own weights and AdaLN vectors and meet only
-// inside one softmax over nt + N keys.  text_first / text_second: the text embeddings [B, nt, D] of the two halves.
+// inside one softmax over nt + N keys.  a.text_first / a.text_second: the text embeddings [B, nt, D] of the two halves.
 //
 // Joint layout (mmdit.h): TEXT FIRST -- positions [0, nt) are c, [nt, nt + N) are x -- so that the valid keys of batch row b, every
 // text key (padded text rows included: the reference never masks them) and the audio keys below lens[b], are the prefix nt + lens[b]
 // and the attention kernels run as they are.  q, k and v^T of both streams land in the joint image straight from the two QKV GEMM
-// epilogues (EpiQKV<T, true>: destination offset and layout length apart from the rotary position, which counts from 0 per stream).
-// The batch runs rectangular: the input conv is called without a mask (mmdit.py:78), so padded frames reach valid ones and are computed.
+// epilogues (qkv_project with a QKVJointLayout: destination offset and layout length apart from the rotary position, which counts from 0
+// per stream).  The batch runs rectangular: the input conv is called without a mask (mmdit.py:78), so padded frames reach valid ones and
+// are computed.
 //
-// Launches per block (a condition, not a measurement): 4 LayerNorm (x and c before the attention, x and c before the FF), 2 QKV,
-// 1 attention, 1 split of its output into the two dense out-projection operands, 2 out-projections, 4 FF GEMMs = 14, plus 2
-// norm-rope launches with qk_norm.  The last block (context_pre_only) has no text out-projection, LayerNorm or FF: 3 LayerNorm, 2 QKV,
-// 1 attention, 1 split, 1 out-projection, 2 FF GEMMs = 10.  Per forward, ahead of the blocks: one launch that zeroes v^T (its Lpad tail columns
-// and whatever the arena held are read by the attention's last key tile, multiplied by zero probabilities) and, with lengths, one
-// launch that makes the joint key lengths.
-template <typename T>
-static int run_mmdit_forward(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, int nt,
-                             const float* mod_row, int mod_stride, const int* lens_dev, int drop_cond_first,
-                             const float* text_first, const float* text_second, hipStream_t s, float* taps = nullptr) {
+// Launches per block (a condition, not a measurement; tests/test_forward_launches_gpu.py holds it): 4 LayerNorm (x and c before the
+// attention, x and c before the FF), 2 QKV, 1 attention, 1 split of its output into the two dense out-projection operands, 2
+// out-projections, 4 FF GEMMs = 14, plus 2 norm-rope launches with qk_norm.  The last block (context_pre_only) has no text out-projection,
+// LayerNorm or FF: 3 LayerNorm, 2 QKV, 1 attention, 1 split, 1 out-projection, 2 FF GEMMs = 10.  Per forward, ahead of the blocks: one
+// launch that zeroes v^T (its Lpad tail columns and whatever the arena held are read by the attention's last key tile, multiplied by zero
+// probabilities) and, with lengths, one launch that makes the joint key lengths.
+template <typename T> static int run_mmdit_forward(f5_engine* e, Work<T>& w, const ForwardArgs& a, hipStream_t s) {
     Packed<T>& P = packed<T>(e);
     const f5_config& c = e->cfg;
-    const int D = c.dim, F = c.ff_dim, inner = e->inner, H = c.heads, L = nt + N;
+    const int D = c.dim, inner = e->inner, H = c.heads, B = a.B, Bp = a.Bp, N = a.N, nt = a.nt, L = nt + N, mod_stride = a.time_stride;
+    float* taps = a.taps;
     auto tap = [&](const float* src, size_t n) -> int {   // f5k_mmdit_taps (diagnostic): the next intermediate, behind the last one
         if (!taps) return F5_OK;
         HIPCHK(hipMemcpyAsync(taps, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -841,142 +896,84 @@ static int run_mmdit_forward(f5_engine* e, Work<T>& w, const float* y, const flo
     Prof& pr = e->prof;
     // the audio embedding: no text columns, the conv unmasked
     const FwdCtx in{e, s, B, Bp, N, Bp * N, nullptr, RowPack{}};
-    if (e->io_split) CHK((embed_input<T, float>(in, w, y, cond, drop_cond_first, nullptr, nullptr, w.x)));
-    else CHK((embed_input<T, T>(in, w, y, cond, drop_cond_first, nullptr, nullptr, w.x)));
+    if (e->io_split) CHK((embed_input<T, float>(in, w, a.y, a.cond, a.drop_cond_first, nullptr, nullptr, w.x)));
+    else CHK((embed_input<T, T>(in, w, a.y, a.cond, a.drop_cond_first, nullptr, nullptr, w.x)));
     CHK(tap(w.x, (size_t)Bp * N * D));
-    const FwdCtx fx{e, s, B, Bp, N, Bp * N, lens_dev, RowPack{}};      // the audio stream's rows
-    const FwdCtx fc{e, s, B, Bp, nt, Bp * nt, nullptr, RowPack{}};     // the text stream's rows
-    const int pl = fx.pl();
+    const FwdCtx fx{e, s, B, Bp, N, Bp * N, a.lens_dev, RowPack{}};           // the audio stream's rows
+    const FwdCtx fc{e, s, B, Bp, nt, Bp * nt, nullptr, RowPack{}, false};     // the text stream's rows (no F5_X3_ABLATE hooks: FwdCtx::x3)
+    const StreamBuf<T> bx{w.x, w.xn, w.ffh, w.mm_aox}, bc{w.mm_c, w.mm_cn, w.mm_ffc, w.mm_aoc};
     // c = cat(c_cond, c_uncond) (mmdit.py:194), or the one half of a forward without cfg_infer
     const size_t half_c = (size_t)B * nt * D * sizeof(float);
-    HIPCHK(hipMemcpyAsync(w.mm_c, text_first, half_c, hipMemcpyDeviceToDevice, s));
-    if (Bp > B) HIPCHK(hipMemcpyAsync(w.mm_c + (size_t)B * nt * D, text_second, half_c, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(w.mm_c, a.text_first, half_c, hipMemcpyDeviceToDevice, s));
+    if (Bp > B) HIPCHK(hipMemcpyAsync(w.mm_c + (size_t)B * nt * D, a.text_second, half_c, hipMemcpyDeviceToDevice, s));
     HIPCHK(pr.timed(PC_MISC, s, [&] {   // (Npad is a multiple of 64 elements: whole 16-byte pieces)
         const long n16 = (long)((size_t)Bp * H * 64 * w.Npad * sizeof(T) / 16);
         hipLaunchKernelGGL(zero_fill16_kernel, dim3(ew_blocks(n16)), dim3(256), 0, s, reinterpret_cast<uint4*>(w.vt), n16);
         return hipGetLastError();
     }));
     const int* kv_lens = nullptr;
-    if (lens_dev) {   // mask = pad(mask, (0, nt), value=True) (modules.py:617), text first: the key prefix nt + len
+    if (a.lens_dev) {   // mask = pad(mask, (0, nt), value=True) (modules.py:617), text first: the key prefix nt + len
         HIPCHK(pr.timed(PC_MISC, s, [&] {
-            hipLaunchKernelGGL(joint_lens_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, lens_dev, w.mm_lens, Bp, nt);
+            hipLaunchKernelGGL(joint_lens_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, a.lens_dev, w.mm_lens, Bp, nt);
             return hipGetLastError();
         }));
         kv_lens = w.mm_lens;
     }
     const bool qk_norm = (c.options & F5_OPT_QK_RMSNORM) != 0;
-    // AdaLN LayerNorm of a stream (rows of n tokens per batch row) into out: LN(x) * (1 + scale) + shift
-    auto adaln = [&](const FwdCtx& f, const float* x, auto* out, const float* scale, const float* shift, int planar) {
-        using TO = std::remove_pointer_t<decltype(out)>;
-        return pr.timed(PC_LN, s, [&] {
-            hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((f.rows + 3) / 4), dim3(256), 0, s, x, D, out, D, f.rows, D, 1e-6f, scale, shift,
-                               mod_stride, f.N, 1, Prefetch{}, (const int*)nullptr, planar, f.wt(F5_WT_LN));
-            return hipGetLastError();
-        });
+    // a stream's AdaLN LayerNorm (no prefetch), and the gated residual update of its stream by an out-projection or FF2
+    auto norm = [&](const FwdCtx& f, const StreamBuf<T>& b, const float* scale, const float* shift) {
+        return adaln_norm(f, b.x, b.xn, scale, shift, mod_stride, Prefetch{}, f.pl());
     };
-    // F5_PREC_F16X3 with plain-f16 attention products (as attention_block): q / k / v^T leave the QKV epilogues as f16
-    bool attn16 = false;
-    if constexpr (std::is_same_v<T, float>) attn16 = e->split16 && e->sw.x3_attn_hi() == 3 && !qk_norm;
-    // one stream's QKV projection into the joint image at layout offset `off`
-    auto qkv = [&](const FwdCtx& f, const T* a, const LinW<T>& lw, int off) -> int {
-        const QKVJointLayout jl{L, off};
-        if constexpr (std::is_same_v<T, float>) {
-            if (attn16) {
-                f16_t *q = reinterpret_cast<f16_t*>(w.q), *k = reinterpret_cast<f16_t*>(w.k), *vt = reinterpret_cast<f16_t*>(w.vt);
-                return f.gemm(a, D, lw, 3 * inner, D,
-                              EpiQKV<f16_t, true>{q, k, vt, lw.b, P.rope_frag, f.N, w.Npad, H, H, attention_q_scale<f16_t>(), nullptr, jl}, pl);
-            }
-        }
-        return f.gemm(a, D, lw, 3 * inner, D,
-                      EpiQKV<T, true>{w.q, w.k, w.vt, lw.b, P.rope_frag, f.N, w.Npad, H, qk_norm ? 0 : H,
-                                      qk_norm ? 1.0f : attention_q_scale<T>(), nullptr, jl}, pl);
+    auto gate_res = [&](const FwdCtx& f, const StreamBuf<T>& b, const LinW<T>& lw, const float* gate, const int* lens) {
+        return EpiGateRes{b.x, b.x, D, lw.b, gate, mod_stride, f.N, lens, f.wt(F5_WT_GATE_RES)};
     };
-    // qk_norm: RMSNorm with the stream's own gains BEFORE the rotary embedding (modules.py:588-608); the epilogue left q / k raw
-    auto norm_rope = [&](const FwdCtx& f, const float* gq, const float* gk, int off) {
-        const long qrows = (long)Bp * H * f.N;
-        return pr.timed(PC_MISC, s, [&] {
-            hipLaunchKernelGGL((qknorm_rope_joint_kernel<T>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, w.q, w.k, gq, gk,
-                               P.rope_cos, P.rope_sin, qrows, f.N, L, off, attention_q_scale<T>(), 1e-6f);
-            return hipGetLastError();
-        });
-    };
-    const double attn_fl = 4.0 * H * 64 * (double)Bp * L * L;
     const int row16 = inner * (int)sizeof(T) / 16;
     for (int l = 0; l < c.depth; ++l) {
-        BlockW<T>& bw = P.blocks[l];
+        const StreamW<T>&wx = P.blocks[l].x, &wc = P.blocks[l].c;
         const bool last = l == c.depth - 1;   // context_pre_only: c is normed, attended to, and dropped
-        const float* mx = mod_row + (size_t)l * 12 * D;   // x: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        const float* mc = mx + 6 * D;                     // c: the same six; in the last block (scale, shift) of an AdaLayerNorm_Final
-        HIPCHK(adaln(fx, w.x, w.xn, mx + D, mx, pl));
-        HIPCHK(adaln(fc, w.mm_c, w.mm_cn, last ? mc : mc + D, last ? mc + D : mc, pl));
-        CHK(qkv(fc, w.mm_cn, bw.qkv_c, 0));
-        CHK(qkv(fx, w.xn, bw.qkv, nt));
-        if (qk_norm) {
-            HIPCHK(norm_rope(fc, bw.qn_c, bw.kn_c, 0));
-            HIPCHK(norm_rope(fx, bw.qn, bw.kn, nt));
-        }
+        const float* mx = a.time_rows + (size_t)l * 12 * D;   // x: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        const float* mc = mx + 6 * D;                         // c: the same six; in the last block (scale, shift) of an AdaLayerNorm_Final
+        HIPCHK(norm(fx, bx, mx + D, mx));
+        HIPCHK(norm(fc, bc, last ? mc : mc + D, last ? mc + D : mc));
+        CHK(qkv_project<T>(fc, w, bc.xn, wc, qk_norm, QKVJointLayout{L, 0}));
+        CHK(qkv_project<T>(fx, w, bx.xn, wx, qk_norm, QKVJointLayout{L, nt}));
         // every query row is computed (q_lens null): no row of ao is left as the arena held it
-        HIPCHK(pr.timed(PC_ATTN, s, attn_fl, [&] {
-            if constexpr (std::is_same_v<T, float>) {
-                if (attn16)
-                    return launch_attention_v2<f16_t>(s, reinterpret_cast<f16_t*>(w.q), reinterpret_cast<f16_t*>(w.k), reinterpret_cast<f16_t*>(w.vt),
-                                                      nullptr, Bp, H, L, w.Npad, kv_lens, Bp, nullptr, nullptr, w.ao);
-            }
-            return launch_attention_any(s, w.q, w.k, w.vt, w.ao, Bp, H, L, w.Npad, kv_lens, Bp, nullptr, nullptr, e->split16, pl, e->sw.x3_attn_hi(),
-                                        fx.wt(F5_WT_ATTN));
-        }));
+        CHK(attend<T>(fx, w, qk_norm, L, kv_lens, Bp, nullptr));
         HIPCHK(pr.timed(PC_MISC, s, [&] {
             hipLaunchKernelGGL(joint_split_kernel, dim3(ew_blocks((long)Bp * L * row16)), dim3(256), 0, s, reinterpret_cast<const uint4*>(w.ao),
-                               last ? nullptr : reinterpret_cast<uint4*>(w.mm_aoc), reinterpret_cast<uint4*>(w.mm_aox), Bp, nt, N, row16);
+                               last ? nullptr : reinterpret_cast<uint4*>(bc.ao), reinterpret_cast<uint4*>(bx.ao), Bp, nt, N, row16);
             return hipGetLastError();
         }));
         if (!last) {   // the text stream: never gated by length (modules.py:643)
-            CHK(fc.gemm(w.mm_aoc, inner, bw.out_c, D, inner,
-                        EpiGateRes{w.mm_c, w.mm_c, D, bw.out_c.b, mc + 2 * D, mod_stride, nt, nullptr, fc.wt(F5_WT_GATE_RES)}, pl));
-            HIPCHK(adaln(fc, w.mm_c, w.mm_cn, mc + 4 * D, mc + 3 * D, pl));
-            CHK(fc.gemm(w.mm_cn, D, bw.ff1_c, F, D, EpiStore<T>{w.mm_ffc, F, bw.ff1_c.b, F5_ACT_GELU_TANH, pl, fc.wt(F5_WT_STORE16)}, pl));
-            CHK(fc.gemm(w.mm_ffc, F, bw.ff2_c, D, F,
-                        EpiGateRes{w.mm_c, w.mm_c, D, bw.ff2_c.b, mc + 5 * D, mod_stride, nt, nullptr, fc.wt(F5_WT_GATE_RES)}, pl));
+            CHK(out_project<T>(fc, bc.ao, wc, gate_res(fc, bc, wc.out, mc + 2 * D, nullptr)));
+            HIPCHK(norm(fc, bc, mc + 4 * D, mc + 3 * D));
+            CHK(ff_block<T>(fc, bc, wc, gate_res(fc, bc, wc.ff2, mc + 5 * D, nullptr)));
         }
         // the audio stream: padded rows get no attention residual (x.masked_fill(~mask, 0), modules.py:640-642) but do get the FF's
-        CHK(fx.gemm(w.mm_aox, inner, bw.out, D, inner,
-                    EpiGateRes{w.x, w.x, D, bw.out.b, mx + 2 * D, mod_stride, N, lens_dev, fx.wt(F5_WT_GATE_RES)}, pl));
-        HIPCHK(adaln(fx, w.x, w.xn, mx + 4 * D, mx + 3 * D, pl));
-        CHK(ff_block<T>(fx, w, bw, EpiGateRes{w.x, w.x, D, bw.ff2.b, mx + 5 * D, mod_stride, N, nullptr, fx.wt(F5_WT_GATE_RES)}));
-        if (!last) CHK(tap(w.mm_c, (size_t)Bp * nt * D));
-        CHK(tap(w.x, (size_t)Bp * N * D));
+        CHK(out_project<T>(fx, bx.ao, wx, gate_res(fx, bx, wx.out, mx + 2 * D, a.lens_dev)));
+        HIPCHK(norm(fx, bx, mx + 4 * D, mx + 3 * D));
+        CHK(ff_block<T>(fx, bx, wx, gate_res(fx, bx, wx.ff2, mx + 5 * D, nullptr)));
+        if (!last) CHK(tap(bc.x, (size_t)Bp * nt * D));
+        CHK(tap(bx.x, (size_t)Bp * N * D));
     }
-    const float* mf = mod_row + ((size_t)c.depth * 12 - 4) * D;   // norm_out: (scale, shift)
-    if (e->io_split) {   // F5_PREC_F16P: final norm to pre-split f32 rows (in c1, free since the conv embedding) + split output projection
-        HIPCHK(adaln(fx, w.x, w.c1, mf, mf + D, 1));
-        return project_out<T, float>(fx, w.c1, w.pred);
-    }
-    HIPCHK(adaln(fx, w.x, w.xn, mf, mf + D, pl));
-    return project_out<T, T>(fx, w.xn, w.pred);
+    const float* mf = a.time_rows + ((size_t)c.depth * 12 - 4) * D;   // norm_out: (scale, shift)
+    // (F5_PREC_F16P: the pre-split rows go to c1, free since the conv embedding)
+    return finish<T>(fx, w, w.c1, w.pred, [&](auto* out, int planar) { return adaln_norm(fx, w.x, out, mf, mf + D, mod_stride, Prefetch{}, planar); });
 }
 
-// dispatches one backbone forward; `step_row` selects the time step's vectors inside the per-call tables
-template <typename T>
-static int run_backbone(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, int step_row,
-                        int per_row_time, const int* lens_dev, int drop_cond_first, const float* text_first,
-                        const float* text_second, hipStream_t s, const RowPack& pk = RowPack{}, int nt = 0, float* taps = nullptr) {
-    if (e->cfg.backbone == F5_BACKBONE_DIT)
-        return run_dit_forward<T>(e, w, y, cond, B, Bp, N, w.mod + (size_t)step_row * e->modN, per_row_time ? e->modN : 0,
-                                  lens_dev, drop_cond_first, text_first, text_second, s, pk);
-    if (e->cfg.backbone == F5_BACKBONE_MMDIT)   // (nt: the text stream's length; the other backbones stretch their text to N)
-        return run_mmdit_forward<T>(e, w, y, cond, B, Bp, N, nt, w.mod + (size_t)step_row * e->modN, per_row_time ? e->modN : 0,
-                                    lens_dev, drop_cond_first, text_first, text_second, s, taps);
-    return run_unett_forward<T>(e, w, y, cond, B, Bp, N, w.temb + (size_t)step_row * e->cfg.dim, per_row_time ? e->cfg.dim : 0,
-                                lens_dev, drop_cond_first, text_first, text_second, s);
-}
-// ... with one time row per batch row, gathered by the caller (mod_gather_kernel): rows [Bp, modN] (DiT) or [Bp, D] (UNetT)
-template <typename T>
-static int run_backbone_rows(f5_engine* e, Work<T>& w, const float* y, const float* cond, int B, int Bp, int N, const float* rows,
-                             const int* lens_dev, const float* text_first, const float* text_second, hipStream_t s,
-                             const RowPack& pk = RowPack{}) {
-    if (e->cfg.backbone == F5_BACKBONE_DIT)
-        return run_dit_forward<T>(e, w, y, cond, B, Bp, N, rows, e->modN, lens_dev, 0, text_first, text_second, s, pk);
-    return run_unett_forward<T>(e, w, y, cond, B, Bp, N, rows, e->cfg.dim, lens_dev, 0, text_first, text_second, s);
+// One backbone forward.  What a backbone cannot run is refused here, by name, and never falls through to another backbone's body: packed
+// rows exist for the DiT only (the API refuses such calls before anything is planned, engine.hip; this is the backstop).
+template <typename T> static int run_backbone(f5_engine* e, Work<T>& w, const ForwardArgs& a, hipStream_t s) {
+    switch (e->cfg.backbone) {
+        case F5_BACKBONE_DIT: return run_dit_forward<T>(e, w, a, s);
+        case F5_BACKBONE_UNETT:
+            if (a.pk) return fail(F5_ESTATE, "the UNetT backbone cannot run a packed batch");
+            return run_unett_forward<T>(e, w, a, s);
+        case F5_BACKBONE_MMDIT:
+            if (a.pk) return fail(F5_ESTATE, "the MMDiT backbone cannot run a packed batch");
+            return run_mmdit_forward<T>(e, w, a, s);
+    }
+    return fail(F5_ESTATE, "unknown backbone %d", e->cfg.backbone);
 }
 // the text staging buffer is part of the arena plan: a longer text moves the carve offsets
 static void reserve_text(f5_engine* e, int nt) {
@@ -1072,14 +1069,12 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
     CHK(run_time_path<T>(e, w, Bp, s));
     // UNetT embeds text at the padded length for every sample (unett.py:196-215), DiT at each sample's own length
     const int* tlens = (e->cfg.backbone == F5_BACKBONE_DIT && lens_host) ? w.lens_plain : nullptr;
-    if (cfg_infer) {
-        CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 0, w.text_c, s));
-        CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 1, w.text_u, s));
-        CHK(run_backbone<T>(e, w, x, cond, B, Bp, N, 0, 1, lens_dev, 0, w.text_c, w.text_u, s, RowPack{}, nt, e->mm_taps));
-    } else {
-        CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, drop_text, w.text_c, s));
-        CHK(run_backbone<T>(e, w, x, cond, B, Bp, N, 0, 1, lens_dev, drop_audio_cond, w.text_c, w.text_c, s, RowPack{}, nt, e->mm_taps));
-    }
+    // every batch row has its own time: row b of the time table
+    ForwardArgs a{x, cond, B, Bp, N, time_table_dev<T>(e, w), time_width(e), lens_dev, 0, w.text_c, w.text_u, nt, RowPack{}, e->mm_taps};
+    CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, cfg_infer ? 0 : drop_text, w.text_c, s));
+    if (cfg_infer) CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 1, w.text_u, s));
+    else a.drop_cond_first = drop_audio_cond, a.text_second = w.text_c;
+    CHK(run_backbone<T>(e, w, a, s));
     HIPCHK(hipMemcpyAsync(out, w.pred, (size_t)Bp * N * e->cfg.mel_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     return F5_OK;
 }
@@ -1165,22 +1160,29 @@ template <typename T> static int sample_body(f5_engine* e, Work<T>& w, const Sam
         const size_t yo = p.frame_at(k) * mel, to = mmdit ? (size_t)k.u0 * p.nt * c.dim : p.frame_at(k) * c.text_dim;
         const float *cond = w.step_cond + yo, *tc = w.text_c + to, *tu = w.text_u + to;
         const int* lens = lens_dev ? lens_dev + p.lens_at(k) : nullptr;
+        const int tw = time_width(e);
+        // both halves in one batch, every batch row at time row `row`
+        ForwardArgs a{x, cond, k.bc, p.halves * k.bc, N, time_table_dev<T>(e, w) + (size_t)row * tw, 0, lens, 0, tc, p.use_cfg ? tu : tc, p.nt, pk, nullptr};
         if (p.items) {   // per-item times: evaluation `row` reads, for every batch row of the chunk, the time row its item is at
-            const bool dit = c.backbone == F5_BACKBONE_DIT;
             HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-                launch_mod_gather(s, dit ? w.mod : w.temb, w.it_idx + (size_t)row * B + k.u0, w.mod_rows, p.halves * k.bc, k.bc,
-                                  dit ? e->modN : c.dim);
+                launch_mod_gather(s, time_table_dev<T>(e, w), w.it_idx + (size_t)row * B + k.u0, w.mod_rows, a.Bp, k.bc, tw);
                 return hipGetLastError();
             }));
-            return run_backbone_rows<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, w.mod_rows, lens, tc, p.use_cfg ? tu : tc, s, pk);
+            a.time_rows = w.mod_rows;
+            a.time_stride = tw;
         }
-        if (!p.split) return run_backbone<T>(e, w, x, cond, k.bc, p.halves * k.bc, N, row, 0, lens, 0, tc, p.use_cfg ? tu : tc, s, pk, p.nt);
-        // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream
+        if (!p.split) return run_backbone<T>(e, w, a, s);
+        // conditional chain on s, unconditional chain (cond dropped, filler text) on the side stream: each half a batch of its own
         hipStream_t s1 = e->side_stream;
         HIPCHK(hipEventRecord(e->ev_fork, s));            // x (and, first time, the text embeddings) ready
         HIPCHK(hipStreamWaitEvent(s1, e->ev_fork, 0));
-        CHK(run_backbone<T>(e, w, x, cond, k.bc, k.bc, N, row, 0, lens, 0, tc, tc, s));
-        CHK(run_backbone<T>(e, w2, x, cond, k.bc, k.bc, N, row, 0, lens, 1, tu, tu, s1));
+        a.Bp = k.bc;
+        a.pk = RowPack{};
+        a.text_second = tc;
+        CHK(run_backbone<T>(e, w, a, s));
+        a.drop_cond_first = 1;
+        a.text_first = a.text_second = tu;
+        CHK(run_backbone<T>(e, w2, a, s1));
         HIPCHK(hipEventRecord(e->ev_join, s1));
         HIPCHK(hipStreamWaitEvent(s, e->ev_join, 0));
         return F5_OK;

@@ -81,15 +81,26 @@ template <typename T> struct LinW {
     int N = 0, K = 0, ldw = 0;
 };
 
+// One stream's weights of a block: q / k / v fused, out-projection, feed-forward pair
+template <typename T> struct StreamW {
+    LinW<T> qkv, out, ff1, ff2;
+    float *qn = nullptr, *kn = nullptr;   // F5_OPT_QK_RMSNORM: gains of the RMSNorm on q / k [64]
+};
 template <typename T> struct BlockW {
-    LinW<T> qkv, out, ff1, ff2, skip;  // skip: UNetT concat projection (no bias)
+    StreamW<T> x;                      // the only stream of the DiT / UNetT; the MMDiT's audio stream
+    // MMDiT: the text stream's own weights (to_q_c / to_k_c / to_v_c fused, to_out_c, ff_c, c_q_norm / c_k_norm); the last,
+    // context_pre_only block has neither c.out nor c.ff1 / c.ff2
+    StreamW<T> c;
+    LinW<T> skip;                      // UNetT concat projection (no bias)
     float* norm1_g = nullptr;          // UNetT RMSNorm gains
     float* norm2_g = nullptr;
-    float *qn = nullptr, *kn = nullptr;   // F5_OPT_QK_RMSNORM: gains of the RMSNorm on q / k [64]
-    // MMDiT: the text stream's own weights (to_q_c / to_k_c / to_v_c fused, to_out_c, ff_c, c_q_norm / c_k_norm); the last,
-    // context_pre_only block has neither out_c nor ff1_c / ff2_c
-    LinW<T> qkv_c, out_c, ff1_c, ff2_c;
-    float *qn_c = nullptr, *kn_c = nullptr;
+};
+// One stream's activation buffers in Work<T>: the f32 residual stream, its normed rows (the A operand of the QKV and FF1 GEMMs), the FF
+// hidden rows and the out-projection's operand.  DiT / UNetT and the MMDiT's audio stream: w.x, w.xn, w.ffh and w.ao (MMDiT: w.mm_aox);
+// the MMDiT's text stream: w.mm_c, w.mm_cn, w.mm_ffc, w.mm_aoc.
+template <typename T> struct StreamBuf {
+    float* x;
+    T *xn, *ffh, *ao;
 };
 
 struct TextBlockW {

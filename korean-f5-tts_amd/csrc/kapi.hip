@@ -132,7 +132,7 @@ template <typename F> static bool row_start_ok(const int32_t* rs, int Bp, int N,
     return rs[Bp] % 4 == 0;
 }
 
-// One attention launch as attention_block (engine_impl.h) makes it.  T = the type of q / k / v^T; p.mode 1 (T = f16_t under
+// One attention launch as attend (engine_impl.h) makes it.  T = the type of q / k / v^T; p.mode 1 (T = f16_t under
 // F5_PREC_F16X3): the f16 kernel writes pre-split f32 rows (Of) instead of T rows.
 template <typename T>
 static int attn_body(const float* q, const float* k, const float* v, int Bp, int H, int N, const f5k_attn& p, bool split16, hipStream_t s) {
@@ -308,8 +308,9 @@ extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* s
 }
 
 // ------------------------------------------------------------------------------------------- f5k_gemm_epi
-// One GEMM through a production epilogue: EpiStore / EpiGateRes / EpiQKV constructed field for field as engine_impl.h does, the
-// rotary table through rope_frag_kernel, packed rows through fill_rowmap_kernel, qk_norm through qknorm_rope_kernel.
+// One GEMM through a production epilogue: EpiStore / EpiGateRes / EpiQKV constructed field for field as engine_impl.h does (EpiQKV: its
+// qkv_project, own layout), the rotary table through rope_frag_kernel, packed rows through fill_rowmap_kernel, qk_norm through
+// launch_qknorm_rope, the launcher qkv_project calls.
 template <typename T, typename Epi>
 static int epi_gemm(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const Epi& epi, int cfg, const int* ml,
                     GemmOperands ops) {
@@ -344,12 +345,8 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
                     EpiQKV<TO>{q, k, static_cast<TO*>(p.out2), bias, frag.p, p.Nseq, p.Npad, p.H, norm ? 0 : p.pe_heads,
                                norm ? 1.0f : p.q_scale, rowmap.p},
                     p.cfg, ml, ops));
-    if (norm) {
-        const long qrows = (long)p.Bp * p.H * p.Nseq;
-        hipLaunchKernelGGL((qknorm_rope_kernel<TO>), dim3((unsigned)((qrows * 16 + 255) / 256)), dim3(256), 0, s, q, k, p.gq, p.gk,
-                           p.rope_cos, p.rope_sin, qrows, p.Nseq, p.H, p.pe_heads, p.q_scale, 1e-6f);
-        KCHK();
-    }
+    if (norm)   // (own layout: the stream is the whole sequence)
+        HIPCHK(launch_qknorm_rope<TO>(s, q, k, p.gq, p.gk, p.rope_cos, p.rope_sin, p.Bp, p.H, p.Nseq, p.Nseq, 0, p.pe_heads, p.q_scale, 1e-6f));
     CHK(copy_f32<TO>(s, p.out0, p.out0_f32, p.n0));
     CHK(copy_f32<TO>(s, p.out1, p.out1_f32, p.n1));
     CHK(copy_f32<TO>(s, p.out2, p.out2_f32, p.n2));

@@ -366,7 +366,8 @@ QKNORM_TOLS = {"f32": 2.5e-6, "f16x3": 1.5e-6, "f16x3p": 1.5e-6, "bf16": 1e-2, "
 @pytest.mark.parametrize("Bp,Nseq,H,pe", [(2, 1024, 16, 1), (3, 200, 4, 4)])
 def test_qknorm_matches_oracle(mode, Bp, Nseq, H, pe):
     """qk_norm = "rms_norm": the QKV epilogue leaves q / k raw (no rotary, no scale), qknorm_rope_kernel applies RMSNorm, rotary,
-    q scale in place.  Reference: oracle RMSNorm (F.rms_norm) and rotary_apply on the float64 QKV result of the rounded operands.
+    q scale in place -- through launch_qknorm_rope, the launcher the engine's qkv_project calls, in the own layout (layout length =
+    Nseq, offset 0; the MMDiT's joint layout is the same kernel at another length and offset).  Reference: oracle RMSNorm (F.rms_norm) and rotary_apply on the float64 QKV result of the rounded operands.
     Under bf16 / f16 the raw q / k are rounded to 16 bit between the two launches and the result again at the end: two roundings
     of the operand type, so the tolerance there is a few of its ulps relative to the largest element."""
     prec = MODES[mode][0]

@@ -1,5 +1,5 @@
 """GPU: attention and the conv position embedding in the forms the DiT engine launches them (f5k_attention_ex / f5k_convpos_ex make
-the launch_* calls of engine_impl.h's attention_block / embed_input): 2B batch rows on a length table of B entries, q_lens, packed
+the launch_* calls of engine_impl.h's attend / embed_input): 2B batch rows on a length table of B entries, q_lens, packed
 output rows (RowPack), the f16x3 output forms (pre-split f32 rows, the f16 kernel's Of, hi_only), the 4-stage conv weight ring.
 
 Reference: launch_oracle -- every batch row alone in float64 on the operands as its path rounds them (tests/test_launch_forms.py
