@@ -10,6 +10,7 @@
  *   f5_sample        <- CFM.sample's ODE solve                       model/cfm.py:151-223 (odeint call :218)
  *   f5_sample_ode    <- the same with odeint_kwargs=dict(method="euler" | "midpoint")  model/cfm.py:42,218
  *   f5_dit_forward   <- DiT.forward / UNetT.forward                  model/backbones/dit.py:278-329, unett.py:217-280
+ *   f5_flow_loss     <- CFM.forward (inference mode)                  model/cfm.py:231-302
  *   f5_text_embed    <- TextEmbedding.forward (+ per-sample loop)    model/backbones/dit.py:86-115,244-258
  *   f5_vocos_decode  <- vocoder.decode(mel)                          infer/utils_infer.py:702-703 (third-party vocos)
  *   f5_vocos_decode_ragged <- the per-item vocoder loop of a batch   eval/eval_infer_batch.py:202-212
@@ -128,6 +129,24 @@ int f5_text_embed(f5_engine* e, const int64_t* text, int32_t B, int32_t nt, cons
 int f5_dit_forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int32_t nt,
                    const float* time_host, const int32_t* lens_host, int32_t B, int32_t N, int32_t cfg_infer,
                    int32_t drop_audio_cond, int32_t drop_text, float* out, f5_stream stream);
+
+/* The teacher-forced flow-matching loss of CFM.forward (cfm.py:261-302) around ONE backbone evaluation, in inference mode (no gradient):
+ *   phi = (1 - time[b]) * x0 + time[b] * x1;  cond = x1 with the frames of span[b] zeroed;  pred = backbone(phi, cond, text, time, drops);
+ *   sq_sum[b] = sum over the frames of span[b] and over mel of (pred - (x1 - x0))^2, accumulated in f64.
+ *   x1 (the mel), x0 (the noise) f32[B, N, mel] and text i64[B, nt] on the device; time HOST f32[B]; lens HOST int32[B] or NULL (= the
+ *   reference's lens=None: every item has N frames), each in (0, N]; span HOST int32[B][2] = (start, end) in frames with
+ *   0 <= start <= end <= lens[b] -- the one interval that the reference's rand_span_mask & mask is; drop_audio_cond, drop_text: cfm.py:286-291.
+ *   sq_sum f64[B] and count int32[B] (= end - start) on the device; pred, cond f32[B, N, mel] and frame_err f32[B, N] on the device, each
+ *   NULL or written: frame_err[b, n] = the frame's mean over mel of the squared error inside the span, +0.0 outside it.
+ * The reference's loss is sum(sq_sum) / (sum(count) * mel), which the caller forms where it wants it: nothing is read back and the host
+ * is not synchronised.  A frame outside span[b] is never read for the loss.  Frames at or past lens[b] get phi and cond as any other
+ * frame (cfm.py:279-283) and the backbone treats them as f5_dit_forward does.  Every backbone f5_dit_forward runs is accepted; the
+ * arithmetic of the glue is written out in csrc/flow.h.  Not captured in a graph.
+ * F5_EINVAL with a message naming the item, before the engine is touched: a non-finite time, lens[b] outside (0, N], a span outside
+ * 0 <= start <= end <= lens[b]. */
+int f5_flow_loss(f5_engine* e, const float* x1, const float* x0, const int64_t* text, int32_t nt, const float* time_host,
+                 const int32_t* lens_host, const int32_t* span_host, int32_t B, int32_t N, int32_t drop_audio_cond, int32_t drop_text,
+                 double* sq_sum, int32_t* count, float* pred, float* cond, float* frame_err, f5_stream stream);
 
 /* The ODE solve of CFM.sample (cfm.py:151-223): step_cond = where(cond_mask, cond, 0); `steps` Euler steps over the
  * HOST time grid t[steps + 1] with classifier-free guidance (cfg_strength < 1e-5 -> single conditional forward);
@@ -815,6 +834,14 @@ int f5k_span_stage(float* y, const float* prev_state, int32_t prev_B, int32_t pr
  * are written and the others are not touched.  prev_state and y_new keep their own pitches, prev_N and N. */
 int f5k_span_stage_pitched(float* y, int32_t pitch, const float* prev_state, int32_t prev_B, int32_t prev_N, const float* y_new,
                            const int32_t* rows, const int32_t* rows_host, int32_t B, int32_t N, int32_t mel, f5_stream stream);
+/* The glue of f5_flow_loss (csrc/flow.h).  span int32[B][2] on the device, span_host the same table on the host (checked: 0 <= start <=
+ * end <= N); t f32[B] on the device.  f5k_flow_mix: phi f32[B, N, mel] = (1 - t[b]) * x0 + t[b] * x1, cond (or NULL) = x1 with the span's
+ * frames +0.0.  f5k_flow_loss_reduce: sq_sum f64[B], count int32[B], frame_err f32[B, N] or NULL from pred, x0, x1 f32[B, N, mel];
+ * part: scratch of B * ceil(N / 64) doubles. */
+int f5k_flow_mix(const float* x0, const float* x1, const float* t, const int32_t* span, const int32_t* span_host, float* phi, float* cond,
+                 int32_t B, int32_t N, int32_t mel, f5_stream stream);
+int f5k_flow_loss_reduce(const float* pred, const float* x0, const float* x1, const int32_t* span, const int32_t* span_host, double* part,
+                         double* sq_sum, int32_t* count, float* frame_err, int32_t B, int32_t N, int32_t mel, f5_stream stream);
 /* dst f32[rows, width] = src[idx[r % nidx], :]; idx int[nidx] (device), width % 4 == 0.  The caller keeps idx inside src. */
 int f5k_mod_gather(const float* src, const int32_t* idx, float* dst, int32_t rows, int32_t nidx, int32_t width, f5_stream stream);
 /* The time rows of an f5_sample_items call (host arithmetic, no device needed): the evaluation times of every live item -- Euler t[b][i];

@@ -92,6 +92,7 @@ SIGNATURES = {
     "f5_finalize": (_i, [_p, _p]),
     "f5_text_embed": (_i, [_p, _p, _i, _i, C.POINTER(_i), _i, _i, _p, _p]),
     "f5_dit_forward": (_i, [_p, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), _i, _i, _i, _i, _i, _p, _p]),
+    "f5_flow_loss": (_i, [_p, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "f5_sample": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p]),
     "f5_sample_ode": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), _i, _f, C.POINTER(_i), _i, _i, _p, _p, _p, _i]),
     "f5_sample_items": (_i, [_p, _p, _i, _p, _p, _p, _i, C.POINTER(_f), C.POINTER(_i), _i, C.POINTER(_f), C.POINTER(_i), _i, _i, _p, _p,
@@ -171,6 +172,8 @@ SIGNATURES = {
     "f5k_midpoint_half_cfg_items": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
     "f5k_euler_cfg_items_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "f5k_midpoint_half_cfg_items_packed": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "f5k_flow_mix": (_i, [_p, _p, _p, _p, C.POINTER(_i), _p, _p, _i, _i, _i, _p]),
+    "f5k_flow_loss_reduce": (_i, [_p, _p, _p, _p, C.POINTER(_i), _p, _p, _p, _p, _i, _i, _i, _p]),
     "f5k_mod_gather": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "f5k_span_stage": (_i, [_p, _p, _i, _i, _p, _p, C.POINTER(_i), _i, _i, _i, _p]),
     "f5k_span_stage_pitched": (_i, [_p, _i, _p, _i, _i, _p, _p, C.POINTER(_i), _i, _i, _i, _p]),

@@ -1,9 +1,10 @@
-"""Drop-in for the reference's `CFM` inference surface (model/cfm.py:34-229): same constructor keywords, same
-`sample()` signature and return value, same attributes read by callers (`.transformer`, `.mel_spec`,
+"""Drop-in for the reference's `CFM` (model/cfm.py:34-302) in inference mode: same constructor keywords, same
+`sample()` and `forward()` signatures and return values, same attributes read by callers (`.transformer`, `.mel_spec`,
 `.vocab_char_map`, `.device`, `.dim`, `.num_channels`).  Argument handling (cfm.py:103-158, 196-216, 219-229) is
 host-side Python; the ODE solve itself (cfm.py:160-191, 218) is ONE call into the HIP engine (f5_sample_ode), with
 odeint_kwargs["method"] "euler" or "midpoint" (torchdiffeq's fixed-grid solvers; midpoint makes 2 evaluations per step).
-Training (`forward`, cfm.py:231-302) is out of scope.
+`forward` (cfm.py:231-302) is the teacher-forced flow-matching loss, one call into the engine too (f5_flow_loss), under no_grad:
+a held-out loss for model selection.  Training -- gradients, an optimizer, a trainer -- is out of scope.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn.utils.rnn import pad_sequence
 
-from .utils import default, exists, get_epss_timesteps, lens_to_mask, list_str_to_idx, list_str_to_tensor
+from .utils import default, exists, get_epss_timesteps, lens_to_mask, list_str_to_idx, list_str_to_tensor, span_from_frac_lengths
 
 
 def clamp_durations(text: torch.Tensor, lens: torch.Tensor, duration, max_duration=65536) -> torch.Tensor:
@@ -120,8 +121,67 @@ class CFM(nn.Module):
     def device(self):
         return self.transformer.device
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training (cfm.py:231-302) is outside the inference hot path")
+    def _flow_inputs(self, inp, text, lens):
+        """The argument handling forward() and flow_loss() share (cfm.py:239-258): (mel as given or computed, text long [B, nt] on
+        the host, lens long [B] on the host)."""
+        self.eval()
+        if inp.ndim == 2:  # raw wave -> mel (cfm.py:240-243)
+            inp = self.mel_spec(inp.to(self.device))
+            inp = inp.permute(0, 2, 1)
+            assert inp.shape[-1] == self.num_channels
+        batch, seq_len = inp.shape[:2]
+        if isinstance(text, list):
+            text = list_str_to_idx(text, self.vocab_char_map) if exists(self.vocab_char_map) else list_str_to_tensor(text)
+            assert text.shape[0] == batch
+        if not exists(lens):
+            lens = torch.full((batch,), seq_len, dtype=torch.long)
+        return inp, text.to("cpu", torch.long), torch.as_tensor(lens).to("cpu", torch.long)
+
+    @staticmethod
+    def _loss_of(sq_sum, count, mel: int):
+        """cfm.py:299-302 from the engine's per-item sums: the mean over the selected elements of the whole batch, f32; NaN when
+        nothing is selected, as the reference's mean over nothing is.  Device ops only."""
+        return (sq_sum.sum() / (count.sum().to(torch.float64) * mel)).to(torch.float32)
+
+    @torch.no_grad()
+    def forward(self, inp, text, *, lens=None, noise_scheduler: str | None = None):
+        """The reference's CFM.forward (cfm.py:231-302) in inference mode: one teacher-forced backbone evaluation at a random time
+        with a random span of the conditioning zeroed, and the mean squared error against the flow x1 - x0 over that span.
+        Returns (loss, cond, pred) as the reference does; no gradient is recorded.  The draws are made where `noise_device` says,
+        in the reference's order (frac_lengths.uniform_, rand_like, randn_like, rand, random() twice): with noise_device="cpu" the
+        same torch.manual_seed / random.seed give the reference's CPU draws.  One engine call (f5_flow_loss)."""
+        from random import random
+        inp, text_cpu, lens = self._flow_inputs(inp, text, lens)
+        batch, seq_len = inp.shape[:2]
+        nd = self._noise_device
+        lens_d = lens.to(nd)
+        frac_lengths = torch.zeros((batch,), device=nd).float().uniform_(*self.frac_lengths_mask)
+        start, end = span_from_frac_lengths(lens_d, frac_lengths)
+        end = torch.minimum(end, lens_d)   # rand_span_mask &= mask (cfm.py:264-265): one interval inside [0, len)
+        x0 = torch.randn(inp.shape, dtype=torch.float32, device=nd)   # randn_like(x1)
+        time = torch.rand((batch,), dtype=torch.float32, device=nd)
+        drop_audio_cond = random() < self.audio_drop_prob
+        drop_text = False
+        if random() < self.cond_drop_prob:
+            drop_audio_cond = drop_text = True
+        span = list(zip(start.tolist(), end.tolist()))
+        sq_sum, count, pred, cond, _ = self.transformer.engine().flow_loss(
+            inp, x0, text_cpu, time.tolist(), span, lens=lens.tolist(), drop_audio_cond=drop_audio_cond, drop_text=drop_text,
+            want_frame_err=False)
+        return self._loss_of(sq_sum, count, self.num_channels), cond, pred
+
+    @torch.no_grad()
+    def flow_loss(self, mel, text, lens, *, time, span, x0, drop_audio_cond=False, drop_text=False):
+        """forward() with every draw supplied by the caller: time (B floats), span (B (start, end) frame pairs inside [0, lens[b]])
+        and the noise x0 [B, N, mel].  Returns (loss, per_item f32[B] -- NaN where an item's span is empty --, pred, cond,
+        frame_err f32[B, N]: a frame's mean squared error inside the span, 0 outside), all on the device."""
+        mel, text_cpu, lens = self._flow_inputs(mel, text, lens)
+        time = [float(v) for v in (time.tolist() if isinstance(time, torch.Tensor) else time)]
+        span = [(int(s), int(e)) for s, e in (span.tolist() if isinstance(span, torch.Tensor) else span)]
+        sq_sum, count, pred, cond, frame_err = self.transformer.engine().flow_loss(
+            mel, x0, text_cpu, time, span, lens=lens.tolist(), drop_audio_cond=drop_audio_cond, drop_text=drop_text)
+        per_item = (sq_sum / (count.to(torch.float64) * self.num_channels)).to(torch.float32)
+        return self._loss_of(sq_sum, count, self.num_channels), per_item, pred, cond, frame_err
 
     def load_state_dict(self, sd, strict=True, assign=False):
         """Accepts the reference's CFM state dict (`transformer.*` keys, optional `mel_spec.*` buffers): the backbone

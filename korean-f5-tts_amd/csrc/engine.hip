@@ -398,6 +398,31 @@ extern "C" int f5_dit_forward(f5_engine* e, const float* x, const float* cond, c
     hipStream_t s = (hipStream_t)stream;
     return F5_OPS(e, forward(e, x, cond, text, nt, time_host, lens_host, B, N, cfg_infer, drop_audio_cond, drop_text, out, s));
 }
+int check_flow_spans(const char* who, const int32_t* span_host, const int32_t* lens_host, int B, int N) {
+    if (!span_host || B <= 0 || N <= 0) return fail(F5_EINVAL, "%s: bad arguments", who);
+    for (int b = 0; b < B; ++b) {
+        const int len = lens_host ? lens_host[b] : N, s0 = span_host[2 * b], s1 = span_host[2 * b + 1];
+        if (len <= 0 || len > N) return fail(F5_EINVAL, "%s: lens[%d]=%d out of (0, N]", who, b, len);
+        if (s0 < 0 || s0 > s1 || s1 > len)
+            return fail(F5_EINVAL, "%s: item %d: span = [%d, %d) outside 0 <= start <= end <= %d frames", who, b, s0, s1, len);
+    }
+    return F5_OK;
+}
+// First what needs no engine (the tables: times, lengths, spans; messages name the item), then the engine, then pointers.
+extern "C" int f5_flow_loss(f5_engine* e, const float* x1, const float* x0, const int64_t* text, int32_t nt, const float* time_host,
+                            const int32_t* lens_host, const int32_t* span_host, int32_t B, int32_t N, int32_t drop_audio_cond,
+                            int32_t drop_text, double* sq_sum, int32_t* count, float* pred, float* cond, float* frame_err, f5_stream stream) {
+    if (!time_host || B <= 0 || B > 65535 || N <= 0) return fail(F5_EINVAL, "f5_flow_loss: bad arguments (0 < B <= 65535, N > 0)");
+    for (int b = 0; b < B; ++b)
+        if (!std::isfinite(time_host[b])) return fail(F5_EINVAL, "f5_flow_loss: item %d: time is not finite", b);
+    CHK(check_flow_spans("f5_flow_loss", span_host, lens_host, B, N));
+    CHK(check_ready("f5_flow_loss", e, B, N));
+    if (!x1 || !x0 || !text || !sq_sum || !count || nt <= 0) return fail(F5_EINVAL, "f5_flow_loss: bad arguments");
+    CHK(check_mmdit_text("f5_flow_loss", e, nt));
+    hipStream_t s = (hipStream_t)stream;
+    return F5_OPS(e, flow_loss(e, x1, x0, text, nt, time_host, lens_host, span_host, B, N, drop_audio_cond, drop_text, sq_sum, count, pred,
+                               cond, frame_err, s));
+}
 // the rules of a slice's row table (f5_sample_span, f5k_span_stage); messages name the item
 int check_span_rows(const char* who, const int32_t* rows_host, int B, const void* prev_state, int prev_B, int prev_N, const void* y_new) {
     if (!rows_host || B <= 0) return fail(F5_EINVAL, "%s: bad arguments", who);

@@ -1053,15 +1053,12 @@ int EngineOps<T>::text_embed(f5_engine* e, const int64_t* text, int B, int nt, c
     const bool per_sample = lens_host && e->cfg.backbone == F5_BACKBONE_DIT;  // unett.py embeds at the padded length
     return run_text_embed<T>(e, w, text, B, nt, per_sample ? w.lens_plain : nullptr, N, drop_text, out, s);
 }
+// One backbone evaluation on a carved arena (f5_dit_forward, f5_flow_loss): the call's tables go up, the time path and the text
+// encoder run, the prediction is left in w.pred [Bp, N, mel].
 template <typename T>
-int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
-                          const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
-                          hipStream_t s) {
+static int forward_into_pred(f5_engine* e, Work<T>& w, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
+                             const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, hipStream_t s) {
     const int Bp = cfg_infer ? 2 * B : B;
-    if (e->cfg.backbone == F5_BACKBONE_MMDIT) reserve_text(e, nt);
-    CHK(ensure_arena(e, B, N, Bp));
-    Work<T> w;
-    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
     std::vector<float> tt(Bp);
     for (int i = 0; i < Bp; ++i) tt[i] = time_host[i % B];
     CHK(upload_small<T>(e, w, plan_sample(e, B, N, lens_host, PlanOptions::whole_batch(B)), tt.data(), Bp, lens_host, nullptr, s));
@@ -1074,8 +1071,44 @@ int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const
     CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, cfg_infer ? 0 : drop_text, w.text_c, s));
     if (cfg_infer) CHK(run_text_embed<T>(e, w, text, B, nt, tlens, N, 1, w.text_u, s));
     else a.drop_cond_first = drop_audio_cond, a.text_second = w.text_c;
-    CHK(run_backbone<T>(e, w, a, s));
+    return run_backbone<T>(e, w, a, s);
+}
+template <typename T>
+int EngineOps<T>::forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
+                          const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
+                          hipStream_t s) {
+    const int Bp = cfg_infer ? 2 * B : B;
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) reserve_text(e, nt);
+    CHK(ensure_arena(e, B, N, Bp));
+    Work<T> w;
+    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
+    CHK(forward_into_pred<T>(e, w, x, cond, text, nt, time_host, lens_host, B, N, cfg_infer, drop_audio_cond, drop_text, s));
     HIPCHK(hipMemcpyAsync(out, w.pred, (size_t)Bp * N * e->cfg.mel_dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return F5_OK;
+}
+// f5_flow_loss: the glue of csrc/flow.h around forward_into_pred.  Buffers the forward's rectangular body leaves alone carry the glue:
+// w.y the mixed input phi, w.step_cond the masked conditioning (the caller's `cond` where one is given), w.rowmap the span table
+// (int2[B]: a forward has no packed rows), w.y_mid the loss kernel's f64 block sums; the times are the forward's own table in w.tdev.
+template <typename T>
+int EngineOps<T>::flow_loss(f5_engine* e, const float* x1, const float* x0, const int64_t* text, int nt, const float* time_host,
+                            const int32_t* lens_host, const int32_t* span_host, int B, int N, int drop_audio_cond, int drop_text, double* sq_sum,
+                            int32_t* count, float* pred, float* cond, float* frame_err, hipStream_t s) {
+    const int mel = e->cfg.mel_dim;
+    if (e->cfg.backbone == F5_BACKBONE_MMDIT) reserve_text(e, nt);
+    CHK(ensure_arena(e, B, N, B));
+    Work<T> w;
+    carve<T>(e, w, e->res_B, e->res_N, e->res_S);
+    static_assert(sizeof(int2) == 2 * sizeof(int32_t), "a span is one int2");
+    CHK(e->stage.upload(w.rowmap, (size_t)B * sizeof(int2), s, [&](char* hb) { memcpy(hb, span_host, (size_t)B * sizeof(int2)); }));
+    // (the times are needed before the forward uploads them: the same values, to the same place)
+    CHK(e->stage.upload(w.tdev, (size_t)B * sizeof(float), s, [&](char* hb) { memcpy(hb, time_host, (size_t)B * sizeof(float)); }));
+    float* cond_buf = cond ? cond : w.step_cond;
+    launch_flow_mix(s, x0, x1, w.tdev, w.rowmap, w.y, cond_buf, B, N, mel);
+    KCHK();
+    CHK(forward_into_pred<T>(e, w, w.y, cond_buf, text, nt, time_host, lens_host, B, N, 0, drop_audio_cond, drop_text, s));
+    launch_flow_loss(s, w.pred, x0, x1, w.rowmap, reinterpret_cast<double*>(w.y_mid), sq_sum, count, frame_err, B, N, mel);
+    KCHK();
+    if (pred) HIPCHK(hipMemcpyAsync(pred, w.pred, (size_t)B * N * mel * sizeof(float), hipMemcpyDeviceToDevice, s));
     return F5_OK;
 }
 // the second (unconditional) half of every [2B ...] activation buffer a DiT forward writes, as a Work of its own: behind the B * N rows

@@ -21,6 +21,7 @@
 #include "attn2.h"
 #include "convpos.h"
 #include "elementwise.h"
+#include "flow.h"
 #include "gemm_dispatch.h"
 #include "mmdit.h"
 
@@ -478,6 +479,9 @@ template <typename T> struct EngineOps {
     static int forward(f5_engine* e, const float* x, const float* cond, const int64_t* text, int nt, const float* time_host,
                        const int32_t* lens_host, int B, int N, int cfg_infer, int drop_audio_cond, int drop_text, float* out,
                        hipStream_t s);
+    static int flow_loss(f5_engine* e, const float* x1, const float* x0, const int64_t* text, int nt, const float* time_host,
+                         const int32_t* lens_host, const int32_t* span_host, int B, int N, int drop_audio_cond, int drop_text, double* sq_sum,
+                         int32_t* count, float* pred, float* cond, float* frame_err, hipStream_t s);
     static int run_sample(f5_engine* e, const SampleCall& c);
     static int prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max, int steps, float cfg_strength, int method, bool want_traj);
 };

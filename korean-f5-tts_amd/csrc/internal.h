@@ -17,6 +17,8 @@ int f5_fail(int code, const char* fmt, ...);  // records the thread-local messag
 // The rules of a slice's row table (engine.hip; f5_sample_span and f5k_span_stage): rows_host[b] in [-1, prev_B), no previous row named
 // twice, a previous state where a row continues, y_new where one begins.
 int check_span_rows(const char* who, const int32_t* rows_host, int B, const void* prev_state, int prev_B, int prev_N, const void* y_new);
+// the rules of a flow-loss span table (f5_flow_loss, f5k_flow_mix, f5k_flow_loss_reduce): 0 <= start <= end <= lens[b] (N where lens is null)
+int check_flow_spans(const char* who, const int32_t* span_host, const int32_t* lens_host, int B, int N);
 
 #define HIPCHK(expr)                                                                                         \
     do {                                                                                                     \

@@ -571,6 +571,24 @@ extern "C" int f5k_span_stage_pitched(float* y, int32_t pitch, const float* prev
     launch_span_stage((hipStream_t)stream, y, prev_state, y_new, rows, B, N, prev_N, mel, pitch);
     return glue_done((hipStream_t)stream);
 }
+// the glue of f5_flow_loss (flow.h); lens null: a span may reach N
+extern "C" int f5k_flow_mix(const float* x0, const float* x1, const float* t, const int32_t* span, const int32_t* span_host, float* phi,
+                            float* cond, int32_t B, int32_t N, int32_t mel, f5_stream stream) {
+    if (!x0 || !x1 || !t || !span || !phi || B <= 0 || N <= 0 || mel <= 0 || mel % 4)
+        return fail(F5_EINVAL, "f5k_flow_mix: bad arguments (mel %% 4 == 0)");
+    CHK(check_flow_spans("f5k_flow_mix", span_host, nullptr, B, N));
+    launch_flow_mix((hipStream_t)stream, x0, x1, t, reinterpret_cast<const int2*>(span), phi, cond, B, N, mel);
+    return glue_done((hipStream_t)stream);
+}
+extern "C" int f5k_flow_loss_reduce(const float* pred, const float* x0, const float* x1, const int32_t* span, const int32_t* span_host,
+                                    double* part, double* sq_sum, int32_t* count, float* frame_err, int32_t B, int32_t N, int32_t mel,
+                                    f5_stream stream) {
+    if (!pred || !x0 || !x1 || !span || !part || !sq_sum || !count || B <= 0 || B > 65535 || N <= 0 || mel <= 0 || mel % 4)
+        return fail(F5_EINVAL, "f5k_flow_loss_reduce: bad arguments (mel %% 4 == 0, B <= 65535)");
+    CHK(check_flow_spans("f5k_flow_loss_reduce", span_host, nullptr, B, N));
+    launch_flow_loss((hipStream_t)stream, pred, x0, x1, reinterpret_cast<const int2*>(span), part, sq_sum, count, frame_err, B, N, mel);
+    return glue_done((hipStream_t)stream);
+}
 extern "C" int f5k_select_rows(const float* a, const float* b, const uint8_t* rowmask, float* out, int64_t rows, int32_t C, f5_stream stream) {
     if (!a || !rowmask || !out || rows <= 0 || C <= 0 || C % 4) return fail(F5_EINVAL, "f5k_select_rows: bad arguments (C %% 4 == 0)");
     launch_select_rows((hipStream_t)stream, a, b, rowmask, out, (long)rows, C);

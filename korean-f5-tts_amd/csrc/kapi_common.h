@@ -5,6 +5,7 @@
 #include "attn2.h"
 #include "convpos.h"
 #include "elementwise.h"
+#include "flow.h"
 #include "gemm_dispatch.h"
 #include "internal.h"
 

@@ -214,6 +214,31 @@ class Engine:
                                                _stream_ptr(self.device)), "f5_dit_forward")
         return out
 
+    def flow_loss(self, x1, x0, text, time, span, lens=None, drop_audio_cond=False, drop_text=False, want_pred=True, want_cond=True,
+                  want_frame_err=True):
+        """CFM.forward's flow-matching loss around one backbone evaluation (f5_flow_loss): x1 (the mel) and x0 (the noise)
+        f32[B, N, mel], text i64[B, nt], time a list of B floats, span a list of B (start, end) frame pairs inside [0, lens[b]].
+        Returns (sq_sum f64[B], count i32[B], pred, cond, frame_err), all on the device, the last three None where not wanted.
+        Nothing is read back and the host does not wait."""
+        B, N, _ = x1.shape
+        x1 = _h2d_async(x1, self.device, torch.float32)
+        x0 = _h2d_async(x0, self.device, torch.float32)
+        text = _h2d_async(text, self.device, torch.long)
+        flat = [int(v) for se in span for v in se]
+        if len(flat) != 2 * B or len(time) != B:
+            raise ValueError(f"flow_loss: {len(time)} times and {len(flat) // 2} spans for a batch of {B}")
+        sq_sum = torch.empty(B, device=self.device, dtype=torch.float64)
+        count = torch.empty(B, device=self.device, dtype=torch.int32)
+        pred = torch.empty(B, N, self.mel_dim, device=self.device, dtype=torch.float32) if want_pred else None
+        cond = torch.empty(B, N, self.mel_dim, device=self.device, dtype=torch.float32) if want_cond else None
+        frame_err = torch.empty(B, N, device=self.device, dtype=torch.float32) if want_frame_err else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.f5_flow_loss(self._h, _ptr(x1), _ptr(x0), _ptr(text), text.shape[1], _lib.float_array(time),
+                                             _lib.int_array(lens), _lib.int_array(flat), B, N, int(drop_audio_cond), int(drop_text),
+                                             _ptr(sq_sum), _ptr(count), _ptr(pred), _ptr(cond), _ptr(frame_err),
+                                             _stream_ptr(self.device)), "f5_flow_loss")
+        return sq_sum, count, pred, cond, frame_err
+
     def mmdit_taps(self, buf: torch.Tensor | None):
         """Diagnostic (tests): later forward() calls of an MMDiT engine copy their intermediates into `buf` (f5k_mmdit_taps); None: off."""
         _lib.check(self.lib.f5k_mmdit_taps(self._h, _ptr(buf)), "f5k_mmdit_taps")

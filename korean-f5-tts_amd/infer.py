@@ -963,6 +963,90 @@ def synthesize_script(model, vocoder, voices, script, *, speed=speed, target_rms
         return wave, target_sample_rate, torch.cat(specs, dim=1), segments
 
 
+def heldout_draws(lens, mel_dim: int, *, seed=0, frac_lengths=(0.7, 1.0)):
+    """The draws of heldout_loss: for utterance u of lens[u] frames, from a CPU generator seeded by (seed, u) alone, the masked span
+    (start, end) -- CFM.forward's span arithmetic (utils.py:69-75) with its two uniform draws -- and then the noise x0 [lens[u], mel].
+    They depend on nothing else: not on the batch an utterance lands in, not on the adapter.  Returns (spans, noises)."""
+    spans, noises = [], []
+    for u, n in enumerate(lens):
+        g = torch.Generator().manual_seed((int(seed) << 32) + u)
+        frac = torch.empty(1).uniform_(*frac_lengths, generator=g)
+        length = (frac * int(n)).long()
+        start = ((int(n) - length) * torch.rand(1, generator=g)).long().clamp(min=0)
+        spans.append((int(start), min(int(start + length), int(n))))
+        noises.append(torch.randn(int(n), mel_dim, generator=g))
+    return spans, noises
+
+
+def heldout_rows(lens, times: int, batch_frames: int) -> list[list[tuple[int, int]]]:
+    """The batches of heldout_loss: every (utterance, time index) pair is a row of its utterance's length, and the rows are
+    grouped by batching.bucket_prompts' frame budget (no duration window, no shuffle)."""
+    from .batching import bucket_prompts
+    rows = [(u, k) for u in range(len(lens)) for k in range(times)]
+    row_lens = [int(lens[u]) for u, _ in rows]
+    max_secs = max(40, max(row_lens) * HOP_LENGTH // SAMPLE_RATE + 1)
+    groups = bucket_prompts(row_lens, infer_batch_size=int(batch_frames), min_secs=0, max_secs=max_secs, shuffle_seed=None)
+    return [[rows[i] for i in g] for g in groups]
+
+
+def heldout_loss(model, mels, texts, *, adapters=(None,), times=8, seed=0, frac_lengths=(0.7, 1.0), batch_frames=38400):
+    """The held-out flow-matching loss of CFM.forward (cfm.py:231-302, no drops) for every adapter in `adapters` (names of resident
+    adapters, None: the base) on ONE resident engine: a model-selection number that needs nothing but the model.
+    mels: a list of U mels [n_u, mel].  texts: a list of U texts -- strings (tokenised as CFM.sample tokenises list[str]) or token-id
+    sequences -- or a mapping adapter name -> such a list (fine-tunes tokenise differently).  Every utterance is evaluated at the
+    stratified times (k + 0.5) / times with ONE span and ONE noise (heldout_draws: the same for every time, batch and adapter).
+    Returns {adapter: {"loss": float, "per_item": [U], "per_time": [times]}}: the mean squared flow error over the masked elements
+    of all rows, per utterance, and per time.  The adapter that was active before the call is active again after it, on an
+    exception too.  The only readback is one copy at the end."""
+    tr = model.transformer
+    mel_dim, U = model.num_channels, len(mels)
+    adapters = list(adapters)
+    per_adapter = texts if isinstance(texts, dict) else {a: texts for a in adapters}
+    for a in adapters:
+        if a not in per_adapter or len(per_adapter[a]) != U:
+            raise ValueError(f"heldout_loss: adapter {a!r} needs one text per utterance ({U})")
+
+    def tokens(t):
+        if isinstance(t, str):
+            return (list_str_to_idx([t], model.vocab_char_map) if model.vocab_char_map is not None else list_str_to_tensor([t]))[0]
+        return torch.as_tensor(t, dtype=torch.long)
+
+    toks = {a: [tokens(t) for t in per_adapter[a]] for a in adapters}
+    lens = [int(m.shape[0]) for m in mels]
+    spans, noises = heldout_draws(lens, mel_dim, seed=seed, frac_lengths=frac_lengths)
+    batches = heldout_rows(lens, times, batch_frames)
+    pad = torch.nn.utils.rnn.pad_sequence
+    sums = {a: [] for a in adapters}
+    before = tr.active_adapter
+    try:
+        eng = tr.engine()
+        for rows in batches:
+            us = [u for u, _ in rows]
+            x1 = pad([mels[u].to("cpu", torch.float32) for u in us], batch_first=True)
+            x0 = pad([noises[u] for u in us], batch_first=True)
+            x1, x0 = x1.to(model.device), x0.to(model.device)   # once per batch: every adapter reads the same device tensors
+            t = [(k + 0.5) / times for _, k in rows]
+            for a in adapters:
+                tr.set_adapter(a)
+                text = pad([toks[a][u] for u in us], padding_value=-1, batch_first=True)
+                sq, cnt, _, _, _ = eng.flow_loss(x1, x0, text, t, [spans[u] for u in us], lens=[lens[u] for u in us],
+                                                 want_pred=False, want_cond=False, want_frame_err=False)
+                sums[a].append(sq)
+    finally:
+        tr.set_adapter(before)
+    order = [r for rows in batches for r in rows]
+    host = torch.stack([torch.cat(sums[a]) for a in adapters]).cpu().double()   # [adapters, rows]: the one readback
+    count = torch.tensor([spans[u][1] - spans[u][0] for u in range(U)], dtype=torch.float64) * mel_dim
+    out = {}
+    for i, a in enumerate(adapters):
+        sq = torch.zeros(U, times, dtype=torch.float64)
+        for (u, k), v in zip(order, host[i].tolist()):
+            sq[u, k] = v
+        out[a] = dict(loss=float(sq.sum() / (count.sum() * times)), per_item=(sq.sum(1) / (count * times)).tolist(),
+                      per_time=(sq.sum(0) / count.sum()).tolist())
+    return out
+
+
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,

@@ -21,6 +21,29 @@ def lens_to_mask(t: torch.Tensor, length: int | None = None) -> torch.Tensor:
     return seq[None, :] < t[:, None]
 
 
+def mask_from_start_end_indices(seq_len: torch.Tensor, start: torch.Tensor, end: torch.Tensor) -> torch.Tensor:
+    """bool [B, max(seq_len)]: frame n of item b is inside [start[b], end[b])   (utils.py:61-66)."""
+    seq = torch.arange(int(seq_len.max()), device=start.device).long()
+    return (seq[None, :] >= start[:, None]) & (seq[None, :] < end[:, None])
+
+
+def span_from_frac_lengths(seq_len: torch.Tensor, frac_lengths: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The random training span of utils.py:69-75 as (start, end), long [B]: lengths = (frac * seq_len).long(), start =
+    (max_start * rand_like(frac)).long().clamp(min=0), end = start + lengths.  Draws `rand_like` where frac_lengths lives, as
+    the reference does.  end <= seq_len, so the reference's `rand_span_mask & mask` is this one interval."""
+    lengths = (frac_lengths * seq_len).long()
+    max_start = seq_len - lengths
+    rand = torch.rand_like(frac_lengths)
+    start = (max_start * rand).long().clamp(min=0)
+    return start, start + lengths
+
+
+def mask_from_frac_lengths(seq_len: torch.Tensor, frac_lengths: torch.Tensor) -> torch.Tensor:
+    """utils.py:69-77."""
+    start, end = span_from_frac_lengths(seq_len, frac_lengths)
+    return mask_from_start_end_indices(seq_len, start, end)
+
+
 def list_str_to_tensor(text: list[str], padding_value=-1) -> torch.Tensor:
     tensors = [torch.tensor([*bytes(t, "UTF-8")]) for t in text]
     return pad_sequence(tensors, padding_value=padding_value, batch_first=True)
