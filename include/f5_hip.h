@@ -56,6 +56,32 @@ extern "C" {
                             entering and of the flow prediction leaving the backbone is what dominates F5_PREC_F16's error (DESIGN.md
                             section 3, tools/x3_ablate.py); meets the 1e-3 parity bar at ~F5_PREC_F16 speed */
 
+#define F5_PREC_F8 5     /* F5_PREC_F16P with the operands of the four GEMMs of every DiT block -- QKV, attention out-projection, FF1, FF2 --
+                            in OCP e4m3 (e4m3fn, never fnuz) on gfx950's block-scaled MFMA (v_mfma_scale_f32_16x16x128_f8f6f4: twice the
+                            fp16 rate per clock, half the operand bytes).  Everything else as F5_PREC_F16P: fp16 attention, split-fp16
+                            input embedding and output projection, f32 residual stream / norms / ODE state, time path, text path and
+                            conv position embedding untouched.  DiT backbone only, not with F5_OPT_ADAPTERS; heads even and
+                            ff_dim % 128 == 0 (every K a whole number of 128-element tiles).
+                            The f8 arithmetic contract (csrc/e4m3.h, quant8.h, gemm8.h):
+                              Scales   powers of two, one e8m0 byte b (value 2^(b - 127)) per ROW of an A operand and per OUTPUT
+                                       CHANNEL of a weight: the smallest power of two s with amax / s <= 448, amax over the row's K real
+                                       elements (pad columns do not count); amax == 0 gives b = 127.  Dynamic and per row, so a row's
+                                       result depends on that row alone: isolated rows, packed == padded, bucketed graph == exact and
+                                       replay == eager hold under f8 as under every other precision.
+                              Codes    code = e4m3(x / s), round to nearest even, saturating at +-448; x / s is exact, so the code is a
+                                       pure function of x.  NaN / Inf inputs are outside the contract.
+                              Product  C[m][n] = 2^(ba[m] + bw[n] - 254) * sum_k codeA[m][k] codeW[n][k], accumulated in f32 by the MFMA.
+                                       The instruction's own scale operands are fed 2^0; the two powers of two are MULTIPLIED ONTO THE
+                                       ACCUMULATORS before the epilogue (exact), which then runs unchanged (EpiQKV, EpiStore + GELU-tanh,
+                                       EpiGateRes / EpiGateResRows).
+                              Rounding points
+                                       xn (QKV / FF1 operand): quantised from the f32 value LN(x)(1 + scale) + shift inside the LayerNorm
+                                       kernel, with no fp16 step between.
+                                       ao (attention output) and ffh (FF hidden, after GELU): ROUNDED TO FP16 FIRST -- the attention kernel
+                                       and FF1's epilogue write today's fp16 buffers -- and quantised from those by the stand-alone
+                                       row quantiser.
+                                       Weights: from the f32 master at f5_finalize; K padding is zero codes; no fp16 copy is kept. */
+
 #define F5_OPT_QK_RMSNORM 1        /* qk_norm="rms_norm" (modules.py:397-404,481-484): weights ...attn.q_norm.weight / k_norm.weight [64] */
 #define F5_OPT_LONG_SKIP 2         /* long_skip_connection=True (dit.py:205,313-324): long_skip_connection.weight [D, 2D] */
 #define F5_OPT_TEXT_AVG_UPSAMPLE 4 /* text_embedding_average_upsampling=True (dit.py:54-84; needs text_mask_padding) */
@@ -691,7 +717,8 @@ int f5_wave_gather(const float* base, int32_t B, const int64_t* start_host, cons
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */
 int f5k_gemm(int32_t prec, const float* A, const float* W, const float* bias, int32_t act, float* out, int32_t M,
              int32_t N, int32_t K, int32_t tile_m, int32_t tile_n, f5_stream stream);
-/* What launch_gemm decides for one problem, as pure host arithmetic (no HIP call, nothing launched): element size 2 or 4, the
+/* What launch_gemm decides for one problem, as pure host arithmetic (no HIP call, nothing launched): element size 1 (e4m3 codes:
+ * plain operands, no conv, K % 128 == 0, tile ids 2, 8, 13 only -- anything else is refused), 2 or 4, the
  * device row count present or not and the row count expected behind it (m_hint, 0: none), the operand form (0 plain, 1 W pre-split,
  * 2 A and W pre-split), implicit conv or not, whether the epilogue admits the ping-pong tile, the forced cfg (-1 auto, -2 the
  * register-staged kernel, else a tile id) and the values of F5_GEMM_CFG (-1: unset) / F5_GEMM_CFG_N (0: every N).
@@ -747,9 +774,23 @@ int f5k_layernorm_mod(const float* x, const float* scale, const float* shift, fl
 int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* scale, const float* shift, void* out, float* out_f32,
                          int32_t R, int32_t D, int32_t rows_per_batch, float eps, int32_t m_limit, int32_t planar,
                          f5_stream stream);
+/* F5_PREC_F8 through f5k_layernorm_mod_ex: out = uint8 [R * D] e4m3 codes followed by R scale bytes (out_f32 NULL, planar 0); it is
+ * f5k_layernorm_q8 below without the packed form. */
+/* The e4m3 output form of the AdaLN LayerNorm (F5_PREC_F8: the A operand of QKV / FF1): codes uint8 [R, D] and one e8m0 scale byte per
+ * row, quantised from the f32 value.  batch_of_row_host (HOST int32[R], or NULL): the packed form, row r takes the scale / shift rows
+ * of batch row batch_of_row_host[r] (rows D apart) instead of r / rows_per_batch.  m_limit >= 0: rows at or past it are not written. */
+int f5k_layernorm_q8(const float* x, const float* scale, const float* shift, uint8_t* codes, uint8_t* scales, int32_t R, int32_t D,
+                     int32_t rows_per_batch, float eps, int32_t m_limit, const int32_t* batch_of_row_host, f5_stream stream);
+/* The stand-alone row quantiser of F5_PREC_F8 on caller-owned DEVICE buffers: x [R, ld] of f32 (prec F5_PREC_F32), bf16 or f16 values,
+ * K real elements per row (K % 4 == 0) -> codes uint8 [R, ldc] (ldc >= K, ldc % 4 == 0; columns past K are not written) and scales
+ * uint8 [R].  m_limit >= 0: device-side row count, rows at or past it are neither read nor written; -1: every row. */
+int f5k_quant_rows_e4m3(int32_t prec, const void* x, int64_t ld, int32_t R, int32_t K, uint8_t* codes, int64_t ldc, uint8_t* scales,
+                        int32_t m_limit, f5_stream stream);
 
 /* One backbone GEMM C = A W^T (A f32 [M, K], W f32 [N, K], bias f32 [N], all cast to the operand type of `prec`) through a
- * production epilogue of csrc/gemm.h, built as the engine builds it.  Outputs go to caller-owned device buffers. */
+ * production epilogue of csrc/gemm.h, built as the engine builds it.  Outputs go to caller-owned device buffers.
+ * F5_PREC_F8: A and W are quantised row by row per the f8 contract (what f5k_quant_rows_e4m3 returns for them; K % 4 == 0) and
+ * multiplied by the e4m3 kernel; cfg -1, 2, 8 or 13; 16-bit outputs (out16 STORE, q / k / v^T) are f16. */
 #define F5K_EPI_STORE 0    /* EpiStore: out0 = act(C + bias) [M, N], f32 or (out16) the 16-bit operand type             */
 #define F5K_EPI_GATE_RES 1 /* EpiGateRes: out0 = x f32 [M, N] = res + gate[b] * (C + bias); rows past lens[b] keep res     */
 #define F5K_EPI_QKV 2      /* EpiQKV: out0 = q, out1 = k [Bp, H, Nseq, 64], out2 = v^T [Bp, H, 64, Npad]                   */
@@ -879,7 +920,9 @@ int f5k_work_plan(const f5_config* c, int32_t B, int32_t N, int32_t S, int32_t c
  * f5_dit_forward of this engine, the audio embedding [Bp, N, D], then per block the text stream c [Bp, nt, D] (not in the last block,
  * which drops it) and the audio stream x [Bp, N, D], back to back; Bp = B, or 2 B with cfg_infer.  sample() never writes them. */
 int f5k_mmdit_taps(f5_engine* e, float* taps);
-/* repeated-launch timing of one GEMM shape (for bench/roofline): returns average microseconds per launch */
+/* repeated-launch timing of one GEMM shape (for bench/roofline): returns average microseconds per launch.  F5_PREC_F8: the e4m3
+ * kernel on random codes into f16 rows (K % 128 == 0; tile_m 0 or -(2 | 8 | 13)); tile_n == 1 adds the stand-alone row quantiser of
+ * an f16 A operand to every timed launch, as the engine runs it in front of the out-projection and FF2. */
 int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tile_m, int32_t tile_n, int32_t iters,
                   float* avg_us, f5_stream stream);
 

@@ -11,9 +11,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libf5hip.so")
 
 F5_OPT_QK_RMSNORM, F5_OPT_LONG_SKIP, F5_OPT_TEXT_AVG_UPSAMPLE, F5_OPT_ADAPTERS = 1, 2, 4, 8
-F5_PREC_F32, F5_PREC_BF16, F5_PREC_F16, F5_PREC_F16X3, F5_PREC_F16P = 0, 1, 2, 3, 4
+F5_PREC_F32, F5_PREC_BF16, F5_PREC_F16, F5_PREC_F16X3, F5_PREC_F16P, F5_PREC_F8 = 0, 1, 2, 3, 4, 5
 PRECISIONS = {"f32": F5_PREC_F32, "fp32": F5_PREC_F32, "bf16": F5_PREC_BF16, "f16": F5_PREC_F16, "fp16": F5_PREC_F16,
-              "f16x3": F5_PREC_F16X3, "f16p": F5_PREC_F16P, "parity": F5_PREC_F16P}
+              "f16x3": F5_PREC_F16X3, "f16p": F5_PREC_F16P, "parity": F5_PREC_F16P, "f8": F5_PREC_F8, "fp8": F5_PREC_F8}
 F5_BACKBONE_DIT, F5_BACKBONE_UNETT, F5_BACKBONE_MMDIT = 0, 1, 2
 BACKBONES = {"DiT": F5_BACKBONE_DIT, "UNetT": F5_BACKBONE_UNETT, "MMDiT": F5_BACKBONE_MMDIT}
 F5_ODE_EULER, F5_ODE_MIDPOINT = 0, 1
@@ -163,6 +163,8 @@ SIGNATURES = {
     "f5k_convpos_ex": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_conv), _p]),
     "f5k_layernorm_mod": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _p]),
     "f5k_layernorm_mod_ex": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _f, _i, _i, _p]),
+    "f5k_layernorm_q8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _i, C.POINTER(_i), _p]),
+    "f5k_quant_rows_e4m3": (_i, [_i, _p, C.c_int64, _i, _i, _p, C.c_int64, _p, _i, _p]),
     "f5k_gemm_epi": (_i, [_i, _p, _p, _p, _i, _i, _i, C.POINTER(f5k_epi), _p]),
     "f5k_pack_input": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "f5k_fill_rowmap": (_i, [_p, _p, _i, _p]),

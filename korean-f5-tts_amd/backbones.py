@@ -36,6 +36,11 @@ class _HipBackbone(nn.Module):
         # the MMDiT: "f16x3" too -- against the reference's vectors at its fixtures' weight scale f16p reaches 1.5e-3
         if precision == "parity":
             precision = "f16p" if self.backbone_name == "DiT" else "f16x3"
+        # "f8" (never the default): "f16p" with e4m3 operands in the four GEMMs of every DiT block (include/f5_hip.h F5_PREC_F8)
+        if precision in ("f8", "fp8"):
+            precision = "f8"
+            if self.backbone_name != "DiT":
+                raise NotImplementedError(f"precision 'f8' is built for the DiT backbone only, not the {self.backbone_name}")
         arch.pop("dropout", None)
         arch.pop("attn_backend", None)          # one attention implementation: the gfx950 flash kernel
         arch.pop("checkpoint_activations", None)
@@ -179,6 +184,9 @@ class _HipBackbone(nn.Module):
         later adds upload to the resident engine, and set_adapter() never rebuilds."""
         if self.backbone_name != "DiT":
             raise NotImplementedError("resident adapters are built for the DiT backbone only")
+        if self.precision == "f8":
+            raise NotImplementedError("resident adapters are not built for precision 'f8': a switch merges into packed 16-bit "
+                                      "operands, and re-quantising e4m3 weights on a switch is a later step")
         if name in self._adapters:
             raise ValueError(f"adapter {name!r} exists: delete_adapter() it first")
         pairs, full = A.split_adapter_tensors(W.strip_prefixes(tensors))

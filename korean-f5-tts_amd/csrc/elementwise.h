@@ -2,6 +2,7 @@
 // All of them stream rows with 16-byte accesses, one wave (64 lanes) per row where a row reduction is needed
 // (wave shuffles only, no LDS), and keep statistics in fp32.
 #pragma once
+#include "e4m3.h"
 #include "f5_common.h"
 
 namespace f5 {
@@ -61,7 +62,8 @@ template <typename TO, bool ROWS>
 __device__ __forceinline__ void layernorm_body(const float* __restrict__ x, int ldx, TO* __restrict__ out, int ldo, int R, int D, float eps,
                                                const float* __restrict__ A, const float* __restrict__ Bv, int vec_stride,
                                                int rows_per_batch, int modulate, const Prefetch& pf, const int* __restrict__ m_limit,
-                                               int planar, int wt, const int2* __restrict__ rowmap) {
+                                               int planar, int wt, const int2* __restrict__ rowmap,
+                                               unsigned char* __restrict__ scales = nullptr) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R || (m_limit && r >= *m_limit)) return;   // (m_limit: rows present in a packed batch, RowPack)
@@ -105,7 +107,26 @@ __device__ __forceinline__ void layernorm_body(const float* __restrict__ x, int 
         }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
-    if (wt) {   // write-through stores: the same expressions, stored by store_row_wt
+    if constexpr (sizeof(TO) == 1) {   // e4m3 codes + one power-of-two scale per row (quant8.h): the same f32 expressions, quantised
+        float4 y[8];
+        float amax = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float4 a = ga[i];
+            const float4 b = gb[i];
+            if (modulate) { a.x += 1.f; a.y += 1.f; a.z += 1.f; a.w += 1.f; }
+            y[i] = make_float4((v[i].x - mean) * rstd * a.x + b.x, (v[i].y - mean) * rstd * a.y + b.y, (v[i].z - mean) * rstd * a.z + b.z,
+                               (v[i].w - mean) * rstd * a.w + b.w);
+            if (lane * 4 + i * 256 < D) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(y[i].x), fabsf(y[i].y))), fmaxf(fabsf(y[i].z), fabsf(y[i].w)));
+        }
+        const unsigned sb = e8m0_for_amax(wave_max(amax));
+        const float inv = e8m0_inverse(sb);
+        unsigned* cr = reinterpret_cast<unsigned*>(out + (size_t)r * ldo);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (lane * 4 + i * 256 < D) cr[lane + i * 64] = e4m3_pack4(y[i].x, y[i].y, y[i].z, y[i].w, inv);
+        if (lane == 0) scales[r] = (unsigned char)sb;
+    } else if (wt) {   // write-through stores: the same expressions, stored by store_row_wt
         float4 y[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {

@@ -23,7 +23,7 @@
 // precision dispatch of one EngineOps<T> member
 #define F5_OPS(e, CALL)                                                  \
     ((e)->cfg.precision == F5_PREC_BF16  ? EngineOps<bf16_t>::CALL       \
-     : ((e)->cfg.precision == F5_PREC_F16 || (e)->cfg.precision == F5_PREC_F16P) ? EngineOps<f16_t>::CALL        \
+     : ((e)->cfg.precision == F5_PREC_F16 || (e)->cfg.precision == F5_PREC_F16P || (e)->cfg.precision == F5_PREC_F8) ? EngineOps<f16_t>::CALL        \
                                          : EngineOps<float>::CALL)
 
 // ------------------------------------------------------------------------------------------------ errors
@@ -65,7 +65,7 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     if (c->mel_dim % 4 || c->text_dim % 4 || c->ff_dim % 8) return fail(F5_EINVAL, "mel_dim/text_dim %% 4, ff_dim %% 8 required");
     if ((2 * c->mel_dim + c->text_dim) % 4) return fail(F5_EINVAL, "2*mel_dim + text_dim must be a multiple of 4");
     if (c->precision != F5_PREC_F32 && c->precision != F5_PREC_BF16 && c->precision != F5_PREC_F16 && c->precision != F5_PREC_F16X3 &&
-        c->precision != F5_PREC_F16P)
+        c->precision != F5_PREC_F16P && c->precision != F5_PREC_F8)
         return fail(F5_EINVAL, "bad precision");
     if (c->precision == F5_PREC_F16X3 && c->ff_dim % 32)
         return fail(F5_EINVAL, "F5_PREC_F16X3 needs ff_dim %% 32 == 0 (whole 32-element blocks of the split operand layout; got %d)", c->ff_dim);
@@ -83,6 +83,15 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     } else if (c->options && c->backbone != F5_BACKBONE_DIT) return fail(F5_EINVAL, "F5_OPT_* are options of the DiT backbone (dit.py:160-166)");
     if ((c->options & F5_OPT_TEXT_AVG_UPSAMPLE) && !c->text_mask_padding)
         return fail(F5_EINVAL, "text_embedding_average_upsampling requires text_mask_padding to be True (dit.py:41-42)");
+    if (c->precision == F5_PREC_F8) {
+        if (c->backbone != F5_BACKBONE_DIT)
+            return fail(F5_EINVAL, "f5_create: F5_PREC_F8 is built for the DiT backbone, not the %s", c->backbone == F5_BACKBONE_UNETT ? "UNetT" : "MMDiT");
+        if (c->options & F5_OPT_ADAPTERS)
+            return fail(F5_EINVAL, "f5_create: F5_PREC_F8 cannot be combined with F5_OPT_ADAPTERS (a switch merges into packed 16-bit operands; re-quantising on a switch is not built)");
+        if (c->heads % 2 || c->ff_dim % 128)
+            return fail(F5_EINVAL, "f5_create: F5_PREC_F8 needs every block GEMM's K to be whole 128-element tiles: heads even (heads * 64 = %d) and ff_dim %% 128 == 0 (ff_dim = %d)",
+                        c->heads * 64, c->ff_dim);
+    }
     f5_engine* e = new f5_engine();
     e->cfg = *c;
     e->inner = c->heads * 64;
@@ -94,7 +103,8 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     // per block 6 D (DiT), or x's 6 D then c's 6 D -- 2 D in the last, context_pre_only block -- (MMDiT); then the final norm's 2 D
     e->modN = (mmdit ? 12 * c->depth - 2 : 6 * c->depth + 2) * c->dim;
     e->split16 = c->precision == F5_PREC_F16X3;
-    e->io_split = c->precision == F5_PREC_F16P;
+    e->f8 = c->precision == F5_PREC_F8;
+    e->io_split = c->precision == F5_PREC_F16P || e->f8;
     e->sw = read_switches(*c);
     if (!valid_len_bucket(e->sw.len_bucket)) {
         const int g = e->sw.len_bucket;

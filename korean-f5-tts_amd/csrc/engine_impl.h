@@ -2,6 +2,7 @@
 // each of which instantiates EngineOps<T> for one operand type).
 #pragma once
 #include "engine_types.h"
+#include "quant8.h"
 
 // --------------------------------------------------------------------------------------------- finalize
 static int need(const WeightStore& ws, const std::string& n, std::initializer_list<int64_t> shape, const Tensor** out) {
@@ -48,18 +49,26 @@ static hipError_t egemm(const f5_engine* e, hipStream_t s, const T* A, int lda, 
 }
 
 // W [N, K] f32 -> T [N, round_up(K, 8)]
+// q8 (F5_PREC_F8, a block GEMM's weight): e4m3 codes + one scale byte per output channel, quantised from the f32 master (quant8.h); K
+// padding is zero codes; no 16-bit copy is kept (L->w stays null)
 template <typename T, bool BB = false>
 static int pack_linear(f5_engine* e, hipStream_t s, const std::string& wname, const std::string& bname, int N, int K,
-                       LinW<T>* L, int n_pad = 0) {
+                       LinW<T>* L, int n_pad = 0, bool q8 = false) {
     const Tensor *w = nullptr, *b = nullptr;
     CHK(need(e->ws, wname, {N, K}, &w));
     const int Np = n_pad ? n_pad : N;
     L->N = Np;
     L->K = K;
-    L->ldw = round_up(K, 64);
-    CHK(dev_alloc(e, &L->w, (size_t)Np * L->ldw));
-    hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)Np * L->ldw)), dim3(256), 0, s, w->p, K, N, K, L->w,
-                       L->ldw, Np);
+    L->ldw = q8 ? round_up(K, GEMM_ROW_BYTES) : round_up(K, 64);
+    if (q8) {
+        if (Np != N || K % 4) return fail(F5_EINVAL, "F5_PREC_F8: weight '%s' [%d, %d] cannot be packed as e4m3 rows", wname.c_str(), N, K);
+        CHK(dev_alloc(e, &L->w8, (size_t)N * L->ldw));
+        CHK(dev_alloc(e, &L->s8, (size_t)round_up(N, 4)));
+        launch_quant_rows_e4m3<float>(s, w->p, K, N, K, L->w8, L->ldw, L->ldw, L->s8, nullptr);
+    } else {
+        CHK(dev_alloc(e, &L->w, (size_t)Np * L->ldw));
+        hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)Np * L->ldw)), dim3(256), 0, s, w->p, K, N, K, L->w, L->ldw, Np);
+    }
     L->b = nullptr;
     if (!bname.empty()) {
         CHK(need(e->ws, bname, {N}, &b));
@@ -67,31 +76,42 @@ static int pack_linear(f5_engine* e, hipStream_t s, const std::string& wname, co
         hipLaunchKernelGGL((cast_pad_kernel<float>), dim3(ew_blocks(Np)), dim3(256), 0, s, b->p, N, 1, N, L->b, Np, 1);
     }
     HIPCHK(hipGetLastError());
+    if (q8) return F5_OK;
     return maybe_split_weight<T, BB>(e, s, L->w, (size_t)Np * L->ldw);
 }
 
 // concatenates several [Ni, K] linears row-wise into one [sum Ni, ldw] operand (+ bias)
 template <typename T, bool BB = false>
 static int pack_concat(f5_engine* e, hipStream_t s, const std::vector<std::string>& pfx, int Ni, int K, LinW<T>* L,
-                       bool bias = true) {
+                       bool bias = true, bool q8 = false) {
     const int n = (int)pfx.size();
     L->N = n * Ni;
     L->K = K;
-    L->ldw = round_up(K, 64);
-    CHK(dev_alloc(e, &L->w, (size_t)L->N * L->ldw));
+    L->ldw = q8 ? round_up(K, GEMM_ROW_BYTES) : round_up(K, 64);
+    if (q8) {   // (pack_linear: a channel's scale is its own row's, so the parts quantise independently)
+        if (K % 4 || Ni % 4) return fail(F5_EINVAL, "F5_PREC_F8: a fused weight [%d x %d, %d] cannot be packed as e4m3 rows", n, Ni, K);
+        CHK(dev_alloc(e, &L->w8, (size_t)L->N * L->ldw));
+        CHK(dev_alloc(e, &L->s8, (size_t)L->N));
+    } else {
+        CHK(dev_alloc(e, &L->w, (size_t)L->N * L->ldw));
+    }
     L->b = nullptr;
     if (bias) CHK(dev_alloc(e, &L->b, (size_t)L->N));
     for (int i = 0; i < n; ++i) {
         const Tensor *w = nullptr, *b = nullptr;
         CHK(need(e->ws, pfx[i] + ".weight", {Ni, K}, &w));
-        hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)Ni * L->ldw)), dim3(256), 0, s, w->p, K, Ni, K,
-                           L->w + (size_t)i * Ni * L->ldw, L->ldw, Ni);
+        if (q8)
+            launch_quant_rows_e4m3<float>(s, w->p, K, Ni, K, L->w8 + (size_t)i * Ni * L->ldw, L->ldw, L->ldw, L->s8 + (size_t)i * Ni, nullptr);
+        else
+            hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)Ni * L->ldw)), dim3(256), 0, s, w->p, K, Ni, K,
+                               L->w + (size_t)i * Ni * L->ldw, L->ldw, Ni);
         if (bias) {
             CHK(need(e->ws, pfx[i] + ".bias", {Ni}, &b));
             HIPCHK(hipMemcpyAsync(L->b + (size_t)i * Ni, b->p, (size_t)Ni * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     }
     HIPCHK(hipGetLastError());
+    if (q8) return F5_OK;
     return maybe_split_weight<T, BB>(e, s, L->w, (size_t)L->N * L->ldw);
 }
 
@@ -148,11 +168,12 @@ template <typename T>
 static int pack_stream(f5_engine* e, hipStream_t s, StreamW<T>& w, const std::string& at, const std::string& sfx, const std::string& out,
                        const std::string& ff, const std::string& norm, bool pre_only) {
     const int D = e->cfg.dim, F = e->cfg.ff_dim, inner = e->inner;
-    CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q" + sfx, at + ".to_k" + sfx, at + ".to_v" + sfx}, inner, D, &w.qkv));
+    const bool q8 = e->f8;   // F5_PREC_F8: these four are the e4m3 operands
+    CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q" + sfx, at + ".to_k" + sfx, at + ".to_v" + sfx}, inner, D, &w.qkv, true, q8));
     if (!pre_only) {
-        CHK(pack_linear_bb<T>(e, s, out + ".weight", out + ".bias", D, inner, &w.out));
-        CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &w.ff1));
-        CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &w.ff2));
+        CHK(pack_linear_bb<T>(e, s, out + ".weight", out + ".bias", D, inner, &w.out, 0, q8));
+        CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &w.ff1, 0, q8));
+        CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &w.ff2, 0, q8));
     }
     if (e->cfg.options & F5_OPT_QK_RMSNORM) {
         CHK(copy_vec(e, s, norm + "q_norm.weight", {64}, &w.qn));
@@ -244,7 +265,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         const std::string at = dit || mmdit ? p + ".attn" : p + ".2";
         const std::string ff = dit ? p + ".ff" : mmdit ? p + ".ff_x" : p + ".4";
         CHK(pack_stream<T>(e, s, b.x, at, "", at + ".to_out.0", ff, at + ".", false));
-        if (dit) {   // the reference's LoRA targets (train/train_lora.py); q / k / v are row ranges of the fused operand
+        if (dit && e->adapters_on) {   // the reference's LoRA targets (train/train_lora.py); q / k / v are row ranges of the fused operand
             const char* qkv_names[3] = {".to_q.weight", ".to_k.weight", ".to_v.weight"};
             for (int j = 0; j < 3; ++j)
                 CHK(reg_target(e, at + qkv_names[j], true, inner, D, b.x.qkv.ldw, b.x.qkv.w + (size_t)j * inner * b.x.qkv.ldw, merge_kind<T>(e)));
@@ -371,6 +392,11 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     w.ao = a.take<T>(jrows * e->inner);
     w.vt = a.take<T>(Bp * c.heads * 64 * w.Npad);
     w.ffh = a.take<T>(rows * F);
+    w.a8 = w.a8s = nullptr;
+    if (e->f8) {   // F5_PREC_F8 only: every other precision's plan is what it was
+        w.a8 = a.take<unsigned char>(rows * std::max(std::max(D, F), (size_t)e->inner));
+        w.a8s = a.take<unsigned char>(rows + 16);
+    }
     w.in_cond = a.take<float>((size_t)B * N * mel);
     w.y = a.take<float>((size_t)B * N * mel);
     w.y_mid = a.take<float>((size_t)B * N * mel);
@@ -524,8 +550,31 @@ struct FwdCtx {
     int wt(int bit) const { return rows <= 4096 && (e->sw.store_wt & bit) ? 1 : 0; }
     double gflops(double n, double k) const { return 2.0 * (pk ? pk.rows_host : (double)rows) * n * k; }
     // one backbone GEMM over all rows, as a profiled launch
+    // F5_PREC_F8, a block GEMM (L holds e4m3 codes): the A operand is the codes in a8 with the row scales a8s -- written by the AdaLN
+    // LayerNorm's e4m3 form (adaln_norm) or by quant8 below -- and A itself is not read
     template <typename T, typename Epi> int gemm(const T* A, int lda, const LinW<T>& L, int n, int k, const Epi& epi, bool a_split = false) const {
+        if constexpr (std::is_same_v<T, f16_t>) {
+            if (e->f8 && L.w8) {
+                HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] {
+                    GemmOpts o{GemmOperands::Plain, -1, ml(), mh()};
+                    o.a_scale = a8s;
+                    o.w_scale = L.s8;
+                    return launch_gemm<e4m3_t>(s, reinterpret_cast<const e4m3_t*>(a8), k, reinterpret_cast<const e4m3_t*>(L.w8), L.ldw, rows, n, k, epi, o);
+                }));
+                return F5_OK;
+            }
+        }
         HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] { return egemm<T>(e, s, A, lda, L.w, L.ldw, rows, n, k, epi, ml(), mh(), a_split); }));
+        return F5_OK;
+    }
+    // F5_PREC_F8: the stand-alone row quantiser on a block GEMM's 16-bit A operand [rows, k] (attention output, FF hidden) into a8 / a8s
+    template <typename T> int quant8(const T* A, int k) const {
+        if constexpr (std::is_same_v<T, f16_t>) {
+            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                launch_quant_rows_e4m3<T>(s, A, k, rows, k, a8, k, k, a8s, ml());
+                return hipGetLastError();
+            }));
+        }
         return F5_OK;
     }
     // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed).  The hooks of the shared stages act on the
@@ -535,6 +584,7 @@ struct FwdCtx {
     template <typename T> void ablate(int bit, T* a, int k) const {
         if (x3 && (e->sw.x3_ablate & bit)) zero_lo_planar(s, a, (size_t)rows * k);
     }
+    unsigned char *a8 = nullptr, *a8s = nullptr;   // F5_PREC_F8: Work::a8 / a8s
 };
 
 // Input embedding: [y, cond, text] packed as rows of U, the input projection, and the conv position embedding (two grouped convs, the second
@@ -597,6 +647,19 @@ template <typename TO>
 static hipError_t adaln_norm(const FwdCtx& f, const float* x, TO* out, const float* scale, const float* shift, int mod_stride, const Prefetch& pf,
                              int planar) {
     const int D = f.e->cfg.dim, rows = f.rows;
+    if constexpr (std::is_same_v<TO, f16_t>) {
+        if (f.e->f8)   // F5_PREC_F8: a block's LayerNorm feeds QKV / FF1 -- e4m3 codes and row scales straight from the f32 value, `out` unused
+            return f.e->prof.timed(PC_LN, f.s, [&] {
+                e4m3_t* codes = reinterpret_cast<e4m3_t*>(f.a8);
+                if (f.pk && mod_stride != 0)
+                    hipLaunchKernelGGL(layernorm_rows_q8_kernel, dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, codes, D, rows, D, 1e-6f, scale, shift,
+                                       mod_stride, pf, f.ml(), f.pk.rowmap, f.a8s);
+                else
+                    hipLaunchKernelGGL(layernorm_q8_kernel, dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, codes, D, rows, D, 1e-6f, scale, shift,
+                                       mod_stride, f.N, 1, pf, f.ml(), f.a8s);
+                return hipGetLastError();
+            });
+    }
     return f.e->prof.timed(PC_LN, f.s, [&] {
         if (f.pk && mod_stride != 0)
             hipLaunchKernelGGL((layernorm_rows_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, out, D, rows, D, 1e-6f, scale, shift,
@@ -670,6 +733,7 @@ template <typename T> static int attend(const FwdCtx& f, Work<T>& w, bool qk_nor
 template <typename T, typename Epi> static int out_project(const FwdCtx& f, T* ao, const StreamW<T>& sw, const Epi& out_epi) {
     const int D = f.e->cfg.dim, inner = f.e->inner;
     f.ablate(8, ao, inner);
+    if (f.e->f8) CHK(f.quant8(ao, inner));
     return f.gemm(ao, inner, sw.out, D, inner, out_epi, f.pl());
 }
 
@@ -690,6 +754,7 @@ template <typename T, typename Epi> static int ff_block(const FwdCtx& f, const S
     f.ablate(16, sb.xn, D);
     CHK(f.gemm(sb.xn, D, sw.ff1, F, D, EpiStore<T>{sb.ffh, F, sw.ff1.b, F5_ACT_GELU_TANH, pl, f.wt(F5_WT_STORE16)}, pl));
     f.ablate(32, sb.ffh, F);
+    if (f.e->f8) CHK(f.quant8(sb.ffh, F));
     return f.gemm(sb.ffh, F, sw.ff2, D, F, out_epi, pl);
 }
 
@@ -751,7 +816,10 @@ template <typename T> static int run_dit_forward(f5_engine* e, Work<T>& w, const
     const f5_config& c = e->cfg;
     const int D = c.dim, N = a.N, rows = a.Bp * N, mod_stride = a.time_stride;
     const RowPack& pk = a.pk;
-    const FwdCtx f{e, s, a.B, a.Bp, N, rows, a.lens_dev, pk};
+    FwdCtx fc{e, s, a.B, a.Bp, N, rows, a.lens_dev, pk};
+    fc.a8 = w.a8;
+    fc.a8s = w.a8s;
+    const FwdCtx& f = fc;
     const int* ml = f.ml();
     const int mh = f.mh(), pl = f.pl();
     const int* gate_lens = pk ? nullptr : a.lens_dev; // (a packed batch has no padded rows to leave untouched)
@@ -765,6 +833,7 @@ template <typename T> static int run_dit_forward(f5_engine* e, Work<T>& w, const
     // weight prefetch from the LayerNorm launches (see layernorm_kernel): only where the GEMMs are latency-bound
     const bool wpf = rows <= 4096 && e->sw.weight_prefetch;
     auto prefetch = [&](const LinW<T>& g0, const LinW<T>& g1) {   // the weights of the two GEMMs behind a LayerNorm
+        if (wpf && e->f8) return Prefetch{(const char*)g0.w8, (size_t)g0.N * g0.ldw, (const char*)g1.w8, (size_t)g1.N * g1.ldw};   // (e4m3 codes)
         return wpf ? Prefetch{(const char*)g0.w, (size_t)g0.N * g0.ldw * sizeof(T), (const char*)g1.w, (size_t)g1.N * g1.ldw * sizeof(T)} : Prefetch{};
     };
     const bool row_mods = pk && mod_stride != 0;   // every batch row of a packed batch has its own vectors
@@ -1129,6 +1198,10 @@ template <typename T> static Work<T> second_half(const f5_engine* e, const Work<
     h.ao = w.ao + rows * e->inner;
     h.vt = w.vt + (size_t)B * c.heads * 64 * w.Npad;
     h.ffh = w.ffh + rows * c.ff_dim;
+    if (e->f8) {   // (rows * the widest K, and one scale byte per row)
+        h.a8 = w.a8 + rows * std::max(std::max((size_t)c.dim, (size_t)c.ff_dim), (size_t)e->inner);
+        h.a8s = w.a8s + rows;
+    }
     if (c.options & F5_OPT_LONG_SKIP) h.cat2 = w.cat2 + rows * 2 * c.dim * io;
     return h;
 }

@@ -80,6 +80,8 @@ template <typename T> struct LinW {
     T* w = nullptr;      // [N, ldw]
     float* b = nullptr;  // [N] or null
     int N = 0, K = 0, ldw = 0;
+    // F5_PREC_F8 (the four block GEMMs): e4m3 codes [N, ldw] and one e8m0 scale byte per output channel [N]; w is then null
+    unsigned char *w8 = nullptr, *s8 = nullptr;
 };
 
 // One stream's weights of a block: q / k / v fused, out-projection, feed-forward pair
@@ -257,6 +259,7 @@ struct f5_engine {
     f5_config cfg{};
     int inner = 0, kin = 0, kin_pad = 0, modN = 0;
     bool io_split = false;     // F5_PREC_F16P: the f16 engine with its input / output layers as split-f16 products on f32 operands
+    bool f8 = false;           // F5_PREC_F8: F5_PREC_F16P (io_split is set too) with e4m3 operands in the four GEMMs of every DiT block
     bool split16 = false;      // F5_PREC_F16X3: the f32 engine with the backbone GEMMs on the f16 pipe (gemm2.h GemmOperands::WSplit)
     Switches sw;
     WeightStore ws;
@@ -324,6 +327,9 @@ template <typename T> struct Work {
     T* acat;
     float *h, *c1, *x, *pred;
     T *xn, *q, *k, *vt, *ao, *ffh;
+    // F5_PREC_F8 (else null): the A operand of the block GEMM about to run -- e4m3 codes [rows, max(D, inner, F)] at the pitch of its K --
+    // and its row scale bytes [rows]
+    unsigned char *a8, *a8s;
     T* cat2;         // UNetT concat buffer [rows, 2D]
     float* skips;    // UNetT skip stack
     float* pred_all; // UNetT proj_out over N+1 tokens

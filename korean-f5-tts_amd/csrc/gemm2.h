@@ -11,7 +11,7 @@
 //     rows beyond M / N are clamped (their results are never stored).
 // Requirements: K % (128 / sizeof(T)) == 0 (the engine pads K), lda/ldw multiples of 16 bytes.
 #pragma once
-#include "gemm.h"
+#include "gemm8.h"
 
 
 namespace f5 {
@@ -302,6 +302,25 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
 #pragma unroll
                 for (int i = 1; i < MI; ++i) lds_read_b128_asm(af[kk][i], sbu + a_row_off + i * 16 * GEMM_ROW_BYTES + co);
             }
+            // e4m3 operands (gemm8.h): the two fragment reads of a row are ONE 32-byte operand of the K = 128 scaled MFMA
+            if constexpr (sizeof(T) == 1) {
+#pragma unroll
+                for (int i = 0; i < MI; ++i) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    wait_row<R, MI, NJ>(1, i, af, wf);
+                    tie(af[0][i]);
+                    if (i == 0) {
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) tie(wf[0][j]);
+                    }
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) {
+                        if (j < NJ - NT) acc[i][j] = Mma8::run(wf[0][j], wf[1][j], af[0][i], af[1][i], acc[i][j]);
+                        else acc[i][j] = Mma8::run(af[0][i], af[1][i], wf[0][j], wf[1][j], acc[i][j]);
+                    }
+                }
+                return;
+            } else {
             // AWSplit: the A operand is ALREADY split in memory (store4_planar by its producer): its two fragment reads are hi and lo.
             // (TwoOfThree, OneOfThree: tools/probe/gemm_split_probe.hip -- 2 of 3 / 1 of 3 MFMAs)
             if constexpr (OPS != GemmOperands::Plain) {
@@ -346,6 +365,7 @@ __device__ __forceinline__ void gemm_tn_glds_body(char* smem, const T* __restric
                         else acc[i][j] = Mma<T>::run(af[kk][i], wf[kk][j], acc[i][j]);
                     }
                 }
+            }
             }
         };
         int stage = 0;

@@ -42,6 +42,10 @@ constexpr bool gemm_has_pingpong(int elem_size, GemmOperands ops) {
     return (elem_size == 2 && ops == GemmOperands::Plain) || (elem_size == 4 && ops == GemmOperands::AWSplit);
 }
 
+// e4m3 operands (element size 1, gemm8.h): the ring tiles instantiated for them -- one many-row tile, one for a few hundred rows, one
+// small tile for few rows and the remainder launch.  No v1 and no ping-pong kernel: K is a whole number of 128-code K-tiles or refused.
+constexpr bool gemm_tile_has_f8(int id) { return id == G2_256x128_8W || id == G2_128x128_8W || id == G2_64x64_4W; }
+
 struct GemmProblem {   // what plan_gemm decides on
     int elem_size, M, N, K;
     bool has_m_limit;       // a device row count comes with the launch
@@ -78,12 +82,47 @@ inline int pick_tile_v1(int M, int N) {
     return G1_64x64;
 }
 
+// The plan for e4m3 operands: plain operands, no implicit conv, whole K-tiles; the cost search of pick_cfg_v2 over the f8 tiles (their
+// times per round are taken as proportional to the 16-bit ones); the remainder split of the many-row tile as for the ping-pong kernel.
+inline GemmPlan plan_gemm_f8(const GemmProblem& p) {
+    GemmPlan r;
+    const GemmPlan refused{false, 0, {}};
+    if (p.ops != GemmOperands::Plain || p.conv || p.K <= 0 || p.K % GEMM_ROW_BYTES != 0 || p.force_cfg == -2) return refused;
+    if (p.force_cfg >= 0 && !gemm_tile_has_f8(p.force_cfg)) return refused;
+    auto pick = [&](int M) {
+        if (p.env_cfg >= 0 && gemm_tile_has_f8(p.env_cfg) && (p.env_n == 0 || p.env_n == p.N)) return p.env_cfg;
+        if (M <= 64) return (int)G2_64x64_4W;
+        int best = G2_64x64_4W;
+        float best_cost = 3.0e38f;
+        for (const GemmTile& c : kGemmTiles) {
+            if (!gemm_tile_has_f8(c.id)) continue;
+            const long tiles = (long)((M + c.bm - 1) / c.bm) * ((p.N + c.bn - 1) / c.bn);
+            const float cost = (float)((tiles + 255) / 256) * c.us;
+            if (cost < best_cost) { best_cost = cost; best = c.id; }
+        }
+        return best;
+    };
+    r.n = 1;
+    if (p.force_cfg == -1 && !p.has_m_limit) {
+        const int rem = p.M % 256, main = p.M - rem;
+        if (rem > 0 && rem <= 64 && main >= 4096 && pick(main) == G2_256x128_8W) {
+            r.n = 2;
+            r.l[0] = {GEMM_RING, G2_256x128_8W, 0, main};
+            r.l[1] = {GEMM_RING, G2_64x64_4W, main, rem};
+            return r;
+        }
+    }
+    r.l[0] = {GEMM_RING, p.force_cfg >= 0 ? p.force_cfg : pick(p.m_hint > 0 ? p.m_hint : p.M), 0, p.M};
+    return r;
+}
+
 // Every dispatch decision (no HIP call, no environment): launch_gemm() executes what this returns, f5k_gemm_plan() shows it to the
 // tests without a GPU.
 inline GemmPlan plan_gemm(const GemmProblem& p) {
     GemmPlan r;
     const GemmPlan refused{false, 0, {}};
     if (p.M <= 0 || p.N <= 0) return r;
+    if (p.elem_size == 1) return plan_gemm_f8(p);
     const bool plain = p.ops == GemmOperands::Plain;
     const GemmTile* forced = p.force_cfg >= 0 ? gemm_tile(p.force_cfg) : nullptr;
     const bool forced_v1 = forced && forced->family == GEMM_V1;
@@ -139,7 +178,8 @@ inline hipError_t launch_gemm_tile(hipStream_t s, const T* A, int lda, const T* 
     if constexpr (I < sizeof(kGemmTiles) / sizeof(kGemmTiles[0])) {
         constexpr GemmTile t = kGemmTiles[I];
         if (t.id != tile) return launch_gemm_tile<T, OPS, Epi, RING_ONLY, I + 1>(s, A, lda, W, ldw, M, N, K, epi, tile, ml, cv);
-        if constexpr (t.family == GEMM_RING) return launch_gemm2<T, t.bm, t.bn, t.wm, t.wn, t.ns, Epi, OPS>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
+        if constexpr (sizeof(T) == 1 && !(t.family == GEMM_RING && gemm_tile_has_f8(t.id))) return hipErrorInvalidValue;   // e4m3: its ring tiles only
+        else if constexpr (t.family == GEMM_RING) return launch_gemm2<T, t.bm, t.bn, t.wm, t.wn, t.ns, Epi, OPS>(s, A, lda, W, ldw, M, N, K, epi, ml, cv);
         else if constexpr (RING_ONLY) return hipErrorInvalidValue;
         else if constexpr (t.family == GEMM_V1 && OPS == GemmOperands::Plain) return launch_gemm1<T, t.bm, t.bn, Epi>(s, A, lda, W, ldw, M, N, K, epi);
         else if constexpr (t.family == GEMM_PINGPONG && gemm_has_pingpong(sizeof(T), OPS)) return launch_gemm3<T, Epi, OPS>(s, A, lda, W, ldw, M, N, K, epi, ml);
@@ -154,6 +194,9 @@ struct GemmOpts {
     const int* m_limit = nullptr;    // device int: rows actually present, <= M (ring / ping-pong only: the engine's operands always qualify)
     int m_hint = 0;                  // the row count the caller expects behind m_limit
     GemmConv conv = {};
+    // e4m3 operands (T = e4m3_t, gemm8.h): one e8m0 scale byte per row of A and per row of W (w_scale 4-byte aligned)
+    const unsigned char* a_scale = nullptr;
+    const unsigned char* w_scale = nullptr;
 };
 
 template <typename T, typename Epi>
@@ -175,7 +218,10 @@ inline hipError_t launch_gemm(hipStream_t s, const T* A, int lda, const T* W, in
                 if (o.ops == GemmOperands::AWSplit) err = launch_gemm_tile<T, GemmOperands::AWSplit, E>(s, A + (size_t)l.row0 * lda, lda, W, ldw, l.rows, N, K, e, l.tile, o.m_limit, c);
                 if (o.ops == GemmOperands::WSplit) err = launch_gemm_tile<T, GemmOperands::WSplit, E>(s, A + (size_t)l.row0 * lda, lda, W, ldw, l.rows, N, K, e, l.tile, o.m_limit, c);
             }
-            if (o.ops == GemmOperands::Plain) err = launch_gemm_tile<T, GemmOperands::Plain, E>(s, A + (size_t)l.row0 * lda, lda, W, ldw, l.rows, N, K, e, l.tile, o.m_limit, c);
+            if constexpr (sizeof(T) == 1) {   // the epilogue behind the operands' scales (row m of the epilogue = row m of a_scale)
+                if (!o.a_scale || !o.w_scale) return hipErrorInvalidValue;
+                err = launch_gemm_tile<T, GemmOperands::Plain, EpiScale8<E>>(s, A + (size_t)l.row0 * lda, lda, W, ldw, l.rows, N, K, EpiScale8<E>{e, o.a_scale, o.w_scale}, l.tile, o.m_limit, c);
+            } else if (o.ops == GemmOperands::Plain) err = launch_gemm_tile<T, GemmOperands::Plain, E>(s, A + (size_t)l.row0 * lda, lda, W, ldw, l.rows, N, K, e, l.tile, o.m_limit, c);
             if (err != hipSuccess) return err;
         }
         return hipSuccess;

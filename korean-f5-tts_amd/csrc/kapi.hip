@@ -33,7 +33,7 @@ extern "C" int f5k_gemm(int32_t prec, const float* A, const float* W, const floa
 // launch_gemm's decision for one problem, without launching (plan_gemm, gemm_dispatch.h): pure host arithmetic, no HIP call
 extern "C" int f5k_gemm_plan(int32_t elem_size, int32_t M, int32_t N, int32_t K, int32_t has_m_limit, int32_t m_hint, int32_t operand_form,
                              int32_t conv, int32_t pp_epilogue, int32_t force_cfg, int32_t env_cfg, int32_t env_cfg_n, int32_t* plan) {
-    if (!plan || (elem_size != 2 && elem_size != 4) || operand_form < 0 || operand_form > 2) return fail(F5_EINVAL, "f5k_gemm_plan: bad arguments");
+    if (!plan || (elem_size != 1 && elem_size != 2 && elem_size != 4) || operand_form < 0 || operand_form > 2) return fail(F5_EINVAL, "f5k_gemm_plan: bad arguments");
     const GemmPlan g = plan_gemm({elem_size, M, N, K, has_m_limit != 0, m_hint, (GemmOperands)operand_form, conv != 0, pp_epilogue != 0, force_cfg, env_cfg, env_cfg_n});
     plan[0] = g.ok ? g.n : -1;
     static_assert(sizeof(g.l) == 8 * sizeof(int32_t), "two launches of four ints");
@@ -77,9 +77,66 @@ static int gemm_time_impl(int M, int N, int K, int cfg, GemmOperands ops, int it
     return F5_OK;
 }
 
+// F5_PREC_F8: the e4m3 kernel on random codes (scale bytes 127) into f16 rows; with_quant: the stand-alone row quantiser of an f16 A
+// operand [M, K] runs inside the timed region, as out_project / ff_block launch it before the GEMM
+static int gemm_time_f8_impl(int M, int N, int K, int cfg, bool with_quant, int iters, float* avg_us, hipStream_t s) {
+    if (K % GEMM_ROW_BYTES) return fail(F5_EINVAL, "f5k_gemm_time: F5_PREC_F8 needs K %% 128 == 0");
+    Scratch<unsigned char> a8, w8, as, ws;
+    Scratch<f16_t> o, a16;
+    HIPCHK(a8.alloc((size_t)M * K));
+    HIPCHK(w8.alloc((size_t)N * K));
+    HIPCHK(as.alloc((size_t)M + 16));
+    HIPCHK(ws.alloc((size_t)N + 16));
+    HIPCHK(o.alloc((size_t)M * N));
+    HIPCHK(a16.alloc((size_t)M * K));
+    const size_t nmax = std::max((size_t)M, (size_t)N) * K;
+    std::vector<unsigned char> h(nmax);
+    unsigned x = 12345u;
+    for (size_t i = 0; i < nmax; ++i) {   // random finite codes (exponent field below 15), non-zero data
+        x = x * 1664525u + 1013904223u;
+        h[i] = (unsigned char)((x >> 9) & 0xF7u);
+    }
+    HIPCHK(hipMemcpy(a8.p, h.data(), (size_t)M * K, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(w8.p, h.data(), (size_t)N * K, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(as.p, 127, (size_t)M + 16));
+    HIPCHK(hipMemset(ws.p, 127, (size_t)N + 16));
+    std::vector<uint16_t> h16((size_t)M * K);
+    for (size_t i = 0; i < h16.size(); ++i) {   // f16 values in (-2, 2)
+        x = x * 1664525u + 1013904223u;
+        h16[i] = (uint16_t)(((x >> 8) & 0x83FFu) | 0x3C00u);
+    }
+    HIPCHK(hipMemcpy(a16.p, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    auto go = [&]() {
+        if (with_quant) launch_quant_rows_e4m3<f16_t>(s, a16.p, K, M, K, a8.p, K, K, as.p, nullptr);
+        GemmOpts op{GemmOperands::Plain, cfg};
+        op.a_scale = as.p;
+        op.w_scale = ws.p;
+        return launch_gemm<e4m3_t>(s, reinterpret_cast<const e4m3_t*>(a8.p), K, reinterpret_cast<const e4m3_t*>(w8.p), K, M, N, K,
+                                   EpiStore<f16_t>{o.p, N, nullptr, 0}, op);
+    };
+    for (int i = 0; i < 3; ++i) HIPCHK(go());
+    HIPCHK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; ++i) HIPCHK(go());
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    *avg_us = ms * 1000.0f / iters;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return F5_OK;
+}
+
 extern "C" int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tm, int32_t tn, int32_t iters,
                              float* avg_us, f5_stream stream) {
     if (!avg_us || M <= 0 || N <= 0 || K <= 0 || iters <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm_time: bad arguments");
+    if (prec == F5_PREC_F8) {   // tile_m: 0 auto or -(tile id 2, 8, 13); tile_n == 1: with the A operand's quantise launch
+        if (tm > 0 || (tm < 0 && !gemm_tile_has_f8(-tm))) return fail(F5_EINVAL, "f5k_gemm_time: F5_PREC_F8 runs on tile ids 2, 8, 13 (tile_m = -id) or 0");
+        return gemm_time_f8_impl(M, N, K, forced_cfg(tm, tn), tn == 1, iters, avg_us, (hipStream_t)stream);
+    }
     const GemmOperands ops = prec == F5_PREC_F16X3 && tm <= 0 ? GemmOperands::WSplit : GemmOperands::Plain;   // (a v1 tile: plain f32)
     return F5K_BY_PREC(prec, gemm_time_impl, M, N, K, forced_cfg(tm, tn), ops, iters, avg_us, (hipStream_t)stream);
 }
@@ -268,6 +325,64 @@ extern "C" int f5k_layernorm_mod(const float* x, const float* scale, const float
     return F5_OK;
 }
 
+// ------------------------------------------------------------------------------------------- F5_PREC_F8 quantisers (quant8.h)
+// The stand-alone row quantiser on caller-owned device buffers: x [R, ld] of f32 (F5_PREC_F32) or 16-bit values -> codes [R, ldc], scales [R].
+extern "C" int f5k_quant_rows_e4m3(int32_t prec, const void* x, int64_t ld, int32_t R, int32_t K, uint8_t* codes, int64_t ldc, uint8_t* scales,
+                                   int32_t m_limit, f5_stream stream) {
+    if (!x || !codes || !scales || R <= 0 || K <= 0 || K % 4 || ld < K || ldc < K || ldc % 4 || m_limit < -1)
+        return fail(F5_EINVAL, "f5k_quant_rows_e4m3: bad arguments (K %% 4 == 0, ld >= K, ldc >= K, ldc %% 4 == 0, m_limit -1 or >= 0)");
+    if (prec != F5_PREC_F32 && prec != F5_PREC_BF16 && prec != F5_PREC_F16) return fail(F5_EINVAL, "f5k_quant_rows_e4m3: rows are f32, bf16 or f16");
+    if (ld % 4 || ((size_t)x & (prec == F5_PREC_F32 ? 15 : 7)))
+        return fail(F5_EINVAL, "f5k_quant_rows_e4m3: rows must start at whole groups of four elements (ld %% 4 == 0, aligned x)");
+    hipStream_t s = (hipStream_t)stream;
+    Scratch<int> ml;
+    if (m_limit >= 0) {
+        HIPCHK(ml.alloc(1));
+        HIPCHK(hipMemcpy(ml.p, &m_limit, 4, hipMemcpyHostToDevice));
+    }
+    const int* mlp = m_limit >= 0 ? ml.p : nullptr;
+    const int Kc = round_up(K, 4);
+    if (prec == F5_PREC_F32) launch_quant_rows_e4m3<float>(s, static_cast<const float*>(x), ld, R, K, codes, ldc, Kc, scales, mlp);
+    else if (prec == F5_PREC_BF16) launch_quant_rows_e4m3<bf16_t>(s, static_cast<const bf16_t*>(x), ld, R, K, codes, ldc, Kc, scales, mlp);
+    else launch_quant_rows_e4m3<f16_t>(s, static_cast<const f16_t*>(x), ld, R, K, codes, ldc, Kc, scales, mlp);
+    KCHK();
+    HIPCHK(hipStreamSynchronize(s));
+    return F5_OK;
+}
+// The e4m3 output form of the AdaLN LayerNorm as adaln_norm launches it: codes [R, D] + scales [R].  batch_of_row_host (HOST int32[R], or
+// NULL): the packed form -- row r takes the vectors of batch row batch_of_row[r] (layernorm_rows_q8_kernel; scale / shift rows are D apart).
+extern "C" int f5k_layernorm_q8(const float* x, const float* scale, const float* shift, uint8_t* codes, uint8_t* scales, int32_t R, int32_t D,
+                                int32_t rows_per_batch, float eps, int32_t m_limit, const int32_t* batch_of_row_host, f5_stream stream) {
+    if (!x || !codes || !scales || R <= 0 || D <= 0 || D % 4 || D > 2048 || rows_per_batch <= 0 || m_limit < -1)
+        return fail(F5_EINVAL, "f5k_layernorm_q8: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    Scratch<int> ml;
+    if (m_limit >= 0) {
+        HIPCHK(ml.alloc(1));
+        HIPCHK(hipMemcpy(ml.p, &m_limit, 4, hipMemcpyHostToDevice));
+    }
+    const int* mlp = m_limit >= 0 ? ml.p : nullptr;
+    e4m3_t* out = reinterpret_cast<e4m3_t*>(codes);
+    Scratch<int2> rowmap;
+    if (batch_of_row_host) {
+        std::vector<int2> h((size_t)R);
+        for (int r = 0; r < R; ++r) {
+            if (batch_of_row_host[r] < 0) return fail(F5_EINVAL, "f5k_layernorm_q8: negative batch row");
+            h[r] = make_int2(batch_of_row_host[r], 0);
+        }
+        HIPCHK(rowmap.alloc((size_t)R));
+        HIPCHK(hipMemcpy(rowmap.p, h.data(), (size_t)R * sizeof(int2), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(layernorm_rows_q8_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, D, out, D, R, D, eps, scale, shift, D, Prefetch{}, mlp,
+                           rowmap.p, scales);
+    } else {
+        hipLaunchKernelGGL(layernorm_q8_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, D, out, D, R, D, eps, scale, shift, D, rows_per_batch, 1,
+                           Prefetch{}, mlp, scales);
+    }
+    KCHK();
+    HIPCHK(hipStreamSynchronize(s));
+    return F5_OK;
+}
+
 template <typename TO>
 static int layernorm_ex_impl(const float* x, const float* scale, const float* shift, void* out, float* out_f32, int R, int D,
                              int rows_per_batch, float eps, int m_limit, int planar, hipStream_t s) {
@@ -299,8 +414,13 @@ extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* s
                                     f5_stream stream) {
     if (!x || !out || R <= 0 || D <= 0 || D % 4 || D > 2048 || rows_per_batch <= 0 || m_limit < -1)
         return fail(F5_EINVAL, "f5k_layernorm_mod_ex: bad arguments");
+    if (prec == F5_PREC_F8) {   // out: the e4m3 codes [R, D], then one scale byte per row
+        if (out_f32 || planar) return fail(F5_EINVAL, "f5k_layernorm_mod_ex: F5_PREC_F8 writes uint8 codes [R, D] then R scale bytes into out (no out_f32, no planar)");
+        return f5k_layernorm_q8(x, scale, shift, static_cast<uint8_t*>(out), static_cast<uint8_t*>(out) + (size_t)R * D, R, D, rows_per_batch, eps, m_limit,
+                                nullptr, stream);
+    }
     if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
-        return fail(F5_EINVAL, "f5k_layernorm_mod_ex: precision must be f32, f16x3, bf16 or f16");
+        return fail(F5_EINVAL, "f5k_layernorm_mod_ex: precision must be f32, f16x3, bf16, f16 or f8");
     if (planar < 0 || planar > 2 || (planar && (prec == F5_PREC_BF16 || prec == F5_PREC_F16 || D % 32)) || (planar == 2 && m_limit >= 0))
         return fail(F5_EINVAL, "f5k_layernorm_mod_ex: planar needs an f32 output and D %% 32 == 0 (planar 2: every row)");
     return F5K_BY_PREC(prec, layernorm_ex_impl, x, scale, shift, out, out_f32, R, D, rows_per_batch, eps, m_limit, planar,
@@ -313,16 +433,19 @@ extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* s
 // launch_qknorm_rope, the launcher qkv_project calls.
 template <typename T, typename Epi>
 static int epi_gemm(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const Epi& epi, int cfg, const int* ml,
-                    GemmOperands ops) {
+                    GemmOperands ops, const unsigned char* sa = nullptr, const unsigned char* sw = nullptr) {
     if (cfg == G3_256x256_PP && !(gemm_has_pingpong(sizeof(T), ops) && gemm3_epilogue_ok(epi)))
         return fail(F5_EINVAL, "f5k_gemm_epi: the ping-pong kernel (cfg 20) takes 16-bit or pre-split operands and a QKV split at 256 columns");
-    HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, {ops, cfg, ml}));
+    GemmOpts o{ops, cfg, ml};
+    o.a_scale = sa;   // (e4m3 operands: the scale bytes of their rows)
+    o.w_scale = sw;
+    HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, o));
     return F5_OK;
 }
 
 template <typename T, typename TO>
 static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const float* bias, const f5k_epi& p, const int* ml,
-                   GemmOperands ops) {
+                   GemmOperands ops, const unsigned char* sa = nullptr, const unsigned char* sw = nullptr) {
     Scratch<float> frag;
     HIPCHK(frag.alloc((size_t)p.maxpos * 64));
     hipLaunchKernelGGL(rope_frag_kernel, dim3(ew_blocks((long)p.maxpos * 16)), dim3(256), 0, s, p.rope_cos, p.rope_sin, frag.p, (long)p.maxpos);
@@ -344,7 +467,7 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
     CHK(epi_gemm<T>(s, a, w, ld, M, N, K,
                     EpiQKV<TO>{q, k, static_cast<TO*>(p.out2), bias, frag.p, p.Nseq, p.Npad, p.H, norm ? 0 : p.pe_heads,
                                norm ? 1.0f : p.q_scale, rowmap.p},
-                    p.cfg, ml, ops));
+                    p.cfg, ml, ops, sa, sw));
     if (norm)   // (own layout: the stream is the whole sequence)
         HIPCHK(launch_qknorm_rope<TO>(s, q, k, p.gq, p.gk, p.rope_cos, p.rope_sin, p.Bp, p.H, p.Nseq, p.Nseq, 0, p.pe_heads, p.q_scale, 1e-6f));
     CHK(copy_f32<TO>(s, p.out0, p.out0_f32, p.n0));
@@ -406,16 +529,66 @@ static int gemm_epi_impl(const float* A, const float* W, const float* bias, int 
     return F5_OK;
 }
 
+// F5_PREC_F8: A and W are quantised per the contract (quant_rows_e4m3_kernel: codes in rows of whole K-tiles, one scale byte per row) and
+// multiplied by the e4m3 kernel; 16-bit outputs (out16 STORE, q / k / v^T) are f16, as in the engine.
+static int gemm_epi_f8_impl(const float* A, const float* W, const float* bias, int M, int N, int K, const f5k_epi& p, hipStream_t s) {
+    const int Kp = round_up(K, GEMM_ROW_BYTES);
+    Scratch<unsigned char> a8, w8, as, ws;
+    HIPCHK(a8.alloc((size_t)M * Kp));
+    HIPCHK(w8.alloc((size_t)N * Kp));
+    HIPCHK(as.alloc((size_t)M + 16));
+    HIPCHK(ws.alloc((size_t)N + 16));
+    launch_quant_rows_e4m3<float>(s, A, K, M, K, a8.p, Kp, Kp, as.p, nullptr);
+    launch_quant_rows_e4m3<float>(s, W, K, N, K, w8.p, Kp, Kp, ws.p, nullptr);
+    KCHK();
+    const e4m3_t* a = reinterpret_cast<const e4m3_t*>(a8.p);
+    const e4m3_t* w = reinterpret_cast<const e4m3_t*>(w8.p);
+    Scratch<int> ml, lens;
+    if (p.m_limit >= 0) {
+        HIPCHK(ml.alloc(1));
+        HIPCHK(hipMemcpy(ml.p, &p.m_limit, 4, hipMemcpyHostToDevice));
+    }
+    const GemmOperands ops = GemmOperands::Plain;
+    switch (p.kind) {
+        case F5K_EPI_STORE:
+            if (p.out16) {
+                CHK(epi_gemm<e4m3_t>(s, a, w, Kp, M, N, Kp, EpiStore<f16_t>{static_cast<f16_t*>(p.out0), N, bias, p.act, 0, wt_fits(store_policy() & F5_WT_STORE16, (size_t)M * N * 2)},
+                                     p.cfg, ml.p, ops, as.p, ws.p));
+                CHK(copy_f32<f16_t>(s, p.out0, p.out0_f32, p.n0));
+            } else {
+                CHK(epi_gemm<e4m3_t>(s, a, w, Kp, M, N, Kp, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, 0}, p.cfg, ml.p, ops, as.p, ws.p));
+            }
+            break;
+        case F5K_EPI_GATE_RES:
+            if (p.lens_host) {
+                HIPCHK(lens.alloc((size_t)p.nlens));
+                HIPCHK(hipMemcpy(lens.p, p.lens_host, (size_t)p.nlens * 4, hipMemcpyHostToDevice));
+            }
+            CHK(epi_gemm<e4m3_t>(s, a, w, Kp, M, N, Kp,
+                                 EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p,
+                                            wt_fits(store_policy() & F5_WT_GATE_RES, (size_t)M * N * 4)},
+                                 p.cfg, ml.p, ops, as.p, ws.p));
+            break;
+        default:
+            CHK((epi_qkv<e4m3_t, f16_t>(s, a, w, Kp, M, N, Kp, bias, p, ml.p, ops, as.p, ws.p)));
+            break;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return F5_OK;
+}
+
 extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const float* bias, int32_t M, int32_t N, int32_t K,
                             const f5k_epi* p, f5_stream stream) {
     if (!A || !W || !p || !p->out0 || M <= 0 || N <= 0 || K <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm_epi: bad arguments (N %% 4 == 0)");
-    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
-        return fail(F5_EINVAL, "f5k_gemm_epi: precision must be f32, f16x3, bf16 or f16");
+    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16 && prec != F5_PREC_F8)
+        return fail(F5_EINVAL, "f5k_gemm_epi: precision must be f32, f16x3, bf16, f16 or f8");
+    if (prec == F5_PREC_F8 && (K % 4 || (p->cfg != -1 && !gemm_tile_has_f8(p->cfg)) || p->planar))
+        return fail(F5_EINVAL, "f5k_gemm_epi: F5_PREC_F8 needs K %% 4 == 0, cfg -1, 2, 8 or 13 and no planar output");
     if (p->cfg != -1 && (!gemm_tile(p->cfg) || v1_tile(p->cfg)))
         return fail(F5_EINVAL, "f5k_gemm_epi: cfg must be -1, 2, 8, 9, 10, 13 or 20");
     if (p->m_limit < -1 || p->m_limit > M) return fail(F5_EINVAL, "f5k_gemm_epi: m_limit must be -1 or 0..M");
     if (p->a_presplit && prec != F5_PREC_F16X3) return fail(F5_EINVAL, "f5k_gemm_epi: a_presplit needs F5_PREC_F16X3");
-    const bool op16 = prec == F5_PREC_BF16 || prec == F5_PREC_F16;
+    const bool op16 = prec == F5_PREC_BF16 || prec == F5_PREC_F16 || prec == F5_PREC_F8;   // (f8: 16-bit outputs are f16)
     switch (p->kind) {
         case F5K_EPI_STORE:
             if (p->out16 && !op16) return fail(F5_EINVAL, "f5k_gemm_epi: a 16-bit STORE needs a 16-bit operand precision");
@@ -450,6 +623,7 @@ extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const 
         }
         default: return fail(F5_EINVAL, "f5k_gemm_epi: unknown epilogue kind");
     }
+    if (prec == F5_PREC_F8) return gemm_epi_f8_impl(A, W, bias, M, N, K, *p, (hipStream_t)stream);
     const GemmOperands ops = prec != F5_PREC_F16X3 ? GemmOperands::Plain : p->a_presplit ? GemmOperands::AWSplit : GemmOperands::WSplit;
     return F5K_BY_PREC(prec, gemm_epi_impl, A, W, bias, M, N, K, *p, ops, (hipStream_t)stream);
 }

@@ -8,6 +8,7 @@
 #include "flow.h"
 #include "gemm_dispatch.h"
 #include "internal.h"
+#include "quant8.h"
 
 using namespace f5;
 #define fail f5_fail

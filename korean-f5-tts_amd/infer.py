@@ -156,6 +156,8 @@ def load_adapter(model, ckpt_path: str, name: str, use_ema: bool = True, *, lora
     from .adapters import split_peft_state_dict
 
     tr = getattr(model, "transformer", model)
+    if getattr(tr, "precision", None) == "f8":   # (before the checkpoint is read: add_adapter would refuse it afterwards)
+        raise NotImplementedError("resident adapters are not built for precision 'f8': load the model in 'f16p' to use adapters")
     _, tensors = split_peft_state_dict(_read_checkpoint_state_dict(ckpt_path, use_ema), base=tr.state_dict())
     tr.add_adapter(name, tensors, lora_alpha=lora_alpha, lora_r=lora_r, alpha_pattern=alpha_pattern, rank_pattern=rank_pattern)
     return model
