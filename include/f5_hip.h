@@ -909,11 +909,12 @@ int f5k_strip_first_token(const float* in, float* out, int32_t Bp, int32_t N, in
  * call_B <= B utterances of call_N <= N frames, both on a dry-run arena.  *total_bytes: the arena size.  main_off / side_off
  * int64[F5K_WORK_BUFFERS]: byte offset of each buffer in the order of F5K_WORK_NAMES, -1 where the config has no such buffer (and for the buffers of f5_sample_items, which
  * an engine carves only once such a call has been made);
- * side_off equals main_off for a buffer both chains share. */
-#define F5K_WORK_BUFFERS 44
+ * side_off equals main_off for a buffer both chains share.  a8 / a8s (F5_PREC_F8 only, else -1): the e4m3 codes of the block GEMM's A
+ * operand, rows * max(dim, ff_dim, heads * 64) bytes, and its row scale bytes. */
+#define F5K_WORK_BUFFERS 46
 #define F5K_WORK_NAMES                                                                                                              \
     "tdev feat th temb st mod lens lens_plain row_start rowmap step_cond text_c text_u tx_a tx_b tx_h1 grn_part uc acat h c1 x pred " \
-    "xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps it_idx"
+    "xn q k ao vt ffh a8 a8s in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps it_idx"
 int f5k_work_plan(const f5_config* c, int32_t B, int32_t N, int32_t S, int32_t call_B, int32_t call_N, int64_t* total_bytes,
                   int64_t* main_off, int64_t* side_off);
 /* Diagnostic taps of the MMDiT forward (tests): `taps` (device f32, or NULL to switch them off) receives, from every later

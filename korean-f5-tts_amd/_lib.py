@@ -55,7 +55,7 @@ _f = C.c_float
 F5K_EPI_STORE, F5K_EPI_GATE_RES, F5K_EPI_QKV, F5K_EPI_QKNORM = 0, 1, 2, 3
 # the buffers of f5k_work_plan, in its order (F5K_WORK_NAMES of include/f5_hip.h)
 F5K_WORK_NAMES = ("tdev feat th temb st mod lens lens_plain row_start rowmap step_cond text_c text_u tx_a tx_b tx_h1 grn_part uc acat h c1 x "
-                  "pred xn q k ao vt ffh in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps "
+                  "pred xn q k ao vt ffh a8 a8s in_cond y y_mid out_buf traj_buf in_mask in_text cat2 skips pred_all mod_rows it_t it_cfg it_steps "
                   "it_idx").split()
 
 

@@ -8,6 +8,18 @@ namespace f5 {
 
 struct e4m3_t { unsigned char v; };   // one OCP e4m3fn code (never fnuz)
 
+// A GEMM operand of F5_PREC_F8 as a value: rows of e4m3 codes `pitch` bytes apart and one e8m0 scale byte per row (an activation's rows, a
+// weight's output channels).  Empty where there is none.  (The row quantisers that fill one are in quant8.h.)
+struct Rows8 {
+    unsigned char* codes = nullptr;
+    unsigned char* scales = nullptr;
+    int pitch = 0;
+    explicit operator bool() const { return codes != nullptr; }
+    const e4m3_t* e4m3() const { return reinterpret_cast<const e4m3_t*>(codes); }
+    Rows8 from_row(size_t r) const { return {codes + r * pitch, scales + r, pitch}; }   // the rows from r on
+    Rows8 at_pitch(int p) const { return {codes, scales, p}; }                          // the same storage as rows of p codes
+};
+
 // 2^(b - 127) of an e8m0 scale byte b (1 .. 254: a normal f32)
 __host__ __device__ __forceinline__ float e8m0_value(unsigned b) {
     const unsigned bits = b << 23;

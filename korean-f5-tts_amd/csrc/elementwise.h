@@ -170,6 +170,27 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
                                                              const int2* __restrict__ rowmap, int planar, int wt) {
     layernorm_body<TO, true>(x, ldx, out, ldo, R, D, eps, A, Bv, vec_stride, 0, 1, pf, m_limit, planar, wt, rowmap);
 }
+// One AdaLN LayerNorm launch, out = LN(x) (1 + scale) + shift over R dense rows of D: what every output form of it is given.  Batch row
+// b's vectors are at scale / shift + b * vec_stride (0: shared); row r belongs to batch row r / rows_per_batch, or -- rowmap: a packed
+// batch whose batch rows have their own vectors -- to rowmap[r].x.  pf: weights to prefetch; m_limit: the device row count of a packed batch.
+struct AdaLN {
+    const float *x, *scale, *shift;
+    int R, D, vec_stride, rows_per_batch;
+    float eps = 1e-6f;
+    const int2* rowmap = nullptr;
+    Prefetch pf{};
+    const int* m_limit = nullptr;
+};
+// ... into rows of TO (planar: pre-split f32 rows; wt: write-through stores).  The e4m3 form is quant8.h's overload.
+template <typename TO> inline void launch_adaln_norm(hipStream_t s, const AdaLN& a, TO* out, int planar, int wt) {
+    const dim3 grid((a.R + 3) / 4), block(256);
+    if (a.rowmap)
+        hipLaunchKernelGGL((layernorm_rows_kernel<TO>), grid, block, 0, s, a.x, a.D, out, a.D, a.R, a.D, a.eps, a.scale, a.shift, a.vec_stride, a.pf,
+                           a.m_limit, a.rowmap, planar, wt);
+    else
+        hipLaunchKernelGGL((layernorm_kernel<TO>), grid, block, 0, s, a.x, a.D, out, a.D, a.R, a.D, a.eps, a.scale, a.shift, a.vec_stride,
+                           a.rows_per_batch, 1, a.pf, a.m_limit, planar, wt);
+}
 
 // x_transformers.RMSNorm as used by UNetT (unett.py:154,168,185): F.normalize(x, dim=-1) * sqrt(D) * g
 template <typename TO>

@@ -20,11 +20,11 @@
 // templates over the MFMA operand type (engine_impl.h), instantiated in engine_{bf16,f16,f32}.hip.
 #include "engine_types.h"
 
-// precision dispatch of one EngineOps<T> member
-#define F5_OPS(e, CALL)                                                  \
-    ((e)->cfg.precision == F5_PREC_BF16  ? EngineOps<bf16_t>::CALL       \
-     : ((e)->cfg.precision == F5_PREC_F16 || (e)->cfg.precision == F5_PREC_F16P || (e)->cfg.precision == F5_PREC_F8) ? EngineOps<f16_t>::CALL        \
-                                         : EngineOps<float>::CALL)
+// precision dispatch of one EngineOps<T> member (prec_info, internal.h)
+#define F5_OPS(e, CALL)                                                             \
+    (prec_info((e)->cfg.precision).elem == PE_BF16  ? EngineOps<bf16_t>::CALL       \
+     : prec_info((e)->cfg.precision).elem == PE_F16 ? EngineOps<f16_t>::CALL        \
+                                                    : EngineOps<float>::CALL)
 
 // ------------------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -64,9 +64,8 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     if (c->heads <= 0 || (c->heads * 64) % 64 != 0 || c->depth <= 0) return fail(F5_EINVAL, "bad heads/depth");
     if (c->mel_dim % 4 || c->text_dim % 4 || c->ff_dim % 8) return fail(F5_EINVAL, "mel_dim/text_dim %% 4, ff_dim %% 8 required");
     if ((2 * c->mel_dim + c->text_dim) % 4) return fail(F5_EINVAL, "2*mel_dim + text_dim must be a multiple of 4");
-    if (c->precision != F5_PREC_F32 && c->precision != F5_PREC_BF16 && c->precision != F5_PREC_F16 && c->precision != F5_PREC_F16X3 &&
-        c->precision != F5_PREC_F16P && c->precision != F5_PREC_F8)
-        return fail(F5_EINVAL, "bad precision");
+    const PrecInfo prec = prec_info(c->precision);
+    if (!prec.valid) return fail(F5_EINVAL, "bad precision");
     if (c->precision == F5_PREC_F16X3 && c->ff_dim % 32)
         return fail(F5_EINVAL, "F5_PREC_F16X3 needs ff_dim %% 32 == 0 (whole 32-element blocks of the split operand layout; got %d)", c->ff_dim);
     if (c->backbone != F5_BACKBONE_DIT && c->backbone != F5_BACKBONE_UNETT && c->backbone != F5_BACKBONE_MMDIT) return fail(F5_EINVAL, "bad backbone");
@@ -102,9 +101,9 @@ extern "C" int f5_create(const f5_config* c, f5_engine** out) {
     e->kin_pad = round_up(e->kin, 64);  // whole 128-byte K-tiles for the LDS-DMA GEMM (pad columns stay zero)
     // per block 6 D (DiT), or x's 6 D then c's 6 D -- 2 D in the last, context_pre_only block -- (MMDiT); then the final norm's 2 D
     e->modN = (mmdit ? 12 * c->depth - 2 : 6 * c->depth + 2) * c->dim;
-    e->split16 = c->precision == F5_PREC_F16X3;
-    e->f8 = c->precision == F5_PREC_F8;
-    e->io_split = c->precision == F5_PREC_F16P || e->f8;
+    e->split16 = prec.split16;
+    e->f8 = prec.f8;
+    e->io_split = prec.io_split;
     e->sw = read_switches(*c);
     if (!valid_len_bucket(e->sw.len_bucket)) {
         const int g = e->sw.len_bucket;

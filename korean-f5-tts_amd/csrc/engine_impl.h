@@ -48,50 +48,24 @@ static hipError_t egemm(const f5_engine* e, hipStream_t s, const T* A, int lda, 
     return launch_gemm<T>(s, A, lda, W, ldw, M, N, K, epi, {ops, -1, m_limit, m_hint});
 }
 
-// W [N, K] f32 -> T [N, round_up(K, 8)]
-// q8 (F5_PREC_F8, a block GEMM's weight): e4m3 codes + one scale byte per output channel, quantised from the f32 master (quant8.h); K
-// padding is zero codes; no 16-bit copy is kept (L->w stays null)
-template <typename T, bool BB = false>
-static int pack_linear(f5_engine* e, hipStream_t s, const std::string& wname, const std::string& bname, int N, int K,
-                       LinW<T>* L, int n_pad = 0, bool q8 = false) {
-    const Tensor *w = nullptr, *b = nullptr;
-    CHK(need(e->ws, wname, {N, K}, &w));
-    const int Np = n_pad ? n_pad : N;
-    L->N = Np;
-    L->K = K;
-    L->ldw = q8 ? round_up(K, GEMM_ROW_BYTES) : round_up(K, 64);
-    if (q8) {
-        if (Np != N || K % 4) return fail(F5_EINVAL, "F5_PREC_F8: weight '%s' [%d, %d] cannot be packed as e4m3 rows", wname.c_str(), N, K);
-        CHK(dev_alloc(e, &L->w8, (size_t)N * L->ldw));
-        CHK(dev_alloc(e, &L->s8, (size_t)round_up(N, 4)));
-        launch_quant_rows_e4m3<float>(s, w->p, K, N, K, L->w8, L->ldw, L->ldw, L->s8, nullptr);
-    } else {
-        CHK(dev_alloc(e, &L->w, (size_t)Np * L->ldw));
-        hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)Np * L->ldw)), dim3(256), 0, s, w->p, K, N, K, L->w, L->ldw, Np);
-    }
-    L->b = nullptr;
-    if (!bname.empty()) {
-        CHK(need(e->ws, bname, {N}, &b));
-        CHK(dev_alloc(e, &L->b, (size_t)Np));
-        hipLaunchKernelGGL((cast_pad_kernel<float>), dim3(ew_blocks(Np)), dim3(256), 0, s, b->p, N, 1, N, L->b, Np, 1);
-    }
-    HIPCHK(hipGetLastError());
-    if (q8) return F5_OK;
-    return maybe_split_weight<T, BB>(e, s, L->w, (size_t)Np * L->ldw);
-}
-
-// concatenates several [Ni, K] linears row-wise into one [sum Ni, ldw] operand (+ bias)
-template <typename T, bool BB = false>
-static int pack_concat(f5_engine* e, hipStream_t s, const std::vector<std::string>& pfx, int Ni, int K, LinW<T>* L,
-                       bool bias = true, bool q8 = false) {
+// What a packed GEMM weight is for; with the engine's precision it decides the operand form.  Backbone: one of the backbone's own GEMM
+// weights, split under F5_PREC_F16X3 (maybe_split_weight).  Block: one of the four GEMMs of a block -- a backbone weight, and under
+// F5_PREC_F8 e4m3 codes + one scale byte per output channel, quantised from the f32 master (quant8.h), with no 16-bit copy (L->w stays null).
+enum class WRole { Other, Backbone, Block };
+// The linears pfx[i] + ".weight" [Ni, K] (+ ".bias"), concatenated row-wise, as one operand L [n Ni, ldw]: rows of T zero-padded to
+// round_up(K, 64) elements, or e4m3 rows zero-padded to whole K-tiles.
+template <typename T, WRole R = WRole::Other>
+static int pack_concat(f5_engine* e, hipStream_t s, const std::vector<std::string>& pfx, int Ni, int K, LinW<T>* L, bool bias = true) {
     const int n = (int)pfx.size();
+    const bool q8 = R == WRole::Block && e->f8;
     L->N = n * Ni;
     L->K = K;
     L->ldw = q8 ? round_up(K, GEMM_ROW_BYTES) : round_up(K, 64);
-    if (q8) {   // (pack_linear: a channel's scale is its own row's, so the parts quantise independently)
-        if (K % 4 || Ni % 4) return fail(F5_EINVAL, "F5_PREC_F8: a fused weight [%d x %d, %d] cannot be packed as e4m3 rows", n, Ni, K);
-        CHK(dev_alloc(e, &L->w8, (size_t)L->N * L->ldw));
-        CHK(dev_alloc(e, &L->s8, (size_t)L->N));
+    if (q8) {   // (a channel's scale is its own row's, so the parts quantise independently; EpiScale8::col reads the scales as words)
+        if (K % 4 || (n > 1 && Ni % 4)) return fail(F5_EINVAL, "F5_PREC_F8: weight '%s' [%d x %d, %d] cannot be packed as e4m3 rows", pfx[0].c_str(), n, Ni, K);
+        L->q.pitch = L->ldw;
+        CHK(dev_alloc(e, &L->q.codes, (size_t)L->N * L->ldw));
+        CHK(dev_alloc(e, &L->q.scales, (size_t)round_up(L->N, 4)));
     } else {
         CHK(dev_alloc(e, &L->w, (size_t)L->N * L->ldw));
     }
@@ -101,7 +75,7 @@ static int pack_concat(f5_engine* e, hipStream_t s, const std::vector<std::strin
         const Tensor *w = nullptr, *b = nullptr;
         CHK(need(e->ws, pfx[i] + ".weight", {Ni, K}, &w));
         if (q8)
-            launch_quant_rows_e4m3<float>(s, w->p, K, Ni, K, L->w8 + (size_t)i * Ni * L->ldw, L->ldw, L->ldw, L->s8 + (size_t)i * Ni, nullptr);
+            launch_quant_rows_e4m3<float>(s, w->p, K, Ni, K, L->q.from_row((size_t)i * Ni), nullptr);
         else
             hipLaunchKernelGGL((cast_pad_kernel<T>), dim3(ew_blocks((long)Ni * L->ldw)), dim3(256), 0, s, w->p, K, Ni, K,
                                L->w + (size_t)i * Ni * L->ldw, L->ldw, Ni);
@@ -112,12 +86,13 @@ static int pack_concat(f5_engine* e, hipStream_t s, const std::vector<std::strin
     }
     HIPCHK(hipGetLastError());
     if (q8) return F5_OK;
-    return maybe_split_weight<T, BB>(e, s, L->w, (size_t)L->N * L->ldw);
+    return maybe_split_weight<T, R != WRole::Other>(e, s, L->w, (size_t)L->N * L->ldw);
 }
-
-// the backbone's own GEMM weights (split in F5_PREC_F16X3)
-template <typename T, typename... Args> static int pack_linear_bb(Args&&... args) { return pack_linear<T, true>(std::forward<Args>(args)...); }
-template <typename T, typename... Args> static int pack_concat_bb(Args&&... args) { return pack_concat<T, true>(std::forward<Args>(args)...); }
+// one linear `name`.weight [N, K] (+ .bias)
+template <typename T, WRole R = WRole::Other>
+static int pack_linear(f5_engine* e, hipStream_t s, const std::string& name, int N, int K, LinW<T>* L, bool bias = true) {
+    return pack_concat<T, R>(e, s, std::vector<std::string>{name}, N, K, L, bias);
+}
 
 static int copy_vec(f5_engine* e, hipStream_t s, const std::string& name, std::initializer_list<int64_t> shape,
                     float** out) {
@@ -168,12 +143,12 @@ template <typename T>
 static int pack_stream(f5_engine* e, hipStream_t s, StreamW<T>& w, const std::string& at, const std::string& sfx, const std::string& out,
                        const std::string& ff, const std::string& norm, bool pre_only) {
     const int D = e->cfg.dim, F = e->cfg.ff_dim, inner = e->inner;
-    const bool q8 = e->f8;   // F5_PREC_F8: these four are the e4m3 operands
-    CHK(pack_concat_bb<T>(e, s, std::vector<std::string>{at + ".to_q" + sfx, at + ".to_k" + sfx, at + ".to_v" + sfx}, inner, D, &w.qkv, true, q8));
+    constexpr WRole blk = WRole::Block;   // (the four e4m3 operands of F5_PREC_F8)
+    CHK((pack_concat<T, blk>(e, s, {at + ".to_q" + sfx, at + ".to_k" + sfx, at + ".to_v" + sfx}, inner, D, &w.qkv)));
     if (!pre_only) {
-        CHK(pack_linear_bb<T>(e, s, out + ".weight", out + ".bias", D, inner, &w.out, 0, q8));
-        CHK(pack_linear_bb<T>(e, s, ff + ".ff.0.0.weight", ff + ".ff.0.0.bias", F, D, &w.ff1, 0, q8));
-        CHK(pack_linear_bb<T>(e, s, ff + ".ff.2.weight", ff + ".ff.2.bias", D, F, &w.ff2, 0, q8));
+        CHK((pack_linear<T, blk>(e, s, out, D, inner, &w.out)));
+        CHK((pack_linear<T, blk>(e, s, ff + ".ff.0.0", F, D, &w.ff1)));
+        CHK((pack_linear<T, blk>(e, s, ff + ".ff.2", D, F, &w.ff2)));
     }
     if (e->cfg.options & F5_OPT_QK_RMSNORM) {
         CHK(copy_vec(e, s, norm + "q_norm.weight", {64}, &w.qn));
@@ -202,8 +177,8 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     KCHK();
     CHK(copy_vec(e, s, "aux.time_freqs", {128}, &P.time_freqs));
     // time MLP
-    CHK(pack_linear<float>(e, s, "time_embed.time_mlp.0.weight", "time_embed.time_mlp.0.bias", D, 256, &P.time0));
-    CHK(pack_linear<float>(e, s, "time_embed.time_mlp.2.weight", "time_embed.time_mlp.2.bias", D, D, &P.time2));
+    CHK(pack_linear<float>(e, s, "time_embed.time_mlp.0", D, 256, &P.time0));
+    CHK(pack_linear<float>(e, s, "time_embed.time_mlp.2", D, D, &P.time2));
     // text encoder
     CHK(copy_vec(e, s, "text_embed.text_embed.weight", {c.text_num_embeds + 1, Dt}, &P.E));
     CHK(reg_target(e, "text_embed.text_embed.weight", false, c.text_num_embeds + 1, Dt, Dt, P.E, MK_F32));
@@ -226,8 +201,8 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         CHK(copy_vec(e, s, p + ".norm.bias", {Dt}, &tb.lnb));
         CHK(copy_vec(e, s, p + ".grn.gamma", {1, 1, 2 * Dt}, &tb.gamma));
         CHK(copy_vec(e, s, p + ".grn.beta", {1, 1, 2 * Dt}, &tb.beta));
-        CHK(pack_linear<float>(e, s, p + ".pwconv1.weight", p + ".pwconv1.bias", 2 * Dt, Dt, &tb.pw1));
-        CHK(pack_linear<float>(e, s, p + ".pwconv2.weight", p + ".pwconv2.bias", Dt, 2 * Dt, &tb.pw2));
+        CHK(pack_linear<float>(e, s, p + ".pwconv1", 2 * Dt, Dt, &tb.pw1));
+        CHK(pack_linear<float>(e, s, p + ".pwconv2", Dt, 2 * Dt, &tb.pw2));
         CHK(reg_target(e, p + ".dwconv.weight", false, Dt, 7, 7, tb.dwk, MK_TAPS));
         CHK(reg_target(e, p + ".dwconv.bias", false, 1, Dt, Dt, tb.dwb, MK_F32));
         CHK(reg_target(e, p + ".norm.weight", false, 1, Dt, Dt, tb.lnw, MK_F32));
@@ -238,7 +213,8 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
         CHK(reg_linear_f32(e, p + ".pwconv2", tb.pw2, Dt, 2 * Dt));
     }
     // input embedding
-    CHK(pack_linear_bb<T>(e, s, in_proj_n + ".weight", in_proj_n + ".bias", D, e->kin, &P.in_proj));
+    constexpr WRole bb = WRole::Backbone;
+    CHK((pack_linear<T, bb>(e, s, in_proj_n, D, e->kin, &P.in_proj)));
     auto zlo = [&](int bit, LinW<T>& L) {   // diagnostic F5_X3_ABLATE: plain f16 weights (lo halves zeroed) for a class
         if (e->sw.x3_ablate & bit) zero_lo_planar(s, L.w, (size_t)L.N * L.ldw);
     };
@@ -286,7 +262,7 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
             CHK(copy_vec(e, s, p + ".1.g", {D}, &b.norm1_g));
             CHK(copy_vec(e, s, p + ".3.g", {D}, &b.norm2_g));
             if (i >= c.depth / 2 && e->ws.get(p + ".0.weight")) {
-                CHK(pack_linear_bb<T>(e, s, p + ".0.weight", "", D, 2 * D, &b.skip));
+                CHK((pack_linear<T, bb>(e, s, p + ".0", D, 2 * D, &b.skip, false)));
                 zlo(512, b.skip);   // diagnostic: the skip projection with plain f16 weights
                 HIPCHK(hipGetLastError());
             }
@@ -320,14 +296,14 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     } else {
         CHK(copy_vec(e, s, "norm_out.g", {D}, &P.norm_out_g));
     }
-    CHK(pack_linear_bb<T>(e, s, "proj_out.weight", "proj_out.bias", mel, D, &P.proj_out));
+    CHK((pack_linear<T, bb>(e, s, "proj_out", mel, D, &P.proj_out)));
     if (c.options & F5_OPT_LONG_SKIP) {
-        CHK(pack_linear_bb<T>(e, s, "long_skip_connection.weight", "", D, 2 * D, &P.long_skip));
-        if (e->io_split) CHK((pack_linear<float, true>(e, s, "long_skip_connection.weight", "", D, 2 * D, &P.long_skip_f)));
+        CHK((pack_linear<T, bb>(e, s, "long_skip_connection", D, 2 * D, &P.long_skip, false)));
+        if (e->io_split) CHK((pack_linear<float, bb>(e, s, "long_skip_connection", D, 2 * D, &P.long_skip_f, false)));
     }
     if (e->io_split) {   // F5_PREC_F16P: the input / output layers once more, as split-planar f32 operands
-        CHK((pack_linear<float, true>(e, s, in_proj_n + ".weight", in_proj_n + ".bias", D, e->kin, &P.in_proj_f)));
-        CHK((pack_linear<float, true>(e, s, "proj_out.weight", "proj_out.bias", mel, D, &P.proj_out_f)));
+        CHK((pack_linear<float, bb>(e, s, in_proj_n, D, e->kin, &P.in_proj_f)));
+        CHK((pack_linear<float, bb>(e, s, "proj_out", mel, D, &P.proj_out_f)));
         P.conv_kp_f = round_up(31 * cpg, GEMM_ROW_BYTES / (int)sizeof(float));
         for (int j = 0; j < 2; ++j) {
             const std::string p = conv_n + std::to_string(j * 2);
@@ -347,6 +323,8 @@ template <typename T> static int finalize_t(f5_engine* e, Packed<T>& P, hipStrea
     HIPCHK(hipGetLastError());
     return F5_OK;
 }
+// F5_PREC_F8: the code bytes one row of Work::a8 is carved with -- the widest K of the four block GEMMs
+static int a8_pitch(const f5_engine* e) { return std::max(std::max(e->cfg.dim, e->cfg.ff_dim), e->inner); }
 template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Work<T>& w, int B, int N, int S) {
     const size_t NT = (size_t)std::max(e->res_nt, 1);
     const f5_config& c = e->cfg;
@@ -392,10 +370,11 @@ template <typename T> static size_t carve_into(const f5_engine* e, Arena& a, Wor
     w.ao = a.take<T>(jrows * e->inner);
     w.vt = a.take<T>(Bp * c.heads * 64 * w.Npad);
     w.ffh = a.take<T>(rows * F);
-    w.a8 = w.a8s = nullptr;
+    w.a8 = Rows8{};
     if (e->f8) {   // F5_PREC_F8 only: every other precision's plan is what it was
-        w.a8 = a.take<unsigned char>(rows * std::max(std::max(D, F), (size_t)e->inner));
-        w.a8s = a.take<unsigned char>(rows + 16);
+        w.a8.pitch = a8_pitch(e);
+        w.a8.codes = a.take<unsigned char>(rows * w.a8.pitch);
+        w.a8.scales = a.take<unsigned char>(rows + 16);
     }
     w.in_cond = a.take<float>((size_t)B * N * mel);
     w.y = a.take<float>((size_t)B * N * mel);
@@ -535,6 +514,23 @@ static int run_text_embed(f5_engine* e, Work<T>& w, const int64_t* text, int B, 
 }
 
 // ---------------------------------------------------------------------------------- stages shared by the three backbones
+// The backbone GEMMs the stages run through FwdCtx::mul, by class.  A class fixes, in this one place: its F5_X3_ABLATE bit (0: no hook);
+// whether its A operand arrives pre-split under F5_PREC_F16X3; and, where its weight holds e4m3 rows (F5_PREC_F8: the first four), whether
+// the AdaLN LayerNorm in front of it wrote the e4m3 A operand (a_from_ln) or the stand-alone row quantiser runs first.
+enum class GemmClass { QKV, OutProj, FF1, FF2, ProjOut, LongSkip, UNetTSkip };
+struct GemmClassInfo { int ablate_bit; bool a_presplit, a_from_ln; };
+constexpr GemmClassInfo gemm_class(GemmClass c) {
+    switch (c) {
+        case GemmClass::QKV: return {1, true, true};
+        case GemmClass::OutProj: return {8, true, false};
+        case GemmClass::FF1: return {16, true, true};
+        case GemmClass::FF2: return {32, true, false};
+        case GemmClass::ProjOut: return {256, true, false};
+        case GemmClass::LongSkip: return {0, false, false};
+        case GemmClass::UNetTSkip: return {512, true, false};   // (launch_cat2 writes the concat pre-split, so that the projection runs on pre-split operands too)
+    }
+    return {0, false, false};
+}
 // What the stages of one forward share: the engine, the stream, the geometry and (DiT) the tables of a packed batch.
 struct FwdCtx {
     f5_engine* e;
@@ -542,6 +538,7 @@ struct FwdCtx {
     int B, Bp, N, rows;    // N: tokens per batch row (UNetT blocks: the frames + the time token); rows = Bp * N: launch geometry, the padded batch
     const int* lens_dev;   // per-batch-row lengths, or null
     RowPack pk;            // packed variable-length batch (rows present = *pk.rows_dev); empty: the padded batch as it is
+    Rows8 a8;              // F5_PREC_F8 (the DiT's blocks): Work::a8, where the e4m3 A operand of the block GEMM about to run is written; else empty
     const int* ml() const { return pk.rows_dev; }              // device row count of a packed batch, or null
     int mh() const { return pk ? (int)pk.rows_host : 0; }      // rows expected (the call's own lengths): tile choice only
     int pl() const { return e->split16 ? 1 : 0; }              // F5_PREC_F16X3: xn / ao / ffh are written pre-split (the A operands of the block GEMMs)
@@ -549,34 +546,39 @@ struct FwdCtx {
     // where a kernel's whole output would otherwise sit dirty in L2 when it ends (the condition of the weight prefetch)
     int wt(int bit) const { return rows <= 4096 && (e->sw.store_wt & bit) ? 1 : 0; }
     double gflops(double n, double k) const { return 2.0 * (pk ? pk.rows_host : (double)rows) * n * k; }
-    // one backbone GEMM over all rows, as a profiled launch
-    // F5_PREC_F8, a block GEMM (L holds e4m3 codes): the A operand is the codes in a8 with the row scales a8s -- written by the AdaLN
-    // LayerNorm's e4m3 form (adaln_norm) or by quant8 below -- and A itself is not read
-    template <typename T, typename Epi> int gemm(const T* A, int lda, const LinW<T>& L, int n, int k, const Epi& epi, bool a_split = false) const {
+    // One backbone GEMM of class c over all rows, A [rows, L.K] times L into epi, as a profiled launch behind the class's diagnostic hook.
+    // The weight's form is the product's: L.q -- e4m3 rows, the A operand in a8 at the pitch of L.K, left there by the LayerNorm or
+    // quantised here from the 16-bit rows a.p (attention output, FF hidden) by the stand-alone launch -- else the rows of egemm.
+    template <typename T, typename Epi> int mul(GemmClass c, ARows<T> a, const LinW<T>& L, const Epi& epi) const {
+        const GemmClassInfo g = gemm_class(c);
+        ablate(g.ablate_bit, a.p, L.K);
         if constexpr (std::is_same_v<T, f16_t>) {
-            if (e->f8 && L.w8) {
-                HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] {
+            if (L.q) {
+                if (!g.a_from_ln) {
+                    const Rows8 q = a8.at_pitch(L.K);
+                    HIPCHK(e->prof.timed(PC_MISC, s, [&] {
+                        launch_quant_rows_e4m3<T>(s, a.p, L.K, rows, L.K, q, ml());
+                        return hipGetLastError();
+                    }));
+                    a = ARows<T>(q);
+                }
+                if (!a.q) return fail(F5_ESTATE, "F5_PREC_F8: a block GEMM was not handed its e4m3 A operand");
+                HIPCHK(e->prof.timed(PC_GEMM, s, gflops(L.N, L.K), [&] {
                     GemmOpts o{GemmOperands::Plain, -1, ml(), mh()};
-                    o.a_scale = a8s;
-                    o.w_scale = L.s8;
-                    return launch_gemm<e4m3_t>(s, reinterpret_cast<const e4m3_t*>(a8), k, reinterpret_cast<const e4m3_t*>(L.w8), L.ldw, rows, n, k, epi, o);
+                    o.a_scale = a.q.scales;
+                    o.w_scale = L.q.scales;
+                    return launch_gemm<e4m3_t>(s, a.q.e4m3(), a.q.pitch, L.q.e4m3(), L.q.pitch, rows, L.N, L.K, epi, o);
                 }));
                 return F5_OK;
             }
         }
-        HIPCHK(e->prof.timed(PC_GEMM, s, gflops(n, k), [&] { return egemm<T>(e, s, A, lda, L.w, L.ldw, rows, n, k, epi, ml(), mh(), a_split); }));
+        HIPCHK(e->prof.timed(PC_GEMM, s, gflops(L.N, L.K), [&] {
+            return egemm<T>(e, s, a.p, L.K, L.w, L.ldw, rows, L.N, L.K, epi, ml(), mh(), g.a_presplit && pl());
+        }));
         return F5_OK;
     }
-    // F5_PREC_F8: the stand-alone row quantiser on a block GEMM's 16-bit A operand [rows, k] (attention output, FF hidden) into a8 / a8s
-    template <typename T> int quant8(const T* A, int k) const {
-        if constexpr (std::is_same_v<T, f16_t>) {
-            HIPCHK(e->prof.timed(PC_MISC, s, [&] {
-                launch_quant_rows_e4m3<T>(s, A, k, rows, k, a8, k, k, a8s, ml());
-                return hipGetLastError();
-            }));
-        }
-        return F5_OK;
-    }
+    // the operand an AdaLN LayerNorm in front of a block's QKV / FF1 writes: e4m3 rows of D codes in a8 where there is one, else the rows xn
+    template <typename T> ARows<T> ln_operand(T* xn) const { return a8 ? ARows<T>(a8.at_pitch(e->cfg.dim)) : ARows<T>(xn); }
     // diagnostic F5_X3_ABLATE: the class's A operand [rows, k] as plain f16 (lo halves zeroed).  The hooks of the shared stages act on the
     // x stream only: finalize_t never ablates the MMDiT text stream's weights, so the text stream's context turns them off (x3 = false)
     // and its activations stay whole too.
@@ -584,7 +586,6 @@ struct FwdCtx {
     template <typename T> void ablate(int bit, T* a, int k) const {
         if (x3 && (e->sw.x3_ablate & bit)) zero_lo_planar(s, a, (size_t)rows * k);
     }
-    unsigned char *a8 = nullptr, *a8s = nullptr;   // F5_PREC_F8: Work::a8 / a8s
 };
 
 // Input embedding: [y, cond, text] packed as rows of U, the input projection, and the conv position embedding (two grouped convs, the second
@@ -640,33 +641,16 @@ static int embed_input(const FwdCtx& f, Work<T>& w, const float* y, const float*
     return F5_OK;
 }
 
-// AdaLN LayerNorm of the residual stream x into out (rows of T, or pre-split f32 rows): out = LN(x) * (1 + scale) + shift.  mod_stride:
-// distance between batch rows' vectors (0: shared).  A packed batch with its own vectors per batch row finds them through the rowmap.
-// pf: weights to prefetch from the launch (see layernorm_kernel).
+// AdaLN LayerNorm of the residual stream x into out: out = LN(x) * (1 + scale) + shift, as rows of TO (planar: pre-split f32 rows) or as
+// the e4m3 operand out.q.  mod_stride: distance between batch rows' vectors (0: shared).  A packed batch with its own vectors per batch
+// row finds them through the rowmap.  pf: weights to prefetch from the launch (see layernorm_kernel).
 template <typename TO>
-static hipError_t adaln_norm(const FwdCtx& f, const float* x, TO* out, const float* scale, const float* shift, int mod_stride, const Prefetch& pf,
-                             int planar) {
-    const int D = f.e->cfg.dim, rows = f.rows;
-    if constexpr (std::is_same_v<TO, f16_t>) {
-        if (f.e->f8)   // F5_PREC_F8: a block's LayerNorm feeds QKV / FF1 -- e4m3 codes and row scales straight from the f32 value, `out` unused
-            return f.e->prof.timed(PC_LN, f.s, [&] {
-                e4m3_t* codes = reinterpret_cast<e4m3_t*>(f.a8);
-                if (f.pk && mod_stride != 0)
-                    hipLaunchKernelGGL(layernorm_rows_q8_kernel, dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, codes, D, rows, D, 1e-6f, scale, shift,
-                                       mod_stride, pf, f.ml(), f.pk.rowmap, f.a8s);
-                else
-                    hipLaunchKernelGGL(layernorm_q8_kernel, dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, codes, D, rows, D, 1e-6f, scale, shift,
-                                       mod_stride, f.N, 1, pf, f.ml(), f.a8s);
-                return hipGetLastError();
-            });
-    }
+static hipError_t adaln_norm(const FwdCtx& f, const float* x, const ARows<TO>& out, const float* scale, const float* shift, int mod_stride,
+                             const Prefetch& pf, int planar) {
+    const AdaLN a{x, scale, shift, f.rows, f.e->cfg.dim, mod_stride, f.N, 1e-6f, f.pk && mod_stride != 0 ? f.pk.rowmap : nullptr, pf, f.ml()};
     return f.e->prof.timed(PC_LN, f.s, [&] {
-        if (f.pk && mod_stride != 0)
-            hipLaunchKernelGGL((layernorm_rows_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, out, D, rows, D, 1e-6f, scale, shift,
-                               mod_stride, pf, f.ml(), f.pk.rowmap, planar, f.wt(F5_WT_LN));
-        else
-            hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, f.s, x, D, out, D, rows, D, 1e-6f, scale, shift,
-                               mod_stride, f.N, 1, pf, f.ml(), planar, f.wt(F5_WT_LN));
+        if (out.q) launch_adaln_norm(f.s, a, out.q);
+        else launch_adaln_norm(f.s, a, out.p, planar, f.wt(F5_WT_LN));
         return hipGetLastError();
     });
 }
@@ -687,21 +671,20 @@ template <typename T, typename Fn> static int with_attn_operands(const f5_engine
 // every head rotated (the MMDiT's joint attention).  With qk_norm the epilogue leaves q / k raw and the norm-rope launch follows:
 // RMSNorm comes BEFORE the rotary embedding (modules.py:481-497, 588-608).
 template <typename T, typename Place>
-static int qkv_project(const FwdCtx& f, Work<T>& w, T* xn, const StreamW<T>& sw, bool qk_norm, const Place& place) {
+static int qkv_project(const FwdCtx& f, Work<T>& w, const ARows<T>& xn, const StreamW<T>& sw, bool qk_norm, const Place& place) {
     constexpr bool joint = std::is_same_v<Place, QKVJointLayout>;
     f5_engine* e = f.e;
     Packed<T>& P = packed<T>(e);
     const f5_config& c = e->cfg;
-    const int D = c.dim, inner = e->inner, H = c.heads;
+    const int H = c.heads;
     const int pe_heads = joint || c.pe_attn_head < 0 ? H : c.pe_attn_head;
     int L = f.N, off = 0;
     if constexpr (joint) L = place.Lseq, off = place.off;
-    f.ablate(1, xn, D);
     return with_attn_operands<T>(e, w, qk_norm, [&](auto* q, auto* k, auto* vt) -> int {
         using TO = std::remove_pointer_t<decltype(q)>;
-        CHK(f.gemm(xn, D, sw.qkv, 3 * inner, D,
-                   EpiQKV<TO, joint>{q, k, vt, sw.qkv.b, P.rope_frag, f.N, w.Npad, H, qk_norm ? 0 : pe_heads,
-                                     qk_norm ? 1.0f : attention_q_scale<TO>(), f.pk.rowmap, place}, f.pl()));
+        CHK(f.mul(GemmClass::QKV, xn, sw.qkv,
+                  EpiQKV<TO, joint>{q, k, vt, sw.qkv.b, P.rope_frag, f.N, w.Npad, H, qk_norm ? 0 : pe_heads,
+                                    qk_norm ? 1.0f : attention_q_scale<TO>(), f.pk.rowmap, place}));
         if (qk_norm)
             HIPCHK(e->prof.timed(PC_MISC, f.s, [&] {
                 return launch_qknorm_rope<TO>(f.s, q, k, sw.qn, sw.kn, P.rope_cos, P.rope_sin, f.Bp, H, f.N, L, off, pe_heads, attention_q_scale<TO>(), 1e-6f);
@@ -731,41 +714,34 @@ template <typename T> static int attend(const FwdCtx& f, Work<T>& w, bool qk_nor
 
 // Out-projection of a stream's attention rows ao with the caller's residual epilogue.
 template <typename T, typename Epi> static int out_project(const FwdCtx& f, T* ao, const StreamW<T>& sw, const Epi& out_epi) {
-    const int D = f.e->cfg.dim, inner = f.e->inner;
-    f.ablate(8, ao, inner);
-    if (f.e->f8) CHK(f.quant8(ao, inner));
-    return f.gemm(ao, inner, sw.out, D, inner, out_epi, f.pl());
+    return f.mul(GemmClass::OutProj, ARows<T>(ao), sw.out, out_epi);
 }
 
-// Attention sub-block of a backbone with one stream, on the normed stream w.xn: QKV projection, attention, out-projection.
+// Attention sub-block of a backbone with one stream, on its normed rows xn: QKV projection, attention, out-projection.
 template <typename T, typename Epi>
-static int attention_block(const FwdCtx& f, Work<T>& w, const StreamW<T>& sw, bool qk_norm, const Epi& out_epi) {
+static int attention_block(const FwdCtx& f, Work<T>& w, const ARows<T>& xn, const StreamW<T>& sw, bool qk_norm, const Epi& out_epi) {
     // (a packed batch masks its keys whatever attn_mask_enabled says: a length-bucket plan packs utterances that fill their whole length,
     //  for which masked and unmasked attention coincide)
     const int* attn_lens = ((f.e->cfg.attn_mask_enabled || f.pk) && f.lens_dev) ? f.lens_dev : nullptr;
-    CHK(qkv_project<T>(f, w, w.xn, sw, qk_norm, QKVOwnLayout{}));
+    CHK(qkv_project<T>(f, w, xn, sw, qk_norm, QKVOwnLayout{}));
     CHK(attend<T>(f, w, qk_norm, f.N, attn_lens, f.B, f.lens_dev));
     return out_project<T>(f, w.ao, sw, out_epi);
 }
 
 // Feed-forward pair on a stream's normed rows sb.xn: FF1 with GELU(tanh) into sb.ffh, FF2 with the caller's residual epilogue.
 template <typename T, typename Epi> static int ff_block(const FwdCtx& f, const StreamBuf<T>& sb, const StreamW<T>& sw, const Epi& out_epi) {
-    const int D = f.e->cfg.dim, F = f.e->cfg.ff_dim, pl = f.pl();
-    f.ablate(16, sb.xn, D);
-    CHK(f.gemm(sb.xn, D, sw.ff1, F, D, EpiStore<T>{sb.ffh, F, sw.ff1.b, F5_ACT_GELU_TANH, pl, f.wt(F5_WT_STORE16)}, pl));
-    f.ablate(32, sb.ffh, F);
-    if (f.e->f8) CHK(f.quant8(sb.ffh, F));
-    return f.gemm(sb.ffh, F, sw.ff2, D, F, out_epi, pl);
+    CHK(f.mul(GemmClass::FF1, sb.xn, sw.ff1, EpiStore<T>{sb.ffh, sw.ff1.N, sw.ff1.b, F5_ACT_GELU_TANH, f.pl(), f.wt(F5_WT_STORE16)}));
+    return f.mul(GemmClass::FF2, ARows<T>(sb.ffh), sw.ff2, out_epi);
 }
 
 // Output projection of the normed stream xn into pred.  U = T: w.xn as the final norm left it; U = float (F5_PREC_F16P): pre-split f32
 // rows, as a product of two pre-split operands.
-template <typename T, typename U> static int project_out(const FwdCtx& f, const U* xn, float* pred) {
+template <typename T, typename U> static int project_out(const FwdCtx& f, U* xn, float* pred) {
     f5_engine* e = f.e;
     Packed<T>& P = packed<T>(e);
     const int D = e->cfg.dim, mel = e->cfg.mel_dim;
     if constexpr (std::is_same_v<U, T>) {
-        return f.gemm(xn, D, P.proj_out, mel, D, EpiStore<float>{pred, mel, P.proj_out.b, F5_ACT_NONE}, f.pl());
+        return f.mul(GemmClass::ProjOut, ARows<T>(xn), P.proj_out, EpiStore<float>{pred, mel, P.proj_out.b, F5_ACT_NONE});
     } else {
         HIPCHK(e->prof.timed(PC_GEMM, f.s, f.gflops(mel, D), [&] {
             return launch_gemm<float>(f.s, xn, D, P.proj_out_f.w, P.proj_out_f.ldw, f.rows, mel, D,
@@ -784,7 +760,6 @@ template <typename T, typename Norm> static int finish(const FwdCtx& f, Work<T>&
         return project_out<T, float>(f, free_f32, pred);
     }
     HIPCHK(norm(w.xn, f.pl()));
-    f.ablate(256, w.xn, f.e->cfg.dim);
     return project_out<T, T>(f, w.xn, pred);
 }
 
@@ -816,10 +791,7 @@ template <typename T> static int run_dit_forward(f5_engine* e, Work<T>& w, const
     const f5_config& c = e->cfg;
     const int D = c.dim, N = a.N, rows = a.Bp * N, mod_stride = a.time_stride;
     const RowPack& pk = a.pk;
-    FwdCtx fc{e, s, a.B, a.Bp, N, rows, a.lens_dev, pk};
-    fc.a8 = w.a8;
-    fc.a8s = w.a8s;
-    const FwdCtx& f = fc;
+    const FwdCtx f{e, s, a.B, a.Bp, N, rows, a.lens_dev, pk, w.a8};
     const int* ml = f.ml();
     const int mh = f.mh(), pl = f.pl();
     const int* gate_lens = pk ? nullptr : a.lens_dev; // (a packed batch has no padded rows to leave untouched)
@@ -833,20 +805,19 @@ template <typename T> static int run_dit_forward(f5_engine* e, Work<T>& w, const
     // weight prefetch from the LayerNorm launches (see layernorm_kernel): only where the GEMMs are latency-bound
     const bool wpf = rows <= 4096 && e->sw.weight_prefetch;
     auto prefetch = [&](const LinW<T>& g0, const LinW<T>& g1) {   // the weights of the two GEMMs behind a LayerNorm
-        if (wpf && e->f8) return Prefetch{(const char*)g0.w8, (size_t)g0.N * g0.ldw, (const char*)g1.w8, (size_t)g1.N * g1.ldw};   // (e4m3 codes)
-        return wpf ? Prefetch{(const char*)g0.w, (size_t)g0.N * g0.ldw * sizeof(T), (const char*)g1.w, (size_t)g1.N * g1.ldw * sizeof(T)} : Prefetch{};
+        return wpf ? Prefetch{g0.bytes(), g0.nbytes(), g1.bytes(), g1.nbytes()} : Prefetch{};
     };
     const bool row_mods = pk && mod_stride != 0;   // every batch row of a packed batch has its own vectors
-    const StreamBuf<T> sb{w.x, w.xn, w.ffh, w.ao};
+    const StreamBuf<T> sb{w.x, f.ln_operand(w.xn), w.ffh, w.ao};
     for (int l = 0; l < c.depth; ++l) {
         const StreamW<T>& sw = P.blocks[l].x;
         const float* m = a.time_rows + (size_t)l * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
         const EpiGateRes attn_epi{w.x, w.x, D, sw.out.b, m + 2 * D, mod_stride, N, gate_lens, f.wt(F5_WT_GATE_RES)};
         const EpiGateRes ff_epi{w.x, w.x, D, sw.ff2.b, m + 5 * D, mod_stride, N, nullptr, f.wt(F5_WT_GATE_RES)};
-        HIPCHK(adaln_norm(f, w.x, w.xn, m + D, m, mod_stride, prefetch(sw.qkv, sw.out), pl));
-        if (row_mods) CHK(attention_block<T>(f, w, sw, qk_norm, EpiGateResRows{attn_epi, pk.rowmap}));
-        else CHK(attention_block<T>(f, w, sw, qk_norm, attn_epi));
-        HIPCHK(adaln_norm(f, w.x, w.xn, m + 4 * D, m + 3 * D, mod_stride, prefetch(sw.ff1, sw.ff2), pl));
+        HIPCHK(adaln_norm(f, w.x, sb.xn, m + D, m, mod_stride, prefetch(sw.qkv, sw.out), pl));
+        if (row_mods) CHK(attention_block<T>(f, w, sb.xn, sw, qk_norm, EpiGateResRows{attn_epi, pk.rowmap}));
+        else CHK(attention_block<T>(f, w, sb.xn, sw, qk_norm, attn_epi));
+        HIPCHK(adaln_norm(f, w.x, sb.xn, m + 4 * D, m + 3 * D, mod_stride, prefetch(sw.ff1, sw.ff2), pl));
         if (row_mods) CHK(ff_block<T>(f, sb, sw, EpiGateResRows{ff_epi, pk.rowmap}));
         else CHK(ff_block<T>(f, sb, sw, ff_epi));
     }
@@ -866,12 +837,12 @@ template <typename T> static int run_dit_forward(f5_engine* e, Work<T>& w, const
             }));
         } else {
             HIPCHK(cat_skip(w.cat2));
-            CHK(f.gemm(w.cat2, 2 * D, P.long_skip, D, 2 * D, epi));
+            CHK(f.mul(GemmClass::LongSkip, ARows<T>(w.cat2), P.long_skip, epi));
         }
     }
     const float* mf = a.time_rows + (size_t)c.depth * 6 * D;  // (scale, shift)
     // (F5_PREC_F16P: the pre-split rows go to c1, free since the conv embedding)
-    return finish<T>(f, w, w.c1, w.pred, [&](auto* out, int planar) { return adaln_norm(f, w.x, out, mf, mf + D, mod_stride, Prefetch{}, planar); });
+    return finish<T>(f, w, w.c1, w.pred, [&](auto* out, int planar) { return adaln_norm(f, w.x, ARows(out), mf, mf + D, mod_stride, Prefetch{}, planar); });
 }
 
 // One UNetT forward over Bp packed rows (unett.py:217-280): time token prepended (N + 1 tokens per row), concat skip
@@ -886,7 +857,7 @@ template <typename T> static int run_unett_forward(f5_engine* e, Work<T>& w, con
     Prof& pr = e->prof;
     float* emb = reinterpret_cast<float*>(w.cat2);  // [rows, 2D] of T >= [rows_in, D] f32; free until the first concat; conv input and output must not alias
     // the input embedding runs on the N frames of every row, unpacked and (unett.py:99-100: conv_pos_embed is called WITHOUT a mask) unmasked
-    const FwdCtx in{e, s, B, Bp, N, rows_in, nullptr, RowPack{}};
+    const FwdCtx in{e, s, B, Bp, N, rows_in, nullptr, RowPack{}, Rows8{}};
     if (e->io_split) CHK((embed_input<T, float>(in, w, a.y, a.cond, a.drop_cond_first, a.text_first, a.text_second, emb)));
     else CHK((embed_input<T, T>(in, w, a.y, a.cond, a.drop_cond_first, a.text_first, a.text_second, emb)));
     // The skip stack needs no copies: the stream entering block l < depth/2 is WRITTEN into skip slot l (by the assemble kernel / the
@@ -897,7 +868,7 @@ template <typename T> static int run_unett_forward(f5_engine* e, Work<T>& w, con
         launch_unett_assemble(s, emb, a.time_rows, a.time_stride, half > 0 ? slot(0) : w.x, Bp, N, D);
         return hipGetLastError();
     }));
-    const FwdCtx f{e, s, B, Bp, Nt, rows, lens_dev, RowPack{}};   // the blocks: N + 1 tokens per row; lens_dev holds len + 1 for UNetT
+    const FwdCtx f{e, s, B, Bp, Nt, rows, lens_dev, RowPack{}, Rows8{}};   // the blocks: N + 1 tokens per row; lens_dev holds len + 1 for UNetT
     const int pl = f.pl();
     auto rmsnorm = [&](const float* x, auto* out, const float* g, int planar) {   // out (rows of T, or pre-split f32 rows) = RMSNorm(x) * g
         return pr.timed(PC_LN, s, [&] {
@@ -916,11 +887,10 @@ template <typename T> static int run_unett_forward(f5_engine* e, Work<T>& w, con
                 launch_cat2(s, w.x, skip, w.cat2, rows, D, pl);   // (F5_PREC_F16X3: pre-split, so that the projection runs on pre-split operands too)
                 return hipGetLastError();
             }));
-            f.ablate(512, w.cat2, 2 * D);   // diagnostic: ... and its A operand as plain f16
-            CHK(f.gemm(w.cat2, 2 * D, bw.skip, D, 2 * D, EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}, pl));
+            CHK(f.mul(GemmClass::UNetTSkip, ARows<T>(w.cat2), bw.skip, EpiStore<float>{w.x, D, nullptr, F5_ACT_NONE}));
         }
         HIPCHK(rmsnorm(x_in, w.xn, bw.norm1_g, pl));
-        CHK(attention_block<T>(f, w, bw.x, false, EpiGateRes{w.x, x_in, D, bw.x.out.b, nullptr, 0, Nt, lens_dev, f.wt(F5_WT_GATE_RES)}));
+        CHK(attention_block<T>(f, w, sb.xn, bw.x, false, EpiGateRes{w.x, x_in, D, bw.x.out.b, nullptr, 0, Nt, lens_dev, f.wt(F5_WT_GATE_RES)}));
         HIPCHK(rmsnorm(w.x, w.xn, bw.norm2_g, pl));
         CHK(ff_block<T>(f, sb, bw.x, EpiGateRes{x_out, w.x, D, bw.x.ff2.b, nullptr, 0, Nt, nullptr, f.wt(F5_WT_GATE_RES)}));
     }
@@ -964,12 +934,12 @@ template <typename T> static int run_mmdit_forward(f5_engine* e, Work<T>& w, con
     if (nt <= 0 || nt > std::max(e->res_nt, 1) || L > w.Npad) return fail(F5_ESTATE, "MMDiT forward: nt=%d outside the arena's text reservation", nt);
     Prof& pr = e->prof;
     // the audio embedding: no text columns, the conv unmasked
-    const FwdCtx in{e, s, B, Bp, N, Bp * N, nullptr, RowPack{}};
+    const FwdCtx in{e, s, B, Bp, N, Bp * N, nullptr, RowPack{}, Rows8{}};
     if (e->io_split) CHK((embed_input<T, float>(in, w, a.y, a.cond, a.drop_cond_first, nullptr, nullptr, w.x)));
     else CHK((embed_input<T, T>(in, w, a.y, a.cond, a.drop_cond_first, nullptr, nullptr, w.x)));
     CHK(tap(w.x, (size_t)Bp * N * D));
-    const FwdCtx fx{e, s, B, Bp, N, Bp * N, a.lens_dev, RowPack{}};           // the audio stream's rows
-    const FwdCtx fc{e, s, B, Bp, nt, Bp * nt, nullptr, RowPack{}, false};     // the text stream's rows (no F5_X3_ABLATE hooks: FwdCtx::x3)
+    const FwdCtx fx{e, s, B, Bp, N, Bp * N, a.lens_dev, RowPack{}, Rows8{}};           // the audio stream's rows
+    const FwdCtx fc{e, s, B, Bp, nt, Bp * nt, nullptr, RowPack{}, Rows8{}, false};     // the text stream's rows (no F5_X3_ABLATE hooks: FwdCtx::x3)
     const StreamBuf<T> bx{w.x, w.xn, w.ffh, w.mm_aox}, bc{w.mm_c, w.mm_cn, w.mm_ffc, w.mm_aoc};
     // c = cat(c_cond, c_uncond) (mmdit.py:194), or the one half of a forward without cfg_infer
     const size_t half_c = (size_t)B * nt * D * sizeof(float);
@@ -1027,7 +997,7 @@ template <typename T> static int run_mmdit_forward(f5_engine* e, Work<T>& w, con
     }
     const float* mf = a.time_rows + ((size_t)c.depth * 12 - 4) * D;   // norm_out: (scale, shift)
     // (F5_PREC_F16P: the pre-split rows go to c1, free since the conv embedding)
-    return finish<T>(fx, w, w.c1, w.pred, [&](auto* out, int planar) { return adaln_norm(fx, w.x, out, mf, mf + D, mod_stride, Prefetch{}, planar); });
+    return finish<T>(fx, w, w.c1, w.pred, [&](auto* out, int planar) { return adaln_norm(fx, w.x, ARows(out), mf, mf + D, mod_stride, Prefetch{}, planar); });
 }
 
 // One backbone forward.  What a backbone cannot run is refused here, by name, and never falls through to another backbone's body: packed
@@ -1198,10 +1168,7 @@ template <typename T> static Work<T> second_half(const f5_engine* e, const Work<
     h.ao = w.ao + rows * e->inner;
     h.vt = w.vt + (size_t)B * c.heads * 64 * w.Npad;
     h.ffh = w.ffh + rows * c.ff_dim;
-    if (e->f8) {   // (rows * the widest K, and one scale byte per row)
-        h.a8 = w.a8 + rows * std::max(std::max((size_t)c.dim, (size_t)c.ff_dim), (size_t)e->inner);
-        h.a8s = w.a8s + rows;
-    }
+    if (e->f8) h.a8 = w.a8.at_pitch(a8_pitch(e)).from_row(rows);   // (rows of the widest K, and one scale byte per row)
     if (c.options & F5_OPT_LONG_SKIP) h.cat2 = w.cat2 + rows * 2 * c.dim * io;
     return h;
 }
@@ -1540,9 +1507,9 @@ size_t EngineOps<T>::work_plan(const f5_engine* e, int B, int N, int S, int call
     const Work<T> h = second_half<T>(e, w, call_B, call_N);
     auto put = [&](int64_t* out, const Work<T>& v) {
         const void* p[] = {v.tdev, v.feat, v.th, v.temb, v.st, v.mod, v.lens, v.lens_plain, v.row_start, v.rowmap, v.step_cond, v.text_c, v.text_u,
-                           v.tx_a, v.tx_b, v.tx_h1, v.grn_part, v.uc, v.acat, v.h, v.c1, v.x, v.pred, v.xn, v.q, v.k, v.ao, v.vt, v.ffh, v.in_cond,
-                           v.y, v.y_mid, v.out_buf, v.traj_buf, v.in_mask, v.in_text, v.cat2, v.skips, v.pred_all, v.mod_rows, v.it_t, v.it_cfg,
-                           v.it_steps, v.it_idx};
+                           v.tx_a, v.tx_b, v.tx_h1, v.grn_part, v.uc, v.acat, v.h, v.c1, v.x, v.pred, v.xn, v.q, v.k, v.ao, v.vt, v.ffh, v.a8.codes,
+                           v.a8.scales, v.in_cond, v.y, v.y_mid, v.out_buf, v.traj_buf, v.in_mask, v.in_text, v.cat2, v.skips, v.pred_all, v.mod_rows,
+                           v.it_t, v.it_cfg, v.it_steps, v.it_idx};
         static_assert(sizeof(p) / sizeof(p[0]) == F5K_WORK_BUFFERS, "one entry per name of F5K_WORK_NAMES");
         for (int i = 0; i < F5K_WORK_BUFFERS; ++i) out[i] = p[i] ? (int64_t)(static_cast<const char*>(p[i]) - dry.base) : -1;
     };

@@ -77,11 +77,21 @@ enum { PC_GEMM = 0, PC_ATTN = 1, PC_LN = 2, PC_CONV = 3, PC_MISC = 4, PC_TEXT = 
 
 // --------------------------------------------------------------------------------------- packed weights
 template <typename T> struct LinW {
-    T* w = nullptr;      // [N, ldw]
+    T* w = nullptr;      // [N, ldw]; null where q holds the weight
     float* b = nullptr;  // [N] or null
     int N = 0, K = 0, ldw = 0;
-    // F5_PREC_F8 (the four block GEMMs): e4m3 codes [N, ldw] and one e8m0 scale byte per output channel [N]; w is then null
-    unsigned char *w8 = nullptr, *s8 = nullptr;
+    Rows8 q;             // F5_PREC_F8 (the four block GEMMs): e4m3 codes [N, ldw] and one e8m0 scale byte per output channel
+    // the packed operand's bytes, whichever form holds it (the LayerNorm launches prefetch them)
+    const char* bytes() const { return q ? reinterpret_cast<const char*>(q.codes) : reinterpret_cast<const char*>(w); }
+    size_t nbytes() const { return (size_t)N * ldw * (q ? 1 : sizeof(T)); }
+};
+// The A operand of a backbone GEMM as its producer left it: rows of T [rows, K] (pre-split f32 rows under F5_PREC_F16X3), or
+// (F5_PREC_F8, from the AdaLN LayerNorm) e4m3 rows.
+template <typename T> struct ARows {
+    T* p = nullptr;
+    Rows8 q;
+    ARows(T* rows) : p(rows) {}
+    ARows(const Rows8& rows8) : q(rows8) {}
 };
 
 // One stream's weights of a block: q / k / v fused, out-projection, feed-forward pair
@@ -103,7 +113,8 @@ template <typename T> struct BlockW {
 // the MMDiT's text stream: w.mm_c, w.mm_cn, w.mm_ffc, w.mm_aoc.
 template <typename T> struct StreamBuf {
     float* x;
-    T *xn, *ffh, *ao;
+    ARows<T> xn;
+    T *ffh, *ao;
 };
 
 struct TextBlockW {
@@ -327,9 +338,9 @@ template <typename T> struct Work {
     T* acat;
     float *h, *c1, *x, *pred;
     T *xn, *q, *k, *vt, *ao, *ffh;
-    // F5_PREC_F8 (else null): the A operand of the block GEMM about to run -- e4m3 codes [rows, max(D, inner, F)] at the pitch of its K --
-    // and its row scale bytes [rows]
-    unsigned char *a8, *a8s;
+    // F5_PREC_F8 (else empty): the A operand of the block GEMM about to run -- e4m3 codes at the pitch of its K, in rows carved for the
+    // widest one, pitch = max(D, inner, F) -- and its row scale bytes [rows]
+    Rows8 a8;
     T* cat2;         // UNetT concat buffer [rows, 2D]
     float* skips;    // UNetT skip stack
     float* pred_all; // UNetT proj_out over N+1 tokens

@@ -36,6 +36,31 @@ int check_flow_spans(const char* who, const int32_t* span_host, const int32_t* l
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
+// What each F5_PREC_* is, stated once: the element type of its MFMA operands and typed buffers (the EngineOps<T> it runs), and what the
+// engine changes around them -- split16: the backbone GEMMs as split-f16 products on f32 operands; io_split: the input / output layers
+// likewise under 16-bit blocks; f8: e4m3 operands in the four block GEMMs.
+enum PrecElem { PE_F32, PE_BF16, PE_F16 };
+struct PrecInfo {
+    bool valid;
+    const char* name;
+    PrecElem elem;
+    bool split16, io_split, f8;
+    // one of the four precisions that are an operand type by themselves: what a kernel-level entry (f5k_*) can be asked for.  f16p and f8
+    // are compositions the engine makes of them.
+    constexpr bool plain() const { return valid && !io_split; }
+};
+constexpr PrecInfo prec_info(int prec) {
+    switch (prec) {
+        case F5_PREC_F32: return {true, "f32", PE_F32, false, false, false};
+        case F5_PREC_BF16: return {true, "bf16", PE_BF16, false, false, false};
+        case F5_PREC_F16: return {true, "f16", PE_F16, false, false, false};
+        case F5_PREC_F16X3: return {true, "f16x3", PE_F32, true, false, false};
+        case F5_PREC_F16P: return {true, "f16p", PE_F16, false, true, false};
+        case F5_PREC_F8: return {true, "f8", PE_F16, false, true, true};
+    }
+    return {false, "?", PE_F32, false, false, false};
+}
+
 // Bump allocator over one hipMalloc'd block; with base == nullptr it only measures (dry run).
 struct Arena {
     char* base = nullptr;

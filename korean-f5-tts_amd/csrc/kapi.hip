@@ -41,6 +41,24 @@ extern "C" int f5k_gemm_plan(int32_t elem_size, int32_t M, int32_t N, int32_t K,
     return F5_OK;
 }
 
+// three warm-up launches of go(), then `iters` of them between two events: the average microseconds of one
+template <typename F> static int time_launches(hipStream_t s, int iters, float* avg_us, F&& go) {
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    for (int i = 0; i < 3; ++i) HIPCHK(go());
+    HIPCHK(hipEventRecord(e0, s));
+    for (int i = 0; i < iters; ++i) HIPCHK(go());
+    HIPCHK(hipEventRecord(e1, s));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    *avg_us = ms * 1000.0f / iters;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return F5_OK;
+}
+
 template <typename T>
 static int gemm_time_impl(int M, int N, int K, int cfg, GemmOperands ops, int iters, float* avg_us, hipStream_t s) {
     const int Kp = round_up(K, v1_tile(cfg) ? 8 : GEMM_ROW_BYTES / (int)sizeof(T));
@@ -60,25 +78,11 @@ static int gemm_time_impl(int M, int N, int K, int cfg, GemmOperands ops, int it
     HIPCHK(hipMemcpy(tmp.p, h.data(), nmax * 4, hipMemcpyHostToDevice));
     GemmStage<T> g;
     CHK(g.stage(s, tmp.p, Kp, tmp.p, Kp, M, N, Kp, Kp, GemmOperands::Plain));   // (timing only: the random W bits are used as they are)
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    auto go = [&]() { return launch_gemm<T>(s, g.a.p, Kp, g.w.p, Kp, M, N, Kp, EpiStore<T>{o.p, N, nullptr, 0}, {ops, cfg}); };
-    for (int i = 0; i < 3; ++i) HIPCHK(go());
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) HIPCHK(go());
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.0f / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return F5_OK;
+    return time_launches(s, iters, avg_us, [&] { return launch_gemm<T>(s, g.a.p, Kp, g.w.p, Kp, M, N, Kp, EpiStore<T>{o.p, N, nullptr, 0}, {ops, cfg}); });
 }
 
 // F5_PREC_F8: the e4m3 kernel on random codes (scale bytes 127) into f16 rows; with_quant: the stand-alone row quantiser of an f16 A
-// operand [M, K] runs inside the timed region, as out_project / ff_block launch it before the GEMM
+// operand [M, K] runs inside the timed region, as FwdCtx::mul launches it in front of the out-projection and FF2
 static int gemm_time_f8_impl(int M, int N, int K, int cfg, bool with_quant, int iters, float* avg_us, hipStream_t s) {
     if (K % GEMM_ROW_BYTES) return fail(F5_EINVAL, "f5k_gemm_time: F5_PREC_F8 needs K %% 128 == 0");
     Scratch<unsigned char> a8, w8, as, ws;
@@ -106,28 +110,14 @@ static int gemm_time_f8_impl(int M, int N, int K, int cfg, bool with_quant, int 
         h16[i] = (uint16_t)(((x >> 8) & 0x83FFu) | 0x3C00u);
     }
     HIPCHK(hipMemcpy(a16.p, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    auto go = [&]() {
-        if (with_quant) launch_quant_rows_e4m3<f16_t>(s, a16.p, K, M, K, a8.p, K, K, as.p, nullptr);
+    const Rows8 a{a8.p, as.p, K}, w{w8.p, ws.p, K};
+    return time_launches(s, iters, avg_us, [&] {
+        if (with_quant) launch_quant_rows_e4m3<f16_t>(s, a16.p, K, M, K, a, nullptr);
         GemmOpts op{GemmOperands::Plain, cfg};
-        op.a_scale = as.p;
-        op.w_scale = ws.p;
-        return launch_gemm<e4m3_t>(s, reinterpret_cast<const e4m3_t*>(a8.p), K, reinterpret_cast<const e4m3_t*>(w8.p), K, M, N, K,
-                                   EpiStore<f16_t>{o.p, N, nullptr, 0}, op);
-    };
-    for (int i = 0; i < 3; ++i) HIPCHK(go());
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) HIPCHK(go());
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.0f / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return F5_OK;
+        op.a_scale = a.scales;
+        op.w_scale = w.scales;
+        return launch_gemm<e4m3_t>(s, a.e4m3(), K, w.e4m3(), K, M, N, K, EpiStore<f16_t>{o.p, N, nullptr, 0}, op);
+    });
 }
 
 extern "C" int f5k_gemm_time(int32_t prec, int32_t M, int32_t N, int32_t K, int32_t tm, int32_t tn, int32_t iters,
@@ -225,8 +215,7 @@ static int attention_run(const char* who, int32_t prec, const float* q, const fl
                          const f5k_attn* p, hipStream_t s) {
     auto bad = [&](const char* what) { return fail(F5_EINVAL, "%s: %s", who, what); };
     if (!q || !k || !v || !p || !p->out || Bp <= 0 || H <= 0 || N <= 0) return bad("bad arguments");
-    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
-        return bad("precision must be f32, f16x3, bf16 or f16");
+    if (!prec_info(prec).plain()) return bad("precision must be f32, f16x3, bf16 or f16");
     const bool x3 = prec == F5_PREC_F16X3;
     if (p->mode != 0 && p->mode != 1) return bad("mode must be 0 (the precision's own kernel) or 1 (attn16)");
     if (p->mode == 1 && !x3) return bad("mode 1 (the f16 kernel writing pre-split f32 rows) exists under F5_PREC_F16X3 only");
@@ -255,7 +244,7 @@ extern "C" int f5k_attention(int32_t prec, const float* q, const float* k, const
     p.nlens = Bp;
     p.n_out = (int64_t)Bp * N * H * 64;
     Scratch<uint16_t> o16;   // a 16-bit kernel's own output rows, copied to `out` as f32
-    if (prec == F5_PREC_BF16 || prec == F5_PREC_F16) {
+    if (kernel_elem(prec) != PE_F32) {
         HIPCHK(o16.alloc((size_t)p.n_out));
         p.out = o16.p;
         p.out_f32 = out;
@@ -318,8 +307,7 @@ extern "C" int f5k_layernorm_mod(const float* x, const float* scale, const float
                                  int32_t rows_per_batch, float eps, f5_stream stream) {
     if (!x || !out || R <= 0 || D <= 0 || D % 4 || D > 2048 || rows_per_batch <= 0) return fail(F5_EINVAL, "f5k_layernorm_mod: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL((layernorm_kernel<float>), dim3((R + 3) / 4), dim3(256), 0, s, x, D, out, D, R, D, eps, scale, shift, D,
-                       rows_per_batch, 1, Prefetch{});
+    launch_adaln_norm(s, AdaLN{x, scale, shift, R, D, D, rows_per_batch, eps}, out, 0, 0);
     KCHK();
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
@@ -331,16 +319,13 @@ extern "C" int f5k_quant_rows_e4m3(int32_t prec, const void* x, int64_t ld, int3
                                    int32_t m_limit, f5_stream stream) {
     if (!x || !codes || !scales || R <= 0 || K <= 0 || K % 4 || ld < K || ldc < K || ldc % 4 || m_limit < -1)
         return fail(F5_EINVAL, "f5k_quant_rows_e4m3: bad arguments (K %% 4 == 0, ld >= K, ldc >= K, ldc %% 4 == 0, m_limit -1 or >= 0)");
-    if (prec != F5_PREC_F32 && prec != F5_PREC_BF16 && prec != F5_PREC_F16) return fail(F5_EINVAL, "f5k_quant_rows_e4m3: rows are f32, bf16 or f16");
+    if (!prec_info(prec).plain() || prec_info(prec).split16) return fail(F5_EINVAL, "f5k_quant_rows_e4m3: rows are f32, bf16 or f16");
     if (ld % 4 || ((size_t)x & (prec == F5_PREC_F32 ? 15 : 7)))
         return fail(F5_EINVAL, "f5k_quant_rows_e4m3: rows must start at whole groups of four elements (ld %% 4 == 0, aligned x)");
     hipStream_t s = (hipStream_t)stream;
-    Scratch<int> ml;
-    if (m_limit >= 0) {
-        HIPCHK(ml.alloc(1));
-        HIPCHK(hipMemcpy(ml.p, &m_limit, 4, hipMemcpyHostToDevice));
-    }
-    const int* mlp = m_limit >= 0 ? ml.p : nullptr;
+    DevInt ml;
+    CHK(ml.set(m_limit));
+    const int* mlp = ml.get();
     const int Kc = round_up(K, 4);
     if (prec == F5_PREC_F32) launch_quant_rows_e4m3<float>(s, static_cast<const float*>(x), ld, R, K, codes, ldc, Kc, scales, mlp);
     else if (prec == F5_PREC_BF16) launch_quant_rows_e4m3<bf16_t>(s, static_cast<const bf16_t*>(x), ld, R, K, codes, ldc, Kc, scales, mlp);
@@ -356,13 +341,8 @@ extern "C" int f5k_layernorm_q8(const float* x, const float* scale, const float*
     if (!x || !codes || !scales || R <= 0 || D <= 0 || D % 4 || D > 2048 || rows_per_batch <= 0 || m_limit < -1)
         return fail(F5_EINVAL, "f5k_layernorm_q8: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    Scratch<int> ml;
-    if (m_limit >= 0) {
-        HIPCHK(ml.alloc(1));
-        HIPCHK(hipMemcpy(ml.p, &m_limit, 4, hipMemcpyHostToDevice));
-    }
-    const int* mlp = m_limit >= 0 ? ml.p : nullptr;
-    e4m3_t* out = reinterpret_cast<e4m3_t*>(codes);
+    DevInt ml;
+    CHK(ml.set(m_limit));
     Scratch<int2> rowmap;
     if (batch_of_row_host) {
         std::vector<int2> h((size_t)R);
@@ -372,12 +352,8 @@ extern "C" int f5k_layernorm_q8(const float* x, const float* scale, const float*
         }
         HIPCHK(rowmap.alloc((size_t)R));
         HIPCHK(hipMemcpy(rowmap.p, h.data(), (size_t)R * sizeof(int2), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(layernorm_rows_q8_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, D, out, D, R, D, eps, scale, shift, D, Prefetch{}, mlp,
-                           rowmap.p, scales);
-    } else {
-        hipLaunchKernelGGL(layernorm_q8_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, D, out, D, R, D, eps, scale, shift, D, rows_per_batch, 1,
-                           Prefetch{}, mlp, scales);
     }
+    launch_adaln_norm(s, AdaLN{x, scale, shift, R, D, D, rows_per_batch, eps, rowmap.p, Prefetch{}, ml.get()}, Rows8{codes, scales, D});
     KCHK();
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
@@ -386,14 +362,11 @@ extern "C" int f5k_layernorm_q8(const float* x, const float* scale, const float*
 template <typename TO>
 static int layernorm_ex_impl(const float* x, const float* scale, const float* shift, void* out, float* out_f32, int R, int D,
                              int rows_per_batch, float eps, int m_limit, int planar, hipStream_t s) {
-    Scratch<int> ml;
-    if (m_limit >= 0) {
-        HIPCHK(ml.alloc(1));
-        HIPCHK(hipMemcpy(ml.p, &m_limit, 4, hipMemcpyHostToDevice));
-    }
+    DevInt ml;
+    CHK(ml.set(m_limit));
     TO* o = static_cast<TO*>(out);
-    hipLaunchKernelGGL((layernorm_kernel<TO>), dim3((R + 3) / 4), dim3(256), 0, s, x, D, o, D, R, D, eps, scale, shift, D, rows_per_batch,
-                       1, Prefetch{}, m_limit >= 0 ? ml.p : nullptr, planar == 1, wt_fits(store_policy() & F5_WT_LN, (size_t)R * D * sizeof(TO)));
+    launch_adaln_norm(s, AdaLN{x, scale, shift, R, D, D, rows_per_batch, eps, nullptr, Prefetch{}, ml.get()}, o, planar == 1,
+                      wt_fits(store_policy() & F5_WT_LN, (size_t)R * D * sizeof(TO)));
     KCHK();
     if constexpr (std::is_same_v<TO, float>) {   // planar 2: the plain rows, then split_planar_kernel (what planar 1 must equal)
         if (planar == 2) {
@@ -419,9 +392,8 @@ extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* s
         return f5k_layernorm_q8(x, scale, shift, static_cast<uint8_t*>(out), static_cast<uint8_t*>(out) + (size_t)R * D, R, D, rows_per_batch, eps, m_limit,
                                 nullptr, stream);
     }
-    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16)
-        return fail(F5_EINVAL, "f5k_layernorm_mod_ex: precision must be f32, f16x3, bf16, f16 or f8");
-    if (planar < 0 || planar > 2 || (planar && (prec == F5_PREC_BF16 || prec == F5_PREC_F16 || D % 32)) || (planar == 2 && m_limit >= 0))
+    if (!prec_info(prec).plain()) return fail(F5_EINVAL, "f5k_layernorm_mod_ex: precision must be f32, f16x3, bf16, f16 or f8");
+    if (planar < 0 || planar > 2 || (planar && (prec_info(prec).elem != PE_F32 || D % 32)) || (planar == 2 && m_limit >= 0))
         return fail(F5_EINVAL, "f5k_layernorm_mod_ex: planar needs an f32 output and D %% 32 == 0 (planar 2: every row)");
     return F5K_BY_PREC(prec, layernorm_ex_impl, x, scale, shift, out, out_f32, R, D, rows_per_batch, eps, m_limit, planar,
                        (hipStream_t)stream);
@@ -431,21 +403,20 @@ extern "C" int f5k_layernorm_mod_ex(int32_t prec, const float* x, const float* s
 // One GEMM through a production epilogue: EpiStore / EpiGateRes / EpiQKV constructed field for field as engine_impl.h does (EpiQKV: its
 // qkv_project, own layout), the rotary table through rope_frag_kernel, packed rows through fill_rowmap_kernel, qk_norm through
 // launch_qknorm_rope, the launcher qkv_project calls.
+// (the staged operands g: rows of g.Kp, which is also the K of the launch)
 template <typename T, typename Epi>
-static int epi_gemm(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const Epi& epi, int cfg, const int* ml,
-                    GemmOperands ops, const unsigned char* sa = nullptr, const unsigned char* sw = nullptr) {
+static int epi_gemm(hipStream_t s, const GemmStage<T>& g, int M, int N, const Epi& epi, int cfg, const int* ml, GemmOperands ops) {
     if (cfg == G3_256x256_PP && !(gemm_has_pingpong(sizeof(T), ops) && gemm3_epilogue_ok(epi)))
         return fail(F5_EINVAL, "f5k_gemm_epi: the ping-pong kernel (cfg 20) takes 16-bit or pre-split operands and a QKV split at 256 columns");
     GemmOpts o{ops, cfg, ml};
-    o.a_scale = sa;   // (e4m3 operands: the scale bytes of their rows)
-    o.w_scale = sw;
-    HIPCHK(launch_gemm<T>(s, a, ld, w, ld, M, N, K, epi, o));
+    o.a_scale = g.sa.p;   // (e4m3 operands: the scale bytes of their rows)
+    o.w_scale = g.sw.p;
+    HIPCHK(launch_gemm<T>(s, g.a.p, g.Kp, g.w.p, g.Kp, M, N, g.Kp, epi, o));
     return F5_OK;
 }
 
 template <typename T, typename TO>
-static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, int K, const float* bias, const f5k_epi& p, const int* ml,
-                   GemmOperands ops, const unsigned char* sa = nullptr, const unsigned char* sw = nullptr) {
+static int epi_qkv(hipStream_t s, const GemmStage<T>& g, int M, int N, const float* bias, const f5k_epi& p, const int* ml, GemmOperands ops) {
     Scratch<float> frag;
     HIPCHK(frag.alloc((size_t)p.maxpos * 64));
     hipLaunchKernelGGL(rope_frag_kernel, dim3(ew_blocks((long)p.maxpos * 16)), dim3(256), 0, s, p.rope_cos, p.rope_sin, frag.p, (long)p.maxpos);
@@ -464,10 +435,10 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
     const bool norm = p.kind == F5K_EPI_QKNORM;
     TO* q = static_cast<TO*>(p.out0);
     TO* k = static_cast<TO*>(p.out1);
-    CHK(epi_gemm<T>(s, a, w, ld, M, N, K,
+    CHK(epi_gemm<T>(s, g, M, N,
                     EpiQKV<TO>{q, k, static_cast<TO*>(p.out2), bias, frag.p, p.Nseq, p.Npad, p.H, norm ? 0 : p.pe_heads,
                                norm ? 1.0f : p.q_scale, rowmap.p},
-                    p.cfg, ml, ops, sa, sw));
+                    p.cfg, ml, ops));
     if (norm)   // (own layout: the stream is the whole sequence)
         HIPCHK(launch_qknorm_rope<TO>(s, q, k, p.gq, p.gk, p.rope_cos, p.rope_sin, p.Bp, p.H, p.Nseq, p.Nseq, 0, p.pe_heads, p.q_scale, 1e-6f));
     CHK(copy_f32<TO>(s, p.out0, p.out0_f32, p.n0));
@@ -477,29 +448,26 @@ static int epi_qkv(hipStream_t s, const T* a, const T* w, int ld, int M, int N, 
     return F5_OK;
 }
 
+// T = e4m3_t (F5_PREC_F8): the e4m3 kernel on operands quantised per the contract (GemmStage); 16-bit outputs are f16, as in the engine.
 template <typename T>
 static int gemm_epi_impl(const float* A, const float* W, const float* bias, int M, int N, int K, const f5k_epi& p, GemmOperands ops,
                          hipStream_t s) {
-    const int Kp = round_up(K, GEMM_ROW_BYTES / (int)sizeof(T));
+    using T16 = typename Out16<T>::type;   // the type of a 16-bit STORE and of q / k / v^T (float operands: none, float)
     GemmStage<T> g;
-    CHK(g.stage(s, A, K, W, K, M, N, K, Kp, ops));
-    Scratch<int> ml;
-    if (p.m_limit >= 0) {
-        HIPCHK(ml.alloc(1));
-        HIPCHK(hipMemcpy(ml.p, &p.m_limit, 4, hipMemcpyHostToDevice));
-    }
+    CHK(g.stage(s, A, K, W, K, M, N, K, round_up(K, GEMM_ROW_BYTES / (int)sizeof(T)), ops));
+    DevInt ml;
+    CHK(ml.set(p.m_limit));
     Scratch<int> lens;
     switch (p.kind) {
         case F5K_EPI_STORE:
             if (p.out16) {
-                if constexpr (sizeof(T) == 2) {
-                    CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp, EpiStore<T>{static_cast<T*>(p.out0), N, bias, p.act, 0, wt_fits(store_policy() & F5_WT_STORE16, (size_t)M * N * sizeof(T))},
-                                    p.cfg, ml.p, ops));
-                    CHK(copy_f32<T>(s, p.out0, p.out0_f32, p.n0));
+                if constexpr (sizeof(T16) == 2) {
+                    CHK(epi_gemm<T>(s, g, M, N, EpiStore<T16>{static_cast<T16*>(p.out0), N, bias, p.act, 0, wt_fits(store_policy() & F5_WT_STORE16, (size_t)M * N * sizeof(T16))},
+                                    p.cfg, ml.get(), ops));
+                    CHK(copy_f32<T16>(s, p.out0, p.out0_f32, p.n0));
                 }
             } else {   // planar 2: the plain store, then split_planar_kernel over the whole output (what planar 1 must equal)
-                CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, p.planar == 1}, p.cfg,
-                                ml.p, ops));
+                CHK(epi_gemm<T>(s, g, M, N, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, p.planar == 1}, p.cfg, ml.get(), ops));
                 if (p.planar == 2) {
                     hipLaunchKernelGGL(split_planar_kernel, dim3(ew_blocks((long)M * N / 32)), dim3(256), 0, s, static_cast<float*>(p.out0),
                                        (long)M * N / 32);
@@ -512,65 +480,17 @@ static int gemm_epi_impl(const float* A, const float* W, const float* bias, int 
                 HIPCHK(lens.alloc((size_t)p.nlens));
                 HIPCHK(hipMemcpy(lens.p, p.lens_host, (size_t)p.nlens * 4, hipMemcpyHostToDevice));
             }
-            CHK(epi_gemm<T>(s, g.a.p, g.w.p, Kp, M, N, Kp,
+            CHK(epi_gemm<T>(s, g, M, N,
                             EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p,
                                        wt_fits(store_policy() & F5_WT_GATE_RES, (size_t)M * N * 4)},
-                            p.cfg, ml.p, ops));
+                            p.cfg, ml.get(), ops));
             break;
-        default:   // QKV / QKNORM: the output type is the operand type, or f16 on f32 operands (the f16x3 attn16 path)
+        default:   // QKV / QKNORM: the output type is the operand's (e4m3: f16), or f16 on f32 operands (the f16x3 attn16 path)
             if (p.out16) {
-                if constexpr (std::is_same_v<T, float>) CHK((epi_qkv<T, f16_t>(s, g.a.p, g.w.p, Kp, M, N, Kp, bias, p, ml.p, ops)));
+                if constexpr (std::is_same_v<T, float>) CHK((epi_qkv<T, f16_t>(s, g, M, N, bias, p, ml.get(), ops)));
             } else {
-                CHK((epi_qkv<T, T>(s, g.a.p, g.w.p, Kp, M, N, Kp, bias, p, ml.p, ops)));
+                CHK((epi_qkv<T, T16>(s, g, M, N, bias, p, ml.get(), ops)));
             }
-            break;
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    return F5_OK;
-}
-
-// F5_PREC_F8: A and W are quantised per the contract (quant_rows_e4m3_kernel: codes in rows of whole K-tiles, one scale byte per row) and
-// multiplied by the e4m3 kernel; 16-bit outputs (out16 STORE, q / k / v^T) are f16, as in the engine.
-static int gemm_epi_f8_impl(const float* A, const float* W, const float* bias, int M, int N, int K, const f5k_epi& p, hipStream_t s) {
-    const int Kp = round_up(K, GEMM_ROW_BYTES);
-    Scratch<unsigned char> a8, w8, as, ws;
-    HIPCHK(a8.alloc((size_t)M * Kp));
-    HIPCHK(w8.alloc((size_t)N * Kp));
-    HIPCHK(as.alloc((size_t)M + 16));
-    HIPCHK(ws.alloc((size_t)N + 16));
-    launch_quant_rows_e4m3<float>(s, A, K, M, K, a8.p, Kp, Kp, as.p, nullptr);
-    launch_quant_rows_e4m3<float>(s, W, K, N, K, w8.p, Kp, Kp, ws.p, nullptr);
-    KCHK();
-    const e4m3_t* a = reinterpret_cast<const e4m3_t*>(a8.p);
-    const e4m3_t* w = reinterpret_cast<const e4m3_t*>(w8.p);
-    Scratch<int> ml, lens;
-    if (p.m_limit >= 0) {
-        HIPCHK(ml.alloc(1));
-        HIPCHK(hipMemcpy(ml.p, &p.m_limit, 4, hipMemcpyHostToDevice));
-    }
-    const GemmOperands ops = GemmOperands::Plain;
-    switch (p.kind) {
-        case F5K_EPI_STORE:
-            if (p.out16) {
-                CHK(epi_gemm<e4m3_t>(s, a, w, Kp, M, N, Kp, EpiStore<f16_t>{static_cast<f16_t*>(p.out0), N, bias, p.act, 0, wt_fits(store_policy() & F5_WT_STORE16, (size_t)M * N * 2)},
-                                     p.cfg, ml.p, ops, as.p, ws.p));
-                CHK(copy_f32<f16_t>(s, p.out0, p.out0_f32, p.n0));
-            } else {
-                CHK(epi_gemm<e4m3_t>(s, a, w, Kp, M, N, Kp, EpiStore<float>{static_cast<float*>(p.out0), N, bias, p.act, 0}, p.cfg, ml.p, ops, as.p, ws.p));
-            }
-            break;
-        case F5K_EPI_GATE_RES:
-            if (p.lens_host) {
-                HIPCHK(lens.alloc((size_t)p.nlens));
-                HIPCHK(hipMemcpy(lens.p, p.lens_host, (size_t)p.nlens * 4, hipMemcpyHostToDevice));
-            }
-            CHK(epi_gemm<e4m3_t>(s, a, w, Kp, M, N, Kp,
-                                 EpiGateRes{static_cast<float*>(p.out0), p.res, N, bias, p.gate, p.gate_stride, p.rows_per_batch, lens.p,
-                                            wt_fits(store_policy() & F5_WT_GATE_RES, (size_t)M * N * 4)},
-                                 p.cfg, ml.p, ops, as.p, ws.p));
-            break;
-        default:
-            CHK((epi_qkv<e4m3_t, f16_t>(s, a, w, Kp, M, N, Kp, bias, p, ml.p, ops, as.p, ws.p)));
             break;
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -580,15 +500,15 @@ static int gemm_epi_f8_impl(const float* A, const float* W, const float* bias, i
 extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const float* bias, int32_t M, int32_t N, int32_t K,
                             const f5k_epi* p, f5_stream stream) {
     if (!A || !W || !p || !p->out0 || M <= 0 || N <= 0 || K <= 0 || (N % 4)) return fail(F5_EINVAL, "f5k_gemm_epi: bad arguments (N %% 4 == 0)");
-    if (prec != F5_PREC_F32 && prec != F5_PREC_F16X3 && prec != F5_PREC_BF16 && prec != F5_PREC_F16 && prec != F5_PREC_F8)
-        return fail(F5_EINVAL, "f5k_gemm_epi: precision must be f32, f16x3, bf16, f16 or f8");
+    const PrecInfo pi = prec_info(prec);
+    if (!pi.plain() && !pi.f8) return fail(F5_EINVAL, "f5k_gemm_epi: precision must be f32, f16x3, bf16, f16 or f8");
     if (prec == F5_PREC_F8 && (K % 4 || (p->cfg != -1 && !gemm_tile_has_f8(p->cfg)) || p->planar))
         return fail(F5_EINVAL, "f5k_gemm_epi: F5_PREC_F8 needs K %% 4 == 0, cfg -1, 2, 8 or 13 and no planar output");
     if (p->cfg != -1 && (!gemm_tile(p->cfg) || v1_tile(p->cfg)))
         return fail(F5_EINVAL, "f5k_gemm_epi: cfg must be -1, 2, 8, 9, 10, 13 or 20");
     if (p->m_limit < -1 || p->m_limit > M) return fail(F5_EINVAL, "f5k_gemm_epi: m_limit must be -1 or 0..M");
     if (p->a_presplit && prec != F5_PREC_F16X3) return fail(F5_EINVAL, "f5k_gemm_epi: a_presplit needs F5_PREC_F16X3");
-    const bool op16 = prec == F5_PREC_BF16 || prec == F5_PREC_F16 || prec == F5_PREC_F8;   // (f8: 16-bit outputs are f16)
+    const bool op16 = pi.elem != PE_F32;   // (f8: 16-bit outputs are f16)
     switch (p->kind) {
         case F5K_EPI_STORE:
             if (p->out16 && !op16) return fail(F5_EINVAL, "f5k_gemm_epi: a 16-bit STORE needs a 16-bit operand precision");
@@ -611,11 +531,8 @@ extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const 
             if (p->row_start_host) {
                 if (p->m_limit != -1 || p->row_start_host[0] != 0 || p->row_start_host[p->Bp] > M)
                     return fail(F5_EINVAL, "f5k_gemm_epi: row_start must start at 0, end <= M and replaces m_limit");
-                for (int b = 0; b < p->Bp; ++b) {
-                    const int cnt = p->row_start_host[b + 1] - p->row_start_host[b];
-                    if (p->row_start_host[b] % 4 || cnt < 0 || cnt > round_up(p->Nseq, 4))
-                        return fail(F5_EINVAL, "f5k_gemm_epi: row_start entries must be multiples of 4, at most round_up(Nseq, 4) apart");
-                }
+                if (!row_start_ok(p->row_start_host, p->Bp, p->Nseq, [](int) { return 0; }))
+                    return fail(F5_EINVAL, "f5k_gemm_epi: row_start entries must be multiples of 4, at most round_up(Nseq, 4) apart");
             } else if (M != p->Bp * p->Nseq) {
                 return fail(F5_EINVAL, "f5k_gemm_epi: M must be Bp * Nseq without row_start");
             }
@@ -623,7 +540,7 @@ extern "C" int f5k_gemm_epi(int32_t prec, const float* A, const float* W, const 
         }
         default: return fail(F5_EINVAL, "f5k_gemm_epi: unknown epilogue kind");
     }
-    if (prec == F5_PREC_F8) return gemm_epi_f8_impl(A, W, bias, M, N, K, *p, (hipStream_t)stream);
+    if (pi.f8) return gemm_epi_impl<e4m3_t>(A, W, bias, M, N, K, *p, GemmOperands::Plain, (hipStream_t)stream);
     const GemmOperands ops = prec != F5_PREC_F16X3 ? GemmOperands::Plain : p->a_presplit ? GemmOperands::AWSplit : GemmOperands::WSplit;
     return F5K_BY_PREC(prec, gemm_epi_impl, A, W, bias, M, N, K, *p, ops, (hipStream_t)stream);
 }
@@ -636,7 +553,7 @@ static int glue_done(hipStream_t s) {
     HIPCHK(hipStreamSynchronize(s));
     return F5_OK;
 }
-static bool glue_prec_ok(int32_t prec) { return prec == F5_PREC_F32 || prec == F5_PREC_F16X3 || prec == F5_PREC_BF16 || prec == F5_PREC_F16; }
+static bool glue_prec_ok(int32_t prec) { return prec_info(prec).plain(); }
 
 template <typename T>
 static int pack_input_impl(const float* x, const float* cond, const float* tc, const float* tu, void* out, int ldo, int B, int Bp, int N, int mel,
@@ -779,7 +696,7 @@ template <typename TO> static int xrmsnorm_impl(const float* x, void* out, int R
 }
 // planar: pre-split rows exist for f32 rows of whole 32-element blocks only
 static bool planar_ok(int32_t prec, int planar, int D) {
-    return planar == 0 || (planar == 1 && (prec == F5_PREC_F32 || prec == F5_PREC_F16X3) && D % 32 == 0);
+    return planar == 0 || (planar == 1 && kernel_elem(prec) == PE_F32 && D % 32 == 0);
 }
 extern "C" int f5k_xrmsnorm(int32_t prec, const float* x, void* out, int32_t R, int32_t D, const float* g, int32_t planar, f5_stream stream) {
     if (!x || !out || !g || R <= 0 || D <= 0 || D % 4 || D > 2048 || !glue_prec_ok(prec) || !planar_ok(prec, planar, D))

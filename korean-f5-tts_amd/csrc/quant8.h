@@ -57,6 +57,10 @@ inline void launch_quant_rows_e4m3(hipStream_t s, const T* x, long ld, int R, in
                                    const int* m_limit) {
     hipLaunchKernelGGL((quant_rows_e4m3_kernel<T>), dim3((R + 3) / 4), dim3(256), 0, s, x, ld, R, K, codes, ldc, Kc, scales, m_limit);
 }
+// ... into an operand whose rows are zero-padded up to their pitch
+template <typename T> inline void launch_quant_rows_e4m3(hipStream_t s, const T* x, long ld, int R, int K, const Rows8& out, const int* m_limit) {
+    launch_quant_rows_e4m3<T>(s, x, ld, R, K, out.codes, out.pitch, out.pitch, out.scales, m_limit);
+}
 
 // The e4m3 output form of the two AdaLN LayerNorm kernels: codes [R, ldo] + one scale byte per row (layernorm_body, TO = e4m3_t).
 // Kernels of their own, so that the ones every other precision launches keep their arguments and their code.
@@ -71,6 +75,17 @@ static __global__ __launch_bounds__(256) void layernorm_rows_q8_kernel(const flo
                                                                 int vec_stride, Prefetch pf, const int* __restrict__ m_limit,
                                                                 const int2* __restrict__ rowmap, unsigned char* __restrict__ scales) {
     layernorm_body<e4m3_t, true>(x, ldx, out, ldo, R, D, eps, A, Bv, vec_stride, 0, 1, pf, m_limit, 0, 0, rowmap, scales);
+}
+// the e4m3 output form of launch_adaln_norm (elementwise.h): codes in rows of out.pitch + one scale byte per row
+inline void launch_adaln_norm(hipStream_t s, const AdaLN& a, const Rows8& out) {
+    const dim3 grid((a.R + 3) / 4), block(256);
+    e4m3_t* codes = reinterpret_cast<e4m3_t*>(out.codes);
+    if (a.rowmap)
+        hipLaunchKernelGGL(layernorm_rows_q8_kernel, grid, block, 0, s, a.x, a.D, codes, out.pitch, a.R, a.D, a.eps, a.scale, a.shift, a.vec_stride, a.pf,
+                           a.m_limit, a.rowmap, out.scales);
+    else
+        hipLaunchKernelGGL(layernorm_q8_kernel, grid, block, 0, s, a.x, a.D, codes, out.pitch, a.R, a.D, a.eps, a.scale, a.shift, a.vec_stride,
+                           a.rows_per_batch, 1, a.pf, a.m_limit, out.scales);
 }
 
 }  // namespace f5

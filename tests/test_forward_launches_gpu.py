@@ -6,7 +6,8 @@ forward, finish), not a measurement: a stage that gains, loses or moves a launch
 
 Per forward, d = depth:
   DiT     gemm 4d + 2 (4 per block, input and output projection), attention d, layernorm 2d + 1, convpos 2, misc 1 (input pack);
-          qk_norm: misc + d (norm-rope);  long skip: gemm + 1, misc + 1 (concat)
+          qk_norm: misc + d (norm-rope);  long skip: gemm + 1, misc + 1 (concat);  f8: misc + 2d (the stand-alone row quantisers in
+          front of the out-projection and FF2; the LayerNorms write the e4m3 operand of QKV and FF1 themselves)
   UNetT   gemm 4d + 2 + d/2 (skip projections of the upper half), attention d, layernorm 2d + 1, convpos 2,
           misc 3 + d/2 (pack, assemble, d/2 concats, strip)
   MMDiT   gemm 8(d - 1) + 5 + 2, attention d, layernorm 4(d - 1) + 3 + 1, convpos 2, misc 2 + d (pack, V^T zero, d splits);
@@ -24,9 +25,9 @@ N, NT, NV = 40, 8, 40
 CLASSES = ("gemm", "attention", "layernorm", "convpos", "misc", "text_encoder", "time_adaln")
 
 
-def dit_forward(d, qk_norm=False, long_skip=False):
+def dit_forward(d, qk_norm=False, long_skip=False, precision="f16"):
     return dict(gemm=4 * d + 2 + (1 if long_skip else 0), attention=d, layernorm=2 * d + 1, convpos=2,
-                misc=1 + (d if qk_norm else 0) + (1 if long_skip else 0))
+                misc=1 + (d if qk_norm else 0) + (1 if long_skip else 0) + (2 * d if precision == "f8" else 0))
 
 
 def unett_forward(d):
@@ -67,11 +68,12 @@ def arch(depth, **kw):
     return dict(dim=256, depth=depth, heads=4, dim_head=64, ff_mult=2, **kw)
 
 
-@pytest.mark.parametrize("opts", [dict(), dict(qk_norm=True), dict(long_skip=True)], ids=["plain", "qk_norm", "long_skip"])
+@pytest.mark.parametrize("opts", [dict(), dict(qk_norm=True), dict(long_skip=True), dict(precision="f8")],
+                         ids=["plain", "qk_norm", "long_skip", "f8"])
 def test_dit_step_launches(opts):
     d = 2
     tr = P.DiT(**arch(d, qk_norm="rms_norm" if opts.get("qk_norm") else None, long_skip_connection=bool(opts.get("long_skip"))),
-               text_num_embeds=NV, mel_dim=100, precision="f16").init_synthetic()
+               text_num_embeds=NV, mel_dim=100, precision=opts.get("precision", "f16")).init_synthetic()
     assert one_step(tr) == expect(dit_forward(d, **opts))
 
 

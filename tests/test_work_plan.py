@@ -4,6 +4,8 @@ independent statement of how many bytes one backbone forward writes into each bu
     T (xn, q, k, ao, vt, ffh, and acat / cat2 unless said otherwise) is 4 bytes for f32 and f16x3, 2 bytes for bf16, f16 and f16p
     f16p packs the input rows (acat) and the long-skip concat (cat2) as f32, and writes its final-norm rows as f32 (into c1, or the
     UNetT's first skip slot)
+    f8 (DiT only) is f16p plus the block GEMM's e4m3 A operand: a8, one code byte per element at rows of max(D, F, inner), and a8s,
+    one scale byte per row
     h, c1, x, pred, skips, pred_all are f32; the UNetT input embedding, f32, is written into cat2 before the first concat
     v^T rows are Npad = round_up(tokens of the RESERVATION, 64) apart
 
@@ -17,7 +19,7 @@ import pytest
 from f5_tts_amd import _lib
 from gpu_util import k_work_plan
 
-PRECS = ("f32", "f16x3", "bf16", "f16", "f16p")
+PRECS = ("f32", "f16x3", "bf16", "f16", "f16p", "f8")   # (f8: the two DiT archs; f5_create refuses it for the UNetT)
 ARCHS = {"dit": (_lib.F5_BACKBONE_DIT, 0),
          "dit_qknorm_longskip": (_lib.F5_BACKBONE_DIT, _lib.F5_OPT_QK_RMSNORM | _lib.F5_OPT_LONG_SKIP),
          "unett": (_lib.F5_BACKBONE_UNETT, 0)}
@@ -42,7 +44,7 @@ def written_bytes(prec, arch, res_N, Bp, N):
     """{buffer: bytes one forward over Bp batch rows of N frames writes, from the buffer's start}."""
     unett = arch == "unett"
     sT = 4 if prec in ("f32", "f16x3") else 2
-    io = 4 if prec == "f16p" else sT          # the element size of acat and of the long-skip cat2
+    io = 4 if prec in ("f16p", "f8") else sT  # the element size of acat and of the long-skip cat2
     kin_pad = round_up(2 * MEL + DT, 64)
     inner = HEADS * 64
     tok, res_tok = (N + 1, res_N + 1) if unett else (N, res_N)   # the UNetT prepends the time token
@@ -53,6 +55,9 @@ def written_bytes(prec, arch, res_N, Bp, N):
          "x": rows * DIM * 4, "pred": rows_in * MEL * 4,
          "xn": rows * DIM * sT, "q": rows * inner * sT, "k": rows * inner * sT, "ao": rows * inner * sT,
          "vt": Bp * HEADS * 64 * npad * sT, "ffh": rows * FF * sT}
+    if prec == "f8":   # the block GEMM's e4m3 A operand: codes at the pitch of the widest K, one scale byte per row
+        w["a8"] = rows * max(DIM, FF, inner)
+        w["a8s"] = rows
     if arch == "dit_qknorm_longskip":
         w["cat2"] = rows * 2 * DIM * io
     if unett:
@@ -76,6 +81,10 @@ def call_shapes(B, N):
 @pytest.mark.parametrize("arch", list(ARCHS))
 @pytest.mark.parametrize("prec", PRECS)
 def test_written_extents_fit_their_regions_and_split_halves_are_disjoint(prec, arch):
+    if prec == "f8" and arch == "unett":
+        with pytest.raises(_lib.F5Error, match="F5_PREC_F8 is built for the DiT backbone"):
+            k_work_plan(config(prec, arch), 1, 5, STEPS, 1, 5)
+        return
     bad = {}   # buffer -> findings
     note = lambda name, msg: bad.setdefault(name, []).append(msg)   # noqa: E731
     for B in (1, 3):
