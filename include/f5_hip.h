@@ -712,6 +712,48 @@ int f5_wave_gather(const float* base, int32_t B, const int64_t* start_host, cons
                    float qscale, const int32_t* seg_count_host, const int32_t* segs_host, const int32_t* out_frames_host,
                    const int64_t* out_start_host, float* out, int64_t out_capacity, f5_stream stream);
 
+/* ----------------------------------------------------------------- DTW-aligned mel-cepstral distance
+ * A measure of the engine's own free-running output against a recording that needs nothing but the two mels: mel-cepstral distortion
+ * between the generated and the recorded utterance, aligned by dynamic time warping.  For a pair (a, b), a has n frames and b has m,
+ * each frame n_mels f32 log-mel values (the model's natural-log mel).  The arithmetic contract:
+ *   cepstra       c_k(x) = sum_{j = 0 .. n_mels-1} (double)x_j * T[k][j] for k = 1 .. n_cep, T[k][j] = sqrt(2 / n_mels) *
+ *                 cos(pi k (j + 0.5) / n_mels): the orthonormal DCT-II without coefficient 0 (the energy).  The table is built on the
+ *                 host in double and uploaded (no device cos).  The sum is f64, j ascending, multiply then add, uncontracted; one
+ *                 thread produces one (row, k) value, so there is no reduction order beside the contract's.  Cepstra stay f64.
+ *   distance      d(i, j) = (10 / ln 10) * sqrt(2 * sum_{k = 1 .. n_cep} (c_k(a_i) - c_k(b_j))^2) in f64, k ascending, with the double
+ *                 4.3429448190325175 for 10 / ln 10.  d is bit-symmetric in its two arguments.
+ *   alignment     the symmetric step pattern with weights (1, 2, 1): D(0, 0) = 2 d(0, 0) and D(i, j) = min(D(i-1, j) + d(i, j),
+ *                 D(i-1, j-1) + 2 d(i, j), D(i, j-1) + d(i, j)), cells outside the grid counting as +inf.  Every path then has total
+ *                 weight exactly n + m, so the pair's value is D(n-1, m-1) / (n + m), in dB: continuous in the inputs and
+ *                 independent of tie-breaking (a division by the path's length would be neither).  A cell is one addition per
+ *                 candidate and a three-way minimum: no order of evaluation changes a bit, a pair's value is the same alone and in
+ *                 any batch, and value(a, b) == value(b, a) bit for bit.
+ * What the number is: an MFCC-style distance with MCD's scale constant.  It compares checkpoints, precisions and sampler settings on
+ * the same held-out set; it is NOT comparable to published MCD figures, which use WORLD / SPTK mel-generalised cepstra.
+ * Pair p's a is a_frames_host[p] rows of n_mels f32, a_row_stride elements apart, the first at a_base[a_start_host[p]]; b likewise.
+ * Both sides are read where they lie (frames [lens_b, dur_b) of item b of sample()'s [B, N, mel] output are a pair's a without a
+ * copy); a_base and b_base may be the same buffer.  out: f64 [P] on the device.  A non-finite mel value makes its own pair's result
+ * non-finite and touches no other pair's.
+ * f5_mel_distance_plan is pure host arithmetic (no HIP call): order_out[0 .. P) is the order in which the workgroups take the pairs
+ * -- largest n * m first, ties by index, so that the long pairs do not form the tail -- and *workspace_bytes_out what the call holds
+ * of the per-device workspace: the cepstra, (sum n + sum m) * n_cep * 8 bytes with the shorter side of every pair rounded up to
+ * whole strips of columns (at most 15 frames more), and the tables (the DCT table sized for 256 mel bins).  Never an n x m matrix:
+ * one 4096 x 4096 pair at n_cep = 13 plans under 2 MiB.
+ * f5_mel_distance is two launches: the cepstra (one thread per (row, k) over the packed rows of both sides, the table through LDS)
+ * and the recurrence (one workgroup per pair over anti-diagonals: a thread owns a strip of adjacent columns of the shorter side,
+ * keeps its D(i-1, j) in registers, gets D(i, j-1) and D(i-1, j-1) from its left neighbour by a lane shift, across waves through a
+ * two-slot LDS ring with one barrier per step; d(i, j) is computed a step ahead, off the dependency chain).  Stand-alone like the
+ * silence stage: no handle, the per-device workspace, one table copy through a pinned slot, no host read, no synchronisation except
+ * the growth of the workspace, no atomics.
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the pair: a null pointer, P < 1 or P > 65535,
+ * a_frames or b_frames outside [1, 4096], n_cep outside [1, min(64, n_mels - 1)], n_mels outside [2, 256], a row stride below n_mels,
+ * a start below 0, more than 2^28 cepstral values in one call. */
+int f5_mel_distance_plan(int32_t P, const int32_t* a_frames_host, const int32_t* b_frames_host, int32_t n_cep, int32_t* order_out,
+                         int64_t* workspace_bytes_out);
+int f5_mel_distance(const float* a_base, const float* b_base, int32_t P, const int64_t* a_start_host, const int32_t* a_frames_host,
+                    int64_t a_row_stride, const int64_t* b_start_host, const int32_t* b_frames_host, int64_t b_row_stride,
+                    int32_t n_mels, int32_t n_cep, double* out /* [P], device */, f5_stream stream);
+
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */

@@ -5,7 +5,7 @@ for gfx950 in csrc/, reached through the C-ABI declared in include/f5_hip.h (cty
 """
 from . import adapters, config, edit, mel, utils, weights  # noqa: F401
 
-__all__ = ["config", "weights", "adapters", "edit", "mel", "utils", "CFM", "DiT", "UNetT", "MMDiT", "Vocos", "BigVGAN", "lib", "infer", "dist", "batching"]
+__all__ = ["config", "weights", "adapters", "edit", "mel", "utils", "CFM", "DiT", "UNetT", "MMDiT", "Vocos", "BigVGAN", "lib", "infer", "dist", "batching", "metrics"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require the built library (CPU-only tooling)
@@ -24,7 +24,7 @@ def __getattr__(name):  # lazy: importing the package must not require the built
     if name == "lib":
         from . import _lib
         return _lib
-    if name in ("infer", "dist", "batching", "engine", "bigvgan", "vocos"):
+    if name in ("infer", "dist", "batching", "engine", "bigvgan", "vocos", "metrics"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -128,6 +128,9 @@ SIGNATURES = {
                                 C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _p, C.c_int64, _p]),
     "f5_wave_gather": (_i, [_p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.POINTER(_i), _f, C.POINTER(_i), C.POINTER(_i),
                             C.POINTER(_i), C.POINTER(C.c_int64), _p, C.c_int64, _p]),
+    "f5_mel_distance_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    "f5_mel_distance": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64,
+                             _i, _i, _p, _p]),
     "f5_bigvgan_create": (_i, [C.POINTER(f5_bigvgan_config), C.POINTER(_p)]),
     "f5_bigvgan_destroy": (_i, [_p]),
     "f5_bigvgan_load_weight": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),

@@ -1049,6 +1049,111 @@ def heldout_loss(model, mels, texts, *, adapters=(None,), times=8, seed=0, frac_
     return out
 
 
+def heldout_distance_plan(items, *, duration="truth", speed=1.0, batch_frames=38400):
+    """The host arithmetic of heldout_distance, the reference's cross-sentence evaluation (eval/utils_eval.py:109-148): for items
+    (prompt_mel [p, mel], prompt_text, target_mel [g, mel], target_text) returns (texts, lens, totals, groups).
+    texts[u]: prompt text + target text -- for two strings with the reference's rule that a prompt text whose last character is one
+    byte gets a trailing space, for two token sequences their concatenation.  lens[u] = p.  totals[u]: the frames sample() is asked
+    for -- duration="truth" (use_truth_duration): p + int(g / speed); duration="text": p + int(p / prompt bytes * target bytes /
+    speed), which needs strings.  groups: batching.bucket_prompts over the totals under the frame budget `batch_frames`, no
+    duration window and no shuffle (as heldout_rows)."""
+    from .batching import bucket_prompts, prompt_text_and_frames
+    if duration not in ("truth", "text"):
+        raise ValueError(f"heldout_distance: duration = {duration!r} (expected 'truth' or 'text')")
+    texts, lens, totals = [], [], []
+    for u, (prompt_mel, prompt_text, target_mel, target_text) in enumerate(items):
+        p, g = int(prompt_mel.shape[0]), int(target_mel.shape[0])
+        both_str = isinstance(prompt_text, str) and isinstance(target_text, str)
+        if isinstance(prompt_text, str) != isinstance(target_text, str):
+            raise ValueError(f"heldout_distance: item {u}: prompt_text and target_text must both be strings or both token sequences")
+        if p < 1 or g < 1:
+            raise ValueError(f"heldout_distance: item {u}: prompt_mel and target_mel need at least one frame each")
+        if both_str:
+            text, by_text = prompt_text_and_frames(p, prompt_text, target_text, speed)
+        elif duration == "text":
+            raise ValueError(f"heldout_distance: duration='text' is a ratio of byte lengths: item {u}'s prompt_text and target_text must be strings")
+        else:
+            text, by_text = [int(v) for v in prompt_text] + [int(v) for v in target_text], None
+        texts.append(text)
+        lens.append(p)
+        totals.append(p + int(g / speed) if duration == "truth" else by_text)
+    max_secs = max(40, max(totals) * HOP_LENGTH // SAMPLE_RATE + 1)
+    groups = bucket_prompts(totals, infer_batch_size=int(batch_frames), min_secs=0, max_secs=max_secs, shuffle_seed=None)
+    return texts, lens, totals, groups
+
+
+def heldout_distance(model, items, *, adapters=(None,), duration="truth", nfe_step=nfe_step, cfg_strength=cfg_strength,
+                     sway_sampling_coef=sway_sampling_coef, seed=0, speed=1.0, n_cep=13, batch_frames=38400):
+    """The distance of what every adapter in `adapters` (names of resident adapters, None: the base) GENERATES from what was recorded,
+    on ONE resident engine: the reference's cross-sentence evaluation (eval/utils_eval.py:109-148 -- every held-out sentence spoken
+    from a prompt of the same speaker) scored by DTW-aligned mel-cepstral distortion (metrics.mel_distance; include/f5_hip.h) in
+    place of the Whisper / WavLM / UTMOS models, which are not built.  Where heldout_loss is teacher-forced, this runs free from
+    noise through sample(): this project's solver, guidance, sway, time grid and operand precision are all in the number.
+    items: a list of U (prompt_mel [p, mel], prompt_text, target_mel [g, mel], target_text), texts as strings or token-id sequences --
+    or a mapping adapter name -> such a list where fine-tunes tokenise differently (the mels are the first adapter's; so are the
+    batches).  duration / speed / batch_frames: heldout_distance_plan.  Per batch the target mels go down ONCE and every adapter
+    runs `set_adapter`, ONE sample() (`sample_items` when the model's isolated rows are on: only then is an item's score independent
+    of its batch neighbours, as everywhere) and ONE f5_mel_distance of the generated frames [p_b, dur_b), read in place from
+    sample()'s output, against the targets.  No vocoder is involved.  The adapter that was active before the call is active again
+    after it, on an exception too.  The only readback is one copy at the end.
+    Returns {adapter: {"mcd": sum_u D_u / sum_u (n_u + m_u), "per_item": [U]}}, in dB per unit of path weight: an MFCC-style distance
+    with MCD's constant, comparable between adapters, precisions and sampler settings on the same items, not to published MCD."""
+    from .metrics import mel_distance
+    tr = model.transformer
+    adapters = list(adapters)
+    per_adapter = items if isinstance(items, dict) else {a: items for a in adapters}
+    U = len(per_adapter[adapters[0]]) if adapters and adapters[0] in per_adapter else 0
+    for a in adapters:
+        if a not in per_adapter or len(per_adapter[a]) != U or U == 0:
+            raise ValueError(f"heldout_distance: adapter {a!r} needs the same items as the others, at least one")
+    plans = {a: heldout_distance_plan(per_adapter[a], duration=duration, speed=speed, batch_frames=batch_frames) for a in adapters}
+    first = per_adapter[adapters[0]]
+    lens, groups = plans[adapters[0]][1], plans[adapters[0]][3]
+    targets = [it[2] for it in first]
+    toks = {}
+    for a in adapters:
+        texts = plans[a][0]
+        toks[a] = [(list_str_to_idx([t], model.vocab_char_map) if model.vocab_char_map is not None else list_str_to_tensor([t]))[0]
+                   if isinstance(t, str) else torch.as_tensor(t, dtype=torch.long) for t in texts]
+        if plans[a][1] != lens:
+            raise ValueError(f"heldout_distance: adapter {a!r}'s prompt mels differ in length from the first adapter's")
+    pad = torch.nn.utils.rnn.pad_sequence
+    sample = model.sample_items if getattr(tr, "isolated_rows", False) else model.sample
+    scores = {a: [] for a in adapters}
+    weights = {a: [] for a in adapters}
+    before = tr.active_adapter
+    try:
+        for run in groups:
+            cond = pad([first[u][0].to("cpu", torch.float32) for u in run], batch_first=True).to(model.device)
+            glens = torch.tensor([lens[u] for u in run])
+            tgt = ragged_items([targets[u].to(torch.float32) for u in run], model.device, "heldout_distance only runs on a GPU (there is "
+                               "no CPU path)", "heldout_distance: the target mels are on different devices")[0]   # once per batch
+            tgt = [t.view(-1, model.num_channels) for t in tgt]
+            for a in adapters:
+                tr.set_adapter(a)
+                text = pad([toks[a][u] for u in run], padding_value=-1, batch_first=True)
+                total = torch.tensor([plans[a][2][u] for u in run])
+                end = clamp_durations(text, glens, total).tolist()
+                out, _ = sample(cond, text, total, lens=glens, steps=nfe_step, cfg_strength=cfg_strength,
+                                sway_sampling_coef=sway_sampling_coef, seed=seed)
+                gen = [(out, b, lens[u], end[b] - lens[u]) for b, u in enumerate(run)]
+                scores[a].append(mel_distance(gen, tgt, n_cep=n_cep))
+                weights[a] += [end[b] - lens[u] + int(targets[u].shape[0]) for b, u in enumerate(run)]
+    finally:
+        tr.set_adapter(before)
+    order = [u for run in groups for u in run]
+    host = torch.stack([torch.cat(scores[a]) for a in adapters]).cpu()          # [adapters, U]: the one readback
+    result = {}
+    for i, a in enumerate(adapters):
+        per_item, D, W = [0.0] * U, 0.0, 0
+        for u, v, w in zip(order, host[i].tolist(), weights[a]):
+            per_item[u] = v
+            D += v * w
+            W += w
+        result[a] = dict(mcd=D / W, per_item=per_item)
+    return result
+
+
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,
