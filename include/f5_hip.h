@@ -754,6 +754,61 @@ int f5_mel_distance(const float* a_base, const float* b_base, int32_t P, const i
                     int64_t a_row_stride, const int64_t* b_start_host, const int32_t* b_frames_host, int64_t b_row_stride,
                     int32_t n_mels, int32_t n_cep, double* out /* [P], device */, f5_stream stream);
 
+/* ----------------------------------------------------------------- the alignment itself: f5_mel_distance with its path
+ * f5_mel_align takes f5_mel_distance's arguments and computes the same D; beside it, it names the path that D(n-1, m-1) belongs to,
+ * so that anything per frame (the pitch tracks below) can be compared along it.  One rule is added to the contract above:
+ *   predecessor   the predecessor of cell (i, j), i a frame of a and j a frame of b, is the candidate whose sum is the minimum of
+ *                 D(i-1, j-1) + 2 d(i, j), D(i-1, j) + d(i, j), D(i, j-1) + d(i, j); on equal sums the diagonal (i-1, j-1) wins
+ *                 first, then (i-1, j), then (i, j-1).  The rule is in terms of a and b: the kernel puts the shorter side on the
+ *                 columns and honours it after that swap.  The path is the chain of predecessors from (n-1, m-1) to (0, 0).
+ * Outputs, all on the device: dist f64 [P], bit for bit what f5_mel_distance writes for the same pairs; path_len i32 [P]; path, i32
+ * pairs (i, j): pair p's path starts at pair sum_{q < p} (n_q + m_q - 1) (2 int32 each) and runs in forward order from (0, 0) to
+ * (n-1, m-1), path_len[p] cells, max(n, m) <= path_len <= n + m - 1; the slots behind it up to the next pair's start are scratch.
+ * A pair whose D(n-1, m-1) is not finite gets path_len = 0.  A pair's path does not depend on the batch it is aligned in.
+ * Three launches: the cepstra, the recurrence in its pointer form (the same body; 2 bits per cell, a thread gathers the codes of its
+ * strip of columns over 16 / W rows into one 32-bit word and stores it when it is full -- the layout is internal) and the backtrack
+ * (one wave per pair, one walking lane, then the wave turns the path forward).  f5_mel_align_plan is f5_mel_distance_plan for this
+ * call: the same order, and a workspace that also holds the back-pointers, ceil(max(n, m) / (16 / W)) * T words of 4 bytes per pair
+ * (W, T: the pair's strip and thread count; 4 MiB for one 4096 x 4096 pair).
+ * F5_EINVAL as f5_mel_distance, and: a null path_len or path, more than 2^26 bytes of back-pointers in one call (split the batch). */
+int f5_mel_align_plan(int32_t P, const int32_t* a_frames_host, const int32_t* b_frames_host, int32_t n_cep, int32_t* order_out,
+                      int64_t* workspace_bytes_out);
+int f5_mel_align(const float* a_base, const float* b_base, int32_t P, const int64_t* a_start_host, const int32_t* a_frames_host,
+                 int64_t a_row_stride, const int64_t* b_start_host, const int32_t* b_frames_host, int64_t b_row_stride, int32_t n_mels,
+                 int32_t n_cep, double* dist /* [P], device */, int32_t* path_len /* [P], device */,
+                 int32_t* path /* [sum (n + m - 1)][2], device */, f5_stream stream);
+
+/* ----------------------------------------------------------------- pitch tracks: YIN on a ragged batch of waveforms
+ * The F0 track of every item of a ragged batch of mono f32 waveforms, on the frame grid of the mel front-end, by the YIN estimator
+ * (de Cheveigne and Kawahara 2002: difference function, cumulative mean normalisation, absolute threshold, parabolic
+ * interpolation), with no smoothing over time, no octave correction and no voicing model beside the threshold.  Item p is
+ * len_host[p] samples from base[start_host[p]], read where they lie.  Frame t of an item, t = 0 .. frames_host[p] - 1, is centred
+ * on sample first_centre + t * hop: frame t of MelSpec for the same wave with first_centre = 0 and len / hop + 1 frames (the
+ * vocos front-end), with first_centre = hop / 2 and len / hop frames (bigvgan's).  The arithmetic contract, everything f64 and
+ * uncontracted, W = window:
+ *   samples       L = W + tau_max + 1, s0 = first_centre + t * hop - L / 2 (integer division); x[j] is sample s0 + j of the item,
+ *                 0 where s0 + j is outside [0, len).
+ *   difference    d(tau) = sum_{j = 0 .. W-1} ((double)x[j] - (double)x[j + tau])^2 for tau = 1 .. tau_max + 1: j ascending,
+ *                 subtract, multiply, then add.
+ *   cumulative    S(tau) = S(tau - 1) + d(tau), S(0) = 0, strictly in ascending tau.
+ *   normalised    d'(tau) = (d(tau) * (double)tau) / S(tau) if S(tau) > 0, else 1.
+ *   choice        the smallest tau in [tau_min, tau_max] with d'(tau) < threshold; from there, while tau + 1 <= tau_max and
+ *                 d'(tau + 1) < d'(tau), tau advances.  No such tau: the frame is unvoiced, f0 = 0 and ap = the minimum of d' over
+ *                 [tau_min, tau_max] (the first one, scanned ascending with <).
+ *   refinement    a, b, c = d'(tau - 1), d'(tau), d'(tau + 1), den = a - 2 b + c; delta = (0.5 (a - c)) / den if den > 0, else 0,
+ *                 clamped to [-0.5, 0.5]; f0 = (double)sample_rate / ((double)tau + delta), ap = b.
+ * f0 and ap: f64, packed item after item, frames_host[p] values each.  A non-finite sample reaches only the frames of its own item
+ * that read it: a frame that holds it inside its first W samples is unvoiced (S is NaN, so d' = 1 at every lag), one that holds
+ * it further out follows the contract on the lags the sample does not reach.  No other item is touched.
+ * One launch (a workgroup per frame, a thread per lag, the samples in LDS), one table copy through a pinned slot, no host read, no
+ * synchronisation except the growth of the per-device workspace, no atomics.
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the item: a null pointer, P < 1 or P > 65535,
+ * window outside [64, 2048], not 2 <= tau_min < tau_max <= 1024, threshold outside (0, 1], sample_rate or hop outside [1, 2^20],
+ * first_centre outside [0, 2^30], start_p < 0, len_p < 1, frames_p < 1, more than 2^22 frames in one call. */
+int f5_pitch_track(const float* base, int32_t P, const int64_t* start_host, const int32_t* len_host, int32_t sample_rate, int32_t hop,
+                   int32_t first_centre, const int32_t* frames_host, int32_t window, int32_t tau_min, int32_t tau_max,
+                   double threshold, double* f0 /* device */, double* ap /* device */, f5_stream stream);
+
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */

@@ -131,6 +131,11 @@ SIGNATURES = {
     "f5_mel_distance_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(C.c_int64)]),
     "f5_mel_distance": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64,
                              _i, _i, _p, _p]),
+    "f5_mel_align_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(C.c_int64)]),
+    "f5_mel_align": (_i, [_p, _p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64,
+                          _i, _i, _p, _p, _p, _p]),
+    "f5_pitch_track": (_i, [_p, _i, C.POINTER(C.c_int64), C.POINTER(_i), _i, _i, _i, C.POINTER(_i), _i, _i, _i, C.c_double, _p, _p,
+                            _p]),
     "f5_bigvgan_create": (_i, [C.POINTER(f5_bigvgan_config), C.POINTER(_p)]),
     "f5_bigvgan_destroy": (_i, [_p]),
     "f5_bigvgan_load_weight": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),

@@ -54,6 +54,7 @@ Only checkpoints are loaded with loaders that execute nothing from the file (saf
 """
 from __future__ import annotations
 
+import math
 import re
 
 import numpy as np
@@ -1151,6 +1152,119 @@ def heldout_distance(model, items, *, adapters=(None,), duration="truth", nfe_st
             D += v * w
             W += w
         result[a] = dict(mcd=D / W, per_item=per_item)
+    return result
+
+
+def prosody_numbers(sums: dict) -> dict:
+    """(f0_rmse_cents, f0_corr, vuv_error) of a set of metrics.prosody sums (one item's, or pooled over items), host arithmetic:
+    f0_rmse_cents = 1200 sqrt(sum (x - y)^2 / both_voiced), f0_corr the Pearson correlation of x and y over the both-voiced cells,
+    vuv_error = vuv_mismatch / cells.  NaN where there is nothing to divide by (no cell voiced on both sides; a constant track)."""
+    nan = float("nan")
+    N, cells = sums["both_voiced"], sums["cells"]
+    rmse = 1200.0 * math.sqrt(sums["diff2"] / N) if N > 0 else nan
+    vx, vy = N * sums["x2"] - sums["x"] * sums["x"], N * sums["y2"] - sums["y"] * sums["y"]
+    corr = (N * sums["xy"] - sums["x"] * sums["y"]) / math.sqrt(vx * vy) if N > 0 and vx > 0 and vy > 0 else nan
+    return dict(f0_rmse_cents=rmse, f0_corr=corr, vuv_error=sums["vuv_mismatch"] / cells if cells > 0 else nan)
+
+
+def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth", nfe_step=nfe_step, cfg_strength=cfg_strength,
+                    sway_sampling_coef=sway_sampling_coef, seed=0, speed=1.0, n_cep=13, batch_frames=38400, window=1024, fmin=60.0,
+                    fmax=600.0, threshold=0.15):
+    """heldout_distance with the three prosody numbers of classical objective TTS evaluation beside it, over ONE alignment: what every
+    adapter GENERATES is vocoded, pitch-tracked (metrics.pitch_track: YIN on the device) and compared with the recording's track
+    along the DTW path of the two mels (metrics.mel_alignment).  items: a list of U (prompt_mel [p, mel], prompt_text, target_wave
+    [samples] at the mel front-end's rate, target_text) -- or a mapping adapter -> list as heldout_distance takes it; the sampler
+    keywords are heldout_distance's, window / fmin / fmax / threshold pitch_track's.  vocoder: one with decode_ragged (Vocos, or
+    `BigVGAN.ragged()`), matching the model's mel front-end.  Per batch the target waves go down ONCE, ONE MelSpec.forward_ragged
+    gives their mels and ONE pitch_track their tracks; every adapter then runs `set_adapter`, ONE sample() as in heldout_distance,
+    ONE decode_ragged of the generated frames [p_b, dur_b), ONE pitch_track of those waves, ONE mel_alignment of the generated
+    frames, in place, against the target mels, and the fold (metrics.prosody).  The adapter that was active before the call is
+    active again after it, on an exception too.  The only readback is one copy at the end.
+    Returns {adapter: {"mcd", "f0_rmse_cents", "f0_corr", "vuv_error", "per_item": [U dicts: "mcd", metrics.prosody's counts and
+    sums, and the three numbers of the item alone]}}.  "mcd" is heldout_distance's for the same items (target_mel = the mel of
+    target_wave) and settings, bit for bit.  The other three are pooled from the per-item sums (prosody_numbers): log2-F0 RMSE in
+    cents and Pearson correlation over the cells voiced on both sides, and the share of cells voiced on one side only; NaN, not an
+    error, where no cell is voiced on both sides.  They are YIN frames on vocoded audio: comparable between checkpoints and settings
+    on the same items; no pYIN / Viterbi smoothing, no octave correction, not WORLD's F0."""
+    from .metrics import PROSODY_SUMS, mel_alignment, pitch_track, prosody
+    _require_ragged_vocoder(vocoder, "heldout_prosody", "there is no per-item path")
+    tr, spec = model.transformer, model.mel_spec
+    hop, rate = spec.hop_length, spec.target_sample_rate
+    pad_, _ = spec._variant()
+    centre = 0 if spec.mel_spec_type == "vocos" else hop // 2
+    adapters = list(adapters)
+    per_adapter = items if isinstance(items, dict) else {a: items for a in adapters}
+    U = len(per_adapter[adapters[0]]) if adapters and adapters[0] in per_adapter else 0
+    for a in adapters:
+        if a not in per_adapter or len(per_adapter[a]) != U or U == 0:
+            raise ValueError(f"heldout_prosody: adapter {a!r} needs the same items as the others, at least one")
+    first = per_adapter[adapters[0]]
+    waves = [it[2].reshape(-1) for it in first]
+    tframes = [(int(w.shape[0]) + 2 * pad_ - spec.n_fft) // hop + 1 for w in waves]
+    if min(tframes) < 1:
+        raise ValueError("heldout_prosody: every target_wave needs at least one mel frame")
+    # (the plan reads a target mel's frame count alone)
+    plans = {a: heldout_distance_plan([(it[0], it[1], torch.empty(g, 0), it[3]) for it, g in zip(per_adapter[a], tframes)],
+                                      duration=duration, speed=speed, batch_frames=batch_frames) for a in adapters}
+    lens, groups = plans[adapters[0]][1], plans[adapters[0]][3]
+    toks = {}
+    for a in adapters:
+        texts = plans[a][0]
+        toks[a] = [(list_str_to_idx([t], model.vocab_char_map) if model.vocab_char_map is not None else list_str_to_tensor([t]))[0]
+                   if isinstance(t, str) else torch.as_tensor(t, dtype=torch.long) for t in texts]
+        if plans[a][1] != lens:
+            raise ValueError(f"heldout_prosody: adapter {a!r}'s prompt mels differ in length from the first adapter's")
+    pad = torch.nn.utils.rnn.pad_sequence
+    sample = model.sample_items if getattr(tr, "isolated_rows", False) else model.sample
+    pitch_kw = dict(sample_rate=rate, hop=hop, first_centre=centre, window=window, fmin=fmin, fmax=fmax, threshold=threshold)
+    names = ("cells", "both_voiced", "vuv_mismatch") + tuple(PROSODY_SUMS)
+    rows = {a: [] for a in adapters}                # per batch: f64 [1 + len(names), B]
+    weights = {a: [] for a in adapters}
+    before = tr.active_adapter
+    try:
+        for run in groups:
+            cond = pad([first[u][0].to("cpu", torch.float32) for u in run], batch_first=True).to(model.device)
+            glens = torch.tensor([lens[u] for u in run])
+            tw = ragged_items([waves[u].to(torch.float32) for u in run], model.device, "heldout_prosody only runs on a GPU (there is "
+                              "no CPU path)", "heldout_prosody: the target waves are on different devices")[0]   # once per batch
+            tmel, tf = spec.forward_ragged(tw)
+            tmel = tmel.permute(0, 2, 1)            # [B, T_max, mel], the storage as it lies
+            tgt = [(tmel, b, 0, tf[b]) for b in range(len(run))]
+            t_f0, _, _ = pitch_track(tw, frames=tf, **pitch_kw)
+            for a in adapters:
+                tr.set_adapter(a)
+                text = pad([toks[a][u] for u in run], padding_value=-1, batch_first=True)
+                total = torch.tensor([plans[a][2][u] for u in run])
+                end = clamp_durations(text, glens, total).tolist()
+                out, _ = sample(cond, text, total, lens=glens, steps=nfe_step, cfg_strength=cfg_strength,
+                                sway_sampling_coef=sway_sampling_coef, seed=seed)
+                gf = [end[b] - lens[u] for b, u in enumerate(run)]
+                wav, wav_lens = vocoder.decode_ragged(out.to(torch.float32).permute(0, 2, 1), ends=end, starts=[lens[u] for u in run])
+                g_f0, _, _ = pitch_track(wav, [int(n) for n in wav_lens], frames=gf, **pitch_kw)
+                gen = [(out, b, lens[u], gf[b]) for b, u in enumerate(run)]
+                dist, path, path_start, path_len = mel_alignment(gen, tgt, n_cep=n_cep)
+                fold = prosody((g_f0, gf), (t_f0, tf), path, path_start, path_len)
+                rows[a].append(torch.stack([dist] + [fold[k].to(torch.float64) for k in names]))
+                weights[a] += [gf[b] + tf[b] for b in range(len(run))]
+    finally:
+        tr.set_adapter(before)
+    order = [u for run in groups for u in run]
+    host = torch.stack([torch.cat(rows[a], dim=1) for a in adapters]).cpu()     # [adapters, 1 + sums, U]: the one readback
+    result = {}
+    for i, a in enumerate(adapters):
+        per_item, D, W = [None] * U, 0.0, 0
+        pooled = {k: 0.0 for k in names}
+        for col, (u, w) in enumerate(zip(order, weights[a])):
+            v = host[i, 0, col].item()
+            sums = {k: host[i, 1 + r, col].item() for r, k in enumerate(names)}
+            for k in ("cells", "both_voiced", "vuv_mismatch"):
+                sums[k] = int(sums[k])
+            per_item[u] = dict(mcd=v, **sums, **prosody_numbers(sums))
+            D += v * w
+            W += w
+            for k in names:
+                pooled[k] += sums[k]
+        result[a] = dict(mcd=D / W, **prosody_numbers(pooled), per_item=per_item)
     return result
 
 

@@ -8,6 +8,7 @@ on the same held-out set, NOT comparable to published MCD figures (those use WOR
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -31,17 +32,20 @@ def strip_width(columns: int) -> int:
     return w
 
 
+def _plan(entry: str, a_frames, b_frames, n_cep: int) -> tuple[list[int], int]:
+    a_frames, b_frames = [int(v) for v in a_frames], [int(v) for v in b_frames]
+    if len(a_frames) != len(b_frames):
+        raise ValueError(f"{entry[3:]}: {len(a_frames)} lengths of a for {len(b_frames)} of b (need one pair each)")
+    P = len(a_frames)
+    order, need = (C.c_int32 * max(P, 1))(), C.c_int64()
+    _lib.check(getattr(_lib.load(), entry)(P, _lib.int_array(a_frames), _lib.int_array(b_frames), int(n_cep), order, C.byref(need)), entry)
+    return list(order)[:P], need.value
+
+
 def mel_distance_plan(a_frames, b_frames, *, n_cep: int = 13) -> tuple[list[int], int]:
     """f5_mel_distance_plan (pure host arithmetic): (the order in which the workgroups take the pairs -- largest n * m first, ties
     by index --, the bytes of the per-device workspace the call holds: the cepstra and the tables, never an n x m matrix)."""
-    a_frames, b_frames = [int(v) for v in a_frames], [int(v) for v in b_frames]
-    if len(a_frames) != len(b_frames):
-        raise ValueError(f"mel_distance_plan: {len(a_frames)} lengths of a for {len(b_frames)} of b (need one pair each)")
-    P = len(a_frames)
-    order, need = (C.c_int32 * max(P, 1))(), C.c_int64()
-    _lib.check(_lib.load().f5_mel_distance_plan(P, _lib.int_array(a_frames), _lib.int_array(b_frames), int(n_cep), order,
-                                                C.byref(need)), "f5_mel_distance_plan")
-    return list(order)[:P], need.value
+    return _plan("f5_mel_distance_plan", a_frames, b_frames, n_cep)
 
 
 def _rows(entry, who: str) -> torch.Tensor:
@@ -75,6 +79,30 @@ def _side(entries, who: str):
     return items, dev, base, starts, int(rows[0].shape[1])
 
 
+def _pairs(who: str, a, b):
+    """Both sides of a call as the library takes them: (keep-alive tensors, device, P, frames of a, frames of b, args) with
+    args(lo, hi) the leading arguments of f5_mel_distance / f5_mel_align for pairs [lo, hi)."""
+    a, b = list(a), list(b)
+    if not a or len(a) != len(b):
+        raise ValueError(f"{who}: {len(a)} entries of a for {len(b)} of b (need one pair each, at least one)")
+    keep_a, dev, base_a, starts_a, stride_a = _side(a, who)
+    keep_b, dev_b, base_b, starts_b, stride_b = _side(b, who)
+    if dev != dev_b:
+        raise ValueError(f"{who}: a and b are on different devices")
+    mels = {int(_rows(e, who).shape[1]) for e in a + b}
+    if len(mels) != 1:
+        raise ValueError(f"{who}: every entry needs the same number of mel bins (got {sorted(mels)})")
+    n_mels = mels.pop()
+    frames_a = [int(_rows(e, who).shape[0]) for e in a]
+    frames_b = [int(_rows(e, who).shape[0]) for e in b]
+
+    def args(lo, hi):
+        i64 = lambda arr: (C.c_int64 * (hi - lo))(*arr[lo:hi])   # noqa: E731
+        return (C.c_void_p(base_a), C.c_void_p(base_b), hi - lo, i64(starts_a), _lib.int_array(frames_a[lo:hi]), stride_a, i64(starts_b),
+                _lib.int_array(frames_b[lo:hi]), stride_b, n_mels)
+    return (keep_a, keep_b), dev, len(a), frames_a, frames_b, args
+
+
 def mel_distance(a, b, *, n_cep: int = 13) -> torch.Tensor:
     """DTW-aligned mel-cepstral distortion of P pairs in ONE f5_mel_distance (include/f5_hip.h): a and b are equal-length lists,
     every entry an f32 [frames, mel] tensor or a view descriptor (tensor [B, N, mel], item, start, frames) -- item b of `sample()`'s
@@ -82,23 +110,158 @@ def mel_distance(a, b, *, n_cep: int = 13) -> torch.Tensor:
     otherwise the side is packed once (wave.ragged_items).  1 <= frames <= 4096, 1 <= n_cep <= min(64, mel - 1), mel <= 256.
     Returns f64 [P] on the device, in dB per unit of path weight; nothing is read back and nothing synchronises.  A pair's value does
     not depend on the batch it is scored in, and value(a, b) == value(b, a) bit for bit."""
-    a, b = list(a), list(b)
-    if not a or len(a) != len(b):
-        raise ValueError(f"mel_distance: {len(a)} entries of a for {len(b)} of b (need one pair each, at least one)")
-    keep_a, dev, base_a, starts_a, stride_a = _side(a, "mel_distance")
-    keep_b, dev_b, base_b, starts_b, stride_b = _side(b, "mel_distance")
-    if dev != dev_b:
-        raise ValueError("mel_distance: a and b are on different devices")
-    mels = {int(_rows(e, "mel_distance").shape[1]) for e in a + b}
-    if len(mels) != 1:
-        raise ValueError(f"mel_distance: every entry needs the same number of mel bins (got {sorted(mels)})")
-    n_mels, P = mels.pop(), len(a)
-    frames_a = [int(_rows(e, "mel_distance").shape[0]) for e in a]
-    frames_b = [int(_rows(e, "mel_distance").shape[0]) for e in b]
+    keep, dev, P, _, _, args = _pairs("mel_distance", a, b)
     out = torch.empty(P, device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().f5_mel_distance(C.c_void_p(base_a), C.c_void_p(base_b), P, starts_a, _lib.int_array(frames_a), stride_a,
-                                               starts_b, _lib.int_array(frames_b), stride_b, n_mels, int(n_cep), _ptr(out),
-                                               _stream_ptr(dev)), "f5_mel_distance")
-    del keep_a, keep_b
+        _lib.check(_lib.load().f5_mel_distance(*args(0, P), int(n_cep), _ptr(out), _stream_ptr(dev)), "f5_mel_distance")
+    del keep
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------- the alignment and the prosody
+MAX_TRACE_BYTES = 1 << 26           # csrc/dtw.hip's kMaxTraceBytes: back-pointers of one f5_mel_align
+PROSODY_SUMS = ("diff", "diff2", "x", "y", "xy", "x2", "y2")
+
+
+def trace_bytes(n: int, m: int) -> int:
+    """The bytes of back-pointers f5_mel_align holds for one n x m pair: a 32-bit word per thread and 16 / W rows of the longer side."""
+    cols, rows = min(int(n), int(m)), max(int(n), int(m))
+    w = strip_width(cols)
+    per = DTW_MAX_STRIP // w
+    return 4 * (-(-rows // per)) * (-(-cols // w))
+
+
+def mel_alignment_plan(a_frames, b_frames, *, n_cep: int = 13) -> tuple[list[int], int]:
+    """f5_mel_align_plan (pure host arithmetic): mel_distance_plan for mel_alignment -- the same order, and a workspace that also
+    holds the back-pointers, 2 bits per cell."""
+    return _plan("f5_mel_align_plan", a_frames, b_frames, n_cep)
+
+
+def mel_alignment(a, b, *, n_cep: int = 13):
+    """mel_distance with its path (f5_mel_align; include/f5_hip.h): a and b as mel_distance takes them.  Returns (dist, path,
+    path_start, path_len): dist f64 [P], bit for bit mel_distance(a, b); path int32 [sum (n + m - 1), 2] on the device, pair p's
+    cells (i, j) -- frame i of a against frame j of b -- in rows path_start[p] .. path_start[p] + path_len[p], in forward order from
+    (0, 0) to (n - 1, m - 1); path_start a host list (the cumulative n + m - 1); path_len int32 [P] on the device, 0 for a pair
+    whose distance is not finite.  On equal sums the diagonal predecessor wins, then (i - 1, j), then (i, j - 1).  Nothing is read
+    back and nothing synchronises.  A batch whose back-pointers exceed MAX_TRACE_BYTES goes down in several calls."""
+    keep, dev, P, frames_a, frames_b, args = _pairs("mel_alignment", a, b)
+    path_start = [0]
+    for n, m in zip(frames_a, frames_b):
+        path_start.append(path_start[-1] + max(n + m - 1, 0))
+    dist = torch.empty(P, device=dev, dtype=torch.float64)
+    path_len = torch.empty(P, device=dev, dtype=torch.int32)
+    path = torch.empty(max(path_start[-1], 1), 2, device=dev, dtype=torch.int32)
+    # consecutive runs of pairs, each under the cap (a pair over it by itself is the library's to refuse)
+    runs, lo, held = [], 0, 0
+    for p in range(P):
+        need = trace_bytes(frames_a[p], frames_b[p]) if frames_a[p] > 0 and frames_b[p] > 0 else 0
+        if p > lo and held + need > MAX_TRACE_BYTES:
+            runs.append((lo, p))
+            lo, held = p, 0
+        held += need
+    runs.append((lo, P))
+    with torch.cuda.device(dev):
+        for lo, hi in runs:
+            _lib.check(_lib.load().f5_mel_align(*args(lo, hi), int(n_cep), C.c_void_p(dist.data_ptr() + 8 * lo),
+                                                C.c_void_p(path_len.data_ptr() + 4 * lo),
+                                                C.c_void_p(path.data_ptr() + 8 * path_start[lo]), _stream_ptr(dev)), "f5_mel_align")
+    del keep
+    return dist, path, path_start[:P], path_len
+
+
+def pitch_lags(sample_rate: int, fmin: float, fmax: float) -> tuple[int, int]:
+    """(tau_min, tau_max) of a search range in Hz: floor(sample_rate / fmax), ceil(sample_rate / fmin)."""
+    return int(math.floor(sample_rate / fmax)), int(math.ceil(sample_rate / fmin))
+
+
+def pitch_track(waves, lens=None, *, sample_rate: int = 24000, hop: int = 256, first_centre: int = 0, frames=None,
+                window: int = 1024, fmin: float = 60.0, fmax: float = 600.0, threshold: float = 0.15):
+    """YIN pitch tracks of a ragged batch of mono waveforms in ONE f5_pitch_track (csrc/pitch.hip; the arithmetic contract is in
+    include/f5_hip.h).  waves: a list of 1-D f32 tensors, or an f32 [B, L_max] device tensor with `lens` (item i is waves[i, :lens[i]],
+    what `decode_ragged` returns), read where they lie; host tensors go down in one copy (wave.ragged_items).  Track frame t is
+    centred on sample first_centre + t * hop: MelSpec's frame t of the same wave with first_centre = 0 and the default frames
+    len // hop + 1 (vocos), with first_centre = hop // 2 and frames = len // hop (bigvgan).  The lags searched are pitch_lags(sample_rate,
+    fmin, fmax): 40 .. 400 at the defaults.  Returns (f0, ap, frames): f64 device tensors packed item after item, frames[i] values
+    each -- f0 in Hz, 0 where the frame is unvoiced; ap the normalised difference at the chosen lag (the minimum over the range
+    where unvoiced) -- and the host list of frame counts.  Nothing is read back and nothing synchronises.
+    These are raw YIN frames: no smoothing over time (no pYIN / Viterbi), no octave correction."""
+    who = "pitch_track"
+    if isinstance(waves, torch.Tensor):
+        if waves.dim() != 2 or lens is None or len(lens) != waves.shape[0]:
+            raise ValueError(f"{who}: a tensor of waves must be [B, L_max] with one length per row (or pass a list of 1-D waveforms)")
+        if any(int(n) > waves.shape[1] for n in lens):
+            raise ValueError(f"{who}: lens exceed the tensor's {waves.shape[1]} samples")
+        waves = [waves[b, :int(n)] for b, n in enumerate(lens)]
+    else:
+        waves = list(waves)
+        if lens is not None:
+            waves = [w[:int(n)] for w, n in zip(waves, lens)]
+    if not waves or any(w.dim() != 1 for w in waves):
+        raise ValueError(f"{who}: need at least one waveform, each 1-D")
+    ns = [int(w.shape[0]) for w in waves]
+    frames = [n // int(hop) + 1 for n in ns] if frames is None else [int(f) for f in frames]
+    if len(frames) != len(ns):
+        raise ValueError(f"{who}: {len(frames)} frame counts for {len(ns)} waveforms")
+    tau_min, tau_max = pitch_lags(int(sample_rate), float(fmin), float(fmax))
+    items, dev, base, starts = ragged_items(waves, None, "pitch_track only runs on a GPU (there is no CPU path)",
+                                            f"{who}: the waveforms are on different devices")
+    total = max(sum(max(f, 0) for f in frames), 1)
+    f0 = torch.empty(total, device=dev, dtype=torch.float64)
+    ap = torch.empty(total, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_pitch_track(C.c_void_p(base), len(ns), starts, _lib.int_array(ns), int(sample_rate), int(hop),
+                                              int(first_centre), _lib.int_array(frames), int(window), tau_min, tau_max,
+                                              float(threshold), _ptr(f0), _ptr(ap), _stream_ptr(dev)), "f5_pitch_track")
+    del items
+    return f0, ap, frames
+
+
+def prosody(a_f0, b_f0, path, path_start, path_len):
+    """The sums of the classical objective prosody numbers along the alignment, per pair, with plain torch ops on the device in f64
+    and without a readback.  a_f0 / b_f0: a list of P f64 tracks per side (Hz, 0 = unvoiced; pair p's have n_p and m_p frames) or
+    (packed track, host list of frame counts) as pitch_track returns them; path, path_start, path_len: mel_alignment's.  Returns a
+    dict of device tensors [P]: "cells" (path cells), "both_voiced" (cells voiced on both sides), "vuv_mismatch" (voiced on one side
+    only), int64; and over the both-voiced cells, with x = log2 f0_a and y = log2 f0_b, the f64 sums "diff" (x - y), "diff2",
+    "x", "y", "xy", "x2", "y2" (PROSODY_SUMS).  The counts are exact; the f64 sums are accumulated by index_add_, whose order on the
+    device is not fixed, so they can differ in the last bits from run to run."""
+    def packed(side):
+        if isinstance(side, tuple):
+            track, counts = side
+            counts = [int(c) for c in counts]
+        else:
+            counts = [int(t.shape[0]) for t in side]
+            track = torch.cat([t.reshape(-1) for t in side])
+        off = [0]
+        for c in counts:
+            off.append(off[-1] + c)
+        return track.to(torch.float64), off[:-1]
+    dev = path.device
+    fa, off_a = packed(a_f0)
+    fb, off_b = packed(b_f0)
+    P = len(path_start)
+    if len(off_a) != P or len(off_b) != P:
+        raise ValueError(f"prosody: {len(off_a)} tracks of a and {len(off_b)} of b for {P} paths")
+    slots = path.shape[0]
+    bounds = torch.tensor(list(path_start)[1:] + [slots], device=dev)
+    pair = torch.bucketize(torch.arange(slots, device=dev), bounds, right=True).clamp_(max=P - 1)   # the pair a slot belongs to
+    start = torch.tensor(list(path_start), device=dev)[pair]
+    live = torch.arange(slots, device=dev) - start < path_len.to(torch.int64)[pair]
+    ia = torch.tensor(off_a, device=dev)[pair] + path[:, 0].to(torch.int64)
+    ib = torch.tensor(off_b, device=dev)[pair] + path[:, 1].to(torch.int64)
+    ia = torch.where(live, ia, torch.zeros_like(ia)).clamp_(0, fa.numel() - 1)       # (dead slots hold scratch)
+    ib = torch.where(live, ib, torch.zeros_like(ib)).clamp_(0, fb.numel() - 1)
+    va, vb = fa.to(dev)[ia], fb.to(dev)[ib]
+    voiced_a, voiced_b = live & (va > 0), live & (vb > 0)
+    both = voiced_a & voiced_b
+    one = torch.ones((), device=dev, dtype=torch.float64)
+    x = torch.log2(torch.where(both, va, one))
+    y = torch.log2(torch.where(both, vb, one))
+
+    def total(v, dtype):
+        return torch.zeros(P, device=dev, dtype=dtype).index_add_(0, pair, v.to(dtype))
+    out = {"cells": total(live, torch.int64), "both_voiced": total(both, torch.int64),
+           "vuv_mismatch": total(voiced_a ^ voiced_b, torch.int64)}
+    terms = {"diff": x - y, "diff2": (x - y) * (x - y), "x": x, "y": y, "xy": x * y, "x2": x * x, "y2": y * y}
+    for name in PROSODY_SUMS:
+        out[name] = total(terms[name], torch.float64)
     return out
