@@ -290,8 +290,38 @@ int f5_prepare_sample(f5_engine* e, int32_t B, int32_t n_min, int32_t n_max, int
  * position tables.  F5_PACK_ROWS=0 does not turn it off (that switch is about f5_sample).  f5_sample, f5_sample_ode and
  * f5_prepare_sample are untouched.  on: 0 = off (the default: every key, launch and result as without this function). */
 int f5_set_isolated_rows(f5_engine* e, int32_t on);
-/* The graph cache holds n graphs, 16 (the default) <= n <= 64, oldest out first; anything else is F5_EINVAL.  For an engine whose
- * calls vary in B as well as in length bucket.  f5_set_length_buckets puts it back to 16; f5_prepare_sample only ever raises it. */
+/* ------------------------------------------------------------------------------------------ graph cache
+ * The body of every sampler call (f5_sample, f5_sample_ode, f5_sample_items, f5_sample_span) is cached as a HIP graph under the
+ * call's signature: everything the launches depend on and nothing else (tests/graph_cache_oracle.py restates these rules).
+ *   - A call takes one of three paths.  The first sighting of a signature launches eagerly and marks it warm; the next sighting
+ *     of a warm signature that has no graph captures one and launches it; a signature that has a graph replays it.  The three
+ *     results are bit-equal.
+ *   - The cache holds `capacity` graphs, 16 by default.  A capture into a full cache pushes out the graph that was captured
+ *     first (first in, first out: a replay does not renew an entry).  A signature whose graph was pushed out is still warm, so
+ *     its next sighting captures again.
+ *   - A clear drops every graph and forgets which signatures were warm: the next sighting of any signature is eager again.  A
+ *     clear pushes nothing out: it does not count as an eviction.  These clear: growth of the reserved batch, frames or steps
+ *     (f5_reserve, or any call larger than what is reserved; with length buckets a call reserves its bucket's ceiling); a text
+ *     longer than any before (f5_prepare_sample's nt_max counts); the first per-item call (f5_sample_items, f5_sample_span) and
+ *     every per-item call with more distinct evaluation times than any before; f5_set_length_buckets; f5_load_weight and
+ *     f5_finalize.  A call that fits what is reserved clears nothing.
+ *   - The unconditional text embedding of a single utterance is kept between calls where it depends on nothing but the weights
+ *     and N: B = 1, guidance on (cfg_strength >= 1e-5), lens_host NULL and no length bucket, the DiT or the UNetT, no
+ *     text_mask_padding with conv_layers > 0 and no F5_OPT_TEXT_AVG_UPSAMPLE.  One embedding is kept, for the N of the call that
+ *     stored it.  Such a call's signature carries whether it reads the kept embedding ("|uc"; every other call's ends in
+ *     "|nouc"), and a call that has to compute and store it -- the first at its N, the first after another N -- always launches
+ *     eagerly, whatever is warm or captured.  Growth of the reserved batch, frames or steps, a first or larger per-item call,
+ *     f5_load_weight and f5_finalize forget the embedding; a longer text alone leaves it, and the call behind that clear is eager
+ *     in any case.
+ *   - A call returns without waiting for the device, so a graph can be pushed out or cleared while its last launch is still
+ *     running: the engine waits for that launch (an event behind it, on the call's stream) before it destroys the graph.  The
+ *     host never waits otherwise.
+ *
+ * f5_set_graph_capacity: the cache holds n graphs, 16 (the default) <= n <= 64; anything else is F5_EINVAL.  For an engine whose
+ * calls vary in B as well as in length bucket.  Shrinking below the number held pushes out the oldest captures at once, each an
+ * eviction.  f5_set_length_buckets clears the cache and puts the capacity back to 16; f5_prepare_sample only ever raises it, to the
+ * number of buckets it was asked for, and evicts like any capture when its range does not fit beside what is held.  A prepared
+ * signature counts as seen (warm): when its graph is pushed out, the next call in that bucket captures again. */
 int f5_set_graph_capacity(f5_engine* e, int32_t n);
 /* out[0..3] = f5_sample bodies captured into a graph (the capturing call launches its graph, and counts here only), replayed from the
  * cache, launched eagerly, and graphs pushed out of the cache by a newer one -- since f5_create or the last reset.  out == NULL

@@ -1371,8 +1371,10 @@ template <typename T> static int launch_sample_body(f5_engine* e, Work<T>& w, co
             if (exec) how = "graph capture + instantiate + launch";
         }
     }
-    if (exec) HIPCHK(hipGraphLaunch(exec, s));
-    else {
+    if (exec) {
+        HIPCHK(hipGraphLaunch(exec, s));
+        CHK(e->gc.launched(exec, s));
+    } else {
         CHK(sample_body<T>(e, w, p, s));
         e->gc.stats.eager++;
     }
@@ -1481,6 +1483,7 @@ int EngineOps<T>::prepare(f5_engine* e, int B, int n_min, int n_max, int nt_max,
         o.n_true = nc;
         const SamplePlan p = plan_sample(e, B, nc, nullptr, o);
         const std::string key = graph_key(p) + "|nouc";
+        e->gc.mark_warm(graph_key(p));   // prepared counts as seen: a bucket whose graph is pushed out captures again on its next call
         if (e->gc.find(key)) continue;
         hipGraphExec_t exec = nullptr;
         CHK(e->gc.capture(key, [&](hipStream_t cs) { return sample_body<T>(e, w, p, cs); }, &exec));

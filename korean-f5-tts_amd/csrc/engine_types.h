@@ -204,9 +204,12 @@ inline bool valid_len_bucket(long g) { return g == 0 || (g >= 8 && g <= 1024 && 
 // captured the second time it is seen: its first call runs eagerly and marks it warm (f5_prepare_sample captures ahead of
 // the first call instead).  The cache holds `capacity` entries, oldest out first: 16, or as many as f5_prepare_sample was
 // asked to keep ready, MAX_CAPACITY at most.
+// sample() returns without a host sync, so the launch of an entry may still be in flight when the entry is pushed out: every launch records
+// the entry's event on the caller's stream (launched), and evict waits for it before it destroys the exec.
 struct GraphCache {
     enum { DEFAULT_CAPACITY = 16, MAX_CAPACITY = 64 };
-    struct Entry { std::string key; hipGraph_t graph; hipGraphExec_t exec; };
+    // done: recorded behind the entry's last launch (made by its first one; null for a graph that never launched, as f5_prepare_sample's)
+    struct Entry { std::string key; hipGraph_t graph; hipGraphExec_t exec; hipEvent_t done; };
     // f5_graph_stats: sample() bodies captured, replayed and launched eagerly, and entries pushed out by a newer capture
     struct Stats { int captures = 0, replays = 0, eager = 0, evictions = 0; };
     Stats stats;
@@ -246,7 +249,7 @@ struct GraphCache {
                     evict(0);
                     stats.evictions++;
                 }
-                graphs.push_back({key, graph, *exec});
+                graphs.push_back({key, graph, *exec, nullptr});
                 stats.captures++;
                 return F5_OK;
             }
@@ -259,7 +262,21 @@ struct GraphCache {
         disabled = true;
         return F5_OK;
     }
+    // after hipGraphLaunch(exec, s): marks the end of that launch on s, for evict
+    int launched(hipGraphExec_t exec, hipStream_t s) {
+        for (auto& g : graphs) {
+            if (g.exec != exec) continue;
+            if (!g.done) HIPCHK(hipEventCreateWithFlags(&g.done, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(g.done, s));
+            break;
+        }
+        return F5_OK;
+    }
     void evict(size_t i) {
+        if (graphs[i].done) {   // the entry's last launch may still be running
+            (void)hipEventSynchronize(graphs[i].done);
+            (void)hipEventDestroy(graphs[i].done);
+        }
         if (graphs[i].exec) (void)hipGraphExecDestroy(graphs[i].exec);
         if (graphs[i].graph) (void)hipGraphDestroy(graphs[i].graph);
         graphs.erase(graphs.begin() + i);
