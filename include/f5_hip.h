@@ -839,6 +839,67 @@ int f5_pitch_track(const float* base, int32_t P, const int64_t* start_host, cons
                    int32_t first_centre, const int32_t* frames_host, int32_t window, int32_t tau_min, int32_t tau_max,
                    double threshold, double* f0 /* device */, double* ap /* device */, f5_stream stream);
 
+/* ----------------------------------------------------------------- smoothed pitch tracks: pYIN candidates and a Viterbi decode
+ * pYIN (Mauch and Dixon 2014) in two calls.  Stage 1 lets every threshold of a prior distribution make YIN's choice, which gives a
+ * frame a few weighted lag candidates; stage 2 decodes one candidate per frame, or "unvoiced", over pitch-bin x voicing states, so
+ * that a jump of an octave for a few frames, outside the transition band, cannot win.  Everything is f64 and uncontracted; every
+ * table is built on the host and passed down, so that the device only adds, multiplies, divides and compares, in the order below.
+ *
+ * Stage 1, f5_pitch_candidates, per frame.  The samples, d(tau), S(tau) and d'(tau) are f5_pitch_track's, by the same code.
+ *   thresholds    s_i = (double)i / (double)N for i = 1 .. N, with the weights w_host[i - 1] (f64, finite, >= 0).
+ *   votes         for i ascending, tau_i is f5_pitch_track's choice at threshold s_i (the smallest tau in [tau_min, tau_max] with
+ *                 d'(tau) < s_i, then on while tau + 1 <= tau_max and d'(tau + 1) < d'(tau)), and prob(tau_i) = prob(tau_i) + w_i.
+ *                 No such tau: prob(tau_g) = prob(tau_g) + w_i * p_absent, tau_g the arg-min of d' over [tau_min, tau_max] (the
+ *                 first one, scanned ascending with <).  prob starts at 0; a lag's sum runs in ascending i.
+ *   candidates    every lag with prob > 0, in ascending lag, is a candidate (tau, f0, prob), f0 by f5_pitch_track's refinement at
+ *                 tau.  A frame whose d'(tau) is NaN at any tau in [1, tau_max + 1] has no candidates.
+ * Outputs on the device, frames packed item after item as f5_pitch_track packs them, N slots per frame: cand_count i32 [frames],
+ * cand_lag i32 [frames][N], cand_f0 and cand_prob f64 [frames][N]; the slots behind a frame's count are written as zeros.  One
+ * launch, a workgroup per frame; a thread per threshold finds tau_i, one lane adds the votes in order.  Otherwise as
+ * f5_pitch_track: one table copy through a pinned slot, no host read, no atomics; an item reads its own samples only.
+ * F5_EINVAL as f5_pitch_track (without the threshold), and: N outside [1, 256], a null w_host, a weight that is not finite or is
+ * negative, p_absent outside [0, 1], a null output.
+ *
+ * Stage 2, f5_pitch_decode, per item, over frames t = 0 .. frames_host[p] - 1 of the candidate arrays (packed as stage 1 writes
+ * them; a frame's count is taken as clamped to [0, N], its candidates in array order, which is ascending lag).
+ *   bins          M pitch bins: edge_host[M + 1] in Hz, strictly ascending, and centre_host[M].  A candidate's bin is the number of
+ *                 j in [1, M - 1] with edge[j] <= f0: compares alone, in [0, M - 1] whatever f0 is.
+ *   transitions   trans_host[M][2 * reach + 1]: entry [i][k] is the weight of going from bin i to bin i + k - reach (a destination
+ *                 outside [0, M - 1] is never read).  stay = 1 - p_switch, computed on the host in f64.
+ *   observation   ov(m) = the sum of prob over the frame's candidates in bin m, in array order; tot = the sum over all of them, in
+ *                 array order; ou = max(0, 1 - tot) / (double)M.  obs(voiced, m) = max(ov(m), 2^-60), obs(unvoiced, m) =
+ *                 max(ou, 2^-60).
+ *   recurrence    delta(v, m) = 1 before frame 0.  inner_v(j) = max over i in [max(0, j - reach), min(M - 1, j + reach)] of
+ *                 delta_prev(v, i) * trans[i][j - i + reach], i ascending, the smallest i winning ties.  For a destination
+ *                 voicing v': c = inner_v'(j) * stay, and the other voicing u replaces it only if inner_u(j) * p_switch > c.
+ *                 delta(v', j) = obs(v', j) * c.  Then every delta of the frame is divided by the frame's maximum (an order-free
+ *                 maximum of exact values), where that maximum is > 0.
+ *   end state     the largest delta of the last frame: unvoiced states scanned before voiced ones, bins ascending, with >.
+ *   path          one back-pointer byte per state and frame (bit 7: the source's voicing, bits 0 .. 6: i - j + reach), walked back
+ *                 from the end state.
+ * Outputs, f64 [frames] on the device, packed like the candidates: f0 -- 0 where the frame's state is unvoiced, otherwise the f0 of
+ * the frame's candidate in the state's bin with the largest prob (the first one in array order on ties), or centre[m] where the bin
+ * holds no candidate of that frame -- and voiced_prob = tot.  An item reads its own frames only: its track is the same alone, in
+ * any batch and in any order.
+ * workspace: device memory for the back-pointers, at least f5_pitch_decode_bytes(frames of the call, M) = 2 * M * frames bytes
+ * (the layout is internal); it is the caller's and can be reused by the next call on the stream.  One launch: a workgroup per
+ * item, a thread per bin carrying both voicings, delta ping-ponging in LDS, the frame's maximum by a wave and LDS max-reduction;
+ * one lane walks the path back, then the workgroup writes the outputs.  The tables go down in one copy through a pinned slot; no
+ * host read, no synchronisation except the growth of the per-device workspace that holds the tables, no atomics.
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the item: a null pointer, N outside [1, 256], P < 1
+ * or P > 65535, frames_p < 1, more than 2^22 frames in one call, M outside [2, 512], reach outside [1, 63], p_switch outside (0, 1),
+ * a table value that is not finite, a negative transition, edges not strictly ascending, workspace_bytes below the need. */
+int f5_pitch_candidates(const float* base, int32_t P, const int64_t* start_host, const int32_t* len_host, int32_t sample_rate,
+                        int32_t hop, int32_t first_centre, const int32_t* frames_host, int32_t window, int32_t tau_min,
+                        int32_t tau_max, int32_t N, const double* w_host, double p_absent, int32_t* cand_count /* device */,
+                        int32_t* cand_lag /* device */, double* cand_f0 /* device */, double* cand_prob /* device */,
+                        f5_stream stream);
+int64_t f5_pitch_decode_bytes(int64_t frames_total, int32_t M);
+int f5_pitch_decode(const int32_t* cand_count, const double* cand_f0, const double* cand_prob, int32_t N, int32_t P,
+                    const int32_t* frames_host, int32_t M, const double* edge_host, const double* centre_host, int32_t reach,
+                    const double* trans_host, double p_switch, void* workspace /* device */, int64_t workspace_bytes,
+                    double* f0 /* device */, double* voiced_prob /* device */, f5_stream stream);
+
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */

@@ -1169,7 +1169,7 @@ def prosody_numbers(sums: dict) -> dict:
 
 def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth", nfe_step=nfe_step, cfg_strength=cfg_strength,
                     sway_sampling_coef=sway_sampling_coef, seed=0, speed=1.0, n_cep=13, batch_frames=38400, window=1024, fmin=60.0,
-                    fmax=600.0, threshold=0.15):
+                    fmax=600.0, threshold=0.15, pitch="yin", p_switch=0.01, p_absent=0.01):
     """heldout_distance with the three prosody numbers of classical objective TTS evaluation beside it, over ONE alignment: what every
     adapter GENERATES is vocoded, pitch-tracked (metrics.pitch_track: YIN on the device) and compared with the recording's track
     along the DTW path of the two mels (metrics.mel_alignment).  items: a list of U (prompt_mel [p, mel], prompt_text, target_wave
@@ -1184,9 +1184,16 @@ def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth"
     sums, and the three numbers of the item alone]}}.  "mcd" is heldout_distance's for the same items (target_mel = the mel of
     target_wave) and settings, bit for bit.  The other three are pooled from the per-item sums (prosody_numbers): log2-F0 RMSE in
     cents and Pearson correlation over the cells voiced on both sides, and the share of cells voiced on one side only; NaN, not an
-    error, where no cell is voiced on both sides.  They are YIN frames on vocoded audio: comparable between checkpoints and settings
-    on the same items; no pYIN / Viterbi smoothing, no octave correction, not WORLD's F0."""
-    from .metrics import PROSODY_SUMS, mel_alignment, pitch_track, prosody
+    error, where no cell is voiced on both sides.
+    pitch: "yin" (the default: raw YIN frames, no smoothing over time, no octave correction -- a few frames of subharmonic energy
+    count as an octave error) or "pyin": both the generated and the target tracks come from metrics.pitch_track_pyin (pYIN
+    candidates and a Viterbi decode; threshold is not read, p_switch / p_absent are its keywords) over ONE set of tables
+    (metrics.pyin_tables(rate, fmin, fmax), built once per call); the returned dict has the same keys.  Either way these are tracks
+    of vocoded audio by this project's own tracker: comparable between checkpoints and settings on the same items with the same
+    `pitch`, not WORLD's F0 and not comparable with published figures."""
+    from .metrics import PROSODY_SUMS, mel_alignment, pitch_track, pitch_track_pyin, prosody, pyin_tables
+    if pitch not in ("yin", "pyin"):
+        raise ValueError(f"heldout_prosody: pitch = {pitch!r} (expected 'yin' or 'pyin')")
     _require_ragged_vocoder(vocoder, "heldout_prosody", "there is no per-item path")
     tr, spec = model.transformer, model.mel_spec
     hop, rate = spec.hop_length, spec.target_sample_rate
@@ -1216,7 +1223,13 @@ def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth"
             raise ValueError(f"heldout_prosody: adapter {a!r}'s prompt mels differ in length from the first adapter's")
     pad = torch.nn.utils.rnn.pad_sequence
     sample = model.sample_items if getattr(tr, "isolated_rows", False) else model.sample
-    pitch_kw = dict(sample_rate=rate, hop=hop, first_centre=centre, window=window, fmin=fmin, fmax=fmax, threshold=threshold)
+    pitch_kw = dict(sample_rate=rate, hop=hop, first_centre=centre, window=window, fmin=fmin, fmax=fmax)
+    if pitch == "yin":
+        pitch_kw["threshold"] = threshold
+        tracker = pitch_track
+    else:
+        pitch_kw.update(p_switch=p_switch, p_absent=p_absent, tables=pyin_tables(rate, fmin, fmax))
+        tracker = pitch_track_pyin
     names = ("cells", "both_voiced", "vuv_mismatch") + tuple(PROSODY_SUMS)
     rows = {a: [] for a in adapters}                # per batch: f64 [1 + len(names), B]
     weights = {a: [] for a in adapters}
@@ -1230,7 +1243,7 @@ def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth"
             tmel, tf = spec.forward_ragged(tw)
             tmel = tmel.permute(0, 2, 1)            # [B, T_max, mel], the storage as it lies
             tgt = [(tmel, b, 0, tf[b]) for b in range(len(run))]
-            t_f0, _, _ = pitch_track(tw, frames=tf, **pitch_kw)
+            t_f0, _, _ = tracker(tw, frames=tf, **pitch_kw)
             for a in adapters:
                 tr.set_adapter(a)
                 text = pad([toks[a][u] for u in run], padding_value=-1, batch_first=True)
@@ -1240,7 +1253,7 @@ def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth"
                                 sway_sampling_coef=sway_sampling_coef, seed=seed)
                 gf = [end[b] - lens[u] for b, u in enumerate(run)]
                 wav, wav_lens = vocoder.decode_ragged(out.to(torch.float32).permute(0, 2, 1), ends=end, starts=[lens[u] for u in run])
-                g_f0, _, _ = pitch_track(wav, [int(n) for n in wav_lens], frames=gf, **pitch_kw)
+                g_f0, _, _ = tracker(wav, [int(n) for n in wav_lens], frames=gf, **pitch_kw)
                 gen = [(out, b, lens[u], gf[b]) for b, u in enumerate(run)]
                 dist, path, path_start, path_len = mel_alignment(gen, tgt, n_cep=n_cep)
                 fold = prosody((g_f0, gf), (t_f0, tf), path, path_start, path_len)

@@ -8,6 +8,7 @@ on the same held-out set, NOT comparable to published MCD figures (those use WOR
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import math
 
 import torch
@@ -184,8 +185,25 @@ def pitch_track(waves, lens=None, *, sample_rate: int = 24000, hop: int = 256, f
     fmin, fmax): 40 .. 400 at the defaults.  Returns (f0, ap, frames): f64 device tensors packed item after item, frames[i] values
     each -- f0 in Hz, 0 where the frame is unvoiced; ap the normalised difference at the chosen lag (the minimum over the range
     where unvoiced) -- and the host list of frame counts.  Nothing is read back and nothing synchronises.
-    These are raw YIN frames: no smoothing over time (no pYIN / Viterbi), no octave correction."""
-    who = "pitch_track"
+    These are raw YIN frames: no smoothing over time, no octave correction -- a few frames of subharmonic energy report the octave
+    below.  `pitch_track_pyin` is the smoothed tracker (pYIN candidates and a Viterbi decode over them)."""
+    waves, ns, frames = _waves_and_frames("pitch_track", waves, lens, hop, frames)
+    tau_min, tau_max = pitch_lags(int(sample_rate), float(fmin), float(fmax))
+    items, dev, base, starts = ragged_items(waves, None, "pitch_track only runs on a GPU (there is no CPU path)",
+                                            "pitch_track: the waveforms are on different devices")
+    total = max(sum(max(f, 0) for f in frames), 1)
+    f0 = torch.empty(total, device=dev, dtype=torch.float64)
+    ap = torch.empty(total, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_pitch_track(C.c_void_p(base), len(ns), starts, _lib.int_array(ns), int(sample_rate), int(hop),
+                                              int(first_centre), _lib.int_array(frames), int(window), tau_min, tau_max,
+                                              float(threshold), _ptr(f0), _ptr(ap), _stream_ptr(dev)), "f5_pitch_track")
+    del items
+    return f0, ap, frames
+
+
+def _waves_and_frames(who: str, waves, lens, hop, frames):
+    """pitch_track's reading of its waveforms: (the items as 1-D tensors, their lengths, their frame counts)."""
     if isinstance(waves, torch.Tensor):
         if waves.dim() != 2 or lens is None or len(lens) != waves.shape[0]:
             raise ValueError(f"{who}: a tensor of waves must be [B, L_max] with one length per row (or pass a list of 1-D waveforms)")
@@ -202,18 +220,193 @@ def pitch_track(waves, lens=None, *, sample_rate: int = 24000, hop: int = 256, f
     frames = [n // int(hop) + 1 for n in ns] if frames is None else [int(f) for f in frames]
     if len(frames) != len(ns):
         raise ValueError(f"{who}: {len(frames)} frame counts for {len(ns)} waveforms")
-    tau_min, tau_max = pitch_lags(int(sample_rate), float(fmin), float(fmax))
-    items, dev, base, starts = ragged_items(waves, None, "pitch_track only runs on a GPU (there is no CPU path)",
+    return waves, ns, frames
+
+
+# ---------------------------------------------------------------------------------------------------- pYIN
+MAX_THRESHOLDS, MAX_BINS, MAX_REACH = 256, 512, 63           # csrc/pitch.hip's kMaxThresholds, kMaxBins, kMaxReach
+
+
+@dataclasses.dataclass(frozen=True)
+class PyinTables:
+    """The host tables of the two pYIN stages (include/f5_hip.h), f64 CPU tensors: w [N] the weight of threshold i / N; edge [M + 1]
+    the bin edges in Hz, ascending; centre [M]; trans [M, 2 * reach + 1], entry [i, k] the weight of going from bin i to bin
+    i + k - reach.  sample_rate, tau_min and tau_max are the search range they were built for."""
+    sample_rate: int
+    tau_min: int
+    tau_max: int
+    w: torch.Tensor
+    edge: torch.Tensor
+    centre: torch.Tensor
+    reach: int
+    trans: torch.Tensor
+
+    @property
+    def n(self) -> int:
+        return int(self.w.numel())
+
+    @property
+    def bins(self) -> int:
+        return int(self.centre.numel())
+
+
+def _f64(values) -> torch.Tensor:
+    return torch.as_tensor(values, dtype=torch.float64).to("cpu").contiguous()
+
+
+def _f64_ptr(t: torch.Tensor):
+    return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_double))
+
+
+def pyin_tables(sample_rate: int = 24000, fmin: float = 60.0, fmax: float = 600.0, *, n_thresholds: int = 100, beta=(2, 18),
+                bins_per_semitone: int = 5, max_semitones_per_frame: int = 5) -> PyinTables:
+    """The tables of pYIN for a search range, built on the host in f64 (the device has no transcendental function to call).
+    w_i = F(i / N) - F((i - 1) / N) for the N = n_thresholds thresholds i / N, F the CDF of the Beta prior over YIN's threshold: for
+    beta = (2, 18), Mauch and Dixon's prior of mean 0.1, the closed form 1 - (1 - s)^19 - 19 s (1 - s)^18; any other (a, b) through
+    scipy.special.betainc.  Bins: M = ceil(12 bins_per_semitone log2(hi / lo)) geometric bins from lo = sample_rate / (tau_max + 1)
+    to hi = sample_rate / (tau_min - 1), the range a refined candidate of the lags pitch_lags(sample_rate, fmin, fmax) can reach:
+    edge[m] = lo (hi / lo)^(m / M), centre[m] = lo (hi / lo)^((m + 0.5) / M).  Transitions: a triangle of half-width reach =
+    bins_per_semitone * max_semitones_per_frame bins (weight reach + 1 - |offset|), each source bin's row divided by its sum over
+    the destinations that exist."""
+    sample_rate, n = int(sample_rate), int(n_thresholds)
+    tau_min, tau_max = pitch_lags(sample_rate, float(fmin), float(fmax))
+    reach = int(bins_per_semitone) * int(max_semitones_per_frame)
+    if not 1 <= n <= MAX_THRESHOLDS:
+        raise ValueError(f"pyin_tables: n_thresholds = {n} (need 1 <= n_thresholds <= {MAX_THRESHOLDS})")
+    if tau_min < 2 or tau_min >= tau_max:
+        raise ValueError(f"pyin_tables: fmin = {fmin}, fmax = {fmax} give the lags {tau_min} .. {tau_max} (need 2 <= tau_min < tau_max)")
+    if not 1 <= reach <= MAX_REACH:
+        raise ValueError(f"pyin_tables: a band of {reach} bins per frame (need 1 <= bins_per_semitone * max_semitones_per_frame <= {MAX_REACH})")
+    a, b = beta
+    if (a, b) == (2, 18):
+        def cdf(s):
+            return 1.0 - (1.0 - s) ** 19 - 19.0 * s * (1.0 - s) ** 18
+    else:
+        try:
+            from scipy.special import betainc       # the package's one optional dependency: only a non-default prior needs it
+        except ImportError as e:
+            raise ImportError(f"pyin_tables: beta = {beta!r} needs scipy (scipy.special.betainc); the default (2, 18) does not") from e
+
+        def cdf(s):
+            return float(betainc(float(a), float(b), s))
+    w = [cdf(i / n) - cdf((i - 1) / n) for i in range(1, n + 1)]
+    lo, hi = sample_rate / (tau_max + 1), sample_rate / (tau_min - 1)
+    M = int(math.ceil(12 * int(bins_per_semitone) * math.log2(hi / lo)))
+    if not 2 <= M <= MAX_BINS:
+        raise ValueError(f"pyin_tables: {M} bins from {lo:.1f} to {hi:.1f} Hz (need 2 <= bins <= {MAX_BINS}: fewer bins_per_semitone)")
+    edge = [lo * (hi / lo) ** (m / M) for m in range(M + 1)]
+    centre = [lo * (hi / lo) ** ((m + 0.5) / M) for m in range(M)]
+    trans = []
+    for i in range(M):
+        row = [float(reach + 1 - abs(k - reach)) if 0 <= i + k - reach < M else 0.0 for k in range(2 * reach + 1)]
+        total = math.fsum(row)
+        trans.append([v / total for v in row])
+    return PyinTables(sample_rate, tau_min, tau_max, _f64(w), _f64(edge), _f64(centre), reach, _f64(trans))
+
+
+def pyin_bytes(frames_total: int, bins: int) -> int:
+    """f5_pitch_decode_bytes: the back-pointers of one f5_pitch_decode, a byte per frame, bin and voicing."""
+    return 2 * int(bins) * int(frames_total)
+
+
+def _tables_for(who: str, tables, sample_rate, fmin, fmax) -> PyinTables:
+    """The tables of a call: built for its range where none are given; given ones must be for its sample rate, and for its lag
+    range where fmin / fmax are given (None: the tables' own range is taken)."""
+    if (fmin is None) != (fmax is None):
+        raise ValueError(f"{who}: give both fmin and fmax, or neither")
+    if tables is None:
+        return pyin_tables(sample_rate, *((60.0, 600.0) if fmin is None else (fmin, fmax)))
+    if tables.sample_rate != int(sample_rate):
+        raise ValueError(f"{who}: the tables were built for {tables.sample_rate} Hz, the waves are at {int(sample_rate)} Hz")
+    if fmin is not None and pitch_lags(int(sample_rate), float(fmin), float(fmax)) != (tables.tau_min, tables.tau_max):
+        raise ValueError(f"{who}: the tables were built for the lags {tables.tau_min} .. {tables.tau_max}, fmin = {fmin} and fmax = {fmax} "
+                         f"give {pitch_lags(int(sample_rate), float(fmin), float(fmax))} (leave fmin and fmax out to take the tables' range)")
+    w = tables.w
+    if w.dim() != 1 or not 1 <= w.numel() <= MAX_THRESHOLDS:
+        raise ValueError(f"{who}: the tables need 1 <= N <= {MAX_THRESHOLDS} weights in w [N]")
+    return tables
+
+
+def pitch_candidates(waves, lens=None, *, sample_rate: int = 24000, hop: int = 256, first_centre: int = 0, frames=None,
+                     window: int = 1024, fmin: float | None = None, fmax: float | None = None, p_absent: float = 0.01,
+                     tables: PyinTables | None = None):
+    """pYIN's stage 1 for a ragged batch in ONE f5_pitch_candidates (csrc/pitch.hip; the contract is in include/f5_hip.h): every
+    threshold i / N of the prior makes YIN's choice on `pitch_track`'s own d', and a frame's candidates are the lags that got votes.
+    waves, lens, sample_rate, hop, first_centre, frames, window: pitch_track's.  fmin / fmax: 60 / 600 Hz where both are left out.  tables:
+    `pyin_tables(sample_rate, fmin, fmax)` by default; given ones must have been built for sample_rate, and either fmin / fmax are
+    left out (the tables bring their lag range) or they name the tables' own lags -- anything else is refused, not ignored.  p_absent: the share of its weight a threshold
+    that no lag is under gives to the frame's deepest dip.  Returns (count int32 [F], lag int32 [F, N], f0 f64 [F, N], prob f64
+    [F, N], frames) on the device, F frames packed item after item: a frame's count candidates in ascending lag, zeros behind them.
+    Nothing is read back and nothing synchronises."""
+    who = "pitch_candidates"
+    waves, ns, frames = _waves_and_frames(who, waves, lens, hop, frames)
+    tab = _tables_for(who, tables, sample_rate, fmin, fmax)
+    items, dev, base, starts = ragged_items(waves, None, f"{who} only runs on a GPU (there is no CPU path)",
                                             f"{who}: the waveforms are on different devices")
-    total = max(sum(max(f, 0) for f in frames), 1)
-    f0 = torch.empty(total, device=dev, dtype=torch.float64)
-    ap = torch.empty(total, device=dev, dtype=torch.float64)
+    total, N = max(sum(max(f, 0) for f in frames), 1), tab.n
+    w = _f64(tab.w)                                 # (host, f64, contiguous, whatever a hand-built PyinTables holds)
+    count = torch.empty(total, device=dev, dtype=torch.int32)
+    lag = torch.empty(total, N, device=dev, dtype=torch.int32)
+    f0 = torch.empty(total, N, device=dev, dtype=torch.float64)
+    prob = torch.empty(total, N, device=dev, dtype=torch.float64)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().f5_pitch_track(C.c_void_p(base), len(ns), starts, _lib.int_array(ns), int(sample_rate), int(hop),
-                                              int(first_centre), _lib.int_array(frames), int(window), tau_min, tau_max,
-                                              float(threshold), _ptr(f0), _ptr(ap), _stream_ptr(dev)), "f5_pitch_track")
+        _lib.check(_lib.load().f5_pitch_candidates(C.c_void_p(base), len(ns), starts, _lib.int_array(ns), tab.sample_rate, int(hop),
+                                                   int(first_centre), _lib.int_array(frames), int(window), tab.tau_min, tab.tau_max, N,
+                                                   _f64_ptr(w), float(p_absent), _ptr(count), _ptr(lag), _ptr(f0), _ptr(prob),
+                                                   _stream_ptr(dev)), "f5_pitch_candidates")
     del items
-    return f0, ap, frames
+    return count, lag, f0, prob, frames
+
+
+def pitch_decode(count, f0, prob, frames, tables: PyinTables, *, p_switch: float = 0.01):
+    """pYIN's stage 2 in ONE f5_pitch_decode: a Viterbi decode per item over pitch bin x voicing, which picks one candidate per frame
+    or "unvoiced"; a move of more than tables.reach bins between two frames is outside the band and is not made.  count int32 [F],
+    f0 and prob f64 [F, N] on the device as pitch_candidates returns them (a frame's candidates in array order), frames the host
+    list of the items' frame counts.  p_switch: the probability of a change of voicing between two frames.  Returns (f0 f64 [F], 0
+    where unvoiced; voiced_prob f64 [F], the frame's summed candidate probability) on the device.  The back-pointers (pyin_bytes)
+    are a tensor of this call.  Nothing is read back and nothing synchronises."""
+    who = "pitch_decode"
+    frames = [int(f) for f in frames]
+    total = sum(max(f, 0) for f in frames)
+    if count.device.type != "cuda" or f0.device != count.device or prob.device != count.device:
+        raise ValueError(f"{who} only runs on a GPU (there is no CPU path): count, f0 and prob must be on one device")
+    if f0.dim() != 2 or prob.shape != f0.shape or count.numel() != f0.shape[0] or f0.shape[0] < max(total, 1):
+        raise ValueError(f"{who}: need count [F], f0 and prob [F, N] with F >= the {total} frames of the items")
+    if count.dtype != torch.int32 or f0.dtype != torch.float64 or prob.dtype != torch.float64:
+        raise ValueError(f"{who}: count must be int32, f0 and prob float64")
+    dev, N, M = count.device, int(f0.shape[1]), tables.bins
+    count, f0, prob = count.contiguous(), f0.contiguous(), prob.contiguous()
+    if tables.edge.numel() != M + 1 or tuple(tables.trans.shape) != (M, 2 * tables.reach + 1):
+        raise ValueError(f"{who}: the tables need edge [M + 1] and trans [M, 2 * reach + 1] for their {M} bins")
+    need = pyin_bytes(max(total, 1), M)
+    work = torch.empty(need, device=dev, dtype=torch.uint8)
+    out = torch.empty(max(total, 1), device=dev, dtype=torch.float64)
+    voiced = torch.empty(max(total, 1), device=dev, dtype=torch.float64)
+    edge, centre, trans = _f64(tables.edge), _f64(tables.centre), _f64(tables.trans)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_pitch_decode(_ptr(count), _ptr(f0), _ptr(prob), N, len(frames), _lib.int_array(frames), M,
+                                               _f64_ptr(edge), _f64_ptr(centre), int(tables.reach), _f64_ptr(trans), float(p_switch),
+                                               _ptr(work), need, _ptr(out), _ptr(voiced), _stream_ptr(dev)), "f5_pitch_decode")
+    return out, voiced
+
+
+def pitch_track_pyin(waves, lens=None, *, sample_rate: int = 24000, hop: int = 256, first_centre: int = 0, frames=None,
+                     window: int = 1024, fmin: float | None = None, fmax: float | None = None, p_switch: float = 0.01,
+                     p_absent: float = 0.01, tables: PyinTables | None = None):
+    """Smoothed pitch tracks of a ragged batch: pYIN (Mauch and Dixon 2014) in two launches, `pitch_candidates` then `pitch_decode`,
+    with pitch_track's arguments (without the threshold; fmin / fmax and tables as pitch_candidates reads them), packing and rules: returns (f0, voiced_prob, frames), f64 device tensors
+    packed item after item -- f0 in Hz, 0 where the decoded state is unvoiced; voiced_prob the summed probability of the frame's
+    candidates -- and the host list of frame counts.  Nothing is read back and nothing synchronises.  An item's track is the same
+    alone, in any batch and in any order.  Where YIN reports the octave below for a few frames, the decode keeps the track inside
+    the band of `max_semitones_per_frame` per frame.  What it is not: WORLD's F0 (DIO / Harvest), or librosa's pyin (no Boltzmann
+    prior over troughs, linear probabilities); digital silence, whose d' is flat, puts its p_absent vote on the smallest lag every
+    frame, and such a stretch decodes as voiced at sample_rate / tau_min unless p_absent = 0."""
+    who = "pitch_track_pyin"
+    tab = _tables_for(who, tables, sample_rate, fmin, fmax)
+    count, _, f0, prob, frames = pitch_candidates(waves, lens, sample_rate=sample_rate, hop=hop, first_centre=first_centre, frames=frames,
+                                                  window=window, fmin=fmin, fmax=fmax, p_absent=p_absent, tables=tab)
+    out, voiced = pitch_decode(count, f0, prob, frames, tab, p_switch=p_switch)
+    return out, voiced, frames
 
 
 def prosody(a_f0, b_f0, path, path_start, path_len):
