@@ -900,6 +900,82 @@ int f5_pitch_decode(const int32_t* cand_count, const double* cand_f0, const doub
                     const double* trans_host, double p_switch, void* workspace /* device */, int64_t workspace_bytes,
                     double* f0 /* device */, double* voiced_prob /* device */, f5_stream stream);
 
+/* ----------------------------------------------------------------- speaker similarity: Gaussian cepstral divergence
+ * A text-independent measure of whether two sets of mel frames come from one voice, with no model: one full-covariance Gaussian per
+ * side over cepstral vectors, and a second-order divergence between the two (Bimbot, Magrin-Chagnolleau and Mathan 1995).  Two calls:
+ * f5_cep_moments gives count, mean and centred scatter of every segment of a ragged set -- additive statistics, which the caller
+ * pools over items into speakers --, f5_gauss_divergence the four raw terms of the divergence for pairs of such records.  Everything
+ * is f64 and uncontracted; the device adds, subtracts, multiplies, divides, takes square roots and compares, in the order below.
+ *
+ * f5_cep_moments.  Segment s is frames_host[s] rows of n_mels f32, row_stride elements apart, the first at base[start_host[s]], read
+ * where it lies (f5_mel_distance's addressing of a side); F = frames_host[s], frames t = 0 .. F - 1.
+ *   cepstra       c_k(t) for k = 1 .. n_cep is f5_mel_distance's: sum_j (double)x_j * T[k][j], j ascending, multiply then add, with
+ *                 T[k][j] = sqrt(2.0 / n_mels) * cos(pi * k * (j + 0.5) / n_mels) evaluated on the host in double in exactly that
+ *                 order of operations (pi * k, times (j + 0.5), divided by n_mels; the cosine is the host C library's).
+ *   deltas        with deltas = 1, dc_k(t) = ((c_k(t+1) - c_k(t-1)) + 2.0 * (c_k(t+2) - c_k(t-2))) / 10.0, every frame index clamped
+ *                 to [0, F - 1].  Deltas are taken over the segment's own frames, whatever the selection below.  The feature vector
+ *                 of a frame is v = [c_1 .. c_n_cep] or [c_1 .. c_n_cep, dc_1 .. dc_n_cep]: C = n_cep * (1 + deltas) entries.
+ *   energy        e(t) = sum_j (double)x_j, j ascending, from 0.
+ *   selection     frame t counts iff (mask == NULL or mask[r] != 0) and (gate_sum < 0 or e(t) >= emax - gate_sum), where r is the
+ *                 frame's index among the frames of the call (segment after segment) and emax the largest e of the segment (a
+ *                 maximum of doubles has no order).  If any e(t) of a segment is not finite, that segment alone reports
+ *                 count = -1 and NaN in every entry of mean and scatter.
+ *   chunks        the frames of a segment are cut into chunks of kMomChunk = 64 consecutive frames (the last one shorter).
+ *   pass 1        a chunk's partial of entry p is the sum of v_p over the chunk's selected frames, t ascending, from 0; the
+ *                 segment's sum is the sum of the chunk partials, chunk ascending, from 0.  n = the selected frames;
+ *                 mean_p = sum_p / (double)n.
+ *   pass 2        for p <= q, a chunk's partial is the sum of (v_p - mean_p) * (v_q - mean_q) over the chunk's selected frames, t
+ *                 ascending, from 0 (subtract, subtract, multiply, then add); scatter_pq is the sum of the chunk partials, chunk
+ *                 ascending, from 0.  Centred sums, never raw second moments.
+ *   empty         n = 0: count = 0, every entry of mean and scatter is +0.
+ * Outputs on the device: count i32 [S]; mean f64 [S][C]; scatter f64 [S][C (C + 1) / 2], the upper triangle packed row-major
+ * ((0,0), (0,1) .. (0,C-1), (1,1) ..).  A segment's record depends on its own frames (and mask entries) alone: it is the same alone
+ * and in any batch.
+ * Six launches: the cepstra and energies (one thread per (row, k), the table through LDS), the selection (a workgroup per segment),
+ * and twice a chunk launch (a workgroup per (segment, chunk) with the chunk's feature vectors in LDS; ONE thread sums an entry over
+ * the chunk's frames) followed by a fold (one thread per entry, chunk ascending).  Stand-alone like f5_mel_distance: no handle, the
+ * per-device workspace, one table copy through a pinned slot, no host read, no synchronisation except the growth of the workspace,
+ * no atomics.  f5_cep_moments_plan is pure host arithmetic (no HIP call): *workspace_bytes_out is what the call holds of the
+ * workspace -- (n_cep + 1) doubles and one byte per frame, C + C (C + 1) / 2 doubles and one int per chunk, and the tables (the DCT
+ * table sized for 256 mel bins).
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the segment: a null pointer (mask may be null),
+ * S < 1 or S > 65535, frames outside [1, 4096], n_mels outside [2, 256], n_cep outside [1, min(32, n_mels - 1)], deltas not 0 or 1,
+ * a row stride below n_mels, a start below 0, a gate_sum that is NaN, more than 2^28 cepstral or partial values in one call.
+ *
+ * f5_gauss_divergence.  Records as f5_cep_moments writes them, two sets: a (a_records of them) and b (b_records; the same arrays
+ * may be passed for both).  Pair p is record i = i_host[p] of a against record j = j_host[p] of b.  With A = scatter / (double)n
+ * entry by entry (the covariance of a record with count n):
+ *   factor        the Cholesky factor L (lower) of A, column c = 0 .. C - 1 in turn: for r >= c, s = A_rc, then s = s - L_rk * L_ck
+ *                 for k = 0 .. c - 1 ascending; L_cc = sqrt(s) and, for r > c, L_rc = s / L_cc: one square root or one division per
+ *                 element.  The s of a diagonal element is the column's pivot.
+ *   X, Y          X = L_i^-1 L_j by forward substitution, column c in turn down its rows r = c .. C - 1: s = (L_j)_rc, then
+ *                 s = s - (L_i)_rk * X_kc for k = c .. r - 1 ascending, X_rc = s / (L_i)_rr (X is lower triangular; nothing above
+ *                 the diagonal enters a sum).  Y = L_j^-1 L_i likewise.
+ *   traces        the column sum of X_rc * X_rc over r = c .. C - 1 ascending, from 0; tr_ij = the column sums added c ascending,
+ *                 from 0.  That is trace(A_i^-1 A_j).  tr_ji likewise from Y.
+ *   means         d = mean_i - mean_j; z = L_i^-1 d by the same substitution (s = d_r, k = 0 .. r - 1); q_i = the sum of z_r * z_r, r
+ *                 ascending, from 0.  q_j likewise with L_j (and the same d).
+ * terms: f64 [P][4] on the device, (tr_ij, tr_ji, q_i, q_j); status i32 [P].  A pair is singular iff either record has count <= C
+ * or a pivot of either factor is <= 0 or not finite: it gets four NaNs and status 1 (otherwise status 0).  That is never an error
+ * and touches no other pair.  A record against itself gives exactly (C, C, 0, 0); (i, j) and (j, i) give the same bits, swapped.
+ * What callers make of the terms (metrics.speaker_numbers): the symmetric Kullback-Leibler divergence in nats, 0.5 ((tr_ij + tr_ji)
+ * - 2 C) + 0.5 (q_i + q_j) -- the log-determinants cancel --, and the arithmetic-harmonic sphericity log(tr_ij tr_ji / C^2).  Neither
+ * is SIM, an embedding cosine, or comparable with any published figure.
+ * One launch: a workgroup of 64 threads per pair, both factors and X (then Y) packed in LDS, thread r owning row r of both factors
+ * and column r of X and Y.  The index tables go down in one copy through a pinned slot; otherwise as f5_cep_moments.
+ * F5_EINVAL, with nothing launched or staged and a message naming the argument or the pair: a null pointer, C outside [1, 64], P < 1
+ * or P > 65535, a_records or b_records < 1, an index outside its records. */
+#define F5_MOM_CHUNK 64 /* kMomChunk: frames of a chunk of f5_cep_moments */
+int f5_cep_moments_plan(int32_t S, const int32_t* frames_host, int32_t n_cep, int32_t deltas, int64_t* workspace_bytes_out);
+int f5_cep_moments(const float* base, int32_t S, const int64_t* start_host, const int32_t* frames_host, int64_t row_stride,
+                   int32_t n_mels, int32_t n_cep, int32_t deltas, const uint8_t* mask /* device, one per frame, or NULL */,
+                   double gate_sum, int32_t* count /* [S], device */, double* mean /* [S][C], device */,
+                   double* scatter /* [S][C (C + 1) / 2], device */, f5_stream stream);
+int f5_gauss_divergence(const int32_t* a_count, const double* a_mean, const double* a_scatter, int32_t a_records,
+                        const int32_t* b_count, const double* b_mean, const double* b_scatter, int32_t b_records, int32_t C,
+                        int32_t P, const int32_t* i_host, const int32_t* j_host, double* terms /* [P][4], device */,
+                        int32_t* status /* [P], device */, f5_stream stream);
+
 /* ----------------------------------------------------------------------------- kernel-level entry points
  * Used by tests/ (parity of each kernel against a torch fp32 restatement) and by the micro-benchmarks.  fp32 in/out;
  * the operands are converted to the requested MFMA precision internally.  They allocate scratch and synchronise. */

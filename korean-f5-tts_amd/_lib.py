@@ -141,6 +141,9 @@ SIGNATURES = {
     "f5_pitch_decode_bytes": (C.c_int64, [C.c_int64, _i]),
     "f5_pitch_decode": (_i, [_p, _p, _p, _i, _i, C.POINTER(_i), _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i,
                              C.POINTER(C.c_double), C.c_double, _p, C.c_int64, _p, _p, _p]),
+    "f5_cep_moments_plan": (_i, [_i, C.POINTER(_i), _i, _i, C.POINTER(C.c_int64)]),
+    "f5_cep_moments": (_i, [_p, _i, C.POINTER(C.c_int64), C.POINTER(_i), C.c_int64, _i, _i, _i, _p, C.c_double, _p, _p, _p, _p]),
+    "f5_gauss_divergence": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _p, _p, _p]),
     "f5_bigvgan_create": (_i, [C.POINTER(f5_bigvgan_config), C.POINTER(_p)]),
     "f5_bigvgan_destroy": (_i, [_p]),
     "f5_bigvgan_load_weight": (_i, [_p, C.c_char_p, _p, C.POINTER(C.c_int64), _i, _p]),

@@ -1281,6 +1281,137 @@ def heldout_prosody(model, vocoder, items, *, adapters=(None,), duration="truth"
     return result
 
 
+def heldout_speaker(model, items, *, adapters=(None,), speakers=None, against=("prompt", "target"), deltas=False, gate_db=None,
+                    duration="truth", nfe_step=nfe_step, cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, seed=0,
+                    speed=1.0, n_cep=13, batch_frames=38400):
+    """Whether what every adapter in `adapters` GENERATES keeps the voice of its prompt, on ONE resident engine, with no model: the
+    Gaussian cepstral divergence (metrics.cepstral_moments / gaussian_divergence; include/f5_hip.h) between the generated frames and
+    the prompt's, and the recording's -- text-independent, where heldout_distance and heldout_prosody compare the same sentence
+    along an alignment.  It stands where the reference's evaluation has SIM (WavLM-ECAPA, eval/utils_eval.py::run_sim), which is
+    not built; it is NOT SIM, not an embedding cosine and not comparable with any published figure.  It is comparable between
+    checkpoints and settings on the same items and speakers.
+    items, adapters, duration / speed / batch_frames and the sampler keywords: heldout_distance's, as are the plan, the batches, the
+    text handling and the choice of `sample` / `sample_items`.  speakers: one label per item (None: every item is its own speaker).
+    against: which of "prompt" and "target" to compare with.  deltas, gate_db, n_cep: cepstral_moments'; gate_db = None keeps every
+    frame, and no threshold is recommended.  Per batch ONE cepstral_moments takes the prompts and targets together, once; every
+    adapter runs `set_adapter`, ONE sample(), ONE cepstral_moments of the generated frames [p_b, dur_b), read in place, and ONE
+    gaussian_divergence.  After the walk the records are pooled per speaker (metrics.merge_moments: the moments are additive, so a
+    speaker's Gaussian rests on all its frames) and the pooled divergences are ONE more call per adapter.  No vocoder is involved.
+    The adapter that was active before the call is active again after it, on an exception too.  The only readback is one copy at
+    the end.
+    Returns {adapter: {"to_prompt": {"kl", "sphericity"}, "to_target": {...}, "per_speaker": {label: {"to_prompt": {...},
+    "to_target": {...}}}, "per_item": [U dicts of the same two], "singular": count}} (only the sides named in `against`).  kl: the
+    symmetric Kullback-Leibler divergence of the two Gaussians in nats; sphericity: the arithmetic-harmonic sphericity measure,
+    which a constant channel offset does not move (metrics.speaker_numbers).  The headline numbers are the means over speakers of
+    the pooled values.  An item or speaker with too few frames for its dimension, or a covariance that is not positive definite, is
+    NaN, is left out of the means and is counted in "singular" (items)."""
+    from .metrics import cepstral_moments, gaussian_divergence, merge_moments, speaker_numbers, Moments
+    who = "heldout_speaker"
+    against = tuple(against)
+    if not against or any(s not in ("prompt", "target") for s in against) or len(set(against)) != len(against):
+        raise ValueError(f"{who}: against = {against!r} (expected 'prompt', 'target' or both)")
+    tr = model.transformer
+    adapters = list(adapters)
+    per_adapter = items if isinstance(items, dict) else {a: items for a in adapters}
+    U = len(per_adapter[adapters[0]]) if adapters and adapters[0] in per_adapter else 0
+    for a in adapters:
+        if a not in per_adapter or len(per_adapter[a]) != U or U == 0:
+            raise ValueError(f"{who}: adapter {a!r} needs the same items as the others, at least one")
+    speakers = list(range(U)) if speakers is None else list(speakers)
+    if len(speakers) != U:
+        raise ValueError(f"{who}: {len(speakers)} speaker labels for {U} items")
+    plans = {a: heldout_distance_plan(per_adapter[a], duration=duration, speed=speed, batch_frames=batch_frames) for a in adapters}
+    first = per_adapter[adapters[0]]
+    lens, groups = plans[adapters[0]][1], plans[adapters[0]][3]
+    targets = [it[2] for it in first]
+    toks = {}
+    for a in adapters:
+        texts = plans[a][0]
+        toks[a] = [(list_str_to_idx([t], model.vocab_char_map) if model.vocab_char_map is not None else list_str_to_tensor([t]))[0]
+                   if isinstance(t, str) else torch.as_tensor(t, dtype=torch.long) for t in texts]
+        if plans[a][1] != lens:
+            raise ValueError(f"{who}: adapter {a!r}'s prompt mels differ in length from the first adapter's")
+    pad = torch.nn.utils.rnn.pad_sequence
+    sample = model.sample_items if getattr(tr, "isolated_rows", False) else model.sample
+    mom_kw = dict(n_cep=n_cep, deltas=deltas, gate_db=gate_db)
+    refs = []                                       # per batch: Moments of [prompts of the run | targets of the run]
+    gens = {a: [] for a in adapters}                # per batch: Moments of the generated frames
+    terms = {a: [] for a in adapters}               # per batch: ([B * sides, 4], [B * sides])
+    before = tr.active_adapter
+    try:
+        for run in groups:
+            B = len(run)
+            cond = pad([first[u][0].to("cpu", torch.float32) for u in run], batch_first=True).to(model.device)
+            glens = torch.tensor([lens[u] for u in run])
+            both = ragged_items([first[u][0].to(torch.float32) for u in run] + [targets[u].to(torch.float32) for u in run], model.device,
+                                f"{who} only runs on a GPU (there is no CPU path)",
+                                f"{who}: the prompt and target mels are on different devices")[0]   # once per batch
+            ref = cepstral_moments([t.view(-1, model.num_channels) for t in both], **mom_kw)
+            refs.append(ref)
+            pairs = [(b, b + B * (side == "target")) for side in against for b in range(B)]
+            for a in adapters:
+                tr.set_adapter(a)
+                text = pad([toks[a][u] for u in run], padding_value=-1, batch_first=True)
+                total = torch.tensor([plans[a][2][u] for u in run])
+                end = clamp_durations(text, glens, total).tolist()
+                out, _ = sample(cond, text, total, lens=glens, steps=nfe_step, cfg_strength=cfg_strength,
+                                sway_sampling_coef=sway_sampling_coef, seed=seed)
+                gen = cepstral_moments([(out, b, lens[u], end[b] - lens[u]) for b, u in enumerate(run)], **mom_kw)
+                gens[a].append(gen)
+                terms[a].append(gaussian_divergence(gen, ref, pairs))
+    finally:
+        tr.set_adapter(before)
+    order = [u for run in groups for u in run]
+    sizes = [len(run) for run in groups]
+
+    def cat(records, part=None):
+        """The records of every batch in one Moments, in `order`; part 0 / 1: the prompt / target half of each batch's references."""
+        pick = (lambda t, B: t) if part is None else (lambda t, B: t[part * B:(part + 1) * B])   # noqa: E731
+        return Moments(*[torch.cat([pick(getattr(m, f), B) for m, B in zip(records, sizes)]) for f in ("count", "mean", "scatter")],
+                       records[0].n_cep, records[0].deltas)
+    labels_in_order = [speakers[u] for u in order]
+    pooled_ref = {side: merge_moments(cat(refs, part=int(side == "target")), labels_in_order) for side in against}
+    labels = pooled_ref[against[0]][1]
+    L, dim = len(labels), refs[0].dim
+    flat = []
+    for a in adapters:
+        pooled_gen, _ = merge_moments(cat(gens[a]), labels_in_order)
+        for side in against:
+            t, s = gaussian_divergence(pooled_gen, pooled_ref[side][0])
+            flat.append(torch.cat([t, s.to(torch.float64).unsqueeze(1)], dim=1))
+        flat += [torch.cat([t, s.to(torch.float64).unsqueeze(1)], dim=1) for t, s in terms[a]]
+    host = torch.cat(flat).cpu().tolist()           # the one readback
+    names = {"prompt": "to_prompt", "target": "to_target"}
+    result, at = {}, 0
+    for a in adapters:
+        res = dict(per_speaker={g: {} for g in labels}, per_item=[{} for _ in range(U)], singular=0)
+        for side in against:
+            rows = host[at:at + L]
+            at += L
+            nums = speaker_numbers([r[:4] for r in rows], dim)
+            for k, g in enumerate(labels):
+                res["per_speaker"][g][names[side]] = dict(kl=nums["kl"][k], sphericity=nums["sphericity"][k])
+            good = [k for k in range(L) if rows[k][4] == 0]
+            res[names[side]] = {key: (math.fsum(nums[key][k] for k in good) / len(good) if good else float("nan"))
+                                for key in ("kl", "sphericity")}
+        singular = set()
+        done = 0
+        for B in sizes:
+            run = order[done:done + B]
+            done += B
+            for side in against:
+                rows = host[at:at + B]
+                at += B
+                nums = speaker_numbers([r[:4] for r in rows], dim)
+                for b, u in enumerate(run):
+                    res["per_item"][u][names[side]] = dict(kl=nums["kl"][b], sphericity=nums["sphericity"][b])
+                    if rows[b][4] != 0:
+                        singular.add(u)
+        res["singular"] = len(singular)
+        result[a] = res
+    return result
+
+
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print, progress=None,
                   target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, cfg_strength=cfg_strength,
                   sway_sampling_coef=sway_sampling_coef, speed=speed, fix_duration=fix_duration, device=None, seed=None,

@@ -64,7 +64,7 @@ def _rows(entry, who: str) -> torch.Tensor:
     return t
 
 
-def _side(entries, who: str):
+def _side(entries, who: str, no_gpu: str = _NO_GPU):
     """One side's items as (keep-alive tensors, device, base pointer, ctypes element offsets, row stride).  Items that lie on the
     device as f32 with unit element stride and one common row stride are passed by offset from the lowest address, where they are;
     anything else is packed once by `ragged_items`' rule (host tensors down in one copy, contiguous f32)."""
@@ -76,7 +76,7 @@ def _side(entries, who: str):
         if stride >= rows[0].shape[1]:
             base = min(t.data_ptr() for t in rows)
             return rows, rows[0].device, base, (C.c_int64 * len(rows))(*[(t.data_ptr() - base) // 4 for t in rows]), stride
-    items, dev, base, starts = ragged_items(rows, None, _NO_GPU, f"{who}: the items are on different devices")
+    items, dev, base, starts = ragged_items(rows, None, no_gpu, f"{who}: the items are on different devices")
     return items, dev, base, starts, int(rows[0].shape[1])
 
 
@@ -458,3 +458,187 @@ def prosody(a_f0, b_f0, path, path_start, path_len):
     for name in PROSODY_SUMS:
         out[name] = total(terms[name], torch.float64)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- speaker similarity
+MOM_CHUNK, MOM_MAX_CEP, MOM_MAX_DIM = 64, 32, 64    # csrc/speaker.hip's kMomChunk, kMaxCep, kMaxDim
+
+
+@dataclasses.dataclass(frozen=True)
+class Moments:
+    """Gaussian statistics of S sets of cepstral vectors, on the device (f5_cep_moments; include/f5_hip.h): count int32 [S] (-1: a
+    segment with a non-finite frame), mean f64 [S, C], scatter f64 [S, C (C + 1) / 2] -- the centred sums sum (v_p - mean_p)
+    (v_q - mean_q), upper triangle packed row-major --, with C = n_cep * (1 + deltas)."""
+    count: torch.Tensor
+    mean: torch.Tensor
+    scatter: torch.Tensor
+    n_cep: int
+    deltas: bool
+
+    @property
+    def dim(self) -> int:
+        return int(self.n_cep) * (2 if self.deltas else 1)
+
+    def __len__(self) -> int:
+        return int(self.count.shape[0])
+
+
+def gate_sum_of(gate_db, n_mels: int) -> float:
+    """f5_cep_moments' gate_sum for a gate of `gate_db` dB of mean log-mel amplitude below the segment's loudest frame, in double
+    on the host: gate_db * ln 10 / 20 * n_mels.  None: -1.0 (no gate)."""
+    if gate_db is None:
+        return -1.0
+    gate_db = float(gate_db)
+    if not gate_db >= 0.0:
+        raise ValueError(f"cepstral_moments: gate_db = {gate_db} (need gate_db >= 0, or None for no gate)")
+    return gate_db * math.log(10.0) / 20.0 * int(n_mels)
+
+
+def cepstral_moments_plan(frames, *, n_cep: int = 13, deltas: bool = False) -> int:
+    """f5_cep_moments_plan (pure host arithmetic): the bytes of the per-device workspace a call over segments of these frame counts
+    holds."""
+    frames = [int(f) for f in frames]
+    need = C.c_int64()
+    _lib.check(_lib.load().f5_cep_moments_plan(len(frames), _lib.int_array(frames), int(n_cep), int(bool(deltas)), C.byref(need)),
+               "f5_cep_moments_plan")
+    return need.value
+
+
+def cepstral_moments(entries, *, n_cep: int = 13, deltas: bool = False, select=None, gate_db=None) -> Moments:
+    """Count, mean and centred scatter of the cepstral vectors of S sets of mel frames in ONE f5_cep_moments (include/f5_hip.h):
+    entries as mel_distance takes a side -- f32 [frames, mel] tensors or view descriptors (tensor [B, N, mel], item, start, frames),
+    read where they lie.  The vectors are mel_distance's cepstra 1 .. n_cep (n_cep <= 32) and, with deltas, their regression deltas
+    over +-2 frames of the segment.  select: an optional bool / uint8 tensor with one entry per frame of the call, entry after entry
+    (a caller with pitch tracks can pass f0 > 0); gate_db: keep the frames whose mean log-mel amplitude is within gate_db dB of
+    the entry's loudest frame (None, the default: every frame -- there is no recommended threshold).  Returns Moments on the
+    device; nothing is read back, and with device entries and a device mask (or none) nothing synchronises -- a host mask, like
+    host entries, goes down in one pageable copy, which does.  An entry's record does not depend on the batch it is in."""
+    who = "cepstral_moments"
+    entries = list(entries)
+    if not entries:
+        raise ValueError(f"{who}: need at least one entry")
+    if not 1 <= int(n_cep) <= MOM_MAX_CEP:          # (before anything is allocated from it)
+        raise ValueError(f"{who}: n_cep = {n_cep} (need 1 <= n_cep <= min({MOM_MAX_CEP}, mel - 1))")
+    rows = [_rows(e, who) for e in entries]
+    keep, dev, base, starts, stride = _side(rows, who, f"{who} only runs on a GPU (there is no CPU path)")
+    mels = {int(t.shape[1]) for t in rows}
+    if len(mels) != 1:
+        raise ValueError(f"{who}: every entry needs the same number of mel bins (got {sorted(mels)})")
+    n_mels = mels.pop()
+    frames = [int(t.shape[0]) for t in rows]
+    S, dim = len(frames), int(n_cep) * (2 if deltas else 1)
+    mask = None
+    if select is not None:
+        mask = torch.as_tensor(select).reshape(-1)
+        if mask.numel() != sum(frames):
+            raise ValueError(f"{who}: select has {mask.numel()} entries for the {sum(frames)} frames of the call")
+        mask = (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    count = torch.empty(S, device=dev, dtype=torch.int32)
+    mean = torch.empty(S, dim, device=dev, dtype=torch.float64)
+    scatter = torch.empty(S, dim * (dim + 1) // 2, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_cep_moments(C.c_void_p(base), S, starts, _lib.int_array(frames), stride, n_mels, int(n_cep),
+                                              int(bool(deltas)), _ptr(mask), gate_sum_of(gate_db, n_mels), _ptr(count), _ptr(mean),
+                                              _ptr(scatter), _stream_ptr(dev)), "f5_cep_moments")
+    del keep
+    return Moments(count, mean, scatter, int(n_cep), bool(deltas))
+
+
+def _triu(dim: int, device):
+    idx = torch.triu_indices(dim, dim, device=device)          # row-major over the upper triangle: the records' packing
+    return idx[0], idx[1]
+
+
+def merge_moments(moments: Moments, groups):
+    """Pools records by label: groups[s] is record s's label (any hashable).  Returns (Moments with one record per label, the labels
+    in order of first appearance).  A label's records are folded in item order with the pairwise update n = n_a + n_b, d = mean_b -
+    mean_a, mean = mean_a + d n_b / n, scatter = scatter_a + scatter_b + d d^T n_a n_b / n, in torch f64 ops on the device, without
+    a readback: what the moments of the concatenated frames would be, up to rounding.  A record with count 0 adds nothing; one with
+    count -1 makes its label's record count -1 and NaN.  The index table goes down in one (pageable, hence synchronous) copy; the
+    fold is then a dozen small torch launches per round, all labels at once, and the number of rounds is the largest number of
+    records under one label: it runs once per evaluation, not per batch, and is the part to restructure if one label ever holds
+    thousands of records."""
+    groups = list(groups)
+    S, dim = len(moments), moments.dim
+    if len(groups) != S:
+        raise ValueError(f"merge_moments: {len(groups)} labels for {S} records")
+    labels, members = [], {}
+    for s, g in enumerate(groups):
+        if g not in members:
+            members[g] = []
+            labels.append(g)
+        members[g].append(s)
+    dev = moments.count.device
+    U = len(labels)
+    rounds = max(len(m) for m in members.values())
+    # round r takes every label's r-th record, all labels at once; the whole index table goes down in ONE copy (-1: no such record)
+    table = torch.tensor([[members[g][r] if r < len(members[g]) else -1 for g in labels] for r in range(rounds)]).to(dev)
+    p, q = _triu(dim, dev)
+    n = torch.zeros(U, device=dev, dtype=torch.float64)
+    bad = torch.zeros(U, device=dev, dtype=torch.bool)
+    mean = torch.zeros(U, dim, device=dev, dtype=torch.float64)
+    scatter = torch.zeros(U, dim * (dim + 1) // 2, device=dev, dtype=torch.float64)
+    zero = torch.zeros((), device=dev, dtype=torch.float64)
+    for r in range(rounds):
+        src = table[r].clamp(min=0)
+        cb = torch.where(table[r] >= 0, moments.count[src], torch.zeros_like(moments.count[src]))
+        bad |= cb < 0
+        live = (cb > 0).unsqueeze(1)
+        nb = cb.clamp(min=0).to(torch.float64)
+        tot = n + nb
+        safe = torch.where(tot > 0, tot, torch.ones_like(tot))
+        d = torch.where(live, moments.mean[src] - mean, zero)          # (no record, an empty or a bad one: d = 0 and no scatter)
+        scatter = scatter + torch.where(live, moments.scatter[src], zero) + d[:, p] * d[:, q] * (n * nb / safe).unsqueeze(1)
+        mean = mean + d * (nb / safe).unsqueeze(1)
+        n = tot
+    nan = torch.full((), float("nan"), device=dev, dtype=torch.float64)
+    count = torch.where(bad, torch.full_like(n, -1.0), n).to(torch.int32)
+    mean = torch.where(bad.unsqueeze(1), nan, mean)
+    scatter = torch.where(bad.unsqueeze(1), nan, scatter)
+    return Moments(count, mean, scatter, moments.n_cep, moments.deltas), labels
+
+
+def gaussian_divergence(a: Moments, b: Moments, pairs=None):
+    """The raw terms of the second-order divergence between record i of a and record j of b for every (i, j) in `pairs` (None:
+    record s of a against record s of b) in ONE f5_gauss_divergence (include/f5_hip.h).  Returns (terms f64 [P, 4] = (tr_ij, tr_ji,
+    q_i, q_j), status int32 [P]) on the device: tr_ij = trace(cov_i^-1 cov_j), q_i = (mean_i - mean_j)^T cov_i^-1 (mean_i - mean_j).
+    A pair with a side of count <= C, or whose covariance is not positive definite in f64, gets NaNs and status 1.  Nothing is read
+    back and nothing synchronises; `speaker_numbers` turns the terms into numbers after the readback."""
+    who = "gaussian_divergence"
+    if a.dim != b.dim:
+        raise ValueError(f"{who}: a has {a.dim}-dimensional records, b {b.dim}")
+    if a.count.device.type != "cuda" or b.count.device != a.count.device:
+        raise RuntimeError(f"{who} only runs on a GPU (there is no CPU path): both sets of records must be on one device")
+    if pairs is None:
+        if len(a) != len(b):
+            raise ValueError(f"{who}: {len(a)} records of a for {len(b)} of b (give pairs)")
+        pairs = [(s, s) for s in range(len(a))]
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    if not pairs:
+        raise ValueError(f"{who}: need at least one pair")
+    dev, P = a.count.device, len(pairs)
+    sides = [(m.count.contiguous(), m.mean.contiguous(), m.scatter.contiguous()) for m in (a, b)]
+    terms = torch.empty(P, 4, device=dev, dtype=torch.float64)
+    status = torch.empty(P, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().f5_gauss_divergence(*[_ptr(t) for t in sides[0]], len(a), *[_ptr(t) for t in sides[1]], len(b), a.dim, P,
+                                                   _lib.int_array([i for i, _ in pairs]), _lib.int_array([j for _, j in pairs]),
+                                                   _ptr(terms), _ptr(status), _stream_ptr(dev)), "f5_gauss_divergence")
+    del sides
+    return terms, status
+
+
+def speaker_numbers(terms, C: int) -> dict:
+    """The two numbers of a pair from gaussian_divergence's terms (host arithmetic after the readback): terms a sequence of four
+    values (tr_ij, tr_ji, q_i, q_j), or of P such rows -- then lists come back.  "kl": the symmetric Kullback-Leibler divergence
+    between the two Gaussians in nats, 0.5 ((tr_ij + tr_ji) - 2 C) + 0.5 (q_i + q_j) (the log-determinants cancel).  "sphericity":
+    log(tr_ij tr_ji / C^2), the arithmetic-harmonic sphericity measure -- covariances alone, so a constant offset of the cepstral
+    mean (a channel) does not move it.  NaN terms (a singular pair) give NaN.  Neither is SIM or an embedding cosine."""
+    rows = terms.tolist() if hasattr(terms, "tolist") else list(terms)
+    single = not rows or not isinstance(rows[0], (list, tuple))
+    kl, sph = [], []
+    for tr_ij, tr_ji, q_i, q_j in ([rows] if single else rows):
+        kl.append(0.5 * ((tr_ij + tr_ji) - 2 * C) + 0.5 * (q_i + q_j))
+        ratio = tr_ij * tr_ji / (C * C)
+        sph.append(math.log(ratio) if ratio > 0 else float("nan"))
+    return dict(kl=kl[0], sphericity=sph[0]) if single else dict(kl=kl, sphericity=sph)
